@@ -5,7 +5,11 @@ CIFAR10-shaped 15-layer Ladder VAE (BASELINE configs[2]: fp32, batch 256 per GPU
 default init under torch.manual_seed(42). Inputs are resident in HBM before the timed region. Weak scaling: every
 rank processes its own 256-image shard; `value` = images of all ranks / max-over-ranks time.
 
-Extra objects in the JSON line:
+A plain run (`--gpus 1 --steps N --warmup W`) sets up, warms up, times the N steps and prints the headline line. The other
+measurements below take runs of their own and are made only with --full (each can still be left out there with its --no-* option).
+--dump-outputs DIR writes what the last timed step computed as DIR/<name>.npy (float32; see dump_outputs).
+
+Extra objects in the JSON line (--full only):
   roofline     — the dominant kernel (the convolution shape with the largest total time in an instrumented eager step, timed
                  with HIP events on the launch stream; not part of `value`): `frac` = matrix FLOPs the kernel ISSUES per launch (Winograd
                  F(2x2,3x3): 16/36 of the direct multiplies, each as six bf16-piece products) / average launch time / the dense peak of
@@ -281,6 +285,29 @@ def time_steps(step, ring, n, world, dev):
     return dt, out
 
 
+DUMP_SAMPLE = 1 << 22   # elements kept of the flat parameter and gradient vectors: 2 x 16 MB (the whole vectors are 2 x 55 MB)
+
+
+def dump_outputs(folder, out, model):
+    """What the last timed step computed, as float32 DIR/<name>.npy: the step's outputs (the dict TrainStep returns), the parameters after
+    its Adamax update and the gradients it applied (the same fixed, seeded sample of DUMP_SAMPLE elements of each, taken from the flat
+    vectors in named_parameters() order and logical layout, so that the arena's packing does not matter), and the BatchNorm running statistics."""
+    import numpy as np
+    params = [p for _, p in model.named_parameters()]
+    flat_p = torch.cat([p.detach().reshape(-1) for p in params])
+    flat_g = torch.cat([(p.grad if p.grad is not None else torch.zeros_like(p)).detach().reshape(-1) for p in params])
+    idx = np.sort(np.random.default_rng(0).choice(flat_p.numel(), min(DUMP_SAMPLE, flat_p.numel()), replace=False))
+    idx = torch.from_numpy(idx).to(flat_p.device)
+    arrays = dict(out)
+    arrays['params_sample'] = flat_p[idx]
+    arrays['grads_sample'] = flat_g[idx]
+    arrays['bn_running_stats'] = torch.cat([b.reshape(-1) for _, b in model.named_buffers() if b.is_floating_point()])
+    os.makedirs(folder, exist_ok=True)
+    for name, t in arrays.items():
+        np.save(os.path.join(folder, name + '.npy'), t.detach().float().cpu().numpy())
+    return sum(t.numel() for t in arrays.values()) * 4
+
+
 def self_launch(args, argv):
     """`python bench.py --gpus N` (N > 1) without a launcher: start the N ranks as CHILD processes through torch.distributed.run
     — before this process has made any GPU call, and never by exec — relay rank 0's JSON line and exit non-zero if any child does."""
@@ -392,10 +419,13 @@ def main():
                     help='weight-gradient kernels on side streams (measured slower than one stream since the Winograd kernels: 57.0 vs 55.1 ms)')
     ap.add_argument('--wgrad-group-rows', type=int, default=int(os.environ.get('LVAE_WGRAD_GROUP_ROWS', '16384')), help='weight gradients of layers with at most this many pixels (N*H*W) are launched in groups (0 = off)')
     ap.add_argument('--wgrad-streams', type=int, default=1, help='side streams the weight-gradient kernels are spread over')
+    ap.add_argument('--full', action='store_true',
+                    help='also make the measurements that take runs of their own: roofline, bf16_shard, other_configs, cpu_baseline')
+    ap.add_argument('--dump-outputs', metavar='DIR', help="write what the last timed step computed as DIR/<name>.npy (rank 0)")
     ap.add_argument('--no-cpu-baseline', action='store_true')
     ap.add_argument('--no-roofline', action='store_true')
-    ap.add_argument('--no-bf16-line', action='store_true', help='skip the nested bf16_shard measurement of the default fp32 run')
-    ap.add_argument('--no-other-configs', action='store_true', help='skip the nested measurements of BASELINE configs[1] and configs[4] (per-GPU shard)')
+    ap.add_argument('--no-bf16-line', action='store_true', help='skip the nested bf16_shard measurement of a --full fp32 run')
+    ap.add_argument('--no-other-configs', action='store_true', help='skip the nested measurements of BASELINE configs[1] and configs[4] (per-GPU shard) of a --full run')
     ap.add_argument('--launch-check', action='store_true',
                     help='rendezvous rehearsal without a GPU: every rank joins the process group (use --backend gloo), all-reduces one host '
                          'scalar and rank 0 prints a JSON line; exercises the self-launch path of --gpus N (tests/test_dist_cpu.py)')
@@ -498,6 +528,8 @@ def main():
     loss, elbo = float(out['loss']), float(out['elbo'])
     if rank == 0:
         log('timed %d steps: %.2f ms/step' % (args.steps, dt / args.steps * 1e3))
+    if rank == 0 and args.dump_outputs:   # before --full's measurements, which step the same model further
+        log('wrote %.1f MB of outputs to %s' % (dump_outputs(args.dump_outputs, out, model) / 2**20, args.dump_outputs))
 
     line = None
     if rank == 0:
@@ -522,13 +554,13 @@ def main():
             line['config']['allreduce_bucket_bytes'] = [4 * (hi - lo) for lo, hi, _ in allreduce.buckets]
             line['config']['backend'] = dist.get_backend() if dist.is_initialized() else None
     step_s = dt / args.steps
-    if rank == 0 and not args.no_roofline:
+    if rank == 0 and args.full and not args.no_roofline:
         (dkey, (dn, dflops, dbytes, dms)), fam_f, fam_ms, n, kind = conv_roofline(model, ring[0])
         line['roofline'] = dominant_kernel_record(dkey, dn, dflops, dbytes, dms, kind, args.dtype)
         line['roofline']['all_conv_fwd_dgrad'] = {'launches_per_step': n, 'algorithmic_flops_per_step': fam_f, 'ms_per_step': fam_ms,
                                                   'effective_tflops': fam_f / (fam_ms * 1e-3) / 1e12}
         line['roofline']['step'] = step_record(step_s, args.batch, args.dtype)
-    if rank == 0 and world == 1 and args.dtype == 'f32' and not args.no_bf16_line:
+    if rank == 0 and args.full and world == 1 and args.dtype == 'f32' and not args.no_bf16_line:
         # BASELINE configs[3] per-GPU shard: same model, same batch, compute_dtype bf16
         from lvae_amd import kernels as K
         model.compute_dtype = 'bf16'
@@ -549,12 +581,12 @@ def main():
             'value': args.batch / s16, 'unit': 'images/s', 'ms_per_step': s16 * 1e3, 'steps': n16, 'dtype': 'bf16',
             'neg_elbo': -float(out16['elbo']), 'roofline': r16}
         log('bf16 shard: %.2f ms/step' % (s16 * 1e3))
-    if rank == 0 and world == 1 and args.dtype == 'f32' and not args.no_other_configs:
+    if rank == 0 and args.full and world == 1 and args.dtype == 'f32' and not args.no_other_configs:
         line['other_configs'] = {}
         for key, desc, cfg, batch, f_img, b_img in OTHER_CONFIGS:
             line['other_configs'][key] = time_other_config(desc, cfg, batch, f_img, b_img, dev)
             log('%s: %.2f ms/step' % (key, line['other_configs'][key]['ms_per_step']))
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
+    if rank == 0 and args.full and world == 1 and not args.no_cpu_baseline:
         log('cpu baseline on %d host cores ...' % host_cores())
         line['cpu_baseline'] = cpu_baseline()
     if rank == 0:

@@ -3,7 +3,7 @@
 #   2. the same for --dtype bf16                                       -> r04_bf16_kernel_by_grid.txt
 #   3. step-level PMC passes (eager step), fp32 and bf16                -> r04_pmc/hbm_traffic.json, hbm_traffic_bf16.json
 #   4. fused residual-block kernels: phase stamps, per-level chain times, whole-step A/B (fused vs one kernel per op)
-#   5. python bench.py (reads 1-3)                                      -> r04_bench_n1.json ; smoke()
+#   5. python bench.py --full (reads 1-3)                               -> r04_bench_n1.json ; smoke()
 # Everything lands in gpurun_out/final4/ (the box's profiles/ does not travel back); copy the summaries to profiles/ afterwards.
 set -x
 cd $GRAFT_REPO_ROOT
@@ -29,7 +29,7 @@ python tools/rb_bench.py 2>&1 | grep -v amdgpu.ids > $OUT/r04_rb_chain_times.txt
 python tools/launch_floor.py 2>&1 | grep -v amdgpu.ids > $OUT/r04_launch_floor.txt
 bash tools/rb_step_ab.sh > $OUT/r04_rb_step_ab.txt 2>&1
 bash tools/rb_step_ab.sh --dtype bf16 > $OUT/r04_rb_step_ab_bf16.txt 2>&1
-python bench.py > $OUT/r04_bench_n1.json 2> $OUT/bench.err || exit 1
+python bench.py --full > $OUT/r04_bench_n1.json 2> $OUT/bench.err || exit 1
 cut -c1-600 $OUT/r04_bench_n1.json
 python -c "import __graft_entry__ as g; g.smoke(); print('smoke ok')" 2>&1 | tail -2
 cat $OUT/pmc_summary_f32.txt | head -12; cat $OUT/pmc_summary_bf16.txt | head -8; cat $OUT/r04_rb_step_ab.txt $OUT/r04_rb_step_ab_bf16.txt

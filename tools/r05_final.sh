@@ -3,7 +3,7 @@
 #   2. the same for --dtype bf16                                       -> r05_bf16_kernel_by_grid.txt
 #   3. step-level PMC passes (eager step), fp32 and bf16                -> r05_pmc/hbm_traffic.json, hbm_traffic_bf16.json
 #   4. whole-step A/B of the deferred BatchNorm-1 apply on this box
-#   5. python bench.py (reads 1-3)                                      -> r05_bench_n1.json ; smoke()
+#   5. python bench.py --full (reads 1-3)                               -> r05_bench_n1.json ; smoke()
 # Everything lands in gpurun_out/final5/ (the box's profiles/ does not travel back); copy the summaries to profiles/ afterwards.
 set -x
 cd $GRAFT_REPO_ROOT
@@ -26,7 +26,7 @@ cp $OUT/r05_kernel_by_grid.txt $OUT/r05_bf16_kernel_by_grid.txt $OUT/r05_kernel_
 cp $OUT/hbm_traffic.json $OUT/hbm_traffic_bf16.json profiles/r05_pmc/
 # round-5 whole-step A/B pairs on THIS box (python-side switches, product library): deferred BatchNorm-1 apply on / off
 CASES="defer=LVAE_DEFER_APPLY=1;nodefer=LVAE_DEFER_APPLY=0" bash tools/rb_step_ab.sh --no-other-configs > $OUT/r05_defer_step_ab.txt 2>&1
-python bench.py > $OUT/r05_bench_n1.json 2> $OUT/bench.err || exit 1
+python bench.py --full > $OUT/r05_bench_n1.json 2> $OUT/bench.err || exit 1
 cut -c1-600 $OUT/r05_bench_n1.json
 python -c "import __graft_entry__ as g; g.smoke(); print('smoke ok')" 2>&1 | tail -2
 cat $OUT/pmc_summary_f32.txt | head -12; cat $OUT/pmc_summary_bf16.txt | head -8; cat $OUT/r05_defer_step_ab.txt
