@@ -145,9 +145,15 @@ typedef struct lvae_conv_desc {
   uint8_t reserved_;      /* 0 */
 } lvae_conv_desc;
 
-/* Scratch bytes lvae_conv2d_f32 can use for `d` (0 when no variant needs any). Large 3x3 / stride-1 / 64-channel layers run
- * as Winograd F(2x2,3x3) on the fp32 MFMA (2.25x fewer multiplies; coefficients 0, +-1, +-1/2, result within a few ulp of
- * the direct sum) when the scratch is supplied; without it the direct halo-tile kernel runs. */
+/* Kernel choice: lvae_conv2d_f32 / _bf16 choose one kernel per descriptor (pos -> bf16 direct -> Winograd -> halo -> 1x1 -> generic,
+ * made on the descriptor without its in_fold), and every query below (_workspace, _variant, _stats_rows, _folds_bn_finalize,
+ * _stats_buffer_rows, lvae_resblock_bf16_storage) answers for exactly the kernel the launch takes. A variant that reads a scratch buffer
+ * needs d->workspace present, at least lvae_conv2d_workspace(d) bytes and 16-byte aligned; otherwise the choice (and every answer)
+ * moves on to the next kernel of the order.
+ *
+ * Scratch bytes lvae_conv2d_f32 can use for `d` (0 when no variant needs any), answered for a sized, 16-byte aligned d->workspace.
+ * Large 3x3 / stride-1 / 64-channel layers run as Winograd F(2x2,3x3) on the fp32 MFMA (2.25x fewer multiplies; coefficients 0, +-1,
+ * +-1/2, result within a few ulp of the direct sum) when the scratch is supplied; without it the direct halo-tile kernel runs. */
 size_t lvae_conv2d_workspace(const lvae_conv_desc* d);
 int lvae_conv2d_f32(const lvae_conv_desc* d, void* stream);
 /* dgrad of a 1x1 / stride-1 convolution whose INPUT was a channel concat (x, x2) — MergeLayer / SkipConnectionMerger,
@@ -350,7 +356,10 @@ int lvae_resblock_conv_f32(const lvae_conv_desc* d, const lvae_rb_ext* ext, void
  *   dw[tap,k,n] += sum_{n,oh,ow} T(x)[n,ih,iw,k] * dy[n,oh,ow,n]     db[n] += sum dy[..,n]
  * written with the strides d->w_stap/w_sk/w_sn into `dw` (accumulating). Deterministic: split-K partial slabs
  * in `workspace` are summed in a fixed order by a second kernel. `dy` is [N,OH,OW,Cout].
- * workspace bytes needed: lvae_conv2d_wgrad_workspace(d).
+ * Kernel choice: img -> bf16 -> Winograd -> 1x1 -> tile -> thin -> generic, made once from `d` and the alignment of dy and workspace;
+ * lvae_conv2d_wgrad_workspace / _variant / _apply_ok and the grouped call answer for that choice with 16-byte aligned dy and workspace.
+ * workspace bytes needed: lvae_conv2d_wgrad_workspace(d). With a dy or workspace that is not 16-byte aligned the launch may take a kernel
+ * that needs more; it then returns LVAE_EWORKSPACE instead of writing past workspace_bytes.
  * replaces: autograd's convolution_backward (weight, bias) for every call site listed above. */
 size_t lvae_conv2d_wgrad_workspace(const lvae_conv_desc* d);
 int lvae_conv2d_wgrad_f32(const lvae_conv_desc* d, const float* dy, float* dw, float* db, void* workspace,

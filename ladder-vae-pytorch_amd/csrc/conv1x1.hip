@@ -300,20 +300,30 @@ static int pick_bm(const PwArgs& a, hipStream_t s) {
   return launch_pw<64, KT, NT, KC>(a, s);  // measured: 64-pixel tiles (2-3 workgroups per CU overlap load / MFMA / store) beat 128
 }
 
-// -1000: not eligible (the caller uses the generic kernel)
-static int conv1x1_try_all(const lvae_conv_desc* d, const float* gate_res, float* gate_out, int gate_act, const float* gb_dout,
-                           const float* gb_ab, float* gb_dab, int gb_act, hipStream_t s, float* y2, int split) {
+// eligibility of the single-shot kernel for d and the extra operands of its gate / gate-backward / dgrad-cat forms (null: not that form);
+// nc: n-contiguous weights
+static bool pw_select(const lvae_conv_desc* d, const float* gate_res, const float* gate_out, const float* gb_dout, const float* gb_ab,
+                      const float* gb_dab, const float* y2, int split, bool& nc) {
   const int K = d->C1 + d->C2, N = d->Cout;
-  if (d->KH != 1 || d->KW != 1 || d->stride != 1 || d->pad != 0 || d->OH != d->H || d->OW != d->W) return -1000;
-  if (K > 128 || N > 128 || d->C1 % 4 || d->C2 % 4 || N % 4 || (gate_out && N % 8)) return -1000;
-  if (gb_dout && (K % 8 || d->C2 != 0 || d->in_scale != nullptr || !al16p(gb_dout) || !al16p(gb_ab) || !al16p(gb_dab))) return -1000;
+  if (d->KH != 1 || d->KW != 1 || d->stride != 1 || d->pad != 0 || d->OH != d->H || d->OW != d->W) return false;
+  if (K > 128 || N > 128 || d->C1 % 4 || d->C2 % 4 || N % 4 || (gate_out && N % 8)) return false;
+  if (gb_dout && (K % 8 || d->C2 != 0 || d->in_scale != nullptr || !al16p(gb_dout) || !al16p(gb_ab) || !al16p(gb_dab))) return false;
   if (!al16p(d->x) || !al16p(d->x2) || !al16p(d->w) || !al16p(d->y) || !al16p(d->bias) || !al16p(d->in_scale) ||
       !al16p(d->in_shift) || !al16p(d->out_scale) || !al16p(gate_res) || !al16p(gate_out))
-    return -1000;
+    return false;
   const bool kc = d->w_sk == 1 && d->w_sn % 4 == 0 && K % 4 == 0;
-  const bool nc = d->w_sn == 1 && d->w_sk % 4 == 0;
-  if (!kc && !nc) return -1000;
-  if (gate_out == nullptr && d->y == nullptr) return -1000;
+  nc = d->w_sn == 1 && d->w_sk % 4 == 0;
+  if (!kc && !nc) return false;
+  if (gate_out == nullptr && d->y == nullptr) return false;
+  return y2 == nullptr || (gate_out == nullptr && d->stats_out == nullptr && split > 0 && split < N && split % 4 == 0 && al16p(y2));
+}
+
+// -1000: not eligible (the gate / dgrad-cat callers then report it)
+static int conv1x1_try_all(const lvae_conv_desc* d, const float* gate_res, float* gate_out, int gate_act, const float* gb_dout,
+                           const float* gb_ab, float* gb_dab, int gb_act, hipStream_t s, float* y2, int split) {
+  bool nc;
+  if (!pw_select(d, gate_res, gate_out, gb_dout, gb_ab, gb_dab, y2, split, nc)) return -1000;
+  const int K = d->C1 + d->C2, N = d->Cout;
   PwArgs a;
   a.d = *d;
   a.M = d->N * d->H * d->W;
@@ -328,7 +338,6 @@ static int conv1x1_try_all(const lvae_conv_desc* d, const float* gate_res, float
   a.gb_act = gb_act;
   a.y2 = y2;
   a.split = split;
-  if (y2 != nullptr && (gate_out != nullptr || d->stats_out != nullptr || split <= 0 || split >= N || split % 4 != 0 || !al16p(y2))) return -1000;
   const bool k64 = K <= 64, n64 = N <= 64;
   if (nc) {
     if (k64) return n64 ? pick_bm<64, 64, false>(a, s) : pick_bm<64, 128, false>(a, s);
@@ -336,6 +345,16 @@ static int conv1x1_try_all(const lvae_conv_desc* d, const float* gate_res, float
   }
   if (k64) return n64 ? pick_bm<64, 64, true>(a, s) : pick_bm<64, 128, true>(a, s);
   return n64 ? pick_bm<128, 64, true>(a, s) : pick_bm<128, 128, true>(a, s);
+}
+
+// plain 1x1 convolution (the route of lvae_conv2d_f32): plan, then a launch that cannot decline
+bool conv1x1_plan(const lvae_conv_desc* d) {
+  bool nc;
+  return pw_select(d, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, 0, nc);
+}
+
+int conv1x1_launch(const lvae_conv_desc* d, hipStream_t s) {
+  return conv1x1_try_all(d, nullptr, nullptr, 0, nullptr, nullptr, nullptr, 0, s, nullptr, 0);
 }
 
 int conv1x1_try_ex(const lvae_conv_desc* d, const float* gate_res, float* gate_out, int gate_act, const float* gb_dout,
@@ -351,6 +370,8 @@ int conv1x1_try(const lvae_conv_desc* d, const float* gate_res, float* gate_out,
 
 namespace lvae {
 int conv_desc_check(const lvae_conv_desc* d, const char* who);
+int conv1x1_gate_fwd_wgs(const lvae_conv_desc* d);
+int conv1x1_gate_fwd_try(const lvae_conv_desc* d, const float* res, float* out, int act, hipStream_t s);
 }
 using namespace lvae;
 
@@ -364,5 +385,55 @@ extern "C" int lvae_conv1x1_dgrad_cat_f32(const lvae_conv_desc* d, float* dx2, i
   LVAE_REQUIRE(rc != -1000, LVAE_EINVAL,
                "lvae_conv1x1_dgrad_cat_f32: shape not supported (1x1, stride 1, at most 128 reduction and 128 output channels, multiples of 4, "
                "16-byte aligned tensors, unit weight stride along one axis): use two lvae_conv2d_f32 launches");
+  return rc;
+}
+
+// GateLayer2d forward fused with its 1x1 convolution and the residual add (lib/nn.py:118-126, 99):
+//   ab = conv1x1(T(x)) + bias  (written to d->y when non-null; needed by the backward)
+//   out[m, c] = act(ab[m, c]) * sigmoid(ab[m, C + c]) + res[m, c]
+// rows of BatchNorm partials ([rows][2][C], C = Cout/2) lvae_conv1x1_gate_f32 writes for its `out` when d->stats_out is set
+extern "C" int32_t lvae_conv1x1_gate_stats_rows(const lvae_conv_desc* d) {
+  if (d == nullptr || d->Cout % 8 != 0) return 0;
+  const int persistent = conv1x1_gate_fwd_wgs(d);  // one row per workgroup of the persistent kernel (conv1x1_gate_fwd.hip)
+  if (persistent) return persistent;
+  const int c4n = d->Cout / 8;
+  if (c4n <= 0 || 256 % c4n != 0 || d->Cout > 128) return 0;
+  return (int32_t)(((int64_t)d->N * d->H * d->W + 63) / 64);  // 64-pixel tiles
+}
+
+extern "C" int lvae_conv1x1_gate_f32(const lvae_conv_desc* d, const float* res, int32_t act, float* out, void* stream) {
+  int rc = conv_desc_check(d, "lvae_conv1x1_gate_f32");
+  if (rc) return rc;
+  LVAE_REQUIRE(out != nullptr, LVAE_EINVAL, "lvae_conv1x1_gate_f32: null out");
+  LVAE_REQUIRE(d->Cout % 2 == 0, LVAE_EINVAL, "lvae_conv1x1_gate_f32: Cout must be 2*C");
+  LVAE_REQUIRE(d->stats_out == nullptr || (d->stats_pivot != nullptr && lvae_conv1x1_gate_stats_rows(d) > 0 &&
+                                           (reinterpret_cast<uintptr_t>(d->stats_pivot) & 15) == 0),
+               LVAE_EINVAL, "lvae_conv1x1_gate_f32: stats_out set but lvae_conv1x1_gate_stats_rows(d) == 0");
+  rc = conv1x1_gate_fwd_try(d, res, out, act, (hipStream_t)stream);
+  LVAE_REQUIRE(rc != -1000 || (d->x_dtype == LVAE_DT_F32 && d->y_dtype == LVAE_DT_F32), LVAE_EINVAL,
+               "lvae_conv1x1_gate_f32: bf16-stored x / ab need the persistent 64-channel kernel with precision LVAE_PREC_BF16");
+  if (rc == -1000) rc = conv1x1_try(d, res, out, act, (hipStream_t)stream);
+  LVAE_REQUIRE(rc != -1000, LVAE_EINVAL,
+               "lvae_conv1x1_gate_f32: unsupported shape (needs a 1x1 stride-1 conv, Cin <= 128, Cout <= 128, channels %% 4 == 0, "
+               "16-byte aligned buffers); use lvae_conv2d_f32 + lvae_gate_fwd_f32");
+  return rc;
+}
+
+// GateLayer2d backward fused with the dgrad of its 1x1 convolution: dab (the gradient w.r.t. the pre-activations ab, also
+// written to `dab` for the weight-gradient call) is formed in the kernel's operand staging from dout and ab, then
+// dx = dab . W^T with the descriptor's epilogue (out_scale = Dropout2d mask of the producer). `d` describes that dgrad:
+// C1 = 2C, Cout = channels of the gate convolution's input, d->x is ignored.
+extern "C" int lvae_conv1x1_gate_bwd_f32(const lvae_conv_desc* d, const float* dout, const float* ab, int32_t act, float* dab,
+                                         void* stream) {
+  LVAE_REQUIRE(d && dout && ab && d->y, LVAE_EINVAL, "lvae_conv1x1_gate_bwd_f32: null pointer");
+  lvae_conv_desc dd = *d;
+  dd.x = ab;  // any valid, aligned device pointer: the A operand is computed, not loaded
+  int rc = conv_desc_check(&dd, "lvae_conv1x1_gate_bwd_f32");
+  if (rc) return rc;
+  LVAE_REQUIRE(dd.C1 % 8 == 0 && dd.C2 == 0, LVAE_EINVAL, "lvae_conv1x1_gate_bwd_f32: C1 must be 2C");
+  rc = conv1x1_try_ex(&dd, nullptr, nullptr, 0, dout, ab, dab, act, (hipStream_t)stream);
+  LVAE_REQUIRE(rc != -1000, LVAE_EINVAL,
+               "lvae_conv1x1_gate_bwd_f32: unsupported shape (needs a 1x1 stride-1 conv, 2C <= 128, Cout <= 128, 16-byte aligned "
+               "buffers); use lvae_gate_bwd_f32 + lvae_conv2d_f32");
   return rc;
 }

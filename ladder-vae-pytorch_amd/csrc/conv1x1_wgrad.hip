@@ -148,10 +148,10 @@ size_t conv1x1_wgrad_workspace(const lvae_conv_desc* d) {
   return (size_t)nwg * ((size_t)64 * d->Cout + d->Cout) * sizeof(float);
 }
 
-// returns -1000 when not eligible
-int conv1x1_wgrad_try(const lvae_conv_desc* d, const float* dy, float* dw, float* db, void* workspace, hipStream_t s) {
-  int nwg, ppw;
-  if (!w1x1_plan(d, nwg, ppw)) return -1000;
+// runs the plan of conv1x1_wgrad_workspace(d) != 0
+int conv1x1_wgrad_launch(const lvae_conv_desc* d, const float* dy, float* dw, float* db, void* workspace, hipStream_t s) {
+  int nwg = 0, ppw = 0;
+  w1x1_plan(d, nwg, ppw);
   W1x1Args a;
   a.x = d->x;
   a.dy = dy;

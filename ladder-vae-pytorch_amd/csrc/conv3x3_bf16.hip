@@ -35,7 +35,6 @@ struct BfArgs {
   int debug;  // phase-skip builds only (-DLVAE_PHASE_DEBUG): 1 = no halo staging, 2 = no epilogue, 4 = no MFMAs, 8 = no weight staging
 };
 
-constexpr int kBfNotEligible = -1000;
 constexpr int BF_LDK = 72;   // bf16 elements per LDS row (64 channels + 8 pad = 144 bytes)
 
 // MI: 32-pixel MFMA row blocks per wave; the workgroup tile is BM = 64 * MI output pixels x 64 output channels, 4 waves 2(M) x 2(N)
@@ -1199,10 +1198,20 @@ int conv3x3_bf16_form(const lvae_conv_desc* d) {
   return conv3x3_bf16_eligible(d, 3) ? 3 : 0;
 }
 
-int conv3x3_bf16_stats_rows(const lvae_conv_desc* d, int split) {
+// plan of the form conv3x3_bf16_form(d) picks: it reads the pre-split weight planes from d->workspace (assume_ws: from a sized, 16-byte
+// aligned one, as lvae_conv2d_workspace asks) and writes one statistics row per pixel tile
+bool conv3x3_bf16_plan(const lvae_conv_desc* d, bool assume_ws, ConvPlan& p) {
+  const int split = conv3x3_bf16_form(d);
+  if (split == 0) return false;
+  const size_t ws = conv3x3_bf16_workspace(d, split);
+  if (!assume_ws && (d->workspace == nullptr || (size_t)d->workspace_bytes < ws || !al16b(d->workspace))) return false;
   BfArgs a;
-  if (d->workspace == nullptr || (size_t)d->workspace_bytes < conv3x3_bf16_workspace(d, split) || !bf_select(d, split, a)) return 0;
-  return ((d->N + a.NI - 1) / a.NI) * a.tiles_h;
+  bf_select(d, split, a);  // (conv3x3_bf16_form accepted d)
+  p = ConvPlan{};
+  p.variant = split == 1 ? LVAE_VARIANT_BF16_DIRECT : LVAE_VARIANT_SIX_DIRECT;
+  p.rows = ((d->N + a.NI - 1) / a.NI) * a.tiles_h;
+  p.workspace = ws;
+  return true;
 }
 
 template <int SPLIT, int MI, bool PRE = false, bool XB = false, bool YB = false>
@@ -1226,12 +1235,11 @@ static int launch_bf(BfArgs a, hipStream_t s) {
 }
 
 // split = 1: bf16 operands; split = 3: fp32-equivalent six-product form. `d->workspace` holds the pre-split weights
-// (conv3x3_bf16_workspace bytes; written here first unless d->workspace_ready). Returns kBfNotEligible when the descriptor or the
-// scratch does not fit.
-int conv3x3_bf16_try(const lvae_conv_desc* d, int split, hipStream_t s) {
+// (conv3x3_bf16_workspace bytes; written here first unless d->workspace_ready).
+int conv3x3_bf16_launch(const lvae_conv_desc* d, const ConvPlan& p, hipStream_t s) {
+  const int split = p.variant == LVAE_VARIANT_BF16_DIRECT ? 1 : 3;
   BfArgs a;
-  if (d->workspace == nullptr || (size_t)d->workspace_bytes < conv3x3_bf16_workspace(d, split) || !al16b(d->workspace)) return kBfNotEligible;
-  if (!bf_select(d, split, a)) return kBfNotEligible;
+  bf_select(d, split, a);  // (the plan accepted d)
   if (!d->workspace_ready) {
     BfPrepEntry e;
     conv3x3_bf16_prep_entry(d, split, &e);
@@ -1335,10 +1343,10 @@ size_t conv3x3_wgrad_bf16_workspace(const lvae_conv_desc* d) {
 void wgrad_reduce_launch(const float* slab_w, const float* slab_b, int ksplit, int ntaps, int Cin, int Cout, int64_t stap, int64_t sk,
                          int64_t sn, float* dw, float* db, hipStream_t s);
 
-// returns kBfNotEligible when the descriptor does not take this kernel
-int conv3x3_wgrad_bf16_try(const lvae_conv_desc* d, const float* dy, float* dw, float* db, void* workspace, hipStream_t s) {
+// runs the plan of conv3x3_wgrad_bf16_workspace(d) != 0 (16-byte aligned dy and workspace: the route of lvae_conv2d_wgrad_f32 checked them)
+int conv3x3_wgrad_bf16_launch(const lvae_conv_desc* d, const float* dy, float* dw, float* db, void* workspace, hipStream_t s) {
   BfWgArgs a;
-  if (!bfwg_plan(d, a) || !al16b(dy) || !al16b(workspace)) return kBfNotEligible;
+  bfwg_plan(d, a);
   a.d = *d;
   a.d.in_fold = nullptr;
   a.dy = dy;

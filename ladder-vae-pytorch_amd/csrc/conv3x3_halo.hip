@@ -276,8 +276,6 @@ __global__ __launch_bounds__(256, 2) void conv3x3_halo_kernel(HaloArgs a) {
   }
 }
 
-constexpr int kHaloNotEligible = -1000;
-
 static bool al16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
 
 // tile geometry for a W-wide image: rows per tile and images per tile so that NI*TH*W <= BM
@@ -355,20 +353,21 @@ static int halo_select(const lvae_conv_desc* d, HaloArgs& a, bool& ncontig_out) 
   return BM;
 }
 
-// rows of BatchNorm partials a launch writes (one per pixel tile), 0 when this kernel would not run
-int conv3x3_halo_stats_rows(const lvae_conv_desc* d) {
+// plan: no workspace, one statistics row per pixel tile
+bool conv3x3_halo_plan(const lvae_conv_desc* d, ConvPlan& p) {
   HaloArgs a;
-  bool nc;
-  if (!halo_select(d, a, nc)) return 0;
-  return ((d->N + a.NI - 1) / a.NI) * a.tiles_h;
+  bool ncontig;
+  const int BM = halo_select(d, a, ncontig);
+  if (BM == 0) return false;
+  p = ConvPlan{};
+  p.rows = ((d->N + a.NI - 1) / a.NI) * a.tiles_h;
+  return true;
 }
 
-// returns kHaloNotEligible when the descriptor does not fit this kernel (the caller then uses the generic one)
-int conv3x3_halo_try(const lvae_conv_desc* d, hipStream_t s) {
+int conv3x3_halo_launch(const lvae_conv_desc* d, hipStream_t s) {
   HaloArgs a;
   bool ncontig = false;
-  const int BM = halo_select(d, a, ncontig);
-  if (BM == 0) return kHaloNotEligible;
+  const int BM = halo_select(d, a, ncontig);  // (the plan accepted d: deterministic, BM != 0)
   const int cin_t = d->C1 <= 32 ? 32 : 64;
   static const int dbg = lvae::debug_phase_switch("LVAE_HALO_DEBUG");  // phase-skip builds (-DLVAE_PHASE_DEBUG) only; 0 in the product
   a.debug = dbg;

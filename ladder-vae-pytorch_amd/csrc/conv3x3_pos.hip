@@ -27,7 +27,6 @@ struct PosArgs {
   uint32_t m_w;  // fastdiv magic of W
 };
 
-constexpr int kPosNotEligible = -1000;
 
 template <int CIN_T, bool B_KCONTIG>
 __global__ __launch_bounds__(256) void conv3x3_pos_kernel(PosArgs a) {
@@ -301,15 +300,15 @@ static bool pos_select(const lvae_conv_desc* d, bool& ncontig) {
   return true;
 }
 
-bool conv3x3_pos_eligible(const lvae_conv_desc* d) {
-  bool nc;
-  return pos_select(d, nc);
-}
-
-int conv3x3_pos_stats_rows(const lvae_conv_desc* d) {
-  bool nc;
-  if (!pos_select(d, nc)) return 0;
-  return ((d->N + 31) / 32) * d->H * d->W;
+// plan: no workspace, one statistics row per (32-image group, position), folds the BatchNorm finalize of its input
+bool conv3x3_pos_plan(const lvae_conv_desc* d, ConvPlan& p) {
+  bool ncontig;
+  if (!pos_select(d, ncontig)) return false;
+  p = ConvPlan{};
+  p.variant = LVAE_VARIANT_POS;
+  p.rows = ((d->N + 31) / 32) * d->H * d->W;
+  p.folds = true;
+  return true;
 }
 
 template <int CIN_T, bool KC>
@@ -335,10 +334,9 @@ static int launch_pos(const PosArgs& a, hipStream_t s) {
   return 0;
 }
 
-// returns kPosNotEligible when the descriptor does not fit this kernel
-int conv3x3_pos_try(const lvae_conv_desc* d, hipStream_t s) {
+int conv3x3_pos_launch(const lvae_conv_desc* d, hipStream_t s) {
   bool ncontig = false;
-  if (!pos_select(d, ncontig)) return kPosNotEligible;
+  pos_select(d, ncontig);  // (the plan accepted d)
   PosArgs a;
   a.d = *d;
   a.d.in_fold = nullptr;

@@ -140,10 +140,10 @@ static int launch_ws(const WTileArgs& a, hipStream_t s) {
   return 0;
 }
 
-// returns -1000 when not eligible
-int conv_wgrad_tile_try(const lvae_conv_desc* d, const float* dy, float* dw, float* db, void* workspace, hipStream_t s) {
+// runs the plan of conv_wgrad_tile_workspace(d) != 0 (16-byte aligned dy: the route of lvae_conv2d_wgrad_f32 checked it)
+int conv_wgrad_tile_launch(const lvae_conv_desc* d, const float* dy, float* dw, float* db, void* workspace, hipStream_t s) {
   WTileArgs a;
-  if (!wtile_plan(d, a) || !al16w(dy)) return -1000;
+  wtile_plan(d, a);
   a.d = *d;
   a.dy = dy;
   static const int dbg = lvae::debug_phase_switch("LVAE_WG_DEBUG");  // phase-skip builds (-DLVAE_PHASE_DEBUG) only; 0 in the product
@@ -197,7 +197,7 @@ int conv_wgrad_tile_kind(const lvae_conv_desc* d) {
   return cin_t == 32 ? 2 : (cin_t == 64 ? 3 : 4);
 }
 
-// n <= kMaxGroup descriptors of the same kind, each with its own workspace: one launch + one grouped reduce
+// n <= kMaxGroup descriptors of the same kind whose route is this kernel, each with its own workspace: one launch + one grouped reduce
 int conv_wgrad_tile_grouped(const lvae_conv_desc* const* ds, const float* const* dy, float* const* dw, float* const* db,
                             void* const* workspace, int n, int kind, hipStream_t s) {
   WTileGroup g;
@@ -207,7 +207,7 @@ int conv_wgrad_tile_grouped(const lvae_conv_desc* const* ds, const float* const*
   size_t lds = 0;
   for (int i = 0; i < n; ++i) {
     WTileArgs& a = g.p[i];
-    if (!wtile_plan(ds[i], a) || !al16w(dy[i])) return -1000;
+    wtile_plan(ds[i], a);
     a.d = *ds[i];
     a.dy = dy[i];
     a.debug = dbg;

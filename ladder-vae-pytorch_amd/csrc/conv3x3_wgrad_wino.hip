@@ -229,10 +229,10 @@ static int launch_wg_wino(const WgWinoArgs& a, hipStream_t s) {
   return 0;
 }
 
-// returns -1000 when not eligible
-int conv_wgrad_wino_try(const lvae_conv_desc* d, const float* dy, float* dw, float* db, void* workspace, hipStream_t s) {
+// runs the plan of conv_wgrad_wino_workspace(d) != 0 (16-byte aligned dy and workspace: the route of lvae_conv2d_wgrad_f32 checked them)
+int conv_wgrad_wino_launch(const lvae_conv_desc* d, const float* dy, float* dw, float* db, void* workspace, hipStream_t s) {
   WgWinoArgs a;
-  if (!wg_wino_plan(d, a) || !al16g(dy) || !al16g(workspace)) return -1000;
+  wg_wino_plan(d, a);
   a.d = *d;
   a.dy = dy;
   a.slab_w = static_cast<float*>(workspace);
@@ -275,12 +275,13 @@ bool conv_wgrad_wino_apply_ok(const lvae_conv_desc* d) {
   return d != nullptr && d->Cout == 64 && (d->W == 16 || d->W == 32) && d->x_dtype == LVAE_DT_F32 && d->y_dtype == LVAE_DT_F32 && wg_wino_plan(d, a);
 }
 
-// returns -1000 when not eligible
-int conv_wgrad_wino_apply_try(const lvae_conv_desc* d, const lvae_bn_apply* ap, float* dw, float* db, void* workspace, hipStream_t s) {
+// runs a descriptor lvae_conv2d_wgrad_apply_ok accepted
+int conv_wgrad_wino_apply_launch(const lvae_conv_desc* d, const lvae_bn_apply* ap, float* dw, float* db, void* workspace, hipStream_t s) {
   WgWinoApArgs g;
   WgWinoArgs& a = g.w;
-  if (!conv_wgrad_wino_apply_ok(d) || !wg_wino_plan(d, a) || !al16g(workspace)) return -1000;
-  if (!al16g(ap->parts) || !al16g(ap->coef) || !al16g(ap->dh) || !al16g(ap->x) || !al16g(ap->out) || !al16g(ap->drop)) return -1000;
+  LVAE_REQUIRE(al16g(workspace) && al16g(ap->parts) && al16g(ap->coef) && al16g(ap->dh) && al16g(ap->x) && al16g(ap->out) && al16g(ap->drop),
+               LVAE_EALIGN, "lvae_conv2d_wgrad_apply_f32: buffers must be 16-byte aligned");
+  wg_wino_plan(d, a);
   a.d = *d;
   a.dy = nullptr;
   a.slab_w = static_cast<float*>(workspace);
@@ -294,7 +295,7 @@ int conv_wgrad_wino_apply_try(const lvae_conv_desc* d, const lvae_bn_apply* ap, 
   return 0;
 }
 
-// n <= kMaxWinoGroup eligible descriptors with the same image width, each with its own workspace; -1000 when one is not eligible
+// n <= kMaxWinoGroup descriptors whose route is this kernel (aligned dy and workspace), all of one image width, each with its own workspace
 int conv_wgrad_wino_grouped(const lvae_conv_desc* const* ds, const float* const* dy, float* const* dw, float* const* db,
                             void* const* workspace, int n, hipStream_t s) {
   WgWinoGroup g;
@@ -303,7 +304,7 @@ int conv_wgrad_wino_grouped(const lvae_conv_desc* const* ds, const float* const*
   const int W = ds[0]->W;
   for (int i = 0; i < n; ++i) {
     WgWinoArgs& a = g.p[i];
-    if (!wg_wino_plan(ds[i], a) || !al16g(dy[i]) || !al16g(workspace[i]) || ds[i]->W != W) return -1000;
+    wg_wino_plan(ds[i], a);
     a.d = *ds[i];
     a.dy = dy[i];
     a.slab_w = static_cast<float*>(workspace[i]);

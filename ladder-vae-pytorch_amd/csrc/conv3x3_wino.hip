@@ -1192,68 +1192,51 @@ static size_t wino_lds_bytes(const lvae_conv_desc* d, const WinoTile& w) {
   return lds < lds_r ? lds_r : lds;
 }
 
-// 0: this kernel would not run for d (every condition conv3x3_wino_try checks); LVAE_VARIANT_WINO_F32 / LVAE_VARIANT_WINO_SIX otherwise
-int conv3x3_wino_variant(const lvae_conv_desc* d) {
-  if (d->workspace == nullptr || !al16w2(d->workspace) || !conv3x3_wino_eligible(d) ||
-      (size_t)d->workspace_bytes < conv3x3_wino_workspace(d))
-    return 0;
-  WinoTile w;
-  if (!wino_tile(d, w) || wino_lds_bytes(d, w) > 159 * 1024) return 0;
-  return wino_split_form(d) ? LVAE_VARIANT_WINO_SIX : LVAE_VARIANT_WINO_F32;
-}
-
 // Folded BatchNorm finalize of the input (lvae_bn_fold, wino_fold_bn): 64-channel inputs, and launches of at most two workgroups per CU
 // (every workgroup re-reads the producer's partial rows from L2: 128-256 KB each; with four rounds per CU a finalize launch is cheaper)
-bool conv3x3_wino_folds(const lvae_conv_desc* d) {
+static bool wino_folds(const lvae_conv_desc* d, const WinoTile& w) {
   static const bool off = tune("LVAE_DISABLE_WINO_FOLD", 0) != 0;  // A/B switch (tuning builds only)
-  if (off || d->C1 > 64 || conv3x3_wino_variant(d) == 0) return false;
-  WinoTile w;
-  if (!wino_tile(d, w)) return false;
+  if (off || d->C1 > 64) return false;
   const bool narrow = w.mt == 1 && wino_narrow(d, w.TH, w.NI);
   const int64_t wgs = (int64_t)((d->N + w.NI - 1) / w.NI) * (d->H / w.TH) * (narrow ? (d->Cout + 31) / 32 : (d->Cout + 63) / 64);
   static const int64_t max_wgs = tune("LVAE_WINO_FOLD_MAX_WGS", 512);
   return wgs <= max_wgs;
 }
 
-// rows of BatchNorm partials a launch writes (one per pixel tile), 0 when this kernel would not run
-int conv3x3_wino_stats_rows(const lvae_conv_desc* d) {
-  if (d->workspace == nullptr || !conv3x3_wino_eligible(d) || (size_t)d->workspace_bytes < conv3x3_wino_workspace(d)) return 0;
+// plan: the transformed weights in d->workspace (assume_ws: in a sized, 16-byte aligned one, as lvae_conv2d_workspace asks), a pixel
+// tile within the LDS limit; one statistics row per pixel tile
+bool conv3x3_wino_plan(const lvae_conv_desc* d, bool assume_ws, ConvPlan& p) {
+  if (!conv3x3_wino_eligible(d)) return false;
+  const size_t ws = conv3x3_wino_workspace(d);
+  if (!assume_ws && (d->workspace == nullptr || (size_t)d->workspace_bytes < ws || !al16w2(d->workspace))) return false;
   WinoTile w;
-  if (!wino_tile(d, w)) return 0;
-  if (wino_lds_bytes(d, w) > 159 * 1024) return 0;
-  return ((d->N + w.NI - 1) / w.NI) * (d->H / w.TH);
-}
-
-// -1000: not eligible. `workspace` must hold conv3x3_wino_workspace(d) bytes (the transformed weights).
-static int conv3x3_wino_launch(const lvae_conv_desc* d, void* workspace, size_t workspace_bytes, const lvae_rb_ext* gate, hipStream_t s);
-
-int conv3x3_wino_try(const lvae_conv_desc* d, void* workspace, size_t workspace_bytes, hipStream_t s) {
-  return conv3x3_wino_launch(d, workspace, workspace_bytes, nullptr, s);
+  if (!wino_tile(d, w) || wino_lds_bytes(d, w) > 159 * 1024) return false;  // + 512 bytes of static LDS (s_coef)
+  p = ConvPlan{};
+  p.variant = wino_split_form(d) ? LVAE_VARIANT_WINO_SIX : LVAE_VARIANT_WINO_F32;
+  p.rows = ((d->N + w.NI - 1) / w.NI) * (d->H / w.TH);
+  p.folds = wino_folds(d, w);
+  p.workspace = ws;
+  return true;
 }
 
 // rows of BatchNorm partials of `out` (= workgroups) when the 256-pixel six-product kernel can run `d` with the GateLayer2d fused behind it
 // (lvae_resblock_conv_f32, LVAE_RB_EPI_GATE, for shapes the whole-image kernels of resblock_img.hip do not take): 0 = it cannot
 int conv3x3_wino2_gate_rows(const lvae_conv_desc* d) {
-  if (d->workspace == nullptr || !al16w2(d->workspace) || !conv3x3_wino_eligible(d) || (size_t)d->workspace_bytes < conv3x3_wino_workspace(d)) return 0;
   if (d->C1 != 64 || d->Cout != 64 || d->out_act != LVAE_ACT_NONE || d->gather != LVAE_GATHER_CONV) return 0;
+  ConvPlan p;
   WinoTile w;
-  if (!wino_tile(d, w) || w.mt != 2 || wino_lds_bytes(d, w) > 159 * 1024) return 0;
-  return ((d->N + w.NI - 1) / w.NI) * (d->H / w.TH);
+  if (!conv3x3_wino_plan(d, false, p) || (d->in_fold != nullptr && !p.folds) || !wino_tile(d, w) || w.mt != 2) return 0;
+  return p.rows;
 }
 
-int conv3x3_wino2_gate_try(const lvae_conv_desc* d, const lvae_rb_ext* gate, hipStream_t s) {
-  if (gate == nullptr || conv3x3_wino2_gate_rows(d) == 0) return -1000;
-  return conv3x3_wino_launch(d, d->workspace, (size_t)d->workspace_bytes, gate, s);
-}
-
-static int conv3x3_wino_launch(const lvae_conv_desc* d, void* workspace, size_t workspace_bytes, const lvae_rb_ext* gate, hipStream_t s) {
-  if (workspace == nullptr || !conv3x3_wino_eligible(d)) return -1000;
-  if (workspace_bytes < conv3x3_wino_workspace(d) || !al16w2(workspace)) return -1000;
+// Runs the plan conv3x3_wino_plan(d) accepted (for a gate: conv3x3_wino2_gate_rows(d) > 0); d->workspace holds the transformed weights
+// (written here first unless d->workspace_ready), d->in_fold only when the plan folds.
+static int wino_launch(const lvae_conv_desc* d, const lvae_rb_ext* gate, hipStream_t s) {
+  WinoTile wtile;
+  wino_tile(d, wtile);
   const int Cin = d->C1;
   WinoArgs a;
   a.d = *d;
-  WinoTile wtile;
-  if (!wino_tile(d, wtile)) return -1000;
   const int TH = wtile.TH, NI = wtile.NI, mt = wtile.mt;
   const bool split = wino_split_form(d);
   a.TH = TH;
@@ -1278,13 +1261,9 @@ static int conv3x3_wino_launch(const lvae_conv_desc* d, void* workspace, size_t 
   const int kpad = wino_kpad(d);
   a.Cin = Cin;
   const size_t lds = wino_lds_bytes(d, wtile);
-  if (lds > 159 * 1024) return -1000;  // + 512 bytes of static LDS (s_coef)
-  const bool folds = conv3x3_wino_folds(d);
+  const bool folds = wino_folds(d, wtile);
   a.f = lvae_bn_fold{};
-  if (d->in_fold != nullptr) {
-    if (!folds) return -1000;  // lvae_conv2d_f32 has checked lvae_conv2d_folds_bn_finalize(d); never run a kernel that ignores the fold
-    a.f = *d->in_fold;
-  }
+  if (d->in_fold != nullptr) a.f = *d->in_fold;
   a.d.in_fold = nullptr;
   a.store_pivot = folds && d->stats_out != nullptr && d->stats_mode == LVAE_STATS_BN_FWD;
   a.g_ws = nullptr;
@@ -1292,7 +1271,6 @@ static int conv3x3_wino_launch(const lvae_conv_desc* d, void* workspace, size_t 
   a.g_ab = a.g_out = a.g_stats = nullptr;
   a.g_act = 0;
   if (gate != nullptr) {
-    if (mt != 2) return -1000;
     a.g_ws = static_cast<const __bf16*>(gate->gate_ws);
     a.g_bias = gate->gate_bias;
     a.g_res = gate->res;
@@ -1316,7 +1294,7 @@ static int conv3x3_wino_launch(const lvae_conv_desc* d, void* workspace, size_t 
     }
     attr_set = true;
   }
-  float* U = static_cast<float*>(workspace);
+  float* U = static_cast<float*>(d->workspace);
   a.U = U;
   const int Npad = a.Npad;
   if (!d->workspace_ready) {
@@ -1336,6 +1314,10 @@ static int conv3x3_wino_launch(const lvae_conv_desc* d, void* workspace, size_t 
   return 0;
 }
 
+int conv3x3_wino_launch(const lvae_conv_desc* d, hipStream_t s) { return wino_launch(d, nullptr, s); }
+
+int conv3x3_wino2_gate_launch(const lvae_conv_desc* d, const lvae_rb_ext* gate, hipStream_t s) { return wino_launch(d, gate, s); }
+
 }  // namespace lvae
 
 using namespace lvae;
@@ -1347,12 +1329,13 @@ int conv3x3_bf16_form(const lvae_conv_desc* d);
 size_t conv3x3_bf16_workspace(const lvae_conv_desc* d, int split);
 void conv3x3_bf16_prep_entry(const lvae_conv_desc* d, int split, void* entry);
 int conv3x3_bf16_prepare_batched(const void* entries, int n, int npad, hipStream_t s);
-bool conv3x3_pos_eligible(const lvae_conv_desc* d);
+bool conv3x3_pos_plan(const lvae_conv_desc* d, ConvPlan& p);
 }  // namespace lvae
 
 extern "C" int lvae_conv2d_prepare_entry(const lvae_conv_desc* d, void* entry) {
   LVAE_REQUIRE(d && entry, LVAE_EINVAL, "lvae_conv2d_prepare_entry: null pointer");
-  if (!conv3x3_pos_eligible(d)) {
+  ConvPlan pos;
+  if (!conv3x3_pos_plan(d, pos)) {
     const int form = conv3x3_bf16_form(d);
     if (form != 0) {
       LVAE_REQUIRE(d->workspace && (size_t)d->workspace_bytes >= conv3x3_bf16_workspace(d, form) && al16w2(d->workspace), LVAE_EINVAL,

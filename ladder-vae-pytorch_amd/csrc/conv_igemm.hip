@@ -354,69 +354,65 @@ int conv_desc_check(const lvae_conv_desc* d, const char* who) {
   return 0;
 }
 
-int conv3x3_bf16_try(const lvae_conv_desc* d, int split, hipStream_t s);
-int conv3x3_bf16_stats_rows(const lvae_conv_desc* d, int split);
-int conv3x3_bf16_form(const lvae_conv_desc* d);
-size_t conv3x3_bf16_workspace(const lvae_conv_desc* d, int split);
-int conv3x3_pos_try(const lvae_conv_desc* d, hipStream_t s);
-int conv3x3_pos_stats_rows(const lvae_conv_desc* d);
-bool conv3x3_pos_eligible(const lvae_conv_desc* d);
-int conv3x3_halo_try(const lvae_conv_desc* d, hipStream_t s);
-int conv3x3_halo_stats_rows(const lvae_conv_desc* d);
-int conv3x3_wino_stats_rows(const lvae_conv_desc* d);
-int conv3x3_wino_try(const lvae_conv_desc* d, void* workspace, size_t workspace_bytes, hipStream_t s);
-size_t conv3x3_wino_workspace(const lvae_conv_desc* d);
-bool conv3x3_wino_eligible(const lvae_conv_desc* d);
-int conv1x1_try(const lvae_conv_desc* d, const float* gate_res, float* gate_out, int gate_act, hipStream_t s);
+bool conv3x3_pos_plan(const lvae_conv_desc* d, ConvPlan& p);
+int conv3x3_pos_launch(const lvae_conv_desc* d, hipStream_t s);
+bool conv3x3_bf16_plan(const lvae_conv_desc* d, bool assume_ws, ConvPlan& p);
+int conv3x3_bf16_launch(const lvae_conv_desc* d, const ConvPlan& p, hipStream_t s);
+bool conv3x3_wino_plan(const lvae_conv_desc* d, bool assume_ws, ConvPlan& p);
+int conv3x3_wino_launch(const lvae_conv_desc* d, hipStream_t s);
+bool conv3x3_halo_plan(const lvae_conv_desc* d, ConvPlan& p);
+int conv3x3_halo_launch(const lvae_conv_desc* d, hipStream_t s);
+bool conv1x1_plan(const lvae_conv_desc* d);
+int conv1x1_launch(const lvae_conv_desc* d, hipStream_t s);
 int conv1x1_gate_fwd_wgs(const lvae_conv_desc* d);
-int conv1x1_gate_fwd_try(const lvae_conv_desc* d, const float* res, float* out, int act, hipStream_t s);
-int conv1x1_try_ex(const lvae_conv_desc* d, const float* gate_res, float* gate_out, int gate_act, const float* gb_dout,
-                   const float* gb_ab, float* gb_dab, int gb_act, hipStream_t s);
+size_t conv3x3_wgrad_bf16_workspace(const lvae_conv_desc* d);
+size_t conv1x1_gate_bwd_fused_workspace(const lvae_conv_desc* d);
 
 static bool aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
+
+enum { ROUTE_POS, ROUTE_BF16, ROUTE_WINO, ROUTE_HALO, ROUTE_1X1, ROUTE_GENERIC };
+
+struct ConvRoute {
+  int kind = ROUTE_GENERIC;
+  ConvPlan plan;  // the generic kernel: LVAE_VARIANT_DIRECT, no statistics, no fold, no workspace
+};
+
+// The kernel of a forward / dgrad convolution, chosen once in the order pos -> bf16 direct -> Winograd -> halo -> 1x1 -> generic. Every
+// lvae_conv2d_* query and the launch read this. The choice is made on the descriptor without its in_fold (a kernel that folds the
+// BatchNorm finalize takes it; lvae_conv2d_f32 refuses it otherwise). assume_ws: answer for a sized, 16-byte aligned workspace instead of
+// d's own (lvae_conv2d_workspace).
+static ConvRoute conv_route(const lvae_conv_desc* d, bool assume_ws = false) {
+  static const bool halo_off = tune("LVAE_DISABLE_HALO", 0) != 0;  // A/B switch (tuning builds only): the generic kernel for everything
+  lvae_conv_desc t = *d;
+  t.in_fold = nullptr;
+  ConvRoute r;
+  if (halo_off) return r;
+  if (conv3x3_pos_plan(&t, r.plan)) r.kind = ROUTE_POS;
+  else if (conv3x3_bf16_plan(&t, assume_ws, r.plan)) r.kind = ROUTE_BF16;
+  else if (conv3x3_wino_plan(&t, assume_ws, r.plan)) r.kind = ROUTE_WINO;
+  else if (conv3x3_halo_plan(&t, r.plan)) r.kind = ROUTE_HALO;
+  else if (conv1x1_plan(&t)) r.kind = ROUTE_1X1;
+  return r;
+}
 
 }  // namespace lvae
 
 using namespace lvae;
 
-extern "C" size_t lvae_conv2d_workspace(const lvae_conv_desc* d) {
-  if (d == nullptr) return 0;
-  if (conv3x3_pos_eligible(d)) return 0;
-  const int form = conv3x3_bf16_form(d);
-  if (form != 0) return conv3x3_bf16_workspace(d, form);  // pre-split bf16 weight planes
-  return conv3x3_wino_eligible(d) ? conv3x3_wino_workspace(d) : 0;
-}
+extern "C" size_t lvae_conv2d_workspace(const lvae_conv_desc* d) { return d ? conv_route(d, true).plan.workspace : 0; }
 
-namespace lvae {
-int conv3x3_wino_variant(const lvae_conv_desc* d);
-bool conv3x3_wino_folds(const lvae_conv_desc* d);
-}
-
-extern "C" int32_t lvae_conv2d_variant(const lvae_conv_desc* d) {
-  if (d == nullptr || tune("LVAE_DISABLE_HALO", 0) != 0) return LVAE_VARIANT_DIRECT;
-  if (conv3x3_pos_eligible(d)) return LVAE_VARIANT_POS;
-  const int form = conv3x3_bf16_form(d);
-  if (form != 0 && d->workspace != nullptr && (size_t)d->workspace_bytes >= conv3x3_bf16_workspace(d, form))
-    return form == 1 ? LVAE_VARIANT_BF16_DIRECT : LVAE_VARIANT_SIX_DIRECT;
-  const int w = conv3x3_wino_variant(d);
-  return w ? w : LVAE_VARIANT_DIRECT;
-}
-
-namespace lvae {
-size_t conv3x3_wgrad_bf16_workspace(const lvae_conv_desc* d);
-size_t conv1x1_gate_bwd_fused_workspace(const lvae_conv_desc* d);
-}
+extern "C" int32_t lvae_conv2d_variant(const lvae_conv_desc* d) { return d ? conv_route(d).plan.variant : LVAE_VARIANT_DIRECT; }
 
 extern "C" int32_t lvae_resblock_bf16_storage(const lvae_conv_desc* d) {
   if (d == nullptr || d->precision != LVAE_PREC_BF16 || d->C1 != 64 || d->C2 != 0 || d->Cout != 64 || d->gather != LVAE_GATHER_CONV) return 0;
-  if (lvae_conv2d_variant(d) != LVAE_VARIANT_BF16_DIRECT) return 0;
   // the block's BatchNorm statistics / BatchNorm-backward sums must come out of the convolutions' own epilogues: the stand-alone
   // statistics kernels have no bf16-storage form
-  if (lvae_conv2d_stats_rows(d) <= 0) return 0;
+  const ConvPlan f = conv_route(d).plan;
+  if (f.variant != LVAE_VARIANT_BF16_DIRECT || f.rows <= 0) return 0;
   lvae_conv_desc t = *d;  // dgrad view of the same layer (same shape; only the gather differs for the kernel choice)
   t.gather = LVAE_GATHER_TRANSPOSED;
-  if (lvae_conv2d_variant(&t) != LVAE_VARIANT_BF16_DIRECT) return 0;
-  if (lvae_conv2d_stats_rows(&t) <= 0) return 0;
+  const ConvPlan b = conv_route(&t).plan;
+  if (b.variant != LVAE_VARIANT_BF16_DIRECT || b.rows <= 0) return 0;
   if (conv3x3_wgrad_bf16_workspace(d) == 0) return 0;
   lvae_conv_desc g = *d;  // the block's GateLayer2d: 1x1, 64 -> 128 forward; its fused backward is described by the 128 -> 64 dgrad view
   g.KH = g.KW = 1; g.pad = 0; g.Cout = 128; g.in_scale = g.in_shift = nullptr; g.out_scale = nullptr; g.in_act = g.out_act = 0; g.in_fold = nullptr;
@@ -426,73 +422,43 @@ extern "C" int32_t lvae_resblock_bf16_storage(const lvae_conv_desc* d) {
   return 1;
 }
 
-extern "C" int32_t lvae_conv2d_stats_rows(const lvae_conv_desc* d) {
-  if (d == nullptr || tune("LVAE_DISABLE_HALO", 0) != 0) return 0;
-  const int p = conv3x3_pos_stats_rows(d);
-  if (p > 0) return p;
-  const int form = conv3x3_bf16_form(d);
-  if (form != 0) return conv3x3_bf16_stats_rows(d, form);
-  const int w = conv3x3_wino_stats_rows(d);
-  if (w > 0) return w;
-  if (d->workspace != nullptr && conv3x3_wino_eligible(d) && (size_t)d->workspace_bytes >= conv3x3_wino_workspace(d)) return 0;
-  return conv3x3_halo_stats_rows(d);
-}
+extern "C" int32_t lvae_conv2d_stats_rows(const lvae_conv_desc* d) { return d ? conv_route(d).plan.rows : 0; }
 
-extern "C" int32_t lvae_conv2d_folds_bn_finalize(const lvae_conv_desc* d) {
-  if (d == nullptr || tune("LVAE_DISABLE_HALO", 0) != 0) return 0;
-  if (conv3x3_pos_eligible(d)) return 1;
-  const int v = lvae_conv2d_variant(d);
-  return (v == LVAE_VARIANT_WINO_F32 || v == LVAE_VARIANT_WINO_SIX) && conv3x3_wino_folds(d) ? 1 : 0;
-}
+extern "C" int32_t lvae_conv2d_folds_bn_finalize(const lvae_conv_desc* d) { return d && conv_route(d).plan.folds ? 1 : 0; }
 
 extern "C" int32_t lvae_conv2d_stats_buffer_rows(const lvae_conv_desc* d) {
   if (d == nullptr) return 0;
-  const int32_t rows = lvae_conv2d_stats_rows(d);
-  if (rows <= 0) return 0;
-  if (d->stats_mode != LVAE_STATS_BN_FWD) return rows;  // BatchNorm-backward sums have no pivot
-  lvae_conv_desc t = *d;  // the pivot row depends on the kernel choice, which is made on the descriptor without its fold
-  t.in_fold = nullptr;
-  return rows + (lvae_conv2d_folds_bn_finalize(&t) != 0 ? 1 : 0);
+  const ConvPlan p = conv_route(d).plan;
+  if (p.rows <= 0) return 0;
+  if (d->stats_mode != LVAE_STATS_BN_FWD) return p.rows;  // BatchNorm-backward sums have no pivot
+  return p.rows + (p.folds ? 1 : 0);
 }
 
 extern "C" int lvae_conv2d_f32(const lvae_conv_desc* d, void* stream) {
   int rc = conv_desc_check(d, "lvae_conv2d_f32");
   if (rc) return rc;
   LVAE_REQUIRE(d->y != nullptr, LVAE_EINVAL, "lvae_conv2d_f32: null y");
-  LVAE_REQUIRE(d->stats_out == nullptr || (d->stats_pivot != nullptr && lvae_conv2d_stats_rows(d) > 0), LVAE_EINVAL,
+  const ConvRoute r = conv_route(d);
+  LVAE_REQUIRE(d->stats_out == nullptr || (d->stats_pivot != nullptr && r.plan.rows > 0), LVAE_EINVAL,
                "lvae_conv2d_f32: stats_out set but lvae_conv2d_stats_rows(d) == 0 (this kernel variant has no statistics epilogue)");
   LVAE_REQUIRE(d->stats_out == nullptr || d->stats_mode == LVAE_STATS_BN_FWD ||
                    (d->stats_mode == LVAE_STATS_BN_BWD && d->stats_x != nullptr && (reinterpret_cast<uintptr_t>(d->stats_x) & 15) == 0),
                LVAE_EINVAL, "lvae_conv2d_f32: bad stats_mode / stats_x");
-  static const bool halo_off = tune("LVAE_DISABLE_HALO", 0) != 0;  // A/B switch (tuning builds only)
   LVAE_REQUIRE((d->x_dtype == LVAE_DT_F32 && d->y_dtype == LVAE_DT_F32 && d->stats_x_dtype == LVAE_DT_F32) ||
-                   lvae_conv2d_variant(d) == LVAE_VARIANT_BF16_DIRECT,
+                   r.plan.variant == LVAE_VARIANT_BF16_DIRECT,
                LVAE_EINVAL, "lvae_conv2d_f32: bf16-stored tensors need the bf16 3x3 kernel (precision LVAE_PREC_BF16, lvae_conv2d_variant(d) == "
                             "LVAE_VARIANT_BF16_DIRECT)");
-  if (d->in_fold != nullptr) {
-    lvae_conv_desc t = *d;  // the kernel choice is made on the descriptor without its fold (as the caller asked lvae_conv2d_folds_bn_finalize)
-    t.in_fold = nullptr;
-    LVAE_REQUIRE(lvae_conv2d_folds_bn_finalize(&t) != 0 && d->in_fold->parts != nullptr &&
-                     (reinterpret_cast<uintptr_t>(d->in_fold->parts) & 15) == 0 && d->C1 % 4 == 0 && d->in_fold->rows > 0 &&
-                     d->in_fold->M > 0 && d->in_scale == nullptr,
-                 LVAE_EINVAL,
-                 "lvae_conv2d_f32: in_fold set but lvae_conv2d_folds_bn_finalize(d) == 0 (or bad parts / rows / M, or in_scale given too)");
-  }
-  if (!halo_off) {
-    int hr = conv3x3_pos_try(d, (hipStream_t)stream);
-    if (hr != -1000) return hr;
-    const int form = conv3x3_bf16_form(d);
-    if (form != 0) {
-      hr = conv3x3_bf16_try(d, form, (hipStream_t)stream);
-      if (hr != -1000) return hr;
-    }
-    hr = conv3x3_wino_try(d, d->workspace, (size_t)d->workspace_bytes, (hipStream_t)stream);
-    if (hr != -1000) return hr;
-    LVAE_REQUIRE(d->in_fold == nullptr, LVAE_EINVAL, "lvae_conv2d_f32: no kernel took the folded BatchNorm finalize (in_fold)");
-    hr = conv3x3_halo_try(d, (hipStream_t)stream);
-    if (hr != -1000) return hr;
-    hr = conv1x1_try(d, nullptr, nullptr, 0, (hipStream_t)stream);
-    if (hr != -1000) return hr;
+  LVAE_REQUIRE(d->in_fold == nullptr || (r.plan.folds && d->in_fold->parts != nullptr && (reinterpret_cast<uintptr_t>(d->in_fold->parts) & 15) == 0 &&
+                                         d->C1 % 4 == 0 && d->in_fold->rows > 0 && d->in_fold->M > 0 && d->in_scale == nullptr),
+               LVAE_EINVAL,
+               "lvae_conv2d_f32: in_fold set but lvae_conv2d_folds_bn_finalize(d) == 0 (or bad parts / rows / M, or in_scale given too)");
+  hipStream_t s = (hipStream_t)stream;
+  switch (r.kind) {
+    case ROUTE_POS: return conv3x3_pos_launch(d, s);
+    case ROUTE_BF16: return conv3x3_bf16_launch(d, r.plan, s);
+    case ROUTE_WINO: return conv3x3_wino_launch(d, s);
+    case ROUTE_HALO: return conv3x3_halo_launch(d, s);
+    case ROUTE_1X1: return conv1x1_launch(d, s);
   }
   ConvArgs a;
   a.d = *d;
@@ -510,7 +476,6 @@ extern "C" int lvae_conv2d_f32(const lvae_conv_desc* d, void* stream) {
     a.cpt = 1;
     a.nchunks = (a.ktot + KC - 1) / KC;
   }
-  hipStream_t s = (hipStream_t)stream;
   const bool w16 = aligned16(d->w) && (d->w_stap % 4 == 0);
   if (!a_vec) return dispatch_tile<false, B_SCALAR>(a, s);
   if (d->w_sn == 1 && w16 && d->Cout % 4 == 0 && d->w_sk % 4 == 0) return dispatch_tile<true, B_NCONTIG>(a, s);
@@ -523,54 +488,4 @@ extern "C" int lvae_conv2d_bf16(const lvae_conv_desc* d, void* stream) {
   lvae_conv_desc dd = *d;
   dd.precision = LVAE_PREC_BF16;
   return lvae_conv2d_f32(&dd, stream);
-}
-
-// GateLayer2d forward fused with its 1x1 convolution and the residual add (lib/nn.py:118-126, 99):
-//   ab = conv1x1(T(x)) + bias  (written to d->y when non-null; needed by the backward)
-//   out[m, c] = act(ab[m, c]) * sigmoid(ab[m, C + c]) + res[m, c]
-// rows of BatchNorm partials ([rows][2][C], C = Cout/2) lvae_conv1x1_gate_f32 writes for its `out` when d->stats_out is set
-extern "C" int32_t lvae_conv1x1_gate_stats_rows(const lvae_conv_desc* d) {
-  if (d == nullptr || d->Cout % 8 != 0) return 0;
-  const int persistent = conv1x1_gate_fwd_wgs(d);  // one row per workgroup of the persistent kernel (conv1x1_gate_fwd.hip)
-  if (persistent) return persistent;
-  const int c4n = d->Cout / 8;
-  if (c4n <= 0 || 256 % c4n != 0 || d->Cout > 128) return 0;
-  return (int32_t)(((int64_t)d->N * d->H * d->W + 63) / 64);  // 64-pixel tiles
-}
-
-extern "C" int lvae_conv1x1_gate_f32(const lvae_conv_desc* d, const float* res, int32_t act, float* out, void* stream) {
-  int rc = conv_desc_check(d, "lvae_conv1x1_gate_f32");
-  if (rc) return rc;
-  LVAE_REQUIRE(out != nullptr, LVAE_EINVAL, "lvae_conv1x1_gate_f32: null out");
-  LVAE_REQUIRE(d->Cout % 2 == 0, LVAE_EINVAL, "lvae_conv1x1_gate_f32: Cout must be 2*C");
-  LVAE_REQUIRE(d->stats_out == nullptr || (d->stats_pivot != nullptr && lvae_conv1x1_gate_stats_rows(d) > 0 &&
-                                           (reinterpret_cast<uintptr_t>(d->stats_pivot) & 15) == 0),
-               LVAE_EINVAL, "lvae_conv1x1_gate_f32: stats_out set but lvae_conv1x1_gate_stats_rows(d) == 0");
-  rc = conv1x1_gate_fwd_try(d, res, out, act, (hipStream_t)stream);
-  LVAE_REQUIRE(rc != -1000 || (d->x_dtype == LVAE_DT_F32 && d->y_dtype == LVAE_DT_F32), LVAE_EINVAL,
-               "lvae_conv1x1_gate_f32: bf16-stored x / ab need the persistent 64-channel kernel with precision LVAE_PREC_BF16");
-  if (rc == -1000) rc = conv1x1_try(d, res, out, act, (hipStream_t)stream);
-  LVAE_REQUIRE(rc != -1000, LVAE_EINVAL,
-               "lvae_conv1x1_gate_f32: unsupported shape (needs a 1x1 stride-1 conv, Cin <= 128, Cout <= 128, channels %% 4 == 0, "
-               "16-byte aligned buffers); use lvae_conv2d_f32 + lvae_gate_fwd_f32");
-  return rc;
-}
-
-// GateLayer2d backward fused with the dgrad of its 1x1 convolution: dab (the gradient w.r.t. the pre-activations ab, also
-// written to `dab` for the weight-gradient call) is formed in the kernel's operand staging from dout and ab, then
-// dx = dab . W^T with the descriptor's epilogue (out_scale = Dropout2d mask of the producer). `d` describes that dgrad:
-// C1 = 2C, Cout = channels of the gate convolution's input, d->x is ignored.
-extern "C" int lvae_conv1x1_gate_bwd_f32(const lvae_conv_desc* d, const float* dout, const float* ab, int32_t act, float* dab,
-                                         void* stream) {
-  LVAE_REQUIRE(d && dout && ab && d->y, LVAE_EINVAL, "lvae_conv1x1_gate_bwd_f32: null pointer");
-  lvae_conv_desc dd = *d;
-  dd.x = ab;  // any valid, aligned device pointer: the A operand is computed, not loaded
-  int rc = conv_desc_check(&dd, "lvae_conv1x1_gate_bwd_f32");
-  if (rc) return rc;
-  LVAE_REQUIRE(dd.C1 % 8 == 0 && dd.C2 == 0, LVAE_EINVAL, "lvae_conv1x1_gate_bwd_f32: C1 must be 2C");
-  rc = conv1x1_try_ex(&dd, nullptr, nullptr, 0, dout, ab, dab, act, (hipStream_t)stream);
-  LVAE_REQUIRE(rc != -1000, LVAE_EINVAL,
-               "lvae_conv1x1_gate_bwd_f32: unsupported shape (needs a 1x1 stride-1 conv, 2C <= 128, Cout <= 128, 16-byte aligned "
-               "buffers); use lvae_gate_bwd_f32 + lvae_conv2d_f32");
-  return rc;
 }

@@ -390,17 +390,17 @@ size_t conv_wgrad_img_workspace(const lvae_conv_desc* d);
 int conv_wgrad_img_kind(const lvae_conv_desc* d);
 int conv_wgrad_img_grouped(const lvae_conv_desc* const* ds, const float* const* dy, float* const* dw, float* const* db,
                            void* const* workspace, int n, int kind, hipStream_t s);
-int conv_wgrad_img_try(const lvae_conv_desc* d, const float* dy, float* dw, float* db, void* workspace, hipStream_t s);
+int conv_wgrad_img_launch(const lvae_conv_desc* d, const float* dy, float* dw, float* db, void* workspace, hipStream_t s);
 size_t conv3x3_wgrad_bf16_workspace(const lvae_conv_desc* d);
-int conv3x3_wgrad_bf16_try(const lvae_conv_desc* d, const float* dy, float* dw, float* db, void* workspace, hipStream_t s);
+int conv3x3_wgrad_bf16_launch(const lvae_conv_desc* d, const float* dy, float* dw, float* db, void* workspace, hipStream_t s);
 int conv_wgrad_wino_grouped(const lvae_conv_desc* const* ds, const float* const* dy, float* const* dw, float* const* db,
                             void* const* workspace, int n, hipStream_t s);
 int conv_wgrad_tile_kind(const lvae_conv_desc* d);
 int conv_wgrad_tile_grouped(const lvae_conv_desc* const* ds, const float* const* dy, float* const* dw, float* const* db,
                             void* const* workspace, int n, int kind, hipStream_t s);
-int conv_wgrad_wino_try(const lvae_conv_desc* d, const float* dy, float* dw, float* db, void* workspace, hipStream_t s);
+int conv_wgrad_wino_launch(const lvae_conv_desc* d, const float* dy, float* dw, float* db, void* workspace, hipStream_t s);
 bool conv_wgrad_wino_apply_ok(const lvae_conv_desc* d);
-int conv_wgrad_wino_apply_try(const lvae_conv_desc* d, const lvae_bn_apply* ap, float* dw, float* db, void* workspace, hipStream_t s);
+int conv_wgrad_wino_apply_launch(const lvae_conv_desc* d, const lvae_bn_apply* ap, float* dw, float* db, void* workspace, hipStream_t s);
 
 // ---------------------------------------------------------------------------------------------------------
 // Weight gradient of the stem convolutions (5x5 stride 2 on the 1- or 3-channel image): the reduction dimension of the
@@ -479,9 +479,9 @@ static size_t thin_wgrad_workspace(const lvae_conv_desc* d) {
 }
 
 size_t conv1x1_wgrad_workspace(const lvae_conv_desc* d);
-int conv1x1_wgrad_try(const lvae_conv_desc* d, const float* dy, float* dw, float* db, void* workspace, hipStream_t s);
+int conv1x1_wgrad_launch(const lvae_conv_desc* d, const float* dy, float* dw, float* db, void* workspace, hipStream_t s);
 size_t conv_wgrad_tile_workspace(const lvae_conv_desc* d);
-int conv_wgrad_tile_try(const lvae_conv_desc* d, const float* dy, float* dw, float* db, void* workspace, hipStream_t s);
+int conv_wgrad_tile_launch(const lvae_conv_desc* d, const float* dy, float* dw, float* db, void* workspace, hipStream_t s);
 
 static void wgrad_plan(const lvae_conv_desc* d, int& ksplit, int& px_per_split, int& ncit, int& ncot) {
   const int Cin = d->C1 + d->C2, M = d->N * d->OH * d->OW, ntaps = d->KH * d->KW;
@@ -499,39 +499,43 @@ static void wgrad_plan(const lvae_conv_desc* d, int& ksplit, int& px_per_split, 
   ksplit = (M + px_per_split - 1) / px_per_split;
 }
 
+static bool al16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
+
+struct WgradRoute {
+  int32_t variant = LVAE_WGRAD_VARIANT_GENERIC;  // LVAE_WGRAD_VARIANT_*
+  size_t workspace = 0;                          // bytes the launch needs
+};
+
+// The kernel of a weight gradient, chosen once in the order img -> bf16 -> Winograd -> 1x1 -> tile -> thin -> generic for the alignment
+// of dy and of the workspace. Every lvae_conv2d_wgrad_* query and launch reads this; the queries, which see no dy, answer for 16-byte
+// aligned dy and workspace.
+static WgradRoute wgrad_route(const lvae_conv_desc* d, bool dy16, bool ws16) {
+  static const bool halo_off = tune("LVAE_DISABLE_HALO", 0) != 0;  // A/B switch (tuning builds only): the generic kernel for everything
+  WgradRoute r;
+  if (!halo_off) {
+    const bool al = dy16 && ws16;
+    if (al && (r.workspace = conv_wgrad_img_workspace(d))) r.variant = LVAE_WGRAD_VARIANT_IMG;   // fp32-stored operands of the <= 8x8 levels, either precision
+    else if (al && (r.workspace = conv3x3_wgrad_bf16_workspace(d))) r.variant = LVAE_WGRAD_VARIANT_BF16;   // precision = LVAE_PREC_BF16
+    else if (al && (r.workspace = conv_wgrad_wino_workspace(d))) r.variant = LVAE_WGRAD_VARIANT_WINO;
+    else if ((r.workspace = conv1x1_wgrad_workspace(d))) r.variant = LVAE_WGRAD_VARIANT_DIRECT_1X1;
+    else if (dy16 && (r.workspace = conv_wgrad_tile_workspace(d))) r.variant = LVAE_WGRAD_VARIANT_TILE;
+    else if ((r.workspace = thin_wgrad_workspace(d))) r.variant = LVAE_WGRAD_VARIANT_THIN;
+    if (r.workspace) return r;
+  }
+  int ksplit, pps, ncit, ncot;
+  wgrad_plan(d, ksplit, pps, ncit, ncot);
+  r.workspace = (size_t)ksplit * ((size_t)d->KH * d->KW * (d->C1 + d->C2) * d->Cout + d->Cout) * sizeof(float);
+  return r;
+}
+
 }  // namespace lvae
 
 using namespace lvae;
 
-extern "C" size_t lvae_conv2d_wgrad_workspace(const lvae_conv_desc* d) {
-  if (!d) return 0;
-  const size_t img = conv_wgrad_img_workspace(d);   // fp32-stored operands of the <= 8x8 levels, either precision
-  if (img) return img;
-  const size_t bf = conv3x3_wgrad_bf16_workspace(d);   // precision = LVAE_PREC_BF16 descriptors that have a bf16 weight-gradient kernel
-  if (bf) return bf;
-  const size_t wino = conv_wgrad_wino_workspace(d);
-  if (wino) return wino;
-  const size_t direct = conv1x1_wgrad_workspace(d);
-  if (direct) return direct;
-  const size_t halo = conv_wgrad_tile_workspace(d);
-  if (halo) return halo;
-  const size_t thin = thin_wgrad_workspace(d);
-  if (thin) return thin;
-  int ksplit, pps, ncit, ncot;
-  wgrad_plan(d, ksplit, pps, ncit, ncot);
-  const size_t per = (size_t)d->KH * d->KW * (d->C1 + d->C2) * d->Cout + d->Cout;
-  return (size_t)ksplit * per * sizeof(float);
-}
+extern "C" size_t lvae_conv2d_wgrad_workspace(const lvae_conv_desc* d) { return d ? wgrad_route(d, true, true).workspace : 0; }
 
 extern "C" int32_t lvae_conv2d_wgrad_variant(const lvae_conv_desc* d) {
-  if (!d) return LVAE_WGRAD_VARIANT_GENERIC;
-  if (conv_wgrad_img_workspace(d)) return LVAE_WGRAD_VARIANT_IMG;
-  if (conv3x3_wgrad_bf16_workspace(d)) return LVAE_WGRAD_VARIANT_BF16;
-  if (conv_wgrad_wino_workspace(d)) return LVAE_WGRAD_VARIANT_WINO;
-  if (conv1x1_wgrad_workspace(d)) return LVAE_WGRAD_VARIANT_DIRECT_1X1;
-  if (conv_wgrad_tile_workspace(d)) return LVAE_WGRAD_VARIANT_TILE;
-  if (thin_wgrad_workspace(d)) return LVAE_WGRAD_VARIANT_THIN;
-  return LVAE_WGRAD_VARIANT_GENERIC;
+  return d ? wgrad_route(d, true, true).variant : LVAE_WGRAD_VARIANT_GENERIC;
 }
 
 extern "C" int lvae_conv2d_wgrad_f32(const lvae_conv_desc* d, const float* dy, float* dw, float* db, void* workspace,
@@ -539,33 +543,23 @@ extern "C" int lvae_conv2d_wgrad_f32(const lvae_conv_desc* d, const float* dy, f
   int rc = conv_desc_check(d, "lvae_conv2d_wgrad_f32");
   if (rc) return rc;
   LVAE_REQUIRE(dy && dw && workspace, LVAE_EINVAL, "lvae_conv2d_wgrad_f32: null dy/dw/workspace");
-  LVAE_REQUIRE(workspace_bytes >= lvae_conv2d_wgrad_workspace(d), LVAE_EWORKSPACE,
-               "lvae_conv2d_wgrad_f32: workspace %zu < %zu", workspace_bytes, lvae_conv2d_wgrad_workspace(d));
-  static const bool halo_off = tune("LVAE_DISABLE_HALO", 0) != 0;
-  if (!halo_off && conv_wgrad_img_workspace(d)) {
-    const int hr = conv_wgrad_img_try(d, dy, dw, db, workspace, (hipStream_t)stream);
-    if (hr != -1000) return hr;
-  }
-  if (!halo_off && conv3x3_wgrad_bf16_workspace(d)) {
-    const int hr = conv3x3_wgrad_bf16_try(d, dy, dw, db, workspace, (hipStream_t)stream);
-    if (hr != -1000) return hr;
-  }
-  LVAE_REQUIRE(d->x_dtype == LVAE_DT_F32 && d->y_dtype == LVAE_DT_F32, LVAE_EINVAL,
+  const WgradRoute r = wgrad_route(d, al16(dy), al16(workspace));
+  LVAE_REQUIRE(workspace_bytes >= r.workspace, LVAE_EWORKSPACE,
+               "lvae_conv2d_wgrad_f32: workspace %zu < %zu (the kernel taken for this dy / workspace alignment; lvae_conv2d_wgrad_workspace "
+               "assumes 16-byte aligned ones)", workspace_bytes, r.workspace);
+  LVAE_REQUIRE((d->x_dtype == LVAE_DT_F32 && d->y_dtype == LVAE_DT_F32) || r.variant == LVAE_WGRAD_VARIANT_IMG || r.variant == LVAE_WGRAD_VARIANT_BF16,
+               LVAE_EINVAL,
                "lvae_conv2d_wgrad_f32: bf16-stored x / dy need the bf16 weight-gradient kernel, which does not take this shape "
                "(lvae_resblock_bf16_storage(d) == 0)");
-  if (!halo_off && conv_wgrad_wino_workspace(d)) {
-    const int hr = conv_wgrad_wino_try(d, dy, dw, db, workspace, (hipStream_t)stream);
-    if (hr != -1000) return hr;
+  hipStream_t s = (hipStream_t)stream;
+  switch (r.variant) {
+    case LVAE_WGRAD_VARIANT_IMG: return conv_wgrad_img_launch(d, dy, dw, db, workspace, s);
+    case LVAE_WGRAD_VARIANT_BF16: return conv3x3_wgrad_bf16_launch(d, dy, dw, db, workspace, s);
+    case LVAE_WGRAD_VARIANT_WINO: return conv_wgrad_wino_launch(d, dy, dw, db, workspace, s);
+    case LVAE_WGRAD_VARIANT_DIRECT_1X1: return conv1x1_wgrad_launch(d, dy, dw, db, workspace, s);
+    case LVAE_WGRAD_VARIANT_TILE: return conv_wgrad_tile_launch(d, dy, dw, db, workspace, s);
   }
-  if (!halo_off && conv1x1_wgrad_workspace(d)) {
-    const int hr = conv1x1_wgrad_try(d, dy, dw, db, workspace, (hipStream_t)stream);
-    if (hr != -1000) return hr;
-  }
-  if (!halo_off && conv_wgrad_tile_workspace(d)) {
-    const int hr = conv_wgrad_tile_try(d, dy, dw, db, workspace, (hipStream_t)stream);
-    if (hr != -1000) return hr;
-  }
-  if (!halo_off && thin_wgrad_workspace(d)) {
+  if (r.variant == LVAE_WGRAD_VARIANT_THIN) {
     ThinWgradArgs ta;
     ta.d = *d;
     ta.dy = dy;
@@ -581,9 +575,9 @@ extern "C" int lvae_conv2d_wgrad_f32(const lvae_conv_desc* d, const float* dy, f
       LVAE_REQUIRE(e == hipSuccess, (int)e, "conv_wgrad_thin: hipFuncSetAttribute failed: %s", hipGetErrorString(e));
       attr_set = true;
     }
-    hipLaunchKernelGGL(conv_wgrad_thin_kernel, dim3(d->N), dim3(256), lds, (hipStream_t)stream, ta);
+    hipLaunchKernelGGL(conv_wgrad_thin_kernel, dim3(d->N), dim3(256), lds, s, ta);
     LVAE_LAUNCH_CHECK("conv_wgrad_thin");
-    wgrad_reduce_launch(ta.slab_w, ta.slab_b, d->N, d->KH * d->KW, d->C1, d->Cout, d->w_stap, d->w_sk, d->w_sn, dw, db, (hipStream_t)stream);
+    wgrad_reduce_launch(ta.slab_w, ta.slab_b, d->N, d->KH * d->KW, d->C1, d->Cout, d->w_stap, d->w_sk, d->w_sn, dw, db, s);
     LVAE_LAUNCH_CHECK("conv2d_wgrad_reduce");
     return 0;
   }
@@ -597,11 +591,9 @@ extern "C" int lvae_conv2d_wgrad_f32(const lvae_conv_desc* d, const float* dy, f
   wgrad_plan(d, a.ksplit, a.px_per_split, a.ncit, a.ncot);
   a.slab_w = static_cast<float*>(workspace);
   a.slab_b = db ? a.slab_w + (size_t)a.ksplit * a.ntaps * a.Cin * d->Cout : nullptr;
-  auto al = [](const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; };
-  const bool xv = (d->C1 % 4 == 0) && (d->C2 % 4 == 0) && al(d->x) && (!d->x2 || al(d->x2)) &&
-                  (!d->in_scale || (al(d->in_scale) && al(d->in_shift)));
-  const bool yv = (d->Cout % 4 == 0) && al(dy);
-  hipStream_t s = (hipStream_t)stream;
+  const bool xv = (d->C1 % 4 == 0) && (d->C2 % 4 == 0) && al16(d->x) && (!d->x2 || al16(d->x2)) &&
+                  (!d->in_scale || (al16(d->in_scale) && al16(d->in_shift)));
+  const bool yv = (d->Cout % 4 == 0) && al16(dy);
   const int grid = a.ksplit * a.ncot * a.ncit * a.ntaps;
   if (xv && yv) hipLaunchKernelGGL((conv_wgrad_kernel<true, true>), dim3(grid), dim3(256), 0, s, a);
   else if (xv) hipLaunchKernelGGL((conv_wgrad_kernel<true, false>), dim3(grid), dim3(256), 0, s, a);
@@ -614,7 +606,7 @@ extern "C" int lvae_conv2d_wgrad_f32(const lvae_conv_desc* d, const float* dy, f
 }
 
 extern "C" int32_t lvae_conv2d_wgrad_apply_ok(const lvae_conv_desc* d) {
-  return d != nullptr && d->precision == LVAE_PREC_F32 && lvae_conv2d_wgrad_variant(d) == LVAE_WGRAD_VARIANT_WINO && conv_wgrad_wino_apply_ok(d) ? 1 : 0;
+  return d != nullptr && d->precision == LVAE_PREC_F32 && wgrad_route(d, true, true).variant == LVAE_WGRAD_VARIANT_WINO && conv_wgrad_wino_apply_ok(d) ? 1 : 0;
 }
 
 extern "C" int lvae_conv2d_wgrad_apply_f32(const lvae_conv_desc* d, const lvae_bn_apply* ap, float* dw, float* db, void* workspace,
@@ -629,9 +621,7 @@ extern "C" int lvae_conv2d_wgrad_apply_f32(const lvae_conv_desc* d, const lvae_b
                LVAE_EINVAL, "lvae_conv2d_wgrad_apply_f32: needs parts / rows, M = N*H*W, the coefficient block, fp32 dh, x and out, no add");
   LVAE_REQUIRE(workspace_bytes >= lvae_conv2d_wgrad_workspace(d), LVAE_EWORKSPACE, "lvae_conv2d_wgrad_apply_f32: workspace %zu < %zu", workspace_bytes,
                lvae_conv2d_wgrad_workspace(d));
-  rc = conv_wgrad_wino_apply_try(d, ap, dw, db, workspace, (hipStream_t)stream);
-  LVAE_REQUIRE(rc != -1000, LVAE_EALIGN, "lvae_conv2d_wgrad_apply_f32: buffers must be 16-byte aligned");
-  return rc;
+  return conv_wgrad_wino_apply_launch(d, ap, dw, db, workspace, (hipStream_t)stream);
 }
 
 extern "C" int lvae_conv2d_wgrad_bf16(const lvae_conv_desc* d, const float* dy, float* dw, float* db, void* workspace,
@@ -656,27 +646,28 @@ extern "C" int lvae_conv2d_wgrad_grouped_f32(const lvae_conv_desc* descs, const 
   LVAE_REQUIRE(descs && dy && dw && db && n > 0 && n <= 4096 && workspace, LVAE_EINVAL, "lvae_conv2d_wgrad_grouped_f32: bad arguments");
   LVAE_REQUIRE(workspace_bytes >= lvae_conv2d_wgrad_grouped_workspace(descs, n), LVAE_EWORKSPACE,
                "lvae_conv2d_wgrad_grouped_f32: workspace %zu < %zu", workspace_bytes, lvae_conv2d_wgrad_grouped_workspace(descs, n));
-  static const bool halo_off = tune("LVAE_DISABLE_HALO", 0) != 0;
   std::vector<void*> ws(n);
+  std::vector<size_t> wsb(n);
   std::vector<int> kind(n);
   char* wp = static_cast<char*>(workspace);
   for (int i = 0; i < n; ++i) {
-    int rc = conv_desc_check(&descs[i], "lvae_conv2d_wgrad_grouped_f32");
+    const lvae_conv_desc& d = descs[i];
+    int rc = conv_desc_check(&d, "lvae_conv2d_wgrad_grouped_f32");
     if (rc) return rc;
     LVAE_REQUIRE(dy[i] && dw[i], LVAE_EINVAL, "lvae_conv2d_wgrad_grouped_f32: null dy/dw at %d", i);
     ws[i] = wp;
-    wp += (lvae_conv2d_wgrad_workspace(&descs[i]) + 255) / 256 * 256;
-    const bool al = (reinterpret_cast<uintptr_t>(dy[i]) & 15) == 0;
-    const int img = !halo_off && al ? conv_wgrad_img_kind(&descs[i]) : -1;   // kinds 100 + ...: whole-image tiles (conv_wgrad_img.hip)
-    const bool bf16 = !halo_off && img < 0 && conv3x3_wgrad_bf16_workspace(&descs[i]) != 0;   // launched one by one (lvae_conv2d_wgrad_f32 below)
-    const bool wino = !halo_off && img < 0 && !bf16 && al && conv_wgrad_wino_workspace(&descs[i]) != 0;
-    const bool groupable = !halo_off && img < 0 && !wino && !bf16 && al && descs[i].Cout % 4 == 0 && (descs[i].C1 + descs[i].C2) % 4 == 0 &&
-                           conv1x1_wgrad_workspace(&descs[i]) == 0;
-    // kinds 0-4: tile kernel variants; 5-7: Winograd kernel for W = 8 / 16 / 32 (grouped only while one problem leaves CUs idle)
+    wsb[i] = (lvae_conv2d_wgrad_workspace(&d) + 255) / 256 * 256;
+    wp += wsb[i];
+    const WgradRoute r = wgrad_route(&d, al16(dy[i]), al16(ws[i]));
+    LVAE_REQUIRE(r.workspace <= wsb[i], LVAE_EWORKSPACE, "lvae_conv2d_wgrad_grouped_f32: entry %d needs %zu workspace bytes for its dy / workspace alignment, has %zu",
+                 i, r.workspace, wsb[i]);
+    // kinds 100 + ...: whole-image tiles (conv_wgrad_img.hip); 0-4: tile kernel variants; 5-7: Winograd kernel for W = 8 / 16 / 32 (grouped
+    // only while one problem leaves CUs idle); -1: launched one by one (lvae_conv2d_wgrad_f32 below)
     static const int64_t wino_group_max = tune("LVAE_WINO_GROUP_MAX_M", 65536);
-    kind[i] = img >= 0 ? 100 + img
-                       : (wino ? ((int64_t)descs[i].N * descs[i].H * descs[i].W < wino_group_max ? (descs[i].W == 8 ? 5 : (descs[i].W == 16 ? 6 : 7)) : -1)
-                               : (groupable ? conv_wgrad_tile_kind(&descs[i]) : -1));
+    kind[i] = -1;
+    if (r.variant == LVAE_WGRAD_VARIANT_IMG) kind[i] = 100 + conv_wgrad_img_kind(&d);
+    else if (r.variant == LVAE_WGRAD_VARIANT_WINO && (int64_t)d.N * d.H * d.W < wino_group_max) kind[i] = d.W == 8 ? 5 : (d.W == 16 ? 6 : 7);
+    else if (r.variant == LVAE_WGRAD_VARIANT_TILE && d.Cout % 4 == 0 && (d.C1 + d.C2) % 4 == 0) kind[i] = conv_wgrad_tile_kind(&d);
   }
   std::vector<char> done(n, 0);
   std::vector<int> kinds;   // the distinct kinds present, ascending
@@ -694,16 +685,18 @@ extern "C" int lvae_conv2d_wgrad_grouped_f32(const lvae_conv_desc* descs, const 
     int idx[kCap];
     int m = 0;
     auto flush = [&]() -> int {
-      if (m == 0) return 0;
+      if (m == 0 || (m == 1 && k < 100)) {   // (a lone tile / Winograd problem goes out one by one below; img: the same kernel)
+        m = 0;
+        return 0;
+      }
       int rc;
-      if (k >= 100) rc = conv_wgrad_img_grouped(gd, gy, gw, gb, gs, m, k - 100, (hipStream_t)stream);   // (one problem too: the same kernel)
-      else rc = m == 1 ? -1000
-                       : (k >= 5 ? conv_wgrad_wino_grouped(gd, gy, gw, gb, gs, m, (hipStream_t)stream)
-                                 : conv_wgrad_tile_grouped(gd, gy, gw, gb, gs, m, k, (hipStream_t)stream));
+      if (k >= 100) rc = conv_wgrad_img_grouped(gd, gy, gw, gb, gs, m, k - 100, (hipStream_t)stream);
+      else if (k >= 5) rc = conv_wgrad_wino_grouped(gd, gy, gw, gb, gs, m, (hipStream_t)stream);
+      else rc = conv_wgrad_tile_grouped(gd, gy, gw, gb, gs, m, k, (hipStream_t)stream);
       if (rc == 0)
         for (int j = 0; j < m; ++j) done[idx[j]] = 1;
       m = 0;
-      return rc == -1000 ? 0 : rc;
+      return rc;
     };
     for (int i = 0; i < n; ++i) {
       if (kind[i] != k) continue;
@@ -718,7 +711,7 @@ extern "C" int lvae_conv2d_wgrad_grouped_f32(const lvae_conv_desc* descs, const 
   }
   for (int i = 0; i < n; ++i) {
     if (done[i]) continue;
-    int rc = lvae_conv2d_wgrad_f32(&descs[i], dy[i], dw[i], db[i], ws[i], lvae_conv2d_wgrad_workspace(&descs[i]), stream);
+    int rc = lvae_conv2d_wgrad_f32(&descs[i], dy[i], dw[i], db[i], ws[i], wsb[i], stream);
     if (rc) return rc;
   }
   return 0;

@@ -336,8 +336,8 @@ static int wgi_launch_xv(const WgImgGroup& g, int n, int max_wgs, size_t lds, in
   }
 }
 
-// n <= kWgImgMax descriptors of one kind (conv_wgrad_img_kind), each with its own workspace: one launch + grouped fixed-order reduces.
-// Returns -1000 when a descriptor is not eligible.
+// n <= kWgImgMax descriptors of one kind (conv_wgrad_img_kind) whose route is this kernel (aligned dy and workspace), each with its own
+// workspace: one launch + grouped fixed-order reduces.
 int conv_wgrad_img_grouped(const lvae_conv_desc* const* ds, const float* const* dy, float* const* dw, float* const* db,
                            void* const* workspace, int n, int kind, hipStream_t s) {
   WgImgGroup g;
@@ -347,7 +347,7 @@ int conv_wgrad_img_grouped(const lvae_conv_desc* const* ds, const float* const* 
   const int split = (kind >> 1) & 1 ? 1 : 3;
   for (int i = 0; i < n; ++i) {
     WgImgProb& a = g.p[i];
-    if (wgi_plan(ds[i], a) != kind || !al16i(dy[i]) || !al16i(workspace[i])) return -1000;
+    wgi_plan(ds[i], a);
     const int ntap = ds[i]->KH * ds[i]->KW;
     a.x = ds[i]->x;
     a.dy = dy[i];
@@ -376,10 +376,8 @@ int conv_wgrad_img_grouped(const lvae_conv_desc* const* ds, const float* const* 
 }
 
 // one gradient: the grouped launch with one problem (the same kernel, tiling and summation order: bitwise equal to the grouped call)
-int conv_wgrad_img_try(const lvae_conv_desc* d, const float* dy, float* dw, float* db, void* workspace, hipStream_t s) {
-  const int kind = conv_wgrad_img_kind(d);
-  if (kind < 0) return -1000;
-  return conv_wgrad_img_grouped(&d, &dy, &dw, &db, &workspace, 1, kind, s);
+int conv_wgrad_img_launch(const lvae_conv_desc* d, const float* dy, float* dw, float* db, void* workspace, hipStream_t s) {
+  return conv_wgrad_img_grouped(&d, &dy, &dw, &db, &workspace, 1, conv_wgrad_img_kind(d), s);
 }
 
 }  // namespace lvae

@@ -807,7 +807,7 @@ size_t resblock_gate_ws_bytes(const lvae_conv_desc* d, int planes);
 void resblock_gate_prep_entry(const lvae_conv_desc* d, int planes, void* entry);
 int resblock_gate_prepare_single(const lvae_conv_desc* d, int planes, hipStream_t s);
 int conv3x3_wino2_gate_rows(const lvae_conv_desc* d);
-int conv3x3_wino2_gate_try(const lvae_conv_desc* d, const lvae_rb_ext* gate, hipStream_t s);
+int conv3x3_wino2_gate_launch(const lvae_conv_desc* d, const lvae_rb_ext* gate, hipStream_t s);
 
 // the 1x1 gate convolution in the direction it is used: 64 -> 128 (forward) or 128 -> 64 (backward)
 static bool rb_gate_ok(const lvae_conv_desc* g) {
@@ -989,9 +989,7 @@ extern "C" int lvae_resblock_conv_f32(const lvae_conv_desc* d, const lvae_rb_ext
       const int rc = resblock_gate_prepare_single(&g, 3, (hipStream_t)stream);
       if (rc) return rc;
     }
-    const int rc = conv3x3_wino2_gate_try(d, ext, (hipStream_t)stream);
-    LVAE_REQUIRE(rc != -1000, LVAE_EINVAL, "lvae_resblock_conv_f32: the Winograd kernel did not take the descriptor");
-    return rc;
+    return conv3x3_wino2_gate_launch(d, ext, (hipStream_t)stream);
   }
   const int split = rb_split(d);
   a.e = lvae_rb_ext{};

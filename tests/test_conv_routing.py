@@ -1,0 +1,153 @@
+"""Kernel routing of the convolution entry points, asked through the host-only queries (no GPU, no launch).
+
+Every query of a family (workspace, variant, statistics rows, folded BatchNorm finalize, bf16 storage, weight-gradient workspace /
+variant / apply) must answer for the kernel the launch takes. The table covers every convolution of the BASELINE configs at their
+batch sizes (forward, dgrad view, weight gradient) in both precisions and both forms, with the workspace absent, sized, too small and
+only 8-byte aligned, and both statistics modes. The descriptors carry fake, never-dereferenced pointers: this module never calls a
+launch entry point. Expected answers: conv_routing_expected.json next to this file.
+"""
+import ctypes as C
+import json
+import os
+
+HERE = os.path.dirname(os.path.abspath(__file__))
+EXPECTED = os.path.join(HERE, 'conv_routing_expected.json')
+
+PREC_F32, PREC_BF16 = 0, 1
+FORM_AUTO, FORM_SIX_PRODUCT_DIRECT = 0, 3
+GATHER_CONV, GATHER_TRANSPOSED = 0, 1
+STATS_BN_FWD, STATS_BN_BWD = 0, 1
+DT_BF16 = 1
+
+# (name, colour channels, image side, downsample flags, images per GPU): BASELINE configs[0], [1], [2] / [3] per GPU, [4] per GPU
+CONFIGS = [
+    ('mnist3', 1, 28, [1, 1, 1], 64),
+    ('mnist12', 1, 28, [0, 0, 0, 1, 0, 0, 1, 0, 0, 1, 0, 0], 256),
+    ('cifar15', 3, 32, [0, 0, 0, 0, 1, 0, 0, 0, 1, 0, 0, 0, 1, 0, 0], 256),
+    ('celeba20', 3, 64, [0, 0, 0, 0, 1, 0, 0, 0, 1, 0, 0, 0, 1, 0, 0, 0, 1, 0, 0, 0], 128),
+]
+NF, ZD = 64, 32   # n_filters, z_dims
+
+
+def _down(h):
+    return (h + 2 - 3) // 2 + 1   # 3x3 stride 2 pad 1
+
+
+def convs(color, img, downsample):
+    """(tag, Cin1, Cin2, Cout, k, stride, pad, transposed, H, W, OH, OW) of every distinct convolution of the model: 5x5 stride-2 stem,
+    residual-block 3x3, gate 1x1 (64 -> 128), merge 1x1 (64 + 64 -> 64), stochastic 3x3 (64 -> 2z, z -> 64), stride-2 3x3 and its
+    transposed up-sampling, and the likelihood head."""
+    out = set()
+    h = (img + 4 - 5) // 2 + 1
+    out.add(('stem', color, 0, NF, 5, 2, 2, False, img, img, h, h))
+    out.add(('head', NF, 0, 100 if color == 3 else 1, 3, 1, 1, False, img, img, img, img))
+    for ds in downsample:
+        if ds:
+            out.add(('down', NF, 0, NF, 3, 2, 1, False, h, h, _down(h), _down(h)))
+            out.add(('up', NF, 0, NF, 3, 2, 1, True, _down(h), _down(h), h, h))
+            h = _down(h)
+        for tag, c1, c2, co, k in (('res', NF, 0, NF, 3), ('gate', NF, 0, 2 * NF, 1), ('merge', NF, NF, NF, 1), ('q', NF, 0, 2 * ZD, 3),
+                                   ('z', ZD, 0, NF, 3)):
+            out.add((tag, c1, c2, co, k, 1, k // 2, False, h, h, h, h))
+    return sorted(out)
+
+
+_BASE = 1 << 32
+
+
+def _fake(i):
+    return _BASE + (i << 24)   # distinct, 256-byte aligned, never dereferenced
+
+
+def make_desc(N, H, W, OH, OW, C1, C2, Cout, k, stride, pad, gather, wsk, wsn, prec, form):
+    from lvae_amd._C import ConvDesc
+    d = ConvDesc()
+    d.x, d.x2, d.C1, d.C2 = _fake(1), (_fake(2) if C2 else None), C1, C2
+    d.w, d.w_stap, d.w_sk, d.w_sn = _fake(3), (C1 + C2) * Cout, wsk, wsn
+    d.bias, d.y = _fake(4), _fake(5)
+    d.N, d.H, d.W, d.OH, d.OW, d.Cout = N, H, W, OH, OW, Cout
+    d.KH = d.KW = k
+    d.stride, d.pad, d.gather, d.precision, d.form = stride, pad, gather, prec, form
+    return d
+
+
+def views(N, conv):
+    """(view, descriptor factory) pairs: the forward convolution and, for a plain convolution without a second source, its dgrad view"""
+    tag, C1, C2, Cout, k, s, p, tr, H, W, OH, OW = conv
+    g = GATHER_TRANSPOSED if tr else GATHER_CONV
+    out = [('fwd', lambda pr, fm: make_desc(N, H, W, OH, OW, C1, C2, Cout, k, s, p, g, Cout, 1, pr, fm))]
+    if not tr and C2 == 0:
+        out.append(('dgrad', lambda pr, fm: make_desc(N, OH, OW, H, W, Cout, 0, C1, k, s, p, GATHER_TRANSPOSED, 1, Cout, pr, fm)))
+    return out
+
+
+WS = ('none', 'sized', 'small', 'align8')
+STATS = (STATS_BN_FWD, STATS_BN_BWD)
+CONV_QUERIES = ('lvae_conv2d_workspace', 'lvae_conv2d_variant', 'lvae_conv2d_stats_rows', 'lvae_conv2d_folds_bn_finalize',
+                'lvae_conv2d_stats_buffer_rows', 'lvae_resblock_bf16_storage')
+WGRAD_QUERIES = ('lvae_conv2d_wgrad_workspace', 'lvae_conv2d_wgrad_variant', 'lvae_conv2d_wgrad_apply_ok')
+
+
+def variants(mk, need, bf16_storage):
+    """The descriptors of one convolution, in a fixed order: storage (fp32, then bf16 when asked) x workspace WS x statistics mode STATS"""
+    for st in ((False, True) if bf16_storage else (False,)):
+        for ws in WS:
+            for mode in STATS:
+                d = mk()
+                if st:
+                    d.x_dtype = d.y_dtype = DT_BF16
+                if ws != 'none':
+                    want = need if need else 4096
+                    d.workspace = _fake(6) + (8 if ws == 'align8' else 0)
+                    d.workspace_bytes = want // 2 if ws == 'small' else want
+                d.stats_out, d.stats_pivot, d.stats_mode = _fake(7), _fake(8), mode
+                if mode == STATS_BN_BWD:
+                    d.stats_x = _fake(9)
+                yield d
+
+
+def table():
+    """{case id: answers}. conv: one [workspace, variant, stats_rows, folds, stats_buffer_rows, bf16_storage] per descriptor of
+    variants(); wgrad: [workspace, variant, apply_ok]; grouped: the grouped workspace of all forward convolutions of a config."""
+    from lvae_amd import _C
+    lib = _C.load()
+    ask = lambda names, d: [int(getattr(lib, q)(C.byref(d))) for q in names]
+    out = {}
+    for cname, color, img, downsample, N in CONFIGS:
+        for prec in (PREC_F32, PREC_BF16):
+            for form in (FORM_AUTO, FORM_SIX_PRODUCT_DIRECT):
+                group = []
+                for conv in convs(color, img, downsample):
+                    for view, mk in views(N, conv):
+                        base = '%s/N%d/%s/%dx%d/%d+%d->%d/k%ds%dp%d%s/p%d/f%d' % (
+                            conv[0], N, view, conv[8], conv[9], conv[1], conv[2], conv[3], conv[4], conv[5], conv[6],
+                            't' if conv[7] else '', prec, form)
+                        m = lambda: mk(prec, form)
+                        if view == 'fwd':
+                            group.append(m())
+                            out['wgrad:' + base] = ask(WGRAD_QUERIES, m())
+                        need = lib.lvae_conv2d_workspace(C.byref(m()))
+                        bf16_storage = prec == PREC_BF16 and conv[0] == 'res'
+                        out['conv:' + base] = [ask(CONV_QUERIES, d) for d in variants(m, need, bf16_storage)]
+                arr = (_C.ConvDesc * len(group))(*group)
+                out['grouped:%s/p%d/f%d' % (cname, prec, form)] = int(lib.lvae_conv2d_wgrad_grouped_workspace(arr, len(group)))
+    return out
+
+
+def test_conv_routing_table():
+    import lvae_amd  # noqa: F401
+    with open(EXPECTED) as f:
+        expected = json.load(f)
+    got = table()
+    assert sorted(got) == sorted(expected)
+    bad = ['%s: got %s, expected %s' % (k, got[k], expected[k]) for k in sorted(got) if got[k] != expected[k]]
+    assert not bad, '%d of %d entries differ:\n%s' % (len(bad), len(got), '\n'.join(bad[:40]))
+
+
+if __name__ == '__main__':   # regenerate the expected answers from the current tree
+    import sys
+    sys.path.insert(0, os.path.dirname(HERE))
+    import lvae_amd  # noqa: F401
+    t = table()
+    with open(EXPECTED, 'w') as f:   # one case per line
+        f.write('{\n%s\n}\n' % ',\n'.join('%s: %s' % (json.dumps(k), json.dumps(t[k], separators=(',', ':'))) for k in sorted(t)))

@@ -909,6 +909,36 @@ def test_conv_wgrad_whole_image_tiles(K, case, prec):
     assert rel(db.cpu() - db0, dy.double().sum((0, 2, 3)).float()) < 3e-6   # the bias gradient sums the unrounded dy
 
 
+def test_conv_wgrad_misaligned_dy_needs_the_workspace_of_its_own_kernel(K):
+    """lvae_conv2d_wgrad_workspace answers for 16-byte aligned dy and workspace: at 256x8x8, 64 -> 64 that is the whole-image kernel. With
+    dy offset by one float the launch takes the generic kernel, whose slabs need more: given the query's bytes it returns LVAE_EWORKSPACE
+    instead of writing past them. The same call with an aligned dy runs (and is checked against the float64 gradient)."""
+    N, C, H, W = 256, 64, 8, 8
+    g = torch.Generator().manual_seed(11)
+    x = torch.randn(N, C, H, W, generator=g)
+    dy = torch.randn(N, C, H, W, generator=g)
+    w = packed_weight(torch.randn(C, C, 3, 3, generator=g) / 24)
+    geom = K.ConvGeom(w, 1, 1)
+    d = K._desc(geom, w, nhwc(x), None, N, H, W, H, W, C, geom.s_ci, geom.s_co, K.GATHER_CONV)
+    lib, C_ = K._C.load(), K._C
+    need = lib.lvae_conv2d_wgrad_workspace(ctypes.byref(d))
+    assert lib.lvae_conv2d_wgrad_variant(ctypes.byref(d)) == C_.WGRAD_VARIANT_IMG
+    ws = torch.empty(max(need, 64 * (9 * C * C + C) * 4), dtype=torch.uint8, device='cuda')   # >= the generic kernel's slabs (ksplit <= 64)
+    store = torch.empty(N * H * W * C + 4, device='cuda')
+    dw, db = torch.zeros_like(w), torch.zeros(C, device='cuda')
+    dy_off = store[1:1 + dy.numel()].view(N, H, W, C)
+    dy_off.copy_(nhwc(dy))
+    with pytest.raises(C_.LvaeHipError, match=r'\(-3\)'):
+        C_.call('lvae_conv2d_wgrad_f32', ctypes.byref(d), C_.ptr(dy_off), C_.ptr(dw), C_.ptr(db), ws.data_ptr(), need, C_.stream_ptr())
+    dy_al = store[4:4 + dy.numel()].view(N, H, W, C)
+    dy_al.copy_(nhwc(dy))
+    C_.call('lvae_conv2d_wgrad_f32', ctypes.byref(d), C_.ptr(dy_al), C_.ptr(dw), C_.ptr(db), ws.data_ptr(), need, C_.stream_ptr())
+    torch.cuda.synchronize()
+    ref = torch.nn.grad.conv2d_weight(x.double(), (C, C, 3, 3), dy.double(), padding=1)
+    assert rel(dw.cpu(), ref.float()) < 3e-6
+    assert rel(db.cpu(), dy.double().sum((0, 2, 3)).float()) < 3e-6
+
+
 @pytest.mark.parametrize('shape', [(256, 16, 16), (70, 16, 16), (130, 16, 16), (64, 32, 32), (19, 32, 32)])
 def test_weight_gradient_that_absorbs_the_batchnorm_apply_in_front_of_it(K, shape):
     """lvae_conv2d_wgrad_apply_f32 == lvae_affine_act_bwd_parts_f32 followed by lvae_conv2d_wgrad_f32: the stored dy (to 1e-6: the partial rows
