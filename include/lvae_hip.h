@@ -32,7 +32,7 @@
 extern "C" {
 #endif
 
-#define LVAE_ABI_VERSION 16
+#define LVAE_ABI_VERSION 17
 
 #define LVAE_EINVAL (-1)   /* bad argument (null pointer, non-positive size, unsupported combination) */
 #define LVAE_EALIGN (-2)   /* pointer / channel count not aligned as the vector path requires */
@@ -555,6 +555,13 @@ int lvae_kl_bookkeeping_bwd_f32(const float* kl, int32_t L, int32_t N, float fre
 int lvae_elbo_loss_fwd_f32(const float* ll, const float* kl_sep, const float* kl_loss, float beta, int32_t N,
                            float* elbo_sep, float* scalars, void* stream);
 int lvae_elbo_loss_bwd_f32(const float* g_loss, float beta, int32_t N, float* d_ll, float* d_kl_loss, void* stream);
+/* The same pair with beta = linear_anneal(step[0], 0, 1, anneal_steps) read on the device (KL warm-up, experiment_manager.py:340-342):
+ * min(max(step / anneal_steps, 0), 1) in double, rounded to float once; 1 when anneal_steps <= 0. step: device int64[1], the number of
+ * completed training steps (advanced with lvae_counter_advance, so a captured step replays with a moving beta). */
+int lvae_elbo_loss_fwd_anneal_f32(const float* ll, const float* kl_sep, const float* kl_loss, const int64_t* step, int64_t anneal_steps,
+                                  int32_t N, float* elbo_sep, float* scalars, void* stream);
+int lvae_elbo_loss_bwd_anneal_f32(const float* g_loss, const int64_t* step, int64_t anneal_steps, int32_t N, float* d_ll,
+                                  float* d_kl_loss, void* stream);
 
 /* Importance-weighted bound — evaluate.py:30,86-87 (the loop is boilr's test_procedure: S forward passes, then
  * logsumexp - log S). elbo [S,N] (sample-major) -> out[n] = log mean_s exp(elbo[s][n]). */
@@ -563,6 +570,14 @@ int lvae_iw_logmeanexp_f32(const float* elbo, int32_t S, int32_t N, float* out, 
  * state [3][N] = running max, sum of exp(elbo - max), plain sum. mode 0: initialise; mode 1: fold in elbo [N]; mode 2: iw[n] = max +
  * log(sumexp) - log S and mean[n] = sum / S. */
 int lvae_iw_online_f32(const float* elbo, float* state, int32_t N, int32_t mode, int32_t S, float* iw, float* mean, void* stream);
+/* Test-pass metrics. lvae_eval_online_f32 keeps per-image double state [5*N + L] across the S samples of a batch: running max and
+ * sum of exp of elbo_sep, sums of elbo_sep, -ll and kl_sep, and the per-layer KL summed over the batch (kl_avg_layerwise * N).
+ * mode 0: initialise; mode 1: fold in one sample. lvae_eval_totals_f64 adds the finished batch to totals [5 + L] (double):
+ * sum of IW bounds, ELBO, recons, KL (each image's mean over the samples), image count, per-layer KL; one workgroup in a fixed
+ * order, so totals are reproducible bit for bit. */
+int lvae_eval_online_f32(const float* elbo_sep, const float* ll, const float* kl_sep, const float* kl_avg_layerwise, double* state,
+                         int32_t N, int32_t L, int32_t mode, void* stream);
+int lvae_eval_totals_f64(const double* state, int32_t N, int32_t L, int32_t S, double* totals, void* stream);
 
 /* ------------------------------------------------------------------------------------------------------------
  * Optimiser and norms over the flat parameter arena — torch.optim.Adamax at experiment_manager.py:76-81 and the

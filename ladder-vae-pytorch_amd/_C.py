@@ -70,7 +70,7 @@ class RbExt(C.Structure):
 RB_PRO_AFFINE, RB_PRO_BN_APPLY, RB_PRO_GATE_BWD = 0, 1, 2
 RB_EPI_PLAIN, RB_EPI_GATE = 0, 1
 
-ABI_VERSION = 16  # LVAE_ABI_VERSION of include/lvae_hip.h
+ABI_VERSION = 17  # LVAE_ABI_VERSION of include/lvae_hip.h
 
 _P, _I, _L, _F, _Z, _U = C.c_void_p, C.c_int32, C.c_int64, C.c_float, C.c_size_t, C.c_uint64
 
@@ -143,7 +143,11 @@ SIGNATURES = {
     'lvae_kl_bookkeeping_bwd_f32': (C.c_int, [_P, _I, _I, _F, _P, _P, _P, _P, _P]),
     'lvae_elbo_loss_fwd_f32': (C.c_int, [_P, _P, _P, _F, _I, _P, _P, _P]),
     'lvae_elbo_loss_bwd_f32': (C.c_int, [_P, _F, _I, _P, _P, _P]),
+    'lvae_elbo_loss_fwd_anneal_f32': (C.c_int, [_P, _P, _P, _P, _L, _I, _P, _P, _P]),
+    'lvae_elbo_loss_bwd_anneal_f32': (C.c_int, [_P, _P, _L, _I, _P, _P, _P]),
     'lvae_iw_online_f32': (C.c_int, [_P, _P, _I, _I, _I, _P, _P, _P]),
+    'lvae_eval_online_f32': (C.c_int, [_P, _P, _P, _P, _P, _I, _I, _I, _P]),
+    'lvae_eval_totals_f64': (C.c_int, [_P, _I, _I, _I, _P, _P]),
     'lvae_iw_logmeanexp_f32': (C.c_int, [_P, _I, _I, _P, _P]),
     'lvae_adamax_step_f32': (C.c_int, [_P, _P, _P, _P, _P, _L, _F, _F, _F, _F, _F, _P, _P, _P]),
     'lvae_sumsq_workspace': (_Z, [_L]),

@@ -32,20 +32,45 @@ def optimizer_state_by_name(model, optimizer):
             'eps': optimizer.eps, 'weight_decay': optimizer.weight_decay}
 
 
+def noise_state(model):
+    """{'seed', 'step'} of the model's on-device Philox stream (None for any other noise source)."""
+    from .noise import PhiloxNoise
+    nz = getattr(model, 'noise', None)
+    if not isinstance(nz, PhiloxNoise):
+        return None
+    return {'seed': int(nz.seed), 'step': int(nz.step.item()) if nz.step is not None else 0}
+
+
 def save_checkpoint(path, model, optimizer=None):
+    """Weights (reference layout), global step, Adamax state and the position of the Philox noise stream, so that a resumed run continues
+    the original one bit for bit."""
     ck = {'model': state_dict_reference_layout(model), 'global_step': int(model.global_step)}
     if optimizer is not None:
         ck['optimizer'] = optimizer_state_by_name(model, optimizer)
+    nz = noise_state(model)
+    if nz is not None:
+        ck['noise'] = nz
+    if getattr(model, 'global_step_dev', None) is not None:
+        ck['global_step_dev'] = int(model.global_step_dev.item())
     torch.save(ck, path)
 
 
 def load_checkpoint(path, model, optimizer=None):
-    """Loads a file written by `save_checkpoint`, or a bare reference `state_dict` file."""
+    """Loads a file written by `save_checkpoint` (with the noise stream's position and the device global-step counter when it holds
+    them), or a bare reference `state_dict` file. Load before a TrainStep captures its graph: the graph keeps the counters it saw."""
     ck = torch.load(path, map_location='cpu')
     sd = ck['model'] if isinstance(ck, dict) and 'model' in ck else ck
     model.load_state_dict(sd)
-    if isinstance(ck, dict):
+    if isinstance(ck, dict) and 'model' in ck:
         model.global_step = int(ck.get('global_step', model.global_step))
+        from .noise import PhiloxNoise
+        if 'noise' in ck and isinstance(getattr(model, 'noise', None), PhiloxNoise):
+            dev = next(model.parameters()).device
+            model.noise.seed = int(ck['noise']['seed'])
+            model.noise.step = torch.full((1,), int(ck['noise']['step']), dtype=torch.int64, device=dev)
+        if getattr(model, 'global_step_dev', None) is not None or 'global_step_dev' in ck:
+            dev = next(model.parameters()).device
+            model.global_step_dev = torch.full((1,), int(ck.get('global_step_dev', model.global_step)), dtype=torch.int64, device=dev)
     if optimizer is not None and isinstance(ck, dict) and 'optimizer' in ck:
         arena = model.pack()
         optimizer._state()

@@ -197,6 +197,43 @@ __global__ __launch_bounds__(256) void elbo_loss_bwd_kernel(const float* g_loss,
   if (blockIdx.x == 0 && threadIdx.x == 0) d_kl_loss[0] = g * beta;
 }
 
+// The same loss with beta = linear_anneal(step[0], 0, 1, anneal_steps) read on the device (KL warm-up, experiment_manager.py:340-342), so
+// that a captured step replays with the beta of the step it runs. Evaluated in double and rounded once, as the host computes it.
+__device__ __forceinline__ float anneal_beta(const int64_t* step, int64_t anneal_steps) {
+  if (anneal_steps <= 0) return 1.f;
+  const double r = fmin(fmax((double)step[0] / (double)anneal_steps, 0.0), 1.0);
+  return (float)(0.0 + (1.0 - 0.0) * r);
+}
+
+__global__ __launch_bounds__(256) void elbo_loss_fwd_anneal_kernel(const float* __restrict__ ll, const float* __restrict__ kl_sep,
+                                                                    const float* kl_loss, const int64_t* step, int64_t anneal_steps,
+                                                                    int N, float* elbo_sep, float* scalars) {
+  __shared__ float red[4];
+  const int t = threadIdx.x;
+  float sl = 0.f, se = 0.f;
+  for (int n = t; n < N; n += 256) {
+    const float e = -(-ll[n] + kl_sep[n]);
+    elbo_sep[n] = e;
+    se += e;
+    sl += -ll[n];
+  }
+  sl = block_sum_256(sl, red);
+  se = block_sum_256(se, red);
+  if (t == 0) {
+    const float recons = sl / (float)N;
+    scalars[0] = recons + kl_loss[0] * anneal_beta(step, anneal_steps);
+    scalars[1] = se / (float)N;
+    scalars[2] = recons;
+  }
+}
+
+__global__ __launch_bounds__(256) void elbo_loss_bwd_anneal_kernel(const float* g_loss, const int64_t* step, int64_t anneal_steps,
+                                                                    int N, float* d_ll, float* d_kl_loss) {
+  const float g = g_loss[0];
+  for (int n = blockIdx.x * 256 + threadIdx.x; n < N; n += gridDim.x * 256) d_ll[n] = -g / (float)N;
+  if (blockIdx.x == 0 && threadIdx.x == 0) d_kl_loss[0] = g * anneal_beta(step, anneal_steps);
+}
+
 // importance-weighted bound: out[n] = logsumexp_s elbo[s][n] - log S   (evaluate.py / boilr test_procedure, restated)
 __global__ __launch_bounds__(256) void iw_logmeanexp_kernel(const float* __restrict__ elbo, int S, int N, float* out) {
   const int n = blockIdx.x * 256 + threadIdx.x;
@@ -400,6 +437,24 @@ extern "C" int lvae_elbo_loss_bwd_f32(const float* g_loss, float beta, int32_t N
   hipLaunchKernelGGL(elbo_loss_bwd_kernel, dim3(grid_for(N, 256)), dim3(256), 0, (hipStream_t)stream, g_loss, beta, N, d_ll,
                      d_kl_loss);
   LVAE_LAUNCH_CHECK("elbo_loss_bwd");
+  return 0;
+}
+
+extern "C" int lvae_elbo_loss_fwd_anneal_f32(const float* ll, const float* kl_sep, const float* kl_loss, const int64_t* step,
+                                             int64_t anneal_steps, int32_t N, float* elbo_sep, float* scalars, void* stream) {
+  LVAE_REQUIRE(ll && kl_sep && kl_loss && step && elbo_sep && scalars && N > 0, LVAE_EINVAL, "lvae_elbo_loss_fwd_anneal_f32: bad args");
+  hipLaunchKernelGGL(elbo_loss_fwd_anneal_kernel, dim3(1), dim3(256), 0, (hipStream_t)stream, ll, kl_sep, kl_loss, step, anneal_steps,
+                     N, elbo_sep, scalars);
+  LVAE_LAUNCH_CHECK("elbo_loss_fwd_anneal");
+  return 0;
+}
+
+extern "C" int lvae_elbo_loss_bwd_anneal_f32(const float* g_loss, const int64_t* step, int64_t anneal_steps, int32_t N, float* d_ll,
+                                             float* d_kl_loss, void* stream) {
+  LVAE_REQUIRE(g_loss && step && d_ll && d_kl_loss && N > 0, LVAE_EINVAL, "lvae_elbo_loss_bwd_anneal_f32: bad args");
+  hipLaunchKernelGGL(elbo_loss_bwd_anneal_kernel, dim3(grid_for(N, 256)), dim3(256), 0, (hipStream_t)stream, g_loss, step,
+                     anneal_steps, N, d_ll, d_kl_loss);
+  LVAE_LAUNCH_CHECK("elbo_loss_bwd_anneal");
   return 0;
 }
 

@@ -24,10 +24,26 @@ def linear_anneal(step, start, end, steps):
     return start + (end - start) * min(max(step / float(steps), 0.0), 1.0)
 
 
-def forward_pass(model, x, beta=1.0, compute_l2=True):
-    """LVAEExperiment.forward_pass (experiment/experiment_manager.py:322-367) on the HIP engine."""
+def global_step_counter(model):
+    """The device int64[1] mirror of `model.global_step` that the annealed loss reads (created on first use, then advanced on the device
+    by every annealed training step, inside its graph)."""
+    dev = next(model.parameters()).device
+    c = getattr(model, 'global_step_dev', None)
+    if c is None or c.device != dev:
+        c = torch.full((1,), int(model.global_step), dtype=torch.int64, device=dev)
+        model.global_step_dev = c
+    return c
+
+
+def forward_pass(model, x, beta=1.0, compute_l2=True, beta_anneal=0):
+    """LVAEExperiment.forward_pass (experiment/experiment_manager.py:322-367) on the HIP engine. beta_anneal != 0: the KL warm-up,
+    beta = linear_anneal(global step, 0, 1, beta_anneal) read on the device from `global_step_counter(model)` (`beta` is ignored)."""
     mo = model(x)
-    elbo_sep, loss, elbo, recons = ops.ElboLossFn.apply(mo['ll'], mo['kl_sep'], mo['kl_loss'], float(beta))
+    if beta_anneal:
+        elbo_sep, loss, elbo, recons = ops.ElboLossAnnealFn.apply(mo['ll'], mo['kl_sep'], mo['kl_loss'], global_step_counter(model),
+                                                                  int(beta_anneal))
+    else:
+        elbo_sep, loss, elbo, recons = ops.ElboLossFn.apply(mo['ll'], mo['kl_sep'], mo['kl_loss'], float(beta))
     out = {'loss': loss, 'elbo': elbo, 'elbo_sep': elbo_sep, 'kl': mo['kl'], 'recons': recons,
            'out_mean': mo['out_mean'], 'out_mode': mo['out_mode'], 'out_sample': mo['out_sample'],
            'likelihood_params': mo['likelihood_params'], 'kl_avg_layerwise': mo['kl_avg_layerwise']}
@@ -41,8 +57,9 @@ class TrainStep:
     """step(x) -> dict of scalars (device tensors, valid until the next step)."""
 
     def __init__(self, model, optimizer, beta=1.0, use_graph=True, allreduce=None, eager_warmup=2, async_wgrad=False,
-                 wgrad_streams=1, wgrad_group_rows=16384):
+                 wgrad_streams=1, wgrad_group_rows=16384, beta_anneal=0):
         self.model, self.opt, self.beta = model, optimizer, beta
+        self.beta_anneal = int(beta_anneal)   # != 0: KL warm-up on the device counter (beta is then ignored)
         dev = next(model.parameters()).device
         self.side = [torch.cuda.Stream(device=dev) for _ in range(max(1, int(wgrad_streams)))] if async_wgrad else None
         self.use_graph, self.allreduce = use_graph, allreduce
@@ -78,7 +95,7 @@ class TrainStep:
         try:
             self.opt.zero_grad()
             K.prepared.prepare_all()  # one launch: transformed weights of every Winograd convolution seen so far
-            out = forward_pass(self.model, x, self.beta)
+            out = forward_pass(self.model, x, self.beta, beta_anneal=self.beta_anneal)
             if self.allreduce is not None:
                 self.allreduce.begin_step()
             ops.set_wgrad_stream(self.side)
@@ -91,6 +108,8 @@ class TrainStep:
             ops.join_wgrad_stream()
             if self.overlap:
                 self.allreduce.finish()  # last bucket + join: the gradients are summed over ranks from here on
+            if self.beta_anneal:
+                K.counter_advance(global_step_counter(self.model), 1)   # the next step's beta; inside the graph when captured
             done = True
         finally:
             if not done:
@@ -180,6 +199,8 @@ class TrainStep:
         return self.static_out
 
     def __call__(self, x):
+        if self.beta_anneal:
+            global_step_counter(self.model)   # (created before this step is counted: it holds the number of COMPLETED steps)
         self.model.global_step += 1
         if not self.use_graph or self.eager_left > 0:
             self.eager_left -= 1

@@ -5,6 +5,8 @@ the absent boilr.eval.BaseOfflineEvaluator / VAEExperimentManager.test_procedure
     In eval mode the bottom-up pass has no noise, so it is run ONCE per batch and only top-down + likelihood are
     replayed S times (saves the 26.5 % bottom-up share of forward FLOPs per extra sample, SURVEY.md §8d);
   * `evaluate(model, batches, S, world)` — mean ELBO / IW bound over a data set, sharded over ranks, one all-reduce;
+  * `test_pass(model, batches, S)` — the reference's test summaries (ELBO, recons, KL, per-layer KL, IW bound), folded on the device
+    into double totals, on a noise stream of its own: the trainer's test / log-likelihood pass, which leaves training untouched;
   * `prior_samples(model, n)` and `inspect_layer_repr(model, n)` — evaluate.py:34-45, 95-114 (arrays instead of PNG grids).
 
 CLI: python -m lvae_amd.evaluate --synthetic --ll --ll-samples 100 --ps  <model flags of main.py>
@@ -80,7 +82,8 @@ def iw_log_likelihood(model, x, n_samples, use_graph=None):
 
 
 def reduce_eval_sums(tot, process_group=None):
-    """[sum of IW bounds, sum of ELBOs, image count] of this rank's shard -> totals over all ranks (one all-reduce)."""
+    """Per-rank sums of this rank's shard ([sum of IW bounds, sum of ELBOs, image count], or test_pass's totals) -> totals over all
+    ranks (one all-reduce)."""
     if torch.distributed.is_initialized() and torch.distributed.get_world_size(process_group) > 1:
         torch.distributed.all_reduce(tot, group=process_group)
     return tot
@@ -98,6 +101,160 @@ def evaluate(model, batches, n_samples, process_group=None):
     tot = reduce_eval_sums(tot, process_group)
     n = float(tot[2])
     return {'elbo/elbo': float(tot[1]) / n, 'elbo/elbo_IW_%d' % n_samples: float(tot[0]) / n, 'n_images': int(n)}
+
+
+class _EvalWeights:
+    """Context of a test pass: every convolution transforms its own weights (the transformed-weight table pinned by a captured training
+    step, and the stamps of its entries, are left exactly as they were), and entries the pass registered are taken out of the table again.
+    Their scratch buffers go to `keep`: an evaluation graph captured meanwhile holds their addresses."""
+
+    def __init__(self, keep):
+        self.keep = keep
+
+    def __enter__(self):
+        P = K.prepared
+        self.saved = (dict(P.entries), P.table, P.enabled)
+        P.enabled = False
+        return self
+
+    def __exit__(self, *exc):
+        P = K.prepared
+        entries, table, enabled = self.saved
+        self.keep.extend(e['U'] for k, e in P.entries.items() if entries.get(k) is not e)
+        P.entries, P.table, P.enabled = entries, table, enabled
+        return False
+
+
+def _test_bottom_up(model, x):
+    """Eval-mode bottom-up of one NCHW batch (no noise drawn) -> (bottom-up values, NHWC image for the likelihood)."""
+    model._begin(x)
+    img_size = tuple(int(s) for s in x.shape[2:])
+    x_pad = K.pad_crop(x, True, model.get_padded_size(x.size()), False)
+    x_nhwc = x_pad if img_size == tuple(x_pad.shape[1:3]) else K.pad_crop(x, True, img_size, False)
+    bu_values = model._bottomup(x_pad)
+    model.noise.end()
+    return bu_values, x_nhwc
+
+
+def _test_sample(model, bu_values, x_nhwc, state, zero):
+    """One top-down sample + likelihood + KL bookkeeping, folded into the per-image state (lvae_eval_online_f32)."""
+    model.noise.begin(x_nhwc.device)
+    out, td = model._topdown(bu_values)
+    if tuple(out.shape[1:3]) != tuple(x_nhwc.shape[1:3]):
+        out = ops.CropFn.apply(out, tuple(x_nhwc.shape[1:3]))
+    ll, _ = model.likelihood(out, x_nhwc, model.noise)
+    kl_ln = ops.StackFn.apply(*td['kl'])
+    kl_sep, kl_avg, _ = K.kl_bookkeeping_fwd(kl_ln, float(model.free_bits))
+    elbo_sep, _ = K.elbo_loss_fwd(ll, kl_sep, zero, 1.0)
+    K.eval_online(state, model.n_layers, 1, elbo_sep, ll, kl_sep, kl_avg)
+    model.noise.end()
+
+
+class _TestGraphs:
+    """The bottom-up pass and one sample of a test batch shape, captured once and replayed for every batch of that shape, in this and in
+    later test passes. Static input x and per-image state; a capture stream of its own (so its scratch workspace is its own too)."""
+
+    def __init__(self, model, x, noise):
+        from .noise import PhiloxNoise
+        dev = x.device
+        self.noise, self.keep = noise, []
+        self.stream = torch.cuda.Stream(device=dev, priority=-1)
+        self.stream.wait_stream(torch.cuda.current_stream(dev))
+        L = model.n_layers
+        with torch.cuda.stream(self.stream), _EvalWeights(self.keep):
+            self.x = x.clone()
+            self.state = torch.empty(5 * x.shape[0] + L, dtype=torch.float64, device=dev)
+            self.zero = torch.zeros(1, device=dev)
+            # one eager pass with a throw-away noise source: lazy initialisation and scratch growth happen outside the capture, and the
+            # caller's noise stream is not advanced by it
+            model.noise = PhiloxNoise(0)
+            bu, x_nhwc = _test_bottom_up(model, self.x)
+            K.eval_online(self.state, L, 0)
+            _test_sample(model, bu, x_nhwc, self.state, self.zero)
+            model.noise = noise
+            noise.begin(dev)          # its device step counter exists before the capture
+            del bu, x_nhwc
+            torch.cuda.synchronize(dev)
+            self.g_bu = torch.cuda.CUDAGraph()
+            with torch.cuda.graph(self.g_bu, stream=self.stream, capture_error_mode='thread_local'):
+                self.bu, self.x_nhwc = _test_bottom_up(model, self.x)
+            self.g_sample = torch.cuda.CUDAGraph()
+            with torch.cuda.graph(self.g_sample, pool=self.g_bu.pool(), stream=self.stream, capture_error_mode='thread_local'):
+                _test_sample(model, self.bu, self.x_nhwc, self.state, self.zero)
+            self.keep.append(K.workspace(0, dev))   # the scratch buffer the captured launches use
+
+    def run(self, x, n_samples, totals, L):
+        cur = torch.cuda.current_stream(x.device)
+        self.stream.wait_stream(cur)
+        with torch.cuda.stream(self.stream):
+            self.x.copy_(x)
+            K.eval_online(self.state, L, 0)
+            self.g_bu.replay()
+            for _ in range(n_samples):
+                self.g_sample.replay()
+            K.eval_totals(self.state, L, n_samples, totals)
+        cur.wait_stream(self.stream)
+
+
+@torch.no_grad()
+def test_pass(model, batches, n_samples, noise=None, process_group=None, use_graph=None):
+    """The reference's test summaries over an iterable of NCHW image batches (each rank passes ITS shard of the test set): means over images
+    and samples of 'elbo/elbo', 'elbo/recons', 'elbo/kl', 'kl_layers/kl_layer_<i>', plus 'elbo/elbo_IW_<S>' when S > 1, and 'n_images'.
+
+    Eval mode: bottom-up once per batch, S top-down samples folded on the device (lvae_eval_online_f32), each batch added to a double
+    accumulator (lvae_eval_totals_f64); one all-reduce of the totals over ranks and one device-to-host copy per pass. The noise comes from
+    `noise` (default: a PhiloxNoise of the model's own, `model.test_noise`, whose stream continues from pass to pass), never from
+    `model.noise`; dropout is off and BatchNorm statistics are only read, so a test pass leaves training exactly as it was.
+    use_graph=None: with on-device Philox noise, bottom-up and one sample are captured once per batch shape and replayed; a replayed
+    noise tape (parity tests) runs eagerly."""
+    from .noise import PhiloxNoise
+    dev = next(model.parameters()).device
+    if noise is None:
+        if getattr(model, 'test_noise', None) is None:
+            model.test_noise = PhiloxNoise(seed=(model.noise.seed if isinstance(model.noise, PhiloxNoise) else 0) ^ 0x7E57)
+        noise = model.test_noise
+    if use_graph is None:
+        use_graph = isinstance(noise, PhiloxNoise)
+    L = model.n_layers
+    totals = torch.zeros(5 + L, dtype=torch.float64, device=dev)
+    train_noise, was_training = model.noise, model.training
+    model.eval()
+    model.noise = noise
+    try:
+        if use_graph:
+            plans = model.__dict__.setdefault('_test_graphs', {})
+            for x in batches:
+                x = x.to(dev).contiguous().float()
+                key = (tuple(x.shape), id(noise), noise.seed, id(model.pack()), model.compute_dtype)
+                plan = plans.get(key)
+                if plan is None or plan.noise is not noise:
+                    plan = plans[key] = _TestGraphs(model, x, noise)
+                plan.run(x, n_samples, totals, L)
+        else:
+            keep = []
+            with _EvalWeights(keep):
+                zero = torch.zeros(1, device=dev)
+                for x in batches:
+                    x = x.to(dev).contiguous().float()
+                    state = torch.empty(5 * x.shape[0] + L, dtype=torch.float64, device=dev)
+                    K.eval_online(state, L, 0)
+                    bu, x_nhwc = _test_bottom_up(model, x)
+                    for _ in range(n_samples):
+                        _test_sample(model, bu, x_nhwc, state, zero)
+                    K.eval_totals(state, L, n_samples, totals)
+            torch.cuda.current_stream(dev).synchronize()   # (the registered scratch buffers of this pass may go now)
+    finally:
+        model.noise = train_noise
+        model.train(was_training)
+    tot = reduce_eval_sums(totals, process_group).cpu().tolist()
+    n = tot[4]
+    res = {'elbo/elbo': tot[1] / n, 'elbo/recons': tot[2] / n, 'elbo/kl': tot[3] / n}
+    for i in range(L):
+        res['kl_layers/kl_layer_%d' % i] = tot[5 + i] / n
+    if n_samples > 1:
+        res['elbo/elbo_IW_%d' % n_samples] = tot[0] / n
+    res['n_images'] = int(n)
+    return res
 
 
 @torch.no_grad()
@@ -153,8 +310,7 @@ def main(argv=None):
         else:
             data = synthetic_batch(exp, args.n_test, gen)
         bs = args.test_batch_size
-        res = evaluate(model, (data[i:i + bs] for i in range(0, data.shape[0], bs)), args.loglikelihood_samples)
-        res['elbo/recons'], res['elbo/kl'] = float('nan'), float('nan')
+        res = test_pass(model, (data[i:i + bs] for i in range(0, data.shape[0], bs)), args.loglikelihood_samples)
         print(exp.test_log_str(res, model.global_step))
     if args.ps:
         np.save('prior_samples.npy', prior_samples(model, 64).cpu().numpy())

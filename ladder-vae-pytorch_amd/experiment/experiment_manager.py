@@ -7,8 +7,8 @@
   * `_make_model` (:38-74), `_make_optimizer` (:76-81, Adamax) and `forward_pass` (:322-367);
   * `train_log_str` / `test_log_str` / `get_metrics_dict` (:369-415).
 
-Out of scope: boilr's trainer loop, checkpoint rotation, tensorboard, dataset downloads. main.py drives
-a minimal loop over synthetic batches (or an .npz file) with the same log lines.
+Out of scope: tensorboard, image grids, dataset downloads. main.py drives a minimal loop over a dataset, synthetic batches
+or an .npz file with the same log lines, test passes, log-likelihood estimates and checkpoint rotation (schedule.py).
 """
 import argparse
 
@@ -81,6 +81,10 @@ def build_parser():
     p.add_argument('--no-graph', action='store_true', help='launch eagerly instead of replaying a captured hipGraph')
     p.add_argument('--log-every', type=int, default=100)
     p.add_argument('--save-checkpoint', type=str, default='', help='write a reference-layout checkpoint here at the end')
+    p.add_argument('--checkpoint-dir', type=str, default='', dest='checkpoint_dir',
+                   help='write <dir>/model_<step>.pt every --checkpoint-every steps, keeping the newest --keep-checkpoint-max')
+    p.add_argument('--synthetic-test', type=int, default=0, dest='synthetic_test', metavar='N',
+                   help='with --synthetic: a fixed seeded test set of N images for the --ts-log-every / --ll-every test passes')
     return p
 
 

@@ -1103,6 +1103,24 @@ def elbo_loss_bwd(g_loss, beta, N):
     return d_ll, d_kl
 
 
+def elbo_loss_fwd_anneal(ll, kl_sep, kl_loss, step, anneal_steps):
+    """elbo_loss_fwd with beta = linear_anneal(step[0], 0, 1, anneal_steps) read on the device (step: device int64[1])."""
+    N = ll.numel()
+    elbo_sep = torch.empty((N,), dtype=torch.float32, device=ll.device)
+    scal = torch.empty((3,), dtype=torch.float32, device=ll.device)
+    call('lvae_elbo_loss_fwd_anneal_f32', ptr(ll), ptr(kl_sep), ptr(kl_loss), ptr(step, (torch.int64,)), int(anneal_steps), N,
+         ptr(elbo_sep), ptr(scal), stream_ptr())
+    return elbo_sep, scal
+
+
+def elbo_loss_bwd_anneal(g_loss, step, anneal_steps, N):
+    d_ll = torch.empty((N,), dtype=torch.float32, device=g_loss.device)
+    d_kl = torch.empty((1,), dtype=torch.float32, device=g_loss.device)
+    call('lvae_elbo_loss_bwd_anneal_f32', ptr(g_loss), ptr(step, (torch.int64,)), int(anneal_steps), N, ptr(d_ll), ptr(d_kl),
+         stream_ptr())
+    return d_ll, d_kl
+
+
 # ----------------------------------------------------------------------------------------------------------------
 def iw_logmeanexp(elbo_sn):
     S, N = elbo_sn.shape
@@ -1114,6 +1132,19 @@ def iw_logmeanexp(elbo_sn):
 def iw_online(state, mode, elbo=None, S=0, iw=None, mean=None):
     """state (3, N). mode 0 init / 1 accumulate elbo (N,) / 2 finalize into iw, mean (N,)."""
     call('lvae_iw_online_f32', ptr(elbo), ptr(state), state.shape[1], int(mode), int(S), ptr(iw), ptr(mean), stream_ptr())
+
+
+def eval_online(state, L, mode, elbo=None, ll=None, kl_sep=None, kl_avg=None):
+    """state: float64 (5 * N + L). mode 0 initialise / 1 fold in one sample's elbo_sep, ll, kl_sep (N,) and kl_avg_layerwise (L,)."""
+    N = (state.numel() - L) // 5
+    call('lvae_eval_online_f32', ptr(elbo), ptr(ll), ptr(kl_sep), ptr(kl_avg), ptr(state, (torch.float64,)), N, int(L), int(mode),
+         stream_ptr())
+
+
+def eval_totals(state, L, S, totals):
+    """totals: float64 (5 + L) += this batch's [sum IW, sum ELBO, sum recons, sum KL, images, per-layer KL sums]."""
+    N = (state.numel() - L) // 5
+    call('lvae_eval_totals_f64', ptr(state, (torch.float64,)), N, int(L), int(S), ptr(totals, (torch.float64,)), stream_ptr())
 
 
 def adamax_step(p, g, exp_avg, exp_inf, mask, lr, beta1, beta2, eps, weight_decay, gscale, step_count):

@@ -3,20 +3,45 @@
 
 Launch N ranks with:  python -m torch.distributed.run --nproc-per-node N --master-addr 127.0.0.1 -m lvae_amd.main ...
 """
+import os
 import time
 
 import numpy as np
 import torch
 
 from . import dist as ldist
+from .checkpoint import save_checkpoint
 from .engine import TrainStep
+from .evaluate import test_pass
 from .experiment.experiment_manager import LVAEExperiment
+from .schedule import TrainSchedule, checkpoint_path, checkpoints_to_delete
 
 
 def synthetic_batch(exp, batch, gen):
     shape = (batch, exp.color_ch) + tuple(exp.img_size)
     u = torch.rand(shape, generator=gen)
     return (u > 0.5).float() if exp.args.likelihood == 'bernoulli' else torch.floor(256 * u) / 255
+
+
+def _shard(x, rank, world):
+    n = x.shape[0]
+    return x[n * rank // world:n * (rank + 1) // world]
+
+
+def test_batches(exp, loader, npz, rank, world):
+    """A callable returning this rank's shard of the test set as an iterable of NCHW batches, or None when there is no test split
+    (DatasetLoader.test, a 'test' key of --data-npz, or --synthetic-test N fixed seeded images)."""
+    args = exp.args
+    bs = args.test_batch_size
+    if loader is not None and getattr(loader, 'test', None) is not None:
+        return lambda: (xs for xs in (_shard(b[0], rank, world) for b in loader.test) if xs.shape[0])
+    if npz is not None and 'test' in npz:
+        data = _shard(torch.from_numpy(npz['test']).float(), rank, world)
+    elif args.synthetic and args.synthetic_test > 0:
+        data = _shard(synthetic_batch(exp, args.synthetic_test, torch.Generator().manual_seed(args.seed + 7919)), rank, world)
+    else:
+        return None
+    return lambda: (data[i:i + bs] for i in range(0, data.shape[0], bs))
 
 
 def main(argv=None):
@@ -33,16 +58,19 @@ def main(argv=None):
         except RuntimeError as e:
             raise SystemExit("%s\n(or pass --synthetic / --data-npz FILE)" % e)
     model, opt = exp.model, exp.optimizer
-    model.noise.seed ^= rank * 0x9E3779B9
     if args.resume:
         from .checkpoint import load_checkpoint
-        load_checkpoint(args.resume, model, opt)
+        load_checkpoint(args.resume, model, opt)   # (weights, Adamax state, global step and the rank-0 noise stream's position)
+    model.noise.seed ^= rank * 0x9E3779B9
     model.train()
     arena = model.pack()
     per_rank = args.batch_size // max(1, world)
-    data = None
+    data = npz = None
     if args.data_npz:
-        data = torch.from_numpy(np.load(args.data_npz)['data']).float()
+        npz = np.load(args.data_npz)
+        data = torch.from_numpy(npz['data']).float()
+    tests = test_batches(exp, loader, npz, rank, world)
+    sched = TrainSchedule.from_args(args, tests is not None)
     if args.simple_data_dependent_init and not args.resume:
         # experiment_manager.py:61-72: the first batch_size training images (parity unpinned, see init.py)
         from .init import data_dependent_init
@@ -52,7 +80,8 @@ def main(argv=None):
             print('data-dependent init: %d convolutions rescaled' % n)
     ldist.broadcast_flat(arena.params)
     allreduce = ldist.GradAllReduce(arena.grads, segments=arena.segments) if world > 1 else None
-    step_fn = TrainStep(model, opt, beta=1.0, use_graph=not args.no_graph and args.beta_anneal == 0, allreduce=allreduce)
+    # --beta-anneal: beta is read on the device from a step counter the step advances itself, so the captured graph replays with it
+    step_fn = TrainStep(model, opt, beta=1.0, use_graph=not args.no_graph, allreduce=allreduce, beta_anneal=args.beta_anneal)
     if rank == 0:
         print(exp.run_description)
         print('parameters: %d   world size: %d   per-rank batch: %d' % (sum(p.numel() for p in model.parameters()), world,
@@ -62,15 +91,23 @@ def main(argv=None):
     per_rank = args.batch_size // world
     gen = torch.Generator().manual_seed(args.seed + 1000 * rank)
     steps = args.steps or args.max_steps
+    first = model.global_step + 1                      # > 1 after --resume: the run continues where the checkpoint left it
+    if not (loader is not None or data is not None):
+        for _ in range(first - 1):                     # the synthetic batches the resumed steps already consumed
+            synthetic_batch(exp, per_rank, gen)
     batches = None
+    epoch = 0
     t0, seen = time.time(), 0
-    for step in range(1, steps + 1):
+    for step in range(first, steps + 1):
         if loader is not None:
-            if step == 1 or batches is None:
+            if batches is None:
                 batches = iter(loader.train)
             try:
                 xb = next(batches)[0]
             except StopIteration:                      # next epoch: reshuffled by the DataLoader
+                epoch += 1
+                if epoch >= args.max_epochs:
+                    break
                 batches = iter(loader.train)
                 xb = next(batches)[0]
             lo, hi = ldist.shard_batch(args.batch_size, rank, world)
@@ -81,8 +118,6 @@ def main(argv=None):
             x = data[idx[lo:hi]]
         else:
             x = synthetic_batch(exp, per_rank, gen)
-        if args.beta_anneal != 0:
-            step_fn.beta = exp.beta()
         out = step_fn(x.to(exp.device, non_blocking=True))
         seen += args.batch_size
         if rank == 0 and (step % args.log_every == 0 or step == steps):
@@ -90,8 +125,20 @@ def main(argv=None):
             dt = time.time() - t0
             print(exp.train_log_str(m, step) + '   [{:.0f} img/s]'.format(seen / dt))
             t0, seen = time.time(), 0
+        n_samples, ckpt = sched.at(step)
+        if n_samples:
+            if data is not None and loader is None:
+                epoch = step * args.batch_size // data.shape[0]
+            res = test_pass(model, tests(), n_samples)
+            if rank == 0:
+                print(exp.test_log_str(res, step, epoch), flush=True)
+            t0, seen = time.time(), 0                  # the training throughput excludes test passes
+        if ckpt and rank == 0:
+            os.makedirs(args.checkpoint_dir, exist_ok=True)
+            save_checkpoint(checkpoint_path(args.checkpoint_dir, step), model, opt)
+            for name in checkpoints_to_delete(os.listdir(args.checkpoint_dir), args.keep_checkpoint_max):
+                os.remove(os.path.join(args.checkpoint_dir, name))
     if args.save_checkpoint and rank == 0:
-        from .checkpoint import save_checkpoint
         save_checkpoint(args.save_checkpoint, model, opt)
     if world > 1:
         torch.distributed.barrier()

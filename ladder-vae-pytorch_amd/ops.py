@@ -789,3 +789,22 @@ class ElboLossFn(Function):
     def backward(ctx, g_sep, g_loss, g_elbo, g_recons):
         d_ll, d_kl = K.elbo_loss_bwd(_c(g_loss).view(1), ctx.beta, ctx.N)
         return d_ll, None, d_kl.view(()) if ctx.kl_dim0 else d_kl, None
+
+
+class ElboLossAnnealFn(Function):
+    """ElboLossFn with beta = linear_anneal(step[0], 0, 1, anneal_steps) read on the device: a captured step replays with the beta of
+    the step it runs (step: device int64[1], the number of completed training steps)."""
+
+    @staticmethod
+    def forward(ctx, ll, kl_sep, kl_loss, step, anneal_steps):
+        ctx.step, ctx.anneal_steps, ctx.N = step, int(anneal_steps), ll.numel()
+        ctx.kl_dim0 = kl_loss.dim() == 0
+        elbo_sep, scal = K.elbo_loss_fwd_anneal(ll, kl_sep, kl_loss, step, anneal_steps)
+        loss, elbo, recons = scal[0], scal[1], scal[2]
+        ctx.mark_non_differentiable(elbo_sep, elbo, recons)
+        return elbo_sep, loss, elbo, recons
+
+    @staticmethod
+    def backward(ctx, g_sep, g_loss, g_elbo, g_recons):
+        d_ll, d_kl = K.elbo_loss_bwd_anneal(_c(g_loss).view(1), ctx.step, ctx.anneal_steps, ctx.N)
+        return d_ll, None, d_kl.view(()) if ctx.kl_dim0 else d_kl, None, None
