@@ -308,17 +308,7 @@ def conv2d(x, weight, g, bias=None, x2=None, in_scale=None, in_shift=None, in_ac
     lib = _C.load()
     coef = fold = None
     if in_bn is not None:
-        sp, pivot, bn = in_bn
-        M = N * H * W
-        if sp.has_pivot and x2 is None and lib.lvae_conv2d_folds_bn_finalize(C.byref(d)):
-            coef = torch.empty((4, C1), dtype=torch.float32, device=x.device)
-            fold = BnFold(ptr(sp.buf), sp.rows, M, ptr(bn.weight), ptr(bn.bias), bn.eps, bn.momentum, ptr(bn.running_mean),
-                          ptr(bn.running_var), ptr(coef))
-            d.in_fold = C.addressof(fold)
-            coef = (coef[0], coef[1], coef[2], coef[3])
-        else:
-            coef = bn_finalize_parts(sp.rows_view(), M, pivot, bn.weight, bn.bias, bn.running_mean, bn.running_var, bn.eps, bn.momentum)
-            d.in_scale, d.in_shift = ptr(coef[0]), ptr(coef[1])
+        coef, fold = _in_bn(d, in_bn, x, in_bn[0].has_pivot and x2 is None and bool(lib.lvae_conv2d_folds_bn_finalize(C.byref(d))))
     parts = None
     if stats_pivot is not None:
         rows = lib.lvae_conv2d_stats_rows(C.byref(d))
@@ -334,6 +324,22 @@ def conv2d(x, weight, g, bias=None, x2=None, in_scale=None, in_shift=None, in_ac
     return y if stats_pivot is None else (y, parts)
 
 
+def _is_1x1(g):
+    return g.KH == 1 and g.KW == 1 and g.stride == 1 and g.pad == 0 and not g.transposed
+
+
+# The two "is this the GateLayer2d convolution (1x1, C -> 2C)" predicates differ in what the kernels behind them take: the single-shot gate
+# kernels (forward, backward) take either weight orientation but at most 128 channels; the persistent backward kernel needs the weight
+# Cout-contiguous and leaves the channel counts to its workspace query.
+def _gate_1x1_single_shot(g, Cn):
+    return (_is_1x1(g) and g.Cout == 2 * Cn and g.Cin <= 128 and g.Cout <= 128 and g.Cin % 4 == 0 and g.Cout % 8 == 0 and
+            (g.s_co == 1 or g.s_ci == 1))
+
+
+def _gate_1x1_persistent(g, Cn):
+    return _is_1x1(g) and g.Cout == 2 * Cn and g.s_co == 1
+
+
 def conv1x1_gate(x, weight, g, bias, res, act, need_ab=True, stats_pivot=None):
     """GateLayer2d forward: ab = conv1x1(x) + bias (returned when need_ab), out = act(a) * sigmoid(b) + res, one kernel.
     Falls back to conv2d + gate_fwd when the fused kernel does not support the shape.
@@ -342,9 +348,7 @@ def conv1x1_gate(x, weight, g, bias, res, act, need_ab=True, stats_pivot=None):
     _chk_nhwc(x, 'x')
     N, H, W, _ = x.shape
     Cn = g.Cout // 2
-    fused_ok = (g.KH == 1 and g.KW == 1 and g.stride == 1 and g.pad == 0 and not g.transposed and g.Cin <= 128 and
-                g.Cout <= 128 and g.Cin % 4 == 0 and g.Cout % 8 == 0 and (g.s_co == 1 or g.s_ci == 1))
-    if not fused_ok or (_ddi is not None and weight.data_ptr() not in _ddi['done']):
+    if not _gate_1x1_single_shot(g, Cn) or (_ddi is not None and weight.data_ptr() not in _ddi['done']):
         ab = conv2d(x, weight, g, bias=bias)
         out = gate_fwd(ab, res, act)
         return (ab, out) if stats_pivot is None else (ab, out, None)
@@ -367,9 +371,7 @@ def conv1x1_gate_bwd(dout, ab, weight, g, act, out_scale=None):
     shape is supported (gate backward formed in the dgrad kernel's operand staging), else gate_bwd + conv2d_dgrad."""
     _chk_nhwc(dout, 'dout')
     N, H, W, Cn = dout.shape
-    fused_ok = (g.KH == 1 and g.KW == 1 and g.stride == 1 and g.pad == 0 and not g.transposed and g.Cout == 2 * Cn and
-                g.Cout <= 128 and g.Cin <= 128 and g.Cout % 8 == 0 and g.Cin % 4 == 0 and (g.s_co == 1 or g.s_ci == 1))
-    if not fused_ok:
+    if not _gate_1x1_single_shot(g, Cn):
         dab = gate_bwd(dout, ab, act)
         return dab, conv2d_dgrad(dab, weight, g, (H, W), out_scale=out_scale)
     dab = torch.empty_like(ab)
@@ -379,19 +381,25 @@ def conv1x1_gate_bwd(dout, ab, weight, g, act, out_scale=None):
     return dab, dx
 
 
-def gate_bwd_fused_ok(x_like, weight, g, dweight=None):
-    """True when conv1x1_gate_bwd_wgrad takes the gate convolution (weight, g) on tensors shaped like x_like (N,H,W,C) — and can therefore
-    also form its dout from a deferred BatchNorm-backward apply (PendingApply)."""
+def gate_bwd_fused_ws(x_like, weight, g, dweight=None):
+    """Scratch bytes conv1x1_gate_bwd_wgrad needs for the gate convolution (weight, g) on tensors shaped like x_like (N,H,W,C); 0: it does
+    not take the shape (the answer depends on the geometry alone). dweight: the gradient buffer, where it exists already."""
     N, H, W, Cn = x_like.shape
-    if not (g.KH == 1 and g.KW == 1 and g.stride == 1 and g.pad == 0 and not g.transposed and g.Cout == 2 * Cn and g.s_co == 1):
-        return False
-    if dweight is not None and tuple(dweight.stride()) != tuple(weight.stride()):
-        return False
-    if form == _C.FORM_F32_MFMA and precision != PREC_BF16:
-        return False
+    if not _gate_1x1_persistent(g, Cn) or (dweight is not None and tuple(dweight.stride()) != tuple(weight.stride())):
+        return 0
     d = _desc(g, weight, x_like, None, N, H, W, H, W, g.Cin, g.s_co, g.s_ci, GATHER_TRANSPOSED)
     d.C1 = g.Cout
-    return bool(_C.load().lvae_conv1x1_gate_bwd_wgrad_workspace(C.byref(d)))
+    return int(_C.load().lvae_conv1x1_gate_bwd_wgrad_workspace(C.byref(d)))
+
+
+def gate_bwd_apply_ok():
+    """conv1x1_gate_bwd_wgrad can form its dout from a deferred BatchNorm-backward apply (PendingApply): every form but the fp32 MFMA."""
+    return not (form == _C.FORM_F32_MFMA and precision != PREC_BF16)
+
+
+def gate_bwd_fused_ok(x_like, weight, g, dweight=None):
+    """True when conv1x1_gate_bwd_wgrad takes the gate convolution (weight, g) on tensors shaped like x_like (N,H,W,C) with a deferred apply."""
+    return gate_bwd_apply_ok() and gate_bwd_fused_ws(x_like, weight, g, dweight) > 0
 
 
 def conv1x1_gate_bwd_wgrad(dout, ab, y, weight, g, act, dweight, dbias, out_scale=None, out_bf16=False, apply=None):
@@ -400,16 +408,14 @@ def conv1x1_gate_bwd_wgrad(dout, ab, y, weight, g, act, dweight, dbias, out_scal
     apply (PendingApply): dout does not exist yet; the kernel forms it from the deferred BatchNorm-backward apply and stores it to apply.out."""
     _chk_nhwc(dout, 'dout')
     N, H, W, Cn = dout.shape
-    if not (g.KH == 1 and g.KW == 1 and g.stride == 1 and g.pad == 0 and not g.transposed and g.Cout == 2 * Cn and g.s_co == 1):
-        return None
-    if tuple(dweight.stride()) != tuple(weight.stride()):
+    if not _gate_1x1_persistent(g, Cn) or tuple(dweight.stride()) != tuple(weight.stride()):
         return None
     if ab.dtype != y.dtype:
         raise _C.LvaeHipError("conv1x1_gate_bwd_wgrad: ab and y must have the same element type")
     dx = torch.empty((N, H, W, g.Cin), dtype=torch.bfloat16 if out_bf16 else torch.float32, device=dout.device)
     d = _desc(g, weight, ab, None, N, H, W, H, W, g.Cin, g.s_co, g.s_ci, GATHER_TRANSPOSED, out_scale=out_scale, y=dx)
     need = _C.load().lvae_conv1x1_gate_bwd_wgrad_workspace(C.byref(d))
-    if not need or (apply is not None and form == _C.FORM_F32_MFMA and precision != PREC_BF16):
+    if not need or (apply is not None and not gate_bwd_apply_ok()):
         return None
     ws = workspace(need, dout.device)
     ap = None
@@ -456,34 +462,26 @@ def _rb_gate_ws(e, gate_w, gate_g, device, bwd):
 def rb_rows(x, weight, g):
     """Workgroups (= statistics rows) of the fused residual-block kernels for the 3x3 convolution (weight, g) on x, 0 when the shape is
     not theirs (needs 3x3 / stride 1 / pad 1, 64 -> 64 channels, H*W a divisor of 64, fp32 NHWC x)."""
+    d = _rb_query_desc(x, weight, g)
+    return int(_C.load().lvae_resblock_conv_rows(C.byref(d))) if d is not None else 0
+
+
+def _rb_query_desc(x, weight, g):
+    """Bare descriptor for the shape queries of the residual-block kernels, None where none of them applies. (No scratch is attached here:
+    asking must not register weights the caller may never run through these kernels.)"""
     if _ddi is not None or x.dtype != torch.float32 or x.dim() != 4 or g.transposed or g.KH != 3 or g.stride != 1 or g.pad != 1:
-        return 0
-    N, H, W, _ = x.shape   # (no scratch is attached here: asking must not register weights the caller may never run through these kernels)
-    d = _desc(g, weight, x, None, N, H, W, H, W, g.Cout, g.s_ci, g.s_co, GATHER_CONV)
-    return int(_C.load().lvae_resblock_conv_rows(C.byref(d)))
+        return None
+    N, H, W, _ = x.shape
+    return _desc(g, weight, x, None, N, H, W, H, W, g.Cout, g.s_ci, g.s_co, GATHER_CONV)
 
 
-# Which residual blocks take the fused launches (measured per level at batch 256, tools/rb_bench.py: forward old -> fused 41 -> 31 us at
-# 8x8, 33 -> 26 at 4x4, 22 -> 27 at 2x2, where the position-major kernels skip the taps outside the image; backward 60 -> 43, 46 -> 33,
-# 37 -> 33): forward from 16 pixels per image up, backward everywhere the kernels exist. LVAE_RB_FWD_MIN_HW / LVAE_RB_BWD_MIN_HW
-# (profiling only) move the thresholds; 0 pixels = never.
-import os as _os
-_RB_FWD_MIN_HW = int(_os.environ.get('LVAE_RB_FWD_MIN_HW', '16'))
-_RB_BWD_MIN_HW = int(_os.environ.get('LVAE_RB_BWD_MIN_HW', '1'))
-_RB_GATE_LARGE = _os.environ.get('LVAE_RB_GATE_LARGE', '1') != '0'   # conv2 + gate in one launch at the >= 16x16 levels (Winograd kernel)
-
-
-def rb_policy(x, weight, g):
-    """(fused forward?, fused backward?) for the residual block whose 3x3 convolutions look like (weight, g) on input x."""
-    if rb_rows(x, weight, g) <= 0:
-        return False, False
-    hw = x.shape[1] * x.shape[2]
-    return (_RB_FWD_MIN_HW > 0 and hw >= _RB_FWD_MIN_HW), (_RB_BWD_MIN_HW > 0 and hw >= _RB_BWD_MIN_HW)
-
-
-def _rb_in_bn(d, in_bn, x, can_fold=True):
+def _in_bn(d, in_bn, x, can_fold=True, coef=None):
     """Training-mode BatchNorm of the convolution input from partial sums: folded into the prologue when the producer stored its pivot
-    (and the kernel that will run can fold), by lvae_bn_finalize_parts_f32 otherwise. Returns (coef 4-tuple, keep-alive)."""
+    (and the kernel that will run can fold), by lvae_bn_finalize_parts_f32 otherwise. in_bn None: the given coefficients. Returns (coef
+    4-tuple, keep-alive)."""
+    if in_bn is None:
+        d.in_scale, d.in_shift = ptr(coef[0]), ptr(coef[1])
+        return coef, None
     sp, pivot, bn = in_bn
     N, H, W, C1 = x.shape
     M = N * H * W
@@ -524,11 +522,7 @@ def rb_conv(x, weight, g, bias, in_act, out_scale, in_bn=None, coef=None, stats_
     N, H, W, _ = x.shape
     y = torch.empty((N, H, W, g.Cout), dtype=torch.float32, device=x.device)
     d, _ = _rb_desc(x, weight, g, False, y, bias, None, None, in_act, out_scale)
-    keep = None
-    if in_bn is not None:
-        coef, keep = _rb_in_bn(d, in_bn, x)
-    else:
-        d.in_scale, d.in_shift = ptr(coef[0]), ptr(coef[1])
+    coef, keep = _in_bn(d, in_bn, x, coef=coef)
     parts = None
     if stats_pivot is not None:
         rows = _C.load().lvae_resblock_conv_rows(C.byref(d))
@@ -543,16 +537,16 @@ def rb_conv(x, weight, g, bias, in_act, out_scale, in_bn=None, coef=None, stats_
     return y, parts, coef
 
 
-def rb_gate_rows(x, weight, g):
+def rb_gate_rows(x, weight, g, whole_image=True):
     """Workgroups (= statistics rows of `out`) of the forward conv + gate fusion for the 3x3 convolution (weight, g) on x: the whole-image
-    kernels' shapes, or the 256-pixel six-product Winograd kernel's (fp32, 16x16 and 32x32 levels at batch 256). 0: not available."""
-    if _ddi is not None or x.dtype != torch.float32 or x.dim() != 4 or g.transposed or g.KH != 3 or g.stride != 1 or g.pad != 1:
+    kernels' shapes (counted as 0 with whole_image=False), or the 256-pixel six-product Winograd kernel's (fp32, 16x16 and 32x32 levels at
+    batch 256). 0: not available."""
+    d = _rb_query_desc(x, weight, g)
+    if d is None:
         return 0
-    N, H, W, _ = x.shape
-    d = _desc(g, weight, x, None, N, H, W, H, W, g.Cout, g.s_ci, g.s_co, GATHER_CONV)
     rows = int(_C.load().lvae_resblock_conv_rows(C.byref(d)))
     if rows > 0:
-        return rows
+        return rows if whole_image else 0
     _conv_ws(d, weight, x.device)   # the Winograd kernel's transformed weights: the buffer the plain convolution of this layer uses too
     return int(_C.load().lvae_resblock_conv_gate_rows(C.byref(d)))
 
@@ -571,11 +565,7 @@ def rb_conv_gate(x, weight, g, bias, in_act, out_scale, gate_w, gate_g, gate_bia
     if not need:   # not a whole-image shape: the Winograd kernel with the gate behind it (its own transformed weights)
         _conv_ws(d, weight, dev)
         can_fold = bool(_C.load().lvae_conv2d_folds_bn_finalize(C.byref(d)))
-    keep = None
-    if in_bn is not None:
-        coef, keep = _rb_in_bn(d, in_bn, x, can_fold)
-    else:
-        d.in_scale, d.in_shift = ptr(coef[0]), ptr(coef[1])
+    coef, keep = _in_bn(d, in_bn, x, can_fold, coef)
     e = RbExt()
     e.prologue, e.epilogue = _C.RB_PRO_AFFINE, _C.RB_EPI_GATE
     _rb_gate_ws(e, gate_w, gate_g, dev, False)
@@ -739,7 +729,7 @@ def conv2d_wgrad_apply(x, weight, g, dweight, dbias, parts, dh, xbn, coef0, act,
 def conv1x1_dgrad_cat(dy, weight, g, C1):
     """Both halves of the input gradient of a 1x1 / stride-1 convolution whose input was the channel concat (x [.., C1], x2 [.., Cin - C1]),
     in one launch: returns (dx, dx2), or None when the shape is not the single-shot 1x1 kernel's (the caller launches one dgrad per half)."""
-    if not (g.KH == 1 and g.KW == 1 and g.stride == 1 and g.pad == 0 and not g.transposed and dy.dtype == torch.float32):
+    if not (_is_1x1(g) and dy.dtype == torch.float32):
         return None
     K_, N_ = g.Cout, g.Cin
     kc = g.s_co == 1 and g.s_ci % 4 == 0

@@ -12,6 +12,7 @@ from torch.nn import init
 
 from .. import kernels as K
 from .. import ops
+from .. import resblock
 
 NONLIN_NAMES = ('relu', 'leakyrelu', 'elu', 'selu')
 
@@ -192,6 +193,7 @@ class ResidualBlock(nn.Module):
             self._drops = (dropout is not None, False)
         else:
             self._drops = (True, True)
+        self.__dict__['sched'] = resblock.BlockState()   # the schedule's per-block state (ops.ResBlockFn): no parameter, buffer or submodule
 
     def _masks(self, x, noise):
         N, C = x.shape[0], x.shape[3]
@@ -208,27 +210,7 @@ class ResidualBlock(nn.Module):
             return self._forward_post_activation(x, noise)
         # masks are drawn in execution order: conv1's dropout, then conv2's (SURVEY.md §8c noise tape)
         m1, m2 = self._masks(x, noise)
-        params = [p for p in self.parameters()]
-        # BatchNorm partials of x, if the previous block's gate kernel produced them: they travel as an attribute of exactly that
-        # tensor object (a view, a copy or any other tensor does not carry them)
-        ent = getattr(x, '_lvae_bn_parts', None)
-        if ent is not None and self.training:
-            self.__dict__['_in_parts'] = ent
-        # the residual block that produced exactly this tensor object (its only consumer is this block): this block's last backward launch,
-        # the BatchNorm-1 apply, can be left to that block's first backward launch (ops._DEFER_APPLY)
-        src = x.__dict__.pop('_lvae_rb_src', None) if hasattr(x, '__dict__') else None
-        if src is not None and self.training and torch.is_grad_enabled():
-            self.__dict__['_in_src'] = src
-        self.__dict__.pop('_pending_apply', None)   # (left behind by a backward pass that was abandoned)
-        self.__dict__['_accepts_deferred'] = None
-        out = ops.ResBlockFn.apply(x, self, m1, m2, self.training, *params)
-        self.__dict__.pop('_in_src', None)
-        self.__dict__.pop('_in_parts', None)
-        if self.training and torch.is_grad_enabled() and self.__dict__.get('_accepts_deferred'):
-            out._lvae_rb_src = self
-        oparts = self.__dict__.pop('_out_parts', None)
-        if oparts is not None:
-            out._lvae_bn_parts = oparts
+        out = ops.residual_block(x, self, m1, m2)
         if self.training:
             for bn in (self.bn1, self.bn2):
                 if bn is not None:

@@ -6,12 +6,13 @@ Functions return None for parameter inputs; activations flow through autograd no
 
 All activations are NHWC (N,H,W,C) contiguous float32 CUDA tensors.
 """
-import os
+from types import SimpleNamespace
 
 import torch
 from torch.autograd import Function
 
 from . import kernels as K
+from . import resblock as RB
 
 _const_cache = {}
 
@@ -60,15 +61,15 @@ def join_wgrad_stream():
             torch.cuda.current_stream().wait_stream(st)
 
 
-def set_wgrad_grouping(max_rows, flush_at=int(os.environ.get('LVAE_WGRAD_FLUSH', '1024'))):
-    """Queue the weight gradients of layers with at most `max_rows` pixels (N*H*W) and issue them `flush_at` at a time (measured
-    on the CIFAR-15 step: 12 -> 43.6 ms, 72 -> 42.8, 288 -> 42.4: fuller groups of each kernel variant; the queued (x, dy) pairs
-    are at most 4 MB each) through
-    lvae_conv2d_wgrad_grouped_f32 (None switches grouping off and flushes). The caller must call flush_wgrad_group() before
-    anything reads the gradients."""
+def set_wgrad_grouping(max_rows, flush_at=None):
+    """Queue the weight gradients of layers with at most `max_rows` pixels (N*H*W) and issue them `flush_at` at a time through
+    lvae_conv2d_wgrad_grouped_f32 (None switches grouping off and flushes). The default, 1024 (RB.switches.wgrad_flush), rests on the grouped
+    entry point taking 32 problems per launch and kernel kind: fuller groups of each kind were faster as far as was measured (CIFAR-15
+    step: 12 -> 43.6 ms, 72 -> 42.8, 288 -> 42.4); no sweep of 1024 itself is recorded. The queued (x, dy) pairs are at most 4 MB each.
+    The caller must call flush_wgrad_group() before anything reads the gradients."""
     flush_wgrad_group()
     _side['group_rows'] = max_rows
-    _side['group_at'] = flush_at
+    _side['group_at'] = RB.switches.wgrad_flush if flush_at is None else flush_at
 
 
 def flush_wgrad_group():
@@ -110,11 +111,6 @@ def wgrad(x, dy, w, g, dw, db, **kw):
 
 
 # ----------------------------------------------------------------------------------------------------------------
-_DGRAD_CAT = os.environ.get('LVAE_DGRAD_CAT', '1') != '0'   # A/B switch, profiling only
-_WGRAD_APPLY = os.environ.get('LVAE_WGRAD_APPLY', '1') != '0'   # A/B switch, profiling only
-_WGRAD_APPLY_MAXW = int(os.environ.get('LVAE_WGRAD_APPLY_MAXW', '16'))   # 32x32 measured +0.09 ms (profiles/r05_wgrad_apply_ab.txt)
-
-
 class ConvFn(Function):
     """y = out_act(conv(cat(x, x2)) + bias); call sites: stem, pre_conv (strided / transposed), merge 1x1,
     stochastic convs, likelihood head. `mod` is the parameter holder (lib.nn.Conv2dParams)."""
@@ -145,7 +141,7 @@ class ConvFn(Function):
                 dx = K.conv2d_dgrad(dy, w, g, hw)
         else:
             C1 = x.shape[3]
-            both = K.conv1x1_dgrad_cat(dy, w, g, C1) if (_DGRAD_CAT and ctx.needs_input_grad[0] and ctx.needs_input_grad[1]) else None
+            both = K.conv1x1_dgrad_cat(dy, w, g, C1) if (RB.switches.dgrad_cat and ctx.needs_input_grad[0] and ctx.needs_input_grad[1]) else None
             if both is not None:
                 dx, dx2 = both   # merge / skip 1x1: both halves of the channel concat from one launch
             else:
@@ -161,299 +157,184 @@ def conv(x, mod, x2=None, out_act=None):
 
 
 # ----------------------------------------------------------------------------------------------------------------
-_GATE_STATS = os.environ.get('LVAE_NO_GATE_STATS') is None  # A/B switch, profiling only
+def _bn_of_half(h, bn, training, parts, pivot):
+    """BatchNorm coefficients of one half of a block as (in_bn, coef), exactly one of them set: in_bn = (parts, pivot, bn) where the kernel
+    that produced h left partial sums (the convolution that reads h finalizes them: kernels.conv2d), else coef = (scale, shift, mean | None,
+    rstd | None) from a statistics pass, the running statistics, or the identity."""
+    if bn is None:
+        return None, _ones_zeros(h.shape[3], h.device) + (None, None)
+    if not training:
+        return None, K.bn_eval_coeffs(bn.weight, bn.bias, bn.running_mean, bn.running_var, bn.eps) + (None, None)
+    if parts is not None:
+        return (parts, pivot, bn), None
+    return None, K.bn_stats(h, bn.weight, bn.bias, bn.running_mean, bn.running_var, bn.eps, bn.momentum)
 
 
-# The fused blocks of the low-resolution levels run as one dependent chain, and every launch streams weights of its own that are cold in
-# the L2s. Inside a block the first launch warms the L2s for the second (kernels.rb_weight_ranges); ACROSS blocks the order is only known
-# from the previous step: each block remembers which fused block ran right after it (per direction) and what that block's first launch
-# streams. Speed only: a stale link makes a launch touch bytes nobody needs; the link holds the scratch tensors themselves (third element of a
-# range, kernels.rb_weight_ranges), so the addresses a launch — or a captured graph — touches stay allocated whatever the cache does.
-import weakref as _weakref
-
-_rb_chain = {'fwd': None, 'bwd': None}
-
-
-def _rb_link(direction, blk, first_ranges):
-    blk.__dict__['_rb_first_' + direction] = first_ranges
-    prev = _rb_chain[direction]
-    prev = prev() if prev is not None else None
-    if prev is not None and prev is not blk:
-        prev.__dict__['_rb_next_' + direction] = _weakref.ref(blk)
-    _rb_chain[direction] = _weakref.ref(blk)
+def _conv_half(h, bn, cv, act, m, training, parts, pivot, stats_pivot, s16):
+    """One half as its own launch: y = (conv(act(bn(h))) + bias) * m, BatchNorm-apply + act fused in the A-operand load, with the partial sums
+    of y around stats_pivot where asked for and the kernel has that epilogue. Returns (y, parts | None, coef)."""
+    in_bn, coef = _bn_of_half(h, bn, training, parts, pivot)
+    if in_bn is not None:
+        return K.conv2d(h, cv.weight, cv.geom(), bias=cv.bias, in_act=act, out_scale=m, in_bn=in_bn, stats_pivot=stats_pivot, out_bf16=s16)
+    r = K.conv2d(h, cv.weight, cv.geom(), bias=cv.bias, in_scale=coef[0], in_shift=coef[1], in_act=act, out_scale=m, stats_pivot=stats_pivot,
+                 out_bf16=s16)
+    return (r if stats_pivot is not None else (r, None)) + (coef,)
 
 
-def _rb_next_ranges(direction, blk):
-    nb = blk.__dict__.get('_rb_next_' + direction)
-    nb = nb() if nb is not None else None
-    return nb.__dict__.get('_rb_first_' + direction) if nb is not None else None
+def _fwd_fused_gate(call, x, blk, m1, m2, training):
+    """conv1 (+ BatchNorm-2 partial sums), then conv2 + gate + residual (+ the next block's BatchNorm partial sums) in ONE launch.
+    'whole-image': both are launches of csrc/resblock_img.hip, each warming the L2s with the weights of the launch after it;
+    'wino-gate': conv1 as its own convolution, the gate behind the Winograd kernel's epilogue (conv3x3_wino.hip)."""
+    act, st, bn2, cv1, cv2, gate = blk.act, blk.sched, blk.bn2, blk.conv1, blk.conv2, blk.gate
+    whole = call.plan.forward == 'whole-image'
+    if whole:
+        in_bn, coef1 = _bn_of_half(x, blk.bn1, True, call.parts, call.pivot)
+        st.link('fwd', K.rb_weight_ranges(x, cv1.weight, cv1.geom(), False))
+        y1, parts2, coef1 = K.rb_conv(x, cv1.weight, cv1.geom(), cv1.bias, act, m1, in_bn=in_bn, coef=coef1, stats_pivot=bn2.running_mean,
+                                      prefetch=K.rb_weight_ranges(x, cv2.weight, cv2.geom(), False, gate=(gate.weight, gate.geom())))
+    else:
+        y1, parts2, coef1 = _conv_half(x, blk.bn1, cv1, act, m1, True, call.parts, call.pivot, bn2.running_mean, False)
+    in_bn, coef2 = _bn_of_half(y1, bn2, True, parts2, bn2.running_mean)
+    call.out_pivot = coef1[2].detach() if call.plan.gate_stats else None   # this block's own batch mean: inside the data range of the residual stream
+    y2, ab, out, call.out_parts, coef2 = K.rb_conv_gate(y1, cv2.weight, cv2.geom(), cv2.bias, act, m2, gate.weight, gate.geom(), gate.bias, x, act,
+                                                        in_bn=in_bn, coef=coef2, stats_pivot=call.out_pivot,
+                                                        prefetch=st.next_ranges('fwd') if whole else None)
+    return y1, y2, ab, out, coef1, coef2
 
 
-# The last launch of a residual block's backward is the BatchNorm-1 apply, dx = BN1'(dh1; x) + dout. When the tensor x is exactly the
-# output of the previous residual block of the chain (lib/nn.py hands the producer over with the tensor object, like the BatchNorm
-# partials) and that block's backward starts with a kernel that can form its `dout` itself (the fused gate-backward launches), the apply
-# is not launched: the block returns an unwritten dx and leaves a kernels.PendingApply with the consumer, whose first launch computes dx
-# in its prologue and stores it there. This assumes what loss.backward() does: the backward pass continues through the producing block
-# (torch.autograd.grad with respect to a tensor BETWEEN two such blocks would be handed the unwritten dx). LVAE_DEFER_APPLY=0 keeps the launch.
-_DEFER_APPLY = os.environ.get('LVAE_DEFER_APPLY', '1') != '0'
-_DEFER_LARGE = os.environ.get('LVAE_DEFER_APPLY_LARGE', '1') != '0'   # ... also into the persistent gate-backward kernel of the >= 16x16 levels
+def _fwd_per_op(call, x, blk, m1, m2, training):
+    """One launch per convolution (conv1's epilogue writes BatchNorm 2's partial sums), then the gate kernel or the residual add."""
+    act, bn2, gate, s16 = blk.act, blk.bn2, blk.gate, call.plan.bf16_internals
+    want_stats = training and bn2 is not None and bn2.running_mean is not None
+    y1, parts2, coef1 = _conv_half(x, blk.bn1, blk.conv1, act, m1, training, call.parts, call.pivot, bn2.running_mean if want_stats else None, s16)
+    y2, _, coef2 = _conv_half(y1, bn2, blk.conv2, act, m2, training, parts2, bn2.running_mean if bn2 is not None else None, None, s16)
+    if gate is None:
+        return y1, y2, None, K.add(y2, x), coef1, coef2
+    # the block output is (usually) the next block's BatchNorm input: statistics in the gate epilogue, around this block's own batch mean
+    call.out_pivot = coef1[2].detach() if call.plan.gate_stats else None
+    r = K.conv1x1_gate(y2, gate.weight, gate.geom(), gate.bias, x, act, stats_pivot=call.out_pivot)
+    ab, out, call.out_parts = r if call.out_pivot is not None else r + (None,)
+    return y1, y2, ab, out, coef1, coef2
 
 
-def _take_pending(blk, dout):
-    pend = blk.__dict__.pop('_pending_apply', None)
-    if pend is not None and pend.out.data_ptr() != dout.data_ptr():
-        raise K._C.LvaeHipError("deferred BatchNorm-backward apply: the gradient that reached the consuming block is not the tensor the "
-                                "producer left unwritten (the block output has another consumer?)")
-    return pend
-
-
+# The last launch of a residual block's backward is the BatchNorm-1 apply, dx = BN1'(dh1; x) + dout. When the tensor x is exactly the output
+# of the previous residual block of the chain (resblock.Handover) and that block's backward starts with a kernel that can form its `dout`
+# itself (BlockPlan.accepts), the apply is not launched: the block returns an unwritten dx and leaves a kernels.PendingApply with the producer,
+# whose first backward launch computes dx in its prologue and stores it there. This assumes what loss.backward() does: the backward pass goes on
+# through the producing block (torch.autograd.grad w.r.t. a tensor BETWEEN two such blocks would get the unwritten dx). LVAE_DEFER_APPLY=0: never.
 class ResBlockFn(Function):
     """Whole pre-activation residual block ('bacdbacd' / 'bacdbac' recipes of lib/nn.py:64-89, with or without
-    BatchNorm, Dropout2d and the gate) as ONE autograd node:
+    BatchNorm, Dropout2d and the gate) as ONE autograd node, run as its resblock.BlockPlan says:
 
-        y1 = drop1(conv1(act(bn1(x))))   -> one conv launch (BN-apply+act fused in the A-operand load, bias + dropout
-        y2 = drop2(conv2(act(bn2(y1))))     scale in the epilogue) + one statistics pass per BN
+        y1 = drop1(conv1(act(bn1(x))))
+        y2 = drop2(conv2(act(bn2(y1))))
         out = gate(conv1x1(y2)) + x      or  y2 + x
-
-    Saved for backward: x, y1, y2, ab and the BN coefficients; act(bn(.)) is recomputed inside the wgrad loader.
-    """
+    Saved for backward: x, y1, y2, ab and the BN coefficients; act(bn(.)) is recomputed inside the wgrad loader."""
 
     @staticmethod
-    def forward(ctx, x, blk, m1, m2, training, *params):
-        act = blk.act
-        dev = x.device
-        C = x.shape[3]
-        st = []
-        h = x
-        # BatchNorm partials of h written by the epilogue of the kernel that produced it: for x by the previous block's gate
-        # kernel (handed over through blk._in_parts by lib/nn.py), for conv1's output by conv1 itself
-        parts, pivot_in = blk.__dict__.pop('_in_parts', None) or (None, None)
-        # compute_dtype bf16: conv outputs and gate pre-activations of the block (and, in backward, their gradients) live in bf16 where
-        # every kernel involved has that form; the block's input / output (the residual stream) stay fp32
-        # low-resolution levels (whole images per workgroup): two fused launches per direction (csrc/resblock_img.hip)
-        full = (training and blk.gate is not None and blk.bn1 is not None and blk.bn2 is not None and blk.gate.bias is not None and
-                blk.conv1.bias is not None and blk.conv2.bias is not None and blk.bn1.running_mean is not None and
-                blk.bn2.running_mean is not None and x.dtype == torch.float32)
-        rb_fwd, rb_bwd = K.rb_policy(x, blk.conv1.weight, blk.conv1.geom()) if full else (False, False)
-        if rb_fwd:
-            return ResBlockFn._forward_fused(ctx, x, blk, m1, m2, parts, pivot_in, rb_bwd)
-        s16 = (not rb_bwd and blk.gate is not None and blk.bn1 is not None and blk.bn2 is not None and blk.gate.bias is not None and
-               (training or not torch.is_grad_enabled()) and K.resblock_bf16_storage(x, blk.conv1.weight, blk.conv1.geom()))
-        # larger levels (fp32): conv2 and the gate in ONE launch (the gate behind the Winograd kernel's epilogue, conv3x3_wino.hip)
-        fuse_gate = bool(full and not s16 and K._RB_GATE_LARGE and K.rb_rows(x, blk.conv2.weight, blk.conv2.geom()) == 0 and
-                         K.rb_gate_rows(x, blk.conv2.weight, blk.conv2.geom()) > 0)   # (whole-image shapes follow rb_policy above)
-        fused_out = None
-        for i, (bn, cv, m) in enumerate(((blk.bn1, blk.conv1, m1), (blk.bn2, blk.conv2, m2))):
-            nxt = blk.bn2 if i == 0 else None  # conv1's output is BatchNorm 2's input: statistics in conv1's epilogue
-            want_stats = training and nxt is not None and nxt.running_mean is not None
-            if i == 1 and fuse_gate:
-                in_bn = coef = None
-                if parts is not None:
-                    in_bn = (parts, bn.running_mean, bn)
-                else:
-                    coef = K.bn_stats(h, bn.weight, bn.bias, bn.running_mean, bn.running_var, bn.eps, bn.momentum)
-                pivot = st[0][3].detach() if (st[0][3] is not None and _GATE_STATS) else None
-                gate = blk.gate
-                y, ab_f, out_f, oparts_f, (sc, sh, mean, rstd) = K.rb_conv_gate(
-                    h, cv.weight, cv.geom(), cv.bias, act, m, gate.weight, gate.geom(), gate.bias, x, act, in_bn=in_bn, coef=coef, stats_pivot=pivot)
-                fused_out = (ab_f, out_f, oparts_f, pivot)
-                st.append((h, sc, sh, mean, rstd))
-                h = y
-                continue
-            if bn is not None and training and parts is not None:
-                # statistics of h exist as partial sums: finalized inside the convolution where the kernel can (<= 4x4 levels)
-                y, parts_out, (sc, sh, mean, rstd) = K.conv2d(
-                    h, cv.weight, cv.geom(), bias=cv.bias, in_act=act, out_scale=m, in_bn=(parts, pivot_in if i == 0 else bn.running_mean, bn),
-                    stats_pivot=nxt.running_mean if want_stats else None, out_bf16=s16)
-            else:
-                if bn is not None:
-                    if training:
-                        sc, sh, mean, rstd = K.bn_stats(h, bn.weight, bn.bias, bn.running_mean, bn.running_var, bn.eps, bn.momentum)
-                    else:
-                        sc, sh = K.bn_eval_coeffs(bn.weight, bn.bias, bn.running_mean, bn.running_var, bn.eps)
-                        mean = rstd = None
-                else:
-                    sc, sh = _ones_zeros(C, dev)
-                    mean = rstd = None
-                if want_stats:
-                    y, parts_out = K.conv2d(h, cv.weight, cv.geom(), bias=cv.bias, in_scale=sc, in_shift=sh, in_act=act, out_scale=m,
-                                            stats_pivot=nxt.running_mean, out_bf16=s16)
-                else:
-                    y, parts_out = K.conv2d(h, cv.weight, cv.geom(), bias=cv.bias, in_scale=sc, in_shift=sh, in_act=act, out_scale=m,
-                                            out_bf16=s16), None
-            parts = parts_out
-            st.append((h, sc, sh, mean, rstd))
-            h = y
-        y2 = h
-        ab = None
-        blk.__dict__['_out_parts'] = None
-        if fused_out is not None:
-            ab, out, oparts, pivot = fused_out
-            if oparts is not None:
-                blk.__dict__['_out_parts'] = (oparts, pivot)
-        elif blk.gate is not None:
-            if training and blk.bn1 is not None and blk.bn1.running_mean is not None and _GATE_STATS:
-                # the block output is (usually) the next block's BatchNorm input: statistics in the gate kernel's epilogue, around
-                # this block's own running mean (same residual stream: a pivot inside the data range); the copy keeps the pivot
-                # fixed when this block's statistics are updated before the consumer's finalize reads it
-                pivot = st[0][3].detach() if st[0][3] is not None else blk.bn1.running_mean.clone()
-                ab, out, oparts = K.conv1x1_gate(y2, blk.gate.weight, blk.gate.geom(), blk.gate.bias, x, act, stats_pivot=pivot)
-                if oparts is not None:
-                    blk.__dict__['_out_parts'] = (oparts, pivot)
-            else:
-                ab, out = K.conv1x1_gate(y2, blk.gate.weight, blk.gate.geom(), blk.gate.bias, x, act)
-        else:
-            out = K.add(y2, x)
-        ctx.blk, ctx.training, ctx.s16 = blk, training, s16
-        (x0, sc1, sh1, mean1, rstd1), (y1, sc2, sh2, mean2, rstd2) = st
-        ctx.rb_bwd = bool(rb_bwd and ab is not None and K.bn_coef_block(sc1, sh1, mean1, rstd1) and K.bn_coef_block(sc2, sh2, mean2, rstd2))
-        ctx.defer_to = blk.__dict__.pop('_in_src', None)
-        acc = 'f32-dh' if ctx.rb_bwd else None   # what the first backward launch of this block can absorb: a deferred apply with an fp32 dh, or any
-        if (not ctx.rb_bwd and _DEFER_LARGE and training and blk.gate is not None and blk.gate.bias is not None and blk.gate.weight.requires_grad and
-                ab is not None and K.gate_bwd_fused_ok(x, blk.gate.weight, blk.gate.geom())):
-            acc = 'any-dh'
-        blk.__dict__['_accepts_deferred'] = acc
-        ctx.save_for_backward(x0, y1, y2, ab, sc1, sh1, mean1, rstd1, sc2, sh2, mean2, rstd2, m1, m2)
-        return out
-
-    @staticmethod
-    def _forward_fused(ctx, x, blk, m1, m2, parts, pivot_in, rb_bwd):
-        """conv1 (+ BatchNorm-2 partial sums) and conv2 + gate + residual (+ the next block's BatchNorm partial sums): two launches."""
-        act = blk.act
-        bn1, bn2, cv1, cv2, gate = blk.bn1, blk.bn2, blk.conv1, blk.conv2, blk.gate
-        in_bn = coef1 = None
-        if parts is not None and parts.has_pivot:
-            in_bn = (parts, pivot_in, bn1)
-        elif parts is not None:
-            N, H, W, _ = x.shape
-            coef1 = K.bn_finalize_parts(parts.rows_view(), N * H * W, pivot_in, bn1.weight, bn1.bias, bn1.running_mean, bn1.running_var,
-                                        bn1.eps, bn1.momentum)
-        else:
-            coef1 = K.bn_stats(x, bn1.weight, bn1.bias, bn1.running_mean, bn1.running_var, bn1.eps, bn1.momentum)
-        _rb_link('fwd', blk, K.rb_weight_ranges(x, cv1.weight, cv1.geom(), False))
-        nxt = K.rb_weight_ranges(x, cv2.weight, cv2.geom(), False, gate=(gate.weight, gate.geom()))   # what the second launch will stream
-        y1, parts2, coef1 = K.rb_conv(x, cv1.weight, cv1.geom(), cv1.bias, act, m1, in_bn=in_bn, coef=coef1, stats_pivot=bn2.running_mean,
-                                      prefetch=nxt)
-        blk.__dict__['_out_parts'] = None
-        pivot = coef1[2].detach() if _GATE_STATS else None   # this block's own batch mean: inside the data range of the residual stream
-        y2, ab, out, oparts, coef2 = K.rb_conv_gate(y1, cv2.weight, cv2.geom(), cv2.bias, act, m2, gate.weight, gate.geom(), gate.bias, x, act,
-                                                    in_bn=(parts2, bn2.running_mean, bn2), stats_pivot=pivot,
-                                                    prefetch=_rb_next_ranges('fwd', blk))
-        if oparts is not None:
-            blk.__dict__['_out_parts'] = (oparts, pivot)
-        ctx.blk, ctx.training, ctx.s16 = blk, True, False
-        ctx.rb_bwd = bool(rb_bwd and K.bn_coef_block(*coef1) and K.bn_coef_block(*coef2))
-        ctx.defer_to = blk.__dict__.pop('_in_src', None)
-        blk.__dict__['_accepts_deferred'] = 'f32-dh' if ctx.rb_bwd else None
-        ctx.save_for_backward(x, y1, y2, ab, coef1[0], coef1[1], coef1[2], coef1[3], coef2[0], coef2[1], coef2[2], coef2[3], m1, m2)
+    def forward(ctx, x, blk, m1, m2, training, call, *params):
+        plan, fwd = call.plan, _fwd_fused_gate if call.plan.forward in ('whole-image', 'wino-gate') else _fwd_per_op
+        y1, y2, ab, out, coef1, coef2 = fwd(call, x, blk, m1, m2, training)
+        if plan.backward == 'whole-image' and not (K.bn_coef_block(*coef1) and K.bn_coef_block(*coef2)):
+            call.plan = plan = plan._replace(backward='composed', accepts=None)
+        ctx.blk, ctx.plan, ctx.training, ctx.defer = blk, plan, training, call.defer
+        ctx.save_for_backward(x, y1, y2, ab, *coef1, *coef2, m1, m2)
         return out
 
     @staticmethod
     def backward(ctx, dout):
-        blk = ctx.blk
-        act = blk.act
+        blk, plan, act = ctx.blk, ctx.plan, ctx.blk.act
         x, y1, y2, ab, sc1, sh1, mean1, rstd1, sc2, sh2, mean2, rstd2, m1, m2 = ctx.saved_tensors
+        coef1, coef2 = (sc1, sh1, mean1, rstd1), (sc2, sh2, mean2, rstd2)
         dout = _c(dout)
-        hw = (x.shape[1], x.shape[2])
-        s16 = ctx.s16   # bf16-stored block internals: every launch below then has to take the bf16-storage kernel (it raises otherwise)
-        if ctx.rb_bwd:
-            # low-resolution levels: gate backward + dgrad conv2, then BatchNorm-2 backward + dgrad conv1, then the BatchNorm-1 apply
-            gate, w2, w1, bn2, bn1 = blk.gate, blk.conv2.weight, blk.conv1.weight, blk.bn2, blk.bn1
-            gw = gate.weight
-            _rb_link('bwd', blk, K.rb_weight_ranges(dout, w2, blk.conv2.geom(), True, gate=(gw, gate.geom()), gate_bwd=True))
-            dab, dy2, dh2, parts2 = K.rb_gate_dgrad(dout, ab, gw, gate.geom(), act, m2, w2, blk.conv2.geom(), bn_bwd=(y1, sc2, act),
-                                                    prefetch=K.rb_weight_ranges(dout, w1, blk.conv1.geom(), True), apply=_take_pending(blk, dout))
-            if gw.requires_grad:
-                wgrad(y2, dab, gw, gate.geom(), grad_buf(gw), grad_buf(gate.bias))
-            wgrad(y1, dy2, w2, blk.conv2.geom(), grad_buf(w2), grad_buf(blk.conv2.bias), in_scale=sc2, in_shift=sh2, in_act=act)
-            dy1, dh1, parts1 = K.rb_apply_dgrad(parts2, dh2, y1, sc2, act, grad_buf(bn2.weight), grad_buf(bn2.bias), m1, w1, blk.conv1.geom(),
-                                                bn_bwd=(x, sc1, act), prefetch=_rb_next_ranges('bwd', blk))
-            wgrad(x, dy1, w1, blk.conv1.geom(), grad_buf(w1), grad_buf(blk.conv1.bias), in_scale=sc1, in_shift=sh1, in_act=act)
-            dx = ResBlockFn._final_apply(ctx, parts1, dh1, x, sc1, sh1, mean1, rstd1, act, bn1, dout)
-            return (dx, None, None, None, None) + (None,) * (len(ctx.needs_input_grad) - 5)
-        pend = _take_pending(blk, dout)
-        if blk.gate is not None:
-            gw = blk.gate.weight
-            dy2 = None
-            if gw.requires_grad and blk.gate.bias is not None:
-                # large levels: gate derivative, dgrad and the gate convolution's weight gradient in one persistent kernel
-                dy2 = K.conv1x1_gate_bwd_wgrad(dout, ab, y2, gw, blk.gate.geom(), act, grad_buf(gw), grad_buf(blk.gate.bias), out_scale=m2,
-                                               out_bf16=s16, apply=pend)
-                if dy2 is not None:
-                    pend = None
-            if pend is not None:   # (the fused kernel did not take the shape after all: the apply gets its launch, writing the tensor dout is)
-                pend = ResBlockFn._run_pending(pend)
-            if dy2 is None:
-                if s16:
-                    raise K._C.LvaeHipError("bf16-stored residual block: the fused gate backward did not take this shape")
-                dab, dy2 = K.conv1x1_gate_bwd(dout, ab, gw, blk.gate.geom(), act, out_scale=m2)
-                wgrad(y2, dab, gw, blk.gate.geom(), grad_buf(gw), grad_buf(blk.gate.bias))
+        if plan.backward == 'whole-image':
+            dh1, parts1 = _bwd_whole_image(blk, dout, x, y1, y2, ab, coef1, coef2, m1, m2)
         else:
-            if pend is not None:
-                pend = ResBlockFn._run_pending(pend)
-            dy2 = K.scale_rows_add(dout, m2, None) if m2 is not None else dout
-        # second half
-        w2 = blk.conv2.weight
-        wgrad(y1, dy2, w2, blk.conv2.geom(), grad_buf(w2), grad_buf(blk.conv2.bias), in_scale=sc2, in_shift=sh2, in_act=act)
-        bn2 = blk.bn2
-        train2 = bn2 is not None and ctx.training
-        parts2 = None
-        if train2 and K.bn_coef_block(sc2, sh2, mean2, rstd2):  # BatchNorm-backward sums in the dgrad kernel's epilogue
-            dh2, parts2 = K.conv2d_dgrad(dy2, w2, blk.conv2.geom(), hw, bn_bwd=(y1, sc2, act), out_bf16=s16)
+            dy2 = _bwd_gate(blk, plan, dout, y2, ab, m2)
+            cv1, bn2 = blk.conv1, blk.bn2
+            dh2, parts2 = _bwd_half(ctx, blk.conv2, bn2, y1, dy2, coef2)
+            absorbed = (plan.wgrad_absorbs_apply and parts2 is not None and _side['stream'] is None and dh2.dtype == torch.float32)
+            if absorbed:
+                # >= 16x16 levels (fp32): the BatchNorm-2 apply runs inside conv1's weight-gradient kernel, which needs its result as an operand
+                # anyway (and stores it for the dgrad below): one launch, its finalize and one tensor pass less
+                dy1 = K.conv2d_wgrad_apply(x, cv1.weight, cv1.geom(), grad_buf(cv1.weight), grad_buf(cv1.bias), parts2, dh2, y1, sc2, act,
+                                           grad_buf(bn2.weight), grad_buf(bn2.bias), drop=m1, in_scale=sc1, in_shift=sh1, in_act=act)
+            else:
+                dy1 = _bwd_apply(ctx, bn2, parts2, dh2, y1, coef2, drop=m1, out_bf16=plan.bf16_internals)
+            dh1, parts1 = _bwd_half(ctx, cv1, blk.bn1, x, dy1, coef1, wgrad_done=absorbed)
+        if parts1 is not None and ctx.defer is not None and (dh1.dtype == torch.float32 or ctx.defer[1] == 'any-dh') and K.bn_coef_block(*coef1):
+            dx = torch.empty_like(x)   # left to the first backward launch of the block that produced x
+            ctx.defer[0].pending = K.PendingApply(parts1, dh1, x, sc1, act, grad_buf(blk.bn1.weight), grad_buf(blk.bn1.bias), dout, dx)
         else:
-            dh2 = K.conv2d_dgrad(dy2, w2, blk.conv2.geom(), hw)
-        w1 = blk.conv1.weight
-        wg1_done = False
-        if (parts2 is not None and _WGRAD_APPLY and not s16 and _side['stream'] is None and w1.requires_grad and dh2.dtype == torch.float32 and
-                x.shape[2] <= _WGRAD_APPLY_MAXW and K.conv2d_wgrad_apply_ok(x, w1, blk.conv1.geom())):
-            # >= 16x16 levels (fp32): the BatchNorm-2 apply runs inside conv1's weight-gradient kernel, which needs its result as an operand
-            # anyway (and stores it for the dgrad below): one launch, its finalize and one tensor pass less
-            dy1 = K.conv2d_wgrad_apply(x, w1, blk.conv1.geom(), grad_buf(w1), grad_buf(blk.conv1.bias), parts2, dh2, y1, sc2, act,
-                                       grad_buf(bn2.weight), grad_buf(bn2.bias), drop=m1, in_scale=sc1, in_shift=sh1, in_act=act)
-            wg1_done = True
-        elif parts2 is not None:
-            dy1 = K.affine_act_bwd_parts(parts2, dh2, y1, sc2, sh2, act, mean2, rstd2, grad_buf(bn2.weight), grad_buf(bn2.bias),
-                                         drop=m1, out_bf16=s16)
-        else:
-            dy1 = K.affine_act_bwd(dh2, y1, sc2, sh2, act, train2, mean2, rstd2,
-                                   grad_buf(bn2.weight) if train2 else None, grad_buf(bn2.bias) if train2 else None, drop=m1)
-        # first half
-        if not wg1_done:
-            wgrad(x, dy1, w1, blk.conv1.geom(), grad_buf(w1), grad_buf(blk.conv1.bias), in_scale=sc1, in_shift=sh1, in_act=act)
-        bn1 = blk.bn1
-        train1 = bn1 is not None and ctx.training
-        parts1 = None
-        if train1 and K.bn_coef_block(sc1, sh1, mean1, rstd1):
-            dh1, parts1 = K.conv2d_dgrad(dy1, w1, blk.conv1.geom(), hw, bn_bwd=(x, sc1, act), out_bf16=s16)
-        else:
-            dh1 = K.conv2d_dgrad(dy1, w1, blk.conv1.geom(), hw)
-        if parts1 is not None:
-            dx = ResBlockFn._final_apply(ctx, parts1, dh1, x, sc1, sh1, mean1, rstd1, act, bn1, dout)
-        else:
-            dx = K.affine_act_bwd(dh1, x, sc1, sh1, act, train1, mean1, rstd1,
-                                  grad_buf(bn1.weight) if train1 else None, grad_buf(bn1.bias) if train1 else None, add=dout)
-        return (dx, None, None, None, None) + (None,) * (len(ctx.needs_input_grad) - 5)
+            dx = _bwd_apply(ctx, blk.bn1, parts1, dh1, x, coef1, add=dout)
+        return (dx, None, None, None, None, None) + (None,) * (len(ctx.needs_input_grad) - 6)
 
 
-    @staticmethod
-    def _run_pending(p):
-        """The launch a deferred apply would have been (its consumer could not absorb it after all)."""
-        n = p.coef0.numel()
-        coef = p.coef0.new_empty(0).set_(p.coef0.untyped_storage(), p.coef0.storage_offset(), (4, n), (n, 1))
-        K.affine_act_bwd_parts(p.parts, p.dh, p.x, coef[0], coef[1], p.act, coef[2], coef[3], p.dgamma, p.dbeta, add=p.add, out=p.out)
-        return None
+def _bwd_whole_image(blk, dout, x, y1, y2, ab, coef1, coef2, m1, m2):
+    """Low-resolution levels: gate backward + dgrad conv2, then BatchNorm-2 backward + dgrad conv1. Returns (dh1, its partial sums)."""
+    act, st, gate, cv2, cv1, bn2 = blk.act, blk.sched, blk.gate, blk.conv2, blk.conv1, blk.bn2
+    gw, w2, w1 = gate.weight, cv2.weight, cv1.weight
+    st.link('bwd', K.rb_weight_ranges(dout, w2, cv2.geom(), True, gate=(gw, gate.geom()), gate_bwd=True))
+    dab, dy2, dh2, parts2 = K.rb_gate_dgrad(dout, ab, gw, gate.geom(), act, m2, w2, cv2.geom(), bn_bwd=(y1, coef2[0], act),
+                                            prefetch=K.rb_weight_ranges(dout, w1, cv1.geom(), True), apply=st.take_pending(dout))
+    if gw.requires_grad:
+        wgrad(y2, dab, gw, gate.geom(), grad_buf(gw), grad_buf(gate.bias))
+    wgrad(y1, dy2, w2, cv2.geom(), grad_buf(w2), grad_buf(cv2.bias), in_scale=coef2[0], in_shift=coef2[1], in_act=act)
+    dy1, dh1, parts1 = K.rb_apply_dgrad(parts2, dh2, y1, coef2[0], act, grad_buf(bn2.weight), grad_buf(bn2.bias), m1, w1, cv1.geom(),
+                                        bn_bwd=(x, coef1[0], act), prefetch=st.next_ranges('bwd'))
+    wgrad(x, dy1, w1, cv1.geom(), grad_buf(w1), grad_buf(cv1.bias), in_scale=coef1[0], in_shift=coef1[1], in_act=act)
+    return dh1, parts1
 
-    @staticmethod
-    def _final_apply(ctx, parts1, dh1, x, sc1, sh1, mean1, rstd1, act, bn1, dout):
-        """dx = BN1'(dh1; x) + dout: launched here, or left to the first backward launch of the block that produced x (see _DEFER_APPLY)."""
-        tgt = ctx.defer_to
-        acc = tgt.__dict__.get('_accepts_deferred') if tgt is not None else None
-        if (_DEFER_APPLY and acc is not None and x.dtype == torch.float32 and (dh1.dtype == torch.float32 or acc == 'any-dh') and
-                K.bn_coef_block(sc1, sh1, mean1, rstd1)):
-            dx = torch.empty_like(x)
-            tgt.__dict__['_pending_apply'] = K.PendingApply(parts1, dh1, x, sc1, act, grad_buf(bn1.weight), grad_buf(bn1.bias), dout, dx)
-            return dx
-        return K.affine_act_bwd_parts(parts1, dh1, x, sc1, sh1, act, mean1, rstd1, grad_buf(bn1.weight), grad_buf(bn1.bias), add=dout)
+
+def _bwd_gate(blk, plan, dout, y2, ab, m2):
+    """dy2, the gradient w.r.t. conv2's output, from dout through the gate (or the residual add)."""
+    gate, act, s16 = blk.gate, blk.act, plan.bf16_internals   # (bf16-stored internals: every launch has to take the bf16-storage kernel)
+    if gate is None:
+        return K.scale_rows_add(dout, m2, None) if m2 is not None else dout
+    gw = gate.weight
+    if plan.backward == 'persistent-gate':
+        # large levels: gate derivative, dgrad and the gate convolution's weight gradient in one persistent kernel
+        dy2 = K.conv1x1_gate_bwd_wgrad(dout, ab, y2, gw, gate.geom(), act, grad_buf(gw), grad_buf(gate.bias), out_scale=m2, out_bf16=s16,
+                                       apply=blk.sched.take_pending(dout))
+        if dy2 is None:
+            raise K._C.LvaeHipError("residual block: the persistent gate backward the block was planned with did not take this shape")
+        return dy2
+    if s16:
+        raise K._C.LvaeHipError("bf16-stored residual block: the fused gate backward did not take this shape")
+    dab, dy2 = K.conv1x1_gate_bwd(dout, ab, gw, gate.geom(), act, out_scale=m2)
+    wgrad(y2, dab, gw, gate.geom(), grad_buf(gw), grad_buf(gate.bias))
+    return dy2
+
+
+def _bwd_half(ctx, cv, bn, h, dy, coef, wgrad_done=False):
+    """Weight gradient and dgrad of one half's convolution y = conv(act(bn(h))): returns (dh, parts) with dh the gradient w.r.t. act(bn(h))
+    and parts the BatchNorm-backward sums where the dgrad kernel's epilogue wrote them (None: a reduction pass has to)."""
+    w, g, act = cv.weight, cv.geom(), ctx.blk.act
+    if not wgrad_done:
+        wgrad(h, dy, w, g, grad_buf(w), grad_buf(cv.bias), in_scale=coef[0], in_shift=coef[1], in_act=act)
+    if bn is not None and ctx.training and K.bn_coef_block(*coef):
+        return K.conv2d_dgrad(dy, w, g, h.shape[1:3], bn_bwd=(h, coef[0], act), out_bf16=ctx.plan.bf16_internals)
+    return K.conv2d_dgrad(dy, w, g, h.shape[1:3]), None
+
+
+def _bwd_apply(ctx, bn, parts, dh, h, coef, drop=None, add=None, out_bf16=False):
+    """Gradient through act(bn(h)); drop: the producer's Dropout2d mask, add: the residual gradient; parts: the reduction is done already."""
+    sc, sh, mean, rstd = coef
+    train = bn is not None and ctx.training
+    dgamma, dbeta = (grad_buf(bn.weight), grad_buf(bn.bias)) if train else (None, None)
+    if parts is not None:
+        return K.affine_act_bwd_parts(parts, dh, h, sc, sh, ctx.blk.act, mean, rstd, dgamma, dbeta, drop=drop, add=add, out_bf16=out_bf16)
+    return K.affine_act_bwd(dh, h, sc, sh, ctx.blk.act, train, mean, rstd, dgamma, dbeta, drop=drop, add=add)
+
+
+def residual_block(x, blk, m1, m2):
+    """`call`: what the node is told beside its tensors (the plan; what came with x) and reports back (the plan as run; the output's partials)."""
+    training = blk.training
+    blk.sched.pending = None   # (left behind by a backward pass that was abandoned)
+    parts, pivot, defer = RB.received(x, training)
+    call = SimpleNamespace(plan=RB.plan_block(blk, x, training), parts=parts, pivot=pivot, defer=defer, out_parts=None, out_pivot=None)
+    out = ResBlockFn.apply(x, blk, m1, m2, training, call, *blk.parameters())
+    return RB.tagged(out, blk, call.plan, call.out_parts, call.out_pivot)
 
 
 # ----------------------------------------------------------------------------------------------------------------
@@ -463,15 +344,7 @@ class BnDropFn(Function):
 
     @staticmethod
     def forward(ctx, x, bn, mask, training, *params):
-        if bn is not None:
-            if training:
-                sc, sh, mean, rstd = K.bn_stats(x, bn.weight, bn.bias, bn.running_mean, bn.running_var, bn.eps, bn.momentum)
-            else:
-                sc, sh = K.bn_eval_coeffs(bn.weight, bn.bias, bn.running_mean, bn.running_var, bn.eps)
-                mean = rstd = None
-        else:
-            sc, sh = _ones_zeros(x.shape[3], x.device)
-            mean = rstd = None
+        _, (sc, sh, mean, rstd) = _bn_of_half(x, bn, training, None, None)
         y = K.affine_act(x, sc, sh, None, row_scale=mask)
         ctx.bn, ctx.training = bn, training
         ctx.save_for_backward(x, sc, sh, mean, rstd, mask)
@@ -663,9 +536,7 @@ class SegmentMarkFn(Function):
 
 def segment_mark(x, tracker, seg):
     y = SegmentMarkFn.apply(x, tracker, seg)
-    parts = getattr(x, '_lvae_bn_parts', None)   # BatchNorm partials travel with the tensor object (lib/nn.py)
-    if parts is not None:
-        y._lvae_bn_parts = parts
+    RB.passed_on(x, (y,))
     return y
 
 
@@ -693,10 +564,7 @@ def fanout(x, n):
     if n <= 1 or not (torch.is_grad_enabled() and x.requires_grad):
         return (x,) * n
     outs = FanoutFn.apply(x, n)
-    parts = getattr(x, '_lvae_bn_parts', None)   # BatchNorm partials travel with the tensor object (lib/nn.py)
-    if parts is not None:
-        for o in outs:
-            o._lvae_bn_parts = parts
+    RB.passed_on(x, outs)
     return outs
 
 

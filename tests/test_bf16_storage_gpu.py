@@ -158,8 +158,9 @@ def test_residual_block_with_bf16_stored_internals(K, shape, monkeypatch):
     N, H, W = shape
     # (the 8x8 level of a training step takes the fused whole-image launches of resblock_img.hip, which keep fp32 storage; this test pins
     # the one-kernel-per-op bf16-storage path, which stays the path of the >= 16x16 levels and of every shape those kernels do not take)
-    monkeypatch.setattr(K, '_RB_FWD_MIN_HW', 0)
-    monkeypatch.setattr(K, '_RB_BWD_MIN_HW', 0)
+    from lvae_amd.resblock import switches
+    monkeypatch.setattr(switches, 'rb_fwd_min_hw', 0)
+    monkeypatch.setattr(switches, 'rb_bwd_min_hw', 0)
     torch.manual_seed(2)
     from lvae_amd.arena import ParamArena
     blk = ResidualGatedBlock(64, 'elu', batchnorm=True, block_type='bacdbacd', dropout=0.2).cuda().train()
