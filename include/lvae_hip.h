@@ -589,6 +589,17 @@ int lvae_eval_totals_f64(const double* state, int32_t N, int32_t L, int32_t S, d
 int lvae_adamax_step_f32(float* p, const float* g, float* exp_avg, float* exp_inf, const float* mask, int64_t n,
                          float lr, float beta1, float beta2, float eps, float weight_decay, const float* gscale,
                          const uint64_t* step_count, void* stream);
+/* The same update, and in the same pass an exponential moving average of the updated parameters: ema[i] += (p_new[i] - ema[i]) * (1 - d)
+ * (the lerp form, three fp32 roundings) with d = min(decay, (1 + n) / (10 + n)) in fp32, n = step_count[0] = the steps completed BEFORE
+ * this one, read on the device, so a captured step replays along the ramp (d = 0.1 at the first step: a young average follows the
+ * weights; decay = 0 makes ema a copy of p). ema [n], 16-byte aligned; 0 <= decay < 1. p, exp_avg and exp_inf come out bit for bit as
+ * from lvae_adamax_step_f32; elements frozen by `mask` keep their ema as well. One more 16-byte load and store per four elements. */
+int lvae_adamax_ema_step_f32(float* p, const float* g, float* exp_avg, float* exp_inf, const float* mask, int64_t n,
+                             float lr, float beta1, float beta2, float eps, float weight_decay, const float* gscale,
+                             const uint64_t* step_count, float* ema, float decay, void* stream);
+/* a[0:n] <-> b[0:n] in one pass (16-byte aligned, not overlapping): the averaged weights exchanged IN PLACE with the trainable prefix of
+ * the parameter arena for a test pass and back, so captured graphs and parameter views keep their addresses. */
+int lvae_swap_f32(float* a, float* b, int64_t n, void* stream);
 /* out[0] = sqrt(sum x^2) ; workspace >= lvae_sumsq_workspace(n) bytes; deterministic two-pass */
 size_t lvae_sumsq_workspace(int64_t n);
 int lvae_l2norm_f32(const float* x, int64_t n, float* out, void* workspace, size_t workspace_bytes, void* stream);

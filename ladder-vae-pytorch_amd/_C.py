@@ -150,6 +150,8 @@ SIGNATURES = {
     'lvae_eval_totals_f64': (C.c_int, [_P, _I, _I, _I, _P, _P]),
     'lvae_iw_logmeanexp_f32': (C.c_int, [_P, _I, _I, _P, _P]),
     'lvae_adamax_step_f32': (C.c_int, [_P, _P, _P, _P, _P, _L, _F, _F, _F, _F, _F, _P, _P, _P]),
+    'lvae_adamax_ema_step_f32': (C.c_int, [_P, _P, _P, _P, _P, _L, _F, _F, _F, _F, _F, _P, _P, _P, _F, _P]),
+    'lvae_swap_f32': (C.c_int, [_P, _P, _L, _P]),
     'lvae_sumsq_workspace': (_Z, [_L]),
     'lvae_l2norm_f32': (C.c_int, [_P, _L, _P, _P, _Z, _P]),
     'lvae_rng_fill_f32': (C.c_int, [_P, _L, _I, _F, _F, _U, _P, _U, _P]),

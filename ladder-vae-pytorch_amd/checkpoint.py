@@ -4,7 +4,9 @@ The reference saves `model.state_dict()` through boilr (absent). The key scheme 
 identical, but its parameters are strided views of one flat arena; `state_dict_reference_layout` returns plain contiguous
 CPU tensors in the reference's memory layout, so a file written here loads into the reference's `LadderVAE` with
 `load_state_dict` and vice versa. Optimiser state is stored per parameter name (torch.optim.Adamax names: exp_avg,
-exp_inf) so it can be re-attached to either implementation.
+exp_inf) so it can be re-attached to either implementation. When the optimizer keeps an exponential moving average of the weights, the file
+also holds `'ema'`: a second complete state dict of the same keys, shapes and layout whose trainable parameters are the averages (buffers
+and frozen parameters as in `'model'`), so the averaged weights load into the reference's `LadderVAE` the same way.
 """
 import torch
 
@@ -32,6 +34,26 @@ def optimizer_state_by_name(model, optimizer):
             'eps': optimizer.eps, 'weight_decay': optimizer.weight_decay}
 
 
+def _ema_views(model, optimizer):
+    """{param_name: view of optimizer.ema with the parameter's logical shape} for every trainable parameter."""
+    arena = model.pack()
+    optimizer._state()
+    out = {}
+    for name, p in model.named_parameters():
+        if p.requires_grad:
+            out[name] = torch.as_strided(optimizer.ema, p.shape, p.stride(), arena.slots[name][0])
+    return out
+
+
+def ema_state_dict_reference_layout(model, optimizer):
+    """`state_dict_reference_layout(model)` with every trainable parameter replaced by its average (BatchNorm running statistics and frozen
+    parameters are not averaged: they are the model's)."""
+    sd = state_dict_reference_layout(model)
+    for name, v in _ema_views(model, optimizer).items():
+        sd[name] = v.detach().to('cpu').contiguous().clone()
+    return sd
+
+
 def noise_state(model):
     """{'seed', 'step'} of the model's on-device Philox stream (None for any other noise source)."""
     from .noise import PhiloxNoise
@@ -47,17 +69,24 @@ def save_checkpoint(path, model, optimizer=None):
     ck = {'model': state_dict_reference_layout(model), 'global_step': int(model.global_step)}
     if optimizer is not None:
         ck['optimizer'] = optimizer_state_by_name(model, optimizer)
+        if getattr(optimizer, 'ema_decay', 0.0) > 0.0:
+            ck['ema'] = ema_state_dict_reference_layout(model, optimizer)
+            ck['ema_decay'] = optimizer.ema_decay
     nz = noise_state(model)
     if nz is not None:
         ck['noise'] = nz
     if getattr(model, 'global_step_dev', None) is not None:
         ck['global_step_dev'] = int(model.global_step_dev.item())
+    tn = getattr(model, 'test_noise', None)
+    if tn is not None and getattr(tn, 'step', None) is not None:
+        ck['test_noise'] = {'step': int(tn.step.item())}   # where the test passes' own stream stands: resumed test lines repeat exactly
     torch.save(ck, path)
 
 
 def load_checkpoint(path, model, optimizer=None):
     """Loads a file written by `save_checkpoint` (with the noise stream's position and the device global-step counter when it holds
-    them), or a bare reference `state_dict` file. Load before a TrainStep captures its graph: the graph keeps the counters it saw."""
+    them), or a bare reference `state_dict` file. Load before a TrainStep captures its graph: the graph keeps the counters it saw.
+    An averaging optimizer gets its average from the file's 'ema'; from a file without one the average starts at the loaded weights."""
     ck = torch.load(path, map_location='cpu')
     sd = ck['model'] if isinstance(ck, dict) and 'model' in ck else ck
     model.load_state_dict(sd)
@@ -68,6 +97,8 @@ def load_checkpoint(path, model, optimizer=None):
             dev = next(model.parameters()).device
             model.noise.seed = int(ck['noise']['seed'])
             model.noise.step = torch.full((1,), int(ck['noise']['step']), dtype=torch.int64, device=dev)
+        if 'test_noise' in ck:
+            model.test_noise_start = int(ck['test_noise']['step'])   # evaluate.test_pass starts its own stream there
         if getattr(model, 'global_step_dev', None) is not None or 'global_step_dev' in ck:
             dev = next(model.parameters()).device
             model.global_step_dev = torch.full((1,), int(ck.get('global_step_dev', model.global_step)), dtype=torch.int64, device=dev)
@@ -81,4 +112,23 @@ def load_checkpoint(path, model, optimizer=None):
             torch.as_strided(optimizer.exp_avg, p.shape, p.stride(), off).copy_(st['exp_avg'])
             torch.as_strided(optimizer.exp_inf, p.shape, p.stride(), off).copy_(st['exp_inf'])
         optimizer.step_count.fill_(int(ck['optimizer']['step']))
+    if optimizer is not None and getattr(optimizer, 'ema_decay', 0.0) > 0.0:
+        arena = model.pack()
+        optimizer._state()
+        if isinstance(ck, dict) and 'model' in ck and 'ema' in ck:
+            for name, view in _ema_views(model, optimizer).items():
+                view.copy_(ck['ema'][name])
+        else:
+            optimizer.ema.copy_(arena.params[:arena.n_train])
+    return ck
+
+
+def load_ema_weights(path, model):
+    """Loads the AVERAGED weights of a file written by `save_checkpoint` into the model (offline evaluation of the average). A file without
+    'ema' (an averaging-free run, an older file, a bare state_dict) is refused."""
+    ck = torch.load(path, map_location='cpu')
+    if not (isinstance(ck, dict) and 'model' in ck and 'ema' in ck):
+        raise ValueError("%s holds no averaged weights (no 'ema' entry): it was not written by a run with --ema-decay > 0" % path)
+    model.load_state_dict(ck['ema'])
+    model.global_step = int(ck.get('global_step', model.global_step))
     return ck

@@ -270,19 +270,29 @@ __global__ __launch_bounds__(256) void iw_online_kernel(const float* __restrict_
 // ---------------------------------------------------------------------------------------------------------
 // Adamax over the flat arena (torch.optim.Adamax semantics) and L2 norm
 // ---------------------------------------------------------------------------------------------------------
+// EMA: the same pass also keeps an exponential moving average of the updated parameters, ema += (p_new - ema) * (1 - d), with the decay
+// ramp d = min(decay, (1 + n) / (10 + n)) over the n completed steps read from the device counter (a replayed graph follows the ramp).
+template <bool EMA>
 __global__ __launch_bounds__(256) void adamax_kernel(float* __restrict__ p, const float* __restrict__ g,
                                                       float* __restrict__ m, float* __restrict__ u,
                                                       const float* __restrict__ mask, int64_t n4, float lr, float b1,
                                                       float b2, float eps, float wd, const float* gscale,
-                                                      const uint64_t* step_count) {
+                                                      const uint64_t* step_count, float* __restrict__ ema, float decay) {
   const float step = (float)(step_count[0] + 1);
   const float clr = lr / (1.f - powf(b1, step));
   const float gs = gscale ? gscale[0] : 1.f;
+  float w = 0.f;   // 1 - d
+  if (EMA) {
+    const float n = (float)step_count[0];
+    w = 1.f - fminf(decay, (1.f + n) / (10.f + n));
+  }
   for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < n4; i += (int64_t)gridDim.x * 256) {
     f32x4 pv = reinterpret_cast<f32x4*>(p)[i], gv = reinterpret_cast<const f32x4*>(g)[i];
     f32x4 mv = reinterpret_cast<f32x4*>(m)[i], uv = reinterpret_cast<f32x4*>(u)[i];
     f32x4 mk = {1.f, 1.f, 1.f, 1.f};
     if (mask) mk = reinterpret_cast<const f32x4*>(mask)[i];
+    f32x4 ev = {0.f, 0.f, 0.f, 0.f};
+    if (EMA) ev = reinterpret_cast<f32x4*>(ema)[i];
 #pragma unroll
     for (int j = 0; j < 4; ++j) {
       if (mk[j] == 0.f) continue;
@@ -291,10 +301,28 @@ __global__ __launch_bounds__(256) void adamax_kernel(float* __restrict__ p, cons
       mv[j] = mv[j] + (gg - mv[j]) * (1.f - b1);  // lerp, as torch
       uv[j] = fmaxf(uv[j] * b2, fabsf(gg) + eps);
       pv[j] -= clr * mv[j] / uv[j];
+      if (EMA) ev[j] = ev[j] + (pv[j] - ev[j]) * w;
     }
     reinterpret_cast<f32x4*>(p)[i] = pv;
     reinterpret_cast<f32x4*>(m)[i] = mv;
     reinterpret_cast<f32x4*>(u)[i] = uv;
+    if (EMA) reinterpret_cast<f32x4*>(ema)[i] = ev;
+  }
+}
+
+// a <-> b in one pass (the averaged weights swapped into the parameter arena for a test pass, and back)
+__global__ __launch_bounds__(256) void swap_kernel(float* __restrict__ a, float* __restrict__ b, int64_t n) {
+  const int64_t n4 = n >> 2;
+  for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < n4; i += (int64_t)gridDim.x * 256) {
+    const f32x4 av = reinterpret_cast<f32x4*>(a)[i], bv = reinterpret_cast<f32x4*>(b)[i];
+    reinterpret_cast<f32x4*>(a)[i] = bv;
+    reinterpret_cast<f32x4*>(b)[i] = av;
+  }
+  if (blockIdx.x == 0 && threadIdx.x < (n & 3)) {
+    const int64_t k = (n4 << 2) + threadIdx.x;
+    const float av = a[k];
+    a[k] = b[k];
+    b[k] = av;
   }
 }
 
@@ -463,9 +491,31 @@ extern "C" int lvae_adamax_step_f32(float* p, const float* g, float* exp_avg, fl
                                     const uint64_t* step_count, void* stream) {
   LVAE_REQUIRE(p && g && exp_avg && exp_inf && step_count && n > 0, LVAE_EINVAL, "lvae_adamax_step_f32: bad args");
   LVAE_REQUIRE(n % 4 == 0, LVAE_EALIGN, "lvae_adamax_step_f32: arena length %lld must be a multiple of 4", (long long)n);
-  hipLaunchKernelGGL(adamax_kernel, dim3(grid_for(n / 4, 256)), dim3(256), 0, (hipStream_t)stream, p, g, exp_avg, exp_inf,
-                     mask, n / 4, lr, beta1, beta2, eps, weight_decay, gscale, step_count);
+  hipLaunchKernelGGL(adamax_kernel<false>, dim3(grid_for(n / 4, 256)), dim3(256), 0, (hipStream_t)stream, p, g, exp_avg, exp_inf,
+                     mask, n / 4, lr, beta1, beta2, eps, weight_decay, gscale, step_count, (float*)nullptr, 0.f);
   LVAE_LAUNCH_CHECK("adamax_step");
+  return 0;
+}
+
+extern "C" int lvae_adamax_ema_step_f32(float* p, const float* g, float* exp_avg, float* exp_inf, const float* mask, int64_t n,
+                                        float lr, float beta1, float beta2, float eps, float weight_decay, const float* gscale,
+                                        const uint64_t* step_count, float* ema, float decay, void* stream) {
+  LVAE_REQUIRE(p && g && exp_avg && exp_inf && step_count && ema && n > 0, LVAE_EINVAL, "lvae_adamax_ema_step_f32: bad args");
+  LVAE_REQUIRE(decay >= 0.f && decay < 1.f, LVAE_EINVAL, "lvae_adamax_ema_step_f32: decay %g outside [0, 1)", (double)decay);
+  LVAE_REQUIRE(n % 4 == 0, LVAE_EALIGN, "lvae_adamax_ema_step_f32: arena length %lld must be a multiple of 4", (long long)n);
+  LVAE_REQUIRE((reinterpret_cast<uintptr_t>(ema) & 15) == 0, LVAE_EALIGN, "lvae_adamax_ema_step_f32: misaligned ema");
+  hipLaunchKernelGGL(adamax_kernel<true>, dim3(grid_for(n / 4, 256)), dim3(256), 0, (hipStream_t)stream, p, g, exp_avg, exp_inf,
+                     mask, n / 4, lr, beta1, beta2, eps, weight_decay, gscale, step_count, ema, decay);
+  LVAE_LAUNCH_CHECK("adamax_ema_step");
+  return 0;
+}
+
+extern "C" int lvae_swap_f32(float* a, float* b, int64_t n, void* stream) {
+  LVAE_REQUIRE(a && b && n > 0, LVAE_EINVAL, "lvae_swap_f32: bad args");
+  LVAE_REQUIRE(((reinterpret_cast<uintptr_t>(a) | reinterpret_cast<uintptr_t>(b)) & 15) == 0, LVAE_EALIGN, "lvae_swap_f32: misaligned buffer");
+  LVAE_REQUIRE(a + n <= b || b + n <= a, LVAE_EINVAL, "lvae_swap_f32: overlapping buffers");
+  hipLaunchKernelGGL(swap_kernel, dim3(grid_for((n + 3) >> 2, 256 * 4)), dim3(256), 0, (hipStream_t)stream, a, b, n);
+  LVAE_LAUNCH_CHECK("swap");
   return 0;
 }
 

@@ -6,7 +6,8 @@ the absent boilr.eval.BaseOfflineEvaluator / VAEExperimentManager.test_procedure
     replayed S times (saves the 26.5 % bottom-up share of forward FLOPs per extra sample, SURVEY.md §8d);
   * `evaluate(model, batches, S, world)` — mean ELBO / IW bound over a data set, sharded over ranks, one all-reduce;
   * `test_pass(model, batches, S)` — the reference's test summaries (ELBO, recons, KL, per-layer KL, IW bound), folded on the device
-    into double totals, on a noise stream of its own: the trainer's test / log-likelihood pass, which leaves training untouched;
+    into double totals, on a noise stream of its own: the trainer's test / log-likelihood pass, which leaves training untouched
+    (with `optimizer=` an averaging Adamax: computed from the averaged weights);
   * `prior_samples(model, n)` and `inspect_layer_repr(model, n)` — evaluate.py:34-45, 95-114 (arrays instead of PNG grids).
 
 CLI: python -m lvae_amd.evaluate --synthetic --ll --ll-samples 100 --ps  <model flags of main.py>
@@ -197,7 +198,7 @@ class _TestGraphs:
 
 
 @torch.no_grad()
-def test_pass(model, batches, n_samples, noise=None, process_group=None, use_graph=None):
+def test_pass(model, batches, n_samples, noise=None, process_group=None, use_graph=None, optimizer=None):
     """The reference's test summaries over an iterable of NCHW image batches (each rank passes ITS shard of the test set): means over images
     and samples of 'elbo/elbo', 'elbo/recons', 'elbo/kl', 'kl_layers/kl_layer_<i>', plus 'elbo/elbo_IW_<S>' when S > 1, and 'n_images'.
 
@@ -206,12 +207,23 @@ def test_pass(model, batches, n_samples, noise=None, process_group=None, use_gra
     `noise` (default: a PhiloxNoise of the model's own, `model.test_noise`, whose stream continues from pass to pass), never from
     `model.noise`; dropout is off and BatchNorm statistics are only read, so a test pass leaves training exactly as it was.
     use_graph=None: with on-device Philox noise, bottom-up and one sample are captured once per batch shape and replayed; a replayed
-    noise tape (parity tests) runs eagerly."""
+    noise tape (parity tests) runs eagerly.
+    optimizer: when it keeps an average of the weights (Adamax(ema_decay > 0)) the whole pass runs inside `optimizer.swap_ema()`, on the
+    averaged weights, and the result says so ('weights': 'ema'). The exchange is in place, so the captured graphs of earlier passes read
+    the current average when they are replayed, and the parameters are back, bit for bit, when the pass returns."""
+    if optimizer is not None and getattr(optimizer, 'ema_decay', 0.0) > 0.0:
+        with optimizer.swap_ema():
+            res = test_pass(model, batches, n_samples, noise=noise, process_group=process_group, use_graph=use_graph)
+        res['weights'] = 'ema'
+        return res
     from .noise import PhiloxNoise
     dev = next(model.parameters()).device
     if noise is None:
         if getattr(model, 'test_noise', None) is None:
             model.test_noise = PhiloxNoise(seed=(model.noise.seed if isinstance(model.noise, PhiloxNoise) else 0) ^ 0x7E57)
+            start = model.__dict__.pop('test_noise_start', None)   # a resumed run (checkpoint.load_checkpoint): the stream goes on
+            if start:
+                model.test_noise.step = torch.full((1,), int(start), dtype=torch.int64, device=dev)
         noise = model.test_noise
     if use_graph is None:
         use_graph = isinstance(noise, PhiloxNoise)
@@ -297,12 +309,21 @@ def main(argv=None):
     p.add_argument('--layer-repr', action='store_true', dest='layer_repr', help='layer inspection -> layer_repr_<i>.npy')
     p.add_argument('--checkpoint', type=str, default='', help='state_dict file (reference key scheme)')
     p.add_argument('--n-test', type=int, default=1000)
+    p.add_argument('--ema', action='store_true', help="evaluate the averaged weights stored in --checkpoint (its 'ema' entry)")
     args = p.parse_args(argv)
+    if args.ema and not args.checkpoint:
+        raise SystemExit('--ema needs --checkpoint FILE: the averaged weights are read from the file')
     exp = LVAEExperiment(args=args)
     model = exp.model
     if args.checkpoint:
-        from .checkpoint import load_checkpoint
-        load_checkpoint(args.checkpoint, model)
+        from .checkpoint import load_checkpoint, load_ema_weights
+        if args.ema:
+            try:
+                load_ema_weights(args.checkpoint, model)
+            except ValueError as e:
+                raise SystemExit(str(e))
+        else:
+            load_checkpoint(args.checkpoint, model)
     if args.ll:
         gen = torch.Generator().manual_seed(args.seed)
         if args.data_npz:
@@ -311,6 +332,8 @@ def main(argv=None):
             data = synthetic_batch(exp, args.n_test, gen)
         bs = args.test_batch_size
         res = test_pass(model, (data[i:i + bs] for i in range(0, data.shape[0], bs)), args.loglikelihood_samples)
+        if args.ema:
+            res['weights'] = 'ema'
         print(exp.test_log_str(res, model.global_step))
     if args.ps:
         np.save('prior_samples.npy', prior_samples(model, 64).cpu().numpy())

@@ -85,7 +85,17 @@ def build_parser():
                    help='write <dir>/model_<step>.pt every --checkpoint-every steps, keeping the newest --keep-checkpoint-max')
     p.add_argument('--synthetic-test', type=int, default=0, dest='synthetic_test', metavar='N',
                    help='with --synthetic: a fixed seeded test set of N images for the --ts-log-every / --ll-every test passes')
+    p.add_argument('--ema-decay', type=_ema_decay, default=0.0, dest='ema_decay', metavar='D',
+                   help='keep an exponential moving average of the weights inside the optimizer step (decay ramps up as min(D, (1+n)/(10+n))); '
+                        'test and log-likelihood passes then use the averaged weights and checkpoints carry them. 0: off')
     return p
+
+
+def _ema_decay(s):
+    d = float(s)
+    if not 0.0 <= d < 1.0:
+        raise argparse.ArgumentTypeError('--ema-decay must lie in [0, 1), got %s' % s)
+    return d
 
 
 class LVAEExperiment:
@@ -159,7 +169,7 @@ class LVAEExperiment:
         return model
 
     def _make_optimizer(self):
-        return Adamax(self.model, lr=self.args.lr, weight_decay=self.args.weight_decay)
+        return Adamax(self.model, lr=self.args.lr, weight_decay=self.args.weight_decay, ema_decay=getattr(self.args, 'ema_decay', 0.0))
 
     def beta(self):
         if self.args.beta_anneal != 0:
@@ -180,6 +190,8 @@ class LVAEExperiment:
         s = "       "
         if epoch is not None:
             s += "[step {}, epoch {}]   ".format(step, epoch)
+        if summaries.get('weights') == 'ema':
+            s += "[averaged weights]   "
         s += "ELBO {:.5g}   recons: {:.3g}   KL: {:.3g}".format(summaries['elbo/elbo'], summaries['elbo/recons'],
                                                                summaries['elbo/kl'])
         for k in summaries.keys():

@@ -1143,6 +1143,22 @@ def adamax_step(p, g, exp_avg, exp_inf, mask, lr, beta1, beta2, eps, weight_deca
     prepared.weights_written()
 
 
+def adamax_ema_step(p, g, exp_avg, exp_inf, mask, lr, beta1, beta2, eps, weight_decay, gscale, step_count, ema, decay):
+    """adamax_step plus, in the same pass, ema += (p_new - ema) * (1 - min(decay, (1 + n) / (10 + n))), n = step_count[0] on the device."""
+    if ema.numel() != p.numel():
+        raise _C.LvaeHipError("ema has %d elements, the parameters %d" % (ema.numel(), p.numel()))
+    call('lvae_adamax_ema_step_f32', ptr(p), ptr(g), ptr(exp_avg), ptr(exp_inf), ptr(mask), p.numel(), lr, beta1, beta2, eps,
+         weight_decay, ptr(gscale), step_count.data_ptr(), ptr(ema), float(decay), stream_ptr())
+    prepared.weights_written()
+
+
+def swap(a, b):
+    """a <-> b in place, one pass (two contiguous fp32 buffers of one length). The caller says when weights moved (weights_written)."""
+    if a.numel() != b.numel() or not (a.is_contiguous() and b.is_contiguous()):
+        raise _C.LvaeHipError("swap needs two contiguous buffers of one length")
+    call('lvae_swap_f32', ptr(a, (torch.float32,)), ptr(b, (torch.float32,)), a.numel(), stream_ptr())
+
+
 def l2norm(x, out=None):
     if out is None:
         out = torch.empty((1,), dtype=torch.float32, device=x.device)

@@ -60,7 +60,7 @@ def main(argv=None):
     model, opt = exp.model, exp.optimizer
     if args.resume:
         from .checkpoint import load_checkpoint
-        load_checkpoint(args.resume, model, opt)   # (weights, Adamax state, global step and the rank-0 noise stream's position)
+        load_checkpoint(args.resume, model, opt)   # (weights, Adamax state and average, global step and the rank-0 noise stream's position)
     model.noise.seed ^= rank * 0x9E3779B9
     model.train()
     arena = model.pack()
@@ -129,7 +129,7 @@ def main(argv=None):
         if n_samples:
             if data is not None and loader is None:
                 epoch = step * args.batch_size // data.shape[0]
-            res = test_pass(model, tests(), n_samples)
+            res = test_pass(model, tests(), n_samples, optimizer=opt)   # (--ema-decay: on the averaged weights)
             if rank == 0:
                 print(exp.test_log_str(res, step, epoch), flush=True)
             t0, seen = time.time(), 0                  # the training throughput excludes test passes
