@@ -84,6 +84,63 @@ __device__ __forceinline__ void split8_3(const f32x4 lo, const f32x4 hi, bf16x8 
   for (int q = 0; q < 3; ++q) af[q] = __builtin_bit_cast(bf16x8, w[q]);
 }
 
+// split4 in the pairwise form of split8_3: four fp32 values -> SPLIT bf16x4 pieces that sum to them exactly (SPLIT = 3) / their
+// round-to-nearest bf16 (SPLIT = 1), one v_cvt_pk_bf16_f32 per two values and stage. Same values as split4; other instructions.
+typedef unsigned int u32x2v __attribute__((ext_vector_type(2)));
+template <int SPLIT>
+__device__ __forceinline__ void split4_packed(const f32x4 v, bf16x4 (&out)[SPLIT]) {
+  u32x2v w[SPLIT];
+#pragma unroll
+  for (int p = 0; p < 2; ++p) {
+    float a = v[2 * p], b = v[2 * p + 1];
+#pragma unroll
+    for (int q = 0; q < SPLIT; ++q) {
+      const bf16x2 h = __builtin_convertvector(f32x2v{a, b}, bf16x2);
+      const unsigned bits = __builtin_bit_cast(unsigned, h);
+      w[q][p] = bits;
+      if (q + 1 < SPLIT) {
+        a -= __builtin_bit_cast(float, bits << 16);  // exact: the remainder of a round-to-nearest to 8 bits has <= 16 significant bits
+        b -= __builtin_bit_cast(float, bits & 0xffff0000u);
+      }
+    }
+  }
+#pragma unroll
+  for (int q = 0; q < SPLIT; ++q) out[q] = __builtin_bit_cast(bf16x4, w[q]);
+}
+
+// eight fp32 values of one MFMA fragment (two scalar split4 calls) -> SPLIT bf16x8 pieces
+template <int SPLIT>
+__device__ __forceinline__ void split_frag(const f32x4 lo4, const f32x4 hi4, bf16x8 (&out)[SPLIT]) {
+  bf16x4 lo[SPLIT], hi[SPLIT];
+  split4<SPLIT>(lo4, lo);
+  split4<SPLIT>(hi4, hi);
+#pragma unroll
+  for (int q = 0; q < SPLIT; ++q) out[q] = bf16x8{lo[q][0], lo[q][1], lo[q][2], lo[q][3], hi[q][0], hi[q][1], hi[q][2], hi[q][3]};
+}
+template <int SPLIT>
+__device__ __forceinline__ void split_frag(const float (&wv)[8], bf16x8 (&out)[SPLIT]) {
+  split_frag<SPLIT>(f32x4{wv[0], wv[1], wv[2], wv[3]}, f32x4{wv[4], wv[5], wv[6], wv[7]}, out);
+}
+
+// The piece products of one fp32-equivalent product, in ascending order of magnitude: (2,0) (0,2) (1,1) (1,0) (0,1) (0,0) for SPLIT = 3
+// (the six-product form; the order is part of the result), the single product for SPLIT = 1. Product k multiplies piece A[k] of the
+// first operand by piece B[k] of the second. Loops that interleave several accumulators index the table; the rest call mfma_pieces.
+template <int SPLIT>
+struct PieceOrder {
+  static_assert(SPLIT == 1 || SPLIT == 3, "one piece (bf16 operands) or three (fp32-equivalent)");
+  static constexpr int N = SPLIT == 1 ? 1 : 6;
+  static constexpr int A[6] = {SPLIT - 1, 0, SPLIT > 1 ? 1 : 0, SPLIT > 1 ? 1 : 0, 0, 0};
+  static constexpr int B[6] = {0, SPLIT - 1, SPLIT > 1 ? 1 : 0, 0, SPLIT > 1 ? 1 : 0, 0};
+};
+
+template <int SPLIT>
+__device__ __forceinline__ f32x16 mfma_pieces(const bf16x8 (&af)[SPLIT], const bf16x8 (&bf)[SPLIT], f32x16 acc) {
+#pragma unroll
+  for (int k = 0; k < PieceOrder<SPLIT>::N; ++k)
+    acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(af[PieceOrder<SPLIT>::A[k]], bf[PieceOrder<SPLIT>::B[k]], acc, 0, 0, 0);
+  return acc;
+}
+
 // One entry of the batched weight pre-transform table (lvae_conv2d_prepare_weights): the same 64 bytes as the Winograd entry of
 // conv3x3_wino.hip. kind: 1 | 3 = planes of a 3x3 weight for conv3x3_bf16.hip / resblock_img.hip; 33 | 35 = 32 + planes of a 1x1 gate weight
 // for resblock_img.hip; 0 | 16 = Winograd (conv3x3_wino.hip)

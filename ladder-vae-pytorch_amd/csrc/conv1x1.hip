@@ -11,6 +11,7 @@
 // a channel sit in the same lane.
 #include <stdlib.h>
 
+#include "bn_stats.h"
 #include "lvae_common.h"
 
 namespace lvae {
@@ -232,11 +233,10 @@ __global__ __launch_bounds__(256) void conv1x1_kernel(PwArgs a) {
         o += *reinterpret_cast<const f32x4*>(a.gate_res + (size_t)m * C + c);
       }
       store_wt4(a.gate_out + (size_t)m * C + c, o);
-      const f32x4 dl = o - piv;
-      st1 += dl;
-      st2 += dl * dl;
+      stats_fwd_accum4(o, piv, st1, st2);
     }
-    if (stats) {  // 256 / c4n row groups x C channels -> one row of partials per workgroup (fixed order)
+    if (stats) {  // 256 / c4n row groups x C channels -> one row of partials per workgroup (fixed order): stats_reduce_groups (bn_stats.h)
+                  // for a group count and width known only at run time
       __syncthreads();  // the staging tile is dead
       const int G = 256 / c4n;
       float* red = smem;
@@ -270,7 +270,6 @@ __global__ __launch_bounds__(256) void conv1x1_kernel(PwArgs a) {
   }
 }
 
-static bool al16p(const void* p) { return p == nullptr || (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
 
 template <int BM, int KT, int NT, bool KC>
 static int launch_pw(const PwArgs& a, hipStream_t s) {
@@ -307,15 +306,15 @@ static bool pw_select(const lvae_conv_desc* d, const float* gate_res, const floa
   const int K = d->C1 + d->C2, N = d->Cout;
   if (d->KH != 1 || d->KW != 1 || d->stride != 1 || d->pad != 0 || d->OH != d->H || d->OW != d->W) return false;
   if (K > 128 || N > 128 || d->C1 % 4 || d->C2 % 4 || N % 4 || (gate_out && N % 8)) return false;
-  if (gb_dout && (K % 8 || d->C2 != 0 || d->in_scale != nullptr || !al16p(gb_dout) || !al16p(gb_ab) || !al16p(gb_dab))) return false;
-  if (!al16p(d->x) || !al16p(d->x2) || !al16p(d->w) || !al16p(d->y) || !al16p(d->bias) || !al16p(d->in_scale) ||
-      !al16p(d->in_shift) || !al16p(d->out_scale) || !al16p(gate_res) || !al16p(gate_out))
+  if (gb_dout && (K % 8 || d->C2 != 0 || d->in_scale != nullptr || !al16_or_null(gb_dout) || !al16_or_null(gb_ab) || !al16_or_null(gb_dab))) return false;
+  if (!al16_or_null(d->x) || !al16_or_null(d->x2) || !al16_or_null(d->w) || !al16_or_null(d->y) || !al16_or_null(d->bias) || !al16_or_null(d->in_scale) ||
+      !al16_or_null(d->in_shift) || !al16_or_null(d->out_scale) || !al16_or_null(gate_res) || !al16_or_null(gate_out))
     return false;
   const bool kc = d->w_sk == 1 && d->w_sn % 4 == 0 && K % 4 == 0;
   nc = d->w_sn == 1 && d->w_sk % 4 == 0;
   if (!kc && !nc) return false;
   if (gate_out == nullptr && d->y == nullptr) return false;
-  return y2 == nullptr || (gate_out == nullptr && d->stats_out == nullptr && split > 0 && split < N && split % 4 == 0 && al16p(y2));
+  return y2 == nullptr || (gate_out == nullptr && d->stats_out == nullptr && split > 0 && split < N && split % 4 == 0 && al16_or_null(y2));
 }
 
 // -1000: not eligible (the gate / dgrad-cat callers then report it)

@@ -24,6 +24,7 @@
 //     v_mfma_f32_32x32x2_f32 and the vector ALU do not overlap on this chip (the fp32 matrix rate equals the packed-fp32 vector rate:
 //     the same lanes), so in an fp32 kernel VALU time adds to MFMA time whichever wave issues it. The bf16 MFMAs have their own unit.
 #include "bf16_frag.h"
+#include "bn_stats.h"
 #include "lvae_common.h"
 
 namespace lvae {
@@ -258,11 +259,12 @@ __global__ __launch_bounds__(512) void conv1x1_gate_bwd_fused_bf16_kernel(GbfArg
         sa += (double)Os[g * 128 + t];
         sb += (double)Os[g * 128 + 64 + t];
       }
-      Cf[256 + t] = (float)(sa / (double)a.ap.M);
-      Cf[320 + t] = (float)(sb / (double)a.ap.M);
+      const BnBwdChannel r = bn_bwd_finish(sa, sb, a.ap.M);
+      Cf[256 + t] = r.c1;
+      Cf[320 + t] = r.c2;
       if (blockIdx.x == 0) {
-        if (a.ap.dbeta) a.ap.dbeta[t] += (float)sa;
-        if (a.ap.dgamma) a.ap.dgamma[t] += (float)sb;
+        if (a.ap.dbeta) a.ap.dbeta[t] += r.dbeta;
+        if (a.ap.dgamma) a.ap.dgamma[t] += r.dgamma;
       }
     }
     __syncthreads();
@@ -276,7 +278,7 @@ __global__ __launch_bounds__(512) void conv1x1_gate_bwd_fused_bf16_kernel(GbfArg
     f32x4 g;
 #pragma unroll
     for (int j = 0; j < 4; ++j) g[j] = dh[j] * act_grad(u[j], apact);
-    return (g - c1 - (xv - mu) * rs * c2) * sc + ad;
+    return bn_bwd_apply(g, xv, c1, c2, mu, rs, sc) + ad;
   };
 
   // dgrad waves: W[co = 16 s + 8 lh + 0..7][ci = wn*32 + li] as the B fragment of k-step s, SPLIT pieces: in registers (bf16 operands) or,
@@ -288,14 +290,12 @@ __global__ __launch_bounds__(512) void conv1x1_gate_bwd_fused_bf16_kernel(GbfArg
 #pragma unroll
     for (int s = 0; s < 8; ++s) {
       const float* wp = a.w + (int64_t)(wn * 32 + li) * a.w_sn + 16 * s + 8 * lh;
-      bf16x4 lo[SPLIT], hi[SPLIT];
-      split4<SPLIT>(*reinterpret_cast<const f32x4*>(wp), lo);
-      split4<SPLIT>(*reinterpret_cast<const f32x4*>(wp + 4), hi);
+      bf16x8 v[SPLIT];
+      split_frag<SPLIT>(*reinterpret_cast<const f32x4*>(wp), *reinterpret_cast<const f32x4*>(wp + 4), v);
 #pragma unroll
       for (int q = 0; q < SPLIT; ++q) {
-        const bf16x8 v = bf16x8{lo[q][0], lo[q][1], lo[q][2], lo[q][3], hi[q][0], hi[q][1], hi[q][2], hi[q][3]};
-        if (WLDS) Wf[((s * 2 + wn) * SPLIT + q) * 64 + lane] = v;
-        else breg[s][q] = v;
+        if (WLDS) Wf[((s * 2 + wn) * SPLIT + q) * 64 + lane] = v[q];
+        else breg[s][q] = v[q];
       }
     }
   }
@@ -371,10 +371,7 @@ __global__ __launch_bounds__(512) void conv1x1_gate_bwd_fused_bf16_kernel(GbfArg
   f32x4 bs_lo8 = zero4, bs_hi8 = zero4;  // S16: channels c8 + 4 .. c8 + 7
   // transposed-read addresses of this lane (bf16_frag.h): pixel row 8 (G >> 1) + (i16 >> 2) of a k-step, channel 16 (G & 1) + 4 (i16 & 3) of a block
   const int trow = 8 * (G >> 1) + (i16 >> 2), tch = 16 * (G & 1) + 4 * (i16 & 3);
-  // piece products in ascending order of magnitude: (2,0) (0,2) (1,1) (1,0) (0,1) (0,0); SPLIT = 1: the single product
-  constexpr int NP = SPLIT == 1 ? 1 : 6;
-  constexpr int PA[6] = {SPLIT - 1, 0, SPLIT > 1 ? 1 : 0, SPLIT > 1 ? 1 : 0, 0, 0};
-  constexpr int PB[6] = {0, SPLIT - 1, SPLIT > 1 ? 1 : 0, 0, SPLIT > 1 ? 1 : 0, 0};
+  using PO = PieceOrder<SPLIT>;   // the loops with an instrument branch (dbg & 2) index the shared piece order themselves
 
   int tile = blockIdx.x;
   if (tile < a.ntiles) prefetch(tile);
@@ -464,10 +461,9 @@ __global__ __launch_bounds__(512) void conv1x1_gate_bwd_fused_bf16_kernel(GbfArg
 #pragma unroll
           for (int q = 0; q < SPLIT; ++q) bw[q] = Wf[((s * 2 + wn) * SPLIT + q) * 64 + lane];
 #pragma unroll
-          for (int k = 0; k < NP; ++k) { if (dbg & 2) accx[k] += (float)af[PA[k]][0] * (float)bw[PB[k]][1]; else accx = __builtin_amdgcn_mfma_f32_32x32x16_bf16(af[PA[k]], bw[PB[k]], accx, 0, 0, 0); }
+          for (int k = 0; k < PO::N; ++k) { if (dbg & 2) accx[k] += (float)af[PO::A[k]][0] * (float)bw[PO::B[k]][1]; else accx = __builtin_amdgcn_mfma_f32_32x32x16_bf16(af[PO::A[k]], bw[PO::B[k]], accx, 0, 0, 0); }
         } else {
-#pragma unroll
-          for (int k = 0; k < NP; ++k) accx = __builtin_amdgcn_mfma_f32_32x32x16_bf16(af[PA[k]], breg[s][PB[k]], accx, 0, 0, 0);
+          accx = mfma_pieces<SPLIT>(af, breg[s], accx);
         }
       }
 #pragma unroll
@@ -491,7 +487,7 @@ __global__ __launch_bounds__(512) void conv1x1_gate_bwd_fused_bf16_kernel(GbfArg
             bf[q] = tr_frag(dp, dp + 4 * GBB_LDA);
           }
 #pragma unroll
-          for (int k = 0; k < NP; ++k) { if (dbg & 2) accw[j][k] += (float)af[PA[k]][0] * (float)bf[PB[k]][1]; else accw[j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(af[PA[k]], bf[PB[k]], accw[j], 0, 0, 0); }
+          for (int k = 0; k < PO::N; ++k) { if (dbg & 2) accw[j][k] += (float)af[PO::A[k]][0] * (float)bf[PO::B[k]][1]; else accw[j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(af[PO::A[k]], bf[PO::B[k]], accw[j], 0, 0, 0); }
         }
       }
     }
@@ -558,7 +554,6 @@ __global__ __launch_bounds__(512) void conv1x1_gate_bwd_fused_bf16_kernel(GbfArg
   }
 }
 
-static bool al16f(const void* p) { return p == nullptr || (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
 
 // workgroups (= weight-gradient slabs) for M pixels: one per CU, fewer when there are fewer tiles
 static int gbf_nwg(int64_t M) {
@@ -581,11 +576,11 @@ size_t conv1x1_gate_bwd_fused_workspace(const lvae_conv_desc* d) {
 
 int conv1x1_gate_bwd_fused(const lvae_conv_desc* d, const float* dout, const float* ab, const float* y, int act, float* dw,
                            int64_t dw_sk, int64_t dw_sn, float* db, void* workspace, const lvae_bn_apply* ap, hipStream_t s) {
-  if (!al16f(dout) || !al16f(ab) || !al16f(y) || !al16f(d->w) || !al16f(d->y) || !al16f(d->out_scale) || !al16f(workspace)) return -1000;
+  if (!al16_or_null(dout) || !al16_or_null(ab) || !al16_or_null(y) || !al16_or_null(d->w) || !al16_or_null(d->y) || !al16_or_null(d->out_scale) || !al16_or_null(workspace)) return -1000;
   GbfArgs a;
   a.ap = lvae_bn_apply{};
   if (ap != nullptr && ap->parts != nullptr) {
-    if (!al16f(ap->parts) || !al16f(ap->coef) || !al16f(ap->dh) || !al16f(ap->x) || !al16f(ap->add) || !al16f(ap->out)) return -1000;
+    if (!al16_or_null(ap->parts) || !al16_or_null(ap->coef) || !al16_or_null(ap->dh) || !al16_or_null(ap->x) || !al16_or_null(ap->add) || !al16_or_null(ap->out)) return -1000;
     a.ap = *ap;
   }
   a.dout = dout;

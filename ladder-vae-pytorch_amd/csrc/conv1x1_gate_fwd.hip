@@ -18,6 +18,7 @@
 #include <stdlib.h>
 
 #include "bf16_frag.h"
+#include "bn_stats.h"
 #include "lvae_common.h"
 
 namespace lvae {
@@ -127,12 +128,7 @@ __global__ __launch_bounds__(256, 2) void conv1x1_gate_fwd_kernel(GateFwdArgs a)
         float wv[8];
 #pragma unroll
         for (int j = 0; j < 8; ++j) wv[j] = a.w[(int64_t)(16 * s + 8 * lh + j) * a.w_sk + (int64_t)(ni * 64 + ch) * a.w_sn];
-        bf16x4 lo[NPIECE], hi[NPIECE];
-        split4<NPIECE>(f32x4{wv[0], wv[1], wv[2], wv[3]}, lo);
-        split4<NPIECE>(f32x4{wv[4], wv[5], wv[6], wv[7]}, hi);
-#pragma unroll
-        for (int q = 0; q < NPIECE; ++q)
-          bq[ni][s][q] = bf16x8{lo[q][0], lo[q][1], lo[q][2], lo[q][3], hi[q][0], hi[q][1], hi[q][2], hi[q][3]};
+        split_frag<NPIECE>(wv, bq[ni][s]);
       }
   } else {
 #pragma unroll
@@ -183,10 +179,7 @@ __global__ __launch_bounds__(256, 2) void conv1x1_gate_fwd_kernel(GateFwdArgs a)
 #pragma unroll
     for (int r = 0; r < 16; ++r) acc0[r] = acc1[r] = 0.f;
     if (BF16) {
-      // piece products in ascending order of magnitude: (2,0) (0,2) (1,1) (1,0) (0,1) (0,0); one piece: the single product
-      constexpr int NP = NPIECE == 1 ? 1 : 6;
-      constexpr int PA[6] = {NPIECE - 1, 0, NPIECE > 1 ? 1 : 0, NPIECE > 1 ? 1 : 0, 0, 0};
-      constexpr int PB[6] = {0, NPIECE - 1, NPIECE > 1 ? 1 : 0, 0, NPIECE > 1 ? 1 : 0, 0};
+      using PO = PieceOrder<NPIECE>;   // the two accumulators take their piece products alternately
       const __bf16* arow = reinterpret_cast<const __bf16*>(As[cur]) + (wm * 32 + li) * GF_LDB + 8 * lh;
 #pragma unroll
       for (int s = 0; s < 4; ++s) {
@@ -194,9 +187,9 @@ __global__ __launch_bounds__(256, 2) void conv1x1_gate_fwd_kernel(GateFwdArgs a)
 #pragma unroll
         for (int q = 0; q < NPIECE; ++q) af[q] = *reinterpret_cast<const bf16x8*>(arow + q * GF_PLANE + 16 * s);
 #pragma unroll
-        for (int k = 0; k < NP; ++k) {
-          acc0 = __builtin_amdgcn_mfma_f32_32x32x16_bf16(af[PA[k]], bq[0][s][PB[k]], acc0, 0, 0, 0);
-          acc1 = __builtin_amdgcn_mfma_f32_32x32x16_bf16(af[PA[k]], bq[1][s][PB[k]], acc1, 0, 0, 0);
+        for (int k = 0; k < PO::N; ++k) {
+          acc0 = __builtin_amdgcn_mfma_f32_32x32x16_bf16(af[PO::A[k]], bq[0][s][PO::B[k]], acc0, 0, 0, 0);
+          acc1 = __builtin_amdgcn_mfma_f32_32x32x16_bf16(af[PO::A[k]], bq[1][s][PO::B[k]], acc1, 0, 0, 0);
         }
       }
     } else {
@@ -252,9 +245,7 @@ __global__ __launch_bounds__(256, 2) void conv1x1_gate_fwd_kernel(GateFwdArgs a)
             if (a.res) v += rv4[k];
             if (m < M) {
               store_wt4(a.out + (size_t)m * 64 + wn * 32 + c4, v);
-              const f32x4 dl = v - piv4;
-              sv1 += dl;
-              sv2 += dl * dl;
+              stats_fwd_accum4(v, piv4, sv1, sv2);
             }
           } else if (m < M) {
             store4_dt(a.y, (size_t)m * 128 + pass * 64 + wn * 32 + c4, v, a.y_bf16 != 0);
@@ -285,7 +276,8 @@ __global__ __launch_bounds__(256, 2) void conv1x1_gate_fwd_kernel(GateFwdArgs a)
     cur ^= 1;
   }
 
-  if (a.stats_out) {  // lanes, then the two row waves, in a fixed order: one row of partials per workgroup
+  if (a.stats_out) {  // lanes (a shuffle tree, not the LDS groups of stats_reduce_groups), then the two row waves, in a fixed order: one row of
+                      // partials per workgroup
     if (WT) {
 #pragma unroll
       for (int o = 8; o < 64; o <<= 1)

@@ -22,6 +22,7 @@
 #include <string.h>
 
 #include "bf16_frag.h"
+#include "bn_stats.h"
 #include "lvae_common.h"
 
 namespace lvae {
@@ -232,19 +233,7 @@ __global__ __launch_bounds__(256, 2) void conv3x3_bf16_kernel(BfArgs a) {
     if (PRE) bq[step % 3][0] = ball[PRE ? step : 0];
     const bf16x8 (&bf)[SPLIT] = bq[step % 3];
 #pragma unroll
-    for (int mi = 0; mi < MI; ++mi) {
-      if (SPLIT == 1) {
-        acc[mi] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(af[cur][mi][0], bf[0], acc[mi], 0, 0, 0);
-      } else {
-        // smallest terms first
-        acc[mi] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(af[cur][mi][SPLIT - 1], bf[0], acc[mi], 0, 0, 0);
-        acc[mi] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(af[cur][mi][0], bf[SPLIT - 1], acc[mi], 0, 0, 0);
-        acc[mi] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(af[cur][mi][1], bf[1], acc[mi], 0, 0, 0);
-        acc[mi] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(af[cur][mi][1], bf[0], acc[mi], 0, 0, 0);
-        acc[mi] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(af[cur][mi][0], bf[1], acc[mi], 0, 0, 0);
-        acc[mi] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(af[cur][mi][0], bf[0], acc[mi], 0, 0, 0);
-      }
-    }
+    for (int mi = 0; mi < MI; ++mi) acc[mi] = mfma_pieces<SPLIT>(af[cur][mi], bf, acc[mi]);
   }
   __syncthreads();  // every wave is done with the patch: LDS becomes the output staging tile
 
@@ -333,55 +322,23 @@ __global__ __launch_bounds__(256, 2) void conv3x3_bf16_kernel(BfArgs a) {
           if (bwd) {
             if (d.stats_out) {
               const f32x4 xv[2] = {sx0[q], sx1[q]};
-const f32x4 ag[2] = {act_grad4(xv[0] * piv[0] + bsh[0], d.stats_act), act_grad4(xv[1] * piv[1] + bsh[1], d.stats_act)};
 #pragma unroll
-              for (int h = 0; h < 2; ++h)
-#pragma unroll
-                for (int j = 0; j < 4; ++j) {
-                  const float gj = v[h][j] * ag[h][j];
-                  st1[h][j] += gj;
-                  st2[h][j] += gj * (xv[h][j] - bmu[h][j]) * brs[h][j];
-                }
+              for (int h = 0; h < 2; ++h) stats_bwd_accum4(v[h], xv[h], piv[h], bsh[h], bmu[h], brs[h], d.stats_act, st1[h], st2[h]);
             }
           } else {
 #pragma unroll
-            for (int h = 0; h < 2; ++h) {
-              const f32x4 dl = v[h] - piv[h];
-              st1[h] += dl;
-              st2[h] += dl * dl;
-            }
+            for (int h = 0; h < 2; ++h) stats_fwd_accum4(v[h], piv[h], st1[h], st2[h]);
           }
         }
       }
     }
-    if (d.stats_out) {  // 32 pixel groups x 64 channels -> one row of partials per pixel tile (fixed order)
-      __syncthreads();
-      float* red = reinterpret_cast<float*>(smem_raw);
-#pragma unroll
-      for (int h = 0; h < 2; ++h) {
-        *reinterpret_cast<f32x4*>(red + (t >> 3) * 64 + c8 + 4 * h) = st1[h];
-        *reinterpret_cast<f32x4*>(red + 2048 + (t >> 3) * 64 + c8 + 4 * h) = st2[h];
-      }
-      __syncthreads();
-      if (t < 128) {
-        const int c = t & 63, which = t >> 6;
-        float v = 0.f;
-#pragma unroll
-        for (int r = 0; r < 32; ++r) v += red[which * 2048 + r * 64 + c];
-        if (co0 + c < d.Cout) d.stats_out[((size_t)tm * 2 + which) * d.Cout + co0 + c] = v;
-      }
-    }
+    if (d.stats_out)  // 32 pixel groups x 64 channels -> one row of partials per pixel tile
+      stats_reduce_groups<32, 64, 2>(reinterpret_cast<float*>(smem_raw), t >> 3, c8, st1, st2, d.stats_out, tm, d.Cout, co0, false, nullptr, 0);
     return;
   }
   const int c4 = (t & 15) * 4, col = co0 + c4;
-  f32x4 st1 = {0.f, 0.f, 0.f, 0.f}, st2 = st1, piv = st1;
-  if (d.stats_out && col < d.Cout) piv = *reinterpret_cast<const f32x4*>(d.stats_pivot + col);
-  f32x4 bsh = piv, bmu = piv, brs = piv;
-  if (d.stats_out && d.stats_mode == LVAE_STATS_BN_BWD && col < d.Cout) {
-    bsh = *reinterpret_cast<const f32x4*>(d.stats_pivot + d.Cout + col);
-    bmu = *reinterpret_cast<const f32x4*>(d.stats_pivot + 2 * d.Cout + col);
-    brs = *reinterpret_cast<const f32x4*>(d.stats_pivot + 3 * d.Cout + col);
-  }
+  f32x4 st1 = {0.f, 0.f, 0.f, 0.f}, st2 = st1, piv, bsh, bmu, brs;
+  stats_load_coef4(d.stats_pivot, d.Cout, col, d.stats_out != nullptr, d.stats_mode == LVAE_STATS_BN_BWD, piv, bsh, bmu, brs);
   if (col < d.Cout) {
     f32x4 bias = {0.f, 0.f, 0.f, 0.f};
     if (d.bias) bias = *reinterpret_cast<const f32x4*>(d.bias + col);
@@ -430,36 +387,16 @@ const f32x4 ag[2] = {act_grad4(xv[0] * piv[0] + bsh[0], d.stats_act), act_grad4(
         if (d.stats_mode == LVAE_STATS_BN_BWD) {
           if (d.stats_out) {
             const f32x4 xv = sxr[q];
-            const f32x4 ag = act_grad4(xv * piv + bsh, d.stats_act);
-#pragma unroll
-            for (int j = 0; j < 4; ++j) {
-              const float gj = v[j] * ag[j];
-              st1[j] += gj;
-              st2[j] += gj * (xv[j] - bmu[j]) * brs[j];
-            }
+            stats_bwd_accum4(v, xv, piv, bsh, bmu, brs, d.stats_act, st1, st2);
           }
         } else {
-          const f32x4 dl = v - piv;
-          st1 += dl;
-          st2 += dl * dl;
+          stats_fwd_accum4(v, piv, st1, st2);
         }
       }
     }
   }
-  if (d.stats_out) {
-    __syncthreads();
-    float* red = reinterpret_cast<float*>(smem_raw);
-    *reinterpret_cast<f32x4*>(red + (t >> 4) * 64 + c4) = st1;
-    *reinterpret_cast<f32x4*>(red + 1024 + (t >> 4) * 64 + c4) = st2;
-    __syncthreads();
-    if (t < 128) {
-      const int c = t & 63, which = t >> 6;
-      float v = 0.f;
-#pragma unroll
-      for (int r = 0; r < 16; ++r) v += red[which * 1024 + r * 64 + c];
-      if (co0 + c < d.Cout) d.stats_out[((size_t)tm * 2 + which) * d.Cout + co0 + c] = v;
-    }
-  }
+  if (d.stats_out)  // 16 pixel groups x 64 channels -> one row of partials per pixel tile
+    stats_reduce_groups<16, 64>(reinterpret_cast<float*>(smem_raw), t >> 4, c4, st1, st2, d.stats_out, tm, d.Cout, co0, false, nullptr, 0);
 }
 
 // (A persistent two-workgroups-per-CU form of this kernel, prefetching the next tile's patch during the MFMAs, was built in round 2 and
@@ -682,16 +619,7 @@ __global__ __launch_bounds__(512) void conv3x3_wgrad_bf16_kernel(BfWgArgs a) {
           bf16x8 afr[SPLIT];
 #pragma unroll
           for (int q = 0; q < SPLIT; ++q) afr[q] = tr_frag(Xs + q * x_plane + (xr0 + off) * LDK + chx, Xs + q * x_plane + (xr1 + off) * LDK + chx);
-          if (SPLIT == 1) {
-            acc[j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(afr[0], bfr[0], acc[j], 0, 0, 0);
-          } else {  // smallest terms first
-            acc[j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(afr[SPLIT - 1], bfr[0], acc[j], 0, 0, 0);
-            acc[j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(afr[0], bfr[SPLIT - 1], acc[j], 0, 0, 0);
-            acc[j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(afr[1], bfr[1], acc[j], 0, 0, 0);
-            acc[j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(afr[1], bfr[0], acc[j], 0, 0, 0);
-            acc[j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(afr[0], bfr[1], acc[j], 0, 0, 0);
-            acc[j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(afr[0], bfr[0], acc[j], 0, 0, 0);
-          }
+          acc[j] = mfma_pieces<SPLIT>(afr, bfr, acc[j]);
         }
       }
     }
@@ -1010,7 +938,6 @@ __global__ __launch_bounds__(512) void conv3x3_wgrad_bf16h_kernel(BfWgArgs a) {
   }
 }
 
-static bool al16b(const void* p) { return p == nullptr || (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
 
 // ---- weight pre-split: piece `plane` of w[tap][k][n] (any strides) in MFMA B-fragment order, zero beyond K / N
 __device__ __forceinline__ void bf_prep_element(const BfPrepEntry& e, int idx) {
@@ -1170,8 +1097,8 @@ static bool bf_select(const lvae_conv_desc* d, int split, BfArgs& a) {
   if (d->in_fold != nullptr) return false;
   if (Cin > 64 || Cin % 4 != 0 || d->Cout % 4 != 0) return false;
   if ((int64_t)d->N * d->H * d->W * Cin >= ((int64_t)1 << 31)) return false;
-  if (!al16b(d->x) || !al16b(d->y) || !al16b(d->bias) || !al16b(d->out_scale) || !al16b(d->in_scale) || !al16b(d->in_shift) ||
-      !al16b(d->stats_pivot) || !al16b(d->stats_x))
+  if (!al16_or_null(d->x) || !al16_or_null(d->y) || !al16_or_null(d->bias) || !al16_or_null(d->out_scale) || !al16_or_null(d->in_scale) || !al16_or_null(d->in_shift) ||
+      !al16_or_null(d->stats_pivot) || !al16_or_null(d->stats_x))
     return false;
   a.d = *d;
   a.Cin = Cin;
@@ -1204,7 +1131,7 @@ bool conv3x3_bf16_plan(const lvae_conv_desc* d, bool assume_ws, ConvPlan& p) {
   const int split = conv3x3_bf16_form(d);
   if (split == 0) return false;
   const size_t ws = conv3x3_bf16_workspace(d, split);
-  if (!assume_ws && (d->workspace == nullptr || (size_t)d->workspace_bytes < ws || !al16b(d->workspace))) return false;
+  if (!assume_ws && (d->workspace == nullptr || (size_t)d->workspace_bytes < ws || !al16_or_null(d->workspace))) return false;
   BfArgs a;
   bf_select(d, split, a);  // (conv3x3_bf16_form accepted d)
   p = ConvPlan{};
@@ -1283,7 +1210,7 @@ static bool bfwg_plan(const lvae_conv_desc* d, BfWgArgs& a) {
   a.split = split;
   if (d->KH != 3 || d->KW != 3 || d->stride != 1 || d->pad != 1 || d->gather != LVAE_GATHER_CONV || d->x2 != nullptr) return false;
   if (d->OH != d->H || d->OW != d->W || d->C1 > 64 || d->C1 % 4 != 0 || d->Cout % 4 != 0) return false;
-  if (!al16b(d->x) || !al16b(d->in_scale) || !al16b(d->in_shift)) return false;
+  if (!al16_or_null(d->x) || !al16_or_null(d->in_scale) || !al16_or_null(d->in_shift)) return false;
   const int64_t M = (int64_t)d->N * d->H * d->W;
   if (M < 256 * 64 || M * 64 >= ((int64_t)1 << 31)) return false;
   // Layers of exactly 16 k pixels with fp32-stored operands (the 8x8 level at batch 256, whose blocks run the fused whole-image launches with

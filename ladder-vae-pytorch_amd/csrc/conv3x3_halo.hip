@@ -10,6 +10,7 @@
 // Tile: BM output pixels = NI images x TH rows x TW (= W) columns, BN = 64 output channels, 4 waves as 2(M) x 2(N).
 #include <stdlib.h>
 
+#include "bn_stats.h"
 #include "lvae_common.h"
 
 namespace lvae {
@@ -213,14 +214,8 @@ __global__ __launch_bounds__(256, 2) void conv3x3_halo_kernel(HaloArgs a) {
     // tile pixel p of a tile that covers whole rows / whole images is pixel (n0*H + oh0)*W + p of the tensor: the output
     // pointer is linear in p (16 pixel rows per pass), only the image index needs a division (for N bound and dropout)
     const int c4 = (t & 15) * 4, col = co0 + c4;
-    f32x4 st1 = {0.f, 0.f, 0.f, 0.f}, st2 = st1, piv = st1;  // BatchNorm partials of the stored values (d.stats_out)
-    if (d.stats_out && col < d.Cout) piv = *reinterpret_cast<const f32x4*>(d.stats_pivot + col);
-    f32x4 bsh = piv, bmu = piv, brs = piv;  // LVAE_STATS_BN_BWD: piv = scale, then shift, mean, rstd of the [4][Cout] block
-    if (d.stats_out && d.stats_mode == LVAE_STATS_BN_BWD && col < d.Cout) {
-      bsh = *reinterpret_cast<const f32x4*>(d.stats_pivot + d.Cout + col);
-      bmu = *reinterpret_cast<const f32x4*>(d.stats_pivot + 2 * d.Cout + col);
-      brs = *reinterpret_cast<const f32x4*>(d.stats_pivot + 3 * d.Cout + col);
-    }
+    f32x4 st1 = {0.f, 0.f, 0.f, 0.f}, st2 = st1, piv, bsh, bmu, brs;  // BatchNorm partials of the stored values (d.stats_out)
+    stats_load_coef4(d.stats_pivot, d.Cout, col, d.stats_out != nullptr, d.stats_mode == LVAE_STATS_BN_BWD, piv, bsh, bmu, brs);
     if (col < d.Cout) {
       f32x4 bias = {0.f, 0.f, 0.f, 0.f};
       if (d.bias) bias = *reinterpret_cast<const f32x4*>(d.bias + col);  // Cout % 4 == 0 on this path
@@ -243,40 +238,19 @@ __global__ __launch_bounds__(256, 2) void conv3x3_halo_kernel(HaloArgs a) {
           if (d.stats_mode == LVAE_STATS_BN_BWD) {
             if (d.stats_out) {
               const f32x4 xv = *reinterpret_cast<const f32x4*>(d.stats_x + (size_t)((n0 * d.H + oh0) * d.W + p) * d.Cout + col);
-              const f32x4 ag = act_grad4(xv * piv + bsh, d.stats_act);
-#pragma unroll
-              for (int j = 0; j < 4; ++j) {
-                const float gj = v[j] * ag[j];
-                st1[j] += gj;
-                st2[j] += gj * (xv[j] - bmu[j]) * brs[j];
-              }
+              stats_bwd_accum4(v, xv, piv, bsh, bmu, brs, d.stats_act, st1, st2);
             }
           } else {
-            const f32x4 dl = v - piv;
-            st1 += dl;
-            st2 += dl * dl;
+            stats_fwd_accum4(v, piv, st1, st2);
           }
         }
       }
     }
-    if (d.stats_out) {  // 16 pixel groups x 64 channels -> one row of partials per pixel tile (fixed order)
-      __syncthreads();  // the staging tile is dead
-      float* red = smem;
-      *reinterpret_cast<f32x4*>(red + (t >> 4) * 64 + c4) = st1;
-      *reinterpret_cast<f32x4*>(red + 1024 + (t >> 4) * 64 + c4) = st2;
-      __syncthreads();
-      if (t < 128) {
-        const int c = t & 63, which = t >> 6;
-        float v = 0.f;
-#pragma unroll
-        for (int r = 0; r < 16; ++r) v += red[which * 1024 + r * 64 + c];
-        if (co0 + c < d.Cout) d.stats_out[((size_t)tm * 2 + which) * d.Cout + co0 + c] = v;
-      }
-    }
+    if (d.stats_out)  // 16 pixel groups x 64 channels -> one row of partials per pixel tile; the staging tile is dead
+      stats_reduce_groups<16, 64>(smem, t >> 4, c4, st1, st2, d.stats_out, tm, d.Cout, co0, false, nullptr, 0);
   }
 }
 
-static bool al16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
 
 // tile geometry for a W-wide image: rows per tile and images per tile so that NI*TH*W <= BM
 static bool halo_plan(int N, int H, int W, int BM, int cin_t, HaloArgs& a) {

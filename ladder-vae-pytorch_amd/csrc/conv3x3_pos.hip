@@ -16,6 +16,7 @@
 // the partial sums the producing kernel's epilogue left (lvae_bn_finalize_parts_f32 as a prologue: 64 loads per thread while the
 // operand loads are in flight, instead of a 5 us launch in a dependent chain); workgroup 0 publishes (scale, shift, mean, rstd)
 // for the backward and updates the running statistics.
+#include "bn_stats.h"
 #include "lvae_common.h"
 
 namespace lvae {
@@ -125,27 +126,13 @@ __global__ __launch_bounds__(256) void conv3x3_pos_kernel(PosArgs a) {
         sb += (double)s_fin[(q * 2 + 1) * 64 + t];
       }
       const float pivot = f.parts[((size_t)rows * 2) * C + t];  // the producer's pivot, stored behind its partial rows
-      const double M = (double)f.M, inv_m = 1.0 / M, dm = sa * inv_m;
-      double m2 = sb - sa * dm;
-      if (m2 < 0.0) m2 = 0.0;
-      const double mean = (double)pivot + dm, var = m2 * inv_m;
-      const float rstd = (float)(1.0 / sqrt(var + (double)f.eps));
       const float gam = f.gamma ? f.gamma[t] : 1.f, bet = f.beta ? f.beta[t] : 0.f;
-      const float scl = gam * rstd, shf = bet - (float)mean * scl;
-      s_fin[512 + t] = scl;
-      s_fin[512 + 64 + t] = shf;
+      const BnChannel r = bn_finalize_channel(sa, sb, pivot, f.M, f.eps, gam, bet);
+      s_fin[512 + t] = r.scale;
+      s_fin[512 + 64 + t] = r.shift;
       if (bid == 0) {
-        if (f.coef_out) {
-          f.coef_out[t] = scl;
-          f.coef_out[C + t] = shf;
-          f.coef_out[2 * C + t] = (float)mean;
-          f.coef_out[3 * C + t] = rstd;
-        }
-        if (f.running_mean) {
-          const double unbiased = f.M > 1 ? m2 / (M - 1.0) : var;
-          f.running_mean[t] = (1.f - f.momentum) * f.running_mean[t] + f.momentum * (float)mean;
-          f.running_var[t] = (1.f - f.momentum) * f.running_var[t] + f.momentum * (float)unbiased;
-        }
+        if (f.coef_out) bn_store_coef(f.coef_out, C, t, r);
+        if (f.running_mean) bn_update_running(f.running_mean, f.running_var, t, f.running_mean[t], f.running_var[t], f.momentum, r, f.M);
       }
     }
     __syncthreads();
@@ -244,6 +231,8 @@ __global__ __launch_bounds__(256) void conv3x3_pos_kernel(PosArgs a) {
         const f32x4 bmu = *reinterpret_cast<const f32x4*>(d.stats_pivot + 2 * d.Cout + col);
         const f32x4 brs = *reinterpret_cast<const f32x4*>(d.stats_pivot + 3 * d.Cout + col);
         const f32x4 xv = *reinterpret_cast<const f32x4*>(d.stats_x + o);
+        // the thread's only row: the terms of stats_bwd_accum4 / stats_fwd_accum4 (bn_stats.h) ARE its sums. Assigned, not accumulated
+        // onto zero: 0 + x is an addition the compiler has to keep
         const f32x4 ag = act_grad4(xv * piv + bsh, d.stats_act);
 #pragma unroll
         for (int j = 0; j < 4; ++j) {
@@ -258,30 +247,13 @@ __global__ __launch_bounds__(256) void conv3x3_pos_kernel(PosArgs a) {
       }
     }
   }
-  if (d.stats_out) {  // 32 rows x 32 channels -> one row of partials per (image group, position), summed in a fixed order
-    __syncthreads();
-    float* red = smem;
-    *reinterpret_cast<f32x4*>(red + row * 32 + oc4) = st1;
-    *reinterpret_cast<f32x4*>(red + 1024 + row * 32 + oc4) = st2;
-    __syncthreads();
-    if (t < 64) {
-      const int c = t & 31, which = t >> 5;
-      float v = 0.f;
-#pragma unroll
-      for (int r = 0; r < 32; ++r) v += red[which * 1024 + r * 32 + c];
-      const int tm = ig * a.P + pos;
-      if (co0 + c < d.Cout) {
-        d.stats_out[((size_t)tm * 2 + which) * d.Cout + co0 + c] = v;
-        // the pivot travels with the partials (row index = number of partial rows): a consumer that finalizes them in its own
-        // prologue must not read it from a buffer that consumer also updates (the running mean)
-        if (tm == 0 && which == 0 && d.stats_mode == LVAE_STATS_BN_FWD)
-          d.stats_out[((size_t)a.n_groups * a.P * 2) * d.Cout + co0 + c] = d.stats_pivot[co0 + c];
-      }
-    }
+  if (d.stats_out) {  // 32 rows x 32 channels -> one row of partials per (image group, position), the pivot row behind the forward rows
+    const int tm = ig * a.P + pos;
+    stats_reduce_groups<32, 32>(smem, row, oc4, st1, st2, d.stats_out, tm, d.Cout, co0, tm == 0 && d.stats_mode == LVAE_STATS_BN_FWD,
+                                d.stats_pivot, (size_t)a.n_groups * a.P);
   }
 }
 
-static bool al16q(const void* p) { return p == nullptr || (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
 
 // eligibility: 3x3 / stride 1 / pad 1 on images of at most 16 pixels, 32 or 64 reduction channels
 static bool pos_select(const lvae_conv_desc* d, bool& ncontig) {
@@ -291,8 +263,8 @@ static bool pos_select(const lvae_conv_desc* d, bool& ncontig) {
   if (d->KH != 3 || d->KW != 3 || d->stride != 1 || d->pad != 1 || d->x2 != nullptr || d->OH != d->H || d->OW != d->W) return false;
   if (d->H * d->W > 16) return false;
   if (Cin > 64 || Cin % 4 != 0 || d->Cout % 4 != 0 || d->w_stap % 4 != 0) return false;
-  if (!al16q(d->x) || !al16q(d->w) || !al16q(d->y) || !al16q(d->bias) || !al16q(d->out_scale) || !al16q(d->in_scale) ||
-      !al16q(d->in_shift) || !al16q(d->stats_pivot) || !al16q(d->stats_x))
+  if (!al16_or_null(d->x) || !al16_or_null(d->w) || !al16_or_null(d->y) || !al16_or_null(d->bias) || !al16_or_null(d->out_scale) || !al16_or_null(d->in_scale) ||
+      !al16_or_null(d->in_shift) || !al16_or_null(d->stats_pivot) || !al16_or_null(d->stats_x))
     return false;
   const bool kc = d->w_sk == 1 && d->w_sn % 4 == 0, nc = d->w_sn == 1 && d->w_sk % 4 == 0;
   if (!kc && !nc) return false;

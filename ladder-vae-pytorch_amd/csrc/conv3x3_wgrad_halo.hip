@@ -59,7 +59,6 @@ __global__ __launch_bounds__(512, 2) void conv_wgrad_ws_grouped_kernel(WTileGrou
 #include "conv3x3_wgrad_halo_body.inc"
 }
 
-static bool al16w(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
 
 static int cin_tile(int Cin) { return Cin <= 32 ? 32 : (Cin <= 64 ? 64 : 128); }
 
@@ -69,7 +68,7 @@ static bool wtile_plan(const lvae_conv_desc* d, WTileArgs& a) {
   if (!(k3 || k1) || d->stride != 1 || d->gather != LVAE_GATHER_CONV || d->OH != d->H || d->OW != d->W) return false;
   if ((int64_t)d->N * d->H * d->W * (Cin > d->Cout ? Cin : d->Cout) >= ((int64_t)1 << 31)) return false;  // 32-bit element offsets
   if (Cin > 128 || (k3 && Cin > 64) || d->C1 % 4 != 0 || d->C2 % 4 != 0 || d->Cout % 4 != 0 || d->W % 2 != 0) return false;
-  if (!al16w(d->x) || (d->x2 && !al16w(d->x2)) || (d->in_scale && (!al16w(d->in_scale) || !al16w(d->in_shift)))) return false;
+  if (!al16(d->x) || (d->x2 && !al16(d->x2)) || (d->in_scale && (!al16(d->in_scale) || !al16(d->in_shift)))) return false;
   const int cin_t = cin_tile(Cin), pad = k3 ? 1 : 0;
   // tile: as many pixels as two LDS buffers allow (at most 128), whole rows, whole images when several fit
   int BM = 128;

@@ -18,6 +18,7 @@
 // (deterministic), applies G^T . G and accumulates into dw with the caller's strides.
 #include <stdlib.h>
 
+#include "bn_stats.h"
 #include "lvae_common.h"
 
 namespace lvae {
@@ -173,7 +174,6 @@ __global__ __launch_bounds__(1024) void conv_wgrad_wino_reduce_grouped_kernel(Wi
   wino_reduce_body<false>(a, blockIdx.x, red, red_b);
 }
 
-static bool al16g(const void* p) { return p == nullptr || (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
 
 static bool wg_wino_plan(const lvae_conv_desc* d, WgWinoArgs& a) {
   static const bool off = tune("LVAE_DISABLE_WINO_WGRAD", 0) != 0 || tune("LVAE_DISABLE_WINO", 0) != 0;  // A/B switch (tuning builds only)
@@ -184,7 +184,7 @@ static bool wg_wino_plan(const lvae_conv_desc* d, WgWinoArgs& a) {
   if (d->W != 8 && d->W != 16 && d->W != 32) return false;
   const int tpr = d->W / 2, tr = 16 / tpr;
   if ((d->H / 2) % tr != 0) return false;
-  if (!al16g(d->x) || !al16g(d->in_scale) || !al16g(d->in_shift)) return false;
+  if (!al16_or_null(d->x) || !al16_or_null(d->in_scale) || !al16_or_null(d->in_shift)) return false;
   const int64_t M = (int64_t)d->N * d->H * d->W;
   static const int64_t min_m = tune("LVAE_WINO_WGRAD_MIN_M", 256 * 64);
   if (M < min_m || M * 256 >= ((int64_t)1 << 31)) return false;
@@ -279,7 +279,7 @@ bool conv_wgrad_wino_apply_ok(const lvae_conv_desc* d) {
 int conv_wgrad_wino_apply_launch(const lvae_conv_desc* d, const lvae_bn_apply* ap, float* dw, float* db, void* workspace, hipStream_t s) {
   WgWinoApArgs g;
   WgWinoArgs& a = g.w;
-  LVAE_REQUIRE(al16g(workspace) && al16g(ap->parts) && al16g(ap->coef) && al16g(ap->dh) && al16g(ap->x) && al16g(ap->out) && al16g(ap->drop),
+  LVAE_REQUIRE(al16_or_null(workspace) && al16_or_null(ap->parts) && al16_or_null(ap->coef) && al16_or_null(ap->dh) && al16_or_null(ap->x) && al16_or_null(ap->out) && al16_or_null(ap->drop),
                LVAE_EALIGN, "lvae_conv2d_wgrad_apply_f32: buffers must be 16-byte aligned");
   wg_wino_plan(d, a);
   a.d = *d;

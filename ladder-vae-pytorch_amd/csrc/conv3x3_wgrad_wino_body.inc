@@ -84,11 +84,12 @@
         sa += (double)smem[g2 * 128 + t];
         sb += (double)smem[g2 * 128 + 64 + t];
       }
-      Cf[256 + t] = (float)(sa / (double)ap.M);
-      Cf[320 + t] = (float)(sb / (double)ap.M);
+      const BnBwdChannel r = bn_bwd_finish(sa, sb, ap.M);
+      Cf[256 + t] = r.c1;
+      Cf[320 + t] = r.c2;
       if (blockIdx.x == 0) {
-        if (ap.dbeta) ap.dbeta[t] += (float)sa;
-        if (ap.dgamma) ap.dgamma[t] += (float)sb;
+        if (ap.dbeta) ap.dbeta[t] += r.dbeta;
+        if (ap.dgamma) ap.dgamma[t] += r.dgamma;
       }
     }
     __syncthreads();   // the scratch is read and Cf is published: the first chunk may be staged
@@ -140,7 +141,7 @@
       for (int k = 0; k < 2; ++k) {
         const f32x4 xv = yreg[AP ? k : 0];
         const f32x4 gq = dreg[k] * act_grad4(xv * ap_sc + ap_sh, ap.act);
-        f32x4 v = (gq - ap_c1 - (xv - ap_mu) * ap_rs * ap_c2) * ap_sc * dmask;
+        f32x4 v = bn_bwd_apply(gq, xv, ap_c1, ap_c2, ap_mu, ap_rs, ap_sc) * dmask;
         if (!dy_ok) v = zero4;
         dreg[k] = v;
         if (cib == 0 && dy_ok) store_wt4(ap.out + doff0 + (k ? 32 * d.Cout : 0), v);

@@ -23,6 +23,7 @@
 #include <string.h>
 
 #include "bf16_frag.h"
+#include "bn_stats.h"
 #include "lvae_common.h"
 
 // build-time experiment switches of the profiling builds (tools/wino_ab.sh); the defaults are the product
@@ -199,27 +200,13 @@ __device__ __forceinline__ void wino_fold_bn(const lvae_bn_fold& f, int C, float
       sb += (double)scratch[k * 128 + C + t];
     }
     const float pivot = f.parts[((size_t)rows * 2) * C + t];  // the producer's pivot, stored behind its partial rows
-    const double M = (double)f.M, inv_m = 1.0 / M, dm = sa * inv_m;
-    double m2 = sb - sa * dm;
-    if (m2 < 0.0) m2 = 0.0;
-    const double mean = (double)pivot + dm, var = m2 * inv_m;
-    const float rstd = (float)(1.0 / sqrt(var + (double)f.eps));
     const float gam = f.gamma ? f.gamma[t] : 1.f, bet = f.beta ? f.beta[t] : 0.f;
-    const float scl = gam * rstd, shf = bet - (float)mean * scl;
-    coef[t] = scl;
-    coef[64 + t] = shf;
+    const BnChannel r = bn_finalize_channel(sa, sb, pivot, f.M, f.eps, gam, bet);
+    coef[t] = r.scale;
+    coef[64 + t] = r.shift;
     if (writer) {
-      if (f.coef_out) {
-        f.coef_out[t] = scl;
-        f.coef_out[C + t] = shf;
-        f.coef_out[2 * C + t] = (float)mean;
-        f.coef_out[3 * C + t] = rstd;
-      }
-      if (f.running_mean) {
-        const double unbiased = f.M > 1 ? m2 / (M - 1.0) : var;
-        f.running_mean[t] = (1.f - f.momentum) * f.running_mean[t] + f.momentum * (float)mean;
-        f.running_var[t] = (1.f - f.momentum) * f.running_var[t] + f.momentum * (float)unbiased;
-      }
+      if (f.coef_out) bn_store_coef(f.coef_out, C, t, r);
+      if (f.running_mean) bn_update_running(f.running_mean, f.running_var, t, f.running_mean[t], f.running_var[t], f.momentum, r, f.M);
     }
   }
   __syncthreads();
@@ -448,9 +435,6 @@ __global__ __launch_bounds__(256, MT == 1 ? 2 : 1) void conv3x3_wino_kernel(Wino
     };
 #pragma unroll
     for (int it = 0; it < (BR < 4 * NSLICE ? BR - 1 : BR); ++it) load_b(it, it);
-    // piece products in ascending order of magnitude: (2,0) (0,2) (1,1) (1,0) (0,1) (0,0)
-    constexpr int PA[6] = {2, 0, 1, 1, 0, 0};
-    constexpr int PB[6] = {0, 2, 1, 0, 1, 0};
 #pragma unroll
     for (int s16 = 0; s16 < NSLICE; ++s16) {
       f32x4 tl[4], th[4];  // t = d[ra] + sgn * d[rb] for the four pixel columns, channels 16 s + 8 lh + {0..3 | 4..7}
@@ -473,23 +457,16 @@ __global__ __launch_bounds__(256, MT == 1 ? 2 : 1) void conv3x3_wino_kernel(Wino
         if (BR < 4 * NSLICE && it + BR - 1 < 4 * NSLICE) load_b(it + BR - 1, (it + BR - 1) % BR);
         const f32x4 vl = j == 0 ? tl[0] - tl[2] : (j == 1 ? tl[1] + tl[2] : (j == 2 ? tl[2] - tl[1] : tl[1] - tl[3]));
         const f32x4 vh = j == 0 ? th[0] - th[2] : (j == 1 ? th[1] + th[2] : (j == 2 ? th[2] - th[1] : th[1] - th[3]));
-        bf16x4 pl[3], ph[3];
         bf16x8 af[3];
         if (dbg & 32) {
           af[0] = __builtin_bit_cast(bf16x8, vl);
           af[1] = __builtin_bit_cast(bf16x8, vh);
           af[2] = __builtin_bit_cast(bf16x8, vl + vh);
         } else {
-        split4<3>(vl, pl);
-        split4<3>(vh, ph);
-#pragma unroll
-        for (int q = 0; q < 3; ++q) af[q] = bf16x8{pl[q][0], pl[q][1], pl[q][2], pl[q][3], ph[q][0], ph[q][1], ph[q][2], ph[q][3]};
+        split_frag<3>(vl, vh, af);
         }
 #pragma unroll
-        for (int h = 0; h < NH; ++h)
-#pragma unroll
-          for (int k = 0; k < 6; ++k)
-            acc[0][j][h] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(af[PA[k]], bq[it % BR][h][PB[k]], acc[0][j][h], 0, 0, 0);
+        for (int h = 0; h < NH; ++h) acc[0][j][h] = mfma_pieces<3>(af, bq[it % BR][h], acc[0][j][h]);
       }
       } else {  // dbg & 2: keep the U stream alive, nothing else
 #pragma unroll
@@ -541,14 +518,8 @@ __global__ __launch_bounds__(256, MT == 1 ? 2 : 1) void conv3x3_wino_kernel(Wino
   WINO_STAMP(4);
   {
     const int c4 = (t % C4N) * 4, col = co0 + c4;
-    f32x4 st1 = zero4, st2 = zero4, piv = zero4;  // BatchNorm partials of the stored values (d.stats_out)
-    if (d.stats_out && col < d.Cout) piv = *reinterpret_cast<const f32x4*>(d.stats_pivot + col);
-    f32x4 bsh = piv, bmu = piv, brs = piv;  // LVAE_STATS_BN_BWD: piv = scale, then shift, mean, rstd of the [4][Cout] block
-    if (d.stats_out && d.stats_mode == LVAE_STATS_BN_BWD && col < d.Cout) {
-      bsh = *reinterpret_cast<const f32x4*>(d.stats_pivot + d.Cout + col);
-      bmu = *reinterpret_cast<const f32x4*>(d.stats_pivot + 2 * d.Cout + col);
-      brs = *reinterpret_cast<const f32x4*>(d.stats_pivot + 3 * d.Cout + col);
-    }
+    f32x4 st1 = zero4, st2 = zero4, piv, bsh, bmu, brs;  // BatchNorm partials of the stored values (d.stats_out)
+    stats_load_coef4(d.stats_pivot, d.Cout, col, d.stats_out != nullptr, d.stats_mode == LVAE_STATS_BN_BWD, piv, bsh, bmu, brs);
     if (col < d.Cout) {
       f32x4 bias = zero4;
       if (d.bias) bias = *reinterpret_cast<const f32x4*>(d.bias + col);
@@ -575,40 +546,18 @@ __global__ __launch_bounds__(256, MT == 1 ? 2 : 1) void conv3x3_wino_kernel(Wino
           if (d.stats_mode == LVAE_STATS_BN_BWD) {
             if (d.stats_out) {
               const f32x4 xv = *reinterpret_cast<const f32x4*>(d.stats_x + (size_t)((n0 * d.H + oh0) * d.W + p) * d.Cout + col);
-              const f32x4 ag = act_grad4(xv * piv + bsh, d.stats_act);
-#pragma unroll
-              for (int j = 0; j < 4; ++j) {
-                const float gj = v[j] * ag[j];
-                st1[j] += gj;
-                st2[j] += gj * (xv[j] - bmu[j]) * brs[j];
-              }
+              stats_bwd_accum4(v, xv, piv, bsh, bmu, brs, d.stats_act, st1, st2);
             }
           } else {
-            const f32x4 dl = v - piv;
-            st1 += dl;
-            st2 += dl * dl;
+            stats_fwd_accum4(v, piv, st1, st2);
           }
         }
       }
     }
     WINO_STAMP(5);
-    if (d.stats_out) {  // PG pixel groups x CW channels -> one row of partials per pixel tile (fixed order)
-      __syncthreads();  // R is dead
-      float* red = smem;
-      *reinterpret_cast<f32x4*>(red + (t / C4N) * CW + c4) = st1;
-      *reinterpret_cast<f32x4*>(red + PG * CW + (t / C4N) * CW + c4) = st2;
-      __syncthreads();
-      if (t < 2 * CW) {
-        const int c = t % CW, which = t / CW;
-        float v = 0.f;
-#pragma unroll
-        for (int r = 0; r < PG; ++r) v += red[which * PG * CW + r * CW + c];
-        if (co0 + c < d.Cout) d.stats_out[((size_t)tm * 2 + which) * d.Cout + co0 + c] = v;
-        // the pivot travels with the partials (row index = number of pixel tiles) for a consumer that finalizes them in its own prologue
-        if (a.store_pivot && tm == 0 && which == 0 && co0 + c < d.Cout)
-          d.stats_out[((size_t)(gridDim.x / a.ntn) * 2) * d.Cout + co0 + c] = d.stats_pivot[co0 + c];
-      }
-    }
+    if (d.stats_out)  // PG pixel groups x CW channels -> one row of partials per pixel tile, the pivot row behind them; R is dead
+      stats_reduce_groups<PG, CW>(smem, t / C4N, c4, st1, st2, d.stats_out, tm, d.Cout, co0, a.store_pivot && tm == 0, d.stats_pivot,
+                                  gridDim.x / a.ntn);
   }
 }
 
@@ -793,8 +742,6 @@ __global__ __launch_bounds__(512) void conv3x3_wino2_kernel(WinoArgs a) {
     };
 #pragma unroll
     for (int it = 0; it < BR - 1; ++it) load_b(it, it);
-    constexpr int PA[6] = {2, 0, 1, 1, 0, 0};  // piece products in ascending order of magnitude
-    constexpr int PB[6] = {0, 2, 1, 0, 1, 0};
     // Software pipeline: the A fragments (transform + exact three-piece split, ~60 vector instructions) of step k + 1 are computed
     // while the 12 MFMAs of step k occupy the matrix unit; the last step of a 16-channel slice overlaps the staging of the next
     // slice instead. Steps of a slice: (position jj, block m) = (0,0) (0,1) (1,0) (1,1).
@@ -822,11 +769,7 @@ __global__ __launch_bounds__(512) void conv3x3_wino2_kernel(WinoArgs a) {
 #if LVAE_W2_PAIRSPLIT
       split8_3(vl, vh, af);
 #else
-      bf16x4 pl[3], ph[3];
-      split4<3>(vl, pl);
-      split4<3>(vh, ph);
-#pragma unroll
-      for (int q = 0; q < 3; ++q) af[q] = bf16x8{pl[q][0], pl[q][1], pl[q][2], pl[q][3], ph[q][0], ph[q][1], ph[q][2], ph[q][3]};
+      split_frag<3>(vl, vh, af);
 #endif
     };
 #pragma unroll
@@ -861,9 +804,7 @@ __global__ __launch_bounds__(512) void conv3x3_wino2_kernel(WinoArgs a) {
         }
 #pragma unroll
         for (int h = 0; h < NH; ++h)
-#pragma unroll
-          for (int kk = 0; kk < 6; ++kk)
-            acc[m][jj][h] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(afc[PA[kk]], bq[it % BR][h][PB[kk]], acc[m][jj][h], 0, 0, 0);
+          acc[m][jj][h] = mfma_pieces<3>(afc, bq[it % BR][h], acc[m][jj][h]);
         if (st < 3) {
 #pragma unroll
           for (int q = 0; q < 3; ++q) afc[q] = afn[q];
@@ -891,14 +832,8 @@ __global__ __launch_bounds__(512) void conv3x3_wino2_kernel(WinoArgs a) {
   // pair 0 holds (M0, M1) -> (M0 + M1, M1); pair 1 holds (M2, M3) -> (M2, -M2 - M3). Accumulator register r <-> tile (r&3) + 8(r>>2) + 4lh.
   float* Rs = smem;  // [wave][b][32 tiles][WLDO]
   const int c4 = (t % C4N) * 4, col = co0 + c4;
-  f32x4 st1 = zero4, st2 = zero4, piv = zero4;  // BatchNorm partials of the stored values (d.stats_out)
-  if (d.stats_out && col < d.Cout) piv = *reinterpret_cast<const f32x4*>(d.stats_pivot + col);
-  f32x4 bsh = piv, bmu = piv, brs = piv;  // LVAE_STATS_BN_BWD: piv = scale, then shift, mean, rstd of the [4][Cout] block
-  if (d.stats_out && d.stats_mode == LVAE_STATS_BN_BWD && col < d.Cout) {
-    bsh = *reinterpret_cast<const f32x4*>(d.stats_pivot + d.Cout + col);
-    bmu = *reinterpret_cast<const f32x4*>(d.stats_pivot + 2 * d.Cout + col);
-    brs = *reinterpret_cast<const f32x4*>(d.stats_pivot + 3 * d.Cout + col);
-  }
+  f32x4 st1 = zero4, st2 = zero4, piv, bsh, bmu, brs;  // BatchNorm partials of the stored values (d.stats_out)
+  stats_load_coef4(d.stats_pivot, d.Cout, col, d.stats_out != nullptr, d.stats_mode == LVAE_STATS_BN_BWD, piv, bsh, bmu, brs);
   f32x4 bias = zero4;
   if (d.bias && col < d.Cout) bias = *reinterpret_cast<const f32x4*>(d.bias + col);
   const int thw = a.TH * a.TW;
@@ -969,18 +904,10 @@ __global__ __launch_bounds__(512) void conv3x3_wino2_kernel(WinoArgs a) {
           } else if (d.stats_mode == LVAE_STATS_BN_BWD) {
             if (d.stats_out) {
               const f32x4 xv = sxr[q];
-              const f32x4 ag = act_grad4(xv * piv + bsh, d.stats_act);
-#pragma unroll
-              for (int j = 0; j < 4; ++j) {
-                const float gj = v[j] * ag[j];
-                st1[j] += gj;
-                st2[j] += gj * (xv[j] - bmu[j]) * brs[j];
-              }
+              stats_bwd_accum4(v, xv, piv, bsh, bmu, brs, d.stats_act, st1, st2);
             }
           } else {
-            const f32x4 dl = v - piv;
-            st1 += dl;
-            st2 += dl * dl;
+            stats_fwd_accum4(v, piv, st1, st2);
           }
         }
       }
@@ -1022,16 +949,15 @@ __global__ __launch_bounds__(512) void conv3x3_wino2_kernel(WinoArgs a) {
       f32x16 acca, accb;
 #pragma unroll
       for (int r = 0; r < 16; ++r) acca[r] = accb[r] = 0.f;
-      constexpr int GPA[6] = {2, 0, 1, 1, 0, 0}, GPB[6] = {0, 2, 1, 0, 1, 0};   // piece products in ascending order of magnitude
 #pragma unroll
       for (int s4 = 0; s4 < 4; ++s4) {
         bf16x8 af[3];
 #pragma unroll
         for (int k = 0; k < 3; ++k) af[k] = *reinterpret_cast<const bf16x8*>(Gs + k * G_PLANE + (gwm * 32 + li) * LDKG + 16 * s4 + 8 * lh);
 #pragma unroll
-        for (int kk = 0; kk < 6; ++kk) {
-          acca = __builtin_amdgcn_mfma_f32_32x32x16_bf16(af[GPA[kk]], gqa[s4][GPB[kk]], acca, 0, 0, 0);
-          accb = __builtin_amdgcn_mfma_f32_32x32x16_bf16(af[GPA[kk]], gqb[s4][GPB[kk]], accb, 0, 0, 0);
+        for (int kk = 0; kk < PieceOrder<3>::N; ++kk) {
+          acca = __builtin_amdgcn_mfma_f32_32x32x16_bf16(af[PieceOrder<3>::A[kk]], gqa[s4][PieceOrder<3>::B[kk]], acca, 0, 0, 0);
+          accb = __builtin_amdgcn_mfma_f32_32x32x16_bf16(af[PieceOrder<3>::A[kk]], gqb[s4][PieceOrder<3>::B[kk]], accb, 0, 0, 0);
         }
       }
       lds_barrier();   // the planes are dead: the area becomes the pre-activation tile [128][132] floats
@@ -1064,50 +990,21 @@ __global__ __launch_bounds__(512) void conv3x3_wino2_kernel(WinoArgs a) {
           for (int j = 0; j < 4; ++j) o[j] *= sigmoidf_(bv[j]);
           o += gres[q];
           store_wt4(a.g_out + (grow + pl) * 64 + c4, o);
-          const f32x4 dl = o - gpiv;
-          st1 += dl;
-          st2 += dl * dl;
+          stats_fwd_accum4(o, gpiv, st1, st2);
         }
       }
     }
   }
   WINO_STAMP(7);
   float* const so = GATE ? a.g_stats : d.stats_out;
-  if (GATE && so != nullptr) {  // BatchNorm partials of `out` (the next block's first BatchNorm): one row per workgroup + the pivot row
-    __syncthreads();
-    float* red = smem;
-    *reinterpret_cast<f32x4*>(red + (t / C4N) * CW + c4) = st1;
-    *reinterpret_cast<f32x4*>(red + PG * CW + (t / C4N) * CW + c4) = st2;
-    __syncthreads();
-    if (t < 2 * CW) {
-      const int c = t % CW, which = t / CW;
-      float v = 0.f;
-#pragma unroll
-      for (int r = 0; r < PG; ++r) v += red[which * PG * CW + r * CW + c];
-      so[((size_t)tm * 2 + which) * 64 + c] = v;
-      if (tm == 0 && which == 0) so[((size_t)(gridDim.x / a.ntn) * 2) * 64 + c] = a.g_pivot[c];
-    }
-  }
-  if (!GATE && d.stats_out) {  // PG pixel groups x CW channels -> one row of partials per workgroup (fixed order)
-    __syncthreads();  // the partial sums are dead
-    float* red = smem;
-    *reinterpret_cast<f32x4*>(red + (t / C4N) * CW + c4) = st1;
-    *reinterpret_cast<f32x4*>(red + PG * CW + (t / C4N) * CW + c4) = st2;
-    __syncthreads();
-    if (t < 2 * CW) {
-      const int c = t % CW, which = t / CW;
-      float v = 0.f;
-#pragma unroll
-      for (int r = 0; r < PG; ++r) v += red[which * PG * CW + r * CW + c];
-      if (co0 + c < d.Cout) d.stats_out[((size_t)tm * 2 + which) * d.Cout + co0 + c] = v;
-      // the pivot travels with the partials (row index = number of pixel tiles) for a consumer that finalizes them in its own prologue
-      if (a.store_pivot && tm == 0 && which == 0 && co0 + c < d.Cout)
-        d.stats_out[((size_t)(gridDim.x / a.ntn) * 2) * d.Cout + co0 + c] = d.stats_pivot[co0 + c];
-    }
-  }
+  // PG pixel groups x CW channels -> one row of partials per workgroup, the pivot row behind them (the partial sums in LDS are dead)
+  if (GATE && so != nullptr)  // BatchNorm partials of `out` (the next block's first BatchNorm)
+    stats_reduce_groups<PG, CW>(smem, t / C4N, c4, st1, st2, so, tm, 64, 0, tm == 0, a.g_pivot, gridDim.x / a.ntn);
+  if (!GATE && d.stats_out)
+    stats_reduce_groups<PG, CW>(smem, t / C4N, c4, st1, st2, d.stats_out, tm, d.Cout, co0, a.store_pivot && tm == 0, d.stats_pivot,
+                                gridDim.x / a.ntn);
 }
 
-static bool al16w2(const void* p) { return p == nullptr || (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
 
 static int wino_kpad(const lvae_conv_desc* d) { return d->C1 <= 64 ? 64 : 128; }
 static bool kpad_is64(const lvae_conv_desc* d) { return d->C1 <= 64; }
@@ -1150,7 +1047,7 @@ bool conv3x3_wino_eligible(const lvae_conv_desc* d) {
   const int Cin = d->C1;
   if (d->KH != 3 || d->KW != 3 || d->stride != 1 || d->pad != 1 || d->x2 != nullptr || d->OH != d->H || d->OW != d->W) return false;
   if (Cin < 36 || Cin > 128 || Cin % 4 != 0 || d->Cout % 4 != 0 || (d->H & 1) || (d->W & 1) || d->W > 128) return false;
-  if (!al16w2(d->x) || !al16w2(d->y) || !al16w2(d->bias) || !al16w2(d->in_scale) || !al16w2(d->in_shift) || !al16w2(d->out_scale)) return false;
+  if (!al16_or_null(d->x) || !al16_or_null(d->y) || !al16_or_null(d->bias) || !al16_or_null(d->in_scale) || !al16_or_null(d->in_shift) || !al16_or_null(d->out_scale)) return false;
   const int64_t M = (int64_t)d->N * d->H * d->W;
   static const int64_t min_m = tune("LVAE_WINO_MIN_M", 256 * 64);
   if (M < min_m || M * 128 >= ((int64_t)1 << 31)) return false;  // large layers only: smaller ones are latency bound
@@ -1208,7 +1105,7 @@ static bool wino_folds(const lvae_conv_desc* d, const WinoTile& w) {
 bool conv3x3_wino_plan(const lvae_conv_desc* d, bool assume_ws, ConvPlan& p) {
   if (!conv3x3_wino_eligible(d)) return false;
   const size_t ws = conv3x3_wino_workspace(d);
-  if (!assume_ws && (d->workspace == nullptr || (size_t)d->workspace_bytes < ws || !al16w2(d->workspace))) return false;
+  if (!assume_ws && (d->workspace == nullptr || (size_t)d->workspace_bytes < ws || !al16_or_null(d->workspace))) return false;
   WinoTile w;
   if (!wino_tile(d, w) || wino_lds_bytes(d, w) > 159 * 1024) return false;  // + 512 bytes of static LDS (s_coef)
   p = ConvPlan{};
@@ -1338,14 +1235,14 @@ extern "C" int lvae_conv2d_prepare_entry(const lvae_conv_desc* d, void* entry) {
   if (!conv3x3_pos_plan(d, pos)) {
     const int form = conv3x3_bf16_form(d);
     if (form != 0) {
-      LVAE_REQUIRE(d->workspace && (size_t)d->workspace_bytes >= conv3x3_bf16_workspace(d, form) && al16w2(d->workspace), LVAE_EINVAL,
+      LVAE_REQUIRE(d->workspace && (size_t)d->workspace_bytes >= conv3x3_bf16_workspace(d, form) && al16_or_null(d->workspace), LVAE_EINVAL,
                    "lvae_conv2d_prepare_entry: no scratch for the pre-split weights");
       conv3x3_bf16_prep_entry(d, form, entry);
       return 0;
     }
   }
   LVAE_REQUIRE(conv3x3_wino_eligible(d) && d->workspace && (size_t)d->workspace_bytes >= conv3x3_wino_workspace(d) &&
-                   al16w2(d->workspace),
+                   al16_or_null(d->workspace),
                LVAE_EINVAL, "lvae_conv2d_prepare_entry: descriptor has no weight pre-transform (lvae_conv2d_workspace(d) == 0) or no scratch");
   WinoPrepEntry e;
   e.w = d->w;

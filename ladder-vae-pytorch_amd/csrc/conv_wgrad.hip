@@ -499,7 +499,6 @@ static void wgrad_plan(const lvae_conv_desc* d, int& ksplit, int& px_per_split, 
   ksplit = (M + px_per_split - 1) / px_per_split;
 }
 
-static bool al16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
 
 struct WgradRoute {
   int32_t variant = LVAE_WGRAD_VARIANT_GENERIC;  // LVAE_WGRAD_VARIANT_*

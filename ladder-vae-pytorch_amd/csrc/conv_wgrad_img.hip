@@ -193,16 +193,8 @@ __global__ __launch_bounds__(512) void wgrad_img_kernel(WgImgGroup g) {
           if (dbg & 2) {
 #pragma unroll
             for (int q = 0; q < SPLIT; ++q) asm volatile("" ::"v"(afr[q]), "v"(bfr[q]));
-          } else
-          if (SPLIT == 1) {
-            acc[j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(afr[0], bfr[0], acc[j], 0, 0, 0);
-          } else {  // piece products in ascending order of magnitude
-            acc[j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(afr[SPLIT - 1], bfr[0], acc[j], 0, 0, 0);
-            acc[j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(afr[0], bfr[SPLIT - 1], acc[j], 0, 0, 0);
-            acc[j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(afr[1], bfr[1], acc[j], 0, 0, 0);
-            acc[j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(afr[1], bfr[0], acc[j], 0, 0, 0);
-            acc[j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(afr[0], bfr[1], acc[j], 0, 0, 0);
-            acc[j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(afr[0], bfr[0], acc[j], 0, 0, 0);
+          } else {
+            acc[j] = mfma_pieces<SPLIT>(afr, bfr, acc[j]);
           }
         }
       }
@@ -239,7 +231,6 @@ __global__ __launch_bounds__(512) void wgrad_img_kernel(WgImgGroup g) {
 // ---------------------------------------------------------------------------------------------------------------------------
 // host side
 // ---------------------------------------------------------------------------------------------------------------------------
-static bool al16i(const void* p) { return p == nullptr || (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
 
 #ifndef LVAE_WGRAD_IMG
 #define LVAE_WGRAD_IMG 1
@@ -256,7 +247,7 @@ static int wgi_plan(const lvae_conv_desc* d, WgImgProb& a) {
   if (HW < 4 || HW > 64 || 64 % HW != 0 || d->N < 1) return -1;
   if (d->C1 > 64 || d->C1 % 4 != 0 || d->Cout % 4 != 0 || d->Cout > (k3 ? 64 : 128)) return -1;
   if (k1 && d->Cout <= 64 && d->C1 <= 32) return -1;   // tiny 1x1 problems: nothing to gain
-  if (!al16i(d->x) || !al16i(d->in_scale) || !al16i(d->in_shift) || (d->in_scale != nullptr && d->in_shift == nullptr)) return -1;
+  if (!al16_or_null(d->x) || !al16_or_null(d->in_scale) || !al16_or_null(d->in_shift) || (d->in_scale != nullptr && d->in_shift == nullptr)) return -1;
   if ((int64_t)d->N * HW * 128 >= ((int64_t)1 << 31)) return -1;
   const int pad = k3 ? 1 : 0;
   a.N = d->N; a.HW = HW; a.W = d->W; a.Cin = d->C1; a.Cout = d->Cout; a.in_act = d->in_act;

@@ -60,6 +60,10 @@ inline int64_t tune(const char* name, int64_t dflt) {
     }                                                                  \
   } while (0)
 
+// 16-byte alignment of a pointer the kernels read with 16-byte loads: of a required pointer, and of an optional one (null = absent)
+inline bool al16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
+inline bool al16_or_null(const void* p) { return p == nullptr || al16(p); }
+
 // 16-byte store of a large output tensor as a write-through (sc1) store. Plain stores leave the lines dirty in the XCD's L2 until the
 // end of the kernel, whose release then writes them back in one go, after the last wave (about bytes / 6 TB/s: ~3 us behind the
 // 16.8 MB of a 256x16x16x64 tensor; MI355X_MICROARCH.md, "boundary" and "publish-large"). Written through, the bytes drain

@@ -3,6 +3,7 @@
 // consecutive channels/rows, per-channel reductions go through registers -> LDS -> per-chunk partials and a
 // fixed-order finalize (no float atomics: bitwise reproducible).
 #include "bf16_frag.h"
+#include "bn_stats.h"
 #include "lvae_common.h"
 
 namespace lvae {
@@ -150,21 +151,12 @@ __global__ __launch_bounds__(256) void bn_finalize_kernel(const float* __restric
   if (tid != 0) return;
   double a = (part[0][0] + part[1][0]) + (part[2][0] + part[3][0]);
   double b = (part[0][1] + part[1][1]) + (part[2][1] + part[3][1]);
-  const double inv_m = 1.0 / (double)M, dm = a * inv_m;  // mean - pivot
-  double m2 = b - a * dm;                                 // sum (x - mean)^2
-  if (m2 < 0.0) m2 = 0.0;
-  const double mean = (double)pivot + dm, var = m2 * inv_m;
-  const float rstd = (float)(1.0 / sqrt(var + (double)eps));
-  const float sc = g * rstd;
-  scale[c] = sc;
-  shift[c] = be - (float)mean * sc;
-  mean_out[c] = (float)mean;
-  rstd_out[c] = rstd;
-  if (running_mean) {
-    const double unbiased = M > 1 ? m2 / (double)(M - 1) : var;
-    running_mean[c] = (1.f - momentum) * rm0 + momentum * (float)mean;
-    running_var[c] = (1.f - momentum) * rv0 + momentum * (float)unbiased;
-  }
+  const BnChannel r = bn_finalize_channel(a, b, pivot, M, eps, g, be);
+  scale[c] = r.scale;
+  shift[c] = r.shift;
+  mean_out[c] = r.mean;
+  rstd_out[c] = r.rstd;
+  if (running_mean) bn_update_running(running_mean, running_var, c, rm0, rv0, momentum, r, M);
 }
 
 __global__ void bn_eval_coeffs_kernel(int C, const float* gamma, const float* beta, const float* rm, const float* rv,
@@ -288,10 +280,11 @@ __global__ __launch_bounds__(256) void affine_bwd_finalize_kernel(const float* _
   if (tid != 0) return;
   const double a = (part[0][0] + part[1][0]) + (part[2][0] + part[3][0]);
   const double b = (part[0][1] + part[1][1]) + (part[2][1] + part[3][1]);
-  if (dbeta) dbeta[c] = db0 + (float)a;
-  if (dgamma) dgamma[c] = dg0 + (float)b;
-  coef[c] = (float)(a / (double)M);
-  coef[C + c] = (float)(b / (double)M);
+  const BnBwdChannel r = bn_bwd_finish(a, b, M);
+  if (dbeta) dbeta[c] = db0 + r.dbeta;
+  if (dgamma) dgamma[c] = dg0 + r.dgamma;
+  coef[c] = r.c1;
+  coef[C + c] = r.c2;
 }
 
 // U: rows per thread and round trip (independent loads in flight)
@@ -336,7 +329,7 @@ __global__ __launch_bounds__(256) void affine_bwd_apply_kernel(const float* __re
       for (int j = 0; j < V; ++j) {
         const float xx = at<V>(xv[u], j);
         float g = at<V>(gv[u], j) * act_grad(xx * sc[j] + sh[j], act);
-        g = (g - c1[j] - (xx - mu[j]) * rs[j] * c2[j]) * sc[j];
+        g = bn_bwd_apply(g, xx, c1[j], c2[j], mu[j], rs[j], sc[j]);
         if (dr) g *= dr[j];
         if (add) g += at<V>(av[u], j);
         at<V>(gv[u], j) = g;
@@ -354,7 +347,7 @@ __global__ __launch_bounds__(256) void affine_bwd_apply_kernel(const float* __re
     for (int j = 0; j < V; ++j) {
       const float xx = at<V>(xv, j);
       float g = at<V>(gv, j) * act_grad(xx * sc[j] + sh[j], act);
-      g = (g - c1[j] - (xx - mu[j]) * rs[j] * c2[j]) * sc[j];
+      g = bn_bwd_apply(g, xx, c1[j], c2[j], mu[j], rs[j], sc[j]);
       if (dr) g *= dr[j];
       if (add) g += at<V>(av, j);
       at<V>(gv, j) = g;
@@ -433,11 +426,12 @@ __global__ __launch_bounds__(256) void affine_bwd_apply_parts_kernel(const float
         sa += (double)red[0][(sl * cols + cg) * 4 + j];
         sb += (double)red[1][(sl * cols + cg) * 4 + j];
       }
-      cf[0][t] = (float)(sa / (double)M);
-      cf[1][t] = (float)(sb / (double)M);
+      const BnBwdChannel r = bn_bwd_finish(sa, sb, M);
+      cf[0][t] = r.c1;
+      cf[1][t] = r.c2;
       if (blockIdx.x == 0) {
-        if (dbeta) dbeta[t] = db0 + (float)sa;
-        if (dgamma) dgamma[t] = dg0 + (float)sb;
+        if (dbeta) dbeta[t] = db0 + r.dbeta;
+        if (dgamma) dgamma[t] = dg0 + r.dgamma;
       }
     }
     __syncthreads();
@@ -453,7 +447,7 @@ __global__ __launch_bounds__(256) void affine_bwd_apply_parts_kernel(const float
     for (int j = 0; j < 4; ++j) {
       const float xx = xq.v[j];
       float g = gq.v[j] * act_grad(xx * sc[j] + sh[j], act);
-      g = (g - c1[j] - (xx - mu[j]) * rs[j] * c2[j]) * sc[j];
+      g = bn_bwd_apply(g, xx, c1[j], c2[j], mu[j], rs[j], sc[j]);
       if (dr) g *= dr[j];
       if (add) g += aq.v[j];
       gq.v[j] = g;

@@ -26,6 +26,7 @@
 #include <string.h>
 
 #include "bf16_frag.h"
+#include "bn_stats.h"
 #include "lvae_common.h"
 
 namespace lvae {
@@ -45,32 +46,6 @@ constexpr int RB_LDO = 68;            // floats per staged output row (64 + 4)
 constexpr int RB_LDG = 132;           // floats per staged gate pre-activation row (128 + 4)
 constexpr int RB_SCR_BYTES = 9216;    // reduction scratch in front of the tile regions
 
-// piece products of the six-product form in ascending order of magnitude: (2,0) (0,2) (1,1) (1,0) (0,1) (0,0)
-template <int SPLIT>
-__device__ __forceinline__ f32x16 mfma_pieces(const bf16x8 (&af)[SPLIT], const bf16x8 (&bf)[SPLIT], f32x16 acc) {
-  if (SPLIT == 1) {
-    acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(af[0], bf[0], acc, 0, 0, 0);
-  } else {
-    acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(af[SPLIT - 1], bf[0], acc, 0, 0, 0);
-    acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(af[0], bf[SPLIT - 1], acc, 0, 0, 0);
-    acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(af[1], bf[1], acc, 0, 0, 0);
-    acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(af[1], bf[0], acc, 0, 0, 0);
-    acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(af[0], bf[1], acc, 0, 0, 0);
-    acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(af[0], bf[0], acc, 0, 0, 0);
-  }
-  return acc;
-}
-
-// eight fp32 weights of one B fragment -> SPLIT bf16x8 pieces
-template <int SPLIT>
-__device__ __forceinline__ void split_frag(const float (&wv)[8], bf16x8 (&out)[SPLIT]) {
-  bf16x4 lo[SPLIT], hi[SPLIT];
-  split4<SPLIT>(f32x4{wv[0], wv[1], wv[2], wv[3]}, lo);
-  split4<SPLIT>(f32x4{wv[4], wv[5], wv[6], wv[7]}, hi);
-#pragma unroll
-  for (int q = 0; q < SPLIT; ++q) out[q] = bf16x8{lo[q][0], lo[q][1], lo[q][2], lo[q][3], hi[q][0], hi[q][1], hi[q][2], hi[q][3]};
-}
-
 // In-kernel phase stamps of the profiling builds (-DLVAE_RB_DBG; tools/rb_stamps.sh): s_memtime per wave at the phase boundaries, written to
 // a buffer of their own that nothing else reads. Never compiled into the product.
 #ifdef LVAE_RB_DBG
@@ -89,49 +64,6 @@ __device__ unsigned long long g_rb_stamps[1024 * 4 * 12];
 #define RB_STAMP(i) do {} while (0)
 #define RB_STAMP_FLUSH do {} while (0)
 #endif
-
-// LDS-only workgroup barrier. __syncthreads() is a workgroup fence, for which hipcc waits for EVERY outstanding memory operation of the
-// wave (s_waitcnt vmcnt(0)): global loads that were requested early on purpose, and the write-through stores of the epilogues, whose
-// completion takes a trip to memory (measured with the phase stamps: 1.2-2 us per barrier behind such stores). All data that crosses
-// waves inside these kernels goes through LDS, so only the LDS counter has to drain.
-__device__ __forceinline__ void rb_bar() { asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory"); }
-
-typedef unsigned int u32x2v __attribute__((ext_vector_type(2)));
-// four fp32 values -> SPLIT bf16x4 pieces that sum to them exactly (SPLIT = 3) / their round-to-nearest bf16 (SPLIT = 1); pairwise, so
-// that hipcc emits one v_cvt_pk_bf16_f32 per two values and stage (bf16_frag.h split8_3)
-template <int SPLIT>
-__device__ __forceinline__ void rb_split4(const f32x4 v, bf16x4 (&out)[SPLIT]) {
-  u32x2v w[SPLIT];
-#pragma unroll
-  for (int p = 0; p < 2; ++p) {
-    float a = v[2 * p], b = v[2 * p + 1];
-#pragma unroll
-    for (int q = 0; q < SPLIT; ++q) {
-      const bf16x2 h = __builtin_convertvector(f32x2v{a, b}, bf16x2);
-      const unsigned bits = __builtin_bit_cast(unsigned, h);
-      w[q][p] = bits;
-      if (q + 1 < SPLIT) {
-        a -= __builtin_bit_cast(float, bits << 16);  // exact: the remainder of a round-to-nearest to 8 bits has <= 16 significant bits
-        b -= __builtin_bit_cast(float, bits & 0xffff0000u);
-      }
-    }
-  }
-#pragma unroll
-  for (int q = 0; q < SPLIT; ++q) out[q] = __builtin_bit_cast(bf16x4, w[q]);
-}
-
-// activation derivative w.r.t. the pre-activation, four values, ONE wave-uniform branch for the common case
-__device__ __forceinline__ f32x4 rb_act_grad4(f32x4 u, int act) {
-  f32x4 r;
-  if (act == LVAE_ACT_ELU) {
-#pragma unroll
-    for (int j = 0; j < 4; ++j) r[j] = u[j] > 0.f ? 1.f : __expf(u[j]);
-    return r;
-  }
-#pragma unroll
-  for (int j = 0; j < 4; ++j) r[j] = act_grad(u[j], act);
-  return r;
-}
 
 // Sum of the partial rows [rows][2][64] a producer's statistics epilogue left, by all 256 threads with 16-byte loads, in a fixed order;
 // the 8 row groups are combined in double by threads 0..63, which hand (channel, sum 1, sum 2) to `finish` between the two barriers.
@@ -171,7 +103,7 @@ __device__ __forceinline__ void rb_parts_finish(const float* __restrict__ parts,
       if (r + 8 * u < rows) acc += v[u];
   }
   *reinterpret_cast<f32x4*>(scr + rg * 128 + q * 4) = acc;   // [8][128]
-  rb_bar();
+  lds_barrier();
 #ifdef LVAE_RB_DBG
   if (ts) ts[9] = __builtin_amdgcn_s_memtime();
 #endif
@@ -184,7 +116,7 @@ __device__ __forceinline__ void rb_parts_finish(const float* __restrict__ parts,
     }
     finish(t, sa, sb);
   }
-  rb_bar();
+  lds_barrier();
 }
 
 // The tile is 64 pixels (whole images) x 64 channels per workgroup, 4 waves. In the 3x3 reduction loop wave w owns the w-th 16-channel
@@ -250,7 +182,7 @@ __global__ __launch_bounds__(256) void rb_conv_kernel(RbArgs a) {
   const int rb_reps = a.flip >= 0 ? LVAE_RB_DBG_REPS : 1;
 #pragma unroll 1
   for (int rb_rep = 0; rb_rep < rb_reps; ++rb_rep) {
-  rb_bar();
+  lds_barrier();
 #endif
   RB_STAMP(0);
   // ---- L2 warm-up for the NEXT launch. Every convolution of a step has weights of its own, so the 221 KB a workgroup streams are cold in
@@ -303,7 +235,7 @@ __global__ __launch_bounds__(256) void rb_conv_kernel(RbArgs a) {
   }
   auto put_interior = [&](int q, f32x4 v) {
     bf16x4 pl[SPLIT];
-    rb_split4<SPLIT>(v, pl);
+    split4_packed<SPLIT>(v, pl);
 #pragma unroll
     for (int k = 0; k < SPLIT; ++k) *reinterpret_cast<bf16x4*>(As + k * a_plane + hp[q]) = pl[k];
   };
@@ -345,26 +277,12 @@ __global__ __launch_bounds__(256) void rb_conv_kernel(RbArgs a) {
     f32x4 sc = one4, sh = zero4;
     if (f.parts != nullptr) {
       rb_parts_finish(f.parts, f.rows, pv, scr, [&](int c, double sa, double sb) {
-        const double M = (double)f.M, inv_m = 1.0 / M, dm = sa * inv_m;
-        double m2 = sb - sa * dm;
-        if (m2 < 0.0) m2 = 0.0;
-        const double mean = (double)pivot + dm, var = m2 * inv_m;
-        const float rstd = (float)(1.0 / sqrt(var + (double)f.eps));
-        const float scl = gam * rstd, shf = bet - (float)mean * scl;
-        scr[1024 + c] = scl;
-        scr[1024 + 64 + c] = shf;
+        const BnChannel r = bn_finalize_channel(sa, sb, pivot, f.M, f.eps, gam, bet);
+        scr[1024 + c] = r.scale;
+        scr[1024 + 64 + c] = r.shift;
         if (bid == 0) {
-          if (f.coef_out) {
-            f.coef_out[c] = scl;
-            f.coef_out[64 + c] = shf;
-            f.coef_out[128 + c] = (float)mean;
-            f.coef_out[192 + c] = rstd;
-          }
-          if (upd) {
-            const double unbiased = f.M > 1 ? m2 / (M - 1.0) : var;
-            f.running_mean[c] = (1.f - f.momentum) * rm0 + f.momentum * (float)mean;
-            f.running_var[c] = (1.f - f.momentum) * rv0 + f.momentum * (float)unbiased;
-          }
+          if (f.coef_out) bn_store_coef(f.coef_out, 64, c, r);
+          if (upd) bn_update_running(f.running_mean, f.running_var, c, rm0, rv0, f.momentum, r, f.M);
         }
       });
       sc = *reinterpret_cast<const f32x4*>(scr + 1024 + c4);
@@ -405,11 +323,12 @@ __global__ __launch_bounds__(256) void rb_conv_kernel(RbArgs a) {
     }
     zero_ring();   // while the loads are in flight
     rb_parts_finish(e.bwd_parts, e.bwd_rows, pv, scr, [&](int c, double sa, double sb) {
-      scr[1024 + c] = (float)(sa / (double)e.bwd_M);
-      scr[1024 + 64 + c] = (float)(sb / (double)e.bwd_M);
+      const BnBwdChannel r = bn_bwd_finish(sa, sb, e.bwd_M);
+      scr[1024 + c] = r.c1;
+      scr[1024 + 64 + c] = r.c2;
       if (bid == 0) {
-        if (e.dbeta) e.dbeta[c] = db0 + (float)sa;
-        if (e.dgamma) e.dgamma[c] = dg0 + (float)sb;
+        if (e.dbeta) e.dbeta[c] = db0 + r.dbeta;
+        if (e.dgamma) e.dgamma[c] = dg0 + r.dgamma;
       }
     }
 #ifdef LVAE_RB_DBG
@@ -420,8 +339,8 @@ __global__ __launch_bounds__(256) void rb_conv_kernel(RbArgs a) {
     RB_STAMP(1);
 #pragma unroll
     for (int q = 0; q < NQ; ++q) {
-      const f32x4 g = gv[q] * rb_act_grad4(xv[q] * sc + sh, bwd_act);
-      f32x4 v = (g - c1 - (xv[q] - mu) * rs * c2) * sc * dm[q];
+      const f32x4 g = gv[q] * act_grad4(xv[q] * sc + sh, bwd_act);
+      f32x4 v = bn_bwd_apply(g, xv[q], c1, c2, mu, rs, sc) * dm[q];
       if (!ok[q]) v = zero4;
       if (ok[q] && e.xt_out) store_wt4(e.xt_out + grow[q] * 64 + c4, v);
       put_interior(q, v);
@@ -455,18 +374,19 @@ __global__ __launch_bounds__(256) void rb_conv_kernel(RbArgs a) {
         bb[q] = *reinterpret_cast<const f32x4*>(e.ab_in + grow[q] * 128 + 64 + c4);
       }
       rb_parts_finish(e.ap_parts, e.ap_rows, pv, scr, [&](int c, double sa, double sb) {
-        scr[1024 + c] = (float)(sa / (double)e.ap_M);
-        scr[1024 + 64 + c] = (float)(sb / (double)e.ap_M);
+        const BnBwdChannel r = bn_bwd_finish(sa, sb, e.ap_M);
+        scr[1024 + c] = r.c1;
+        scr[1024 + 64 + c] = r.c2;
         if (bid == 0) {
-          if (e.ap_dbeta) e.ap_dbeta[c] = db0 + (float)sa;
-          if (e.ap_dgamma) e.ap_dgamma[c] = dg0 + (float)sb;
+          if (e.ap_dbeta) e.ap_dbeta[c] = db0 + r.dbeta;
+          if (e.ap_dgamma) e.ap_dgamma[c] = dg0 + r.dgamma;
         }
       });
       const f32x4 c1 = *reinterpret_cast<const f32x4*>(scr + 1024 + c4), c2 = *reinterpret_cast<const f32x4*>(scr + 1024 + 64 + c4);
 #pragma unroll
       for (int q = 0; q < NQ; ++q) {
-        const f32x4 g = go[q] * rb_act_grad4(xa[q] * sc + sh, ap_act);
-        const f32x4 v = (g - c1 - (xa[q] - mu) * rs * c2) * sc + ad[q];
+        const f32x4 g = go[q] * act_grad4(xa[q] * sc + sh, ap_act);
+        const f32x4 v = bn_bwd_apply(g, xa[q], c1, c2, mu, rs, sc) + ad[q];
         go[q] = v;
         if (ok[q]) store_wt4(e.ap_out + grow[q] * 64 + c4, v);
       }
@@ -501,7 +421,7 @@ __global__ __launch_bounds__(256) void rb_conv_kernel(RbArgs a) {
         da[j] = gs;
         db[j] = gs * (1.f - s);
       }
-      da = da * rb_act_grad4(aa[q], gate_act);
+      da = da * act_grad4(aa[q], gate_act);
       db = db * act_fwd4(aa[q], gate_act);
       if (!ok[q]) da = db = zero4;
       if (ok[q] && e.dab) {
@@ -509,8 +429,8 @@ __global__ __launch_bounds__(256) void rb_conv_kernel(RbArgs a) {
         store_wt4(e.dab + grow[q] * 128 + 64 + c4, db);
       }
       bf16x4 pa[SPLIT], pb[SPLIT];
-      rb_split4<SPLIT>(da, pa);
-      rb_split4<SPLIT>(db, pb);
+      split4_packed<SPLIT>(da, pa);
+      split4_packed<SPLIT>(db, pb);
 #pragma unroll
       for (int k = 0; k < SPLIT; ++k) {
         *reinterpret_cast<bf16x4*>(Ds + k * d_plane + p * LDD + c4) = pa[k];
@@ -518,7 +438,7 @@ __global__ __launch_bounds__(256) void rb_conv_kernel(RbArgs a) {
       }
     }
     RB_STAMP(8);
-    rb_bar();
+    lds_barrier();
     f32x16 acc1;
 #pragma unroll
     for (int r = 0; r < 16; ++r) acc1[r] = 0.f;
@@ -532,13 +452,13 @@ __global__ __launch_bounds__(256) void rb_conv_kernel(RbArgs a) {
       }
     }
     RB_STAMP(9);
-    rb_bar();  // Ds is dead: its head becomes the dy2 staging tile
+    lds_barrier();  // Ds is dead: its head becomes the dy2 staging tile
     float* Os1 = reinterpret_cast<float*>(mainr);
     if (g1_on) {
 #pragma unroll
       for (int r = 0; r < 16; ++r) Os1[(wm * 32 + (r & 3) + 8 * (r >> 2) + 4 * lh) * LDO + wn * 32 + li] = acc1[r];
     }
-    rb_bar();
+    lds_barrier();
 #pragma unroll
     for (int q = 0; q < NQ; ++q) {
       const int p = p0 + 16 * q;
@@ -607,7 +527,7 @@ __global__ __launch_bounds__(256) void rb_conv_kernel(RbArgs a) {
       for (int r = 0; r < 16; ++r) acc[mb][nh][r] = 0.f;
 
   RB_STAMP(2);
-  rb_bar();
+  lds_barrier();
   RB_STAMP(3);
 
   // =====================================================================================================================
@@ -653,7 +573,7 @@ __global__ __launch_bounds__(256) void rb_conv_kernel(RbArgs a) {
       }
   }
 
-  rb_bar();  // every wave is done with the patch: the region becomes the output staging tiles
+  lds_barrier();  // every wave is done with the patch: the region becomes the output staging tiles
 
   // =====================================================================================================================
   // epilogue: the four waves' partial tiles [wave][64][68] -> summed by the reader -> 16-byte row stores
@@ -667,7 +587,7 @@ __global__ __launch_bounds__(256) void rb_conv_kernel(RbArgs a) {
 #pragma unroll
       for (int r = 0; r < 16; ++r)
         Os[wave * OSW + (mb * 32 + (r & 3) + 8 * (r >> 2) + 4 * lh) * LDO + nh * 32 + li] = acc[mb][nh][r];
-  rb_bar();
+  lds_barrier();
   RB_STAMP(5);
   auto os_sum = [&](int p) {
     const float* o = Os + p * LDO + c4;
@@ -692,13 +612,9 @@ __global__ __launch_bounds__(256) void rb_conv_kernel(RbArgs a) {
         store_wt4(d.y + grow[q] * 64 + c4, v);
         if (stats_out) {
           if (stats_fwd) {
-            const f32x4 dl = v - ep_piv;
-            st1 += dl;
-            st2 += dl * dl;
+            stats_fwd_accum4(v, ep_piv, st1, st2);
           } else {
-            const f32x4 g = v * rb_act_grad4(ep_sx[q] * ep_piv + ep_bsh, stats_act);
-            st1 += g;
-            st2 += g * (ep_sx[q] - ep_bmu) * ep_brs;
+            stats_bwd_accum4(v, ep_sx[q], ep_piv, ep_bsh, ep_bmu, ep_brs, stats_act, st1, st2);
           }
         }
       }
@@ -716,11 +632,11 @@ __global__ __launch_bounds__(256) void rb_conv_kernel(RbArgs a) {
       if (!ok[q]) v = zero4;
       if (ok[q]) store_wt4(d.y + grow[q] * 64 + c4, v);
       bf16x4 pl[SPLIT];
-      rb_split4<SPLIT>(v, pl);
+      split4_packed<SPLIT>(v, pl);
 #pragma unroll
       for (int k = 0; k < SPLIT; ++k) *reinterpret_cast<bf16x4*>(Gs + k * g_plane + p * LDK + c4) = pl[k];
     }
-    rb_bar();
+    lds_barrier();
     f32x16 acca, accb;
 #pragma unroll
     for (int r = 0; r < 16; ++r) acca[r] = accb[r] = 0.f;
@@ -732,7 +648,7 @@ __global__ __launch_bounds__(256) void rb_conv_kernel(RbArgs a) {
       acca = mfma_pieces<SPLIT>(af, gqa[s], acca);
       if (MI == 2) accb = mfma_pieces<SPLIT>(af, gqb[s], accb);
     }
-    rb_bar();  // the partial tiles and Gs are dead: the region becomes the pre-activation tile [BM][132]
+    lds_barrier();  // the partial tiles and Gs are dead: the region becomes the pre-activation tile [BM][132]
     constexpr int LDG = RB_LDG;
     float* Qs = reinterpret_cast<float*>(mainr);
 #pragma unroll
@@ -745,7 +661,7 @@ __global__ __launch_bounds__(256) void rb_conv_kernel(RbArgs a) {
         Qs[row * LDG + wave * 32 + li] = acca[r];
       }
     }
-    rb_bar();
+    lds_barrier();
     stats_out = e.out_stats;
     stats_pivot = e.out_stats_pivot;
 #pragma unroll
@@ -763,22 +679,21 @@ __global__ __launch_bounds__(256) void rb_conv_kernel(RbArgs a) {
         for (int j = 0; j < 4; ++j) o[j] *= sigmoidf_(bv[j]);
         o += ep_res[q];
         store_wt4(e.out + grow[q] * 64 + c4, o);
-        if (stats_out) {
-          const f32x4 dl = o - ep_piv;
-          st1 += dl;
-          st2 += dl * dl;
-        }
+        if (stats_out) stats_fwd_accum4(o, ep_piv, st1, st2);
       }
     }
   }
 
   RB_STAMP(6);
-  if (stats_out) {  // 16 row groups x 64 channels -> one row of partials per workgroup (fixed order); the pivot travels behind the rows
-    rb_bar();
+  // 16 row groups x 64 channels -> one row of partials per workgroup (fixed order); the pivot travels behind the rows. This is
+  // stats_reduce_groups<16, 64> (bn_stats.h) written out, as are the coefficient loads above: called from here the helpers cost the
+  // variants that sit at the register limit a spill (20 bytes of scratch in the fp32 64-pixel BatchNorm-apply kernel)
+  if (stats_out) {
+    lds_barrier();
     float* red = reinterpret_cast<float*>(mainr);
     *reinterpret_cast<f32x4*>(red + (t >> 4) * 64 + c4) = st1;
     *reinterpret_cast<f32x4*>(red + 1024 + (t >> 4) * 64 + c4) = st2;
-    rb_bar();
+    lds_barrier();
     if (t < 128) {
       const int c = t & 63, which = t >> 6;
       float v = 0.f;
@@ -798,7 +713,6 @@ __global__ __launch_bounds__(256) void rb_conv_kernel(RbArgs a) {
 // ---------------------------------------------------------------------------------------------------------------------------
 // host side
 // ---------------------------------------------------------------------------------------------------------------------------
-static bool al16r(const void* p) { return p == nullptr || (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
 
 size_t conv3x3_bf16_workspace(const lvae_conv_desc* d, int split);
 void conv3x3_bf16_prep_entry(const lvae_conv_desc* d, int split, void* entry);
@@ -927,7 +841,7 @@ extern "C" size_t lvae_resblock_gate_workspace(const lvae_conv_desc* g) { return
 
 extern "C" int lvae_resblock_gate_prepare_entry(const lvae_conv_desc* g, void* entry) {
   LVAE_REQUIRE(rb_gate_ok(g) && entry, LVAE_EINVAL, "lvae_resblock_gate_prepare_entry: needs a 64 -> 128 or 128 -> 64 1x1 descriptor and an entry buffer");
-  LVAE_REQUIRE(g->workspace && (size_t)g->workspace_bytes >= resblock_gate_ws_bytes(g, rb_split(g)) && al16r(g->workspace), LVAE_EINVAL,
+  LVAE_REQUIRE(g->workspace && (size_t)g->workspace_bytes >= resblock_gate_ws_bytes(g, rb_split(g)) && al16_or_null(g->workspace), LVAE_EINVAL,
                "lvae_resblock_gate_prepare_entry: no scratch for the pre-split gate weights");
   resblock_gate_prep_entry(g, rb_split(g), entry);
   return 0;
@@ -959,7 +873,7 @@ extern "C" int lvae_resblock_conv_prepare_entry(const lvae_conv_desc* d, void* e
   RbArgs a;
   int mi;
   LVAE_REQUIRE(rb_plan(d, a, mi), LVAE_EINVAL, "lvae_resblock_conv_prepare_entry: shape not supported (lvae_resblock_conv_rows(d) == 0)");
-  LVAE_REQUIRE(d->workspace && (size_t)d->workspace_bytes >= conv3x3_bf16_workspace(d, rb_split(d)) && al16r(d->workspace), LVAE_EINVAL,
+  LVAE_REQUIRE(d->workspace && (size_t)d->workspace_bytes >= conv3x3_bf16_workspace(d, rb_split(d)) && al16_or_null(d->workspace), LVAE_EINVAL,
                "lvae_resblock_conv_prepare_entry: no scratch for the pre-split weights");
   conv3x3_bf16_prep_entry(d, rb_split(d), entry);
   return 0;
@@ -977,13 +891,13 @@ extern "C" int lvae_resblock_conv_f32(const lvae_conv_desc* d, const lvae_rb_ext
                  "lvae_resblock_conv_f32: shape not supported (whole-image kernels: 3x3 / stride 1 / pad 1, 64 -> 64 channels, H*W a divisor of 64, "
                  "fp32 tensors; conv + gate also for lvae_resblock_conv_gate_rows(d) > 0)");
     const lvae_rb_ext& e = *ext;
-    LVAE_REQUIRE(e.out && al16r(e.out) && al16r(e.ab) && al16r(e.res) && al16r(e.gate_bias) && al16r(e.out_stats) && al16r(e.out_stats_pivot) &&
+    LVAE_REQUIRE(e.out && al16_or_null(e.out) && al16_or_null(e.ab) && al16_or_null(e.res) && al16_or_null(e.gate_bias) && al16_or_null(e.out_stats) && al16_or_null(e.out_stats_pivot) &&
                      (e.out_stats == nullptr || e.out_stats_pivot != nullptr) && d->stats_out == nullptr && d->x != nullptr && d->y != nullptr,
                  LVAE_EINVAL, "lvae_resblock_conv_f32: gate epilogue needs x, y, out (16-byte aligned tensors); statistics of y are not available with it");
     lvae_conv_desc g = lvae_conv_desc{};
     g.w = e.gate_w; g.w_sk = e.gate_w_sk; g.w_sn = e.gate_w_sn; g.precision = d->precision; g.C1 = 64; g.Cout = 128;
     g.workspace = e.gate_ws; g.workspace_bytes = e.gate_ws_bytes;
-    LVAE_REQUIRE(e.gate_ws != nullptr && al16r(e.gate_ws) && (size_t)e.gate_ws_bytes >= resblock_gate_ws_bytes(&g, 3) && (e.gate_ws_ready || e.gate_w != nullptr),
+    LVAE_REQUIRE(e.gate_ws != nullptr && al16_or_null(e.gate_ws) && (size_t)e.gate_ws_bytes >= resblock_gate_ws_bytes(&g, 3) && (e.gate_ws_ready || e.gate_w != nullptr),
                  LVAE_EWORKSPACE, "lvae_resblock_conv_f32: gate_ws missing or smaller than lvae_resblock_gate_workspace(), or not ready and no gate_w");
     if (!e.gate_ws_ready) {
       const int rc = resblock_gate_prepare_single(&g, 3, (hipStream_t)stream);
@@ -999,37 +913,37 @@ extern "C" int lvae_resblock_conv_f32(const lvae_conv_desc* d, const lvae_rb_ext
   LVAE_REQUIRE(pro >= LVAE_RB_PRO_AFFINE && pro <= LVAE_RB_PRO_GATE_BWD && (epi == LVAE_RB_EPI_PLAIN || epi == LVAE_RB_EPI_GATE), LVAE_EINVAL,
                "lvae_resblock_conv_f32: bad prologue / epilogue id");
   LVAE_REQUIRE(epi == LVAE_RB_EPI_PLAIN || pro == LVAE_RB_PRO_AFFINE, LVAE_EINVAL, "lvae_resblock_conv_f32: the gate epilogue goes with the forward prologue");
-  LVAE_REQUIRE(d->workspace != nullptr && (size_t)d->workspace_bytes >= conv3x3_bf16_workspace(d, split) && al16r(d->workspace), LVAE_EWORKSPACE,
+  LVAE_REQUIRE(d->workspace != nullptr && (size_t)d->workspace_bytes >= conv3x3_bf16_workspace(d, split) && al16_or_null(d->workspace), LVAE_EWORKSPACE,
                "lvae_resblock_conv_f32: workspace (pre-split weights) missing or smaller than lvae_resblock_conv_workspace(d)");
-  LVAE_REQUIRE(al16r(d->y) && al16r(d->bias) && al16r(d->out_scale) && al16r(d->in_scale) && al16r(d->in_shift) && al16r(d->stats_pivot) &&
-                   al16r(d->stats_x) && al16r(d->stats_out),
+  LVAE_REQUIRE(al16_or_null(d->y) && al16_or_null(d->bias) && al16_or_null(d->out_scale) && al16_or_null(d->in_scale) && al16_or_null(d->in_shift) && al16_or_null(d->stats_pivot) &&
+                   al16_or_null(d->stats_x) && al16_or_null(d->stats_out),
                LVAE_EALIGN, "lvae_resblock_conv_f32: pointers must be 16-byte aligned");
   LVAE_REQUIRE((d->in_scale == nullptr) || (d->in_shift != nullptr), LVAE_EINVAL, "lvae_resblock_conv_f32: in_scale without in_shift");
   LVAE_REQUIRE(d->stats_out == nullptr || (d->stats_pivot != nullptr && (d->stats_mode == LVAE_STATS_BN_FWD ||
                                                                            (d->stats_mode == LVAE_STATS_BN_BWD && d->stats_x != nullptr))),
                LVAE_EINVAL, "lvae_resblock_conv_f32: bad stats_pivot / stats_mode / stats_x");
   if (pro == LVAE_RB_PRO_AFFINE) {
-    LVAE_REQUIRE(d->x != nullptr && al16r(d->x), LVAE_EINVAL, "lvae_resblock_conv_f32: null or unaligned x");
+    LVAE_REQUIRE(d->x != nullptr && al16_or_null(d->x), LVAE_EINVAL, "lvae_resblock_conv_f32: null or unaligned x");
     if (d->in_fold != nullptr) {
       a.f = *d->in_fold;
-      LVAE_REQUIRE(a.f.parts != nullptr && al16r(a.f.parts) && a.f.rows > 0 && a.f.M > 0 && d->in_scale == nullptr, LVAE_EINVAL,
+      LVAE_REQUIRE(a.f.parts != nullptr && al16_or_null(a.f.parts) && a.f.rows > 0 && a.f.M > 0 && d->in_scale == nullptr, LVAE_EINVAL,
                    "lvae_resblock_conv_f32: bad in_fold (parts / rows / M, or in_scale given too)");
     }
   } else {
     LVAE_REQUIRE(d->in_fold == nullptr && d->in_scale == nullptr, LVAE_EINVAL, "lvae_resblock_conv_f32: input transform with a backward prologue");
-    LVAE_REQUIRE(al16r(e.pro_drop) && al16r(e.xt_out), LVAE_EALIGN, "lvae_resblock_conv_f32: pro_drop / xt_out must be 16-byte aligned");
+    LVAE_REQUIRE(al16_or_null(e.pro_drop) && al16_or_null(e.xt_out), LVAE_EALIGN, "lvae_resblock_conv_f32: pro_drop / xt_out must be 16-byte aligned");
   }
   if (pro == LVAE_RB_PRO_BN_APPLY) {
-    LVAE_REQUIRE(d->x && e.bwd_x && e.bwd_parts && e.bwd_coef && e.bwd_rows > 0 && e.bwd_M > 0 && al16r(d->x) && al16r(e.bwd_x) &&
-                     al16r(e.bwd_parts) && al16r(e.bwd_coef),
+    LVAE_REQUIRE(d->x && e.bwd_x && e.bwd_parts && e.bwd_coef && e.bwd_rows > 0 && e.bwd_M > 0 && al16_or_null(d->x) && al16_or_null(e.bwd_x) &&
+                     al16_or_null(e.bwd_parts) && al16_or_null(e.bwd_coef),
                  LVAE_EINVAL, "lvae_resblock_conv_f32: BatchNorm-apply prologue needs x (= dh), bwd_x, bwd_parts / rows / M and the coefficient block, 16-byte aligned");
   }
   if (pro == LVAE_RB_PRO_GATE_BWD) {
-    LVAE_REQUIRE((e.dout || e.ap_parts) && e.ab_in && al16r(e.dout) && al16r(e.ab_in) && al16r(e.dab), LVAE_EINVAL,
+    LVAE_REQUIRE((e.dout || e.ap_parts) && e.ab_in && al16_or_null(e.dout) && al16_or_null(e.ab_in) && al16_or_null(e.dab), LVAE_EINVAL,
                  "lvae_resblock_conv_f32: gate-backward prologue needs dout (or the deferred apply that produces it) and ab_in (16-byte aligned tensors)");
     if (e.ap_parts != nullptr) {
-      LVAE_REQUIRE(e.ap_rows > 0 && e.ap_M > 0 && e.ap_coef && e.ap_dh && e.ap_x && e.ap_add && e.ap_out && al16r(e.ap_parts) && al16r(e.ap_coef) &&
-                       al16r(e.ap_dh) && al16r(e.ap_x) && al16r(e.ap_add) && al16r(e.ap_out),
+      LVAE_REQUIRE(e.ap_rows > 0 && e.ap_M > 0 && e.ap_coef && e.ap_dh && e.ap_x && e.ap_add && e.ap_out && al16_or_null(e.ap_parts) && al16_or_null(e.ap_coef) &&
+                       al16_or_null(e.ap_dh) && al16_or_null(e.ap_x) && al16_or_null(e.ap_add) && al16_or_null(e.ap_out),
                    LVAE_EINVAL, "lvae_resblock_conv_f32: deferred apply needs ap_parts / ap_rows / ap_M, the coefficient block, ap_dh, ap_x, ap_add and ap_out, 16-byte aligned");
     }
   } else {
@@ -1040,7 +954,7 @@ extern "C" int lvae_resblock_conv_f32(const lvae_conv_desc* d, const lvae_rb_ext
     g.w = e.gate_w; g.w_sk = e.gate_w_sk; g.w_sn = e.gate_w_sn; g.precision = d->precision;
     g.C1 = epi == LVAE_RB_EPI_GATE ? 64 : 128; g.Cout = epi == LVAE_RB_EPI_GATE ? 128 : 64;
     g.workspace = e.gate_ws; g.workspace_bytes = e.gate_ws_bytes;
-    LVAE_REQUIRE(e.gate_ws != nullptr && al16r(e.gate_ws) && (size_t)e.gate_ws_bytes >= resblock_gate_ws_bytes(&g, split) &&
+    LVAE_REQUIRE(e.gate_ws != nullptr && al16_or_null(e.gate_ws) && (size_t)e.gate_ws_bytes >= resblock_gate_ws_bytes(&g, split) &&
                      (e.gate_ws_ready || e.gate_w != nullptr),
                  LVAE_EWORKSPACE, "lvae_resblock_conv_f32: gate_ws missing or smaller than lvae_resblock_gate_workspace(), or not ready and no gate_w");
     if (!e.gate_ws_ready) {
@@ -1049,8 +963,8 @@ extern "C" int lvae_resblock_conv_f32(const lvae_conv_desc* d, const lvae_rb_ext
     }
   }
   if (epi == LVAE_RB_EPI_GATE) {
-    LVAE_REQUIRE(e.out && al16r(e.out) && al16r(e.ab) && al16r(e.res) && al16r(e.gate_bias) && al16r(e.out_stats) &&
-                     al16r(e.out_stats_pivot) && (e.out_stats == nullptr || e.out_stats_pivot != nullptr) && d->stats_out == nullptr,
+    LVAE_REQUIRE(e.out && al16_or_null(e.out) && al16_or_null(e.ab) && al16_or_null(e.res) && al16_or_null(e.gate_bias) && al16_or_null(e.out_stats) &&
+                     al16_or_null(e.out_stats_pivot) && (e.out_stats == nullptr || e.out_stats_pivot != nullptr) && d->stats_out == nullptr,
                  LVAE_EINVAL, "lvae_resblock_conv_f32: gate epilogue needs out (16-byte aligned tensors); statistics of y are not available with it");
   }
   if (!d->workspace_ready) {
