@@ -580,6 +580,27 @@ int lvae_eval_online_f32(const float* elbo_sep, const float* ll, const float* kl
 int lvae_eval_totals_f64(const double* state, int32_t N, int32_t L, int32_t S, double* totals, void* stream);
 
 /* ------------------------------------------------------------------------------------------------------------
+ * Picture grids — torchvision's make_grid (padding 2) + save_image and boilr's img_grid_pad_value, restated from their published
+ * behaviour (evaluate.py:33-45, 95-114 and boilr's save_images / generate_and_save_reconstructions write such grids; parity unpinned).
+ * Sources are fp32 image sets with C = 1 or 3 (anything else: LVAE_EINVAL), each NCHW contiguous (`*_nhwc` = 0) or NHWC contiguous (1).
+ * N is the number of grid images. With b == NULL grid image k is a[k]; with b given N is even, k even is a[k/2] and k odd is b[k/2]
+ * (input, reconstruction, input, ...), so each source holds N/2 images.
+ * ---------------------------------------------------------------------------------------------------------- */
+/* count[0] = how many border values of all N images are < threshold, count[1] = how many are NaN (device int32[2], set here).
+ * A border value: the pixel clamped to [0, 1], summed over channels in channel order, divided by C in fp32; taken for rows 0 and H-1 in
+ * full and columns 0 and W-1 of rows 1 .. H-2 (n_b = N * (2W + 2 max(H-2, 0)) values). torch.median returns the lower middle element, so
+ * "median < t" is "count[0] >= (n_b - 1)/2 + 1 and count[1] == 0" (a NaN makes the median NaN): integer counts, reproducible. */
+int lvae_image_border_count_f32(const float* a, int32_t a_nhwc, const float* b, int32_t b_nhwc, int32_t N, int32_t C, int32_t H,
+                                int32_t W, float threshold, int32_t* count, void* stream);
+/* grid: uint8 [Hg][Wg][3], xmaps = min(nrow, N), ymaps = ceil(N / xmaps), Hg = (H+2)*ymaps + 2, Wg = (W+2)*xmaps + 2; grid_bytes must be
+ * Hg*Wg*3 (else LVAE_EINVAL). Image k at row (k / xmaps)*(H+2) + 2, column (k % xmaps)*(W+2) + 2; all other pixels, unfilled cells
+ * included, carry the padding value. One channel is replicated to three. byte = trunc(clamp(v*255 + 0.5, 0, 255)) with the product and
+ * the sum rounded separately in fp32; NaN -> 0. Padding value: with border_count (the counts above, read on the device: the host never
+ * waits for them) 1.0 when the median rule holds and 0.0 otherwise; with border_count == NULL, pad_value. */
+int lvae_image_grid_u8(const float* a, int32_t a_nhwc, const float* b, int32_t b_nhwc, int32_t N, int32_t C, int32_t H, int32_t W,
+                       int32_t nrow, const int32_t* border_count, float pad_value, uint8_t* grid, int64_t grid_bytes, void* stream);
+
+/* ------------------------------------------------------------------------------------------------------------
  * Optimiser and norms over the flat parameter arena — torch.optim.Adamax at experiment_manager.py:76-81 and the
  * L2 loop at experiment_manager.py:346-350.
  * ---------------------------------------------------------------------------------------------------------- */

@@ -8,10 +8,16 @@ the absent boilr.eval.BaseOfflineEvaluator / VAEExperimentManager.test_procedure
   * `test_pass(model, batches, S)` — the reference's test summaries (ELBO, recons, KL, per-layer KL, IW bound), folded on the device
     into double totals, on a noise stream of its own: the trainer's test / log-likelihood pass, which leaves training untouched
     (with `optimizer=` an averaging Adamax: computed from the averaged weights);
-  * `prior_samples(model, n)` and `inspect_layer_repr(model, n)` — evaluate.py:34-45, 95-114 (arrays instead of PNG grids).
+  * `prior_samples(model, n)` and `inspect_layer_repr(model, n)` — evaluate.py:34-45, 95-114, as arrays;
+  * `reconstructions(model, x)` — inputs beside what the model makes of them (boilr's generate_and_save_reconstructions, restated);
+  * `image_pass(model, nrows, x, step)` — the trainer's pictures (--ts-img-every): a grid of prior samples and a grid of input /
+    reconstruction pairs, formed on the device (images.py), on a noise stream of their own, leaving training untouched.
 
-CLI: python -m lvae_amd.evaluate --synthetic --ll --ll-samples 100 --ps  <model flags of main.py>
+CLI: python -m lvae_amd.evaluate --synthetic --ll --ll-samples 100 --ps --layer-repr --recons --img-dir DIR  <model flags of main.py>
+     --ps and --layer-repr write prior_samples.npy and layer_repr_<i>.npy; with --img-dir DIR they also write the reference's pictures
+     DIR/samples_0.png and DIR/sample_mode_layer<i>.png (grids of 12 x 12), and --recons writes DIR/reconstructions.png (72 pairs).
 """
+import os
 
 import numpy as np
 import torch
@@ -285,7 +291,7 @@ def inspect_layer_repr(model, n=8):
     """evaluate.py:95-114: for every layer i, n calls of `sample_prior(n, mode_layers=range(i), constant_layers=range(i+1, L))`
     concatenated — each call (one row of the reference's image grid) draws the layers above i once for its whole batch, samples
     layer i per image and takes the mode below, so a row shows what layer i encodes. Returns a list of L tensors (n*n, C, H, W);
-    the reference writes each as a PNG grid with nrow = n (image files are out of scope)."""
+    the reference writes each as a PNG grid with nrow = n (images.image_grid + write_png; the CLI does so under --img-dir)."""
     was_training = model.training
     model.eval()
     try:
@@ -300,9 +306,64 @@ def inspect_layer_repr(model, n=8):
         model.train(was_training)
 
 
-def main(argv=None):
-    from .experiment.experiment_manager import LVAEExperiment, build_parser
-    from .main import synthetic_batch
+@torch.no_grad()
+def reconstructions(model, x):
+    """One eval-mode forward pass of the NCHW batch x -> (x, recon), both NCHW on the device: recon is the likelihood's mean where it has
+    one and its sample otherwise (the logistic mixture has no mean), boilr's order of preference. Noise comes from `model.noise`."""
+    was_training = model.training
+    model.eval()
+    try:
+        x = x.to(next(model.parameters()).device).contiguous().float()
+        out = model(x)
+        return x, (out['out_mean'] if out['out_mean'] is not None else out['out_sample'])
+    finally:
+        model.train(was_training)
+
+
+IMAGE_NOISE_TAG = 0x1A6E5      # the picture noise stream's seed is the model's seed with these bits flipped
+IMAGE_NOISE_STRIDE = 1 << 20   # and its counter starts at step * this: the pictures of two steps never share a draw
+
+
+@torch.no_grad()
+def image_pass(model, nrows, x=None, step=0, optimizer=None):
+    """The trainer's pictures -> (sample grid, reconstruction grid or None), uint8 (Hg, Wg, 3) device tensors (images.image_grid).
+
+    The sample grid holds nrows^2 prior samples; with x (an NCHW batch) the reconstruction grid holds min(nrows^2 // 2, len(x)) input /
+    reconstruction pairs, nrows pictures per row. Eval mode, convolutions transform their own weights (_EvalWeights), eager launches; with
+    an averaging optimizer the pass runs on the averaged weights (`optimizer.swap_ema()`). Noise comes from a fresh PhiloxNoise made from
+    the model's seed and `step`, never from `model.noise` or `model.test_noise`: the pictures of step N do not depend on what ran before,
+    so a resumed run writes the same ones. On return training mode, `model.noise` and the prepared-weight table are as they were."""
+    if optimizer is not None and getattr(optimizer, 'ema_decay', 0.0) > 0.0:
+        with optimizer.swap_ema():
+            return image_pass(model, nrows, x, step)
+    from .images import image_grid
+    from .noise import PhiloxNoise
+    dev = next(model.parameters()).device
+    noise = PhiloxNoise(0)
+    noise.seed = (model.noise.seed if isinstance(model.noise, PhiloxNoise) else 0) ^ IMAGE_NOISE_TAG
+    noise.step = torch.full((1,), int(step) * IMAGE_NOISE_STRIDE, dtype=torch.int64, device=dev)
+    nrows = int(nrows)
+    train_noise, was_training = model.noise, model.training
+    model.eval()
+    model.noise = noise
+    keep = []
+    try:
+        with _EvalWeights(keep):
+            sample_grid = image_grid(model.sample_prior(nrows * nrows), nrows)
+            recon_grid = None
+            n = 0 if x is None else min(nrows * nrows // 2, int(x.shape[0]))
+            if n > 0:
+                xin, rec = reconstructions(model, x[:n])
+                recon_grid = image_grid(xin, nrows, second=rec)
+        torch.cuda.current_stream(dev).synchronize()   # (the registered scratch buffers of this pass may go now)
+    finally:
+        model.noise = train_noise
+        model.train(was_training)
+    return sample_grid, recon_grid
+
+
+def build_eval_parser():
+    from .experiment.experiment_manager import build_parser
     p = build_parser()
     p.add_argument('--ll', action='store_true', help='importance-weighted log-likelihood')
     p.add_argument('--ps', action='store_true', help='prior samples -> prior_samples.npy')
@@ -310,7 +371,27 @@ def main(argv=None):
     p.add_argument('--checkpoint', type=str, default='', help='state_dict file (reference key scheme)')
     p.add_argument('--n-test', type=int, default=1000)
     p.add_argument('--ema', action='store_true', help="evaluate the averaged weights stored in --checkpoint (its 'ema' entry)")
+    # (--img-dir DIR is a flag of build_parser: here samples_0.png with --ps, sample_mode_layer<i>.png with --layer-repr)
+    p.add_argument('--recons', action='store_true', help='inputs beside their reconstructions -> DIR/reconstructions.png (needs --img-dir)')
+    return p
+
+
+def parse_eval_args(argv=None):
+    p = build_eval_parser()
     args = p.parse_args(argv)
+    if args.recons and not args.img_dir:
+        p.error('--recons needs --img-dir DIR: the picture is written there')
+    return args
+
+
+IMG_GRID_N = 12   # the reference's evaluate.py:24
+
+
+def main(argv=None):
+    from .experiment.experiment_manager import LVAEExperiment
+    from .images import image_grid, write_png
+    from .main import synthetic_batch
+    args = parse_eval_args(argv)
     if args.ema and not args.checkpoint:
         raise SystemExit('--ema needs --checkpoint FILE: the averaged weights are read from the file')
     exp = LVAEExperiment(args=args)
@@ -324,12 +405,15 @@ def main(argv=None):
                 raise SystemExit(str(e))
         else:
             load_checkpoint(args.checkpoint, model)
-    if args.ll:
+    if args.img_dir:
+        os.makedirs(args.img_dir, exist_ok=True)
+    if args.ll or args.recons:
         gen = torch.Generator().manual_seed(args.seed)
         if args.data_npz:
             data = torch.from_numpy(np.load(args.data_npz)['data']).float()
         else:
             data = synthetic_batch(exp, args.n_test, gen)
+    if args.ll:
         bs = args.test_batch_size
         res = test_pass(model, (data[i:i + bs] for i in range(0, data.shape[0], bs)), args.loglikelihood_samples)
         if args.ema:
@@ -340,6 +424,17 @@ def main(argv=None):
     if args.layer_repr:
         for i, s in enumerate(inspect_layer_repr(model, 8)):
             np.save('layer_repr_%d.npy' % i, s.cpu().numpy())
+    if not args.img_dir:
+        return
+    # the reference's pictures, after everything above so that the arrays do not depend on --img-dir
+    if args.ps:            # evaluate.py:34-36
+        write_png(os.path.join(args.img_dir, 'samples_0.png'), image_grid(prior_samples(model, IMG_GRID_N ** 2), IMG_GRID_N))
+    if args.recons:        # evaluate.py:39-41, from the first images of the evaluation data
+        xin, rec = reconstructions(model, data[:IMG_GRID_N ** 2 // 2])
+        write_png(os.path.join(args.img_dir, 'reconstructions.png'), image_grid(xin, IMG_GRID_N, second=rec))
+    if args.layer_repr:    # evaluate.py:95-114
+        for i, s in enumerate(inspect_layer_repr(model, IMG_GRID_N)):
+            write_png(os.path.join(args.img_dir, 'sample_mode_layer%d.png' % i), image_grid(s.contiguous(), IMG_GRID_N))
 
 
 if __name__ == '__main__':

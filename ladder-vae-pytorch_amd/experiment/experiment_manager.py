@@ -7,8 +7,8 @@
   * `_make_model` (:38-74), `_make_optimizer` (:76-81, Adamax) and `forward_pass` (:322-367);
   * `train_log_str` / `test_log_str` / `get_metrics_dict` (:369-415).
 
-Out of scope: tensorboard, image grids, dataset downloads. main.py drives a minimal loop over a dataset, synthetic batches
-or an .npz file with the same log lines, test passes, log-likelihood estimates and checkpoint rotation (schedule.py).
+Out of scope: tensorboard, dataset downloads. main.py drives a minimal loop over a dataset, synthetic batches
+or an .npz file with the same log lines, test passes, log-likelihood estimates, checkpoint rotation (schedule.py) and picture grids (images.py).
 """
 import argparse
 
@@ -85,6 +85,9 @@ def build_parser():
                    help='write <dir>/model_<step>.pt every --checkpoint-every steps, keeping the newest --keep-checkpoint-max')
     p.add_argument('--synthetic-test', type=int, default=0, dest='synthetic_test', metavar='N',
                    help='with --synthetic: a fixed seeded test set of N images for the --ts-log-every / --ll-every test passes')
+    p.add_argument('--img-dir', type=str, default='', dest='img_dir', metavar='DIR',
+                   help='trainer: write DIR/sample_<step>.png and, with a test split, DIR/reconstruction_<step>.png every --ts-img-every '
+                        'steps; evaluate: also write the picture grids of --ps, --layer-repr and --recons there')
     p.add_argument('--ema-decay', type=_ema_decay, default=0.0, dest='ema_decay', metavar='D',
                    help='keep an exponential moving average of the weights inside the optimizer step (decay ramps up as min(D, (1+n)/(10+n))); '
                         'test and log-likelihood passes then use the averaged weights and checkpoints carry them. 0: off')

@@ -1137,6 +1137,58 @@ def eval_totals(state, L, S, totals):
     call('lvae_eval_totals_f64', ptr(state, (torch.float64,)), N, int(L), int(S), ptr(totals, (torch.float64,)), stream_ptr())
 
 
+def _img_src(t, name):
+    """(tensor, nhwc flag, (n, C, H, W)) of an image set given in the NCHW convention: NCHW contiguous, or the NCHW view of an NHWC
+    contiguous buffer (what the model returns). No copy, no layout change."""
+    if t.dim() != 4 or t.dtype != torch.float32:
+        raise _C.LvaeHipError("%s: need a float32 (N, C, H, W) tensor, got %s %s" % (name, t.dtype, tuple(t.shape)))
+    if t.is_contiguous():
+        return t, 0, tuple(t.shape)
+    if t.permute(0, 2, 3, 1).is_contiguous():
+        return t, 1, tuple(t.shape)
+    raise _C.LvaeHipError("%s: neither NCHW nor NHWC contiguous (strides %s)" % (name, t.stride()))
+
+
+def _img_pair(a, b):
+    a, a_nhwc, (n, Cn, H, W) = _img_src(a, 'images')
+    b_nhwc = 0
+    if b is not None:
+        b, b_nhwc, shape_b = _img_src(b, 'second')
+        if shape_b != (n, Cn, H, W):
+            raise _C.LvaeHipError("the two image sets differ in shape: %s and %s" % ((n, Cn, H, W), shape_b))
+        n *= 2
+    return a, a_nhwc, b, b_nhwc, n, Cn, H, W
+
+
+def image_border_count(a, b=None, threshold=0.2):
+    """int32 [2] on the device: how many border values of the images (of both sets) are below `threshold`, and how many are NaN."""
+    a, a_nhwc, b, b_nhwc, n, Cn, H, W = _img_pair(a, b)
+    count = torch.empty((2,), dtype=torch.int32, device=a.device)
+    call('lvae_image_border_count_f32', ptr(a), a_nhwc, ptr(b), b_nhwc, n, Cn, H, W, float(threshold), ptr(count, (torch.int32,)),
+         stream_ptr())
+    return count
+
+
+def image_grid_shape(n, nrow, H, W):
+    """(Hg, Wg) of make_grid(padding=2) for n images of H x W, nrow per row (a single image is padded like any other)."""
+    xmaps = min(int(nrow), n)
+    ymaps = -(-n // xmaps)
+    return (H + 2) * ymaps + 2, (W + 2) * xmaps + 2
+
+
+def image_grid(a, nrow, b=None, border_count=None, pad_value=0.0):
+    """uint8 (Hg, Wg, 3) grid of the images a (with b: a[0], b[0], a[1], b[1], ...), nrow per row. The padding value is decided on the
+    device from `border_count` (image_border_count) when given, else it is `pad_value`."""
+    a, a_nhwc, b, b_nhwc, n, Cn, H, W = _img_pair(a, b)
+    if n < 1 or int(nrow) < 1:
+        raise _C.LvaeHipError("image_grid needs at least one image and nrow >= 1")
+    Hg, Wg = image_grid_shape(n, nrow, H, W)
+    grid = torch.empty((Hg, Wg, 3), dtype=torch.uint8, device=a.device)
+    call('lvae_image_grid_u8', ptr(a), a_nhwc, ptr(b), b_nhwc, n, Cn, H, W, int(nrow), ptr(border_count, (torch.int32,)),
+         float(pad_value), ptr(grid, (torch.uint8,)), grid.numel(), stream_ptr())
+    return grid
+
+
 def adamax_step(p, g, exp_avg, exp_inf, mask, lr, beta1, beta2, eps, weight_decay, gscale, step_count):
     call('lvae_adamax_step_f32', ptr(p), ptr(g), ptr(exp_avg), ptr(exp_inf), ptr(mask), p.numel(), lr, beta1, beta2, eps,
          weight_decay, ptr(gscale), step_count.data_ptr(), stream_ptr())

@@ -12,8 +12,9 @@ import torch
 from . import dist as ldist
 from .checkpoint import save_checkpoint
 from .engine import TrainStep
-from .evaluate import test_pass
+from .evaluate import image_pass, test_pass
 from .experiment.experiment_manager import LVAEExperiment
+from .images import write_png
 from .schedule import TrainSchedule, checkpoint_path, checkpoints_to_delete
 
 
@@ -42,6 +43,9 @@ def test_batches(exp, loader, npz, rank, world):
     else:
         return None
     return lambda: (data[i:i + bs] for i in range(0, data.shape[0], bs))
+
+
+IMG_NROWS = 8   # pictures of --ts-img-every: 8 x 8 samples, 32 input / reconstruction pairs
 
 
 def main(argv=None):
@@ -133,6 +137,16 @@ def main(argv=None):
             if rank == 0:
                 print(exp.test_log_str(res, step, epoch), flush=True)
             t0, seen = time.time(), 0                  # the training throughput excludes test passes
+        if rank == 0 and args.img_dir and sched.images_at(step):
+            # boilr's sample_<step>.png / reconstruction_<step>.png; rank 0 alone, no collective. The reconstructions show the first test
+            # batch of this rank's shard, so without a test split there are none
+            x_img = next(iter(tests()), None) if tests is not None else None
+            sample_grid, recon_grid = image_pass(model, IMG_NROWS, x=x_img, step=step, optimizer=opt)
+            os.makedirs(args.img_dir, exist_ok=True)
+            write_png(os.path.join(args.img_dir, 'sample_%d.png' % step), sample_grid)
+            if recon_grid is not None:
+                write_png(os.path.join(args.img_dir, 'reconstruction_%d.png' % step), recon_grid)
+            t0, seen = time.time(), 0                  # nor the pictures
         if ckpt and rank == 0:
             os.makedirs(args.checkpoint_dir, exist_ok=True)
             save_checkpoint(checkpoint_path(args.checkpoint_dir, step), model, opt)
