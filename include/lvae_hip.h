@@ -601,6 +601,24 @@ int lvae_image_grid_u8(const float* a, int32_t a_nhwc, const float* b, int32_t b
                        int32_t nrow, const int32_t* border_count, float pad_value, uint8_t* grid, int64_t grid_bytes, void* stream);
 
 /* ------------------------------------------------------------------------------------------------------------
+ * Device-resident training data (csrc/batch_feed.hip; data.DeviceDataset). The reference feeds each step from a shuffling DataLoader
+ * (experiment/data.py:99-106); here the image table stays in HBM and the batch of a step is gathered by one launch inside the step.
+ * ---------------------------------------------------------------------------------------------------------- */
+#define LVAE_FEED_U8 0   /* src_kind: uint8 values, converted as (float)v / 255.0f (an IEEE division: torch's u8.float().div_(255.0)) */
+#define LVAE_FEED_F32 1  /*           float32 values, copied */
+/* out [n_rows][C][H][W] float32 (NCHW contiguous, 16-byte aligned): row r is image number
+ *   index[(cursor[0] % steps_per_epoch) * B_global + lo + r]   with an index table (device int32 [steps_per_epoch * B_global]; base = 0), or
+ *   base + r                                                   with index == NULL (cursor must be NULL too: storage order).
+ * src: N images, each CHW contiguous (src_hwc = 0) or HWC contiguous (src_hwc = 1; uint8 only); uint8 tables 4-byte, float32 tables
+ * 16-byte aligned. cursor: device int64[1], the number of COMPLETED steps, advanced with lvae_counter_advance as the last launch of a
+ * step; NULL = position 0. [lo, lo + n_rows) is this rank's part of the global batch. An index outside [0, N) is never dereferenced: its
+ * row comes out as NaN. One thread per four floats and one 16-byte store when C*H*W (for HWC also H*W) is a multiple of 4; element by
+ * element otherwise. No allocation, no synchronisation. */
+int lvae_batch_gather_f32(const void* src, int32_t src_kind, int32_t src_hwc, int32_t N, int32_t C, int32_t H, int32_t W,
+                          const int32_t* index, const int64_t* cursor, int32_t steps_per_epoch, int32_t B_global, int32_t lo,
+                          int64_t base, int32_t n_rows, float* out, void* stream);
+
+/* ------------------------------------------------------------------------------------------------------------
  * Optimiser and norms over the flat parameter arena — torch.optim.Adamax at experiment_manager.py:76-81 and the
  * L2 loop at experiment_manager.py:346-350.
  * ---------------------------------------------------------------------------------------------------------- */

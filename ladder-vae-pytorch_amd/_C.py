@@ -17,6 +17,7 @@ PREC_F32, PREC_BF16 = 0, 1
 DT_F32, DT_BF16 = 0, 1
 VARIANT_DIRECT, VARIANT_POS, VARIANT_WINO_F32, VARIANT_WINO_SIX, VARIANT_BF16_DIRECT, VARIANT_SIX_DIRECT = 0, 2, 3, 4, 5, 6
 WGRAD_VARIANT_GENERIC, WGRAD_VARIANT_IMG, WGRAD_VARIANT_BF16, WGRAD_VARIANT_WINO, WGRAD_VARIANT_DIRECT_1X1, WGRAD_VARIANT_TILE, WGRAD_VARIANT_THIN = range(7)
+FEED_U8, FEED_F32 = 0, 1
 FORM_AUTO, FORM_F32_MFMA, FORM_SIX_PRODUCT, FORM_SIX_PRODUCT_DIRECT = 0, 1, 2, 3
 
 
@@ -150,6 +151,7 @@ SIGNATURES = {
     'lvae_eval_totals_f64': (C.c_int, [_P, _I, _I, _I, _P, _P]),
     'lvae_image_border_count_f32': (C.c_int, [_P, _I, _P, _I, _I, _I, _I, _I, _F, _P, _P]),
     'lvae_image_grid_u8': (C.c_int, [_P, _I, _P, _I, _I, _I, _I, _I, _I, _P, _F, _P, _L, _P]),
+    'lvae_batch_gather_f32': (C.c_int, [_P, _I, _I, _I, _I, _I, _I, _P, _P, _I, _I, _I, _L, _I, _P, _P]),
     'lvae_iw_logmeanexp_f32': (C.c_int, [_P, _I, _I, _P, _P]),
     'lvae_adamax_step_f32': (C.c_int, [_P, _P, _P, _P, _P, _L, _F, _F, _F, _F, _F, _P, _P, _P]),
     'lvae_adamax_ema_step_f32': (C.c_int, [_P, _P, _P, _P, _P, _L, _F, _F, _F, _F, _F, _P, _P, _P, _F, _P]),

@@ -12,6 +12,9 @@ downloads (there is no network here): the same on-disk formats, the same tensors
   torchvision's crop offsets (round((218-148)/2) = 35, round((178-148)/2) = 15) and Pillow's two-pass fixed-point antialiased
   bilinear resize, bit for bit (tests/golden/celeba_resize.npz was made with Pillow itself). JPEG decoding is not on this path.
 Loaders: train shuffled with drop_last, test in order with `test_batch_size` (:99-106).
+
+`DeviceDataset` (below the loaders) keeps a whole image set in device memory instead and lets the training step gather its own batch:
+the order is a pure function of (seed, global step), so a run with real data repeats and resumes exactly.
 """
 import os
 import pickle
@@ -194,3 +197,163 @@ class DatasetLoader:
         self.data_shape = self.train.dataset[0][0].size()
         self.img_size = self.data_shape[1:]
         self.color_ch = self.data_shape[0]
+
+
+# ---------------------------------------------------------------------------------------------------------------------
+# Device-resident data: the image table in HBM, one gather launch per batch (csrc/batch_feed.hip)
+# ---------------------------------------------------------------------------------------------------------------------
+def epoch_permutation(seed, epoch, n):
+    """The order in which epoch `epoch` (0-based) visits the n images: a pure function of its arguments, identical on every rank."""
+    mix = (int(seed) * 0x9E3779B1 + int(epoch) * 0x85EBCA77 + 0x165667B1) % (1 << 63)
+    return torch.randperm(int(n), generator=torch.Generator().manual_seed(mix))
+
+
+def device_storage(x):
+    """(array, kind) a host image set is kept as on the device: float32 images whose every value is k/255 exactly (ToTensor data, 0/1
+    data) become uint8 — a quarter of the memory, and the gather's v/255 gives back the same floats bit for bit — anything else stays
+    float32, unchanged. uint8 input stays uint8. kind is 'uint8' or 'float32'."""
+    x = torch.as_tensor(x)
+    if x.dtype == torch.uint8:
+        return x.contiguous(), 'uint8'
+    x = x.float().contiguous()
+    q = (x * 255.0).round()
+    if bool(((q >= 0) & (q <= 255)).all()):
+        u = q.to(torch.uint8)
+        if torch.equal(u.float().div_(255.0), x):
+            return u, 'uint8'
+    return x, 'float32'
+
+
+class DeviceDataset:
+    """N images in device memory; the batch of global step s is rows indices(s)[lo:hi] of it, gathered by one HIP launch.
+
+    images: host uint8 (N,C,H,W), uint8 (N,H,W,C) with channels_last=True, or float32 (N,C,H,W) (stored as uint8 when `device_storage`
+    says every value survives). batch_size is GLOBAL (this rank gets dist.shard_batch(batch_size, rank, world) of it); None makes a set
+    that is only read in storage order (`batches`, a test split). steps_per_epoch = N // batch_size (drop_last, as the reference's train
+    loader); epoch e visits epoch_permutation(seed, e, N)[:steps_per_epoch * batch_size].
+
+    On the device: the image table, an int32 index table with the current epoch's order, and `cursor`, an int64[1] holding the number of
+    completed steps. A training step gathers through (index table, cursor) and advances the cursor as its last launch; before a step that
+    begins a new epoch the host replaces the index table with a copy ordered on the step's stream (`before_step`), so a captured graph
+    keeps the addresses it baked in. Host-side queries (`indices`, sizes) need no GPU; device memory is taken on first use."""
+
+    def __init__(self, images, batch_size, seed, rank=0, world=1, device=None, channels_last=False):
+        from .dist import shard_batch
+        images = torch.as_tensor(images)
+        if images.dim() != 4:
+            raise ValueError("DeviceDataset needs (N, C, H, W) images (or (N, H, W, C) with channels_last), got shape %s" % (tuple(images.shape),))
+        if channels_last and images.dtype != torch.uint8:
+            raise ValueError("channels_last storage is for uint8 images")
+        self.host, self.kind = device_storage(images)
+        self.channels_last = bool(channels_last)
+        self.N = int(images.shape[0])
+        self.chw = (images.shape[3], images.shape[1], images.shape[2]) if channels_last else tuple(images.shape[1:])
+        self.seed, self.rank, self.world, self.device = int(seed), int(rank), int(world), device
+        self.batch_size = None if batch_size is None else int(batch_size)
+        if self.batch_size is not None:
+            if self.batch_size < 1 or self.N < self.batch_size:
+                raise ValueError("%d images do not fill one batch of %d" % (self.N, self.batch_size))
+            self.lo, self.hi = shard_batch(self.batch_size, rank, world)
+            self.steps_per_epoch = self.N // self.batch_size
+        self.table = self.index = self.cursor = None
+        self._index_epoch = None        # the epoch whose order the device index table holds (or will, once the queued copy has run)
+        self._perm = (None, None)
+        self._stage, self._stage_done, self._next_stage = [None, None], [None, None], 0
+
+    # ---- host side -------------------------------------------------------------------------------------------------
+    @property
+    def nbytes(self):
+        """Bytes of device memory the image table takes."""
+        return self.host.numel() * self.host.element_size()
+
+    @property
+    def rows(self):
+        """Images per step on this rank."""
+        return self.hi - self.lo
+
+    def _order(self, epoch):
+        if self._perm[0] != epoch:
+            self._perm = (epoch, epoch_permutation(self.seed, epoch, self.N)[:self.steps_per_epoch * self.batch_size])
+        return self._perm[1]
+
+    def epoch_of(self, step):
+        """0-based epoch of the 1-based global step."""
+        return (int(step) - 1) // self.steps_per_epoch
+
+    def indices(self, step):
+        """The global batch's image numbers of global step `step` (1-based, as model.global_step counts): a host int64 tensor [batch_size]."""
+        if step < 1:
+            raise ValueError("steps count from 1")
+        pos = (int(step) - 1) % self.steps_per_epoch
+        return self._order(self.epoch_of(step))[pos * self.batch_size:(pos + 1) * self.batch_size].clone()
+
+    # ---- device side -----------------------------------------------------------------------------------------------
+    def _dev(self):
+        if self.table is None:
+            if self.device is None:
+                self.device = torch.device('cuda', torch.cuda.current_device())
+            self.table = self.host.to(self.device)
+        return self.table
+
+    def _load_index(self, epoch):
+        """Queue the order of `epoch` into the device index table on the current stream. Two pinned staging buffers alternate, and one is
+        rewritten only after the copy that last read it has finished."""
+        if self._index_epoch == epoch:
+            return
+        self._dev()
+        n = self.steps_per_epoch * self.batch_size
+        if self.index is None:
+            self.index = torch.empty(n, dtype=torch.int32, device=self.device)
+        k = self._next_stage
+        self._next_stage ^= 1
+        if self._stage[k] is None:
+            self._stage[k] = torch.empty(n, dtype=torch.int32).pin_memory()
+            self._stage_done[k] = torch.cuda.Event()
+        else:
+            self._stage_done[k].synchronize()
+        self._stage[k].copy_(self._order(epoch))
+        self.index.copy_(self._stage[k], non_blocking=True)
+        self._stage_done[k].record(torch.cuda.current_stream(self.device))
+        self._index_epoch = epoch
+
+    def attach(self, model):
+        """Start (or, after a resume, continue) feeding `model`: the cursor takes model.global_step, the completed steps."""
+        self._dev()
+        if self.cursor is None:
+            self.cursor = torch.empty(1, dtype=torch.int64, device=self.device)
+        self.cursor.fill_(int(model.global_step))
+        self._load_index(int(model.global_step) // self.steps_per_epoch)
+        return self
+
+    def before_step(self, completed_steps):
+        """Host part of a fed step, outside any graph: when the step after `completed_steps` begins an epoch, replace the index table."""
+        self._load_index(int(completed_steps) // self.steps_per_epoch)
+
+    def new_batch(self, n=None):
+        return torch.empty((self.rows if n is None else n,) + tuple(self.chw), dtype=torch.float32, device=self._dev().device)
+
+    def gather(self, out):
+        """This rank's batch at the device cursor into `out` (one launch, capturable)."""
+        from . import kernels as K
+        return K.batch_gather(self.table, self.channels_last, out, index=self.index, cursor=self.cursor,
+                              steps_per_epoch=self.steps_per_epoch, global_batch=self.batch_size, lo=self.lo)
+
+    def advance(self):
+        """The step is complete: cursor += 1 (one launch, capturable; the last of a step, so an abandoned step does not move it)."""
+        from . import kernels as K
+        K.counter_advance(self.cursor, 1)
+
+    def batch(self, step):
+        """This rank's batch of global step `step`, gathered eagerly at a host-given position (the cursor is neither read nor moved)."""
+        from . import kernels as K
+        self._load_index(self.epoch_of(step))
+        pos = (int(step) - 1) % self.steps_per_epoch
+        return K.batch_gather(self.table, self.channels_last, self.new_batch(), index=self.index[pos * self.batch_size:(pos + 1) * self.batch_size],
+                              steps_per_epoch=1, global_batch=self.batch_size, lo=self.lo)
+
+    def batches(self, n):
+        """Consecutive device batches of n images in storage order, the last one short."""
+        from . import kernels as K
+        table = self._dev()
+        for base in range(0, self.N, int(n)):
+            yield K.batch_gather(table, self.channels_last, self.new_batch(min(int(n), self.N - base)), base=base)

@@ -6,6 +6,8 @@ and is advanced by a kernel inside the graph, so every replay draws fresh noise.
 all-reduce is part of the same graph: each bucket of the (completion-ordered) gradient arena is exchanged on a side stream as
 soon as backward has left it (dist.GradAllReduce), and Adamax waits for the last one. LVAE_DDP_MODE=split keeps the exchange
 outside the graphs instead (fwd+bwd graph | eager all-reduce | Adamax graph): collectives that are not captured.
+With a `feed` (data.DeviceDataset) the step also forms its own batch: a gather from the device-resident image table is its first launch
+and the advance of the feed's cursor its last, so the replayed graph takes nothing from the host but an index table once per epoch.
 """
 import os
 import sys
@@ -54,11 +56,13 @@ def forward_pass(model, x, beta=1.0, compute_l2=True, beta_anneal=0):
 
 
 class TrainStep:
-    """step(x) -> dict of scalars (device tensors, valid until the next step)."""
+    """step(x) -> dict of scalars (device tensors, valid until the next step). With feed=DeviceDataset: step(), the batch is gathered on
+    the device at the feed's cursor (eager steps and the captured step alike: gather | forward, backward, exchange, Adamax | cursor advance)."""
 
     def __init__(self, model, optimizer, beta=1.0, use_graph=True, allreduce=None, eager_warmup=2, async_wgrad=False,
-                 wgrad_streams=1, wgrad_group_rows=16384, beta_anneal=0):
+                 wgrad_streams=1, wgrad_group_rows=16384, beta_anneal=0, feed=None):
         self.model, self.opt, self.beta = model, optimizer, beta
+        self.feed = feed
         self.beta_anneal = int(beta_anneal)   # != 0: KL warm-up on the device counter (beta is then ignored)
         dev = next(model.parameters()).device
         self.side = [torch.cuda.Stream(device=dev) for _ in range(max(1, int(wgrad_streams)))] if async_wgrad else None
@@ -89,10 +93,15 @@ class TrainStep:
                 self.overlap, self.fallback_reason = False, why
         if self.overlap:
             model.grad_tracker = allreduce   # the model's segment markers report to it during backward
+        if feed is not None:
+            feed.attach(model)               # cursor = model.global_step: a resumed run continues in the middle of its epoch
+            self.static_x = feed.new_batch()
 
     def _fwd_bwd(self, x):
         done = False
         try:
+            if self.feed is not None:
+                x = self.feed.gather(self.static_x)   # first launch of a fed step
             self.opt.zero_grad()
             K.prepared.prepare_all()  # one launch: transformed weights of every Winograd convolution seen so far
             out = forward_pass(self.model, x, self.beta, beta_anneal=self.beta_anneal)
@@ -136,11 +145,14 @@ class TrainStep:
         if self.allreduce is not None and not self.overlap:
             self.allreduce.run()
         self.opt.step()
+        if self.feed is not None:
+            self.feed.advance()   # last launch: a step abandoned before this point leaves the cursor where it was
         return out
 
     def _capture(self, x):
-        self.static_x = torch.empty_like(x)
-        self.static_x.copy_(x)
+        if self.feed is None:
+            self.static_x = torch.empty_like(x)
+            self.static_x.copy_(x)
         fused = self.allreduce is None or not self.allreduce.active or self.overlap
         torch.cuda.synchronize()
         self.graph_a = torch.cuda.CUDAGraph()
@@ -157,10 +169,14 @@ class TrainStep:
                 self.static_out = self._fwd_bwd(self.static_x)
                 if fused:
                     self.opt.step()
+                    if self.feed is not None:
+                        self.feed.advance()
             if not fused:
                 self.graph_b = torch.cuda.CUDAGraph()
                 with torch.cuda.graph(self.graph_b, pool=self.graph_a.pool(), capture_error_mode='thread_local'):
                     self.opt.step()
+                    if self.feed is not None:
+                        self.feed.advance()
         except BaseException:
             # a failed capture leaves no usable graph: drop both so that the next call captures again (or runs eagerly) from clean state
             self.graph_a = self.graph_b = None
@@ -198,9 +214,13 @@ class TrainStep:
         K.prepared.weights_written()
         return self.static_out
 
-    def __call__(self, x):
+    def __call__(self, x=None):
+        if (x is None) == (self.feed is None):
+            raise ValueError("a step takes its batch either as x or from feed=, not both and not neither")
         if self.beta_anneal:
             global_step_counter(self.model)   # (created before this step is counted: it holds the number of COMPLETED steps)
+        if self.feed is not None:
+            self.feed.before_step(self.model.global_step)   # outside the graph: a new epoch's index table, ordered before the step
         self.model.global_step += 1
         if not self.use_graph or self.eager_left > 0:
             self.eager_left -= 1
@@ -208,7 +228,7 @@ class TrainStep:
         just_captured = self.graph_a is None
         if just_captured:
             self._capture(x)  # the Python forward ran once while capturing: it already counted this step's BN forwards
-        else:
+        elif self.feed is None:
             self.static_x.copy_(x, non_blocking=True)
         if self.trace and self.graph_b is not None:
             return self._traced_split_step()
@@ -234,7 +254,7 @@ class AutoExchangeStep:
     update), reduces the times with MAX over ranks (dist.FormSelector) and continues with the faster form; the other form's graph is dropped.
     LVAE_DDP_MODE=split|overlap skips the trial. `timings_ms` / `chosen` go into bench.py's line (config.grad_exchange_ab)."""
 
-    def __init__(self, model, optimizer, flat_grads, segments, group=None, trial_steps=3, forms=None, **step_kwargs):
+    def __init__(self, model, optimizer, flat_grads, segments, group=None, trial_steps=3, forms=None, feed=None, **step_kwargs):
         from . import dist as ldist
         self.model = model
         env = os.environ.get('LVAE_DDP_MODE')
@@ -245,7 +265,7 @@ class AutoExchangeStep:
             ar = ldist.GradAllReduce(flat_grads, group=group, segments=segments, mode=f, comm=comm)
             if comm is None:
                 comm = ar.comm
-            st = TrainStep(model, optimizer, allreduce=ar, **step_kwargs)
+            st = TrainStep(model, optimizer, allreduce=ar, feed=feed, **step_kwargs)   # one feed, one cursor: every trial step is a real step
             if f == 'overlap' and not st.overlap and 'split' in forms:
                 continue   # the overlapped form is not available here (capture probe refused): it would just be a second 'split'
             self.ars[f], self.steps[f] = ar, st
@@ -274,7 +294,7 @@ class AutoExchangeStep:
     def allreduce(self):
         return self.ars[self.chosen or next(iter(self.ars))]
 
-    def __call__(self, x):
+    def __call__(self, x=None):
         if self.chosen is not None:
             return self.steps[self.chosen](x)
         import torch.distributed as tdist
@@ -285,7 +305,7 @@ class AutoExchangeStep:
         if warming:
             self._untimed[form] = self._untimed.get(form, 0) + 1
             return st(x)
-        on_gpu = x.is_cuda
+        on_gpu = x is None or x.is_cuda
         if tdist.is_initialized() and tdist.get_world_size(self.group) > 1:
             tdist.barrier(group=self.group)
         if on_gpu:

@@ -88,6 +88,10 @@ def build_parser():
     p.add_argument('--img-dir', type=str, default='', dest='img_dir', metavar='DIR',
                    help='trainer: write DIR/sample_<step>.png and, with a test split, DIR/reconstruction_<step>.png every --ts-img-every '
                         'steps; evaluate: also write the picture grids of --ps, --layer-repr and --recons there')
+    p.add_argument('--device-data', action='store_true', dest='device_data',
+                   help='keep the training set (and the test split) in device memory and gather every batch inside the step; the data '
+                        'order is then a function of --seed and the step, so runs with a data set repeat and --resume continues exactly. '
+                        'With a data set (-d) or --data-npz; not with --synthetic')
     p.add_argument('--ema-decay', type=_ema_decay, default=0.0, dest='ema_decay', metavar='D',
                    help='keep an exponential moving average of the weights inside the optimizer step (decay ramps up as min(D, (1+n)/(10+n))); '
                         'test and log-likelihood passes then use the averaged weights and checkpoints carry them. 0: off')
@@ -121,6 +125,9 @@ class LVAEExperiment:
         if len(args.z_dims) != len(args.downsample):
             raise RuntimeError("length of list of latent dimensions ({}) does not match length of list of downsampling "
                                "factors ({})".format(len(args.z_dims), len(args.downsample)))
+        if getattr(args, 'device_data', False) and args.synthetic:
+            raise SystemExit("--device-data feeds the step from a data set kept in device memory; --synthetic has none "
+                             "(use --device-data with -d DATASET or --data-npz FILE)")
         assert args.weight_decay >= 0.0
         assert 0.0 <= args.dropout <= 1.0
         if args.dropout < 1e-5:

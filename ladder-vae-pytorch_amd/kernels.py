@@ -1230,3 +1230,24 @@ def rng_fill(out, kind, lo, hi, seed, offset, stream_id):
 
 def counter_advance(counter, by=1):
     call('lvae_counter_advance', counter.data_ptr(), int(by), stream_ptr())
+
+
+def batch_gather(table, channels_last, out, index=None, cursor=None, steps_per_epoch=0, global_batch=0, lo=0, base=0):
+    """out (n, C, H, W) float32 <- n images of `table` (uint8 (N,C,H,W), uint8 (N,H,W,C) with channels_last, or float32 (N,C,H,W)).
+    With `index` (device int32 [steps_per_epoch * global_batch]) row r is image index[(cursor[0] % steps_per_epoch) * global_batch + lo + r]
+    (`cursor`: device int64[1] of completed steps, None = position 0); without it, image base + r. uint8 -> float32 as v / 255."""
+    if table.dim() != 4 or table.dtype not in (torch.uint8, torch.float32) or not table.is_contiguous():
+        raise _C.LvaeHipError("batch_gather: the image table must be a contiguous 4-d uint8 or float32 tensor")
+    N = table.shape[0]
+    Cn, H, W = (table.shape[3], table.shape[1], table.shape[2]) if channels_last else tuple(table.shape[1:])
+    n = out.shape[0]
+    if out.dtype != torch.float32 or tuple(out.shape) != (n, Cn, H, W) or not out.is_contiguous():
+        raise _C.LvaeHipError("batch_gather: out must be contiguous float32 (n, %d, %d, %d), got %s %s" % (Cn, H, W, out.dtype,
+                                                                                                          tuple(out.shape)))
+    if index is not None and index.numel() != int(steps_per_epoch) * int(global_batch):
+        raise _C.LvaeHipError("batch_gather: the index table has %d entries, an epoch %d x %d" % (index.numel(), steps_per_epoch,
+                                                                                                 global_batch))
+    call('lvae_batch_gather_f32', ptr(table), _C.FEED_U8 if table.dtype == torch.uint8 else _C.FEED_F32, int(bool(channels_last)), N, Cn,
+         H, W, ptr(index, (torch.int32,)), ptr(cursor, (torch.int64,)), int(steps_per_epoch), int(global_batch), int(lo), int(base), n,
+         ptr(out, (torch.float32,)), stream_ptr())
+    return out

@@ -11,6 +11,7 @@ import torch
 
 from . import dist as ldist
 from .checkpoint import save_checkpoint
+from .data import DeviceDataset
 from .engine import TrainStep
 from .evaluate import image_pass, test_pass
 from .experiment.experiment_manager import LVAEExperiment
@@ -29,12 +30,28 @@ def _shard(x, rank, world):
     return x[n * rank // world:n * (rank + 1) // world]
 
 
-def test_batches(exp, loader, npz, rank, world):
+def image_table(dataset):
+    """(images, channels_last) of a DatasetLoader data set as it is stored: the float NCHW tensor of a TensorDataset, or CelebA's uint8 NHWC
+    array, which --device-data keeps as it is (the per-item permute / float / div happens in the gather instead)."""
+    if hasattr(dataset, 'tensors'):
+        return dataset.tensors[0], False
+    return dataset.data, True
+
+
+def test_batches(exp, loader, npz, rank, world, on_device=False):
     """A callable returning this rank's shard of the test set as an iterable of NCHW batches, or None when there is no test split
-    (DatasetLoader.test, a 'test' key of --data-npz, or --synthetic-test N fixed seeded images)."""
+    (DatasetLoader.test, a 'test' key of --data-npz, or --synthetic-test N fixed seeded images). on_device (--device-data): the shard is
+    kept in device memory and the batches are gathered from it (data.DeviceDataset.batches)."""
     args = exp.args
     bs = args.test_batch_size
     if loader is not None and getattr(loader, 'test', None) is not None:
+        if on_device:
+            # the same images per rank as below: every test batch is split over the ranks, in batches of one rank's part of a full one
+            imgs, channels_last = image_table(loader.test.dataset)
+            mine = torch.cat([_shard(imgs[i:i + bs], rank, world) for i in range(0, imgs.shape[0], bs)])
+            per = max(1, _shard(imgs[:bs], rank, world).shape[0])
+            ds = DeviceDataset(mine, None, args.seed, device=exp.device, channels_last=channels_last)
+            return lambda: ds.batches(per)
         return lambda: (xs for xs in (_shard(b[0], rank, world) for b in loader.test) if xs.shape[0])
     if npz is not None and 'test' in npz:
         data = _shard(torch.from_numpy(npz['test']).float(), rank, world)
@@ -42,6 +59,9 @@ def test_batches(exp, loader, npz, rank, world):
         data = _shard(synthetic_batch(exp, args.synthetic_test, torch.Generator().manual_seed(args.seed + 7919)), rank, world)
     else:
         return None
+    if on_device:
+        ds = DeviceDataset(data, None, args.seed, device=exp.device)
+        return lambda: ds.batches(bs)
     return lambda: (data[i:i + bs] for i in range(0, data.shape[0], bs))
 
 
@@ -73,7 +93,14 @@ def main(argv=None):
     if args.data_npz:
         npz = np.load(args.data_npz)
         data = torch.from_numpy(npz['data']).float()
-    tests = test_batches(exp, loader, npz, rank, world)
+    tests = test_batches(exp, loader, npz, rank, world, on_device=args.device_data)
+    feed = None
+    if args.device_data:
+        if args.batch_size % world:
+            raise SystemExit('--batch-size must be divisible by the world size')
+        # the whole training set in device memory; the step gathers its own batch, in an order that is a function of (--seed, step)
+        imgs, channels_last = image_table(loader.train.dataset) if loader is not None else (data, False)
+        feed = DeviceDataset(imgs, args.batch_size, args.seed, rank=rank, world=world, device=exp.device, channels_last=channels_last)
     sched = TrainSchedule.from_args(args, tests is not None)
     if args.simple_data_dependent_init and not args.resume:
         # experiment_manager.py:61-72: the first batch_size training images (parity unpinned, see init.py)
@@ -85,7 +112,8 @@ def main(argv=None):
     ldist.broadcast_flat(arena.params)
     allreduce = ldist.GradAllReduce(arena.grads, segments=arena.segments) if world > 1 else None
     # --beta-anneal: beta is read on the device from a step counter the step advances itself, so the captured graph replays with it
-    step_fn = TrainStep(model, opt, beta=1.0, use_graph=not args.no_graph, allreduce=allreduce, beta_anneal=args.beta_anneal)
+    step_fn = TrainStep(model, opt, beta=1.0, use_graph=not args.no_graph, allreduce=allreduce, beta_anneal=args.beta_anneal,
+                        feed=feed)
     if rank == 0:
         print(exp.run_description)
         print('parameters: %d   world size: %d   per-rank batch: %d' % (sum(p.numel() for p in model.parameters()), world,
@@ -96,6 +124,9 @@ def main(argv=None):
     gen = torch.Generator().manual_seed(args.seed + 1000 * rank)
     steps = args.steps or args.max_steps
     first = model.global_step + 1                      # > 1 after --resume: the run continues where the checkpoint left it
+    if feed is not None and rank == 0:
+        print('device data: %d images, %.1f MB as %s in device memory, %d steps per epoch' % (feed.N, feed.nbytes / 1e6, feed.kind,
+                                                                                          feed.steps_per_epoch))
     if not (loader is not None or data is not None):
         for _ in range(first - 1):                     # the synthetic batches the resumed steps already consumed
             synthetic_batch(exp, per_rank, gen)
@@ -103,7 +134,11 @@ def main(argv=None):
     epoch = 0
     t0, seen = time.time(), 0
     for step in range(first, steps + 1):
-        if loader is not None:
+        if feed is not None:
+            epoch = feed.epoch_of(step)
+            if epoch >= args.max_epochs:
+                break
+        elif loader is not None:
             if batches is None:
                 batches = iter(loader.train)
             try:
@@ -122,7 +157,7 @@ def main(argv=None):
             x = data[idx[lo:hi]]
         else:
             x = synthetic_batch(exp, per_rank, gen)
-        out = step_fn(x.to(exp.device, non_blocking=True))
+        out = step_fn() if feed is not None else step_fn(x.to(exp.device, non_blocking=True))
         seen += args.batch_size
         if rank == 0 and (step % args.log_every == 0 or step == steps):
             m = exp.get_metrics_dict(out)
@@ -131,7 +166,7 @@ def main(argv=None):
             t0, seen = time.time(), 0
         n_samples, ckpt = sched.at(step)
         if n_samples:
-            if data is not None and loader is None:
+            if data is not None and loader is None and feed is None:
                 epoch = step * args.batch_size // data.shape[0]
             res = test_pass(model, tests(), n_samples, optimizer=opt)   # (--ema-decay: on the averaged weights)
             if rank == 0:
