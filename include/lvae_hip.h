@@ -578,6 +578,22 @@ int lvae_iw_online_f32(const float* elbo, float* state, int32_t N, int32_t mode,
 int lvae_eval_online_f32(const float* elbo_sep, const float* ll, const float* kl_sep, const float* kl_avg_layerwise, double* state,
                          int32_t N, int32_t L, int32_t mode, void* stream);
 int lvae_eval_totals_f64(const double* state, int32_t N, int32_t L, int32_t S, double* totals, void* stream);
+/* Training-log summaries (boilr's summarizer: the mean of every step's metrics since the last train line), kept on the device.
+ * acc: device double [2 + 6 + L], 8-byte aligned:
+ *   [0] steps folded   [1] non-finite steps   [2] sum loss   [3] sum elbo   [4] sum recons   [5] sum kl   [6] sum l2   [7] sum grad
+ *   [8 + l] sum kl_layers[l], 0 <= l < L <= 64
+ * lvae_summary_fold_f64 folds one step: loss, elbo, recons, kl, l2 are device float[1]; kl_layers device float[L] (may be NULL when L = 0);
+ * grad_norm device float[1] or NULL; gscale device float[1] or NULL (the 1/world factor lvae_adamax_step_f32 applies; needs grad_norm).
+ * Every value is widened to double exactly and added to its slot, so a window's sum is the sequential double sum of the per-step floats in
+ * step order, bit for bit, launched eagerly or replayed. The grad slot receives grad_norm[0] * gscale[0] formed in fp32 (grad_norm[0]
+ * without gscale, 0 without grad_norm). A step whose loss or grad value is not finite adds 1 to slot [1] and nothing to any other slot; a
+ * non-finite value elsewhere (a kl_layers entry, say) is added as it is and shows in that mean only. One launch of one wave: each slot
+ * belongs to one thread (thread i owns slot i, with L > 56 also slot i + 64), plain loads and stores, no LDS, no atomics.
+ * lvae_summary_take_f64: out[i] = acc[i]; acc[i] = 0 for i < n (1 <= n <= 72; out: device double [n], not acc). Stream-ordered between
+ * two steps, so it cannot race a replayed step. */
+int lvae_summary_fold_f64(const float* loss, const float* elbo, const float* recons, const float* kl, const float* l2,
+                          const float* grad_norm, const float* gscale, const float* kl_layers, int32_t L, double* acc, void* stream);
+int lvae_summary_take_f64(double* acc, int32_t n, double* out, void* stream);
 
 /* ------------------------------------------------------------------------------------------------------------
  * Picture grids — torchvision's make_grid (padding 2) + save_image and boilr's img_grid_pad_value, restated from their published

@@ -63,9 +63,10 @@ def noise_state(model):
     return {'seed': int(nz.seed), 'step': int(nz.step.item()) if nz.step is not None else 0}
 
 
-def save_checkpoint(path, model, optimizer=None):
+def save_checkpoint(path, model, optimizer=None, summary=None):
     """Weights (reference layout), global step, Adamax state and the position of the Philox noise stream, so that a resumed run continues
-    the original one bit for bit."""
+    the original one bit for bit. With a `summary` (summary.TrainSummary) also 'summary': the open log window's accumulator as a list of
+    floats, so that the run resumed in the middle of a window prints the train line of the uninterrupted one."""
     ck = {'model': state_dict_reference_layout(model), 'global_step': int(model.global_step)}
     if optimizer is not None:
         ck['optimizer'] = optimizer_state_by_name(model, optimizer)
@@ -80,13 +81,16 @@ def save_checkpoint(path, model, optimizer=None):
     tn = getattr(model, 'test_noise', None)
     if tn is not None and getattr(tn, 'step', None) is not None:
         ck['test_noise'] = {'step': int(tn.step.item())}   # where the test passes' own stream stands: resumed test lines repeat exactly
+    if summary is not None:
+        ck['summary'] = summary.state()
     torch.save(ck, path)
 
 
-def load_checkpoint(path, model, optimizer=None):
+def load_checkpoint(path, model, optimizer=None, summary=None):
     """Loads a file written by `save_checkpoint` (with the noise stream's position and the device global-step counter when it holds
     them), or a bare reference `state_dict` file. Load before a TrainStep captures its graph: the graph keeps the counters it saw.
-    An averaging optimizer gets its average from the file's 'ema'; from a file without one the average starts at the loaded weights."""
+    An averaging optimizer gets its average from the file's 'ema'; from a file without one the average starts at the loaded weights.
+    A `summary` gets the file's open log window; from a file without one it starts an empty window."""
     ck = torch.load(path, map_location='cpu')
     sd = ck['model'] if isinstance(ck, dict) and 'model' in ck else ck
     model.load_state_dict(sd)
@@ -120,6 +124,11 @@ def load_checkpoint(path, model, optimizer=None):
                 view.copy_(ck['ema'][name])
         else:
             optimizer.ema.copy_(arena.params[:arena.n_train])
+    if summary is not None:
+        if isinstance(ck, dict) and 'model' in ck and 'summary' in ck:
+            summary.load_state(ck['summary'])
+        else:
+            summary.load_state([0.0] * summary.acc.numel())
     return ck
 
 

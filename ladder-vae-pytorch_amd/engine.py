@@ -8,6 +8,8 @@ soon as backward has left it (dist.GradAllReduce), and Adamax waits for the last
 outside the graphs instead (fwd+bwd graph | eager all-reduce | Adamax graph): collectives that are not captured.
 With a `feed` (data.DeviceDataset) the step also forms its own batch: a gather from the device-resident image table is its first launch
 and the advance of the feed's cursor its last, so the replayed graph takes nothing from the host but an index table once per epoch.
+With a `summary` (summary.TrainSummary) the step also folds its own metrics and the norm of the final gradient into the log window's
+device accumulator, immediately before Adamax: two more launches, captured with the rest.
 """
 import os
 import sys
@@ -60,9 +62,11 @@ class TrainStep:
     the device at the feed's cursor (eager steps and the captured step alike: gather | forward, backward, exchange, Adamax | cursor advance)."""
 
     def __init__(self, model, optimizer, beta=1.0, use_graph=True, allreduce=None, eager_warmup=2, async_wgrad=False,
-                 wgrad_streams=1, wgrad_group_rows=16384, beta_anneal=0, feed=None):
+                 wgrad_streams=1, wgrad_group_rows=16384, beta_anneal=0, feed=None, summary=None):
         self.model, self.opt, self.beta = model, optimizer, beta
         self.feed = feed
+        self.summary = summary                # None: the step issues not one launch more
+        self._grad_norm = None
         self.beta_anneal = int(beta_anneal)   # != 0: KL warm-up on the device counter (beta is then ignored)
         dev = next(model.parameters()).device
         self.side = [torch.cuda.Stream(device=dev) for _ in range(max(1, int(wgrad_streams)))] if async_wgrad else None
@@ -140,10 +144,21 @@ class TrainStep:
             ops.set_wgrad_stream(None)
         return {k: out[k].detach() for k in ('loss', 'elbo', 'recons', 'kl', 'l2', 'kl_avg_layerwise')}
 
+    def _fold(self, out):
+        """The step's metrics and the norm of the gradient Adamax is about to apply (summed over ranks by now, scaled like Adamax scales it)
+        into the log window. Called immediately before every `self.opt.step()`; captured with it."""
+        if self.summary is None:
+            return
+        grads = self.model.arena.grads
+        if self._grad_norm is None:
+            self._grad_norm = torch.empty((1,), dtype=torch.float32, device=grads.device)
+        self.summary.fold(out, K.l2norm(grads, out=self._grad_norm), self.opt.gscale)
+
     def _eager(self, x):
         out = self._fwd_bwd(x)
         if self.allreduce is not None and not self.overlap:
             self.allreduce.run()
+        self._fold(out)
         self.opt.step()
         if self.feed is not None:
             self.feed.advance()   # last launch: a step abandoned before this point leaves the cursor where it was
@@ -168,12 +183,14 @@ class TrainStep:
             with torch.cuda.graph(self.graph_a, capture_error_mode='thread_local'):
                 self.static_out = self._fwd_bwd(self.static_x)
                 if fused:
+                    self._fold(self.static_out)
                     self.opt.step()
                     if self.feed is not None:
                         self.feed.advance()
             if not fused:
                 self.graph_b = torch.cuda.CUDAGraph()
                 with torch.cuda.graph(self.graph_b, pool=self.graph_a.pool(), capture_error_mode='thread_local'):
+                    self._fold(self.static_out)
                     self.opt.step()
                     if self.feed is not None:
                         self.feed.advance()
@@ -254,7 +271,8 @@ class AutoExchangeStep:
     update), reduces the times with MAX over ranks (dist.FormSelector) and continues with the faster form; the other form's graph is dropped.
     LVAE_DDP_MODE=split|overlap skips the trial. `timings_ms` / `chosen` go into bench.py's line (config.grad_exchange_ab)."""
 
-    def __init__(self, model, optimizer, flat_grads, segments, group=None, trial_steps=3, forms=None, feed=None, **step_kwargs):
+    def __init__(self, model, optimizer, flat_grads, segments, group=None, trial_steps=3, forms=None, feed=None, summary=None,
+                 **step_kwargs):
         from . import dist as ldist
         self.model = model
         env = os.environ.get('LVAE_DDP_MODE')
@@ -265,7 +283,8 @@ class AutoExchangeStep:
             ar = ldist.GradAllReduce(flat_grads, group=group, segments=segments, mode=f, comm=comm)
             if comm is None:
                 comm = ar.comm
-            st = TrainStep(model, optimizer, allreduce=ar, feed=feed, **step_kwargs)   # one feed, one cursor: every trial step is a real step
+            # one feed, one cursor, one summary: every trial step is a real step
+            st = TrainStep(model, optimizer, allreduce=ar, feed=feed, summary=summary, **step_kwargs)
             if f == 'overlap' and not st.overlap and 'split' in forms:
                 continue   # the overlapped form is not available here (capture probe refused): it would just be a second 'split'
             self.ars[f], self.steps[f] = ar, st

@@ -95,6 +95,11 @@ def build_parser():
     p.add_argument('--ema-decay', type=_ema_decay, default=0.0, dest='ema_decay', metavar='D',
                    help='keep an exponential moving average of the weights inside the optimizer step (decay ramps up as min(D, (1+n)/(10+n))); '
                         'test and log-likelihood passes then use the averaged weights and checkpoints carry them. 0: off')
+    p.add_argument('--window-summaries', action='store_true', dest='window_summaries',
+                   help='the train line prints the mean of every step since the previous train line, over all ranks (summed on the device '
+                        'inside the step), with the gradient norm and the number of non-finite steps, instead of the last step of rank 0')
+    p.add_argument('--history', type=str, default='', metavar='FILE',
+                   help='rank 0 appends one JSON object per printed train and test line to FILE (JSONL)')
     return p
 
 

@@ -1137,6 +1137,30 @@ def eval_totals(state, L, S, totals):
     call('lvae_eval_totals_f64', ptr(state, (torch.float64,)), N, int(L), int(S), ptr(totals, (torch.float64,)), stream_ptr())
 
 
+SUMMARY_FIXED, SUMMARY_MAX_LAYERS = 8, 64   # slots of lvae_summary_fold_f64's accumulator before the per-layer KLs; the most layers it takes
+
+
+def summary_fold(loss, elbo, recons, kl, l2, kl_layers, acc, grad_norm=None, gscale=None):
+    """acc: float64 (8 + L) += one training step's fp32 scalars (device tensors of one element; kl_layers (L,)), laid out as
+    [steps, non-finite steps, loss, elbo, recons, kl, l2, grad, kl_layer_0 ...]. grad = grad_norm * gscale (fp32), grad_norm alone, or 0.
+    A step whose loss or grad is not finite only counts in slot 1. One launch of one wave; captured steps replay it."""
+    L = acc.numel() - SUMMARY_FIXED
+    n_kl = 0 if kl_layers is None else kl_layers.numel()
+    if acc.dim() != 1 or n_kl != L or (n_kl and not kl_layers.is_contiguous()):
+        raise _C.LvaeHipError("summary_fold: the accumulator has %d slots, which is not 8 + %d contiguous per-layer KLs" % (acc.numel(), n_kl))
+    f32 = (torch.float32,)
+    call('lvae_summary_fold_f64', ptr(loss, f32), ptr(elbo, f32), ptr(recons, f32), ptr(kl, f32), ptr(l2, f32), ptr(grad_norm, f32),
+         ptr(gscale, f32), ptr(kl_layers, f32) if n_kl else None, L, ptr(acc, (torch.float64,)), stream_ptr())
+
+
+def summary_take(acc, out):
+    """out <- acc, acc <- 0 (two float64 vectors of one length): one launch, stream-ordered between two steps."""
+    if acc.numel() != out.numel():
+        raise _C.LvaeHipError("summary_take: %d slots into a buffer of %d" % (acc.numel(), out.numel()))
+    call('lvae_summary_take_f64', ptr(acc, (torch.float64,)), acc.numel(), ptr(out, (torch.float64,)), stream_ptr())
+    return out
+
+
 def _img_src(t, name):
     """(tensor, nhwc flag, (n, C, H, W)) of an image set given in the NCHW convention: NCHW contiguous, or the NCHW view of an NHWC
     contiguous buffer (what the model returns). No copy, no layout change."""

@@ -17,6 +17,7 @@ from .evaluate import image_pass, test_pass
 from .experiment.experiment_manager import LVAEExperiment
 from .images import write_png
 from .schedule import TrainSchedule, checkpoint_path, checkpoints_to_delete
+from .summary import History, TrainSummary, train_line_suffix
 
 
 def synthetic_batch(exp, batch, gen):
@@ -82,9 +83,12 @@ def main(argv=None):
         except RuntimeError as e:
             raise SystemExit("%s\n(or pass --synthetic / --data-npz FILE)" % e)
     model, opt = exp.model, exp.optimizer
+    # --window-summaries: every step folds its metrics into a device accumulator; a train line is the mean since the previous one
+    summary = TrainSummary(len(args.z_dims), exp.device) if args.window_summaries else None
     if args.resume:
         from .checkpoint import load_checkpoint
-        load_checkpoint(args.resume, model, opt)   # (weights, Adamax state and average, global step and the rank-0 noise stream's position)
+        # (weights, Adamax state and average, global step, the rank-0 noise stream's position and the open log window)
+        load_checkpoint(args.resume, model, opt, summary=summary)
     model.noise.seed ^= rank * 0x9E3779B9
     model.train()
     arena = model.pack()
@@ -113,7 +117,8 @@ def main(argv=None):
     allreduce = ldist.GradAllReduce(arena.grads, segments=arena.segments) if world > 1 else None
     # --beta-anneal: beta is read on the device from a step counter the step advances itself, so the captured graph replays with it
     step_fn = TrainStep(model, opt, beta=1.0, use_graph=not args.no_graph, allreduce=allreduce, beta_anneal=args.beta_anneal,
-                        feed=feed)
+                        feed=feed, summary=summary)
+    history = History(args.history) if args.history and rank == 0 else None
     if rank == 0:
         print(exp.run_description)
         print('parameters: %d   world size: %d   per-rank batch: %d' % (sum(p.numel() for p in model.parameters()), world,
@@ -159,10 +164,20 @@ def main(argv=None):
             x = synthetic_batch(exp, per_rank, gen)
         out = step_fn() if feed is not None else step_fn(x.to(exp.device, non_blocking=True))
         seen += args.batch_size
-        if rank == 0 and (step % args.log_every == 0 or step == steps):
+        if summary is not None and (step % args.log_every == 0 or step == steps):
+            m = summary.take()                         # a collective: every rank takes its window, rank 0 prints the mean over all
+            if rank == 0:
+                dt = time.time() - t0
+                print(exp.train_log_str(m, step) + train_line_suffix(m, summary.ranks) + '   [{:.0f} img/s]'.format(seen / dt))
+                if history is not None:
+                    history.write(step, 'train', m, steps=m['steps'], nonfinite_steps=m['nonfinite_steps'])
+            t0, seen = time.time(), 0
+        elif rank == 0 and (step % args.log_every == 0 or step == steps):
             m = exp.get_metrics_dict(out)
             dt = time.time() - t0
             print(exp.train_log_str(m, step) + '   [{:.0f} img/s]'.format(seen / dt))
+            if history is not None:
+                history.write(step, 'train', m)
             t0, seen = time.time(), 0
         n_samples, ckpt = sched.at(step)
         if n_samples:
@@ -171,6 +186,8 @@ def main(argv=None):
             res = test_pass(model, tests(), n_samples, optimizer=opt)   # (--ema-decay: on the averaged weights)
             if rank == 0:
                 print(exp.test_log_str(res, step, epoch), flush=True)
+                if history is not None:
+                    history.write(step, 'test', res, epoch=epoch)
             t0, seen = time.time(), 0                  # the training throughput excludes test passes
         if rank == 0 and args.img_dir and sched.images_at(step):
             # boilr's sample_<step>.png / reconstruction_<step>.png; rank 0 alone, no collective. The reconstructions show the first test
@@ -184,11 +201,13 @@ def main(argv=None):
             t0, seen = time.time(), 0                  # nor the pictures
         if ckpt and rank == 0:
             os.makedirs(args.checkpoint_dir, exist_ok=True)
-            save_checkpoint(checkpoint_path(args.checkpoint_dir, step), model, opt)
+            save_checkpoint(checkpoint_path(args.checkpoint_dir, step), model, opt, summary=summary)
             for name in checkpoints_to_delete(os.listdir(args.checkpoint_dir), args.keep_checkpoint_max):
                 os.remove(os.path.join(args.checkpoint_dir, name))
     if args.save_checkpoint and rank == 0:
-        save_checkpoint(args.save_checkpoint, model, opt)
+        save_checkpoint(args.save_checkpoint, model, opt, summary=summary)
+    if history is not None:
+        history.close()
     if world > 1:
         torch.distributed.barrier()
         torch.distributed.destroy_process_group()
