@@ -12,7 +12,7 @@
 #include <stdlib.h>
 
 #include "bn_stats.h"
-#include "lvae_common.h"
+#include "lvae_host.h"
 
 namespace lvae {
 
@@ -273,22 +273,10 @@ __global__ __launch_bounds__(256) void conv1x1_kernel(PwArgs a) {
 
 template <int BM, int KT, int NT, bool KC>
 static int launch_pw(const PwArgs& a, hipStream_t s) {
-  auto kern = conv1x1_kernel<BM, KT, NT, KC>;
   constexpr size_t lds_in = (size_t)(BM * (KT + 4) + (KC ? NT * (KT + 4) : KT * NT)) * sizeof(float);
   constexpr size_t lds_out = (size_t)BM * (NT + 4) * sizeof(float);
   constexpr size_t lds = lds_in > lds_out ? lds_in : lds_out;
-  static std::atomic<bool> attr_set{false};  // idempotent attribute write; the flag itself is race-free
-  if (!attr_set) {
-    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-    if (e != hipSuccess) {
-      set_error("conv1x1: hipFuncSetAttribute failed: %s", hipGetErrorString(e));
-      return (int)e;
-    }
-    attr_set = true;
-  }
-  hipLaunchKernelGGL(kern, dim3((a.M + BM - 1) / BM), dim3(256), lds, s, a);
-  LVAE_LAUNCH_CHECK("conv1x1");
-  return 0;
+  return launch_lds<conv1x1_kernel<BM, KT, NT, KC>>("conv1x1", dim3((a.M + BM - 1) / BM), dim3(256), lds, (int)lds, s, a);
 }
 
 template <int KT, int NT, bool KC>
@@ -356,22 +344,17 @@ int conv1x1_launch(const lvae_conv_desc* d, hipStream_t s) {
   return conv1x1_try_all(d, nullptr, nullptr, 0, nullptr, nullptr, nullptr, 0, s, nullptr, 0);
 }
 
-int conv1x1_try_ex(const lvae_conv_desc* d, const float* gate_res, float* gate_out, int gate_act, const float* gb_dout,
+static int conv1x1_try_ex(const lvae_conv_desc* d, const float* gate_res, float* gate_out, int gate_act, const float* gb_dout,
                    const float* gb_ab, float* gb_dab, int gb_act, hipStream_t s) {
   return conv1x1_try_all(d, gate_res, gate_out, gate_act, gb_dout, gb_ab, gb_dab, gb_act, s, nullptr, 0);
 }
 
-int conv1x1_try(const lvae_conv_desc* d, const float* gate_res, float* gate_out, int gate_act, hipStream_t s) {
+static int conv1x1_try(const lvae_conv_desc* d, const float* gate_res, float* gate_out, int gate_act, hipStream_t s) {
   return conv1x1_try_all(d, gate_res, gate_out, gate_act, nullptr, nullptr, nullptr, 0, s, nullptr, 0);
 }
 
 }  // namespace lvae
 
-namespace lvae {
-int conv_desc_check(const lvae_conv_desc* d, const char* who);
-int conv1x1_gate_fwd_wgs(const lvae_conv_desc* d);
-int conv1x1_gate_fwd_try(const lvae_conv_desc* d, const float* res, float* out, int act, hipStream_t s);
-}
 using namespace lvae;
 
 extern "C" int lvae_conv1x1_dgrad_cat_f32(const lvae_conv_desc* d, float* dx2, int32_t split, void* stream) {

@@ -25,12 +25,9 @@
 //     the same lanes), so in an fp32 kernel VALU time adds to MFMA time whichever wave issues it. The bf16 MFMAs have their own unit.
 #include "bf16_frag.h"
 #include "bn_stats.h"
-#include "lvae_common.h"
+#include "lvae_host.h"
 
 namespace lvae {
-
-void wgrad_reduce_launch(const float* slab_w, const float* slab_b, int ksplit, int ntaps, int Cin, int Cout, int64_t stap, int64_t sk,
-                         int64_t sn, float* dw, float* db, hipStream_t s);
 
 struct GbfArgs {
   const float* dout;   // [M][64]
@@ -574,7 +571,7 @@ size_t conv1x1_gate_bwd_fused_workspace(const lvae_conv_desc* d) {
   return (size_t)gbf_nwg(M) * (64 * 128 + 128) * sizeof(float);
 }
 
-int conv1x1_gate_bwd_fused(const lvae_conv_desc* d, const float* dout, const float* ab, const float* y, int act, float* dw,
+static int conv1x1_gate_bwd_fused(const lvae_conv_desc* d, const float* dout, const float* ab, const float* y, int act, float* dw,
                            int64_t dw_sk, int64_t dw_sn, float* db, void* workspace, const lvae_bn_apply* ap, hipStream_t s) {
   if (!al16_or_null(dout) || !al16_or_null(ab) || !al16_or_null(y) || !al16_or_null(d->w) || !al16_or_null(d->y) || !al16_or_null(d->out_scale) || !al16_or_null(workspace)) return -1000;
   GbfArgs a;
@@ -601,16 +598,6 @@ int conv1x1_gate_bwd_fused(const lvae_conv_desc* d, const float* dout, const flo
   a.slab_w = static_cast<float*>(workspace);
   a.slab_b = db ? a.slab_w + (size_t)nwg * 64 * 128 : nullptr;
   constexpr size_t lds = (size_t)(2 * 64 * GB_LDA + 64 * GB_LDY) * sizeof(float);
-  static std::atomic<bool> attr_set{false};  // idempotent attribute write; the flag itself is race-free
-  if (!attr_set) {
-    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(conv1x1_gate_bwd_fused_kernel),
-                                       hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-    if (e != hipSuccess) {
-      set_error("conv1x1_gate_bwd_fused: hipFuncSetAttribute failed: %s", hipGetErrorString(e));
-      return (int)e;
-    }
-    attr_set = true;
-  }
   const bool f32_mfma = d->form == LVAE_FORM_F32_MFMA;  // default for fp32: the six-product form on the bf16 MFMA
   const bool with_ap = a.ap.parts != nullptr;
   if (with_ap && (f32_mfma && d->precision != LVAE_PREC_BF16)) {
@@ -618,37 +605,31 @@ int conv1x1_gate_bwd_fused(const lvae_conv_desc* d, const float* dout, const flo
     return LVAE_EINVAL;
   }
   const bool elu = act == LVAE_ACT_ELU && (!with_ap || a.ap.act == LVAE_ACT_ELU);
-#define GBF_LAUNCH(SP, S16_, AP_, LDS_)                                                                                                   \
+  const char* name = "conv1x1_gate_bwd_fused";
+  const dim3 grid(nwg), block(512);
+  if (d->precision == LVAE_PREC_BF16) {  // bf16 operands: within the 64 KB default
+#define GBF_LAUNCH(S16_, AP_)                                                                                                             \
   do {                                                                                                                                    \
-    if (elu) hipLaunchKernelGGL((conv1x1_gate_bwd_fused_bf16_kernel<SP, S16_, AP_, true>), dim3(nwg), dim3(512), LDS_, s, a);            \
-    else hipLaunchKernelGGL((conv1x1_gate_bwd_fused_bf16_kernel<SP, S16_, AP_, false>), dim3(nwg), dim3(512), LDS_, s, a);               \
+    if (elu) hipLaunchKernelGGL((conv1x1_gate_bwd_fused_bf16_kernel<1, S16_, AP_, true>), grid, block, gbb_lds(1), s, a);                \
+    else hipLaunchKernelGGL((conv1x1_gate_bwd_fused_bf16_kernel<1, S16_, AP_, false>), grid, block, gbb_lds(1), s, a);                   \
   } while (0)
-  if (d->precision == LVAE_PREC_BF16) {
     if (with_ap) {
-      if (a.in_bf16 && a.dx_bf16) GBF_LAUNCH(1, true, true, gbb_lds(1));
-      else GBF_LAUNCH(1, false, true, gbb_lds(1));
-    } else if (a.in_bf16 && a.dx_bf16) GBF_LAUNCH(1, true, false, gbb_lds(1));
-    else GBF_LAUNCH(1, false, false, gbb_lds(1));
-  } else if (!f32_mfma) {
-    static std::atomic<bool> attr3_set{false};
-    if (!attr3_set) {
-      hipError_t e = hipSuccess;
-      const void* ks[4] = {(const void*)conv1x1_gate_bwd_fused_bf16_kernel<3, false, false, false>, (const void*)conv1x1_gate_bwd_fused_bf16_kernel<3, false, false, true>,
-                           (const void*)conv1x1_gate_bwd_fused_bf16_kernel<3, false, true, false>, (const void*)conv1x1_gate_bwd_fused_bf16_kernel<3, false, true, true>};
-      for (int i = 0; i < 4 && e == hipSuccess; ++i) e = hipFuncSetAttribute(ks[i], hipFuncAttributeMaxDynamicSharedMemorySize, (int)gbb_lds(3));
-      if (e != hipSuccess) {
-        set_error("conv1x1_gate_bwd_fused: hipFuncSetAttribute failed: %s", hipGetErrorString(e));
-        return (int)e;
-      }
-      attr3_set = true;
-    }
-    if (with_ap) GBF_LAUNCH(3, false, true, gbb_lds(3));
-    else GBF_LAUNCH(3, false, false, gbb_lds(3));
+      if (a.in_bf16 && a.dx_bf16) GBF_LAUNCH(true, true);
+      else GBF_LAUNCH(false, true);
+    } else if (a.in_bf16 && a.dx_bf16) GBF_LAUNCH(true, false);
+    else GBF_LAUNCH(false, false);
 #undef GBF_LAUNCH
+    LVAE_LAUNCH_CHECK(name);
   } else {
-    hipLaunchKernelGGL(conv1x1_gate_bwd_fused_kernel, dim3(nwg), dim3(512), lds, s, a);
+    constexpr size_t lds3 = gbb_lds(3);
+    int rc;
+    if (f32_mfma) rc = launch_lds<conv1x1_gate_bwd_fused_kernel>(name, grid, block, lds, (int)lds, s, a);
+    else if (with_ap && elu) rc = launch_lds<conv1x1_gate_bwd_fused_bf16_kernel<3, false, true, true>>(name, grid, block, lds3, (int)lds3, s, a);
+    else if (with_ap) rc = launch_lds<conv1x1_gate_bwd_fused_bf16_kernel<3, false, true, false>>(name, grid, block, lds3, (int)lds3, s, a);
+    else if (elu) rc = launch_lds<conv1x1_gate_bwd_fused_bf16_kernel<3, false, false, true>>(name, grid, block, lds3, (int)lds3, s, a);
+    else rc = launch_lds<conv1x1_gate_bwd_fused_bf16_kernel<3, false, false, false>>(name, grid, block, lds3, (int)lds3, s, a);
+    if (rc) return rc;
   }
-  LVAE_LAUNCH_CHECK("conv1x1_gate_bwd_fused");
   // slabs are [nwg][ci][co]: the gate convolution's weight element (ci, co) lives at dw[ci * dw_sk + co * dw_sn]
   wgrad_reduce_launch(a.slab_w, a.slab_b, nwg, 1, 64, 128, 0, dw_sk, dw_sn, dw, db, s);
   LVAE_LAUNCH_CHECK("conv1x1_gate_bwd_fused_reduce");

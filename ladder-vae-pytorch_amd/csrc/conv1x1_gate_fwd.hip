@@ -19,7 +19,7 @@
 
 #include "bf16_frag.h"
 #include "bn_stats.h"
-#include "lvae_common.h"
+#include "lvae_host.h"
 
 namespace lvae {
 

@@ -9,7 +9,7 @@
 // Partials go to the usual split-K slabs [workgroup][ci][co] (+ [workgroup][co] for the bias), reduced in fixed order.
 #include <stdlib.h>
 
-#include "lvae_common.h"
+#include "lvae_host.h"
 
 namespace lvae {
 
@@ -123,9 +123,6 @@ __global__ __launch_bounds__(256, 1) void conv1x1_wgrad_kernel(W1x1Args a) {
   }
 }
 
-void wgrad_reduce_launch(const float* slab_w, const float* slab_b, int ksplit, int ntaps, int Cin, int Cout, int64_t stap,
-                         int64_t sk, int64_t sn, float* dw, float* db, hipStream_t s);
-
 static bool w1x1_plan(const lvae_conv_desc* d, int& nwg, int& ppw) {
   static const bool off = tune("LVAE_DISABLE_W1X1", 0) != 0;  // A/B switch (tuning builds only)
   if (off) return false;
@@ -162,20 +159,9 @@ int conv1x1_wgrad_launch(const lvae_conv_desc* d, const float* dy, float* dw, fl
   a.slab_b = db ? a.slab_w + (size_t)nwg * 64 * d->Cout : nullptr;
   const int nb = d->Cout / 32;
   const size_t lds = ((size_t)4 * 2 * nb * 16 * 64 + 4 * nb * 32) * sizeof(float);
-  static std::atomic<bool> attr_set{false};  // idempotent attribute write; the flag itself is race-free
-  if (!attr_set) {
-    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(conv1x1_wgrad_kernel<4>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-    if (e == hipSuccess)
-      e = hipFuncSetAttribute(reinterpret_cast<const void*>(conv1x1_wgrad_kernel<2>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-    if (e != hipSuccess) {
-      set_error("conv1x1_wgrad: hipFuncSetAttribute failed: %s", hipGetErrorString(e));
-      return (int)e;
-    }
-    attr_set = true;
-  }
-  if (nb == 4) hipLaunchKernelGGL(conv1x1_wgrad_kernel<4>, dim3(nwg), dim3(256), lds, s, a);
-  else hipLaunchKernelGGL(conv1x1_wgrad_kernel<2>, dim3(nwg), dim3(256), lds, s, a);
-  LVAE_LAUNCH_CHECK("conv1x1_wgrad");
+  const int rc = nb == 4 ? launch_lds<conv1x1_wgrad_kernel<4>>("conv1x1_wgrad", dim3(nwg), dim3(256), lds, 160 * 1024, s, a)
+                         : launch_lds<conv1x1_wgrad_kernel<2>>("conv1x1_wgrad", dim3(nwg), dim3(256), lds, 160 * 1024, s, a);
+  if (rc) return rc;
   wgrad_reduce_launch(a.slab_w, a.slab_b, nwg, 1, 64, d->Cout, d->w_stap, d->w_sk, d->w_sn, dw, db, s);
   LVAE_LAUNCH_CHECK("conv2d_wgrad_reduce");
   return 0;

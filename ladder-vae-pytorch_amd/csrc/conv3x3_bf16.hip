@@ -23,7 +23,7 @@
 
 #include "bf16_frag.h"
 #include "bn_stats.h"
-#include "lvae_common.h"
+#include "lvae_host.h"
 
 namespace lvae {
 
@@ -1106,7 +1106,7 @@ static bool bf_select(const lvae_conv_desc* d, int split, BfArgs& a) {
   return bf_plan(d, split, a);
 }
 
-bool conv3x3_bf16_eligible(const lvae_conv_desc* d, int split) {
+static bool conv3x3_bf16_eligible(const lvae_conv_desc* d, int split) {
   BfArgs a;
   return bf_select(d, split, a);
 }
@@ -1143,22 +1143,10 @@ bool conv3x3_bf16_plan(const lvae_conv_desc* d, bool assume_ws, ConvPlan& p) {
 
 template <int SPLIT, int MI, bool PRE = false, bool XB = false, bool YB = false>
 static int launch_bf(BfArgs a, hipStream_t s) {
-  auto kern = conv3x3_bf16_kernel<SPLIT, MI, PRE, XB, YB>;
-  static std::atomic<bool> attr_set{false};  // idempotent attribute write; the flag itself is race-free
-  if (!attr_set) {
-    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-    if (e != hipSuccess) {
-      set_error("conv3x3_bf16: hipFuncSetAttribute failed: %s", hipGetErrorString(e));
-      return (int)e;
-    }
-    attr_set = true;
-  }
   const int img_groups = (a.d.N + a.NI - 1) / a.NI;
   a.ntn = (a.d.Cout + 63) / 64;
   a.d.in_fold = nullptr;
-  hipLaunchKernelGGL(kern, dim3(img_groups * a.tiles_h * a.ntn), dim3(256), bf_lds_bytes(SPLIT, a.halo_px, 64 * MI), s, a);
-  LVAE_LAUNCH_CHECK("conv3x3_bf16");
-  return 0;
+  return launch_lds<conv3x3_bf16_kernel<SPLIT, MI, PRE, XB, YB>>("conv3x3_bf16", dim3(img_groups * a.tiles_h * a.ntn), dim3(256), bf_lds_bytes(SPLIT, a.halo_px, 64 * MI), 160 * 1024, s, a);
 }
 
 // split = 1: bf16 operands; split = 3: fp32-equivalent six-product form. `d->workspace` holds the pre-split weights
@@ -1267,9 +1255,6 @@ size_t conv3x3_wgrad_bf16_workspace(const lvae_conv_desc* d) {
   return (size_t)(q ? q : bfwg_nwg(a)) * ((size_t)9 * d->C1 * d->Cout + d->Cout) * sizeof(float);
 }
 
-void wgrad_reduce_launch(const float* slab_w, const float* slab_b, int ksplit, int ntaps, int Cin, int Cout, int64_t stap, int64_t sk,
-                         int64_t sn, float* dw, float* db, hipStream_t s);
-
 // runs the plan of conv3x3_wgrad_bf16_workspace(d) != 0 (16-byte aligned dy and workspace: the route of lvae_conv2d_wgrad_f32 checked them)
 int conv3x3_wgrad_bf16_launch(const lvae_conv_desc* d, const float* dy, float* dw, float* db, void* workspace, hipStream_t s) {
   BfWgArgs a;
@@ -1282,21 +1267,13 @@ int conv3x3_wgrad_bf16_launch(const lvae_conv_desc* d, const float* dy, float* d
     a.slab_w = static_cast<float*>(workspace);
     a.slab_b = db ? a.slab_w + (size_t)nr * 9 * d->C1 * d->Cout : nullptr;
     const size_t qlds = (size_t)2 * (a.halo_px + 128) * BFH_LDK * 2;
-    static const hipError_t attr = [] {
-      hipError_t e = hipFuncSetAttribute((const void*)conv3x3_wgrad_bf16h_kernel<true, true>, hipFuncAttributeMaxDynamicSharedMemorySize, 159 * 1024);
-      if (e == hipSuccess) e = hipFuncSetAttribute((const void*)conv3x3_wgrad_bf16h_kernel<false, true>, hipFuncAttributeMaxDynamicSharedMemorySize, 159 * 1024);
-      if (e == hipSuccess) e = hipFuncSetAttribute((const void*)conv3x3_wgrad_bf16h_kernel<true, false>, hipFuncAttributeMaxDynamicSharedMemorySize, 159 * 1024);
-      return e;
-    }();
-    if (attr != hipSuccess) {
-      set_error("conv3x3_wgrad_bf16: hipFuncSetAttribute failed: %s", hipGetErrorString(attr));
-      return (int)attr;
-    }
+    const char* name = "conv3x3_wgrad_bf16h";
     const dim3 qgrid(2 * nr);
-    if (xb && dyb) hipLaunchKernelGGL((conv3x3_wgrad_bf16h_kernel<true, true>), qgrid, dim3(512), qlds, s, a);
-    else if (dyb) hipLaunchKernelGGL((conv3x3_wgrad_bf16h_kernel<false, true>), qgrid, dim3(512), qlds, s, a);
-    else hipLaunchKernelGGL((conv3x3_wgrad_bf16h_kernel<true, false>), qgrid, dim3(512), qlds, s, a);
-    LVAE_LAUNCH_CHECK("conv3x3_wgrad_bf16h");
+    int rc;
+    if (xb && dyb) rc = launch_lds<conv3x3_wgrad_bf16h_kernel<true, true>>(name, qgrid, dim3(512), qlds, 159 * 1024, s, a);
+    else if (dyb) rc = launch_lds<conv3x3_wgrad_bf16h_kernel<false, true>>(name, qgrid, dim3(512), qlds, 159 * 1024, s, a);
+    else rc = launch_lds<conv3x3_wgrad_bf16h_kernel<true, false>>(name, qgrid, dim3(512), qlds, 159 * 1024, s, a);
+    if (rc) return rc;
     wgrad_reduce_launch(a.slab_w, a.slab_b, nr, 9, d->C1, d->Cout, d->w_stap, d->w_sk, d->w_sn, dw, db, s);
     LVAE_LAUNCH_CHECK("conv3x3_wgrad_bf16_reduce");
     return 0;

@@ -11,11 +11,9 @@
 #include <stdlib.h>
 
 #include "bn_stats.h"
-#include "lvae_common.h"
+#include "lvae_host.h"
 
 namespace lvae {
-
-int conv_desc_check(const lvae_conv_desc* d, const char* who);
 
 struct HaloArgs {
   lvae_conv_desc d;
@@ -279,26 +277,13 @@ static bool halo_plan(int N, int H, int W, int BM, int cin_t, HaloArgs& a) {
 
 template <int BM, int CIN_T, bool B_KCONTIG>
 static int launch_halo(HaloArgs a, hipStream_t s) {
-  auto kern = conv3x3_halo_kernel<BM, CIN_T, B_KCONTIG>;
-  static std::atomic<bool> attr_set{false};  // idempotent attribute write; the flag itself is race-free
-  if (!attr_set) {
-    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                       160 * 1024);
-    if (e != hipSuccess) {
-      set_error("conv3x3_halo: hipFuncSetAttribute failed: %s", hipGetErrorString(e));
-      return (int)e;
-    }
-    attr_set = true;
-  }
   constexpr int ks = (BM == 32 && CIN_T >= 64) ? 64 : 32;
   size_t lds = ((size_t)a.halo_px * (CIN_T + 4) + 2 * 64 * (ks + 4)) * sizeof(float);
   const size_t lds_out = (size_t)(BM == 32 ? 2 : 1) * BM * 68 * sizeof(float);  // epilogue staging tile(s)
   if (lds < lds_out) lds = lds_out;
   const int img_groups = (a.d.N + a.NI - 1) / a.NI;
   a.ntn = (a.d.Cout + 63) / 64;
-  hipLaunchKernelGGL(kern, dim3(img_groups * a.tiles_h * a.ntn), dim3(256), lds, s, a);
-  LVAE_LAUNCH_CHECK("conv3x3_halo");
-  return 0;
+  return launch_lds<conv3x3_halo_kernel<BM, CIN_T, B_KCONTIG>>("conv3x3_halo", dim3(img_groups * a.tiles_h * a.ntn), dim3(256), lds, 160 * 1024, s, a);
 }
 
 // eligibility + tile plan: returns the tile size (128 / 64 / 32), 0 when the descriptor does not fit this kernel

@@ -17,7 +17,7 @@
 // operand loads are in flight, instead of a 5 us launch in a dependent chain); workgroup 0 publishes (scale, shift, mean, rstd)
 // for the backward and updates the running statistics.
 #include "bn_stats.h"
-#include "lvae_common.h"
+#include "lvae_host.h"
 
 namespace lvae {
 
@@ -285,25 +285,13 @@ bool conv3x3_pos_plan(const lvae_conv_desc* d, ConvPlan& p) {
 
 template <int CIN_T, bool KC>
 static int launch_pos(const PosArgs& a, hipStream_t s) {
-  auto kern = conv3x3_pos_kernel<CIN_T, KC>;
-  static std::atomic<bool> attr_set{false};  // idempotent attribute write; the flag itself is race-free
-  if (!attr_set) {
-    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, 157 * 1024);
-    if (e != hipSuccess) {
-      set_error("conv3x3_pos: hipFuncSetAttribute failed: %s", hipGetErrorString(e));
-      return (int)e;
-    }
-    attr_set = true;
-  }
   // taps a position can have at most: 9 unless the image is narrower / lower than 3
   const int th = a.d.H >= 3 ? 3 : a.d.H, tw = a.d.W >= 3 ? 3 : a.d.W;
   constexpr size_t asz = (size_t)32 * (CIN_T + 4), bsz = KC ? (size_t)32 * (CIN_T + 4) : (size_t)CIN_T * 32;
   size_t lds = (size_t)th * tw * (asz + bsz) * sizeof(float);
   const size_t lds_out = (size_t)4 * 32 * 36 * sizeof(float);
   if (lds < lds_out) lds = lds_out;
-  hipLaunchKernelGGL(kern, dim3(a.n_groups * a.P * a.ntn), dim3(256), lds, s, a);
-  LVAE_LAUNCH_CHECK("conv3x3_pos");
-  return 0;
+  return launch_lds<conv3x3_pos_kernel<CIN_T, KC>>("conv3x3_pos", dim3(a.n_groups * a.P * a.ntn), dim3(256), lds, 157 * 1024, s, a);
 }
 
 int conv3x3_pos_launch(const lvae_conv_desc* d, hipStream_t s) {

@@ -21,7 +21,7 @@
 //                           | MFMA   : bar; compute(i); bar for i < T;       [slabs]; bar
 #include <stdlib.h>
 
-#include "lvae_common.h"
+#include "lvae_host.h"
 
 namespace lvae {
 
@@ -45,6 +45,7 @@ __global__ __launch_bounds__(512, 2) void conv_wgrad_ws_kernel(WTileArgs a) {
 // Several independent weight gradients in one launch (blockIdx.y = problem): the low-resolution levels fill 16-64 CUs per
 // problem, and their launches are independent of everything but their own inputs.
 constexpr int kMaxGroup = 12;
+static_assert(kMaxGroup <= kMaxReduceGroup, "a group is reduced by one wgrad_reduce_grouped_launch");
 struct WTileGroup {
   WTileArgs p[kMaxGroup];
 };
@@ -118,25 +119,10 @@ size_t conv_wgrad_tile_workspace(const lvae_conv_desc* d) {
   return ((size_t)a.ksplit * ((size_t)d->KH * d->KW * a.Cin * d->Cout + d->Cout)) * sizeof(float);
 }
 
-void wgrad_reduce_launch(const float* slab_w, const float* slab_b, int ksplit, int ntaps, int Cin, int Cout, int64_t stap,
-                         int64_t sk, int64_t sn, float* dw, float* db, hipStream_t s);
-
 template <int CIN_T, int NKW>
 static int launch_ws(const WTileArgs& a, hipStream_t s) {
-  auto kern = conv_wgrad_ws_kernel<CIN_T, NKW>;
-  static std::atomic<bool> attr_set{false};  // idempotent attribute write; the flag itself is race-free
-  if (!attr_set) {
-    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-    if (e != hipSuccess) {
-      set_error("conv_wgrad_ws: hipFuncSetAttribute failed: %s", hipGetErrorString(e));
-      return (int)e;
-    }
-    attr_set = true;
-  }
   const size_t lds = (size_t)2 * a.buf_floats * sizeof(float);
-  hipLaunchKernelGGL(kern, dim3(a.ncot * a.ksplit), dim3(512), lds, s, a);
-  LVAE_LAUNCH_CHECK("conv_wgrad_ws");
-  return 0;
+  return launch_lds<conv_wgrad_ws_kernel<CIN_T, NKW>>("conv_wgrad_ws", dim3(a.ncot * a.ksplit), dim3(512), lds, 160 * 1024, s, a);
 }
 
 // runs the plan of conv_wgrad_tile_workspace(d) != 0 (16-byte aligned dy: the route of lvae_conv2d_wgrad_f32 checked it)
@@ -160,31 +146,9 @@ int conv_wgrad_tile_launch(const lvae_conv_desc* d, const float* dy, float* dw, 
   return 0;
 }
 
-struct ReduceArgs {
-  const float* slab_w;
-  const float* slab_b;
-  int ksplit, ntaps, Cin, Cout;
-  int64_t stap, sk, sn;
-  float* dw;
-  float* db;
-};
-void wgrad_reduce_grouped_launch(const ReduceArgs* r, int n, hipStream_t s);
-
 template <int CIN_T, int NKW>
 static int launch_ws_grouped(const WTileGroup& g, int n, int max_wgs, size_t lds, hipStream_t s) {
-  auto kern = conv_wgrad_ws_grouped_kernel<CIN_T, NKW>;
-  static std::atomic<bool> attr_set{false};  // idempotent attribute write; the flag itself is race-free
-  if (!attr_set) {
-    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-    if (e != hipSuccess) {
-      set_error("conv_wgrad_ws_grouped: hipFuncSetAttribute failed: %s", hipGetErrorString(e));
-      return (int)e;
-    }
-    attr_set = true;
-  }
-  hipLaunchKernelGGL(kern, dim3(max_wgs, n), dim3(512), lds, s, g);
-  LVAE_LAUNCH_CHECK("conv_wgrad_ws_grouped");
-  return 0;
+  return launch_lds<conv_wgrad_ws_grouped_kernel<CIN_T, NKW>>("conv_wgrad_ws_grouped", dim3(max_wgs, n), dim3(512), lds, 160 * 1024, s, g);
 }
 
 // kind of the tile kernel a descriptor would use (-1: not eligible): 0 <32,3>, 1 <64,3>, 2 <32,1>, 3 <64,1>, 4 <128,1>

@@ -19,7 +19,7 @@
 #include <stdlib.h>
 
 #include "bn_stats.h"
-#include "lvae_common.h"
+#include "lvae_host.h"
 
 namespace lvae {
 
@@ -210,23 +210,11 @@ size_t conv_wgrad_wino_workspace(const lvae_conv_desc* d) {
 
 template <int TPR>
 static int launch_wg_wino(const WgWinoArgs& a, hipStream_t s) {
-  auto kern = conv_wgrad_wino_kernel<TPR>;
   constexpr int W = 2 * TPR, HW2 = W + 2, TR = 16 / TPR, HP = (2 * TR + 2) * HW2;
   size_t lds = (size_t)2 * (HP * WG_XS + 64 * WG_DS) * sizeof(float);
   const size_t lds_r = (size_t)(4 * 4 * 2 * 16 * 64 + 128) * sizeof(float);
   if (lds < lds_r) lds = lds_r;
-  static std::atomic<bool> attr_set{false};  // idempotent attribute write; the flag itself is race-free
-  if (!attr_set) {
-    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-    if (e != hipSuccess) {
-      set_error("conv_wgrad_wino: hipFuncSetAttribute failed: %s", hipGetErrorString(e));
-      return (int)e;
-    }
-    attr_set = true;
-  }
-  hipLaunchKernelGGL(kern, dim3(a.nranges * a.ncog * 2), dim3(512), lds, s, a);
-  LVAE_LAUNCH_CHECK("conv_wgrad_wino");
-  return 0;
+  return launch_lds<conv_wgrad_wino_kernel<TPR>>("conv_wgrad_wino", dim3(a.nranges * a.ncog * 2), dim3(512), lds, 160 * 1024, s, a);
 }
 
 // runs the plan of conv_wgrad_wino_workspace(d) != 0 (16-byte aligned dy and workspace: the route of lvae_conv2d_wgrad_f32 checked them)
@@ -250,23 +238,11 @@ int conv_wgrad_wino_launch(const lvae_conv_desc* d, const float* dy, float* dw, 
 
 template <int TPR>
 static int launch_wg_wino_ap(const WgWinoApArgs& g, hipStream_t s) {
-  auto kern = conv_wgrad_wino_ap_kernel<TPR>;
   constexpr int W = 2 * TPR, HW2 = W + 2, TR = 16 / TPR, HP = (2 * TR + 2) * HW2;
   size_t lds = (size_t)2 * (HP * WG_XS + 64 * WG_DS) * sizeof(float);
   const size_t lds_r = (size_t)(4 * 4 * 2 * 16 * 64 + 128) * sizeof(float);
   if (lds < lds_r) lds = lds_r;
-  static std::atomic<bool> attr_set{false};  // idempotent attribute write; the flag itself is race-free
-  if (!attr_set) {
-    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-    if (e != hipSuccess) {
-      set_error("conv_wgrad_wino_ap: hipFuncSetAttribute failed: %s", hipGetErrorString(e));
-      return (int)e;
-    }
-    attr_set = true;
-  }
-  hipLaunchKernelGGL(kern, dim3(g.w.nranges * g.w.ncog * 2), dim3(512), lds, s, g);
-  LVAE_LAUNCH_CHECK("conv_wgrad_wino_ap");
-  return 0;
+  return launch_lds<conv_wgrad_wino_ap_kernel<TPR>>("conv_wgrad_wino_ap", dim3(g.w.nranges * g.w.ncog * 2), dim3(512), lds, 160 * 1024, s, g);
 }
 
 // 1 when the weight gradient of `d` can take its dY operand from a deferred BatchNorm-backward apply (lvae_conv2d_wgrad_apply_f32)
@@ -322,22 +298,13 @@ int conv_wgrad_wino_grouped(const lvae_conv_desc* const* ds, const float* const*
   size_t lds = (size_t)2 * (hp * WG_XS + 64 * WG_DS) * sizeof(float);
   const size_t lds_r = (size_t)(4 * 4 * 2 * 16 * 64 + 128) * sizeof(float);
   if (lds < lds_r) lds = lds_r;
-  const void* kern = W == 8 ? (const void*)conv_wgrad_wino_grouped_kernel<4>
-                            : (W == 16 ? (const void*)conv_wgrad_wino_grouped_kernel<8> : (const void*)conv_wgrad_wino_grouped_kernel<16>);
-  static std::atomic<bool> attr_set[3] = {};
-  const int slot = W == 8 ? 0 : (W == 16 ? 1 : 2);
-  if (!attr_set[slot]) {
-    hipError_t e = hipFuncSetAttribute(kern, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-    if (e != hipSuccess) {
-      set_error("conv_wgrad_wino_grouped: hipFuncSetAttribute failed: %s", hipGetErrorString(e));
-      return (int)e;
-    }
-    attr_set[slot] = true;
-  }
-  if (W == 8) hipLaunchKernelGGL(conv_wgrad_wino_grouped_kernel<4>, dim3(max_wgs, n), dim3(512), lds, s, g);
-  else if (W == 16) hipLaunchKernelGGL(conv_wgrad_wino_grouped_kernel<8>, dim3(max_wgs, n), dim3(512), lds, s, g);
-  else hipLaunchKernelGGL(conv_wgrad_wino_grouped_kernel<16>, dim3(max_wgs, n), dim3(512), lds, s, g);
-  LVAE_LAUNCH_CHECK("conv_wgrad_wino_grouped");
+  const char* name = "conv_wgrad_wino_grouped";
+  const dim3 grid(max_wgs, n);
+  int rc;
+  if (W == 8) rc = launch_lds<conv_wgrad_wino_grouped_kernel<4>>(name, grid, dim3(512), lds, 160 * 1024, s, g);
+  else if (W == 16) rc = launch_lds<conv_wgrad_wino_grouped_kernel<8>>(name, grid, dim3(512), lds, 160 * 1024, s, g);
+  else rc = launch_lds<conv_wgrad_wino_grouped_kernel<16>>(name, grid, dim3(512), lds, 160 * 1024, s, g);
+  if (rc) return rc;
   hipLaunchKernelGGL(conv_wgrad_wino_reduce_grouped_kernel, dim3(64 * max_ncog, n), dim3(1024), 0, s, rg);
   LVAE_LAUNCH_CHECK("conv_wgrad_wino_reduce_grouped");
   return 0;

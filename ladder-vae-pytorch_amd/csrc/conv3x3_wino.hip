@@ -24,7 +24,7 @@
 
 #include "bf16_frag.h"
 #include "bn_stats.h"
-#include "lvae_common.h"
+#include "lvae_host.h"
 
 // build-time experiment switches of the profiling builds (tools/wino_ab.sh); the defaults are the product
 #ifndef LVAE_W1_RING
@@ -1035,13 +1035,13 @@ static bool wino_split_form(const lvae_conv_desc* d) {
   return wino_tile_for(d, 128, 256, TH, NI) && !wino_narrow(d, TH, NI);
 }
 
-size_t conv3x3_wino_workspace(const lvae_conv_desc* d) {
+static size_t conv3x3_wino_workspace(const lvae_conv_desc* d) {
   const int ntn = (d->Cout + 63) / 64;
   if (wino_split_form(d)) return (size_t)16 * 4 * (2 * ntn) * 3 * 1024;  // bf16 pieces [16][4 k16][Npad/32][3][64 lanes][8]
   return (size_t)16 * ntn * 64 * wino_kpad(d) * sizeof(float);  // 16 position slabs [Kpad/8][2][Npad][4]
 }
 
-bool conv3x3_wino_eligible(const lvae_conv_desc* d) {
+static bool conv3x3_wino_eligible(const lvae_conv_desc* d) {
   static const bool off = tune("LVAE_DISABLE_WINO", 0) != 0;  // A/B switch (tuning builds only)
   if (off) return false;
   const int Cin = d->C1;
@@ -1177,20 +1177,6 @@ static int wino_launch(const lvae_conv_desc* d, const lvae_rb_ext* gate, hipStre
     a.g_pivot = gate->out_stats_pivot;
     a.g_act = gate->act;
   }
-  static std::atomic<bool> attr_set{false};  // idempotent attribute write; the flag itself is race-free
-  if (!attr_set) {
-    hipError_t e = hipFuncSetAttribute((const void*)conv3x3_wino_kernel<64, 2, 1, false>, hipFuncAttributeMaxDynamicSharedMemorySize, 80 * 1024);
-    if (e == hipSuccess) e = hipFuncSetAttribute((const void*)conv3x3_wino_kernel<64, 1, 1, false>, hipFuncAttributeMaxDynamicSharedMemorySize, 80 * 1024);
-    if (e == hipSuccess) e = hipFuncSetAttribute((const void*)conv3x3_wino_kernel<128, 2, 1, false>, hipFuncAttributeMaxDynamicSharedMemorySize, 159 * 1024);
-    if (e == hipSuccess) e = hipFuncSetAttribute((const void*)conv3x3_wino_kernel<64, 2, 1, true>, hipFuncAttributeMaxDynamicSharedMemorySize, 80 * 1024);
-    if (e == hipSuccess) e = hipFuncSetAttribute((const void*)conv3x3_wino2_kernel<false>, hipFuncAttributeMaxDynamicSharedMemorySize, 159 * 1024);
-    if (e == hipSuccess) e = hipFuncSetAttribute((const void*)conv3x3_wino2_kernel<true>, hipFuncAttributeMaxDynamicSharedMemorySize, 159 * 1024);
-    if (e != hipSuccess) {
-      set_error("conv3x3_wino: hipFuncSetAttribute failed: %s", hipGetErrorString(e));
-      return (int)e;
-    }
-    attr_set = true;
-  }
   float* U = static_cast<float*>(d->workspace);
   a.U = U;
   const int Npad = a.Npad;
@@ -1201,14 +1187,13 @@ static int wino_launch(const lvae_conv_desc* d, const lvae_rb_ext* gate, hipStre
   }
   const int img_groups = (d->N + NI - 1) / NI;
   const dim3 grid(img_groups * a.tiles_h * a.ntn);
-  if (mt == 2 && gate != nullptr) hipLaunchKernelGGL(conv3x3_wino2_kernel<true>, grid, dim3(512), lds, s, a);
-  else if (mt == 2) hipLaunchKernelGGL(conv3x3_wino2_kernel<false>, grid, dim3(512), lds, s, a);
-  else if (split) hipLaunchKernelGGL((conv3x3_wino_kernel<64, 2, 1, true>), grid, dim3(256), lds, s, a);
-  else if (narrow) hipLaunchKernelGGL((conv3x3_wino_kernel<64, 1, 1, false>), grid, dim3(256), lds, s, a);
-  else if (kpad == 64) hipLaunchKernelGGL((conv3x3_wino_kernel<64, 2, 1, false>), grid, dim3(256), lds, s, a);
-  else hipLaunchKernelGGL((conv3x3_wino_kernel<128, 2, 1, false>), grid, dim3(256), lds, s, a);
-  LVAE_LAUNCH_CHECK("conv3x3_wino");
-  return 0;
+  const char* name = "conv3x3_wino";
+  if (mt == 2 && gate != nullptr) return launch_lds<conv3x3_wino2_kernel<true>>(name, grid, dim3(512), lds, 159 * 1024, s, a);
+  if (mt == 2) return launch_lds<conv3x3_wino2_kernel<false>>(name, grid, dim3(512), lds, 159 * 1024, s, a);
+  if (split) return launch_lds<conv3x3_wino_kernel<64, 2, 1, true>>(name, grid, dim3(256), lds, 80 * 1024, s, a);
+  if (narrow) return launch_lds<conv3x3_wino_kernel<64, 1, 1, false>>(name, grid, dim3(256), lds, 80 * 1024, s, a);
+  if (kpad == 64) return launch_lds<conv3x3_wino_kernel<64, 2, 1, false>>(name, grid, dim3(256), lds, 80 * 1024, s, a);
+  return launch_lds<conv3x3_wino_kernel<128, 2, 1, false>>(name, grid, dim3(256), lds, 159 * 1024, s, a);
 }
 
 int conv3x3_wino_launch(const lvae_conv_desc* d, hipStream_t s) { return wino_launch(d, nullptr, s); }
@@ -1220,14 +1205,6 @@ int conv3x3_wino2_gate_launch(const lvae_conv_desc* d, const lvae_rb_ext* gate, 
 using namespace lvae;
 
 extern "C" size_t lvae_conv2d_prepare_entry_bytes(void) { return sizeof(WinoPrepEntry); }
-
-namespace lvae {
-int conv3x3_bf16_form(const lvae_conv_desc* d);
-size_t conv3x3_bf16_workspace(const lvae_conv_desc* d, int split);
-void conv3x3_bf16_prep_entry(const lvae_conv_desc* d, int split, void* entry);
-int conv3x3_bf16_prepare_batched(const void* entries, int n, int npad, hipStream_t s);
-bool conv3x3_pos_plan(const lvae_conv_desc* d, ConvPlan& p);
-}  // namespace lvae
 
 extern "C" int lvae_conv2d_prepare_entry(const lvae_conv_desc* d, void* entry) {
   LVAE_REQUIRE(d && entry, LVAE_EINVAL, "lvae_conv2d_prepare_entry: null pointer");

@@ -15,7 +15,7 @@
 // consecutive rows are bank-conflict free; global loads of stage s+1 are issued before the MFMAs of stage s.
 #include <stdlib.h>
 
-#include "lvae_common.h"
+#include "lvae_host.h"
 
 namespace lvae {
 
@@ -301,23 +301,10 @@ __global__ __launch_bounds__(256) void conv_igemm_kernel(ConvArgs a) {
 template <int BM, int BN, bool A_VEC, int B_MODE>
 static int launch_conv(const ConvArgs& a, hipStream_t s) {
   constexpr size_t smem = (size_t)(2 * BM * LDK + 2 * BN * LDK) * sizeof(float);
-  static std::atomic<bool> attr_set{false};  // idempotent attribute write; the flag itself is race-free
-  auto kern = conv_igemm_kernel<BM, BN, A_VEC, B_MODE>;
-  if (!attr_set) {
-    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                       (int)smem);
-    if (e != hipSuccess) {
-      set_error("conv2d: hipFuncSetAttribute failed: %s", hipGetErrorString(e));
-      return (int)e;
-    }
-    attr_set = true;
-  }
   const int ntm = (a.M + BM - 1) / BM;
   ConvArgs b = a;
   b.ntn = (a.d.Cout + BN - 1) / BN;
-  hipLaunchKernelGGL(kern, dim3(ntm * b.ntn), dim3(256), smem, s, b);
-  LVAE_LAUNCH_CHECK("conv2d");
-  return 0;
+  return launch_lds<conv_igemm_kernel<BM, BN, A_VEC, B_MODE>>("conv2d", dim3(ntm * b.ntn), dim3(256), smem, (int)smem, s, b);
 }
 
 template <bool A_VEC, int B_MODE>
@@ -353,20 +340,6 @@ int conv_desc_check(const lvae_conv_desc* d, const char* who) {
   }
   return 0;
 }
-
-bool conv3x3_pos_plan(const lvae_conv_desc* d, ConvPlan& p);
-int conv3x3_pos_launch(const lvae_conv_desc* d, hipStream_t s);
-bool conv3x3_bf16_plan(const lvae_conv_desc* d, bool assume_ws, ConvPlan& p);
-int conv3x3_bf16_launch(const lvae_conv_desc* d, const ConvPlan& p, hipStream_t s);
-bool conv3x3_wino_plan(const lvae_conv_desc* d, bool assume_ws, ConvPlan& p);
-int conv3x3_wino_launch(const lvae_conv_desc* d, hipStream_t s);
-bool conv3x3_halo_plan(const lvae_conv_desc* d, ConvPlan& p);
-int conv3x3_halo_launch(const lvae_conv_desc* d, hipStream_t s);
-bool conv1x1_plan(const lvae_conv_desc* d);
-int conv1x1_launch(const lvae_conv_desc* d, hipStream_t s);
-int conv1x1_gate_fwd_wgs(const lvae_conv_desc* d);
-size_t conv3x3_wgrad_bf16_workspace(const lvae_conv_desc* d);
-size_t conv1x1_gate_bwd_fused_workspace(const lvae_conv_desc* d);
 
 static bool aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
 

@@ -12,11 +12,9 @@
 #include <algorithm>
 #include <vector>
 
-#include "lvae_common.h"
+#include "lvae_host.h"
 
 namespace lvae {
-
-int conv_desc_check(const lvae_conv_desc* d, const char* who);
 
 constexpr int KP = 32;   // pixels per stage
 constexpr int CT = 64;   // channel tile (both ci and co)
@@ -310,15 +308,6 @@ void wgrad_reduce_launch(const float* slab_w, const float* slab_b, int ksplit, i
                        Cout, stap, sk, sn, dw, db);
 }
 
-struct ReduceArgs {
-  const float* slab_w;
-  const float* slab_b;
-  int ksplit, ntaps, Cin, Cout;
-  int64_t stap, sk, sn;
-  float* dw;
-  float* db;
-};
-constexpr int kMaxReduceGroup = 12;
 struct ReduceGroup {
   ReduceArgs p[kMaxReduceGroup];
 };
@@ -383,24 +372,6 @@ void wgrad_reduce_grouped_launch(const ReduceArgs* r, int n, hipStream_t s) {
   for (int i = n; i < kMaxReduceGroup; ++i) g.p[i] = g.p[0];
   hipLaunchKernelGGL(wgrad_reduce_grouped_kernel, dim3((max_tot / 4 + 15) / 16, n), dim3(256), 0, s, g);
 }
-
-size_t conv_wgrad_wino_workspace(const lvae_conv_desc* d);
-// whole-image tiles of the <= 8x8 levels on the bf16 matrix pipe (conv_wgrad_img.hip): up to 32 gradients per launch
-size_t conv_wgrad_img_workspace(const lvae_conv_desc* d);
-int conv_wgrad_img_kind(const lvae_conv_desc* d);
-int conv_wgrad_img_grouped(const lvae_conv_desc* const* ds, const float* const* dy, float* const* dw, float* const* db,
-                           void* const* workspace, int n, int kind, hipStream_t s);
-int conv_wgrad_img_launch(const lvae_conv_desc* d, const float* dy, float* dw, float* db, void* workspace, hipStream_t s);
-size_t conv3x3_wgrad_bf16_workspace(const lvae_conv_desc* d);
-int conv3x3_wgrad_bf16_launch(const lvae_conv_desc* d, const float* dy, float* dw, float* db, void* workspace, hipStream_t s);
-int conv_wgrad_wino_grouped(const lvae_conv_desc* const* ds, const float* const* dy, float* const* dw, float* const* db,
-                            void* const* workspace, int n, hipStream_t s);
-int conv_wgrad_tile_kind(const lvae_conv_desc* d);
-int conv_wgrad_tile_grouped(const lvae_conv_desc* const* ds, const float* const* dy, float* const* dw, float* const* db,
-                            void* const* workspace, int n, int kind, hipStream_t s);
-int conv_wgrad_wino_launch(const lvae_conv_desc* d, const float* dy, float* dw, float* db, void* workspace, hipStream_t s);
-bool conv_wgrad_wino_apply_ok(const lvae_conv_desc* d);
-int conv_wgrad_wino_apply_launch(const lvae_conv_desc* d, const lvae_bn_apply* ap, float* dw, float* db, void* workspace, hipStream_t s);
 
 // ---------------------------------------------------------------------------------------------------------
 // Weight gradient of the stem convolutions (5x5 stride 2 on the 1- or 3-channel image): the reduction dimension of the
@@ -477,11 +448,6 @@ static size_t thin_wgrad_workspace(const lvae_conv_desc* d) {
   if (lds > 160 * 1024) return 0;
   return (size_t)d->N * ((size_t)K * d->Cout + d->Cout) * sizeof(float);
 }
-
-size_t conv1x1_wgrad_workspace(const lvae_conv_desc* d);
-int conv1x1_wgrad_launch(const lvae_conv_desc* d, const float* dy, float* dw, float* db, void* workspace, hipStream_t s);
-size_t conv_wgrad_tile_workspace(const lvae_conv_desc* d);
-int conv_wgrad_tile_launch(const lvae_conv_desc* d, const float* dy, float* dw, float* db, void* workspace, hipStream_t s);
 
 static void wgrad_plan(const lvae_conv_desc* d, int& ksplit, int& px_per_split, int& ncit, int& ncot) {
   const int Cin = d->C1 + d->C2, M = d->N * d->OH * d->OW, ntaps = d->KH * d->KW;
@@ -568,14 +534,8 @@ extern "C" int lvae_conv2d_wgrad_f32(const lvae_conv_desc* d, const float* dy, f
     ta.slab_w = static_cast<float*>(workspace);
     ta.slab_b = db ? ta.slab_w + (size_t)d->N * ta.K * d->Cout : nullptr;
     const size_t lds = ((size_t)(ta.PH * ta.PW * d->C1 + 3) / 4 * 4 + (size_t)d->OH * d->OW * 64) * sizeof(float);
-    static std::atomic<bool> attr_set{false};  // idempotent attribute write; the flag itself is race-free
-    if (!attr_set) {
-      hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(conv_wgrad_thin_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-      LVAE_REQUIRE(e == hipSuccess, (int)e, "conv_wgrad_thin: hipFuncSetAttribute failed: %s", hipGetErrorString(e));
-      attr_set = true;
-    }
-    hipLaunchKernelGGL(conv_wgrad_thin_kernel, dim3(d->N), dim3(256), lds, s, ta);
-    LVAE_LAUNCH_CHECK("conv_wgrad_thin");
+    rc = launch_lds<conv_wgrad_thin_kernel>("conv_wgrad_thin", dim3(d->N), dim3(256), lds, 160 * 1024, s, ta);
+    if (rc) return rc;
     wgrad_reduce_launch(ta.slab_w, ta.slab_b, d->N, d->KH * d->KW, d->C1, d->Cout, d->w_stap, d->w_sk, d->w_sn, dw, db, s);
     LVAE_LAUNCH_CHECK("conv2d_wgrad_reduce");
     return 0;

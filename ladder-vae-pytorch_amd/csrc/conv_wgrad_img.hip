@@ -27,7 +27,7 @@
 #include <stdlib.h>
 
 #include "bf16_frag.h"
-#include "lvae_common.h"
+#include "lvae_host.h"
 
 namespace lvae {
 
@@ -289,31 +289,9 @@ int conv_wgrad_img_kind(const lvae_conv_desc* d) {
   return wgi_plan(d, a);
 }
 
-struct ReduceArgs {
-  const float* slab_w;
-  const float* slab_b;
-  int ksplit, ntaps, Cin, Cout;
-  int64_t stap, sk, sn;
-  float* dw;
-  float* db;
-};
-void wgrad_reduce_grouped_launch(const ReduceArgs* r, int n, hipStream_t s);
-
 template <int KIND, int SPLIT, int XV>
 static int wgi_launch(const WgImgGroup& g, int n, int max_wgs, size_t lds, hipStream_t s) {
-  auto kern = wgrad_img_kernel<KIND, SPLIT, XV>;
-  static std::atomic<bool> attr_set{false};  // idempotent attribute write; the flag itself is race-free
-  if (!attr_set) {
-    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-    if (e != hipSuccess) {
-      set_error("conv_wgrad_img: hipFuncSetAttribute failed: %s", hipGetErrorString(e));
-      return (int)e;
-    }
-    attr_set = true;
-  }
-  hipLaunchKernelGGL(kern, dim3(max_wgs, n), dim3(512), lds, s, g);
-  LVAE_LAUNCH_CHECK("conv_wgrad_img");
-  return 0;
+  return launch_lds<wgrad_img_kernel<KIND, SPLIT, XV>>("conv_wgrad_img", dim3(max_wgs, n), dim3(512), lds, 160 * 1024, s, g);
 }
 
 template <int KIND, int SPLIT>
@@ -359,8 +337,8 @@ int conv_wgrad_img_grouped(const lvae_conv_desc* const* ds, const float* const* 
   if (kind & 1) rc = split == 1 ? wgi_launch_xv<1, 1>(g, n, max_wgs, lds, xv, s) : wgi_launch_xv<1, 3>(g, n, max_wgs, lds, xv, s);
   else rc = split == 1 ? wgi_launch_xv<0, 1>(g, n, max_wgs, lds, xv, s) : wgi_launch_xv<0, 3>(g, n, max_wgs, lds, xv, s);
   if (rc) return rc;
-  for (int i0 = 0; i0 < n; i0 += 12) {
-    wgrad_reduce_grouped_launch(r + i0, n - i0 < 12 ? n - i0 : 12, s);
+  for (int i0 = 0; i0 < n; i0 += kMaxReduceGroup) {
+    wgrad_reduce_grouped_launch(r + i0, n - i0 < kMaxReduceGroup ? n - i0 : kMaxReduceGroup, s);
     LVAE_LAUNCH_CHECK("conv_wgrad_img_reduce");
   }
   return 0;

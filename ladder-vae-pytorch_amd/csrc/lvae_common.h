@@ -219,14 +219,4 @@ inline int grid_for(int64_t work_items, int per_block, int cap = 256 * 8) {
   return (int)g;
 }
 
-// One forward / dgrad kernel family's accepted choice for a convolution descriptor. A family's *_plan() fills it and returns false
-// when the family does not take the descriptor (every condition its launch depends on: buffer alignment, workspace, tile, LDS);
-// its *_launch() runs exactly that choice and can no longer decline. The route of lvae_conv2d_* (conv_igemm.hip) walks the plans once.
-struct ConvPlan {
-  int32_t variant = LVAE_VARIANT_DIRECT;  // LVAE_VARIANT_*
-  int32_t rows = 0;                       // rows of statistics partials the launch writes (0: no statistics epilogue)
-  bool folds = false;                     // folds the BatchNorm finalize of its input (lvae_bn_fold)
-  size_t workspace = 0;                   // bytes of d->workspace the launch reads (pre-transformed weights)
-};
-
 }  // namespace lvae

@@ -27,7 +27,7 @@
 
 #include "bf16_frag.h"
 #include "bn_stats.h"
-#include "lvae_common.h"
+#include "lvae_host.h"
 
 namespace lvae {
 
@@ -714,15 +714,6 @@ __global__ __launch_bounds__(256) void rb_conv_kernel(RbArgs a) {
 // host side
 // ---------------------------------------------------------------------------------------------------------------------------
 
-size_t conv3x3_bf16_workspace(const lvae_conv_desc* d, int split);
-void conv3x3_bf16_prep_entry(const lvae_conv_desc* d, int split, void* entry);
-int conv3x3_bf16_prepare_single(const lvae_conv_desc* d, int split, hipStream_t s);
-size_t resblock_gate_ws_bytes(const lvae_conv_desc* d, int planes);
-void resblock_gate_prep_entry(const lvae_conv_desc* d, int planes, void* entry);
-int resblock_gate_prepare_single(const lvae_conv_desc* d, int planes, hipStream_t s);
-int conv3x3_wino2_gate_rows(const lvae_conv_desc* d);
-int conv3x3_wino2_gate_launch(const lvae_conv_desc* d, const lvae_rb_ext* gate, hipStream_t s);
-
 // the 1x1 gate convolution in the direction it is used: 64 -> 128 (forward) or 128 -> 64 (backward)
 static bool rb_gate_ok(const lvae_conv_desc* g) {
   return g != nullptr && g->w != nullptr && ((g->C1 == 64 && g->Cout == 128) || (g->C1 == 128 && g->Cout == 64));
@@ -790,19 +781,7 @@ static bool rb_plan(const lvae_conv_desc* d, RbArgs& a, int& mi) {
 
 template <int SPLIT, int MI, int PRO, int EPI, bool ELU, bool AP = false>
 static int rb_launch(const RbArgs& a, hipStream_t s) {
-  auto kern = rb_conv_kernel<SPLIT, MI, PRO, EPI, ELU, AP>;
-  static std::atomic<bool> attr_set{false};  // idempotent attribute write; the flag itself is race-free
-  if (!attr_set) {
-    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-    if (e != hipSuccess) {
-      set_error("resblock_conv: hipFuncSetAttribute failed: %s", hipGetErrorString(e));
-      return (int)e;
-    }
-    attr_set = true;
-  }
-  hipLaunchKernelGGL(kern, dim3(a.nwg), dim3(256), rb_lds_bytes(SPLIT, MI, a.halo_px, PRO, EPI), s, a);
-  LVAE_LAUNCH_CHECK("resblock_conv");
-  return 0;
+  return launch_lds<rb_conv_kernel<SPLIT, MI, PRO, EPI, ELU, AP>>("resblock_conv", dim3(a.nwg), dim3(256), rb_lds_bytes(SPLIT, MI, a.halo_px, PRO, EPI), 160 * 1024, s, a);
 }
 
 // every activation id this launch will look at is ELU (ids of features the launch does not use are ignored)
