@@ -578,6 +578,22 @@ int lvae_iw_online_f32(const float* elbo, float* state, int32_t N, int32_t mode,
 int lvae_eval_online_f32(const float* elbo_sep, const float* ll, const float* kl_sep, const float* kl_avg_layerwise, double* state,
                          int32_t N, int32_t L, int32_t mode, void* stream);
 int lvae_eval_totals_f64(const double* state, int32_t N, int32_t L, int32_t S, double* totals, void* stream);
+/* Latent usage of a test pass: per latent unit (one (pixel, channel) position of a stochastic layer, U = HW * Z of them, in NHWC order
+ * u = pixel * Z + channel) the sums over images of the posterior mean, of its square and of the analytical KL(q || p).
+ * lvae_latent_stats_fold_f32 adds one batch to sums, device double [3][U] = sum mu_q, sum mu_q^2, sum KL. p and q are the fp32
+ * (mu | logvar) tensors lvae_normal_stochastic_fwd_f32 reads: q [N][HW][2Z], p the same or, with p_bcast, [1][HW][2Z] read for every image.
+ * The KL of an element is the fp32 expression that kernel sums into kl_spatial (analytical, whatever analytical_kl is); all sums are
+ * double. Two launches: partial sums per batch slice into workspace (>= lvae_latent_stats_workspace(N, HW, Z) bytes, 8-byte aligned),
+ * then the slices in slice order onto sums; no atomics, so the same inputs give the same bits, launched eagerly or replayed. Null
+ * pointers, N, HW or Z <= 0 or a workspace that is too small: LVAE_EINVAL, nothing launched.
+ * lvae_latent_stats_finalize_f64 (one workgroup, fixed order): unit_out, device double [3][U] = per unit the mean KL, the mean of mu_q and
+ * its population variance sum mu^2 / n - (sum mu / n)^2 clamped at 0; layer_out, device double [4] = units with KL > kl_threshold, units
+ * with variance > var_threshold, U, sum over units of the mean KL. n_images <= 0: LVAE_EINVAL. */
+size_t lvae_latent_stats_workspace(int32_t N, int32_t HW, int32_t Z);
+int lvae_latent_stats_fold_f32(const float* p, int32_t p_bcast, const float* q, int32_t N, int32_t HW, int32_t Z, double* sums,
+                               void* workspace, size_t workspace_bytes, void* stream);
+int lvae_latent_stats_finalize_f64(const double* sums, int64_t U, int64_t n_images, double kl_threshold, double var_threshold,
+                                   double* unit_out, double* layer_out, void* stream);
 /* Training-log summaries (boilr's summarizer: the mean of every step's metrics since the last train line), kept on the device.
  * acc: device double [2 + 6 + L], 8-byte aligned:
  *   [0] steps folded   [1] non-finite steps   [2] sum loss   [3] sum elbo   [4] sum recons   [5] sum kl   [6] sum l2   [7] sum grad

@@ -192,6 +192,15 @@ __device__ __forceinline__ float sigmoidf_(float x) { return __builtin_amdgcn_rc
 // numerically stable softplus, threshold 20 like torch
 __device__ __forceinline__ float softplusf_(float x) { return x > 20.f ? x : log1pf(expf(x)); }
 
+// analytical KL(N(qmu, exp(qlv)) || N(pmu, exp(plv))) of one element (lib/stochastic.py:87): what the stochastic block sums into kl_spatial and
+// the latent statistics average per unit
+__device__ __forceinline__ float normal_kl(float qmu, float qlv, float pmu, float plv) {
+  const float qs = expf(0.5f * qlv), ps = expf(0.5f * plv);
+  const float r = qs / ps, vr = r * r;
+  const float t = (qmu - pmu) / ps;
+  return 0.5f * (vr + t * t - 1.f - logf(vr));
+}
+
 __device__ __forceinline__ float wave_sum(float v) {
 #pragma unroll
   for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);

@@ -22,13 +22,6 @@ __device__ __forceinline__ float normal_logprob(float z, float mu, float lv) {
   return -(d * d) / (2.f * sd * sd) - logf(sd) - kLogSqrt2Pi;
 }
 
-__device__ __forceinline__ float normal_kl(float qmu, float qlv, float pmu, float plv) {
-  const float qs = expf(0.5f * qlv), ps = expf(0.5f * plv);
-  const float r = qs / ps, vr = r * r;
-  const float t = (qmu - pmu) / ps;
-  return 0.5f * (vr + t * t - 1.f - logf(vr));
-}
-
 __global__ __launch_bounds__(256) void stoch_fwd_kernel(StochArgs a, float* __restrict__ z_out, float* logprob_p,
                                                          float* logprob_q, float* kl_samplewise, float* kl_spatial) {
   __shared__ float red[4];

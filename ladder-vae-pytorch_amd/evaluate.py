@@ -143,10 +143,11 @@ def _test_bottom_up(model, x):
     return bu_values, x_nhwc
 
 
-def _test_sample(model, bu_values, x_nhwc, state, zero):
-    """One top-down sample + likelihood + KL bookkeeping, folded into the per-image state (lvae_eval_online_f32)."""
+def _test_sample(model, bu_values, x_nhwc, state, zero, latent_stats=None):
+    """One top-down sample + likelihood + KL bookkeeping, folded into the per-image state (lvae_eval_online_f32). With latent_stats (a
+    latent.LatentStats) every stochastic layer also folds its p and q parameters into it; the noise drawn is the same either way."""
     model.noise.begin(x_nhwc.device)
-    out, td = model._topdown(bu_values)
+    out, td = model._topdown(bu_values, latent_stats=latent_stats)
     if tuple(out.shape[1:3]) != tuple(x_nhwc.shape[1:3]):
         out = ops.CropFn.apply(out, tuple(x_nhwc.shape[1:3]))
     ll, _ = model.likelihood(out, x_nhwc, model.noise)
@@ -159,12 +160,14 @@ def _test_sample(model, bu_values, x_nhwc, state, zero):
 
 class _TestGraphs:
     """The bottom-up pass and one sample of a test batch shape, captured once and replayed for every batch of that shape, in this and in
-    later test passes. Static input x and per-image state; a capture stream of its own (so its scratch workspace is its own too)."""
+    later test passes. Static input x and per-image state; a capture stream of its own (so its scratch workspace is its own too).
+    With latent_stats a second sample graph, which also holds the L folds into that object's accumulator, is captured into the same pool:
+    the pass replays it for the first sample of a batch and the plain one for the rest."""
 
-    def __init__(self, model, x, noise):
+    def __init__(self, model, x, noise, latent_stats=None):
         from .noise import PhiloxNoise
         dev = x.device
-        self.noise, self.keep = noise, []
+        self.noise, self.keep, self.latent_stats = noise, [], latent_stats
         self.stream = torch.cuda.Stream(device=dev, priority=-1)
         self.stream.wait_stream(torch.cuda.current_stream(dev))
         L = model.n_layers
@@ -178,6 +181,11 @@ class _TestGraphs:
             bu, x_nhwc = _test_bottom_up(model, self.x)
             K.eval_online(self.state, L, 0)
             _test_sample(model, bu, x_nhwc, self.state, self.zero)
+            if latent_stats is not None:   # the folds' scratch grows here too; what this throw-away sample added is taken out again
+                sums = latent_stats.buf.clone()
+                _test_sample(model, bu, x_nhwc, self.state, self.zero, latent_stats)
+                latent_stats.buf.copy_(sums)
+                del sums
             model.noise = noise
             noise.begin(dev)          # its device step counter exists before the capture
             del bu, x_nhwc
@@ -188,6 +196,11 @@ class _TestGraphs:
             self.g_sample = torch.cuda.CUDAGraph()
             with torch.cuda.graph(self.g_sample, pool=self.g_bu.pool(), stream=self.stream, capture_error_mode='thread_local'):
                 _test_sample(model, self.bu, self.x_nhwc, self.state, self.zero)
+            self.g_sample_stats = None
+            if latent_stats is not None:
+                self.g_sample_stats = torch.cuda.CUDAGraph()
+                with torch.cuda.graph(self.g_sample_stats, pool=self.g_bu.pool(), stream=self.stream, capture_error_mode='thread_local'):
+                    _test_sample(model, self.bu, self.x_nhwc, self.state, self.zero, latent_stats)
             self.keep.append(K.workspace(0, dev))   # the scratch buffer the captured launches use
 
     def run(self, x, n_samples, totals, L):
@@ -197,14 +210,16 @@ class _TestGraphs:
             self.x.copy_(x)
             K.eval_online(self.state, L, 0)
             self.g_bu.replay()
-            for _ in range(n_samples):
-                self.g_sample.replay()
+            for s in range(n_samples):
+                (self.g_sample_stats if s == 0 and self.g_sample_stats is not None else self.g_sample).replay()
+            if self.latent_stats is not None:
+                self.latent_stats.count(x.shape[0])
             K.eval_totals(self.state, L, n_samples, totals)
         cur.wait_stream(self.stream)
 
 
 @torch.no_grad()
-def test_pass(model, batches, n_samples, noise=None, process_group=None, use_graph=None, optimizer=None):
+def test_pass(model, batches, n_samples, noise=None, process_group=None, use_graph=None, optimizer=None, latent_stats=None):
     """The reference's test summaries over an iterable of NCHW image batches (each rank passes ITS shard of the test set): means over images
     and samples of 'elbo/elbo', 'elbo/recons', 'elbo/kl', 'kl_layers/kl_layer_<i>', plus 'elbo/elbo_IW_<S>' when S > 1, and 'n_images'.
 
@@ -216,10 +231,15 @@ def test_pass(model, batches, n_samples, noise=None, process_group=None, use_gra
     noise tape (parity tests) runs eagerly.
     optimizer: when it keeps an average of the weights (Adamax(ema_decay > 0)) the whole pass runs inside `optimizer.swap_ema()`, on the
     averaged weights, and the result says so ('weights': 'ema'). The exchange is in place, so the captured graphs of earlier passes read
-    the current average when they are replayed, and the parameters are back, bit for bit, when the pass returns."""
+    the current average when they are replayed, and the parameters are back, bit for bit, when the pass returns.
+    latent_stats: a latent.LatentStats. The FIRST sample of every batch (one ancestral sample per image) also folds every layer's p and q
+    parameters into it; the pass ends with its `take()` (a collective, like the all-reduce of the totals) and the result gains the
+    'latent/*' counts and 'latent_arrays' (per layer 'kl', 'mu_mean', 'mu_var' as (Z, h, w) arrays). Every other key is bit for bit what the
+    pass returns without it: the folds draw no noise and write nothing the pass reads."""
     if optimizer is not None and getattr(optimizer, 'ema_decay', 0.0) > 0.0:
         with optimizer.swap_ema():
-            res = test_pass(model, batches, n_samples, noise=noise, process_group=process_group, use_graph=use_graph)
+            res = test_pass(model, batches, n_samples, noise=noise, process_group=process_group, use_graph=use_graph,
+                            latent_stats=latent_stats)
         res['weights'] = 'ema'
         return res
     from .noise import PhiloxNoise
@@ -235,6 +255,8 @@ def test_pass(model, batches, n_samples, noise=None, process_group=None, use_gra
         use_graph = isinstance(noise, PhiloxNoise)
     L = model.n_layers
     totals = torch.zeros(5 + L, dtype=torch.float64, device=dev)
+    if latent_stats is not None:
+        latent_stats.reset()
     train_noise, was_training = model.noise, model.training
     model.eval()
     model.noise = noise
@@ -243,10 +265,11 @@ def test_pass(model, batches, n_samples, noise=None, process_group=None, use_gra
             plans = model.__dict__.setdefault('_test_graphs', {})
             for x in batches:
                 x = x.to(dev).contiguous().float()
-                key = (tuple(x.shape), id(noise), noise.seed, id(model.pack()), model.compute_dtype)
+                key = (tuple(x.shape), id(noise), noise.seed, id(model.pack()), model.compute_dtype,
+                       None if latent_stats is None else id(latent_stats))
                 plan = plans.get(key)
-                if plan is None or plan.noise is not noise:
-                    plan = plans[key] = _TestGraphs(model, x, noise)
+                if plan is None or plan.noise is not noise or plan.latent_stats is not latent_stats:
+                    plan = plans[key] = _TestGraphs(model, x, noise, latent_stats)
                 plan.run(x, n_samples, totals, L)
         else:
             keep = []
@@ -257,8 +280,10 @@ def test_pass(model, batches, n_samples, noise=None, process_group=None, use_gra
                     state = torch.empty(5 * x.shape[0] + L, dtype=torch.float64, device=dev)
                     K.eval_online(state, L, 0)
                     bu, x_nhwc = _test_bottom_up(model, x)
-                    for _ in range(n_samples):
-                        _test_sample(model, bu, x_nhwc, state, zero)
+                    for s in range(n_samples):
+                        _test_sample(model, bu, x_nhwc, state, zero, latent_stats if s == 0 else None)
+                    if latent_stats is not None:
+                        latent_stats.count(x.shape[0])
                     K.eval_totals(state, L, n_samples, totals)
             torch.cuda.current_stream(dev).synchronize()   # (the registered scratch buffers of this pass may go now)
     finally:
@@ -272,6 +297,10 @@ def test_pass(model, batches, n_samples, noise=None, process_group=None, use_gra
     if n_samples > 1:
         res['elbo/elbo_IW_%d' % n_samples] = tot[0] / n
     res['n_images'] = int(n)
+    if latent_stats is not None:
+        lat = latent_stats.take(process_group)
+        res.update((k, v) for k, v in lat.items() if k.startswith('latent/'))
+        res['latent_arrays'] = lat['arrays']
     return res
 
 
@@ -373,6 +402,7 @@ def build_eval_parser():
     p.add_argument('--ema', action='store_true', help="evaluate the averaged weights stored in --checkpoint (its 'ema' entry)")
     # (--img-dir DIR is a flag of build_parser: here samples_0.png with --ps, sample_mode_layer<i>.png with --layer-repr)
     p.add_argument('--recons', action='store_true', help='inputs beside their reconstructions -> DIR/reconstructions.png (needs --img-dir)')
+    # (--latent-stats and its two thresholds are flags of build_parser: here with --ll, and the arrays go to latent_stats.npz)
     return p
 
 
@@ -381,6 +411,8 @@ def parse_eval_args(argv=None):
     args = p.parse_args(argv)
     if args.recons and not args.img_dir:
         p.error('--recons needs --img-dir DIR: the picture is written there')
+    if args.latent_stats and not args.ll:
+        p.error('--latent-stats needs --ll: the statistics are folded during the log-likelihood pass')
     return args
 
 
@@ -415,10 +447,18 @@ def main(argv=None):
             data = synthetic_batch(exp, args.n_test, gen)
     if args.ll:
         bs = args.test_batch_size
-        res = test_pass(model, (data[i:i + bs] for i in range(0, data.shape[0], bs)), args.loglikelihood_samples)
+        lat = None
+        if args.latent_stats:
+            from .latent import LatentStats, latent_line_suffix, save_npz
+            lat = LatentStats(model, exp.device, args.latent_kl_threshold, args.latent_var_threshold)
+        res = test_pass(model, (data[i:i + bs] for i in range(0, data.shape[0], bs)), args.loglikelihood_samples, latent_stats=lat)
         if args.ema:
             res['weights'] = 'ema'
-        print(exp.test_log_str(res, model.global_step))
+        line = exp.test_log_str(res, model.global_step)
+        if lat is not None:
+            line += latent_line_suffix(res, lat.kl_threshold, lat.var_threshold)
+            save_npz('latent_stats.npz', res['latent_arrays'], lat.kl_threshold, lat.var_threshold, res['n_images'])
+        print(line)
     if args.ps:
         np.save('prior_samples.npy', prior_samples(model, 64).cpu().numpy())
     if args.layer_repr:

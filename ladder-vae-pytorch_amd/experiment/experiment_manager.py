@@ -100,6 +100,12 @@ def build_parser():
                         'inside the step), with the gradient norm and the number of non-finite steps, instead of the last step of rank 0')
     p.add_argument('--history', type=str, default='', metavar='FILE',
                    help='rank 0 appends one JSON object per printed train and test line to FILE (JSONL)')
+    p.add_argument('--latent-stats', action='store_true', dest='latent_stats',
+                   help='every test / log-likelihood pass also counts, per stochastic layer, the latent units in use (summed on the device '
+                        'during the pass): units whose mean KL(q||p) over the test images exceeds --latent-kl-threshold, and units whose '
+                        'posterior mean varies over them by more than --latent-var-threshold; printed after the test line')
+    p.add_argument('--latent-kl-threshold', type=float, default=0.01, dest='latent_kl_threshold', metavar='T')
+    p.add_argument('--latent-var-threshold', type=float, default=0.01, dest='latent_var_threshold', metavar='T')
     return p
 
 

@@ -1137,6 +1137,34 @@ def eval_totals(state, L, S, totals):
     call('lvae_eval_totals_f64', ptr(state, (torch.float64,)), N, int(L), int(S), ptr(totals, (torch.float64,)), stream_ptr())
 
 
+def latent_stats_fold(p, q, sums, N=None):
+    """sums: float64 (3, U) view += this batch's [sum mu_q, sum mu_q^2, sum KL(q || p)] per latent unit, U = H * W * Z in NHWC order.
+    p (N|1,H,W,2Z), q (N,H,W,2Z): the fp32 (mu | logvar) tensors normal_stochastic_fwd reads. Two launches, no allocation once the scratch
+    buffer of the stream is large enough."""
+    if N is None:
+        N = q.shape[0]
+    _, H, W, Z2 = q.shape
+    if not (p.dtype == q.dtype == torch.float32 and q.is_contiguous() and tuple(p.shape[1:]) == (H, W, Z2) and Z2 % 2 == 0):
+        raise _C.LvaeHipError("latent_stats_fold: p %s / q %s are not fp32 (mu | logvar) tensors of one layer" % (tuple(p.shape), tuple(q.shape)))
+    if sums.numel() != 3 * H * W * (Z2 // 2) or not sums.is_contiguous():
+        raise _C.LvaeHipError("latent_stats_fold: sums has %d entries, this layer 3 x %d units" % (sums.numel(), H * W * (Z2 // 2)))
+    need = _C.load().lvae_latent_stats_workspace(int(N), H * W, Z2 // 2)
+    ws = workspace(need, q.device)
+    call('lvae_latent_stats_fold_f32', ptr(p), int(p.shape[0] == 1 and N > 1), ptr(q), int(N), H * W, Z2 // 2, ptr(sums, (torch.float64,)),
+         ws.data_ptr(), ws.numel(), stream_ptr())
+
+
+def latent_stats_finalize(sums, n_images, kl_threshold, var_threshold, unit_out, layer_out):
+    """sums float64 (3, U) -> unit_out float64 (3, U) = per-unit mean KL, mean and population variance of mu_q; layer_out float64 (4,) =
+    [units with KL > kl_threshold, units with variance > var_threshold, U, sum of the per-unit KLs]. One launch of one workgroup."""
+    U = sums.numel() // 3
+    if unit_out.numel() != 3 * U or layer_out.numel() != 4:
+        raise _C.LvaeHipError("latent_stats_finalize: outputs of %d and %d entries for %d units" % (unit_out.numel(), layer_out.numel(), U))
+    f64 = (torch.float64,)
+    call('lvae_latent_stats_finalize_f64', ptr(sums, f64), U, int(n_images), float(kl_threshold), float(var_threshold), ptr(unit_out, f64),
+         ptr(layer_out, f64), stream_ptr())
+
+
 SUMMARY_FIXED, SUMMARY_MAX_LAYERS = 8, 64   # slots of lvae_summary_fold_f64's accumulator before the per-layer KLs; the most layers it takes
 
 

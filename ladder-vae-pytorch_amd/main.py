@@ -16,6 +16,7 @@ from .engine import TrainStep
 from .evaluate import image_pass, test_pass
 from .experiment.experiment_manager import LVAEExperiment
 from .images import write_png
+from .latent import LatentStats, latent_line_suffix
 from .schedule import TrainSchedule, checkpoint_path, checkpoints_to_delete
 from .summary import History, TrainSummary, train_line_suffix
 
@@ -119,6 +120,8 @@ def main(argv=None):
     step_fn = TrainStep(model, opt, beta=1.0, use_graph=not args.no_graph, allreduce=allreduce, beta_anneal=args.beta_anneal,
                         feed=feed, summary=summary)
     history = History(args.history) if args.history and rank == 0 else None
+    # --latent-stats: the first sample of every test batch also folds each layer's posterior into a device accumulator
+    latent = LatentStats(model, exp.device, args.latent_kl_threshold, args.latent_var_threshold) if args.latent_stats and tests is not None else None
     if rank == 0:
         print(exp.run_description)
         print('parameters: %d   world size: %d   per-rank batch: %d' % (sum(p.numel() for p in model.parameters()), world,
@@ -183,9 +186,12 @@ def main(argv=None):
         if n_samples:
             if data is not None and loader is None and feed is None:
                 epoch = step * args.batch_size // data.shape[0]
-            res = test_pass(model, tests(), n_samples, optimizer=opt)   # (--ema-decay: on the averaged weights)
+            res = test_pass(model, tests(), n_samples, optimizer=opt, latent_stats=latent)   # (--ema-decay: on the averaged weights)
             if rank == 0:
-                print(exp.test_log_str(res, step, epoch), flush=True)
+                line = exp.test_log_str(res, step, epoch)
+                if latent is not None:
+                    line += latent_line_suffix(res, latent.kl_threshold, latent.var_threshold)
+                print(line, flush=True)
                 if history is not None:
                     history.write(step, 'test', res, epoch=epoch)
             t0, seen = time.time(), 0                  # the training throughput excludes test passes

@@ -251,7 +251,9 @@ class LadderVAE(nn.Module):
         self.noise.end()  # the next call draws fresh dropout masks
         return out
 
-    def _topdown(self, bu_values=None, n_img_prior=None, mode_layers=None, constant_layers=None, forced_latent=None):
+    def _topdown(self, bu_values=None, n_img_prior=None, mode_layers=None, constant_layers=None, forced_latent=None, latent_stats=None):
+        """latent_stats: engine-only keyword — a latent.LatentStats whose slot i the stochastic block of layer i folds its (mu | logvar)
+        tensors into (inference mode only); None issues exactly the launches of a pass without it."""
         if mode_layers is None:
             mode_layers = []
         if constant_layers is None:
@@ -289,7 +291,8 @@ class LadderVAE(nn.Module):
             out, _, aux = self.top_down_layers[i](out, skip_connection_input=out, inference_mode=inference_mode,
                                                   bu_value=bu_value, n_img_prior=n_img_prior, use_mode=i in mode_layers,
                                                   force_constant_output=i in constant_layers, forced_latent=fl,
-                                                  noise=self.noise, rows=(lp_mat[i], kl_mat[i]))
+                                                  noise=self.noise, rows=(lp_mat[i], kl_mat[i]),
+                                                  stats=None if latent_stats is None else latent_stats.slot(i))
             z[i] = aux['z']
             kl[i] = aux['kl_samplewise']
             kl_spatial[i] = aux['kl_spatial']

@@ -115,7 +115,8 @@ class History:
         rec = {'step': int(step), 'split': split}
         if epoch is not None:
             rec['epoch'] = int(epoch)
-        rec['metrics'] = {k: v for k, v in metrics.items() if k not in extra}
+        # ('latent_arrays' of a test pass with --latent-stats: whole arrays, not a line's numbers; the 'latent/*' counts stay)
+        rec['metrics'] = {k: v for k, v in metrics.items() if k not in extra and k != 'latent_arrays'}
         rec.update(extra)
         self.f.write(json.dumps(rec) + '\n')
         self.f.flush()
