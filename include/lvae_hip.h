@@ -668,6 +668,36 @@ int lvae_adamax_step_f32(float* p, const float* g, float* exp_avg, float* exp_in
 int lvae_adamax_ema_step_f32(float* p, const float* g, float* exp_avg, float* exp_inf, const float* mask, int64_t n,
                              float lr, float beta1, float beta2, float eps, float weight_decay, const float* gscale,
                              const uint64_t* step_count, float* ema, float decay, void* stream);
+/* A learning-rate schedule as a function of the optimizer's own step counter, so that a captured step replays with the lr of the step it
+ * runs. n = completed steps (step_count[0] before the update), W = warmup_steps, T = decay_steps, m = min_lr / base_lr, t = n - W:
+ *   n <  W:  lr = base_lr * (n + 1) / W                    (linear warm-up: the first step is not zero, step W - 1 reaches base_lr)
+ *   n >= W:  lr = base_lr * f, with f by `kind`:
+ *     LVAE_LR_CONSTANT  1
+ *     LVAE_LR_COSINE    m + (1 - m) * (1 + cos(pi * min(t, T) / T)) / 2
+ *     LVAE_LR_LINEAR    1 - (1 - m) * min(t, T) / T
+ *     LVAE_LR_STEP      max(m, gamma ^ floor(t / T))
+ *     LVAE_LR_EXP       max(m, gamma ^ (t / T))
+ * evaluated in double from the exact integer counter and rounded to float once. Valid: base_lr > 0, 0 <= min_lr <= base_lr,
+ * 0 < gamma <= 1, warmup_steps >= 0, a known kind, and decay_steps > 0 unless the kind is LVAE_LR_CONSTANT; anything else: LVAE_EINVAL. */
+enum { LVAE_LR_CONSTANT = 0, LVAE_LR_COSINE = 1, LVAE_LR_LINEAR = 2, LVAE_LR_STEP = 3, LVAE_LR_EXP = 4 };
+typedef struct lvae_lr_schedule {
+  float base_lr;
+  float min_lr;
+  float gamma;
+  int32_t kind;
+  int64_t warmup_steps;
+  int64_t decay_steps;
+} lvae_lr_schedule;
+/* *lr = the schedule's value at n completed steps. Host only: no GPU, no stream; the function the kernel below runs on the device (host
+ * and device libm may round a cos / pow differently: the two agree to one float spacing). */
+int lvae_lr_schedule_at(const lvae_lr_schedule* schedule, uint64_t n, float* lr);
+/* lvae_adamax_ema_step_f32 with lr = schedule(step_count[0]) computed inside the same kernel (no further launch). `schedule` is a host
+ * pointer read at the call: its values travel as a kernel argument, so a captured launch keeps them. ema may be NULL (no average:
+ * lvae_adamax_step_f32's update; `decay` is then ignored). lr_out: device float[1] or NULL, receives the lr this step applied. With a
+ * LVAE_LR_CONSTANT schedule without warm-up every output is bit for bit that of the unscheduled entry points with lr = base_lr. */
+int lvae_adamax_sched_step_f32(float* p, const float* g, float* exp_avg, float* exp_inf, const float* mask, int64_t n,
+                               const lvae_lr_schedule* schedule, float beta1, float beta2, float eps, float weight_decay,
+                               const float* gscale, const uint64_t* step_count, float* ema, float decay, float* lr_out, void* stream);
 /* a[0:n] <-> b[0:n] in one pass (16-byte aligned, not overlapping): the averaged weights exchanged IN PLACE with the trainable prefix of
  * the parameter arena for a test pass and back, so captured graphs and parameter views keep their addresses. */
 int lvae_swap_f32(float* a, float* b, int64_t n, void* stream);

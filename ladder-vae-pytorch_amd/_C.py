@@ -68,6 +68,14 @@ class RbExt(C.Structure):
                 ('ap_out', C.c_void_p)]
 
 
+class LrScheduleStruct(C.Structure):
+    """mirror of struct lvae_lr_schedule"""
+    _fields_ = [('base_lr', C.c_float), ('min_lr', C.c_float), ('gamma', C.c_float), ('kind', C.c_int32),
+                ('warmup_steps', C.c_int64), ('decay_steps', C.c_int64)]
+
+
+LR_KINDS = {'constant': 0, 'cosine': 1, 'linear': 2, 'step': 3, 'exp': 4}   # LVAE_LR_*
+
 RB_PRO_AFFINE, RB_PRO_BN_APPLY, RB_PRO_GATE_BWD = 0, 1, 2
 RB_EPI_PLAIN, RB_EPI_GATE = 0, 1
 
@@ -160,6 +168,8 @@ SIGNATURES = {
     'lvae_iw_logmeanexp_f32': (C.c_int, [_P, _I, _I, _P, _P]),
     'lvae_adamax_step_f32': (C.c_int, [_P, _P, _P, _P, _P, _L, _F, _F, _F, _F, _F, _P, _P, _P]),
     'lvae_adamax_ema_step_f32': (C.c_int, [_P, _P, _P, _P, _P, _L, _F, _F, _F, _F, _F, _P, _P, _P, _F, _P]),
+    'lvae_lr_schedule_at': (C.c_int, [C.POINTER(LrScheduleStruct), _U, C.POINTER(C.c_float)]),
+    'lvae_adamax_sched_step_f32': (C.c_int, [_P, _P, _P, _P, _P, _L, C.POINTER(LrScheduleStruct), _F, _F, _F, _F, _P, _P, _P, _F, _P, _P]),
     'lvae_swap_f32': (C.c_int, [_P, _P, _L, _P]),
     'lvae_sumsq_workspace': (_Z, [_L]),
     'lvae_l2norm_f32': (C.c_int, [_P, _L, _P, _P, _Z, _P]),

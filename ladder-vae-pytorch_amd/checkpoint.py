@@ -63,16 +63,27 @@ def noise_state(model):
     return {'seed': int(nz.seed), 'step': int(nz.step.item()) if nz.step is not None else 0}
 
 
+def lr_schedule_record(optimizer):
+    """What a checkpoint keeps of a scheduled optimizer under 'lr_schedule': LrSchedule's fields and the base lr, plain Python values; None
+    without a schedule. A resumed run uses the schedule it was started with (load_checkpoint does not touch it); the record says what the
+    file's run used."""
+    sched = getattr(optimizer, 'schedule', None)
+    return None if sched is None else dict(sched.state_dict(), base_lr=optimizer.lr)
+
+
 def save_checkpoint(path, model, optimizer=None, summary=None):
     """Weights (reference layout), global step, Adamax state and the position of the Philox noise stream, so that a resumed run continues
     the original one bit for bit. With a `summary` (summary.TrainSummary) also 'summary': the open log window's accumulator as a list of
-    floats, so that the run resumed in the middle of a window prints the train line of the uninterrupted one."""
+    floats, so that the run resumed in the middle of a window prints the train line of the uninterrupted one. A scheduled lr is a function
+    of the Adamax step and of the schedule, stored as 'lr_schedule' (`lr_schedule_record`)."""
     ck = {'model': state_dict_reference_layout(model), 'global_step': int(model.global_step)}
     if optimizer is not None:
         ck['optimizer'] = optimizer_state_by_name(model, optimizer)
         if getattr(optimizer, 'ema_decay', 0.0) > 0.0:
             ck['ema'] = ema_state_dict_reference_layout(model, optimizer)
             ck['ema_decay'] = optimizer.ema_decay
+        if lr_schedule_record(optimizer) is not None:
+            ck['lr_schedule'] = lr_schedule_record(optimizer)
     nz = noise_state(model)
     if nz is not None:
         ck['noise'] = nz

@@ -3,6 +3,7 @@
 #include <stdarg.h>
 
 #include "lvae_common.h"
+#include "lr_schedule.h"
 
 namespace lvae {
 
@@ -272,12 +273,19 @@ __global__ __launch_bounds__(256) void iw_online_kernel(const float* __restrict_
 // ---------------------------------------------------------------------------------------------------------
 // EMA: the same pass also keeps an exponential moving average of the updated parameters, ema += (p_new - ema) * (1 - d), with the decay
 // ramp d = min(decay, (1 + n) / (10 + n)) over the n completed steps read from the device counter (a replayed graph follows the ramp).
-template <bool EMA>
+// SCHED: lr is not the host's value but the schedule's at the n completed steps of the same counter (lr_schedule.h; the schedule is constant
+// over a run, so a captured launch may keep it), and block 0 leaves the lr it applied in lr_out (optional) for the log.
+template <bool EMA, bool SCHED>
 __global__ __launch_bounds__(256) void adamax_kernel(float* __restrict__ p, const float* __restrict__ g,
                                                       float* __restrict__ m, float* __restrict__ u,
                                                       const float* __restrict__ mask, int64_t n4, float lr, float b1,
                                                       float b2, float eps, float wd, const float* gscale,
-                                                      const uint64_t* step_count, float* __restrict__ ema, float decay) {
+                                                      const uint64_t* step_count, float* __restrict__ ema, float decay,
+                                                      lvae_lr_schedule sched, float* lr_out) {
+  if (SCHED) {
+    lr = lr_schedule_eval(sched, step_count[0]);
+    if (lr_out && blockIdx.x == 0 && threadIdx.x == 0) lr_out[0] = lr;
+  }
   const float step = (float)(step_count[0] + 1);
   const float clr = lr / (1.f - powf(b1, step));
   const float gs = gscale ? gscale[0] : 1.f;
@@ -491,8 +499,9 @@ extern "C" int lvae_adamax_step_f32(float* p, const float* g, float* exp_avg, fl
                                     const uint64_t* step_count, void* stream) {
   LVAE_REQUIRE(p && g && exp_avg && exp_inf && step_count && n > 0, LVAE_EINVAL, "lvae_adamax_step_f32: bad args");
   LVAE_REQUIRE(n % 4 == 0, LVAE_EALIGN, "lvae_adamax_step_f32: arena length %lld must be a multiple of 4", (long long)n);
-  hipLaunchKernelGGL(adamax_kernel<false>, dim3(grid_for(n / 4, 256)), dim3(256), 0, (hipStream_t)stream, p, g, exp_avg, exp_inf,
-                     mask, n / 4, lr, beta1, beta2, eps, weight_decay, gscale, step_count, (float*)nullptr, 0.f);
+  hipLaunchKernelGGL((adamax_kernel<false, false>), dim3(grid_for(n / 4, 256)), dim3(256), 0, (hipStream_t)stream, p, g, exp_avg,
+                     exp_inf, mask, n / 4, lr, beta1, beta2, eps, weight_decay, gscale, step_count, (float*)nullptr, 0.f,
+                     lvae_lr_schedule{}, (float*)nullptr);
   LVAE_LAUNCH_CHECK("adamax_step");
   return 0;
 }
@@ -504,9 +513,52 @@ extern "C" int lvae_adamax_ema_step_f32(float* p, const float* g, float* exp_avg
   LVAE_REQUIRE(decay >= 0.f && decay < 1.f, LVAE_EINVAL, "lvae_adamax_ema_step_f32: decay %g outside [0, 1)", (double)decay);
   LVAE_REQUIRE(n % 4 == 0, LVAE_EALIGN, "lvae_adamax_ema_step_f32: arena length %lld must be a multiple of 4", (long long)n);
   LVAE_REQUIRE((reinterpret_cast<uintptr_t>(ema) & 15) == 0, LVAE_EALIGN, "lvae_adamax_ema_step_f32: misaligned ema");
-  hipLaunchKernelGGL(adamax_kernel<true>, dim3(grid_for(n / 4, 256)), dim3(256), 0, (hipStream_t)stream, p, g, exp_avg, exp_inf,
-                     mask, n / 4, lr, beta1, beta2, eps, weight_decay, gscale, step_count, ema, decay);
+  hipLaunchKernelGGL((adamax_kernel<true, false>), dim3(grid_for(n / 4, 256)), dim3(256), 0, (hipStream_t)stream, p, g, exp_avg,
+                     exp_inf, mask, n / 4, lr, beta1, beta2, eps, weight_decay, gscale, step_count, ema, decay, lvae_lr_schedule{},
+                     (float*)nullptr);
   LVAE_LAUNCH_CHECK("adamax_ema_step");
+  return 0;
+}
+
+// what lr_schedule_eval takes for granted (written so that a NaN fails every test)
+static int lr_schedule_valid(const lvae_lr_schedule* s, const char* who) {
+  LVAE_REQUIRE(s, LVAE_EINVAL, "%s: no schedule", who);
+  LVAE_REQUIRE(s->base_lr > 0.f, LVAE_EINVAL, "%s: base_lr %g must be positive", who, (double)s->base_lr);
+  LVAE_REQUIRE(s->min_lr >= 0.f && s->min_lr <= s->base_lr, LVAE_EINVAL, "%s: min_lr %g outside [0, base_lr = %g]", who,
+               (double)s->min_lr, (double)s->base_lr);
+  LVAE_REQUIRE(s->gamma > 0.f && s->gamma <= 1.f, LVAE_EINVAL, "%s: gamma %g outside (0, 1]", who, (double)s->gamma);
+  LVAE_REQUIRE(s->warmup_steps >= 0, LVAE_EINVAL, "%s: warmup_steps %lld is negative", who, (long long)s->warmup_steps);
+  LVAE_REQUIRE(s->kind >= LVAE_LR_CONSTANT && s->kind <= LVAE_LR_EXP, LVAE_EINVAL, "%s: unknown kind %d", who, (int)s->kind);
+  LVAE_REQUIRE(s->kind == LVAE_LR_CONSTANT || s->decay_steps > 0, LVAE_EINVAL, "%s: decay_steps %lld must be positive", who,
+               (long long)s->decay_steps);
+  return 0;
+}
+
+extern "C" int lvae_lr_schedule_at(const lvae_lr_schedule* schedule, uint64_t n, float* lr) {
+  if (int rc = lr_schedule_valid(schedule, "lvae_lr_schedule_at")) return rc;
+  LVAE_REQUIRE(lr, LVAE_EINVAL, "lvae_lr_schedule_at: no output");
+  *lr = lr_schedule_eval(*schedule, n);
+  return 0;
+}
+
+extern "C" int lvae_adamax_sched_step_f32(float* p, const float* g, float* exp_avg, float* exp_inf, const float* mask, int64_t n,
+                                          const lvae_lr_schedule* schedule, float beta1, float beta2, float eps, float weight_decay,
+                                          const float* gscale, const uint64_t* step_count, float* ema, float decay, float* lr_out,
+                                          void* stream) {
+  LVAE_REQUIRE(p && g && exp_avg && exp_inf && step_count && n > 0, LVAE_EINVAL, "lvae_adamax_sched_step_f32: bad args");
+  if (int rc = lr_schedule_valid(schedule, "lvae_adamax_sched_step_f32")) return rc;
+  LVAE_REQUIRE(n % 4 == 0, LVAE_EALIGN, "lvae_adamax_sched_step_f32: arena length %lld must be a multiple of 4", (long long)n);
+  const dim3 grid(grid_for(n / 4, 256));
+  if (ema) {
+    LVAE_REQUIRE(decay >= 0.f && decay < 1.f, LVAE_EINVAL, "lvae_adamax_sched_step_f32: decay %g outside [0, 1)", (double)decay);
+    LVAE_REQUIRE((reinterpret_cast<uintptr_t>(ema) & 15) == 0, LVAE_EALIGN, "lvae_adamax_sched_step_f32: misaligned ema");
+    hipLaunchKernelGGL((adamax_kernel<true, true>), grid, dim3(256), 0, (hipStream_t)stream, p, g, exp_avg, exp_inf, mask, n / 4, 0.f,
+                       beta1, beta2, eps, weight_decay, gscale, step_count, ema, decay, *schedule, lr_out);
+  } else {
+    hipLaunchKernelGGL((adamax_kernel<false, true>), grid, dim3(256), 0, (hipStream_t)stream, p, g, exp_avg, exp_inf, mask, n / 4, 0.f,
+                       beta1, beta2, eps, weight_decay, gscale, step_count, (float*)nullptr, 0.f, *schedule, lr_out);
+  }
+  LVAE_LAUNCH_CHECK("adamax_sched_step");
   return 0;
 }
 

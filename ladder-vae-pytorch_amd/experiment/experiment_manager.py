@@ -17,7 +17,7 @@ import torch
 from .. import engine
 from ..models.lvae import LadderVAE
 from ..noise import PhiloxNoise
-from ..optim import Adamax
+from ..optim import Adamax, LrSchedule
 
 DATASETS = {
     # name: (color_ch, (H, W), default likelihood)  — experiment/data.py:32-97, experiment_manager.py:279-288
@@ -104,6 +104,14 @@ def build_parser():
                    help='every test / log-likelihood pass also counts, per stochastic layer, the latent units in use (summed on the device '
                         'during the pass): units whose mean KL(q||p) over the test images exceeds --latent-kl-threshold, and units whose '
                         'posterior mean varies over them by more than --latent-var-threshold; printed after the test line')
+    p.add_argument('--lr-schedule', type=str, choices=['constant', 'cosine', 'linear', 'step', 'exp'], default='constant', dest='lr_schedule',
+                   help='after --lr-warmup: keep --lr, or bring it down over --lr-decay-steps steps (cosine / linear: to --lr-min; step: times '
+                        '--lr-gamma every --lr-decay-steps steps; exp: times --lr-gamma per --lr-decay-steps steps, continuously; both not '
+                        'below --lr-min). Computed on the device from the optimizer step counter, inside the captured step')
+    p.add_argument('--lr-warmup', type=int, default=0, dest='lr_warmup', metavar='N', help='raise the lr linearly over the first N steps')
+    p.add_argument('--lr-decay-steps', type=int, default=0, dest='lr_decay_steps', metavar='T')
+    p.add_argument('--lr-min', type=float, default=0.0, dest='lr_min')
+    p.add_argument('--lr-gamma', type=float, default=0.1, dest='lr_gamma')
     p.add_argument('--latent-kl-threshold', type=float, default=0.01, dest='latent_kl_threshold', metavar='T')
     p.add_argument('--latent-var-threshold', type=float, default=0.01, dest='latent_var_threshold', metavar='T')
     return p
@@ -139,6 +147,10 @@ class LVAEExperiment:
         if getattr(args, 'device_data', False) and args.synthetic:
             raise SystemExit("--device-data feeds the step from a data set kept in device memory; --synthetic has none "
                              "(use --device-data with -d DATASET or --data-npz FILE)")
+        if getattr(args, 'lr_schedule', 'constant') != 'constant' and args.lr_decay_steps <= 0:
+            raise SystemExit("--lr-schedule %s needs --lr-decay-steps > 0" % args.lr_schedule)
+        if getattr(args, 'lr_min', 0.0) > args.lr:
+            raise SystemExit("--lr-min %g exceeds --lr %g" % (args.lr_min, args.lr))
         assert args.weight_decay >= 0.0
         assert 0.0 <= args.dropout <= 1.0
         if args.dropout < 1e-5:
@@ -189,8 +201,19 @@ class LVAEExperiment:
         model.compute_dtype = a.compute_dtype
         return model
 
+    @staticmethod
+    def _make_schedule(args):
+        """The LrSchedule of the --lr-* flags; None (the plain optimizer step) unless one of them asks for a moving lr."""
+        if getattr(args, 'lr_warmup', 0) <= 0 and getattr(args, 'lr_schedule', 'constant') == 'constant':
+            return None
+        try:
+            return LrSchedule(args.lr_schedule, args.lr_warmup, args.lr_decay_steps, args.lr_min, args.lr_gamma)
+        except ValueError as e:
+            raise SystemExit(str(e))
+
     def _make_optimizer(self):
-        return Adamax(self.model, lr=self.args.lr, weight_decay=self.args.weight_decay, ema_decay=getattr(self.args, 'ema_decay', 0.0))
+        return Adamax(self.model, lr=self.args.lr, weight_decay=self.args.weight_decay, ema_decay=getattr(self.args, 'ema_decay', 0.0),
+                      schedule=self._make_schedule(self.args))
 
     def beta(self):
         if self.args.beta_anneal != 0:

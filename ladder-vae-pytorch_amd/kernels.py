@@ -1256,6 +1256,31 @@ def adamax_ema_step(p, g, exp_avg, exp_inf, mask, lr, beta1, beta2, eps, weight_
     prepared.weights_written()
 
 
+def lr_schedule_struct(base_lr, kind, warmup_steps, decay_steps, min_lr, gamma):
+    """struct lvae_lr_schedule of the arguments (`kind` by name: _C.LR_KINDS)."""
+    if kind not in _C.LR_KINDS:
+        raise ValueError("unknown lr schedule %r (one of %s)" % (kind, ', '.join(_C.LR_KINDS)))
+    return _C.LrScheduleStruct(float(base_lr), float(min_lr), float(gamma), _C.LR_KINDS[kind], int(warmup_steps), int(decay_steps))
+
+
+def lr_schedule_at(schedule, n):
+    """The lr a _C.LrScheduleStruct gives at n completed steps: the host twin of what the scheduled Adamax kernel computes. Needs no GPU."""
+    lr = C.c_float()
+    call('lvae_lr_schedule_at', C.byref(schedule), int(n), C.byref(lr))
+    return lr.value
+
+
+def adamax_sched_step(p, g, exp_avg, exp_inf, mask, schedule, beta1, beta2, eps, weight_decay, gscale, step_count, ema=None, decay=0.0,
+                      lr_out=None):
+    """adamax_step / adamax_ema_step (`ema` None or a buffer) with lr = schedule(step_count[0]) evaluated inside the kernel; `lr_out`
+    (device float[1], optional) receives the lr applied."""
+    if ema is not None and ema.numel() != p.numel():
+        raise _C.LvaeHipError("ema has %d elements, the parameters %d" % (ema.numel(), p.numel()))
+    call('lvae_adamax_sched_step_f32', ptr(p), ptr(g), ptr(exp_avg), ptr(exp_inf), ptr(mask), p.numel(), C.byref(schedule), beta1,
+         beta2, eps, weight_decay, ptr(gscale), step_count.data_ptr(), ptr(ema), float(decay), ptr(lr_out, (torch.float32,)), stream_ptr())
+    prepared.weights_written()
+
+
 def swap(a, b):
     """a <-> b in place, one pass (two contiguous fp32 buffers of one length). The caller says when weights moved (weights_written)."""
     if a.numel() != b.numel() or not (a.is_contiguous() and b.is_contiguous()):

@@ -10,7 +10,7 @@ import numpy as np
 import torch
 
 from . import dist as ldist
-from .checkpoint import save_checkpoint
+from .checkpoint import lr_schedule_record, save_checkpoint
 from .data import DeviceDataset
 from .engine import TrainStep
 from .evaluate import image_pass, test_pass
@@ -67,6 +67,11 @@ def test_batches(exp, loader, npz, rank, world, on_device=False):
     return lambda: (data[i:i + bs] for i in range(0, data.shape[0], bs))
 
 
+def lr_suffix(m):
+    """What a scheduled lr appends to a train line: the lr of the step the line falls due at."""
+    return '   lr: {:.3g}'.format(m['lr/lr']) if 'lr/lr' in m else ''
+
+
 IMG_NROWS = 8   # pictures of --ts-img-every: 8 x 8 samples, 32 input / reconstruction pairs
 
 
@@ -89,7 +94,11 @@ def main(argv=None):
     if args.resume:
         from .checkpoint import load_checkpoint
         # (weights, Adamax state and average, global step, the rank-0 noise stream's position and the open log window)
-        load_checkpoint(args.resume, model, opt, summary=summary)
+        ck = load_checkpoint(args.resume, model, opt, summary=summary)
+        was = ck.get('lr_schedule') if isinstance(ck, dict) and 'model' in ck else None
+        if rank == 0 and was != lr_schedule_record(opt):
+            print('warning: %s was written with the lr schedule %s; continuing with %s' % (args.resume, was, lr_schedule_record(opt)))
+        del ck
     model.noise.seed ^= rank * 0x9E3779B9
     model.train()
     arena = model.pack()
@@ -171,14 +180,18 @@ def main(argv=None):
             m = summary.take()                         # a collective: every rank takes its window, rank 0 prints the mean over all
             if rank == 0:
                 dt = time.time() - t0
-                print(exp.train_log_str(m, step) + train_line_suffix(m, summary.ranks) + '   [{:.0f} img/s]'.format(seen / dt))
+                if opt.schedule is not None:
+                    m['lr/lr'] = opt.current_lr()      # of this step, not a window mean: the accumulator's layout stays as it is
+                print(exp.train_log_str(m, step) + train_line_suffix(m, summary.ranks) + lr_suffix(m) + '   [{:.0f} img/s]'.format(seen / dt))
                 if history is not None:
                     history.write(step, 'train', m, steps=m['steps'], nonfinite_steps=m['nonfinite_steps'])
             t0, seen = time.time(), 0
         elif rank == 0 and (step % args.log_every == 0 or step == steps):
             m = exp.get_metrics_dict(out)
             dt = time.time() - t0
-            print(exp.train_log_str(m, step) + '   [{:.0f} img/s]'.format(seen / dt))
+            if opt.schedule is not None:
+                m['lr/lr'] = opt.current_lr()
+            print(exp.train_log_str(m, step) + lr_suffix(m) + '   [{:.0f} img/s]'.format(seen / dt))
             if history is not None:
                 history.write(step, 'train', m)
             t0, seen = time.time(), 0

@@ -3,6 +3,9 @@
 
 With `ema_decay > 0` the same kernel pass also keeps an exponential moving average of the weights (`self.ema`), the weights a test
 ELBO / importance-weighted bound is normally reported from; `swap_ema()` puts it in the parameters' place for a test pass.
+
+With a `schedule` (LrSchedule) the kernel computes the learning rate itself from the device step counter, so a captured step replays along
+warm-up and decay; `lr_now` holds the rate of the last step.
 """
 import contextlib
 
@@ -20,8 +23,49 @@ def ema_decay_at(decay, n):
     return min(f(decay), (f(1) + n) / (f(10) + n))
 
 
+class LrSchedule:
+    """Linear warm-up over `warmup_steps` steps, then `kind` ('constant', 'cosine', 'linear', 'step', 'exp') over `decay_steps` steps down
+    to `min_lr` (struct lvae_lr_schedule of include/lvae_hip.h has the formulas). The base rate is the optimizer's `lr`."""
+    FIELDS = ('kind', 'warmup_steps', 'decay_steps', 'min_lr', 'gamma')
+
+    def __init__(self, kind='constant', warmup_steps=0, decay_steps=0, min_lr=0.0, gamma=0.1):
+        self.kind, self.warmup_steps, self.decay_steps = str(kind), int(warmup_steps), int(decay_steps)
+        self.min_lr, self.gamma = float(min_lr), float(gamma)
+        if self.kind not in K._C.LR_KINDS:
+            raise ValueError("unknown lr schedule %r (one of %s)" % (kind, ', '.join(K._C.LR_KINDS)))
+        if not self.min_lr >= 0.0:
+            raise ValueError("min_lr must not be negative, got %r" % (min_lr,))
+        if not 0.0 < self.gamma <= 1.0:
+            raise ValueError("gamma must lie in (0, 1], got %r" % (gamma,))
+        if self.warmup_steps < 0:
+            raise ValueError("warmup_steps must not be negative, got %r" % (warmup_steps,))
+        if self.kind != 'constant' and self.decay_steps <= 0:
+            raise ValueError("a %s schedule needs decay_steps > 0, got %r" % (self.kind, decay_steps))
+
+    def struct(self, base_lr):
+        """struct lvae_lr_schedule for this schedule on `base_lr` (checked against it: base_lr > 0, min_lr <= base_lr)."""
+        if not float(base_lr) > 0.0:
+            raise ValueError("a scheduled lr must be positive, got %r" % (base_lr,))
+        if self.min_lr > float(base_lr):
+            raise ValueError("min_lr %r exceeds the base lr %r" % (self.min_lr, base_lr))
+        return K.lr_schedule_struct(base_lr, self.kind, self.warmup_steps, self.decay_steps, self.min_lr, self.gamma)
+
+    def at(self, base_lr, n):
+        """The lr of the step that follows `n` completed ones, as the kernel computes it (lvae_lr_schedule_at: host code, no GPU)."""
+        return K.lr_schedule_at(self.struct(base_lr), n)
+
+    def state_dict(self):
+        return {k: getattr(self, k) for k in self.FIELDS}
+
+    def __eq__(self, other):
+        return isinstance(other, LrSchedule) and self.state_dict() == other.state_dict()
+
+    def __repr__(self):
+        return 'LrSchedule(%s)' % ', '.join('%s=%r' % kv for kv in self.state_dict().items())
+
+
 class Adamax:
-    def __init__(self, model, lr=3e-4, betas=(0.9, 0.999), eps=1e-8, weight_decay=0.0, ema_decay=0.0):
+    def __init__(self, model, lr=3e-4, betas=(0.9, 0.999), eps=1e-8, weight_decay=0.0, ema_decay=0.0, schedule=None):
         self.model = model
         self.lr, self.betas, self.eps, self.weight_decay = float(lr), (float(betas[0]), float(betas[1])), float(eps), float(weight_decay)
         self.ema_decay = float(ema_decay)
@@ -30,6 +74,9 @@ class Adamax:
         self.exp_avg = self.exp_inf = self.step_count = None
         self.ema = None     # float32 [arena.n_train] when ema_decay > 0: the averaged trainable prefix, in the arena's layout
         self.gscale = None  # device float[1]: 1/world_size after a SUM all-reduce
+        self.schedule = schedule   # LrSchedule or None: `lr` itself at every step
+        self._sched = None if schedule is None else schedule.struct(self.lr)
+        self.lr_now = None  # device float[1] with a schedule: the lr the last step applied
         self._arena = None
         self._swapped = False
 
@@ -42,6 +89,8 @@ class Adamax:
             self.step_count = torch.zeros(1, dtype=torch.int64, device=dev)
             if self.ema_decay > 0.0:
                 self.ema = arena.params[:arena.n_train].detach().clone()
+            if self.schedule is not None:
+                self.lr_now = torch.zeros(1, dtype=torch.float32, device=dev)
             self._arena = arena
         return arena
 
@@ -49,6 +98,8 @@ class Adamax:
         self._state().zero_grad()
 
     def step(self):
+        if self.schedule is not None:
+            return self._scheduled_step()
         arena = self._state()
         if self.ema is None:
             K.adamax_step(arena.params[:arena.n_train], arena.grads, self.exp_avg, self.exp_inf, None, self.lr, self.betas[0],
@@ -58,6 +109,15 @@ class Adamax:
                 raise RuntimeError("Adamax.step() inside swap_ema(): the parameters hold the average")
             K.adamax_ema_step(arena.params[:arena.n_train], arena.grads, self.exp_avg, self.exp_inf, None, self.lr, self.betas[0],
                               self.betas[1], self.eps, self.weight_decay, self.gscale, self.step_count, self.ema, self.ema_decay)
+        K.counter_advance(self.step_count, 1)
+
+    def _scheduled_step(self):
+        """step() with the lr of the schedule at the device step counter, with the average or without; the lr applied is left in lr_now."""
+        arena = self._state()
+        if self._swapped:
+            raise RuntimeError("Adamax.step() inside swap_ema(): the parameters hold the average")
+        K.adamax_sched_step(arena.params[:arena.n_train], arena.grads, self.exp_avg, self.exp_inf, None, self._sched, self.betas[0],
+                            self.betas[1], self.eps, self.weight_decay, self.gscale, self.step_count, self.ema, self.ema_decay, self.lr_now)
         K.counter_advance(self.step_count, 1)
 
     @contextlib.contextmanager
@@ -88,7 +148,16 @@ class Adamax:
               'betas': self.betas, 'eps': self.eps, 'weight_decay': self.weight_decay}
         if self.ema is not None:
             sd['ema'], sd['ema_decay'] = self.ema, self.ema_decay
+        sd['schedule'] = None if self.schedule is None else self.schedule.state_dict()
         return sd
+
+    def current_lr(self):
+        """The lr the last step applied: `lr` itself without a schedule, else a device-to-host read of lr_now (0 before this optimizer's
+        first step)."""
+        if self.schedule is None:
+            return self.lr
+        self._state()
+        return float(self.lr_now.item())
 
     def load_state_dict(self, sd):
         self._state()
