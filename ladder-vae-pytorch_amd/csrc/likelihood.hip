@@ -17,14 +17,17 @@ __global__ __launch_bounds__(256) void bernoulli_fwd_kernel(const float* __restr
   const size_t base = (size_t)n * P;
   float acc = 0.f;
   for (int64_t i = threadIdx.x; i < P; i += 256) {
-    const float m = sigmoidf_(logits[base + i]);
+    const float lg = logits[base + i];
+    const float m = sigmoidf_(lg);
     if (mean) mean[base + i] = m;
     if (mode) mode[base + i] = rintf(m);  // torch.round: half to even
     if (sample) sample[base + i] = u[base + i] < m ? 1.f : 0.f;
     if (x) {
       const float xv = x[base + i];
-      // F.binary_cross_entropy clamps each log term at -100
-      const float l1 = fmaxf(logf(m), -100.f), l0 = fmaxf(logf(1.f - m), -100.f);
+      // F.binary_cross_entropy clamps each log term at -100. log(m) = lg - log1p(exp(lg)) is lg itself below -20 (the correction is under 2.1e-9);
+      // taken from m it jumped from -87.3 to the clamp, because the hardware reciprocal in sigmoidf_ returns 0 once 1 / (1 + exp(-lg)) is denormal.
+      // (log(1 - m) reaches the clamp from lg = 17 on, where m rounds to 1, as the fp32 reference's does.)
+      const float l1 = fmaxf(lg < -20.f ? lg : logf(m), -100.f), l0 = fmaxf(logf(1.f - m), -100.f);
       acc += xv * l1 + (1.f - xv) * l0;
       if (dll) {
         // autograd of BCE then sigmoid: -(m - x) / max(m(1-m), 1e-12) * m(1-m)

@@ -374,7 +374,10 @@ __device__ __forceinline__ void philox4(uint64_t ctr, uint32_t stream_id, uint32
   out[0] = c0; out[1] = c1; out[2] = c2; out[3] = c3;
 }
 
-__device__ __forceinline__ float u01(uint32_t r) { return ((r >> 8) + 0.5f) * (1.f / 16777216.f); }  // (0,1)
+// [2^-25, 1 - 2^-24]: (k + 0.5) * 2^-24 for k = r >> 8 < 2^24, in fp32. From k = 2^23 on, k + 0.5 is a tie and rounds to even, which for the
+// one input k = 2^24 - 1 is 2^24, i.e. exactly 1.0 (probability 2^-24 per draw): clamped to the largest float below 1, so that a uniform draw
+// never reaches its upper end and a keep-probability of 1 keeps everything. Every other draw is what it was without the clamp.
+__device__ __forceinline__ float u01(uint32_t r) { return fminf(((r >> 8) + 0.5f) * (1.f / 16777216.f), 0x1.fffffep-1f); }
 
 __global__ __launch_bounds__(256) void rng_fill_kernel(float* __restrict__ out, int64_t n, int kind, float lo, float hi,
                                                         uint64_t seed, const uint64_t* offset, uint64_t stream_id) {
