@@ -162,6 +162,9 @@ int lvae_conv2d_f32(const lvae_conv_desc* d, void* stream);
  * dx2 [N,H,W,Cout - split]. At most 128 reduction and 128 output channels, multiples of 4; otherwise LVAE_EINVAL (use two launches with
  * a weight offset, as lvae_conv2d_f32 allows). */
 int lvae_conv1x1_dgrad_cat_f32(const lvae_conv_desc* d, float* dx2, int32_t split, void* stream);
+/* 1 when lvae_conv1x1_dgrad_cat_f32 takes `d` as given with this split (dx2 assumed 16-byte aligned), 0 when it would return
+ * LVAE_EINVAL. Host only, no launch. */
+int32_t lvae_conv1x1_dgrad_cat_ok(const lvae_conv_desc* d, int32_t split);
 /* Which kernel family lvae_conv2d_f32 runs for `d` as given (workspace and form included): diagnostics for the parity tests and for
  * bench.py's roofline record (which matrix unit issues the FLOPs). */
 enum {
@@ -216,6 +219,13 @@ int lvae_conv1x1_gate_f32(const lvae_conv_desc* d, const float* res, int32_t act
  * lvae_bn_finalize_parts_f32 / lvae_bn_fold, then one row whose first C floats are the pivot (0 rows: not supported for this
  * shape, leave stats_out NULL). */
 int32_t lvae_conv1x1_gate_stats_rows(const lvae_conv_desc* d);
+/* Which kernel lvae_conv1x1_gate_f32 runs for `d` as given (the alignment of the pointers it carries included; res and out assumed
+ * 16-byte aligned): 0 = none, the call would return LVAE_EINVAL — compose lvae_conv2d_f32 + lvae_gate_fwd_f32. Host only, no launch. */
+enum {
+  LVAE_GATE_PERSISTENT = 1, /* persistent kernel of the 64-channel blocks (the only one with bf16 storage) */
+  LVAE_GATE_SINGLE_SHOT = 2 /* single-shot 1x1 kernel with the gate epilogue: Cin <= 128, 2C <= 128 */
+};
+int32_t lvae_conv1x1_gate_variant(const lvae_conv_desc* d);
 /* GateLayer2d backward fused with the dgrad of its 1x1 convolution (autograd of lib/nn.py:118-126): forms
  *   dab[m,c] = dout*sigmoid(b)*act'(a) ; dab[m,C+c] = dout*act(a)*sigmoid(b)*(1-sigmoid(b))      (a, b = the halves of ab)
  * in the kernel's operand staging (also written to `dab` [M,2C] when non-NULL: the weight gradient of the gate convolution
@@ -224,6 +234,9 @@ int32_t lvae_conv1x1_gate_stats_rows(const lvae_conv_desc* d);
  * Same shape limits as lvae_conv1x1_gate_f32, otherwise LVAE_EINVAL (compose lvae_gate_bwd_f32 + lvae_conv2d_f32). */
 int lvae_conv1x1_gate_bwd_f32(const lvae_conv_desc* d, const float* dout, const float* ab, int32_t act, float* dab,
                               void* stream);
+/* 1 when lvae_conv1x1_gate_bwd_f32 takes `d` as given (d->x ignored; dout, ab and dab assumed 16-byte aligned), 0 when it would
+ * return LVAE_EINVAL. Host only, no launch. */
+int32_t lvae_conv1x1_gate_bwd_ok(const lvae_conv_desc* d);
 
 /* GateLayer2d backward of a 64-channel block as ONE persistent kernel: gate derivative + input gradient (exactly
  * lvae_conv1x1_gate_bwd_f32, same descriptor) AND the weight / bias gradient of the gate convolution, dw[ci*dw_sk + co*dw_sn] +=
@@ -254,6 +267,10 @@ typedef struct lvae_bn_apply {
   const float* drop;   /* lvae_conv2d_wgrad_apply_f32 only: Dropout2d mask [N][C] multiplied into the result, or NULL */
 } lvae_bn_apply;
 size_t lvae_conv1x1_gate_bwd_wgrad_workspace(const lvae_conv_desc* d);
+/* 1 when lvae_conv1x1_gate_bwd_wgrad_f32 takes `d` as given with a deferred apply (`ap`): lvae_conv1x1_gate_bwd_wgrad_workspace(d) != 0
+ * and not form LVAE_FORM_F32_MFMA at precision LVAE_PREC_F32. Both queries ignore d->x and assume the operands outside the descriptor
+ * 16-byte aligned. Host only, no launch. */
+int32_t lvae_conv1x1_gate_bwd_wgrad_apply_ok(const lvae_conv_desc* d);
 int lvae_conv1x1_gate_bwd_wgrad_f32(const lvae_conv_desc* d, const float* dout, const float* ab, const float* y, int32_t act,
                                     float* dw, int64_t dw_sk, int64_t dw_sn, float* db, void* workspace, size_t workspace_bytes,
                                     const lvae_bn_apply* ap, void* stream);

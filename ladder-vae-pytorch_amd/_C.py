@@ -16,6 +16,7 @@ GATHER_CONV, GATHER_TRANSPOSED = 0, 1
 PREC_F32, PREC_BF16 = 0, 1
 DT_F32, DT_BF16 = 0, 1
 VARIANT_DIRECT, VARIANT_POS, VARIANT_WINO_F32, VARIANT_WINO_SIX, VARIANT_BF16_DIRECT, VARIANT_SIX_DIRECT = 0, 2, 3, 4, 5, 6
+GATE_PERSISTENT, GATE_SINGLE_SHOT = 1, 2   # lvae_conv1x1_gate_variant (0: none)
 WGRAD_VARIANT_GENERIC, WGRAD_VARIANT_IMG, WGRAD_VARIANT_BF16, WGRAD_VARIANT_WINO, WGRAD_VARIANT_DIRECT_1X1, WGRAD_VARIANT_TILE, WGRAD_VARIANT_THIN = range(7)
 FEED_U8, FEED_F32 = 0, 1
 FORM_AUTO, FORM_F32_MFMA, FORM_SIX_PRODUCT, FORM_SIX_PRODUCT_DIRECT = 0, 1, 2, 3
@@ -91,6 +92,7 @@ SIGNATURES = {
     'lvae_conv2d_f32': (C.c_int, [C.POINTER(ConvDesc), _P]),
     'lvae_conv2d_bf16': (C.c_int, [C.POINTER(ConvDesc), _P]),
     'lvae_conv1x1_dgrad_cat_f32': (C.c_int, [C.POINTER(ConvDesc), _P, _I, _P]),
+    'lvae_conv1x1_dgrad_cat_ok': (_I, [C.POINTER(ConvDesc), _I]),
     'lvae_conv2d_stats_rows': (_I, [C.POINTER(ConvDesc)]),
     'lvae_conv2d_variant': (_I, [C.POINTER(ConvDesc)]),
     'lvae_resblock_bf16_storage': (_I, [C.POINTER(ConvDesc)]),
@@ -101,8 +103,11 @@ SIGNATURES = {
     'lvae_conv2d_prepare_weights': (C.c_int, [_P, _I, _I, _P]),
     'lvae_conv1x1_gate_f32': (C.c_int, [C.POINTER(ConvDesc), _P, _I, _P, _P]),
     'lvae_conv1x1_gate_stats_rows': (_I, [C.POINTER(ConvDesc)]),
+    'lvae_conv1x1_gate_variant': (_I, [C.POINTER(ConvDesc)]),
     'lvae_conv1x1_gate_bwd_f32': (C.c_int, [C.POINTER(ConvDesc), _P, _P, _I, _P, _P]),
+    'lvae_conv1x1_gate_bwd_ok': (_I, [C.POINTER(ConvDesc)]),
     'lvae_conv1x1_gate_bwd_wgrad_workspace': (_Z, [C.POINTER(ConvDesc)]),
+    'lvae_conv1x1_gate_bwd_wgrad_apply_ok': (_I, [C.POINTER(ConvDesc)]),
     'lvae_conv1x1_gate_bwd_wgrad_f32': (C.c_int, [C.POINTER(ConvDesc), _P, _P, _P, _I, _P, _L, _L, _P, _P, _Z, C.POINTER(BnApply), _P]),
     'lvae_resblock_gate_workspace': (_Z, [C.POINTER(ConvDesc)]),
     'lvae_resblock_gate_prepare_entry': (C.c_int, [C.POINTER(ConvDesc), _P]),

@@ -287,46 +287,46 @@ static int pick_bm(const PwArgs& a, hipStream_t s) {
   return launch_pw<64, KT, NT, KC>(a, s);  // measured: 64-pixel tiles (2-3 workgroups per CU overlap load / MFMA / store) beat 128
 }
 
-// eligibility of the single-shot kernel for d and the extra operands of its gate / gate-backward / dgrad-cat forms (null: not that form);
-// nc: n-contiguous weights
-static bool pw_select(const lvae_conv_desc* d, const float* gate_res, const float* gate_out, const float* gb_dout, const float* gb_ab,
-                      const float* gb_dab, const float* y2, int split, bool& nc) {
+// Whether the single-shot kernel takes d in form f: every condition its launch depends on except the alignment of f's own operands,
+// which the entry points check. p.rows: rows of BatchNorm partials the gate-forward epilogue writes (one per 64-pixel workgroup; 0 when a
+// thread would not keep its channel group across rows, 256 % c4n != 0).
+bool conv1x1_plan(const lvae_conv_desc* d, const PwForm& f, ConvPlan& p) {
   const int K = d->C1 + d->C2, N = d->Cout;
+  const bool gate = f.kind == PW_GATE_FWD, gate_bwd = f.kind == PW_GATE_BWD;
   if (d->KH != 1 || d->KW != 1 || d->stride != 1 || d->pad != 0 || d->OH != d->H || d->OW != d->W) return false;
-  if (K > 128 || N > 128 || d->C1 % 4 || d->C2 % 4 || N % 4 || (gate_out && N % 8)) return false;
-  if (gb_dout && (K % 8 || d->C2 != 0 || d->in_scale != nullptr || !al16_or_null(gb_dout) || !al16_or_null(gb_ab) || !al16_or_null(gb_dab))) return false;
-  if (!al16_or_null(d->x) || !al16_or_null(d->x2) || !al16_or_null(d->w) || !al16_or_null(d->y) || !al16_or_null(d->bias) || !al16_or_null(d->in_scale) ||
-      !al16_or_null(d->in_shift) || !al16_or_null(d->out_scale) || !al16_or_null(gate_res) || !al16_or_null(gate_out))
+  if (K > 128 || N <= 0 || N > 128 || d->C1 % 4 || d->C2 % 4 || N % 4 || (gate && N % 8)) return false;
+  if (gate_bwd && (K % 8 || d->C2 != 0 || d->in_scale != nullptr)) return false;
+  if (!(gate_bwd || al16_or_null(d->x)) || !al16_or_null(d->x2) || !al16_or_null(d->w) || !al16_or_null(d->y) || !al16_or_null(d->bias) ||
+      !al16_or_null(d->in_scale) || !al16_or_null(d->in_shift) || !al16_or_null(d->out_scale))
     return false;
   const bool kc = d->w_sk == 1 && d->w_sn % 4 == 0 && K % 4 == 0;
-  nc = d->w_sn == 1 && d->w_sk % 4 == 0;
+  const bool nc = d->w_sn == 1 && d->w_sk % 4 == 0;
   if (!kc && !nc) return false;
-  if (gate_out == nullptr && d->y == nullptr) return false;
-  return y2 == nullptr || (gate_out == nullptr && d->stats_out == nullptr && split > 0 && split < N && split % 4 == 0 && al16_or_null(y2));
+  if (!gate && d->y == nullptr) return false;
+  if (f.kind == PW_DGRAD_CAT && (d->stats_out != nullptr || f.split <= 0 || f.split >= N || f.split % 4)) return false;
+  p = ConvPlan{};
+  if (gate && 256 % (N / 8) == 0) p.rows = (int32_t)(((int64_t)d->N * d->H * d->W + 63) / 64);
+  return true;
 }
 
-// -1000: not eligible (the gate / dgrad-cat callers then report it)
-static int conv1x1_try_all(const lvae_conv_desc* d, const float* gate_res, float* gate_out, int gate_act, const float* gb_dout,
-                           const float* gb_ab, float* gb_dab, int gb_act, hipStream_t s, float* y2, int split) {
-  bool nc;
-  if (!pw_select(d, gate_res, gate_out, gb_dout, gb_ab, gb_dab, y2, split, nc)) return -1000;
+int conv1x1_launch(const lvae_conv_desc* d, const PwForm& f, hipStream_t s) {
   const int K = d->C1 + d->C2, N = d->Cout;
   PwArgs a;
   a.d = *d;
   a.M = d->N * d->H * d->W;
   a.K = K;
   a.ohw = d->H * d->W;
-  a.gate_res = gate_res;
-  a.gate_out = gate_out;
-  a.gate_act = gate_act;
-  a.gb_dout = gb_dout;
-  a.gb_ab = gb_ab;
-  a.gb_dab = gb_dab;
-  a.gb_act = gb_act;
-  a.y2 = y2;
-  a.split = split;
+  a.gate_res = f.res;
+  a.gate_out = f.out;
+  a.gate_act = f.kind == PW_GATE_FWD ? f.act : 0;
+  a.gb_dout = f.dout;
+  a.gb_ab = f.ab;
+  a.gb_dab = f.dab;
+  a.gb_act = f.kind == PW_GATE_BWD ? f.act : 0;
+  a.y2 = f.y2;
+  a.split = f.split;
   const bool k64 = K <= 64, n64 = N <= 64;
-  if (nc) {
+  if (d->w_sn == 1) {  // n-contiguous weights
     if (k64) return n64 ? pick_bm<64, 64, false>(a, s) : pick_bm<64, 128, false>(a, s);
     return n64 ? pick_bm<128, 64, false>(a, s) : pick_bm<128, 128, false>(a, s);
   }
@@ -334,88 +334,121 @@ static int conv1x1_try_all(const lvae_conv_desc* d, const float* gate_res, float
   return n64 ? pick_bm<128, 64, true>(a, s) : pick_bm<128, 128, true>(a, s);
 }
 
-// plain 1x1 convolution (the route of lvae_conv2d_f32): plan, then a launch that cannot decline
-bool conv1x1_plan(const lvae_conv_desc* d) {
-  bool nc;
-  return pw_select(d, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, 0, nc);
+// The kernel of lvae_conv1x1_gate_f32 for d, chosen once: persistent, then single-shot, then none (0). Every gate-forward query and the
+// launch read this; p.rows: rows of statistics partials.
+static int32_t gate_fwd_route(const lvae_conv_desc* d, ConvPlan& p) {
+  PwForm f;
+  f.kind = PW_GATE_FWD;
+  p = ConvPlan{};
+  if (d == nullptr) return 0;
+  if (conv1x1_gate_fwd_plan(d, p)) return LVAE_GATE_PERSISTENT;
+  if (d->x_dtype == LVAE_DT_F32 && d->y_dtype == LVAE_DT_F32 && conv1x1_plan(d, f, p)) return LVAE_GATE_SINGLE_SHOT;
+  return 0;
 }
 
-int conv1x1_launch(const lvae_conv_desc* d, hipStream_t s) {
-  return conv1x1_try_all(d, nullptr, nullptr, 0, nullptr, nullptr, nullptr, 0, s, nullptr, 0);
+// the single-shot gate backward + dgrad; d->x is ignored (the A operand is computed, not loaded)
+static bool gate_bwd_plan(const lvae_conv_desc* d) {
+  PwForm f;
+  f.kind = PW_GATE_BWD;
+  ConvPlan p;
+  return d != nullptr && conv1x1_plan(d, f, p);
 }
 
-static int conv1x1_try_ex(const lvae_conv_desc* d, const float* gate_res, float* gate_out, int gate_act, const float* gb_dout,
-                   const float* gb_ab, float* gb_dab, int gb_act, hipStream_t s) {
-  return conv1x1_try_all(d, gate_res, gate_out, gate_act, gb_dout, gb_ab, gb_dab, gb_act, s, nullptr, 0);
-}
-
-static int conv1x1_try(const lvae_conv_desc* d, const float* gate_res, float* gate_out, int gate_act, hipStream_t s) {
-  return conv1x1_try_all(d, gate_res, gate_out, gate_act, nullptr, nullptr, nullptr, 0, s, nullptr, 0);
+static bool dgrad_cat_plan(const lvae_conv_desc* d, int split) {
+  PwForm f;
+  f.kind = PW_DGRAD_CAT;
+  f.split = split;
+  ConvPlan p;
+  return d != nullptr && d->x2 == nullptr && d->x_dtype == LVAE_DT_F32 && d->y_dtype == LVAE_DT_F32 && conv1x1_plan(d, f, p);
 }
 
 }  // namespace lvae
 
 using namespace lvae;
 
+#define PW_REQUIRE_AL16(who, p) LVAE_REQUIRE(al16_or_null(p), LVAE_EALIGN, who ": " #p " must be 16-byte aligned")
+
+extern "C" int32_t lvae_conv1x1_dgrad_cat_ok(const lvae_conv_desc* d, int32_t split) { return dgrad_cat_plan(d, split) ? 1 : 0; }
+
 extern "C" int lvae_conv1x1_dgrad_cat_f32(const lvae_conv_desc* d, float* dx2, int32_t split, void* stream) {
   int rc = conv_desc_check(d, "lvae_conv1x1_dgrad_cat_f32");
   if (rc) return rc;
-  LVAE_REQUIRE(d->y != nullptr && dx2 != nullptr && split > 0 && split < d->Cout && split % 4 == 0 && d->stats_out == nullptr && d->x2 == nullptr,
-               LVAE_EINVAL, "lvae_conv1x1_dgrad_cat_f32: needs y, dx2, 0 < split < Cout (a multiple of 4), no statistics epilogue, one input tensor");
-  LVAE_REQUIRE(d->x_dtype == LVAE_DT_F32 && d->y_dtype == LVAE_DT_F32, LVAE_EINVAL, "lvae_conv1x1_dgrad_cat_f32: fp32 tensors only");
-  rc = conv1x1_try_all(d, nullptr, nullptr, 0, nullptr, nullptr, nullptr, 0, (hipStream_t)stream, dx2, split);
-  LVAE_REQUIRE(rc != -1000, LVAE_EINVAL,
-               "lvae_conv1x1_dgrad_cat_f32: shape not supported (1x1, stride 1, at most 128 reduction and 128 output channels, multiples of 4, "
-               "16-byte aligned tensors, unit weight stride along one axis): use two lvae_conv2d_f32 launches");
-  return rc;
+  LVAE_REQUIRE(dx2 != nullptr, LVAE_EINVAL, "lvae_conv1x1_dgrad_cat_f32: null dx2");
+  LVAE_REQUIRE(dgrad_cat_plan(d, split), LVAE_EINVAL,
+               "lvae_conv1x1_dgrad_cat_f32: not supported (needs y, 0 < split < Cout (a multiple of 4), no statistics epilogue, one fp32 input "
+               "tensor; 1x1, stride 1, at most 128 reduction and 128 output channels, multiples of 4, 16-byte aligned tensors, unit weight "
+               "stride along one axis): use two lvae_conv2d_f32 launches");
+  PW_REQUIRE_AL16("lvae_conv1x1_dgrad_cat_f32", dx2);
+  PwForm f;
+  f.kind = PW_DGRAD_CAT;
+  f.y2 = dx2;
+  f.split = split;
+  return conv1x1_launch(d, f, (hipStream_t)stream);
 }
 
 // GateLayer2d forward fused with its 1x1 convolution and the residual add (lib/nn.py:118-126, 99):
 //   ab = conv1x1(T(x)) + bias  (written to d->y when non-null; needed by the backward)
 //   out[m, c] = act(ab[m, c]) * sigmoid(ab[m, C + c]) + res[m, c]
+extern "C" int32_t lvae_conv1x1_gate_variant(const lvae_conv_desc* d) {
+  ConvPlan p;
+  return gate_fwd_route(d, p);
+}
+
 // rows of BatchNorm partials ([rows][2][C], C = Cout/2) lvae_conv1x1_gate_f32 writes for its `out` when d->stats_out is set
 extern "C" int32_t lvae_conv1x1_gate_stats_rows(const lvae_conv_desc* d) {
-  if (d == nullptr || d->Cout % 8 != 0) return 0;
-  const int persistent = conv1x1_gate_fwd_wgs(d);  // one row per workgroup of the persistent kernel (conv1x1_gate_fwd.hip)
-  if (persistent) return persistent;
-  const int c4n = d->Cout / 8;
-  if (c4n <= 0 || 256 % c4n != 0 || d->Cout > 128) return 0;
-  return (int32_t)(((int64_t)d->N * d->H * d->W + 63) / 64);  // 64-pixel tiles
+  ConvPlan p;
+  gate_fwd_route(d, p);
+  return p.rows;
 }
 
 extern "C" int lvae_conv1x1_gate_f32(const lvae_conv_desc* d, const float* res, int32_t act, float* out, void* stream) {
   int rc = conv_desc_check(d, "lvae_conv1x1_gate_f32");
   if (rc) return rc;
   LVAE_REQUIRE(out != nullptr, LVAE_EINVAL, "lvae_conv1x1_gate_f32: null out");
-  LVAE_REQUIRE(d->Cout % 2 == 0, LVAE_EINVAL, "lvae_conv1x1_gate_f32: Cout must be 2*C");
-  LVAE_REQUIRE(d->stats_out == nullptr || (d->stats_pivot != nullptr && lvae_conv1x1_gate_stats_rows(d) > 0 &&
-                                           (reinterpret_cast<uintptr_t>(d->stats_pivot) & 15) == 0),
-               LVAE_EINVAL, "lvae_conv1x1_gate_f32: stats_out set but lvae_conv1x1_gate_stats_rows(d) == 0");
-  rc = conv1x1_gate_fwd_try(d, res, out, act, (hipStream_t)stream);
-  LVAE_REQUIRE(rc != -1000 || (d->x_dtype == LVAE_DT_F32 && d->y_dtype == LVAE_DT_F32), LVAE_EINVAL,
+  ConvPlan p;
+  const int32_t variant = gate_fwd_route(d, p);
+  LVAE_REQUIRE(variant != 0 || (d->x_dtype == LVAE_DT_F32 && d->y_dtype == LVAE_DT_F32), LVAE_EINVAL,
                "lvae_conv1x1_gate_f32: bf16-stored x / ab need the persistent 64-channel kernel with precision LVAE_PREC_BF16");
-  if (rc == -1000) rc = conv1x1_try(d, res, out, act, (hipStream_t)stream);
-  LVAE_REQUIRE(rc != -1000, LVAE_EINVAL,
-               "lvae_conv1x1_gate_f32: unsupported shape (needs a 1x1 stride-1 conv, Cin <= 128, Cout <= 128, channels %% 4 == 0, "
+  LVAE_REQUIRE(variant != 0, LVAE_EINVAL,
+               "lvae_conv1x1_gate_f32: unsupported shape (needs a 1x1 stride-1 conv, Cin <= 128, Cout = 2C <= 128, channels %% 4 == 0, "
                "16-byte aligned buffers); use lvae_conv2d_f32 + lvae_gate_fwd_f32");
-  return rc;
+  LVAE_REQUIRE(d->stats_out == nullptr || (d->stats_pivot != nullptr && p.rows > 0 && al16(d->stats_pivot)), LVAE_EINVAL,
+               "lvae_conv1x1_gate_f32: stats_out set but lvae_conv1x1_gate_stats_rows(d) == 0");
+  if (variant == LVAE_GATE_PERSISTENT) return conv1x1_gate_fwd_launch(d, p, res, out, act, (hipStream_t)stream);
+  PW_REQUIRE_AL16("lvae_conv1x1_gate_f32", res);
+  PW_REQUIRE_AL16("lvae_conv1x1_gate_f32", out);
+  PwForm f;
+  f.kind = PW_GATE_FWD;
+  f.act = act;
+  f.res = res;
+  f.out = out;
+  return conv1x1_launch(d, f, (hipStream_t)stream);
 }
 
 // GateLayer2d backward fused with the dgrad of its 1x1 convolution: dab (the gradient w.r.t. the pre-activations ab, also
 // written to `dab` for the weight-gradient call) is formed in the kernel's operand staging from dout and ab, then
 // dx = dab . W^T with the descriptor's epilogue (out_scale = Dropout2d mask of the producer). `d` describes that dgrad:
 // C1 = 2C, Cout = channels of the gate convolution's input, d->x is ignored.
+extern "C" int32_t lvae_conv1x1_gate_bwd_ok(const lvae_conv_desc* d) { return gate_bwd_plan(d) ? 1 : 0; }
+
 extern "C" int lvae_conv1x1_gate_bwd_f32(const lvae_conv_desc* d, const float* dout, const float* ab, int32_t act, float* dab,
                                          void* stream) {
   LVAE_REQUIRE(d && dout && ab && d->y, LVAE_EINVAL, "lvae_conv1x1_gate_bwd_f32: null pointer");
   lvae_conv_desc dd = *d;
-  dd.x = ab;  // any valid, aligned device pointer: the A operand is computed, not loaded
+  dd.x = ab;  // any valid device pointer: the A operand is computed, not loaded
   int rc = conv_desc_check(&dd, "lvae_conv1x1_gate_bwd_f32");
   if (rc) return rc;
-  LVAE_REQUIRE(dd.C1 % 8 == 0 && dd.C2 == 0, LVAE_EINVAL, "lvae_conv1x1_gate_bwd_f32: C1 must be 2C");
-  rc = conv1x1_try_ex(&dd, nullptr, nullptr, 0, dout, ab, dab, act, (hipStream_t)stream);
-  LVAE_REQUIRE(rc != -1000, LVAE_EINVAL,
-               "lvae_conv1x1_gate_bwd_f32: unsupported shape (needs a 1x1 stride-1 conv, 2C <= 128, Cout <= 128, 16-byte aligned "
+  LVAE_REQUIRE(gate_bwd_plan(&dd), LVAE_EINVAL,
+               "lvae_conv1x1_gate_bwd_f32: unsupported shape (needs a 1x1 stride-1 conv, C1 = 2C <= 128, Cout <= 128, 16-byte aligned "
                "buffers); use lvae_gate_bwd_f32 + lvae_conv2d_f32");
-  return rc;
+  PW_REQUIRE_AL16("lvae_conv1x1_gate_bwd_f32", dout);
+  PW_REQUIRE_AL16("lvae_conv1x1_gate_bwd_f32", ab);
+  PW_REQUIRE_AL16("lvae_conv1x1_gate_bwd_f32", dab);
+  PwForm f;
+  f.kind = PW_GATE_BWD;
+  f.act = act;
+  f.dout = dout;
+  f.ab = ab;
+  f.dab = dab;
+  return conv1x1_launch(&dd, f, (hipStream_t)stream);
 }

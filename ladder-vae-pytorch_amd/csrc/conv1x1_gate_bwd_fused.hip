@@ -559,25 +559,44 @@ static int gbf_nwg(int64_t M) {
 }
 
 // `d` describes the dgrad of the gate convolution exactly as for lvae_conv1x1_gate_bwd_f32 (C1 = 2C = 128, Cout = C = 64, weight
-// strides of the transposed view, y = dx, out_scale = dropout mask). 0 when this kernel does not take the shape.
-size_t conv1x1_gate_bwd_fused_workspace(const lvae_conv_desc* d) {
+// strides of the transposed view, y = dx, out_scale = dropout mask; d->x is ignored). False when this kernel does not take it;
+// p.workspace: bytes of its weight-gradient slabs. with_apply: dout comes from a deferred lvae_bn_apply. The operands the descriptor
+// does not carry are assumed 16-byte aligned.
+bool conv1x1_gate_bwd_fused_plan(const lvae_conv_desc* d, bool with_apply, ConvPlan& p) {
   static const bool off = tune("LVAE_DISABLE_GATE_FUSED", 0) != 0;  // A/B switch (tuning builds only)
-  if (off || d == nullptr) return 0;
-  if (d->KH != 1 || d->KW != 1 || d->stride != 1 || d->pad != 0 || d->OH != d->H || d->OW != d->W) return 0;
-  if (d->C1 != 128 || d->C2 != 0 || d->Cout != 64 || d->w_sk != 1 || d->w_sn % 4 != 0 || d->in_scale != nullptr) return 0;
+  if (off || d == nullptr) return false;
+  if (d->KH != 1 || d->KW != 1 || d->stride != 1 || d->pad != 0 || d->OH != d->H || d->OW != d->W) return false;
+  if (d->C1 != 128 || d->C2 != 0 || d->Cout != 64 || d->w_sk != 1 || d->w_sn % 4 != 0 || d->in_scale != nullptr) return false;
+  if (!al16_or_null(d->w) || !al16_or_null(d->y) || !al16_or_null(d->out_scale)) return false;
+  const bool bf16 = d->precision == LVAE_PREC_BF16;
+  if ((d->x_dtype == LVAE_DT_BF16 || d->y_dtype == LVAE_DT_BF16) && !bf16) return false;  // bf16 storage exists in the bf16-operand kernel only
+  if (with_apply && d->form == LVAE_FORM_F32_MFMA && !bf16) return false;  // the deferred apply exists in the bf16-matrix-pipe kernels only
   const int64_t M = (int64_t)d->N * d->H * d->W;
   static const int64_t min_m = tune("LVAE_GATE_FUSED_MIN_M", 256 * 64);
-  if (M < min_m || M >= ((int64_t)1 << 31)) return 0;
-  return (size_t)gbf_nwg(M) * (64 * 128 + 128) * sizeof(float);
+  if (M < min_m || M >= ((int64_t)1 << 31)) return false;
+  p = ConvPlan{};
+  p.workspace = (size_t)gbf_nwg(M) * (64 * 128 + 128) * sizeof(float);
+  return true;
 }
 
-static int conv1x1_gate_bwd_fused(const lvae_conv_desc* d, const float* dout, const float* ab, const float* y, int act, float* dw,
-                           int64_t dw_sk, int64_t dw_sn, float* db, void* workspace, const lvae_bn_apply* ap, hipStream_t s) {
-  if (!al16_or_null(dout) || !al16_or_null(ab) || !al16_or_null(y) || !al16_or_null(d->w) || !al16_or_null(d->y) || !al16_or_null(d->out_scale) || !al16_or_null(workspace)) return -1000;
+#define GBF_REQUIRE_AL16(p) LVAE_REQUIRE(al16_or_null(p), LVAE_EALIGN, "lvae_conv1x1_gate_bwd_wgrad_f32: " #p " must be 16-byte aligned")
+
+// runs the planned kernel; checks only the alignment of the operands the plan cannot see
+static int conv1x1_gate_bwd_fused_launch(const lvae_conv_desc* d, const float* dout, const float* ab, const float* y, int act, float* dw,
+                                         int64_t dw_sk, int64_t dw_sn, float* db, void* workspace, const lvae_bn_apply* ap, hipStream_t s) {
+  GBF_REQUIRE_AL16(dout);
+  GBF_REQUIRE_AL16(ab);
+  GBF_REQUIRE_AL16(y);
+  GBF_REQUIRE_AL16(workspace);
   GbfArgs a;
   a.ap = lvae_bn_apply{};
   if (ap != nullptr && ap->parts != nullptr) {
-    if (!al16_or_null(ap->parts) || !al16_or_null(ap->coef) || !al16_or_null(ap->dh) || !al16_or_null(ap->x) || !al16_or_null(ap->add) || !al16_or_null(ap->out)) return -1000;
+    GBF_REQUIRE_AL16(ap->parts);
+    GBF_REQUIRE_AL16(ap->coef);
+    GBF_REQUIRE_AL16(ap->dh);
+    GBF_REQUIRE_AL16(ap->x);
+    GBF_REQUIRE_AL16(ap->add);
+    GBF_REQUIRE_AL16(ap->out);
     a.ap = *ap;
   }
   a.dout = dout;
@@ -593,17 +612,12 @@ static int conv1x1_gate_bwd_fused(const lvae_conv_desc* d, const float* dout, co
   a.act = act;
   a.in_bf16 = d->x_dtype == LVAE_DT_BF16;
   a.dx_bf16 = d->y_dtype == LVAE_DT_BF16;
-  if ((a.in_bf16 || a.dx_bf16) && d->precision != LVAE_PREC_BF16) return -1000;  // bf16 storage exists in the bf16-operand kernel only
   const int nwg = gbf_nwg(a.M);
   a.slab_w = static_cast<float*>(workspace);
   a.slab_b = db ? a.slab_w + (size_t)nwg * 64 * 128 : nullptr;
   constexpr size_t lds = (size_t)(2 * 64 * GB_LDA + 64 * GB_LDY) * sizeof(float);
   const bool f32_mfma = d->form == LVAE_FORM_F32_MFMA;  // default for fp32: the six-product form on the bf16 MFMA
   const bool with_ap = a.ap.parts != nullptr;
-  if (with_ap && (f32_mfma && d->precision != LVAE_PREC_BF16)) {
-    set_error("conv1x1_gate_bwd_fused: the deferred BatchNorm-backward apply exists in the bf16-matrix-pipe kernels only (not with LVAE_FORM_F32_MFMA)");
-    return LVAE_EINVAL;
-  }
   const bool elu = act == LVAE_ACT_ELU && (!with_ap || a.ap.act == LVAE_ACT_ELU);
   const char* name = "conv1x1_gate_bwd_fused";
   const dim3 grid(nwg), block(512);
@@ -640,7 +654,15 @@ static int conv1x1_gate_bwd_fused(const lvae_conv_desc* d, const float* dout, co
 
 using namespace lvae;
 
-extern "C" size_t lvae_conv1x1_gate_bwd_wgrad_workspace(const lvae_conv_desc* d) { return conv1x1_gate_bwd_fused_workspace(d); }
+extern "C" size_t lvae_conv1x1_gate_bwd_wgrad_workspace(const lvae_conv_desc* d) {
+  ConvPlan p;
+  return conv1x1_gate_bwd_fused_plan(d, false, p) ? p.workspace : 0;
+}
+
+extern "C" int32_t lvae_conv1x1_gate_bwd_wgrad_apply_ok(const lvae_conv_desc* d) {
+  ConvPlan p;
+  return conv1x1_gate_bwd_fused_plan(d, true, p) ? 1 : 0;
+}
 
 extern "C" int lvae_conv1x1_gate_bwd_wgrad_f32(const lvae_conv_desc* d, const float* dout, const float* ab, const float* y, int32_t act,
                                                float* dw, int64_t dw_sk, int64_t dw_sn, float* db, void* workspace,
@@ -650,12 +672,11 @@ extern "C" int lvae_conv1x1_gate_bwd_wgrad_f32(const lvae_conv_desc* d, const fl
   if (with_ap)
     LVAE_REQUIRE(ap->rows > 0 && ap->M == (int64_t)d->N * d->H * d->W && ap->coef && ap->dh && ap->x && ap->out, LVAE_EINVAL,
                  "lvae_conv1x1_gate_bwd_wgrad_f32: deferred apply needs parts / rows, M = N*H*W, the coefficient block, dh, x and out");
-  const size_t need = conv1x1_gate_bwd_fused_workspace(d);
-  LVAE_REQUIRE(need > 0, LVAE_EINVAL,
-               "lvae_conv1x1_gate_bwd_wgrad_f32: unsupported shape (needs the gate of a 64-channel block: 1x1, 128 -> 64 dgrad view, at "
-               "least 16384 pixels); use lvae_conv1x1_gate_bwd_f32 + lvae_conv2d_wgrad_f32");
-  LVAE_REQUIRE(workspace_bytes >= need, LVAE_EWORKSPACE, "lvae_conv1x1_gate_bwd_wgrad_f32: workspace %zu < %zu", workspace_bytes, need);
-  const int rc = conv1x1_gate_bwd_fused(d, dout, ab, y, act, dw, dw_sk, dw_sn, db, workspace, ap, (hipStream_t)stream);
-  LVAE_REQUIRE(rc != -1000, LVAE_EALIGN, "lvae_conv1x1_gate_bwd_wgrad_f32: buffers must be 16-byte aligned");
-  return rc;
+  ConvPlan p;
+  LVAE_REQUIRE(conv1x1_gate_bwd_fused_plan(d, with_ap, p), LVAE_EINVAL,
+               "lvae_conv1x1_gate_bwd_wgrad_f32: not supported (needs the gate of a 64-channel block: 1x1, 128 -> 64 dgrad view, at least 16384 "
+               "pixels, 16-byte aligned w / y / out_scale, bf16 storage only with precision LVAE_PREC_BF16, a deferred apply not with "
+               "LVAE_FORM_F32_MFMA); use lvae_conv1x1_gate_bwd_f32 + lvae_conv2d_wgrad_f32");
+  LVAE_REQUIRE(workspace_bytes >= p.workspace, LVAE_EWORKSPACE, "lvae_conv1x1_gate_bwd_wgrad_f32: workspace %zu < %zu", workspace_bytes, p.workspace);
+  return conv1x1_gate_bwd_fused_launch(d, dout, ab, y, act, dw, dw_sk, dw_sn, db, workspace, ap, (hipStream_t)stream);
 }

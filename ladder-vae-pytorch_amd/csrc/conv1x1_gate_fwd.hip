@@ -309,27 +309,31 @@ __global__ __launch_bounds__(256, 2) void conv1x1_gate_fwd_kernel(GateFwdArgs a)
   }
 }
 
-// workgroups the persistent kernel runs for this descriptor (== rows of BatchNorm partials it writes); 0: not this kernel
-int conv1x1_gate_fwd_wgs(const lvae_conv_desc* d) {
+// Whether the persistent kernel takes d; p.rows: the workgroups it runs (== rows of BatchNorm partials it writes). res and out, which the
+// descriptor does not carry, are assumed 16-byte aligned.
+bool conv1x1_gate_fwd_plan(const lvae_conv_desc* d, ConvPlan& p) {
   static const bool off = tune("LVAE_DISABLE_GATE_FWD_PERSISTENT", 0) != 0;  // A/B switch (tuning builds only)
   static const int max_wgs = (int)tune("LVAE_GATE_FWD_WGS", 512);
   static const int64_t min_m = tune("LVAE_GATE_FWD_MIN_M", 0);
-  if (off || d == nullptr) return 0;
-  if (d->KH != 1 || d->KW != 1 || d->stride != 1 || d->pad != 0 || d->OH != d->H || d->OW != d->W || d->gather != LVAE_GATHER_CONV) return 0;
-  if (d->C1 != 64 || d->C2 != 0 || d->x2 != nullptr || d->Cout != 128) return 0;
-  if (d->in_scale != nullptr || d->in_fold != nullptr || d->out_scale != nullptr || d->out_act != LVAE_ACT_NONE) return 0;
-  if (d->x == nullptr || (reinterpret_cast<uintptr_t>(d->x) & 15) != 0) return 0;
+  if (off || d == nullptr) return false;
+  if (d->KH != 1 || d->KW != 1 || d->stride != 1 || d->pad != 0 || d->OH != d->H || d->OW != d->W || d->gather != LVAE_GATHER_CONV) return false;
+  if (d->C1 != 64 || d->C2 != 0 || d->x2 != nullptr || d->Cout != 128) return false;
+  if (d->in_scale != nullptr || d->in_fold != nullptr || d->out_scale != nullptr || d->out_act != LVAE_ACT_NONE) return false;
+  if (d->x == nullptr || !al16(d->x)) return false;
+  // bf16 storage of x / ab: the bf16-operand form only, and it moves 16-byte pieces
+  if ((d->x_dtype == LVAE_DT_BF16 || d->y_dtype == LVAE_DT_BF16) &&
+      (d->precision != LVAE_PREC_BF16 || !al16_or_null(d->y) || !al16_or_null(d->stats_pivot)))
+    return false;
   const int64_t M = (int64_t)d->N * d->H * d->W;
-  if (M < min_m || M >= ((int64_t)1 << 31) - 64) return 0;
+  if (M < min_m || M >= ((int64_t)1 << 31) - 64) return false;
   const int64_t tiles = (M + GF_BM - 1) / GF_BM;
   const int cap = max_wgs > 0 ? max_wgs : 512;
-  return (int)(tiles < cap ? tiles : cap);
+  p = ConvPlan{};
+  p.rows = (int32_t)(tiles < cap ? tiles : cap);
+  return true;
 }
 
-// -1000: not eligible (the caller uses conv1x1_kernel)
-int conv1x1_gate_fwd_try(const lvae_conv_desc* d, const float* res, float* out, int act, hipStream_t s) {
-  const int wgs = conv1x1_gate_fwd_wgs(d);
-  if (wgs == 0 || out == nullptr) return -1000;
+int conv1x1_gate_fwd_launch(const lvae_conv_desc* d, const ConvPlan& p, const float* res, float* out, int act, hipStream_t s) {
   GateFwdArgs a;
   a.x = d->x;
   a.w = d->w;
@@ -351,8 +355,8 @@ int conv1x1_gate_fwd_try(const lvae_conv_desc* d, const float* res, float* out, 
                     reinterpret_cast<uintptr_t>(d->stats_pivot)) & 15) == 0;
   // fp32: on the fp32 MFMA by default (the kernel is HBM-bound: the six-product form measured the same); d->form = LVAE_FORM_SIX_PRODUCT asks for it
   const int split = d->precision == LVAE_PREC_BF16 ? 1 : (d->form == LVAE_FORM_SIX_PRODUCT ? 3 : 0);
-  const dim3 grid(wgs), block(256);
-  if ((a.x_bf16 || a.y_bf16) && !(split == 1 && al)) return -1000;  // bf16 storage: bf16-operand form, aligned buffers
+  const dim3 grid(p.rows), block(256);
+  LVAE_REQUIRE(al || !(a.x_bf16 || a.y_bf16), LVAE_EALIGN, "conv1x1_gate_fwd: res and out must be 16-byte aligned with bf16-stored x / ab");
   if ((wt || a.x_bf16 || a.y_bf16) && al) {
     if (split == 1 && a.x_bf16 && (a.y_bf16 || a.y == nullptr)) hipLaunchKernelGGL((conv1x1_gate_fwd_kernel<true, 1, true>), grid, block, 0, s, a);
     else if (split == 1) hipLaunchKernelGGL((conv1x1_gate_fwd_kernel<true, 1>), grid, block, 0, s, a);

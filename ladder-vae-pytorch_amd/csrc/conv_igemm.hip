@@ -364,7 +364,7 @@ static ConvRoute conv_route(const lvae_conv_desc* d, bool assume_ws = false) {
   else if (conv3x3_bf16_plan(&t, assume_ws, r.plan)) r.kind = ROUTE_BF16;
   else if (conv3x3_wino_plan(&t, assume_ws, r.plan)) r.kind = ROUTE_WINO;
   else if (conv3x3_halo_plan(&t, r.plan)) r.kind = ROUTE_HALO;
-  else if (conv1x1_plan(&t)) r.kind = ROUTE_1X1;
+  else if (conv1x1_plan(&t, PwForm{}, r.plan)) r.kind = ROUTE_1X1;
   return r;
 }
 
@@ -389,10 +389,10 @@ extern "C" int32_t lvae_resblock_bf16_storage(const lvae_conv_desc* d) {
   if (conv3x3_wgrad_bf16_workspace(d) == 0) return 0;
   lvae_conv_desc g = *d;  // the block's GateLayer2d: 1x1, 64 -> 128 forward; its fused backward is described by the 128 -> 64 dgrad view
   g.KH = g.KW = 1; g.pad = 0; g.Cout = 128; g.in_scale = g.in_shift = nullptr; g.out_scale = nullptr; g.in_act = g.out_act = 0; g.in_fold = nullptr;
-  if (conv1x1_gate_fwd_wgs(&g) == 0) return 0;
+  ConvPlan gp;
+  if (!conv1x1_gate_fwd_plan(&g, gp)) return 0;
   g.C1 = 128; g.Cout = 64; g.w_sk = 1; g.w_sn = 128;
-  if (conv1x1_gate_bwd_fused_workspace(&g) == 0) return 0;
-  return 1;
+  return conv1x1_gate_bwd_fused_plan(&g, false, gp) ? 1 : 0;
 }
 
 extern "C" int32_t lvae_conv2d_stats_rows(const lvae_conv_desc* d) { return d ? conv_route(d).plan.rows : 0; }
@@ -431,7 +431,7 @@ extern "C" int lvae_conv2d_f32(const lvae_conv_desc* d, void* stream) {
     case ROUTE_BF16: return conv3x3_bf16_launch(d, r.plan, s);
     case ROUTE_WINO: return conv3x3_wino_launch(d, s);
     case ROUTE_HALO: return conv3x3_halo_launch(d, s);
-    case ROUTE_1X1: return conv1x1_launch(d, s);
+    case ROUTE_1X1: return conv1x1_launch(d, PwForm{}, s);
   }
   ConvArgs a;
   a.d = *d;

@@ -8,12 +8,13 @@ namespace lvae {
 
 // One forward / dgrad kernel family's accepted choice for a convolution descriptor. A family's *_plan() fills it and returns false
 // when the family does not take the descriptor (every condition its launch depends on: buffer alignment, workspace, tile, LDS);
-// its *_launch() runs exactly that choice and can no longer decline. The route of lvae_conv2d_* (conv_igemm.hip) walks the plans once.
+// its *_launch() runs exactly that choice and can no longer decline. The route of lvae_conv2d_* (conv_igemm.hip) walks the plans once;
+// the 1x1 gate / concat-dgrad entry points (conv1x1.hip, conv1x1_gate_bwd_fused.hip) and their queries ask theirs the same way.
 struct ConvPlan {
   int32_t variant = LVAE_VARIANT_DIRECT;  // LVAE_VARIANT_*
   int32_t rows = 0;                       // rows of statistics partials the launch writes (0: no statistics epilogue)
   bool folds = false;                     // folds the BatchNorm finalize of its input (lvae_bn_fold)
-  size_t workspace = 0;                   // bytes of d->workspace the launch reads (pre-transformed weights)
+  size_t workspace = 0;                   // bytes of workspace the launch needs (pre-transformed weights, weight-gradient slabs)
 };
 
 // One problem of the grouped fixed-order slab reduce (wgrad_reduce_grouped_launch): ksplit slabs of [ntaps][Cin][Cout] (+ [Cout])
@@ -59,16 +60,29 @@ int resblock_gate_prepare_single(const lvae_conv_desc* d, int planes, hipStream_
 size_t conv3x3_wgrad_bf16_workspace(const lvae_conv_desc* d);
 int conv3x3_wgrad_bf16_launch(const lvae_conv_desc* d, const float* dy, float* dw, float* db, void* workspace, hipStream_t s);
 
-// conv1x1.hip
-bool conv1x1_plan(const lvae_conv_desc* d);
-int conv1x1_launch(const lvae_conv_desc* d, hipStream_t s);
+// conv1x1.hip: the single-shot kernel. PwForm says which form of it a launch is and carries that form's operands outside the descriptor
+// (the plan reads kind and split only: it assumes those operands 16-byte aligned, the entry points check them).
+enum { PW_PLAIN, PW_GATE_FWD, PW_GATE_BWD, PW_DGRAD_CAT };
+struct PwForm {
+  int kind = PW_PLAIN;
+  int act = 0;                               // PW_GATE_FWD / PW_GATE_BWD: LVAE_ACT_* of the gate
+  const float* res = nullptr;                // PW_GATE_FWD: residual [M][C] or null, out [M][C]
+  float* out = nullptr;
+  const float* dout = nullptr;               // PW_GATE_BWD: dout [M][C], ab [M][2C], dab [M][2C] or null
+  const float* ab = nullptr;
+  float* dab = nullptr;
+  float* y2 = nullptr;                       // PW_DGRAD_CAT: columns [split, Cout) go to y2
+  int split = 0;
+};
+bool conv1x1_plan(const lvae_conv_desc* d, const PwForm& f, ConvPlan& p);  // p.rows: PW_GATE_FWD only
+int conv1x1_launch(const lvae_conv_desc* d, const PwForm& f, hipStream_t s);
 
-// conv1x1_gate_fwd.hip
-int conv1x1_gate_fwd_wgs(const lvae_conv_desc* d);
-int conv1x1_gate_fwd_try(const lvae_conv_desc* d, const float* res, float* out, int act, hipStream_t s);
+// conv1x1_gate_fwd.hip: the persistent gate forward of the 64-channel blocks (p.rows = its workgroups)
+bool conv1x1_gate_fwd_plan(const lvae_conv_desc* d, ConvPlan& p);
+int conv1x1_gate_fwd_launch(const lvae_conv_desc* d, const ConvPlan& p, const float* res, float* out, int act, hipStream_t s);
 
-// conv1x1_gate_bwd_fused.hip
-size_t conv1x1_gate_bwd_fused_workspace(const lvae_conv_desc* d);
+// conv1x1_gate_bwd_fused.hip: the persistent gate backward (p.workspace = its slabs); with_apply: with a deferred lvae_bn_apply
+bool conv1x1_gate_bwd_fused_plan(const lvae_conv_desc* d, bool with_apply, ConvPlan& p);
 
 // conv_wgrad.hip
 void wgrad_reduce_launch(const float* slab_w, const float* slab_b, int ksplit, int ntaps, int Cin, int Cout, int64_t stap,

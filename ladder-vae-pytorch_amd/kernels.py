@@ -324,40 +324,28 @@ def conv2d(x, weight, g, bias=None, x2=None, in_scale=None, in_shift=None, in_ac
     return y if stats_pivot is None else (y, parts)
 
 
-def _is_1x1(g):
-    return g.KH == 1 and g.KW == 1 and g.stride == 1 and g.pad == 0 and not g.transposed
-
-
-# The two "is this the GateLayer2d convolution (1x1, C -> 2C)" predicates differ in what the kernels behind them take: the single-shot gate
-# kernels (forward, backward) take either weight orientation but at most 128 channels; the persistent backward kernel needs the weight
-# Cout-contiguous and leaves the channel counts to its workspace query.
-def _gate_1x1_single_shot(g, Cn):
-    return (_is_1x1(g) and g.Cout == 2 * Cn and g.Cin <= 128 and g.Cout <= 128 and g.Cin % 4 == 0 and g.Cout % 8 == 0 and
-            (g.s_co == 1 or g.s_ci == 1))
-
-
-def _gate_1x1_persistent(g, Cn):
-    return _is_1x1(g) and g.Cout == 2 * Cn and g.s_co == 1
-
-
 def conv1x1_gate(x, weight, g, bias, res, act, need_ab=True, stats_pivot=None):
     """GateLayer2d forward: ab = conv1x1(x) + bias (returned when need_ab), out = act(a) * sigmoid(b) + res, one kernel.
-    Falls back to conv2d + gate_fwd when the fused kernel does not support the shape.
+    Falls back to conv2d + gate_fwd when the fused kernel does not support the shape (lvae_conv1x1_gate_variant == 0).
     stats_pivot (C,): also return BatchNorm partials of `out` (rows, 2, C) around that pivot, or None when unsupported:
     returns (ab, out, parts)."""
     _chk_nhwc(x, 'x')
     N, H, W, _ = x.shape
     Cn = g.Cout // 2
-    if not _gate_1x1_single_shot(g, Cn) or (_ddi is not None and weight.data_ptr() not in _ddi['done']):
+    lib = _C.load()
+    fused = _ddi is None or weight.data_ptr() in _ddi['done']
+    if fused:
+        ab = torch.empty((N, H, W, g.Cout), dtype=x.dtype, device=x.device) if need_ab else None   # bf16-stored x: bf16-stored ab
+        d = _desc(g, weight, x, None, N, H, W, H, W, g.Cout, g.s_ci, g.s_co, GATHER_CONV, bias, y=ab)
+        fused = bool(lib.lvae_conv1x1_gate_variant(C.byref(d)))
+    if not fused:
         ab = conv2d(x, weight, g, bias=bias)
         out = gate_fwd(ab, res, act)
         return (ab, out) if stats_pivot is None else (ab, out, None)
-    ab = torch.empty((N, H, W, g.Cout), dtype=x.dtype, device=x.device) if need_ab else None   # bf16-stored x: bf16-stored ab
     out = torch.empty((N, H, W, Cn), dtype=torch.float32, device=x.device)
-    d = _desc(g, weight, x, None, N, H, W, H, W, g.Cout, g.s_ci, g.s_co, GATHER_CONV, bias, y=ab)
     parts = None
     if stats_pivot is not None:
-        rows = _C.load().lvae_conv1x1_gate_stats_rows(C.byref(d))
+        rows = lib.lvae_conv1x1_gate_stats_rows(C.byref(d))
         if rows > 0:
             buf = torch.empty((rows + 1, 2, Cn), dtype=torch.float32, device=x.device)   # last row: the pivot (written by the kernel)
             parts = StatParts(buf, rows, True)
@@ -368,38 +356,46 @@ def conv1x1_gate(x, weight, g, bias, res, act, need_ab=True, stats_pivot=None):
 
 def conv1x1_gate_bwd(dout, ab, weight, g, act, out_scale=None):
     """Backward of conv1x1_gate w.r.t. the convolution input and the pre-activations: returns (dab, dx). One kernel when the
-    shape is supported (gate backward formed in the dgrad kernel's operand staging), else gate_bwd + conv2d_dgrad."""
+    shape is supported (gate backward formed in the dgrad kernel's operand staging; lvae_conv1x1_gate_bwd_ok), else gate_bwd +
+    conv2d_dgrad."""
     _chk_nhwc(dout, 'dout')
     N, H, W, Cn = dout.shape
-    if not _gate_1x1_single_shot(g, Cn):
+    dx = torch.empty((N, H, W, g.Cin), dtype=torch.float32, device=dout.device)
+    d = _desc(g, weight, ab, None, N, H, W, H, W, g.Cin, g.s_co, g.s_ci, GATHER_TRANSPOSED, out_scale=out_scale, y=dx)
+    if g.Cout != 2 * Cn or not _C.load().lvae_conv1x1_gate_bwd_ok(C.byref(d)):
         dab = gate_bwd(dout, ab, act)
         return dab, conv2d_dgrad(dab, weight, g, (H, W), out_scale=out_scale)
     dab = torch.empty_like(ab)
-    dx = torch.empty((N, H, W, g.Cin), dtype=torch.float32, device=dout.device)
-    d = _desc(g, weight, ab, None, N, H, W, H, W, g.Cin, g.s_co, g.s_ci, GATHER_TRANSPOSED, out_scale=out_scale, y=dx)
     call('lvae_conv1x1_gate_bwd_f32', C.byref(d), ptr(dout), ptr(ab), ACT[act], ptr(dab), stream_ptr())
     return dab, dx
 
 
-def gate_bwd_fused_ws(x_like, weight, g, dweight=None):
-    """Scratch bytes conv1x1_gate_bwd_wgrad needs for the gate convolution (weight, g) on tensors shaped like x_like (N,H,W,C); 0: it does
-    not take the shape (the answer depends on the geometry alone). dweight: the gradient buffer, where it exists already."""
+def _gate_bwd_fused_desc(x_like, weight, g, dweight):
+    """The 128 -> 64 dgrad view the persistent gate backward is asked about, for the gate convolution (weight, g) on tensors shaped like
+    x_like (N,H,W,C); None where Python alone can tell that it does not apply (what the library cannot see)."""
     N, H, W, Cn = x_like.shape
-    if not _gate_1x1_persistent(g, Cn) or (dweight is not None and tuple(dweight.stride()) != tuple(weight.stride())):
-        return 0
+    if g.Cout != 2 * Cn or (dweight is not None and tuple(dweight.stride()) != tuple(weight.stride())):
+        return None
     d = _desc(g, weight, x_like, None, N, H, W, H, W, g.Cin, g.s_co, g.s_ci, GATHER_TRANSPOSED)
     d.C1 = g.Cout
-    return int(_C.load().lvae_conv1x1_gate_bwd_wgrad_workspace(C.byref(d)))
+    return d
 
 
-def gate_bwd_apply_ok():
-    """conv1x1_gate_bwd_wgrad can form its dout from a deferred BatchNorm-backward apply (PendingApply): every form but the fp32 MFMA."""
-    return not (form == _C.FORM_F32_MFMA and precision != PREC_BF16)
+def gate_bwd_fused_ws(x_like, weight, g, dweight=None):
+    """Scratch bytes conv1x1_gate_bwd_wgrad needs for the gate convolution (weight, g) on tensors shaped like x_like (N,H,W,C); 0: it does
+    not take the shape. dweight: the gradient buffer, where it exists already."""
+    d = _gate_bwd_fused_desc(x_like, weight, g, dweight)
+    return int(_C.load().lvae_conv1x1_gate_bwd_wgrad_workspace(C.byref(d))) if d is not None else 0
 
 
-def gate_bwd_fused_ok(x_like, weight, g, dweight=None):
-    """True when conv1x1_gate_bwd_wgrad takes the gate convolution (weight, g) on tensors shaped like x_like (N,H,W,C) with a deferred apply."""
-    return gate_bwd_apply_ok() and gate_bwd_fused_ws(x_like, weight, g, dweight) > 0
+def gate_bwd_apply_ok(x_like, weight, g, dweight=None):
+    """True when conv1x1_gate_bwd_wgrad takes the gate convolution (weight, g) on tensors shaped like x_like (N,H,W,C) with a deferred
+    BatchNorm-backward apply (PendingApply) forming its dout."""
+    d = _gate_bwd_fused_desc(x_like, weight, g, dweight)
+    return d is not None and bool(_C.load().lvae_conv1x1_gate_bwd_wgrad_apply_ok(C.byref(d)))
+
+
+gate_bwd_fused_ok = gate_bwd_apply_ok   # (the name the residual-block tests ask by)
 
 
 def conv1x1_gate_bwd_wgrad(dout, ab, y, weight, g, act, dweight, dbias, out_scale=None, out_bf16=False, apply=None):
@@ -408,14 +404,15 @@ def conv1x1_gate_bwd_wgrad(dout, ab, y, weight, g, act, dweight, dbias, out_scal
     apply (PendingApply): dout does not exist yet; the kernel forms it from the deferred BatchNorm-backward apply and stores it to apply.out."""
     _chk_nhwc(dout, 'dout')
     N, H, W, Cn = dout.shape
-    if not _gate_1x1_persistent(g, Cn) or tuple(dweight.stride()) != tuple(weight.stride()):
+    if g.Cout != 2 * Cn or tuple(dweight.stride()) != tuple(weight.stride()):
         return None
     if ab.dtype != y.dtype:
         raise _C.LvaeHipError("conv1x1_gate_bwd_wgrad: ab and y must have the same element type")
     dx = torch.empty((N, H, W, g.Cin), dtype=torch.bfloat16 if out_bf16 else torch.float32, device=dout.device)
     d = _desc(g, weight, ab, None, N, H, W, H, W, g.Cin, g.s_co, g.s_ci, GATHER_TRANSPOSED, out_scale=out_scale, y=dx)
-    need = _C.load().lvae_conv1x1_gate_bwd_wgrad_workspace(C.byref(d))
-    if not need or (apply is not None and not gate_bwd_apply_ok()):
+    lib = _C.load()
+    need = lib.lvae_conv1x1_gate_bwd_wgrad_workspace(C.byref(d))
+    if not need or (apply is not None and not lib.lvae_conv1x1_gate_bwd_wgrad_apply_ok(C.byref(d))):
         return None
     ws = workspace(need, dout.device)
     ap = None
@@ -729,18 +726,15 @@ def conv2d_wgrad_apply(x, weight, g, dweight, dbias, parts, dh, xbn, coef0, act,
 def conv1x1_dgrad_cat(dy, weight, g, C1):
     """Both halves of the input gradient of a 1x1 / stride-1 convolution whose input was the channel concat (x [.., C1], x2 [.., Cin - C1]),
     in one launch: returns (dx, dx2), or None when the shape is not the single-shot 1x1 kernel's (the caller launches one dgrad per half)."""
-    if not (_is_1x1(g) and dy.dtype == torch.float32):
-        return None
-    K_, N_ = g.Cout, g.Cin
-    kc = g.s_co == 1 and g.s_ci % 4 == 0
-    nc = g.s_ci == 1 and g.s_co % 4 == 0
-    if K_ > 128 or N_ > 128 or K_ % 4 or N_ % 4 or C1 % 4 or not (0 < C1 < N_) or not (kc or nc):
-        return None
     _chk_nhwc(dy, 'dy')
     N, H, W, _ = dy.shape
+    if not 0 < C1 < g.Cin:
+        return None
     dx = torch.empty((N, H, W, C1), dtype=torch.float32, device=dy.device)
-    dx2 = torch.empty((N, H, W, N_ - C1), dtype=torch.float32, device=dy.device)
-    d = _desc(g, weight, dy, None, N, H, W, H, W, N_, g.s_co, g.s_ci, GATHER_TRANSPOSED, y=dx)
+    dx2 = torch.empty((N, H, W, g.Cin - C1), dtype=torch.float32, device=dy.device)
+    d = _desc(g, weight, dy, None, N, H, W, H, W, g.Cin, g.s_co, g.s_ci, GATHER_TRANSPOSED, y=dx)
+    if not _C.load().lvae_conv1x1_dgrad_cat_ok(C.byref(d), C1):
+        return None
     call('lvae_conv1x1_dgrad_cat_f32', C.byref(d), ptr(dx2), C1, stream_ptr())
     return dx, dx2
 

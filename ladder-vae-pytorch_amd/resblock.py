@@ -76,7 +76,7 @@ def plan_block(blk, x, training):
         if gate is not None and gate.bias is not None and gate.weight.requires_grad and \
                 K.gate_bwd_fused_ws(x, gate.weight, gate.geom(), gate.weight.grad) > 0:
             backward = 'persistent-gate'
-            if training and not whole_fwd and sw.defer_apply_large and K.gate_bwd_apply_ok():   # (the whole-image forward never announced it)
+            if training and not whole_fwd and sw.defer_apply_large and K.gate_bwd_apply_ok(x, gate.weight, gate.geom(), gate.weight.grad):   # (the whole-image forward never announced it)
                 accepts = 'any-dh'
         absorbs = bool(training and bn2 is not None and sw.wgrad_apply and not s16 and cv1.weight.requires_grad and
                        x.shape[2] <= sw.wgrad_apply_maxw and K.conv2d_wgrad_apply_ok(x, cv1.weight, cv1.geom()))

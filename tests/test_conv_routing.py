@@ -5,6 +5,11 @@ variant / apply) must answer for the kernel the launch takes. The table covers e
 batch sizes (forward, dgrad view, weight gradient) in both precisions and both forms, with the workspace absent, sized, too small and
 only 8-byte aligned, and both statistics modes. The descriptors carry fake, never-dereferenced pointers: this module never calls a
 launch entry point. Expected answers: conv_routing_expected.json next to this file.
+
+The 1x1 gate / concat-dgrad family (`gate:` and `merge:` cases, also with form F32_MFMA) answers through its own queries: the kernel of the
+gate forward and its statistics rows on the forward view, the single-shot gate backward, the persistent gate backward's workspace and
+whether it takes a deferred apply on the 128 -> 64 dgrad view, and the one-launch concat dgrad of a merge convolution at split = C1.
+DECLINES lists descriptors those kernels refuse, with the answers written down from the kernels' conditions.
 """
 import ctypes as C
 import json
@@ -14,7 +19,7 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 EXPECTED = os.path.join(HERE, 'conv_routing_expected.json')
 
 PREC_F32, PREC_BF16 = 0, 1
-FORM_AUTO, FORM_SIX_PRODUCT_DIRECT = 0, 3
+FORM_AUTO, FORM_F32_MFMA, FORM_SIX_PRODUCT_DIRECT = 0, 1, 3
 GATHER_CONV, GATHER_TRANSPOSED = 0, 1
 STATS_BN_FWD, STATS_BN_BWD = 0, 1
 DT_BF16 = 1
@@ -106,6 +111,87 @@ def variants(mk, need, bf16_storage):
                 yield d
 
 
+GATE_FWD_QUERIES = ('lvae_conv1x1_gate_variant', 'lvae_conv1x1_gate_stats_rows')
+GATE_BWD_QUERIES = ('lvae_conv1x1_gate_bwd_ok', 'lvae_conv1x1_gate_bwd_wgrad_workspace', 'lvae_conv1x1_gate_bwd_wgrad_apply_ok')
+
+
+def gate_fwd_desc(N, H, W, C, prec, form):
+    return make_desc(N, H, W, H, W, C, 0, 2 * C, 1, 1, 0, GATHER_CONV, 2 * C, 1, prec, form)
+
+
+def gate_bwd_desc(N, H, W, C, prec, form):
+    """the dgrad view of the gate convolution C -> 2C: what both gate backwards are described by"""
+    return make_desc(N, H, W, H, W, 2 * C, 0, C, 1, 1, 0, GATHER_TRANSPOSED, 1, 2 * C, prec, form)
+
+
+def merge_dgrad_desc(N, H, W, C1, C2, Cout, prec, form):
+    return make_desc(N, H, W, H, W, Cout, 0, C1 + C2, 1, 1, 0, GATHER_TRANSPOSED, 1, Cout, prec, form)
+
+
+def gate_table(lib):
+    """gate: [variant, stats_rows, gate_bwd_ok, persistent-backward workspace, apply_ok]; merge: [dgrad_cat_ok at split = C1]"""
+    ask = lambda names, d: [int(getattr(lib, q)(C.byref(d))) for q in names]
+    out = {}
+    for cname, color, img, downsample, N in CONFIGS:
+        for tag, C1, C2, Cout, k, s, p, tr, H, W, OH, OW in convs(color, img, downsample):
+            for prec in (PREC_F32, PREC_BF16):
+                for form in (FORM_AUTO, FORM_SIX_PRODUCT_DIRECT, FORM_F32_MFMA):
+                    base = '%s/N%d/%dx%d/%d+%d->%d/p%d/f%d' % (tag, N, H, W, C1, C2, Cout, prec, form)
+                    if tag == 'gate':
+                        out['gate:' + base] = (ask(GATE_FWD_QUERIES, gate_fwd_desc(N, H, W, C1, prec, form)) +
+                                               ask(GATE_BWD_QUERIES, gate_bwd_desc(N, H, W, C1, prec, form)))
+                    elif tag == 'merge':
+                        out['merge:' + base] = [int(lib.lvae_conv1x1_dgrad_cat_ok(C.byref(merge_dgrad_desc(N, H, W, C1, C2, Cout, prec, form)), C1))]
+    return out
+
+
+def _mod(d, **fields):
+    for k, v in fields.items():
+        setattr(d, k, v)
+    return d
+
+
+GATE_PERSISTENT, GATE_SINGLE_SHOT = 1, 2
+# Descriptors the 1x1 kernels decline (or take by another kernel), on the 16x16 level at batch 256 (65536 pixels: 512 workgroups of the
+# persistent forward, 256 slabs of [64][128] + [128] floats of the persistent backward) unless a shape is given. The answers follow from
+# the conditions of the kernels: the single-shot kernel needs 1x1 / stride 1, at most 128 reduction and output channels (multiples of 4; 8
+# for the gate), 16-byte aligned descriptor pointers and a unit weight stride along one axis with the other a multiple of 4; the
+# persistent forward is 64 -> 128 with x aligned, any weight strides, bf16 storage only at bf16 precision; the persistent backward is the
+# 128 -> 64 view with w_sk = 1, w_sn % 4 == 0, w / y / out_scale aligned, at least 16384 pixels, bf16 storage only at bf16 precision.
+_BIG = (256, 16, 16)
+_WS = 256 * (64 * 128 + 128) * 4
+DECLINES = [   # (name, kind, descriptor factory, expected)
+    ('w+4', 'fwd', lambda: _mod(gate_fwd_desc(*_BIG, 64, PREC_F32, FORM_AUTO), w=_fake(3) + 4), [GATE_PERSISTENT, 512]),
+    ('w+4', 'bwd', lambda: _mod(gate_bwd_desc(*_BIG, 64, PREC_F32, FORM_AUTO), w=_fake(3) + 4), [0, 0, 0]),
+    ('w+4', 'cat64', lambda: _mod(merge_dgrad_desc(*_BIG, 64, 64, 64, PREC_F32, FORM_AUTO), w=_fake(3) + 4), [0]),
+    ('w+4 small', 'fwd', lambda: _mod(gate_fwd_desc(4, 8, 8, 16, PREC_F32, FORM_AUTO), w=_fake(3) + 4), [0, 0]),
+    ('aligned small', 'fwd', lambda: gate_fwd_desc(4, 8, 8, 16, PREC_F32, FORM_AUTO), [GATE_SINGLE_SHOT, 4]),
+    ('aligned small', 'bwd', lambda: gate_bwd_desc(4, 8, 8, 16, PREC_F32, FORM_AUTO), [1, 0, 0]),
+    ('split 62', 'cat62', lambda: merge_dgrad_desc(*_BIG, 64, 64, 64, PREC_F32, FORM_AUTO), [0]),
+    ('split Cout', 'cat128', lambda: merge_dgrad_desc(*_BIG, 64, 64, 64, PREC_F32, FORM_AUTO), [0]),
+    ('split 64', 'cat64', lambda: merge_dgrad_desc(*_BIG, 64, 64, 64, PREC_F32, FORM_AUTO), [1]),
+    ('132 reduction channels', 'fwd', lambda: gate_fwd_desc(*_BIG, 132, PREC_F32, FORM_AUTO), [0, 0]),
+    ('132 reduction channels', 'bwd', lambda: _mod(gate_bwd_desc(*_BIG, 64, PREC_F32, FORM_AUTO), C1=132), [0, 0, 0]),
+    ('132 reduction channels', 'cat64', lambda: _mod(merge_dgrad_desc(*_BIG, 64, 64, 64, PREC_F32, FORM_AUTO), C1=132), [0]),
+    ('no unit stride', 'fwd', lambda: _mod(gate_fwd_desc(*_BIG, 64, PREC_F32, FORM_AUTO), w_sk=256, w_sn=2), [GATE_PERSISTENT, 512]),
+    ('no unit stride small', 'fwd', lambda: _mod(gate_fwd_desc(4, 8, 8, 16, PREC_F32, FORM_AUTO), w_sk=64, w_sn=2), [0, 0]),
+    ('no unit stride', 'bwd', lambda: _mod(gate_bwd_desc(*_BIG, 64, PREC_F32, FORM_AUTO), w_sk=2, w_sn=256), [0, 0, 0]),
+    ('no unit stride', 'cat64', lambda: _mod(merge_dgrad_desc(*_BIG, 64, 64, 64, PREC_F32, FORM_AUTO), w_sk=2, w_sn=128), [0]),
+    ('w_sn 130', 'bwd', lambda: _mod(gate_bwd_desc(*_BIG, 64, PREC_F32, FORM_AUTO), w_sn=130), [0, 0, 0]),
+    ('w_sn 130', 'cat64', lambda: _mod(merge_dgrad_desc(*_BIG, 64, 64, 64, PREC_F32, FORM_AUTO), w_sn=130), [0]),
+    ('w_sn 18 small', 'fwd', lambda: _mod(gate_fwd_desc(4, 8, 8, 16, PREC_F32, FORM_AUTO), w_sk=1, w_sn=18), [0, 0]),
+    ('bf16 x at fp32', 'fwd', lambda: _mod(gate_fwd_desc(*_BIG, 64, PREC_F32, FORM_AUTO), x_dtype=DT_BF16), [0, 0]),
+    ('bf16 x at fp32', 'bwd', lambda: _mod(gate_bwd_desc(*_BIG, 64, PREC_F32, FORM_AUTO), x_dtype=DT_BF16), [1, 0, 0]),
+    ('bf16 x at bf16', 'fwd', lambda: _mod(gate_fwd_desc(*_BIG, 64, PREC_BF16, FORM_AUTO), x_dtype=DT_BF16), [GATE_PERSISTENT, 512]),
+    ('bf16 x at bf16', 'bwd', lambda: _mod(gate_bwd_desc(*_BIG, 64, PREC_BF16, FORM_AUTO), x_dtype=DT_BF16), [1, _WS, 1]),
+    ('bf16 x', 'cat64', lambda: _mod(merge_dgrad_desc(*_BIG, 64, 64, 64, PREC_BF16, FORM_AUTO), x_dtype=DT_BF16), [0]),
+    ('Cout 24', 'fwd', lambda: gate_fwd_desc(3, 3, 3, 12, PREC_F32, FORM_AUTO), [GATE_SINGLE_SHOT, 0]),
+    ('f32 mfma', 'bwd', lambda: gate_bwd_desc(*_BIG, 64, PREC_F32, FORM_F32_MFMA), [1, _WS, 0]),
+    ('f32 mfma at bf16', 'bwd', lambda: gate_bwd_desc(*_BIG, 64, PREC_BF16, FORM_F32_MFMA), [1, _WS, 1]),
+    ('16383 pixels', 'bwd', lambda: gate_bwd_desc(1, 127, 129, 64, PREC_F32, FORM_AUTO), [1, 0, 0]),
+]
+
+
 def table():
     """{case id: answers}. conv: one [workspace, variant, stats_rows, folds, stats_buffer_rows, bf16_storage] per descriptor of
     variants(); wgrad: [workspace, variant, apply_ok]; grouped: the grouped workspace of all forward convolutions of a config."""
@@ -131,7 +217,26 @@ def table():
                         out['conv:' + base] = [ask(CONV_QUERIES, d) for d in variants(m, need, bf16_storage)]
                 arr = (_C.ConvDesc * len(group))(*group)
                 out['grouped:%s/p%d/f%d' % (cname, prec, form)] = int(lib.lvae_conv2d_wgrad_grouped_workspace(arr, len(group)))
+    out.update(gate_table(lib))
     return out
+
+
+def test_gate_plan_declines():
+    import lvae_amd  # noqa: F401
+    from lvae_amd import _C
+    lib = _C.load()
+    bad = []
+    for name, kind, mk, want in DECLINES:
+        d = mk()
+        if kind == 'fwd':
+            got = [int(getattr(lib, q)(C.byref(d))) for q in GATE_FWD_QUERIES]
+        elif kind == 'bwd':
+            got = [int(getattr(lib, q)(C.byref(d))) for q in GATE_BWD_QUERIES]
+        else:
+            got = [int(lib.lvae_conv1x1_dgrad_cat_ok(C.byref(d), int(kind[3:])))]
+        if got != want:
+            bad.append('%s (%s): got %s, expected %s' % (name, kind, got, want))
+    assert not bad, '\n'.join(bad)
 
 
 def test_conv_routing_table():

@@ -402,6 +402,93 @@ def test_conv1x1_gate_bwd_fused(K, shape):
     assert rel(nchw(dx), x.grad * mask.view(N, C, 1, 1)) < 3e-6
 
 
+def _record_calls(K, monkeypatch):
+    names, real = [], K.call
+    monkeypatch.setattr(K, 'call', lambda name, *args: (names.append(name), real(name, *args))[1])
+    return names
+
+
+@pytest.mark.parametrize('shape', [(2, 8, 2, 2), (3, 12, 3, 3), (2, 64, 3, 3), (2, 132, 2, 2)])
+def test_conv1x1_gate_wrappers_launch_what_the_queries_answer(K, shape, monkeypatch):
+    """K.conv1x1_gate launches lvae_conv1x1_gate_f32 exactly when lvae_conv1x1_gate_variant != 0 and lvae_conv2d_f32 + lvae_gate_fwd_f32
+    otherwise; K.conv1x1_gate_bwd likewise against lvae_conv1x1_gate_bwd_ok. Either way the fp64 result at the neighbours' tolerance."""
+    N, C, H, W = shape
+    g = torch.Generator().manual_seed(21)
+    x = torch.randn(N, C, H, W, generator=g, dtype=torch.float64, requires_grad=True)
+    res = torch.randn(N, C, H, W, generator=g, dtype=torch.float64)
+    w = torch.randn(2 * C, C, 1, 1, generator=g, dtype=torch.float64) / math.sqrt(C)
+    b = torch.randn(2 * C, generator=g, dtype=torch.float64)
+    ab = F.conv2d(x, w, b)
+    ab.retain_grad()
+    a_, b_ = ab.chunk(2, 1)
+    out = F.elu(a_) * torch.sigmoid(b_) + res
+    dout = torch.randn(out.shape, generator=g, dtype=torch.float64)
+    out.backward(dout)
+    wp = packed_weight(w.float())
+    geom = K.ConvGeom(wp, 1, 0)
+    lib, byref = K._C.load(), ctypes.byref
+    xd, abd, doutd = nhwc(x.detach().float()), nhwc(ab.detach().float()), nhwc(dout.float())
+
+    d = K._desc(geom, wp, xd, None, N, H, W, H, W, 2 * C, geom.s_ci, geom.s_co, K.GATHER_CONV, b.float().cuda(), y=torch.empty_like(abd))
+    variant = lib.lvae_conv1x1_gate_variant(byref(d))
+    assert variant == {8: K._C.GATE_SINGLE_SHOT, 12: K._C.GATE_SINGLE_SHOT, 64: K._C.GATE_PERSISTENT, 132: 0}[C]
+    names = _record_calls(K, monkeypatch)
+    ab_k, out_k = K.conv1x1_gate(xd, wp, geom, b.float().cuda(), nhwc(res.float()), 'elu')
+    assert names == (['lvae_conv1x1_gate_f32'] if variant else ['lvae_conv2d_f32', 'lvae_gate_fwd_f32'])
+    assert rel(nchw(ab_k).double(), ab.detach()) < 2e-6 and rel(nchw(out_k).double(), out.detach()) < 2e-6
+
+    d = K._desc(geom, wp, abd, None, N, H, W, H, W, C, geom.s_co, geom.s_ci, K.GATHER_TRANSPOSED, y=torch.empty_like(xd))
+    ok = lib.lvae_conv1x1_gate_bwd_ok(byref(d))
+    assert ok == (0 if C == 132 else 1)
+    del names[:]
+    dab_k, dx_k = K.conv1x1_gate_bwd(doutd, abd, wp, geom, 'elu')
+    assert names == (['lvae_conv1x1_gate_bwd_f32'] if ok else ['lvae_gate_bwd_f32', 'lvae_conv2d_f32'])
+    assert rel(nchw(dab_k).double(), ab.grad) < 2e-6 and rel(nchw(dx_k).double(), x.grad) < 2e-6
+
+
+def _one_float_past_alignment(wp):
+    """the same tap-linear weight layout in a flat buffer, starting one float past a 16-byte boundary"""
+    flat = torch.zeros(wp.numel() + 1, device='cuda')
+    v = torch.as_strided(flat, wp.shape, wp.stride(), 1)
+    v.copy_(wp)
+    assert v.data_ptr() % 16 == 4
+    return v
+
+
+def test_conv1x1_gate_and_concat_dgrad_compose_for_an_unaligned_weight_view(K, monkeypatch):
+    """A weight view at an unaligned offset is not the fused 1x1 kernels': the wrappers take the composed path (bit-identical to composing
+    by hand) instead of raising, conv1x1_dgrad_cat returns None, and the backward of a merge convolution completes with the two launches."""
+    from lvae_amd import ops
+    from lvae_amd.lib.nn import Conv2dParams
+    N, C, H, W = 2, 8, 3, 3
+    g = torch.Generator().manual_seed(22)
+    x, res = nhwc(torch.randn(N, C, H, W, generator=g)), nhwc(torch.randn(N, C, H, W, generator=g))
+    wu = _one_float_past_alignment(packed_weight(torch.randn(2 * C, C, 1, 1, generator=g) / math.sqrt(C)))
+    b = torch.randn(2 * C, generator=g).cuda()
+    geom = K.ConvGeom(wu, 1, 0)
+    ab, out = K.conv1x1_gate(x, wu, geom, b, res, 'elu')
+    ab_ref = K.conv2d(x, wu, geom, bias=b)
+    assert torch.equal(ab, ab_ref) and torch.equal(out, K.gate_fwd(ab_ref, res, 'elu'))
+    dout = nhwc(torch.randn(N, C, H, W, generator=g))
+    dab, dx = K.conv1x1_gate_bwd(dout, ab, wu, geom, 'elu')
+    dab_ref = K.gate_bwd(dout, ab, 'elu')
+    assert torch.equal(dab, dab_ref) and torch.equal(dx, K.conv2d_dgrad(dab_ref, wu, geom, (H, W)))
+
+    mod = Conv2dParams(2 * C, C, 1).cuda()   # merge 1x1 over cat(x, x2): C1 = C2 = Co = 8
+    mod.weight.data = _one_float_past_alignment(packed_weight(mod.weight.detach().cpu()))
+    mod.weight.requires_grad_(False)
+    mod.bias.requires_grad_(False)
+    mg = mod.geom()
+    dy = nhwc(torch.randn(N, C, H, W, generator=g))
+    assert K.conv1x1_dgrad_cat(dy, mod.weight, mg, C) is None
+    x1, x2 = x.clone().requires_grad_(True), res.clone().requires_grad_(True)
+    names = _record_calls(K, monkeypatch)
+    ops.conv(x1, mod, x2=x2).backward(dy)
+    assert names == ['lvae_conv2d_f32'] * 3
+    assert torch.equal(x1.grad, K.conv2d_dgrad(dy, mod.weight, mg, (H, W), ci_range=(0, C)))
+    assert torch.equal(x2.grad, K.conv2d_dgrad(dy, mod.weight, mg, (H, W), ci_range=(C, 2 * C)))
+
+
 @pytest.mark.parametrize('shape', [(256, 256), (7, 70), (1, 3), (300, 1)])
 def test_colsum(K, shape):
     g = torch.Generator().manual_seed(2)
