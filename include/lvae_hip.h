@@ -373,8 +373,10 @@ int lvae_resblock_conv_f32(const lvae_conv_desc* d, const lvae_rb_ext* ext, void
  *   dw[tap,k,n] += sum_{n,oh,ow} T(x)[n,ih,iw,k] * dy[n,oh,ow,n]     db[n] += sum dy[..,n]
  * written with the strides d->w_stap/w_sk/w_sn into `dw` (accumulating). Deterministic: split-K partial slabs
  * in `workspace` are summed in a fixed order by a second kernel. `dy` is [N,OH,OW,Cout].
- * Kernel choice: img -> bf16 -> Winograd -> 1x1 -> tile -> thin -> generic, made once from `d` and the alignment of dy and workspace;
- * lvae_conv2d_wgrad_workspace / _variant / _apply_ok and the grouped call answer for that choice with 16-byte aligned dy and workspace.
+ * Kernel choice: one ordered table of kernel families, img -> bf16 -> Winograd -> 1x1 -> tile -> thin -> generic; each row holds the family's
+ * plan (every condition its launch depends on) and whether it needs 16-byte aligned dy and / or workspace, and the first row that takes `d`
+ * is the choice, made once per call. lvae_conv2d_wgrad_workspace / _variant / _apply_ok and the grouped queries answer for that choice with
+ * 16-byte aligned dy and workspace.
  * workspace bytes needed: lvae_conv2d_wgrad_workspace(d). With a dy or workspace that is not 16-byte aligned the launch may take a kernel
  * that needs more; it then returns LVAE_EWORKSPACE instead of writing past workspace_bytes.
  * replaces: autograd's convolution_backward (weight, bias) for every call site listed above. */
@@ -410,12 +412,18 @@ enum {
 int32_t lvae_conv2d_wgrad_variant(const lvae_conv_desc* d);
 /* n independent weight gradients (descs[i], dy[i], dw[i], db[i]; db[i] may be NULL): same results as n calls of
  * lvae_conv2d_wgrad_f32 in index order. The low-resolution levels of the ladder fill 16-64 CUs per gradient and depend on
- * nothing but their own inputs, so launches that share a kernel variant go out together (up to 12 per launch, one grouped
- * slab reduction); everything else is issued one by one. No two entries may accumulate into overlapping dw/db.
+ * nothing but their own inputs, so gradients of one kernel family that share its kernel instantiation go out together: up to 12 per
+ * launch in the tile family (by its template pair), up to 12 in the Winograd family (by image width, below 65536 pixels per gradient),
+ * up to 32 in the whole-image family (by its kind), each with grouped slab reductions. Groups are issued first (tile, Winograd,
+ * whole-image; entries in index order), then everything else one by one in index order, a tile or Winograd gradient alone in its group
+ * among them. No two entries may accumulate into overlapping dw/db.
  * workspace: lvae_conv2d_wgrad_grouped_workspace(descs, n) bytes. */
 size_t lvae_conv2d_wgrad_grouped_workspace(const lvae_conv_desc* descs, int32_t n);
 int lvae_conv2d_wgrad_grouped_f32(const lvae_conv_desc* descs, const float* const* dy, float* const* dw, float* const* db,
                                   int32_t n, void* workspace, size_t workspace_bytes, void* stream);
+/* Host only, no launch. How lvae_conv2d_wgrad_grouped_f32 issues descs[0..n) given 16-byte aligned dy and workspace:
+ * launch_of[i] = index, in issue order, of the launch that computes entry i. Returns the number of launches. */
+int32_t lvae_conv2d_wgrad_grouped_schedule(const lvae_conv_desc* descs, int32_t n, int32_t* launch_of);
 
 /* ------------------------------------------------------------------------------------------------------------
  * BatchNorm2d (training statistics) — lib/nn.py:80-81 (nn.BatchNorm2d, momentum 0.1, eps 1e-5)

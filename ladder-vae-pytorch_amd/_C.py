@@ -124,6 +124,7 @@ SIGNATURES = {
     'lvae_conv2d_wgrad_apply_f32': (C.c_int, [C.POINTER(ConvDesc), C.POINTER(BnApply), _P, _P, _P, _Z, _P]),
     'lvae_conv2d_wgrad_grouped_workspace': (_Z, [C.POINTER(ConvDesc), _I]),
     'lvae_conv2d_wgrad_grouped_f32': (C.c_int, [C.POINTER(ConvDesc), _P, _P, _P, _I, _P, _Z, _P]),
+    'lvae_conv2d_wgrad_grouped_schedule': (_I, [C.POINTER(ConvDesc), _I, C.POINTER(_I)]),
     'lvae_bn_stats_workspace': (_Z, [_L, _I]),
     'lvae_bn_stats_f32': (C.c_int, [_P, _L, _I, _P, _P, _F, _F, _P, _P, _P, _P, _P, _P, _P, _Z, _P]),
     'lvae_bn_finalize_parts_f32': (C.c_int, [_P, _I, _L, _I, _P, _P, _P, _F, _F, _P, _P, _P, _P, _P, _P, _P]),

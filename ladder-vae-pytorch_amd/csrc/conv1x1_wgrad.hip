@@ -139,32 +139,30 @@ static bool w1x1_plan(const lvae_conv_desc* d, int& nwg, int& ppw) {
   return true;
 }
 
-size_t conv1x1_wgrad_workspace(const lvae_conv_desc* d) {
+bool conv1x1_wgrad_plan(const lvae_conv_desc* d, WgradPlan& p) {
   int nwg, ppw;
-  if (!w1x1_plan(d, nwg, ppw)) return 0;
-  return (size_t)nwg * ((size_t)64 * d->Cout + d->Cout) * sizeof(float);
+  if (!w1x1_plan(d, nwg, ppw)) return false;
+  p.set_slabs(nwg, (size_t)64 * d->Cout, d->Cout);
+  return true;
 }
 
-// runs the plan of conv1x1_wgrad_workspace(d) != 0
-int conv1x1_wgrad_launch(const lvae_conv_desc* d, const float* dy, float* dw, float* db, void* workspace, hipStream_t s) {
+int conv1x1_wgrad_launch(const WgradOp& o, hipStream_t s) {
+  const lvae_conv_desc* d = o.d;
   int nwg = 0, ppw = 0;
   w1x1_plan(d, nwg, ppw);
   W1x1Args a;
   a.x = d->x;
-  a.dy = dy;
+  a.dy = o.dy;
   a.M = d->N * d->H * d->W;
   a.Cout = d->Cout;
   a.ppw = ppw;
-  a.slab_w = static_cast<float*>(workspace);
-  a.slab_b = db ? a.slab_w + (size_t)nwg * 64 * d->Cout : nullptr;
+  a.slab_w = o.slab_w();
+  a.slab_b = o.slab_b();
   const int nb = d->Cout / 32;
   const size_t lds = ((size_t)4 * 2 * nb * 16 * 64 + 4 * nb * 32) * sizeof(float);
   const int rc = nb == 4 ? launch_lds<conv1x1_wgrad_kernel<4>>("conv1x1_wgrad", dim3(nwg), dim3(256), lds, 160 * 1024, s, a)
                          : launch_lds<conv1x1_wgrad_kernel<2>>("conv1x1_wgrad", dim3(nwg), dim3(256), lds, 160 * 1024, s, a);
-  if (rc) return rc;
-  wgrad_reduce_launch(a.slab_w, a.slab_b, nwg, 1, 64, d->Cout, d->w_stap, d->w_sk, d->w_sn, dw, db, s);
-  LVAE_LAUNCH_CHECK("conv2d_wgrad_reduce");
-  return 0;
+  return rc ? rc : wgrad_op_reduce(o, s);
 }
 
 }  // namespace lvae

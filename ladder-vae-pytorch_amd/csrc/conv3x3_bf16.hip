@@ -1248,56 +1248,53 @@ static int bfwg_half_ranges(const lvae_conv_desc* d, const BfWgArgs& a) {
   return 128;
 }
 
-size_t conv3x3_wgrad_bf16_workspace(const lvae_conv_desc* d) {
+// slabs: the pixel ranges of the half-slab form, else the workgroups of the whole-slab form
+bool conv3x3_wgrad_bf16_plan(const lvae_conv_desc* d, WgradPlan& p) {
   BfWgArgs a;
-  if (!bfwg_plan(d, a)) return 0;
+  if (!bfwg_plan(d, a)) return false;
   const int q = bfwg_half_ranges(d, a);
-  return (size_t)(q ? q : bfwg_nwg(a)) * ((size_t)9 * d->C1 * d->Cout + d->Cout) * sizeof(float);
+  p.set_slabs(q ? q : bfwg_nwg(a), (size_t)9 * d->C1 * d->Cout, d->Cout);
+  p.takes_bf16_storage = true;
+  return true;
 }
 
-// runs the plan of conv3x3_wgrad_bf16_workspace(d) != 0 (16-byte aligned dy and workspace: the route of lvae_conv2d_wgrad_f32 checked them)
-int conv3x3_wgrad_bf16_launch(const lvae_conv_desc* d, const float* dy, float* dw, float* db, void* workspace, hipStream_t s) {
+// 16-byte aligned dy and workspace: the route checked them
+int conv3x3_wgrad_bf16_launch(const WgradOp& o, hipStream_t s) {
+  const lvae_conv_desc* d = o.d;
+  const int nslab = o.plan.slabs;
   BfWgArgs a;
   bfwg_plan(d, a);
   a.d = *d;
   a.d.in_fold = nullptr;
-  a.dy = dy;
+  a.dy = o.dy;
+  a.slab_w = o.slab_w();
+  a.slab_b = o.slab_b();
   const bool xb = d->x_dtype == LVAE_DT_BF16, dyb = d->y_dtype == LVAE_DT_BF16;
-  if (const int nr = bfwg_half_ranges(d, a)) {
-    a.slab_w = static_cast<float*>(workspace);
-    a.slab_b = db ? a.slab_w + (size_t)nr * 9 * d->C1 * d->Cout : nullptr;
+  if (bfwg_half_ranges(d, a)) {
     const size_t qlds = (size_t)2 * (a.halo_px + 128) * BFH_LDK * 2;
     const char* name = "conv3x3_wgrad_bf16h";
-    const dim3 qgrid(2 * nr);
+    const dim3 qgrid(2 * nslab);
     int rc;
     if (xb && dyb) rc = launch_lds<conv3x3_wgrad_bf16h_kernel<true, true>>(name, qgrid, dim3(512), qlds, 159 * 1024, s, a);
     else if (dyb) rc = launch_lds<conv3x3_wgrad_bf16h_kernel<false, true>>(name, qgrid, dim3(512), qlds, 159 * 1024, s, a);
     else rc = launch_lds<conv3x3_wgrad_bf16h_kernel<true, false>>(name, qgrid, dim3(512), qlds, 159 * 1024, s, a);
     if (rc) return rc;
-    wgrad_reduce_launch(a.slab_w, a.slab_b, nr, 9, d->C1, d->Cout, d->w_stap, d->w_sk, d->w_sn, dw, db, s);
-    LVAE_LAUNCH_CHECK("conv3x3_wgrad_bf16_reduce");
-    return 0;
+  } else {
+    size_t lds = (size_t)a.split * (a.halo_px + a.bm) * BF_LDK * 2;
+    if (lds < 64 * 64 * 4) lds = 64 * 64 * 4;   // bias-gradient reduction of the 8-channel mapping
+    const dim3 grid(nslab, (d->Cout + 63) / 64);
+    const bool c8ok = d->C1 % 8 == 0 && d->Cout % 8 == 0;
+    if (dyb && c8ok && xb) {
+      if (a.bm == 128) hipLaunchKernelGGL((conv3x3_wgrad_bf16_kernel<2, 1, true, true>), grid, dim3(512), lds, s, a);
+      else hipLaunchKernelGGL((conv3x3_wgrad_bf16_kernel<1, 1, true, true>), grid, dim3(512), lds, s, a);
+    } else if (dyb && c8ok) {
+      if (a.bm == 128) hipLaunchKernelGGL((conv3x3_wgrad_bf16_kernel<2, 1, false, true>), grid, dim3(512), lds, s, a);
+      else hipLaunchKernelGGL((conv3x3_wgrad_bf16_kernel<1, 1, false, true>), grid, dim3(512), lds, s, a);
+    } else if (a.bm == 128) hipLaunchKernelGGL((conv3x3_wgrad_bf16_kernel<2, 1>), grid, dim3(512), lds, s, a);
+    else hipLaunchKernelGGL((conv3x3_wgrad_bf16_kernel<1, 1>), grid, dim3(512), lds, s, a);
+    LVAE_LAUNCH_CHECK("conv3x3_wgrad_bf16");
   }
-  const int nwg = bfwg_nwg(a);
-  a.slab_w = static_cast<float*>(workspace);
-  a.slab_b = db ? a.slab_w + (size_t)nwg * 9 * d->C1 * d->Cout : nullptr;
-  size_t lds = (size_t)a.split * (a.halo_px + a.bm) * BF_LDK * 2;
-  if (lds < 32 * 64 * 4) lds = 32 * 64 * 4;
-  const dim3 grid(nwg, (d->Cout + 63) / 64);
-  if (lds < 64 * 64 * 4) lds = 64 * 64 * 4;   // bias-gradient reduction of the 8-channel mapping
-  const bool c8ok = d->C1 % 8 == 0 && d->Cout % 8 == 0;
-  if (dyb && c8ok && xb) {
-    if (a.bm == 128) hipLaunchKernelGGL((conv3x3_wgrad_bf16_kernel<2, 1, true, true>), grid, dim3(512), lds, s, a);
-    else hipLaunchKernelGGL((conv3x3_wgrad_bf16_kernel<1, 1, true, true>), grid, dim3(512), lds, s, a);
-  } else if (dyb && c8ok) {
-    if (a.bm == 128) hipLaunchKernelGGL((conv3x3_wgrad_bf16_kernel<2, 1, false, true>), grid, dim3(512), lds, s, a);
-    else hipLaunchKernelGGL((conv3x3_wgrad_bf16_kernel<1, 1, false, true>), grid, dim3(512), lds, s, a);
-  } else if (a.bm == 128) hipLaunchKernelGGL((conv3x3_wgrad_bf16_kernel<2, 1>), grid, dim3(512), lds, s, a);
-  else hipLaunchKernelGGL((conv3x3_wgrad_bf16_kernel<1, 1>), grid, dim3(512), lds, s, a);
-  LVAE_LAUNCH_CHECK("conv3x3_wgrad_bf16");
-  wgrad_reduce_launch(a.slab_w, a.slab_b, nwg, 9, d->C1, d->Cout, d->w_stap, d->w_sk, d->w_sn, dw, db, s);
-  LVAE_LAUNCH_CHECK("conv3x3_wgrad_bf16_reduce");
-  return 0;
+  return wgrad_op_reduce(o, s);
 }
 
 }  // namespace lvae

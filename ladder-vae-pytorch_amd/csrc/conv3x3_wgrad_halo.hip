@@ -21,6 +21,9 @@
 //                           | MFMA   : bar; compute(i); bar for i < T;       [slabs]; bar
 #include <stdlib.h>
 
+#include <algorithm>
+#include <type_traits>
+
 #include "lvae_host.h"
 
 namespace lvae {
@@ -44,10 +47,9 @@ __global__ __launch_bounds__(512, 2) void conv_wgrad_ws_kernel(WTileArgs a) {
 
 // Several independent weight gradients in one launch (blockIdx.y = problem): the low-resolution levels fill 16-64 CUs per
 // problem, and their launches are independent of everything but their own inputs.
-constexpr int kMaxGroup = 12;
-static_assert(kMaxGroup <= kMaxReduceGroup, "a group is reduced by one wgrad_reduce_grouped_launch");
+static_assert(kWgradTileGroup <= kMaxReduceGroup, "a group is reduced by one wgrad_reduce_grouped_launch");
 struct WTileGroup {
-  WTileArgs p[kMaxGroup];
+  WTileArgs p[kWgradTileGroup];
 };
 static_assert(sizeof(WTileGroup) <= 4096, "kernel argument block");
 
@@ -59,7 +61,6 @@ __global__ __launch_bounds__(512, 2) void conv_wgrad_ws_grouped_kernel(WTileGrou
   const int grp = blockIdx.x;
 #include "conv3x3_wgrad_halo_body.inc"
 }
-
 
 static int cin_tile(int Cin) { return Cin <= 32 ? 32 : (Cin <= 64 ? 64 : 128); }
 
@@ -112,88 +113,65 @@ static bool wtile_plan(const lvae_conv_desc* d, WTileArgs& a) {
   return a.ntiles < 65536;
 }
 
-// workspace bytes needed by this path, or 0 when the descriptor is not eligible
-size_t conv_wgrad_tile_workspace(const lvae_conv_desc* d) {
-  WTileArgs a;
-  if (!wtile_plan(d, a)) return 0;
-  return ((size_t)a.ksplit * ((size_t)d->KH * d->KW * a.Cin * d->Cout + d->Cout)) * sizeof(float);
+// f(cin_t, nkw) with the values of a template pair <CIN_T, NKW> as compile-time constants: 0 <32,3>, 1 <64,3>, 2 <32,1>, 3 <64,1>, 4 <128,1>
+template <typename F>
+static int with_tile_pair(int pair, F f) {
+  using std::integral_constant;
+  switch (pair) {
+    case 0: return f(integral_constant<int, 32>{}, integral_constant<int, 3>{});
+    case 1: return f(integral_constant<int, 64>{}, integral_constant<int, 3>{});
+    case 2: return f(integral_constant<int, 32>{}, integral_constant<int, 1>{});
+    case 3: return f(integral_constant<int, 64>{}, integral_constant<int, 1>{});
+    default: return f(integral_constant<int, 128>{}, integral_constant<int, 1>{});
+  }
 }
 
-template <int CIN_T, int NKW>
-static int launch_ws(const WTileArgs& a, hipStream_t s) {
-  const size_t lds = (size_t)2 * a.buf_floats * sizeof(float);
-  return launch_lds<conv_wgrad_ws_kernel<CIN_T, NKW>>("conv_wgrad_ws", dim3(a.ncot * a.ksplit), dim3(512), lds, 160 * 1024, s, a);
+bool conv_wgrad_tile_plan(const lvae_conv_desc* d, WgradPlan& p) {
+  WTileArgs a;
+  if (!wtile_plan(d, a)) return false;
+  const int cin_t = cin_tile(a.Cin);
+  p.group = (d->KH == 3 ? 0 : 2) + (cin_t == 32 ? 0 : (cin_t == 64 ? 1 : 2));   // group key: the template pair of with_tile_pair
+  p.set_slabs(a.ksplit, (size_t)d->KH * d->KW * a.Cin * d->Cout, d->Cout);
+  return true;
 }
 
-// runs the plan of conv_wgrad_tile_workspace(d) != 0 (16-byte aligned dy: the route of lvae_conv2d_wgrad_f32 checked it)
-int conv_wgrad_tile_launch(const lvae_conv_desc* d, const float* dy, float* dw, float* db, void* workspace, hipStream_t s) {
-  WTileArgs a;
+// the kernel arguments and the slab reduce of one gradient; returns the kernel's workgroups
+static int tile_fill(const WgradOp& o, WTileArgs& a, ReduceArgs& r) {
+  static const int dbg = lvae::debug_phase_switch("LVAE_WG_DEBUG");  // phase-skip builds (-DLVAE_PHASE_DEBUG) only; 0 in the product
+  const lvae_conv_desc* d = o.d;
   wtile_plan(d, a);
   a.d = *d;
-  a.dy = dy;
-  static const int dbg = lvae::debug_phase_switch("LVAE_WG_DEBUG");  // phase-skip builds (-DLVAE_PHASE_DEBUG) only; 0 in the product
+  a.dy = o.dy;
   a.debug = dbg;
-  const int ntaps = d->KH * d->KW;
-  a.slab_w = static_cast<float*>(workspace);
-  a.slab_b = db ? a.slab_w + (size_t)a.ksplit * ntaps * a.Cin * d->Cout : nullptr;
-  const int cin_t = cin_tile(a.Cin);
-  int rc;
-  if (d->KH == 3) rc = cin_t == 32 ? launch_ws<32, 3>(a, s) : launch_ws<64, 3>(a, s);
-  else rc = cin_t == 32 ? launch_ws<32, 1>(a, s) : (cin_t == 64 ? launch_ws<64, 1>(a, s) : launch_ws<128, 1>(a, s));
-  if (rc) return rc;
-  wgrad_reduce_launch(a.slab_w, a.slab_b, a.ksplit, ntaps, a.Cin, d->Cout, d->w_stap, d->w_sk, d->w_sn, dw, db, s);
-  LVAE_LAUNCH_CHECK("conv2d_wgrad_reduce");
-  return 0;
+  a.slab_w = o.slab_w();
+  a.slab_b = o.slab_b();
+  r = ReduceArgs{a.slab_w, a.slab_b, a.ksplit, d->KH * d->KW, a.Cin, d->Cout, d->w_stap, d->w_sk, d->w_sn, o.dw, o.db};
+  return a.ncot * a.ksplit;
 }
 
-template <int CIN_T, int NKW>
-static int launch_ws_grouped(const WTileGroup& g, int n, int max_wgs, size_t lds, hipStream_t s) {
-  return launch_lds<conv_wgrad_ws_grouped_kernel<CIN_T, NKW>>("conv_wgrad_ws_grouped", dim3(max_wgs, n), dim3(512), lds, 160 * 1024, s, g);
-}
+static size_t tile_lds(const WTileArgs& a) { return (size_t)2 * a.buf_floats * sizeof(float); }
 
-// kind of the tile kernel a descriptor would use (-1: not eligible): 0 <32,3>, 1 <64,3>, 2 <32,1>, 3 <64,1>, 4 <128,1>
-int conv_wgrad_tile_kind(const lvae_conv_desc* d) {
-  WTileArgs a;
-  if (!wtile_plan(d, a)) return -1;
-  const int cin_t = cin_tile(a.Cin);
-  if (d->KH == 3) return cin_t == 32 ? 0 : 1;
-  return cin_t == 32 ? 2 : (cin_t == 64 ? 3 : 4);
-}
-
-// n <= kMaxGroup descriptors of the same kind whose route is this kernel, each with its own workspace: one launch + one grouped reduce
-int conv_wgrad_tile_grouped(const lvae_conv_desc* const* ds, const float* const* dy, float* const* dw, float* const* db,
-                            void* const* workspace, int n, int kind, hipStream_t s) {
+// n <= kWgradTileGroup gradients of one plan.group, each with its own workspace (16-byte aligned dy: the route checked it). One gradient
+// runs the single kernel and its reduce, several the grouped kernel and one grouped reduce.
+int conv_wgrad_tile_launch(const WgradOp* o, int n, hipStream_t s) {
   WTileGroup g;
-  ReduceArgs r[kMaxGroup];
-  static const int dbg = lvae::debug_phase_switch("LVAE_WG_DEBUG");  // phase-skip builds (-DLVAE_PHASE_DEBUG) only; 0 in the product
+  ReduceArgs r[kWgradTileGroup];
   int max_wgs = 0;
   size_t lds = 0;
   for (int i = 0; i < n; ++i) {
-    WTileArgs& a = g.p[i];
-    wtile_plan(ds[i], a);
-    a.d = *ds[i];
-    a.dy = dy[i];
-    a.debug = dbg;
-    const int ntaps = ds[i]->KH * ds[i]->KW;
-    a.slab_w = static_cast<float*>(workspace[i]);
-    a.slab_b = db[i] ? a.slab_w + (size_t)a.ksplit * ntaps * a.Cin * ds[i]->Cout : nullptr;
-    if (a.ncot * a.ksplit > max_wgs) max_wgs = a.ncot * a.ksplit;
-    const size_t l = (size_t)2 * a.buf_floats * sizeof(float);
-    if (l > lds) lds = l;
-    r[i] = ReduceArgs{a.slab_w, a.slab_b, a.ksplit, ntaps, a.Cin, ds[i]->Cout, ds[i]->w_stap, ds[i]->w_sk, ds[i]->w_sn, dw[i], db[i]};
+    max_wgs = std::max(max_wgs, tile_fill(o[i], g.p[i], r[i]));
+    lds = std::max(lds, tile_lds(g.p[i]));
   }
-  for (int i = n; i < kMaxGroup; ++i) g.p[i] = g.p[0];
-  int rc;
-  switch (kind) {
-    case 0: rc = launch_ws_grouped<32, 3>(g, n, max_wgs, lds, s); break;
-    case 1: rc = launch_ws_grouped<64, 3>(g, n, max_wgs, lds, s); break;
-    case 2: rc = launch_ws_grouped<32, 1>(g, n, max_wgs, lds, s); break;
-    case 3: rc = launch_ws_grouped<64, 1>(g, n, max_wgs, lds, s); break;
-    default: rc = launch_ws_grouped<128, 1>(g, n, max_wgs, lds, s);
-  }
+  for (int i = n; i < kWgradTileGroup; ++i) g.p[i] = g.p[0];
+  const int rc = with_tile_pair(o->plan.group, [&](auto cin_t, auto nkw) {
+    constexpr int C = decltype(cin_t)::value, K = decltype(nkw)::value;
+    if (n == 1) return launch_lds<conv_wgrad_ws_kernel<C, K>>("conv_wgrad_ws", dim3(max_wgs), dim3(512), lds, 160 * 1024, s, g.p[0]);
+    return launch_lds<conv_wgrad_ws_grouped_kernel<C, K>>("conv_wgrad_ws_grouped", dim3(max_wgs, n), dim3(512), lds, 160 * 1024, s, g);
+  });
   if (rc) return rc;
-  wgrad_reduce_grouped_launch(r, n, s);
-  LVAE_LAUNCH_CHECK("conv2d_wgrad_reduce_grouped");
+  if (n == 1) wgrad_reduce_launch(r->slab_w, r->slab_b, r->ksplit, r->ntaps, r->Cin, r->Cout, r->stap, r->sk, r->sn, r->dw, r->db, s);
+  else wgrad_reduce_grouped_launch(r, n, s);
+  LVAE_LAUNCH_CHECK(n == 1 ? "conv2d_wgrad_reduce" : "conv2d_wgrad_reduce_grouped");
   return 0;
 }
 

@@ -18,6 +18,9 @@
 // (deterministic), applies G^T . G and accumulates into dw with the caller's strides.
 #include <stdlib.h>
 
+#include <algorithm>
+#include <type_traits>
+
 #include "bn_stats.h"
 #include "lvae_host.h"
 
@@ -59,9 +62,8 @@ __global__ __launch_bounds__(512, 2) void conv_wgrad_wino_ap_kernel(WgWinoApArgs
 #include "conv3x3_wgrad_wino_body.inc"
 }
 
-constexpr int kMaxWinoGroup = 12;
 struct WgWinoGroup {
-  WgWinoArgs p[kMaxWinoGroup];
+  WgWinoArgs p[kWgradWinoGroup];
 };
 static_assert(sizeof(WgWinoGroup) <= 4096, "kernel argument block");
 
@@ -86,7 +88,7 @@ struct WinoReduceArgs {
   float* db;
 };
 struct WinoReduceGroup {
-  WinoReduceArgs p[kMaxWinoGroup];
+  WinoReduceArgs p[kWgradWinoGroup];
 };
 
 // dw[tap(a,b)][ci][co] += (G^T (sum_ranges slab) G)[a][b], 1024-thread workgroups, ranges summed in eight slices (slice = range mod 8,
@@ -174,7 +176,6 @@ __global__ __launch_bounds__(1024) void conv_wgrad_wino_reduce_grouped_kernel(Wi
   wino_reduce_body<false>(a, blockIdx.x, red, red_b);
 }
 
-
 static bool wg_wino_plan(const lvae_conv_desc* d, WgWinoArgs& a) {
   static const bool off = tune("LVAE_DISABLE_WINO_WGRAD", 0) != 0 || tune("LVAE_DISABLE_WINO", 0) != 0;  // A/B switch (tuning builds only)
   if (off) return false;
@@ -202,111 +203,83 @@ static bool wg_wino_plan(const lvae_conv_desc* d, WgWinoArgs& a) {
   return true;
 }
 
-size_t conv_wgrad_wino_workspace(const lvae_conv_desc* d) {
+// group key: the image width (one kernel instantiation per width); problems of at least LVAE_WINO_GROUP_MAX_M pixels fill the chip alone
+bool conv_wgrad_wino_plan(const lvae_conv_desc* d, WgradPlan& p) {
+  static const int64_t group_max_m = tune("LVAE_WINO_GROUP_MAX_M", 65536);
   WgWinoArgs a;
-  if (!wg_wino_plan(d, a)) return 0;
-  return (size_t)a.nranges * a.ncog * (2 * 16 * 32 * 64 + 64) * sizeof(float);
+  if (!wg_wino_plan(d, a)) return false;
+  p.group = (int64_t)d->N * d->H * d->W < group_max_m ? d->W : -1;
+  p.set_slabs(a.nranges, (size_t)a.ncog * 2 * 16 * 32 * 64, (size_t)a.ncog * 64);
+  p.apply_ok = d->precision == LVAE_PREC_F32 && d->Cout == 64 && (d->W == 16 || d->W == 32) && d->x_dtype == LVAE_DT_F32 && d->y_dtype == LVAE_DT_F32;
+  return true;
 }
 
-template <int TPR>
-static int launch_wg_wino(const WgWinoArgs& a, hipStream_t s) {
-  constexpr int W = 2 * TPR, HW2 = W + 2, TR = 16 / TPR, HP = (2 * TR + 2) * HW2;
-  size_t lds = (size_t)2 * (HP * WG_XS + 64 * WG_DS) * sizeof(float);
-  const size_t lds_r = (size_t)(4 * 4 * 2 * 16 * 64 + 128) * sizeof(float);
-  if (lds < lds_r) lds = lds_r;
-  return launch_lds<conv_wgrad_wino_kernel<TPR>>("conv_wgrad_wino", dim3(a.nranges * a.ncog * 2), dim3(512), lds, 160 * 1024, s, a);
+// f(tiles per row) with the value as a compile-time constant
+template <typename F>
+static int with_tpr(int W, F f) {
+  if (W == 8) return f(std::integral_constant<int, 4>{});
+  if (W == 16) return f(std::integral_constant<int, 8>{});
+  return f(std::integral_constant<int, 16>{});
 }
 
-// runs the plan of conv_wgrad_wino_workspace(d) != 0 (16-byte aligned dy and workspace: the route of lvae_conv2d_wgrad_f32 checked them)
-int conv_wgrad_wino_launch(const lvae_conv_desc* d, const float* dy, float* dw, float* db, void* workspace, hipStream_t s) {
-  WgWinoArgs a;
-  wg_wino_plan(d, a);
-  a.d = *d;
-  a.dy = dy;
-  a.slab_w = static_cast<float*>(workspace);
-  a.slab_b = db ? a.slab_w + (size_t)a.nranges * a.ncog * 2 * 16 * 32 * 64 : nullptr;
-  int rc;
-  if (d->W == 8) rc = launch_wg_wino<4>(a, s);
-  else if (d->W == 16) rc = launch_wg_wino<8>(a, s);
-  else rc = launch_wg_wino<16>(a, s);
-  if (rc) return rc;
-  const WinoReduceArgs ra{a.slab_w, a.slab_b, a.nranges, a.ncog, d->Cout, 0, d->w_stap, d->w_sk, d->w_sn, dw, db};
-  hipLaunchKernelGGL(conv_wgrad_wino_reduce_kernel, dim3(128 * a.ncog), dim3(1024), 0, s, ra);
-  LVAE_LAUNCH_CHECK("conv_wgrad_wino_reduce");
-  return 0;
+// LDS of the three kernels: two chunk buffers of x halo + dy, or the exchange of the two tile halves at the end
+static size_t wg_wino_lds(int W) {
+  const int tpr = W / 2, hp = (2 * (16 / tpr) + 2) * (W + 2);
+  return std::max((size_t)2 * (hp * WG_XS + 64 * WG_DS), (size_t)(4 * 4 * 2 * 16 * 64 + 128)) * sizeof(float);
 }
 
-template <int TPR>
-static int launch_wg_wino_ap(const WgWinoApArgs& g, hipStream_t s) {
-  constexpr int W = 2 * TPR, HW2 = W + 2, TR = 16 / TPR, HP = (2 * TR + 2) * HW2;
-  size_t lds = (size_t)2 * (HP * WG_XS + 64 * WG_DS) * sizeof(float);
-  const size_t lds_r = (size_t)(4 * 4 * 2 * 16 * 64 + 128) * sizeof(float);
-  if (lds < lds_r) lds = lds_r;
-  return launch_lds<conv_wgrad_wino_ap_kernel<TPR>>("conv_wgrad_wino_ap", dim3(g.w.nranges * g.w.ncog * 2), dim3(512), lds, 160 * 1024, s, g);
+// the kernel arguments and the slab reduce of one gradient (dy null: formed by a deferred apply); returns the kernel's workgroups
+static int wino_fill(const WgradOp& o, WgWinoArgs& a, WinoReduceArgs& r) {
+  wg_wino_plan(o.d, a);
+  a.d = *o.d;
+  a.dy = o.dy;
+  a.slab_w = o.slab_w();
+  a.slab_b = o.slab_b();
+  r = WinoReduceArgs{a.slab_w, a.slab_b, a.nranges, a.ncog, o.d->Cout, 0, o.d->w_stap, o.d->w_sk, o.d->w_sn, o.dw, o.db};
+  return a.nranges * a.ncog * 2;
 }
 
-// 1 when the weight gradient of `d` can take its dY operand from a deferred BatchNorm-backward apply (lvae_conv2d_wgrad_apply_f32)
-bool conv_wgrad_wino_apply_ok(const lvae_conv_desc* d) {
-  WgWinoArgs a;
-  return d != nullptr && d->Cout == 64 && (d->W == 16 || d->W == 32) && d->x_dtype == LVAE_DT_F32 && d->y_dtype == LVAE_DT_F32 && wg_wino_plan(d, a);
-}
-
-// runs a descriptor lvae_conv2d_wgrad_apply_ok accepted
-int conv_wgrad_wino_apply_launch(const lvae_conv_desc* d, const lvae_bn_apply* ap, float* dw, float* db, void* workspace, hipStream_t s) {
+// one gradient of a plan with apply_ok whose dY is ap's result (16-byte aligned workspace and ap operands: the entry point checked them)
+int conv_wgrad_wino_apply_launch(const WgradOp& o, const lvae_bn_apply* ap, hipStream_t s) {
   WgWinoApArgs g;
-  WgWinoArgs& a = g.w;
-  LVAE_REQUIRE(al16_or_null(workspace) && al16_or_null(ap->parts) && al16_or_null(ap->coef) && al16_or_null(ap->dh) && al16_or_null(ap->x) && al16_or_null(ap->out) && al16_or_null(ap->drop),
-               LVAE_EALIGN, "lvae_conv2d_wgrad_apply_f32: buffers must be 16-byte aligned");
-  wg_wino_plan(d, a);
-  a.d = *d;
-  a.dy = nullptr;
-  a.slab_w = static_cast<float*>(workspace);
-  a.slab_b = db ? a.slab_w + (size_t)a.nranges * a.ncog * 2 * 16 * 32 * 64 : nullptr;
+  WinoReduceArgs r;
+  const int wgs = wino_fill(o, g.w, r);
   g.ap = *ap;
-  int rc = d->W == 16 ? launch_wg_wino_ap<8>(g, s) : launch_wg_wino_ap<16>(g, s);
+  auto launch = [&](auto tpr) {
+    return launch_lds<conv_wgrad_wino_ap_kernel<decltype(tpr)::value>>("conv_wgrad_wino_ap", dim3(wgs), dim3(512), wg_wino_lds(o.d->W),
+                                                                       160 * 1024, s, g);
+  };
+  const int rc = o.d->W == 16 ? launch(std::integral_constant<int, 8>{}) : launch(std::integral_constant<int, 16>{});   // apply_ok: W = 16 or 32
   if (rc) return rc;
-  const WinoReduceArgs ra{a.slab_w, a.slab_b, a.nranges, a.ncog, d->Cout, 0, d->w_stap, d->w_sk, d->w_sn, dw, db};
-  hipLaunchKernelGGL(conv_wgrad_wino_reduce_kernel, dim3(128 * a.ncog), dim3(1024), 0, s, ra);
+  hipLaunchKernelGGL(conv_wgrad_wino_reduce_kernel, dim3(128 * r.ncog), dim3(1024), 0, s, r);
   LVAE_LAUNCH_CHECK("conv_wgrad_wino_reduce");
   return 0;
 }
 
-// n <= kMaxWinoGroup descriptors whose route is this kernel (aligned dy and workspace), all of one image width, each with its own workspace
-int conv_wgrad_wino_grouped(const lvae_conv_desc* const* ds, const float* const* dy, float* const* dw, float* const* db,
-                            void* const* workspace, int n, hipStream_t s) {
+// n <= kWgradWinoGroup gradients of one plan.group, each with its own workspace (16-byte aligned dy and workspace: the route checked
+// them). One gradient runs the single kernel and the half-workgroup reduce, several the grouped kernel and the grouped reduce.
+int conv_wgrad_wino_launch(const WgradOp* o, int n, hipStream_t s) {
   WgWinoGroup g;
   WinoReduceGroup rg;
   int max_wgs = 0, max_ncog = 0;
-  const int W = ds[0]->W;
   for (int i = 0; i < n; ++i) {
-    WgWinoArgs& a = g.p[i];
-    wg_wino_plan(ds[i], a);
-    a.d = *ds[i];
-    a.dy = dy[i];
-    a.slab_w = static_cast<float*>(workspace[i]);
-    a.slab_b = db[i] ? a.slab_w + (size_t)a.nranges * a.ncog * 2 * 16 * 32 * 64 : nullptr;
-    if (a.nranges * a.ncog * 2 > max_wgs) max_wgs = a.nranges * a.ncog * 2;
-    if (a.ncog > max_ncog) max_ncog = a.ncog;
-    rg.p[i] = WinoReduceArgs{a.slab_w, a.slab_b, a.nranges, a.ncog, ds[i]->Cout, 0, ds[i]->w_stap, ds[i]->w_sk, ds[i]->w_sn, dw[i], db[i]};
+    max_wgs = std::max(max_wgs, wino_fill(o[i], g.p[i], rg.p[i]));
+    max_ncog = std::max(max_ncog, g.p[i].ncog);
   }
-  for (int i = n; i < kMaxWinoGroup; ++i) {
+  for (int i = n; i < kWgradWinoGroup; ++i) {
     g.p[i] = g.p[0];
     rg.p[i] = rg.p[0];
   }
-  const int tpr = W / 2;
-  const int hp = (2 * (16 / tpr) + 2) * (W + 2);
-  size_t lds = (size_t)2 * (hp * WG_XS + 64 * WG_DS) * sizeof(float);
-  const size_t lds_r = (size_t)(4 * 4 * 2 * 16 * 64 + 128) * sizeof(float);
-  if (lds < lds_r) lds = lds_r;
-  const char* name = "conv_wgrad_wino_grouped";
-  const dim3 grid(max_wgs, n);
-  int rc;
-  if (W == 8) rc = launch_lds<conv_wgrad_wino_grouped_kernel<4>>(name, grid, dim3(512), lds, 160 * 1024, s, g);
-  else if (W == 16) rc = launch_lds<conv_wgrad_wino_grouped_kernel<8>>(name, grid, dim3(512), lds, 160 * 1024, s, g);
-  else rc = launch_lds<conv_wgrad_wino_grouped_kernel<16>>(name, grid, dim3(512), lds, 160 * 1024, s, g);
+  const size_t lds = wg_wino_lds(o->d->W);
+  const int rc = with_tpr(o->d->W, [&](auto tpr) {
+    constexpr int T = decltype(tpr)::value;
+    if (n == 1) return launch_lds<conv_wgrad_wino_kernel<T>>("conv_wgrad_wino", dim3(max_wgs), dim3(512), lds, 160 * 1024, s, g.p[0]);
+    return launch_lds<conv_wgrad_wino_grouped_kernel<T>>("conv_wgrad_wino_grouped", dim3(max_wgs, n), dim3(512), lds, 160 * 1024, s, g);
+  });
   if (rc) return rc;
-  hipLaunchKernelGGL(conv_wgrad_wino_reduce_grouped_kernel, dim3(64 * max_ncog, n), dim3(1024), 0, s, rg);
-  LVAE_LAUNCH_CHECK("conv_wgrad_wino_reduce_grouped");
+  if (n == 1) hipLaunchKernelGGL(conv_wgrad_wino_reduce_kernel, dim3(128 * max_ncog), dim3(1024), 0, s, rg.p[0]);
+  else hipLaunchKernelGGL(conv_wgrad_wino_reduce_grouped_kernel, dim3(64 * max_ncog, n), dim3(1024), 0, s, rg);
+  LVAE_LAUNCH_CHECK(n == 1 ? "conv_wgrad_wino_reduce" : "conv_wgrad_wino_reduce_grouped");
   return 0;
 }
 

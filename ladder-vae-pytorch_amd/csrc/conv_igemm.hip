@@ -386,7 +386,8 @@ extern "C" int32_t lvae_resblock_bf16_storage(const lvae_conv_desc* d) {
   t.gather = LVAE_GATHER_TRANSPOSED;
   const ConvPlan b = conv_route(&t).plan;
   if (b.variant != LVAE_VARIANT_BF16_DIRECT || b.rows <= 0) return 0;
-  if (conv3x3_wgrad_bf16_workspace(d) == 0) return 0;
+  WgradPlan wp;
+  if (!conv3x3_wgrad_bf16_plan(d, wp)) return 0;
   lvae_conv_desc g = *d;  // the block's GateLayer2d: 1x1, 64 -> 128 forward; its fused backward is described by the 128 -> 64 dgrad view
   g.KH = g.KW = 1; g.pad = 0; g.Cout = 128; g.in_scale = g.in_shift = nullptr; g.out_scale = nullptr; g.in_act = g.out_act = 0; g.in_fold = nullptr;
   ConvPlan gp;

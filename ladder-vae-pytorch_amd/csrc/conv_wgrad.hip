@@ -10,6 +10,7 @@
 #include <stdlib.h>
 
 #include <algorithm>
+#include <map>
 #include <vector>
 
 #include "lvae_host.h"
@@ -295,6 +296,15 @@ __global__ __launch_bounds__(256) void wgrad_reduce_kernel(const float* __restri
   }
 }
 
+// one gradient's slabs as its plan lays them out. Cin = C1 + C2 also for the families that read x only (bf16, 1x1, thin): their plans
+// require x2 == nullptr, and conv_desc_check ties C2 == 0 to that.
+int wgrad_op_reduce(const WgradOp& o, hipStream_t s) {
+  const lvae_conv_desc* d = o.d;
+  wgrad_reduce_launch(o.slab_w(), o.slab_b(), o.plan.slabs, d->KH * d->KW, d->C1 + d->C2, d->Cout, d->w_stap, d->w_sk, d->w_sn, o.dw, o.db, s);
+  LVAE_LAUNCH_CHECK("conv2d_wgrad_reduce");
+  return 0;
+}
+
 void wgrad_reduce_launch(const float* slab_w, const float* slab_b, int ksplit, int ntaps, int Cin, int Cout, int64_t stap,
                          int64_t sk, int64_t sn, float* dw, float* db, hipStream_t s) {
   const int per = ntaps * Cin * Cout, tot = per + (db ? Cout : 0);
@@ -439,14 +449,31 @@ __global__ __launch_bounds__(256) void conv_wgrad_thin_kernel(ThinWgradArgs a) {
   }
 }
 
-// workspace bytes of the thin path, 0 when not eligible
-static size_t thin_wgrad_workspace(const lvae_conv_desc* d) {
+static size_t thin_lds(const lvae_conv_desc* d) {
+  return ((size_t)((d->H + 2 * d->pad) * (d->W + 2 * d->pad) * d->C1 + 3) / 4 * 4 + (size_t)d->OH * d->OW * 64) * sizeof(float);
+}
+
+static bool thin_wgrad_plan(const lvae_conv_desc* d, WgradPlan& p) {
   const int K = d->KH * d->KW * d->C1;
-  if (d->gather != LVAE_GATHER_CONV || d->x2 != nullptr || d->C2 != 0 || d->in_scale != nullptr) return 0;
-  if (K > 76 || d->Cout > 64 || d->OH * d->OW > 1024 || d->N < 32 || d->N > 65535) return 0;
-  const size_t lds = ((size_t)((d->H + 2 * d->pad) * (d->W + 2 * d->pad) * d->C1 + 3) / 4 * 4 + (size_t)d->OH * d->OW * 64) * sizeof(float);
-  if (lds > 160 * 1024) return 0;
-  return (size_t)d->N * ((size_t)K * d->Cout + d->Cout) * sizeof(float);
+  if (d->gather != LVAE_GATHER_CONV || d->x2 != nullptr || d->C2 != 0 || d->in_scale != nullptr) return false;
+  if (K > 76 || d->Cout > 64 || d->OH * d->OW > 1024 || d->N < 32 || d->N > 65535) return false;
+  if (thin_lds(d) > 160 * 1024) return false;
+  p.set_slabs(d->N, (size_t)K * d->Cout, d->Cout);
+  return true;
+}
+
+static int thin_wgrad_launch(const WgradOp& o, hipStream_t s) {
+  const lvae_conv_desc* d = o.d;
+  ThinWgradArgs ta;
+  ta.d = *d;
+  ta.dy = o.dy;
+  ta.K = d->KH * d->KW * d->C1;
+  ta.PH = d->H + 2 * d->pad;
+  ta.PW = d->W + 2 * d->pad;
+  ta.slab_w = o.slab_w();
+  ta.slab_b = o.slab_b();
+  const int rc = launch_lds<conv_wgrad_thin_kernel>("conv_wgrad_thin", dim3(d->N), dim3(256), thin_lds(d), 160 * 1024, s, ta);
+  return rc ? rc : wgrad_op_reduce(o, s);
 }
 
 static void wgrad_plan(const lvae_conv_desc* d, int& ksplit, int& px_per_split, int& ncit, int& ncot) {
@@ -465,32 +492,118 @@ static void wgrad_plan(const lvae_conv_desc* d, int& ksplit, int& px_per_split, 
   ksplit = (M + px_per_split - 1) / px_per_split;
 }
 
-
-struct WgradRoute {
-  int32_t variant = LVAE_WGRAD_VARIANT_GENERIC;  // LVAE_WGRAD_VARIANT_*
-  size_t workspace = 0;                          // bytes the launch needs
-};
-
-// The kernel of a weight gradient, chosen once in the order img -> bf16 -> Winograd -> 1x1 -> tile -> thin -> generic for the alignment
-// of dy and of the workspace. Every lvae_conv2d_wgrad_* query and launch reads this; the queries, which see no dy, answer for 16-byte
-// aligned dy and workspace.
-static WgradRoute wgrad_route(const lvae_conv_desc* d, bool dy16, bool ws16) {
-  static const bool halo_off = tune("LVAE_DISABLE_HALO", 0) != 0;  // A/B switch (tuning builds only): the generic kernel for everything
-  WgradRoute r;
-  if (!halo_off) {
-    const bool al = dy16 && ws16;
-    if (al && (r.workspace = conv_wgrad_img_workspace(d))) r.variant = LVAE_WGRAD_VARIANT_IMG;   // fp32-stored operands of the <= 8x8 levels, either precision
-    else if (al && (r.workspace = conv3x3_wgrad_bf16_workspace(d))) r.variant = LVAE_WGRAD_VARIANT_BF16;   // precision = LVAE_PREC_BF16
-    else if (al && (r.workspace = conv_wgrad_wino_workspace(d))) r.variant = LVAE_WGRAD_VARIANT_WINO;
-    else if ((r.workspace = conv1x1_wgrad_workspace(d))) r.variant = LVAE_WGRAD_VARIANT_DIRECT_1X1;
-    else if (dy16 && (r.workspace = conv_wgrad_tile_workspace(d))) r.variant = LVAE_WGRAD_VARIANT_TILE;
-    else if ((r.workspace = thin_wgrad_workspace(d))) r.variant = LVAE_WGRAD_VARIANT_THIN;
-    if (r.workspace) return r;
-  }
+// the generic kernel takes every descriptor
+static bool generic_wgrad_plan(const lvae_conv_desc* d, WgradPlan& p) {
   int ksplit, pps, ncit, ncot;
   wgrad_plan(d, ksplit, pps, ncit, ncot);
-  r.workspace = (size_t)ksplit * ((size_t)d->KH * d->KW * (d->C1 + d->C2) * d->Cout + d->Cout) * sizeof(float);
-  return r;
+  p.set_slabs(ksplit, (size_t)d->KH * d->KW * (d->C1 + d->C2) * d->Cout, d->Cout);
+  return true;
+}
+
+static int generic_wgrad_launch(const WgradOp& o, hipStream_t s) {
+  const lvae_conv_desc* d = o.d;
+  WgradArgs a;
+  a.d = *d;
+  a.dy = o.dy;
+  a.M = d->N * d->OH * d->OW;
+  a.ohw = d->OH * d->OW;
+  a.Cin = d->C1 + d->C2;
+  a.ntaps = d->KH * d->KW;
+  wgrad_plan(d, a.ksplit, a.px_per_split, a.ncit, a.ncot);
+  a.slab_w = o.slab_w();
+  a.slab_b = o.slab_b();
+  const bool xv = (d->C1 % 4 == 0) && (d->C2 % 4 == 0) && al16(d->x) && (!d->x2 || al16(d->x2)) &&
+                  (!d->in_scale || (al16(d->in_scale) && al16(d->in_shift)));
+  const bool yv = (d->Cout % 4 == 0) && al16(o.dy);
+  const int grid = a.ksplit * a.ncot * a.ncit * a.ntaps;
+  if (xv && yv) hipLaunchKernelGGL((conv_wgrad_kernel<true, true>), dim3(grid), dim3(256), 0, s, a);
+  else if (xv) hipLaunchKernelGGL((conv_wgrad_kernel<true, false>), dim3(grid), dim3(256), 0, s, a);
+  else if (yv) hipLaunchKernelGGL((conv_wgrad_kernel<false, true>), dim3(grid), dim3(256), 0, s, a);
+  else hipLaunchKernelGGL((conv_wgrad_kernel<false, false>), dim3(grid), dim3(256), 0, s, a);
+  LVAE_LAUNCH_CHECK("conv2d_wgrad");
+  return wgrad_op_reduce(o, s);
+}
+
+// The kernel of a weight gradient: the first family of this table, in its order, whose alignment needs dy and the workspace meet and whose
+// plan takes the descriptor. Every lvae_conv2d_wgrad_* query and launch reads the routed plan; the queries, which see no dy, answer for
+// 16-byte aligned dy and workspace.
+struct WgradFamily {
+  int32_t variant;                                    // LVAE_WGRAD_VARIANT_*
+  bool (*plan)(const lvae_conv_desc*, WgradPlan&);
+  bool dy16, ws16;                                    // needs 16-byte aligned dy / workspace
+};
+// (The cross-file plans are called through lambdas: tests/test_csrc_layout.py counts a function of lvae_host.h as used by a file that calls
+// it, and a bare name in a table is no call.)
+static const WgradFamily kWgradFamilies[] = {
+    {LVAE_WGRAD_VARIANT_IMG, [](auto d, auto& p) { return conv_wgrad_img_plan(d, p); }, true, true},       // fp32-stored operands of the <= 8x8 levels
+    {LVAE_WGRAD_VARIANT_BF16, [](auto d, auto& p) { return conv3x3_wgrad_bf16_plan(d, p); }, true, true},  // precision = LVAE_PREC_BF16
+    {LVAE_WGRAD_VARIANT_WINO, [](auto d, auto& p) { return conv_wgrad_wino_plan(d, p); }, true, true},
+    {LVAE_WGRAD_VARIANT_DIRECT_1X1, [](auto d, auto& p) { return conv1x1_wgrad_plan(d, p); }, false, false},
+    {LVAE_WGRAD_VARIANT_TILE, [](auto d, auto& p) { return conv_wgrad_tile_plan(d, p); }, true, false},
+    {LVAE_WGRAD_VARIANT_THIN, thin_wgrad_plan, false, false},
+    {LVAE_WGRAD_VARIANT_GENERIC, generic_wgrad_plan, false, false},   // takes everything
+};
+
+static WgradPlan wgrad_route(const lvae_conv_desc* d, bool dy16, bool ws16) {
+  static const bool halo_off = tune("LVAE_DISABLE_HALO", 0) != 0;  // A/B switch (tuning builds only): the generic kernel for everything
+  for (const WgradFamily& f : kWgradFamilies) {
+    WgradPlan p;
+    p.variant = f.variant;
+    if ((f.dy16 && !dy16) || (f.ws16 && !ws16) || (halo_off && f.variant != LVAE_WGRAD_VARIANT_GENERIC)) continue;
+    if (f.plan(d, p)) return p;
+  }
+  return WgradPlan{};   // not reached: the last family takes everything
+}
+
+// runs n gradients of one plan: one (n = 1), or a group of wgrad_schedule
+static int wgrad_launch(const WgradOp* o, int n, hipStream_t s) {
+  switch (o->plan.variant) {
+    case LVAE_WGRAD_VARIANT_IMG: return conv_wgrad_img_grouped(o, n, s);
+    case LVAE_WGRAD_VARIANT_BF16: return conv3x3_wgrad_bf16_launch(*o, s);
+    case LVAE_WGRAD_VARIANT_WINO: return conv_wgrad_wino_launch(o, n, s);
+    case LVAE_WGRAD_VARIANT_DIRECT_1X1: return conv1x1_wgrad_launch(*o, s);
+    case LVAE_WGRAD_VARIANT_TILE: return conv_wgrad_tile_launch(o, n, s);
+    case LVAE_WGRAD_VARIANT_THIN: return thin_wgrad_launch(*o, s);
+    default: return generic_wgrad_launch(*o, s);
+  }
+}
+
+static const std::pair<int32_t, int> kWgradGroupings[] = {   // (variant, capacity) of the families with a grouped launch, in issue order
+    {LVAE_WGRAD_VARIANT_TILE, kWgradTileGroup}, {LVAE_WGRAD_VARIANT_WINO, kWgradWinoGroup}, {LVAE_WGRAD_VARIANT_IMG, kWgradImgGroup}};
+constexpr int kWgradMaxGroup = std::max({kWgradTileGroup, kWgradWinoGroup, kWgradImgGroup});
+
+// How n routed gradients go out, as the entries of each launch in issue order; a pure function of the plans. First the groups: family by
+// family, by ascending key inside a family, entries in index order, a full group flushed at the family's capacity. Then, one by one in
+// index order, everything else: plans without a key, and a tile or Winograd gradient left alone in its group (those two families have a
+// single-gradient kernel; the whole-image family has one kernel, so its group of one stays in place).
+static std::vector<std::vector<int>> wgrad_schedule(const WgradOp* ops, int n) {
+  std::vector<std::vector<int>> launches;
+  std::vector<char> grouped(n, 0);
+  for (const auto& [variant, cap] : kWgradGroupings) {
+    std::map<int32_t, std::vector<int>> members;   // key -> its entries
+    for (int i = 0; i < n; ++i)
+      if (ops[i].plan.variant == variant && ops[i].plan.group >= 0) members[ops[i].plan.group].push_back(i);
+    for (const auto& km : members)
+      for (size_t m0 = 0; m0 < km.second.size(); m0 += cap) {
+        const size_t m1 = std::min(km.second.size(), m0 + cap);
+        if (m1 - m0 == 1 && variant != LVAE_WGRAD_VARIANT_IMG) continue;
+        launches.emplace_back(km.second.begin() + m0, km.second.begin() + m1);
+        for (const int i : launches.back()) grouped[i] = 1;
+      }
+  }
+  for (int i = 0; i < n; ++i)
+    if (!grouped[i]) launches.push_back({i});
+  return launches;
+}
+
+// the checks of one gradient's operands against its routed plan (have: the bytes behind o.workspace; who: the entry point, and the entry)
+static int wgrad_op_check(const WgradOp& o, size_t have, const char* who) {
+  LVAE_REQUIRE(have >= o.plan.workspace, LVAE_EWORKSPACE,
+               "%s: workspace %zu < %zu (the kernel taken for this dy / workspace alignment; lvae_conv2d_wgrad_workspace assumes 16-byte "
+               "aligned ones)", who, have, o.plan.workspace);
+  LVAE_REQUIRE((o.d->x_dtype == LVAE_DT_F32 && o.d->y_dtype == LVAE_DT_F32) || o.plan.takes_bf16_storage, LVAE_EINVAL,
+               "%s: bf16-stored x / dy need the bf16 weight-gradient kernel, which does not take this shape (lvae_resblock_bf16_storage(d) == 0)", who);
+  return 0;
 }
 
 }  // namespace lvae
@@ -503,84 +616,35 @@ extern "C" int32_t lvae_conv2d_wgrad_variant(const lvae_conv_desc* d) {
   return d ? wgrad_route(d, true, true).variant : LVAE_WGRAD_VARIANT_GENERIC;
 }
 
+extern "C" int32_t lvae_conv2d_wgrad_apply_ok(const lvae_conv_desc* d) { return d && wgrad_route(d, true, true).apply_ok ? 1 : 0; }
+
 extern "C" int lvae_conv2d_wgrad_f32(const lvae_conv_desc* d, const float* dy, float* dw, float* db, void* workspace,
                                      size_t workspace_bytes, void* stream) {
   int rc = conv_desc_check(d, "lvae_conv2d_wgrad_f32");
   if (rc) return rc;
   LVAE_REQUIRE(dy && dw && workspace, LVAE_EINVAL, "lvae_conv2d_wgrad_f32: null dy/dw/workspace");
-  const WgradRoute r = wgrad_route(d, al16(dy), al16(workspace));
-  LVAE_REQUIRE(workspace_bytes >= r.workspace, LVAE_EWORKSPACE,
-               "lvae_conv2d_wgrad_f32: workspace %zu < %zu (the kernel taken for this dy / workspace alignment; lvae_conv2d_wgrad_workspace "
-               "assumes 16-byte aligned ones)", workspace_bytes, r.workspace);
-  LVAE_REQUIRE((d->x_dtype == LVAE_DT_F32 && d->y_dtype == LVAE_DT_F32) || r.variant == LVAE_WGRAD_VARIANT_IMG || r.variant == LVAE_WGRAD_VARIANT_BF16,
-               LVAE_EINVAL,
-               "lvae_conv2d_wgrad_f32: bf16-stored x / dy need the bf16 weight-gradient kernel, which does not take this shape "
-               "(lvae_resblock_bf16_storage(d) == 0)");
-  hipStream_t s = (hipStream_t)stream;
-  switch (r.variant) {
-    case LVAE_WGRAD_VARIANT_IMG: return conv_wgrad_img_launch(d, dy, dw, db, workspace, s);
-    case LVAE_WGRAD_VARIANT_BF16: return conv3x3_wgrad_bf16_launch(d, dy, dw, db, workspace, s);
-    case LVAE_WGRAD_VARIANT_WINO: return conv_wgrad_wino_launch(d, dy, dw, db, workspace, s);
-    case LVAE_WGRAD_VARIANT_DIRECT_1X1: return conv1x1_wgrad_launch(d, dy, dw, db, workspace, s);
-    case LVAE_WGRAD_VARIANT_TILE: return conv_wgrad_tile_launch(d, dy, dw, db, workspace, s);
-  }
-  if (r.variant == LVAE_WGRAD_VARIANT_THIN) {
-    ThinWgradArgs ta;
-    ta.d = *d;
-    ta.dy = dy;
-    ta.K = d->KH * d->KW * d->C1;
-    ta.PH = d->H + 2 * d->pad;
-    ta.PW = d->W + 2 * d->pad;
-    ta.slab_w = static_cast<float*>(workspace);
-    ta.slab_b = db ? ta.slab_w + (size_t)d->N * ta.K * d->Cout : nullptr;
-    const size_t lds = ((size_t)(ta.PH * ta.PW * d->C1 + 3) / 4 * 4 + (size_t)d->OH * d->OW * 64) * sizeof(float);
-    rc = launch_lds<conv_wgrad_thin_kernel>("conv_wgrad_thin", dim3(d->N), dim3(256), lds, 160 * 1024, s, ta);
-    if (rc) return rc;
-    wgrad_reduce_launch(ta.slab_w, ta.slab_b, d->N, d->KH * d->KW, d->C1, d->Cout, d->w_stap, d->w_sk, d->w_sn, dw, db, s);
-    LVAE_LAUNCH_CHECK("conv2d_wgrad_reduce");
-    return 0;
-  }
-  WgradArgs a;
-  a.d = *d;
-  a.dy = dy;
-  a.M = d->N * d->OH * d->OW;
-  a.ohw = d->OH * d->OW;
-  a.Cin = d->C1 + d->C2;
-  a.ntaps = d->KH * d->KW;
-  wgrad_plan(d, a.ksplit, a.px_per_split, a.ncit, a.ncot);
-  a.slab_w = static_cast<float*>(workspace);
-  a.slab_b = db ? a.slab_w + (size_t)a.ksplit * a.ntaps * a.Cin * d->Cout : nullptr;
-  const bool xv = (d->C1 % 4 == 0) && (d->C2 % 4 == 0) && al16(d->x) && (!d->x2 || al16(d->x2)) &&
-                  (!d->in_scale || (al16(d->in_scale) && al16(d->in_shift)));
-  const bool yv = (d->Cout % 4 == 0) && al16(dy);
-  const int grid = a.ksplit * a.ncot * a.ncit * a.ntaps;
-  if (xv && yv) hipLaunchKernelGGL((conv_wgrad_kernel<true, true>), dim3(grid), dim3(256), 0, s, a);
-  else if (xv) hipLaunchKernelGGL((conv_wgrad_kernel<true, false>), dim3(grid), dim3(256), 0, s, a);
-  else if (yv) hipLaunchKernelGGL((conv_wgrad_kernel<false, true>), dim3(grid), dim3(256), 0, s, a);
-  else hipLaunchKernelGGL((conv_wgrad_kernel<false, false>), dim3(grid), dim3(256), 0, s, a);
-  LVAE_LAUNCH_CHECK("conv2d_wgrad");
-  wgrad_reduce_launch(a.slab_w, a.slab_b, a.ksplit, a.ntaps, a.Cin, d->Cout, d->w_stap, d->w_sk, d->w_sn, dw, db, s);
-  LVAE_LAUNCH_CHECK("conv2d_wgrad_reduce");
-  return 0;
-}
-
-extern "C" int32_t lvae_conv2d_wgrad_apply_ok(const lvae_conv_desc* d) {
-  return d != nullptr && d->precision == LVAE_PREC_F32 && wgrad_route(d, true, true).variant == LVAE_WGRAD_VARIANT_WINO && conv_wgrad_wino_apply_ok(d) ? 1 : 0;
+  const WgradOp o{d, wgrad_route(d, al16(dy), al16(workspace)), dy, dw, db, workspace};
+  rc = wgrad_op_check(o, workspace_bytes, "lvae_conv2d_wgrad_f32");
+  return rc ? rc : wgrad_launch(&o, 1, (hipStream_t)stream);
 }
 
 extern "C" int lvae_conv2d_wgrad_apply_f32(const lvae_conv_desc* d, const lvae_bn_apply* ap, float* dw, float* db, void* workspace,
                                            size_t workspace_bytes, void* stream) {
-  int rc = conv_desc_check(d, "lvae_conv2d_wgrad_apply_f32");
+  const char* who = "lvae_conv2d_wgrad_apply_f32";
+  int rc = conv_desc_check(d, who);
   if (rc) return rc;
-  LVAE_REQUIRE(lvae_conv2d_wgrad_apply_ok(d), LVAE_EINVAL,
-               "lvae_conv2d_wgrad_apply_f32: shape not supported (the Winograd-domain fp32 weight gradient of a 64 -> 64 layer, W = 16 or 32): "
-               "use lvae_affine_act_bwd_parts_f32 + lvae_conv2d_wgrad_f32");
+  const WgradOp o{d, wgrad_route(d, true, true), nullptr, dw, db, workspace};
+  LVAE_REQUIRE(o.plan.apply_ok, LVAE_EINVAL,
+               "%s: shape not supported (the Winograd-domain fp32 weight gradient of a 64 -> 64 layer, W = 16 or 32): "
+               "use lvae_affine_act_bwd_parts_f32 + lvae_conv2d_wgrad_f32", who);
   LVAE_REQUIRE(ap && ap->parts && ap->rows > 0 && ap->M == (int64_t)d->N * d->H * d->W && ap->coef && ap->dh && ap->x && ap->out && ap->add == nullptr &&
                    ap->dh_bf16 == 0 && dw && workspace,
-               LVAE_EINVAL, "lvae_conv2d_wgrad_apply_f32: needs parts / rows, M = N*H*W, the coefficient block, fp32 dh, x and out, no add");
-  LVAE_REQUIRE(workspace_bytes >= lvae_conv2d_wgrad_workspace(d), LVAE_EWORKSPACE, "lvae_conv2d_wgrad_apply_f32: workspace %zu < %zu", workspace_bytes,
-               lvae_conv2d_wgrad_workspace(d));
-  return conv_wgrad_wino_apply_launch(d, ap, dw, db, workspace, (hipStream_t)stream);
+               LVAE_EINVAL, "%s: needs parts / rows, M = N*H*W, the coefficient block, fp32 dh, x and out, no add", who);
+  LVAE_REQUIRE(workspace_bytes >= o.plan.workspace, LVAE_EWORKSPACE, "%s: workspace %zu < %zu", who, workspace_bytes, o.plan.workspace);
+  const void* const operand[] = {workspace, ap->parts, ap->coef, ap->dh, ap->x, ap->out, ap->drop};
+  const char* const name[] = {"workspace", "ap->parts", "ap->coef", "ap->dh", "ap->x", "ap->out", "ap->drop"};
+  for (int i = 0; i < 7; ++i) LVAE_REQUIRE(al16_or_null(operand[i]), LVAE_EALIGN, "%s: %s must be 16-byte aligned", who, name[i]);
+  return conv_wgrad_wino_apply_launch(o, ap, (hipStream_t)stream);
 }
 
 extern "C" int lvae_conv2d_wgrad_bf16(const lvae_conv_desc* d, const float* dy, float* dw, float* db, void* workspace,
@@ -591,86 +655,54 @@ extern "C" int lvae_conv2d_wgrad_bf16(const lvae_conv_desc* d, const float* dy, 
   return lvae_conv2d_wgrad_f32(&dd, dy, dw, db, workspace, workspace_bytes, stream);
 }
 
-// n independent weight gradients; same result as n calls of lvae_conv2d_wgrad_f32. Launches that share a tile-kernel
-// variant and are float4-aligned go out together (<= 12 per launch), everything else one by one.
+// n independent weight gradients; same result as n calls of lvae_conv2d_wgrad_f32. Every entry is routed once (again only where its dy or
+// its workspace is not 16-byte aligned) and owns a 256-byte aligned piece of the workspace; wgrad_schedule says which entries share a launch.
+static size_t wgrad_piece(const WgradPlan& aligned) { return (aligned.workspace + 255) / 256 * 256; }
+
 extern "C" size_t lvae_conv2d_wgrad_grouped_workspace(const lvae_conv_desc* descs, int32_t n) {
   size_t tot = 0;
-  for (int i = 0; descs && i < n; ++i) tot += (lvae_conv2d_wgrad_workspace(&descs[i]) + 255) / 256 * 256;
+  for (int i = 0; descs && i < n; ++i) tot += wgrad_piece(wgrad_route(&descs[i], true, true));
   return tot;
+}
+
+extern "C" int32_t lvae_conv2d_wgrad_grouped_schedule(const lvae_conv_desc* descs, int32_t n, int32_t* launch_of) {
+  if (!descs || !launch_of || n <= 0) return 0;
+  std::vector<WgradOp> ops(n);
+  for (int i = 0; i < n; ++i) ops[i].plan = wgrad_route(&descs[i], true, true);
+  const std::vector<std::vector<int>> launches = wgrad_schedule(ops.data(), n);
+  for (size_t l = 0; l < launches.size(); ++l)
+    for (const int i : launches[l]) launch_of[i] = (int32_t)l;
+  return (int32_t)launches.size();
 }
 
 extern "C" int lvae_conv2d_wgrad_grouped_f32(const lvae_conv_desc* descs, const float* const* dy, float* const* dw,
                                              float* const* db, int32_t n, void* workspace, size_t workspace_bytes,
                                              void* stream) {
-  LVAE_REQUIRE(descs && dy && dw && db && n > 0 && n <= 4096 && workspace, LVAE_EINVAL, "lvae_conv2d_wgrad_grouped_f32: bad arguments");
-  LVAE_REQUIRE(workspace_bytes >= lvae_conv2d_wgrad_grouped_workspace(descs, n), LVAE_EWORKSPACE,
-               "lvae_conv2d_wgrad_grouped_f32: workspace %zu < %zu", workspace_bytes, lvae_conv2d_wgrad_grouped_workspace(descs, n));
-  std::vector<void*> ws(n);
-  std::vector<size_t> wsb(n);
-  std::vector<int> kind(n);
-  char* wp = static_cast<char*>(workspace);
+  const char* who = "lvae_conv2d_wgrad_grouped_f32";
+  LVAE_REQUIRE(descs && dy && dw && db && n > 0 && n <= 4096 && workspace, LVAE_EINVAL, "%s: bad arguments", who);
+  std::vector<WgradOp> ops(n);
+  char* ws = static_cast<char*>(workspace);
   for (int i = 0; i < n; ++i) {
-    const lvae_conv_desc& d = descs[i];
-    int rc = conv_desc_check(&d, "lvae_conv2d_wgrad_grouped_f32");
+    const lvae_conv_desc* d = &descs[i];
+    int rc = conv_desc_check(d, who);
     if (rc) return rc;
-    LVAE_REQUIRE(dy[i] && dw[i], LVAE_EINVAL, "lvae_conv2d_wgrad_grouped_f32: null dy/dw at %d", i);
-    ws[i] = wp;
-    wsb[i] = (lvae_conv2d_wgrad_workspace(&d) + 255) / 256 * 256;
-    wp += wsb[i];
-    const WgradRoute r = wgrad_route(&d, al16(dy[i]), al16(ws[i]));
-    LVAE_REQUIRE(r.workspace <= wsb[i], LVAE_EWORKSPACE, "lvae_conv2d_wgrad_grouped_f32: entry %d needs %zu workspace bytes for its dy / workspace alignment, has %zu",
-                 i, r.workspace, wsb[i]);
-    // kinds 100 + ...: whole-image tiles (conv_wgrad_img.hip); 0-4: tile kernel variants; 5-7: Winograd kernel for W = 8 / 16 / 32 (grouped
-    // only while one problem leaves CUs idle); -1: launched one by one (lvae_conv2d_wgrad_f32 below)
-    static const int64_t wino_group_max = tune("LVAE_WINO_GROUP_MAX_M", 65536);
-    kind[i] = -1;
-    if (r.variant == LVAE_WGRAD_VARIANT_IMG) kind[i] = 100 + conv_wgrad_img_kind(&d);
-    else if (r.variant == LVAE_WGRAD_VARIANT_WINO && (int64_t)d.N * d.H * d.W < wino_group_max) kind[i] = d.W == 8 ? 5 : (d.W == 16 ? 6 : 7);
-    else if (r.variant == LVAE_WGRAD_VARIANT_TILE && d.Cout % 4 == 0 && (d.C1 + d.C2) % 4 == 0) kind[i] = conv_wgrad_tile_kind(&d);
-  }
-  std::vector<char> done(n, 0);
-  std::vector<int> kinds;   // the distinct kinds present, ascending
-  for (int i = 0; i < n; ++i)
-    if (kind[i] >= 0 && std::find(kinds.begin(), kinds.end(), kind[i]) == kinds.end()) kinds.push_back(kind[i]);
-  std::sort(kinds.begin(), kinds.end());
-  for (int k : kinds) {
-    constexpr int kCap = 32;
-    const int cap = k >= 100 ? kCap : 12;
-    const lvae_conv_desc* gd[kCap];
-    const float* gy[kCap];
-    float* gw[kCap];
-    float* gb[kCap];
-    void* gs[kCap];
-    int idx[kCap];
-    int m = 0;
-    auto flush = [&]() -> int {
-      if (m == 0 || (m == 1 && k < 100)) {   // (a lone tile / Winograd problem goes out one by one below; img: the same kernel)
-        m = 0;
-        return 0;
-      }
-      int rc;
-      if (k >= 100) rc = conv_wgrad_img_grouped(gd, gy, gw, gb, gs, m, k - 100, (hipStream_t)stream);
-      else if (k >= 5) rc = conv_wgrad_wino_grouped(gd, gy, gw, gb, gs, m, (hipStream_t)stream);
-      else rc = conv_wgrad_tile_grouped(gd, gy, gw, gb, gs, m, k, (hipStream_t)stream);
-      if (rc == 0)
-        for (int j = 0; j < m; ++j) done[idx[j]] = 1;
-      m = 0;
-      return rc;
-    };
-    for (int i = 0; i < n; ++i) {
-      if (kind[i] != k) continue;
-      gd[m] = &descs[i]; gy[m] = dy[i]; gw[m] = dw[i]; gb[m] = db[i]; gs[m] = ws[i]; idx[m] = i;
-      if (++m == cap) {
-        int rc = flush();
-        if (rc) return rc;
-      }
-    }
-    int rc = flush();
+    LVAE_REQUIRE(dy[i] && dw[i], LVAE_EINVAL, "%s: null dy/dw at %d", who, i);
+    WgradPlan p = wgrad_route(d, true, true);
+    const size_t piece = wgrad_piece(p);
+    LVAE_REQUIRE((size_t)(ws - static_cast<char*>(workspace)) + piece <= workspace_bytes, LVAE_EWORKSPACE, "%s: workspace %zu < %zu", who,
+                 workspace_bytes, lvae_conv2d_wgrad_grouped_workspace(descs, n));
+    if (!al16(dy[i]) || !al16(ws)) p = wgrad_route(d, al16(dy[i]), al16(ws));
+    ops[i] = WgradOp{d, p, dy[i], dw[i], db[i], ws};
+    char entry[64];
+    snprintf(entry, sizeof entry, "%s: entry %d", who, i);
+    rc = wgrad_op_check(ops[i], piece, entry);
     if (rc) return rc;
+    ws += piece;
   }
-  for (int i = 0; i < n; ++i) {
-    if (done[i]) continue;
-    int rc = lvae_conv2d_wgrad_f32(&descs[i], dy[i], dw[i], db[i], ws[i], wsb[i], stream);
+  WgradOp group[kWgradMaxGroup];
+  for (const std::vector<int>& l : wgrad_schedule(ops.data(), n)) {
+    for (size_t j = 0; j < l.size(); ++j) group[j] = ops[l[j]];
+    const int rc = wgrad_launch(group, (int)l.size(), (hipStream_t)stream);
     if (rc) return rc;
   }
   return 0;

@@ -42,9 +42,8 @@ struct WgImgProb {
   uint32_t m_hw, m_w, m_per_img, m_halo_w;
 };
 static_assert(sizeof(WgImgProb) == 112, "argument block layout");
-constexpr int kWgImgMax = 32;
 struct WgImgGroup {
-  WgImgProb p[kWgImgMax];
+  WgImgProb p[kWgradImgGroup];
 };
 static_assert(sizeof(WgImgGroup) <= 4096, "kernel argument block");
 
@@ -277,16 +276,14 @@ static int wgi_plan(const lvae_conv_desc* d, WgImgProb& a) {
   return (k3 ? 0 : 1) | ((d->precision == LVAE_PREC_BF16 ? 1 : 0) << 1) | (xv << 2);
 }
 
-size_t conv_wgrad_img_workspace(const lvae_conv_desc* d) {
+// group key: the kind (one kernel instantiation per kind)
+bool conv_wgrad_img_plan(const lvae_conv_desc* d, WgradPlan& p) {
   WgImgProb a;
-  if (wgi_plan(d, a) < 0) return 0;
-  const size_t ntap = d->KH * d->KW;
-  return (size_t)a.nwg * (ntap * a.Cin * a.Cout + a.Cout) * sizeof(float);
-}
-
-int conv_wgrad_img_kind(const lvae_conv_desc* d) {
-  WgImgProb a;
-  return wgi_plan(d, a);
+  const int kind = wgi_plan(d, a);
+  if (kind < 0) return false;
+  p.group = kind;
+  p.set_slabs(a.nwg, (size_t)d->KH * d->KW * a.Cin * a.Cout, a.Cout);
+  return true;
 }
 
 template <int KIND, int SPLIT, int XV>
@@ -305,33 +302,33 @@ static int wgi_launch_xv(const WgImgGroup& g, int n, int max_wgs, size_t lds, in
   }
 }
 
-// n <= kWgImgMax descriptors of one kind (conv_wgrad_img_kind) whose route is this kernel (aligned dy and workspace), each with its own
-// workspace: one launch + grouped fixed-order reduces.
-int conv_wgrad_img_grouped(const lvae_conv_desc* const* ds, const float* const* dy, float* const* dw, float* const* db,
-                           void* const* workspace, int n, int kind, hipStream_t s) {
+// n <= kWgradImgGroup gradients of one plan.group, each with its own workspace: one launch + grouped fixed-order reduces. A single
+// gradient is a group of one (the same kernel, tiling and summation order: bitwise equal to any grouping).
+int conv_wgrad_img_grouped(const WgradOp* o, int n, hipStream_t s) {
   WgImgGroup g;
-  ReduceArgs r[kWgImgMax];
+  ReduceArgs r[kWgradImgGroup];
   int max_wgs = 0;
   size_t lds = 0;
+  const int kind = o[0].plan.group;
   const int split = (kind >> 1) & 1 ? 1 : 3;
   for (int i = 0; i < n; ++i) {
+    const lvae_conv_desc* d = o[i].d;
     WgImgProb& a = g.p[i];
-    wgi_plan(ds[i], a);
-    const int ntap = ds[i]->KH * ds[i]->KW;
-    a.x = ds[i]->x;
-    a.dy = dy[i];
-    a.in_scale = ds[i]->in_scale;
-    a.in_shift = ds[i]->in_shift;
-    a.slab_w = static_cast<float*>(workspace[i]);
-    a.slab_b = db[i] ? a.slab_w + (size_t)a.nwg * ntap * a.Cin * a.Cout : nullptr;
+    wgi_plan(d, a);
+    a.x = d->x;
+    a.dy = o[i].dy;
+    a.in_scale = d->in_scale;
+    a.in_shift = d->in_shift;
+    a.slab_w = o[i].slab_w();
+    a.slab_b = o[i].slab_b();
     if (a.nwg > max_wgs) max_wgs = a.nwg;
     const int ldd = (kind & 1) ? WGI_LDD1 : WGI_LDK;
     size_t l = (size_t)split * ((size_t)a.halo_px * WGI_LDK + 64 * ldd) * 2;
     if (l < 16 * 128 * 4) l = 16 * 128 * 4;   // bias-gradient reduction
     if (l > lds) lds = l;
-    r[i] = ReduceArgs{a.slab_w, a.slab_b, a.nwg, ntap, a.Cin, a.Cout, ds[i]->w_stap, ds[i]->w_sk, ds[i]->w_sn, dw[i], db[i]};
+    r[i] = ReduceArgs{a.slab_w, a.slab_b, a.nwg, d->KH * d->KW, a.Cin, a.Cout, d->w_stap, d->w_sk, d->w_sn, o[i].dw, o[i].db};
   }
-  for (int i = n; i < kWgImgMax; ++i) g.p[i] = g.p[0];
+  for (int i = n; i < kWgradImgGroup; ++i) g.p[i] = g.p[0];
   const int xv = kind >> 2;
   int rc;
   if (kind & 1) rc = split == 1 ? wgi_launch_xv<1, 1>(g, n, max_wgs, lds, xv, s) : wgi_launch_xv<1, 3>(g, n, max_wgs, lds, xv, s);
@@ -342,11 +339,6 @@ int conv_wgrad_img_grouped(const lvae_conv_desc* const* ds, const float* const* 
     LVAE_LAUNCH_CHECK("conv_wgrad_img_reduce");
   }
   return 0;
-}
-
-// one gradient: the grouped launch with one problem (the same kernel, tiling and summation order: bitwise equal to the grouped call)
-int conv_wgrad_img_launch(const lvae_conv_desc* d, const float* dy, float* dw, float* db, void* workspace, hipStream_t s) {
-  return conv_wgrad_img_grouped(&d, &dy, &dw, &db, &workspace, 1, conv_wgrad_img_kind(d), s);
 }
 
 }  // namespace lvae

@@ -29,6 +29,32 @@ struct ReduceArgs {
 };
 constexpr int kMaxReduceGroup = 12;  // problems per wgrad_reduce_grouped_launch
 
+// One weight-gradient kernel family's accepted choice for a descriptor, by the rule of ConvPlan: <family>_plan() fills it and returns false
+// when the family does not take the descriptor; the family's launches run that plan and cannot decline. The alignment a family needs from
+// dy and the workspace stands in the table of the route (conv_wgrad.hip), which walks the plans once per gradient and sets `variant`.
+struct WgradPlan {
+  int32_t variant = LVAE_WGRAD_VARIANT_GENERIC;  // LVAE_WGRAD_VARIANT_*
+  int32_t group = -1;                 // key inside the family: plans of equal (variant, group) may share one grouped launch; -1: never grouped
+  int32_t slabs = 0;                  // partial slabs the launch writes (ksplit / workgroups / ranges)
+  size_t w_floats = 0, b_floats = 0;  // one slab's weight part and its bias row: the workspace is [slabs][w_floats] then [slabs][b_floats]
+  size_t workspace = 0;               // bytes
+  bool takes_bf16_storage = false, apply_ok = false;  // bf16-stored x / dy accepted; deferred BatchNorm apply as dY accepted
+  void set_slabs(int n, size_t w, size_t b) { slabs = n, w_floats = w, b_floats = b, workspace = (size_t)n * (w + b) * sizeof(float); }
+};
+
+// One gradient as a launch sees it: descriptor, routed plan, the operands outside the descriptor (db may be null)
+struct WgradOp {
+  const lvae_conv_desc* d;
+  WgradPlan plan;
+  const float* dy;
+  float *dw, *db;
+  void* workspace;
+  float* slab_w() const { return static_cast<float*>(workspace); }
+  float* slab_b() const { return db ? slab_w() + (size_t)plan.slabs * plan.w_floats : nullptr; }
+};
+// gradients per grouped launch of the families that have one: each sizes its family's p[] argument array and bounds the scheduler's groups
+constexpr int kWgradTileGroup = 12, kWgradWinoGroup = 12, kWgradImgGroup = 32;
+
 // conv_igemm.hip
 int conv_desc_check(const lvae_conv_desc* d, const char* who);
 
@@ -57,8 +83,8 @@ int conv3x3_bf16_prepare_batched(const void* entries, int n, int npad, hipStream
 size_t resblock_gate_ws_bytes(const lvae_conv_desc* d, int planes);
 void resblock_gate_prep_entry(const lvae_conv_desc* d, int planes, void* entry);
 int resblock_gate_prepare_single(const lvae_conv_desc* d, int planes, hipStream_t s);
-size_t conv3x3_wgrad_bf16_workspace(const lvae_conv_desc* d);
-int conv3x3_wgrad_bf16_launch(const lvae_conv_desc* d, const float* dy, float* dw, float* db, void* workspace, hipStream_t s);
+bool conv3x3_wgrad_bf16_plan(const lvae_conv_desc* d, WgradPlan& p);
+int conv3x3_wgrad_bf16_launch(const WgradOp& o, hipStream_t s);
 
 // conv1x1.hip: the single-shot kernel. PwForm says which form of it a launch is and carries that form's operands outside the descriptor
 // (the plan reads kind and split only: it assumes those operands 16-byte aligned, the entry points check them).
@@ -88,32 +114,24 @@ bool conv1x1_gate_bwd_fused_plan(const lvae_conv_desc* d, bool with_apply, ConvP
 void wgrad_reduce_launch(const float* slab_w, const float* slab_b, int ksplit, int ntaps, int Cin, int Cout, int64_t stap,
                          int64_t sk, int64_t sn, float* dw, float* db, hipStream_t s);
 void wgrad_reduce_grouped_launch(const ReduceArgs* r, int n, hipStream_t s);
+int wgrad_op_reduce(const WgradOp& o, hipStream_t s);  // one gradient's slabs as its plan lays them out, launch checked
 
-// conv_wgrad_img.hip: whole-image tiles of the <= 8x8 levels on the bf16 matrix pipe, up to 32 gradients per launch
-size_t conv_wgrad_img_workspace(const lvae_conv_desc* d);
-int conv_wgrad_img_kind(const lvae_conv_desc* d);
-int conv_wgrad_img_grouped(const lvae_conv_desc* const* ds, const float* const* dy, float* const* dw, float* const* db,
-                           void* const* workspace, int n, int kind, hipStream_t s);
-int conv_wgrad_img_launch(const lvae_conv_desc* d, const float* dy, float* dw, float* db, void* workspace, hipStream_t s);
+// conv_wgrad_img.hip: whole-image tiles of the <= 8x8 levels on the bf16 matrix pipe; a single gradient is a group of one
+bool conv_wgrad_img_plan(const lvae_conv_desc* d, WgradPlan& p);
+int conv_wgrad_img_grouped(const WgradOp* o, int n, hipStream_t s);
 
 // conv3x3_wgrad_halo.hip
-size_t conv_wgrad_tile_workspace(const lvae_conv_desc* d);
-int conv_wgrad_tile_kind(const lvae_conv_desc* d);
-int conv_wgrad_tile_grouped(const lvae_conv_desc* const* ds, const float* const* dy, float* const* dw, float* const* db,
-                            void* const* workspace, int n, int kind, hipStream_t s);
-int conv_wgrad_tile_launch(const lvae_conv_desc* d, const float* dy, float* dw, float* db, void* workspace, hipStream_t s);
+bool conv_wgrad_tile_plan(const lvae_conv_desc* d, WgradPlan& p);
+int conv_wgrad_tile_launch(const WgradOp* o, int n, hipStream_t s);  // n = 1: the single kernel, else the grouped one
 
-// conv3x3_wgrad_wino.hip
-size_t conv_wgrad_wino_workspace(const lvae_conv_desc* d);
-int conv_wgrad_wino_grouped(const lvae_conv_desc* const* ds, const float* const* dy, float* const* dw, float* const* db,
-                            void* const* workspace, int n, hipStream_t s);
-int conv_wgrad_wino_launch(const lvae_conv_desc* d, const float* dy, float* dw, float* db, void* workspace, hipStream_t s);
-bool conv_wgrad_wino_apply_ok(const lvae_conv_desc* d);
-int conv_wgrad_wino_apply_launch(const lvae_conv_desc* d, const lvae_bn_apply* ap, float* dw, float* db, void* workspace, hipStream_t s);
+// conv3x3_wgrad_wino.hip (ap: the deferred BatchNorm-backward apply that forms dY, for a plan with apply_ok)
+bool conv_wgrad_wino_plan(const lvae_conv_desc* d, WgradPlan& p);
+int conv_wgrad_wino_launch(const WgradOp* o, int n, hipStream_t s);  // n = 1: the single kernel, else the grouped one
+int conv_wgrad_wino_apply_launch(const WgradOp& o, const lvae_bn_apply* ap, hipStream_t s);
 
 // conv1x1_wgrad.hip
-size_t conv1x1_wgrad_workspace(const lvae_conv_desc* d);
-int conv1x1_wgrad_launch(const lvae_conv_desc* d, const float* dy, float* dw, float* db, void* workspace, hipStream_t s);
+bool conv1x1_wgrad_plan(const lvae_conv_desc* d, WgradPlan& p);
+int conv1x1_wgrad_launch(const WgradOp& o, hipStream_t s);
 
 // Launch of a kernel whose dynamic LDS may exceed the 64 KB default: raises the kernel's limit to max_lds the first time THIS kernel is
 // launched (one flag per kernel: the template argument), launches, checks. name: as it appears in lvae_last_error().

@@ -10,6 +10,11 @@ The 1x1 gate / concat-dgrad family (`gate:` and `merge:` cases, also with form F
 gate forward and its statistics rows on the forward view, the single-shot gate backward, the persistent gate backward's workspace and
 whether it takes a deferred apply on the 128 -> 64 dgrad view, and the one-launch concat dgrad of a merge convolution at split = C1.
 DECLINES lists descriptors those kernels refuse, with the answers written down from the kernels' conditions.
+
+The weight gradient is routed through one ordered table of kernel families (img -> bf16 -> Winograd -> 1x1 -> tile -> thin -> generic).
+WGRAD_DECLINES lists descriptors one family refuses and the next takes. `schedule:` cases are the answer of
+lvae_conv2d_wgrad_grouped_schedule, [launches, launch_of...], for the forward convolutions of a config and for the synthetic lists
+SCHEDULE_LISTS at the edges of the grouping rule; tests/test_kernels_gpu.py runs the same lists on the GPU.
 """
 import ctypes as C
 import json
@@ -192,9 +197,94 @@ DECLINES = [   # (name, kind, descriptor factory, expected)
 ]
 
 
+def same_conv_desc(N, H, W, C1, C2, Cout, k, prec=PREC_F32, form=FORM_AUTO):
+    """a stride-1 "same" convolution (k = 1 or 3) as the weight gradient sees it"""
+    return make_desc(N, H, W, H, W, C1, C2, Cout, k, 1, k // 2, GATHER_CONV, Cout, 1, prec, form)
+
+
+# Lists of (N, C1, C2, Cout, H, W, k) stride-1 "same" convolutions whose gradients go out in one grouped call, at the edges of the
+# schedule: a group flushes at its family's capacity (12 tile, 12 Winograd, 32 whole-image), a tile or Winograd gradient left alone goes
+# out singly after all groups, a whole-image group of one stays in place, Winograd groups form per image width and only below 65536 pixels.
+_TILE = (4, 64, 0, 64, 16, 16, 3)         # 1024 pixels: below the Winograd floor, above the whole-image sizes -> tile kernel <64, 3>
+_IMG = (16, 64, 0, 64, 2, 2, 3)           # whole-image kernel, 3x3 kind
+_IMG1 = (20, 64, 0, 128, 4, 4, 1)         # whole-image kernel, 1x1 kind
+_WINO16 = (64, 64, 0, 64, 16, 16, 3)      # 16384 pixels: Winograd, width 16
+_WINO32 = (16, 64, 0, 64, 32, 32, 3)      # 16384 pixels: Winograd, width 32
+_WINO8 = (257, 64, 0, 128, 8, 8, 3)       # Winograd, width 8, two output-channel blocks (64 -> 128 is not a whole-image shape)
+_WINO_BIG = (256, 64, 0, 64, 16, 16, 3)   # 65536 pixels: Winograd, fills the chip alone
+_MERGE = (4, 64, 64, 64, 16, 16, 1)       # merge 1x1 over cat(x, x2): tile kernel <128, 1>
+_ODD = (2, 16, 0, 6, 16, 16, 3)           # Cout % 4 != 0: generic kernel
+SCHEDULE_LISTS = {
+    'tile13': [_TILE] * 13,
+    'img34': [_IMG] * 34,
+    'wino_same_width': [_WINO16, _WINO16],
+    'wino_two_widths': [_WINO16, _WINO32],
+    'wino_65536': [_WINO_BIG, _WINO_BIG],
+    'merge_x2': [_MERGE, _MERGE],
+    'mixed': [_WINO32, _IMG, _ODD, _TILE, _WINO8, _MERGE, _IMG1, _WINO16, _WINO_BIG, _IMG, _WINO8, _TILE, _WINO32, _IMG1, _MERGE, _WINO16,
+              _TILE, _IMG],
+}
+
+
+def schedule(lib, descs):
+    """[launches, launch_of[0], launch_of[1], ...] of lvae_conv2d_wgrad_grouped_schedule"""
+    from lvae_amd._C import ConvDesc
+    n = len(descs)
+    arr = (ConvDesc * n)(*descs)
+    launch_of = (C.c_int32 * n)(*([-1] * n))
+    return [int(lib.lvae_conv2d_wgrad_grouped_schedule(arr, n, launch_of))] + list(launch_of)
+
+
+# Descriptors one weight-gradient family refuses and a later one takes: (name, descriptor factory, [workspace, variant, apply_ok]). The
+# answers follow from the kernels' conditions; every workspace is slabs * (taps * Cin * Cout + Cout) * 4 bytes unless noted.
+WG_GENERIC, WG_IMG, WG_BF16, WG_WINO, WG_1X1, WG_TILE, WG_THIN = range(7)
+_L8 = (256, 8, 8, 64, 0, 64, 3)   # the 8x8 level at batch 256: 16384 pixels, a whole-image shape
+
+
+def _slabs(n, taps, cin, cout):
+    return n * (taps * cin * cout + cout) * 4
+
+
+_WINO_SLAB = 2 * 16 * 32 * 64 + 64   # floats per Winograd range and output-channel block: 2 ci blocks x 16 positions x 32 ci x 64 co, + bias
+WGRAD_DECLINES = [
+    # the whole-image kernel: 64 tiles of one image, 8 per workgroup -> 32 slabs
+    ('8x8 level', lambda: same_conv_desc(*_L8), [_slabs(32, 9, 64, 64), WG_IMG, 0]),
+    # x only 4-byte aligned: img, Winograd and tile all load x in 16-byte pieces; not a stem -> generic, 512 / 9 taps -> 57 pixel ranges
+    ('x+4', lambda: _mod(same_conv_desc(*_L8), x=_fake(1) + 4), [_slabs(57, 9, 64, 64), WG_GENERIC, 0]),
+    # in_scale without in_shift: only img spells the refusal out; Winograd takes it: 256 chunks of 16 tiles, at least 4 per range -> 64
+    # ranges (W = 8: no deferred apply)
+    ('in_scale without in_shift', lambda: _mod(same_conv_desc(*_L8), in_scale=_fake(10)), [64 * _WINO_SLAB * 4, WG_WINO, 0]),
+    # the direct 1x1 kernel starts at 32768 pixels (256 workgroups); one pixel less has an odd width, which the tile kernel refuses -> generic
+    ('1x1 at 32768 pixels', lambda: same_conv_desc(128, 16, 16, 64, 0, 128, 1), [_slabs(256, 1, 64, 128), WG_1X1, 0]),
+    ('1x1 at 32767 pixels', lambda: same_conv_desc(7, 31, 151, 64, 0, 128, 1), [_slabs(64, 1, 64, 128), WG_GENERIC, 0]),
+    # the Winograd floor of 16384 pixels: N = 64 has 256 chunks of 16 tiles, at least 4 per range -> 64 ranges, and takes a deferred apply
+    # (64 -> 64, W = 16); N = 63 goes to the tile kernel, whose two LDS buffers hold 64-pixel tiles of a 16-wide image with 64 input
+    # channels (128-pixel ones need 170 KB) -> 252 tiles, fewer than the 256 workgroups wanted -> 252 slabs
+    ('3x3 at 16384 pixels', lambda: same_conv_desc(64, 16, 16, 64, 0, 64, 3), [64 * _WINO_SLAB * 4, WG_WINO, 1]),
+    ('3x3 at 16128 pixels', lambda: same_conv_desc(63, 16, 16, 64, 0, 64, 3), [_slabs(252, 9, 64, 64), WG_TILE, 0]),
+    # the stem (5x5 stride 2 on 3 channels): the thin kernel wants at least 32 images, one slab each; below, the generic kernel with
+    # 512 / 25 taps -> 21 wanted, 31 * 256 pixels / 256 = 31 possible -> 21 pixel ranges
+    ('stem at N = 32', lambda: make_desc(32, 32, 32, 16, 16, 3, 0, 64, 5, 2, 2, GATHER_CONV, 64, 1, PREC_F32, FORM_AUTO),
+     [_slabs(32, 25, 3, 64), WG_THIN, 0]),
+    ('stem at N = 31', lambda: make_desc(31, 32, 32, 16, 16, 3, 0, 64, 5, 2, 2, GATHER_CONV, 64, 1, PREC_F32, FORM_AUTO),
+     [_slabs(21, 25, 3, 64), WG_GENERIC, 0]),
+    # odd W: the tile kernel pairs pixels -> generic, 960 pixels / 256 -> 4 ranges
+    ('odd W', lambda: same_conv_desc(4, 16, 15, 64, 0, 64, 3), [_slabs(4, 9, 64, 64), WG_GENERIC, 0]),
+    # bf16-stored x at bf16 precision: img wants fp32 storage, the bf16 kernel takes it. 256x16x16: 512 tiles of 128 pixels -> the half-slab
+    # form with 128 pixel ranges; 256x8x8: only 128 tiles of 128 pixels, fewer than CUs -> 256 tiles of 64, 2 per workgroup -> 128 slabs of
+    # the whole-slab form
+    ('bf16 x at bf16, 16x16', lambda: _mod(same_conv_desc(256, 16, 16, 64, 0, 64, 3, PREC_BF16), x_dtype=DT_BF16), [_slabs(128, 9, 64, 64), WG_BF16, 0]),
+    ('bf16 x at bf16, 8x8', lambda: _mod(same_conv_desc(*_L8, PREC_BF16), x_dtype=DT_BF16), [_slabs(128, 9, 64, 64), WG_BF16, 0]),
+    # 64 -> 128 3x3 at 257x8x8: more than img's 64 output channels -> Winograd with two output-channel blocks: 257 chunks, 128 / 2 = 64
+    # ranges wanted -> 5 chunks per range -> 52 ranges
+    ('3x3 64 -> 128 on 8x8', lambda: same_conv_desc(257, 8, 8, 64, 0, 128, 3), [52 * 2 * _WINO_SLAB * 4, WG_WINO, 0]),
+]
+
+
 def table():
     """{case id: answers}. conv: one [workspace, variant, stats_rows, folds, stats_buffer_rows, bf16_storage] per descriptor of
-    variants(); wgrad: [workspace, variant, apply_ok]; grouped: the grouped workspace of all forward convolutions of a config."""
+    variants(); wgrad: [workspace, variant, apply_ok]; grouped: the grouped workspace of all forward convolutions of a config; schedule:
+    how the grouped call issues them, and the lists of SCHEDULE_LISTS."""
     from lvae_amd import _C
     lib = _C.load()
     ask = lambda names, d: [int(getattr(lib, q)(C.byref(d))) for q in names]
@@ -217,6 +307,9 @@ def table():
                         out['conv:' + base] = [ask(CONV_QUERIES, d) for d in variants(m, need, bf16_storage)]
                 arr = (_C.ConvDesc * len(group))(*group)
                 out['grouped:%s/p%d/f%d' % (cname, prec, form)] = int(lib.lvae_conv2d_wgrad_grouped_workspace(arr, len(group)))
+                out['schedule:%s/p%d/f%d' % (cname, prec, form)] = schedule(lib, group)
+    for name, specs in SCHEDULE_LISTS.items():
+        out['schedule:%s/p0/f0' % name] = schedule(lib, [same_conv_desc(N, H, W, C1, C2, Cout, k) for N, C1, C2, Cout, H, W, k in specs])
     out.update(gate_table(lib))
     return out
 
@@ -236,6 +329,19 @@ def test_gate_plan_declines():
             got = [int(lib.lvae_conv1x1_dgrad_cat_ok(C.byref(d), int(kind[3:])))]
         if got != want:
             bad.append('%s (%s): got %s, expected %s' % (name, kind, got, want))
+    assert not bad, '\n'.join(bad)
+
+
+def test_wgrad_plan_declines():
+    import lvae_amd  # noqa: F401
+    from lvae_amd import _C
+    lib = _C.load()
+    bad = []
+    for name, mk, want in WGRAD_DECLINES:
+        d = mk()
+        got = [int(getattr(lib, q)(C.byref(d))) for q in WGRAD_QUERIES]
+        if got != want:
+            bad.append('%s: got %s, expected %s' % (name, got, want))
     assert not bad, '\n'.join(bad)
 
 

@@ -111,7 +111,7 @@ def test_every_struct_is_defined_in_one_file():
 def test_cross_file_interface_is_in_lvae_host_h():
     host = statements(sources('.h')['lvae_host.h'])
     declared = [FUNCTION.match(h).group(1) for k, h, _ in host if k == 'decl' and FUNCTION.match(h)]
-    assert len(declared) == len(set(declared)) and len(declared) >= 40, 'each function once'
+    assert len(declared) == len(set(declared)) and len(declared) >= 38, 'each function once'
     hips = sources('.hip')
     defined = {f: {FUNCTION.match(h).group(1) for k, h, _ in statements(text) if k == 'def' and FUNCTION.match(h)} for f, text in hips.items()}
     code = {f: strip(text) for f, text in hips.items()}

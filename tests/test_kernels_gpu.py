@@ -203,6 +203,93 @@ def test_conv_wgrad_grouped(K):
         assert torch.equal(dw, rw) and torch.equal(db, rb)   # same kernels, same summation order: bitwise equal
 
 
+def test_conv_wgrad_grouped_at_group_edges(K):
+    """lvae_conv2d_wgrad_grouped_f32 on the lists of test_conv_routing.SCHEDULE_LISTS (a group of 12 tile gradients and a 13th alone, 32 + 2
+    whole-image gradients, Winograd groups of widths 16, 8 and 32, Winograd gradients that never group, merge convolutions with x2, all of
+    them shuffled): the schedule query answers what the routing table expects, the grouped results equal the one-by-one calls bit for bit,
+    and each gradient agrees with the float64 one (5e-6 where the Winograd-domain kernel runs, 3e-6 elsewhere, as in the tests above).
+    Gradients accumulate onto non-zero buffers; every fourth entry has no bias gradient."""
+    import json
+    from test_conv_routing import EXPECTED, SCHEDULE_LISTS, schedule
+    with open(EXPECTED) as f:
+        expected = json.load(f)
+    lib = K._C.load()
+    g = torch.Generator().manual_seed(57)
+    shared = {}   # spec -> operands on the device and the float64 gradients, made once
+
+    def operands(spec):
+        if spec not in shared:
+            N, C1, C2, Co, H, W, k = spec
+            Ci = C1 + C2
+            x = torch.randn(N, Ci, H, W, generator=g)
+            w = torch.randn(Co, Ci, k, k, generator=g) / math.sqrt(Ci * k * k)
+            dy = torch.randn(N, Co, H, W, generator=g)
+            xin, kw = x.double(), {}
+            if k == 3:   # the fused BatchNorm-apply + ELU prologue
+                sc, sh = torch.rand(Ci, generator=g) + 0.5, torch.randn(Ci, generator=g) * 0.3
+                xin = F.elu(x.double() * sc.double().view(1, -1, 1, 1) + sh.double().view(1, -1, 1, 1))
+                kw = dict(in_scale=sc.cuda(), in_shift=sh.cuda(), in_act='elu')
+            gw = torch.nn.grad.conv2d_weight(xin, (Co, Ci, k, k), dy.double(), padding=k // 2).float()
+            gb = dy.double().sum((0, 2, 3)).float()
+            wp = packed_weight(w)
+            xd = nhwc(x)
+            if C2:
+                kw['x2'] = xd[..., C1:].contiguous()
+                xd = xd[..., :C1].contiguous()
+            shared[spec] = (xd, nhwc(dy), wp, K.ConvGeom(wp, 1, k // 2), kw, gw, gb)
+        return shared[spec]
+
+    for name, specs in SCHEDULE_LISTS.items():
+        items, ones, descs = [], [], []
+        for i, spec in enumerate(specs):
+            N, C1, C2, Co, H, W, k = spec
+            x, dy, wp, geom, kw, gw, gb = operands(spec)
+            dw0 = torch.randn(Co, C1 + C2, k, k, generator=g) * 0.1
+            db0 = torch.randn(Co, generator=g) if i % 4 != 3 else None
+            one_w, one_b = packed_weight(dw0), (None if db0 is None else db0.cuda())
+            K.conv2d_wgrad(x, dy, wp, geom, one_w, one_b, **kw)
+            ones.append((one_w, one_b, dw0, db0))
+            items.append((x, dy, wp, geom, packed_weight(dw0), None if db0 is None else db0.cuda(), kw))
+            descs.append(K._desc(geom, wp, x, kw.get('x2'), N, H, W, H, W, Co, geom.s_ci, geom.s_co, K.GATHER_CONV, None, kw.get('in_scale'),
+                                 kw.get('in_shift'), kw.get('in_act')))
+        assert schedule(lib, descs) == expected['schedule:%s/p0/f0' % name], name
+        K.conv2d_wgrad_grouped(items)
+        for i, ((x, dy, wp, geom, dw, db, kw), (one_w, one_b, dw0, db0)) in enumerate(zip(items, ones)):
+            assert torch.equal(dw, one_w) and (db is None or torch.equal(db, one_b)), (name, i)
+            gw, gb = operands(specs[i])[5:]
+            tol = 5e-6 if lib.lvae_conv2d_wgrad_variant(ctypes.byref(descs[i])) == K._C.WGRAD_VARIANT_WINO else 3e-6
+            assert rel(dw.cpu() - dw0, gw) < tol, (name, i)
+            assert db is None or rel(db.cpu() - db0, gb) < tol, (name, i)
+
+
+def test_conv_wgrad_apply_names_the_unaligned_operand(K):
+    """lvae_conv2d_wgrad_apply_f32 checks the alignment of the workspace and of each operand of the deferred apply itself: with ap->out one
+    float past a 16-byte boundary it returns LVAE_EALIGN naming `out` and launches nothing (no buffer changes)."""
+    C_ = K._C
+    N, H, W, C = 64, 16, 16, 64
+    g = torch.Generator().manual_seed(12)
+    rn = lambda *s_: torch.randn(*s_, generator=g).cuda()
+    x, dh, xbn = rn(N, H, W, C), rn(N, H, W, C), rn(N, H, W, C)
+    w = packed_weight(torch.randn(C, C, 3, 3, generator=g) / 24)
+    geom = K.ConvGeom(w, 1, 1)
+    assert K.conv2d_wgrad_apply_ok(x, w, geom)
+    coef = K.bn_stats(xbn, None, None, None, None)
+    parts = rn(256, 2, C)
+    d = K._desc(geom, w, x, None, N, H, W, H, W, C, geom.s_ci, geom.s_co, K.GATHER_CONV)
+    need = C_.load().lvae_conv2d_wgrad_workspace(ctypes.byref(d))
+    ws = K.workspace(need, x.device)
+    store = torch.full((N * H * W * C + 4,), 7.0, device='cuda')
+    out = store[1:1 + N * H * W * C]
+    assert out.data_ptr() % 16 == 4
+    dw, db, dgamma, dbeta = torch.ones_like(w), torch.ones(C, device='cuda'), torch.ones(C, device='cuda'), torch.ones(C, device='cuda')
+    ap = C_.BnApply(C_.ptr(parts), parts.shape[0], K.ACT['elu'], N * H * W, C_.ptr(coef[0]), C_.ptr(dh), C_.ptr(xbn), None, C_.ptr(dgamma), C_.ptr(dbeta),
+                    C_.ptr(out), 0, 0, None)
+    with pytest.raises(C_.LvaeHipError, match=r'\(-2\).*\bout\b'):
+        C_.call('lvae_conv2d_wgrad_apply_f32', ctypes.byref(d), ctypes.byref(ap), C_.ptr(dw), C_.ptr(db), ws.data_ptr(), ws.numel(), C_.stream_ptr())
+    torch.cuda.synchronize()
+    assert bool((store == 7.0).all()) and all(bool((t == 1.0).all()) for t in (dw, db, dgamma, dbeta))
+
+
 def test_prepared_weights_cache(K):
     """lvae_conv2d_prepare_weights: one batched transform serves later convolutions; any write to the weights (torch in-place
     op or a raw-pointer kernel announced through weights_written) makes the convolution transform them itself again."""
