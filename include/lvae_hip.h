@@ -588,6 +588,37 @@ int lvae_elbo_loss_fwd_anneal_f32(const float* ll, const float* kl_sep, const fl
 int lvae_elbo_loss_bwd_anneal_f32(const float* g_loss, const int64_t* step, int64_t anneal_steps, int32_t N, float* d_ll,
                                   float* d_kl_loss, void* stream);
 
+/* Training on the K-sample importance-weighted bound (Burda et al.; the reference trains on the single-sample ELBO only, so
+ * there is no call site to name). Rows are sample-major, row n = k*B + b for sample k of image b, the layout of lvae_iw_logmeanexp_f32.
+ *   lw[k][b]   = ll - beta*kl_sep                                   log weight of a row
+ *   bound[b]   = max_k lw + log sum_k exp(lw - max) - log K         [B]
+ *   w[k][b]    = exp(lw - max) / sum_k exp(lw - max)                [K*B], the self-normalised weights the backward reads
+ *   elbo_sep[n] = ll[n] - kl_sep[n]                                 [K*B], as lvae_elbo_loss_fwd_f32 writes it
+ *   scalars[0] = loss = -mean_b bound[b]
+ *          [1] = elbo = mean over the K*B rows of ll - kl_sep (the single-sample ELBO)     [2] = recons = mean of -ll
+ *          [3] = iw = mean_b logmeanexp_k(ll - kl_sep), the bound at beta = 1              [4] = ess = mean_b 1 / sum_k w^2
+ * One workgroup, one thread per image striding over k, double arithmetic, sums in a fixed order and no atomics: the same inputs give the
+ * same bits, launched eagerly or replayed. A row with lw = -inf among finite ones gets weight exactly 0; an image whose rows are all
+ * -inf (or hold +inf) gets torch.logsumexp's bound and torch.softmax's NaN weights. K, B <= 0 or K*B > INT32_MAX: LVAE_EINVAL.
+ * bwd (of `loss` only; the other outputs are metrics): d_ll[n] = -g*w[n]/B, d_kl_sep[n] = g*beta*w[n]/B, g = g_loss[0] on device;
+ * with K = 1 that is exactly -g/B and g*beta/B.
+ * The *_anneal_* pair reads beta = linear_anneal(step[0], 0, 1, anneal_steps) on the device exactly as lvae_elbo_loss_fwd_anneal_f32 does. */
+int lvae_iw_loss_fwd_f32(const float* ll, const float* kl_sep, float beta, int32_t K, int32_t B, float* elbo_sep, float* w, float* bound,
+                         float* scalars, void* stream);
+int lvae_iw_loss_bwd_f32(const float* g_loss, const float* w, float beta, int32_t K, int32_t B, float* d_ll, float* d_kl_sep,
+                         void* stream);
+int lvae_iw_loss_fwd_anneal_f32(const float* ll, const float* kl_sep, const int64_t* step, int64_t anneal_steps, int32_t K, int32_t B,
+                                float* elbo_sep, float* w, float* bound, float* scalars, void* stream);
+int lvae_iw_loss_bwd_anneal_f32(const float* g_loss, const float* w, const int64_t* step, int64_t anneal_steps, int32_t K, int32_t B,
+                                float* d_ll, float* d_kl_sep, void* stream);
+/* Broadcast over samples: the bottom-up pass is a deterministic function of the image, so it runs on B images and each level's output
+ * (and the image the likelihood reads) is repeated for the K samples: out[k][i] = in[i], 0 <= k < K, i < n (n = elements of the B-image
+ * tensor). bwd: din[i] = sum_k dout[k][i] accumulated in fp32 in ascending k, bit for bit the sequential float32 sum. 16-byte accesses
+ * with a scalar tail of n % 4 elements; in / out / dout / din 16-byte aligned (LVAE_EALIGN otherwise). fp32 only: under LVAE_PREC_BF16
+ * the block outputs that cross this point stay fp32 (LVAE_DT_* above). */
+int lvae_repeat_samples_fwd_f32(const float* in, int64_t n, int32_t K, float* out, void* stream);
+int lvae_repeat_samples_bwd_f32(const float* dout, int64_t n, int32_t K, float* din, void* stream);
+
 /* Importance-weighted bound — evaluate.py:30,86-87 (the loop is boilr's test_procedure: S forward passes, then
  * logsumexp - log S). elbo [S,N] (sample-major) -> out[n] = log mean_s exp(elbo[s][n]). */
 int lvae_iw_logmeanexp_f32(const float* elbo, int32_t S, int32_t N, float* out, void* stream);

@@ -160,6 +160,12 @@ SIGNATURES = {
     'lvae_elbo_loss_bwd_f32': (C.c_int, [_P, _F, _I, _P, _P, _P]),
     'lvae_elbo_loss_fwd_anneal_f32': (C.c_int, [_P, _P, _P, _P, _L, _I, _P, _P, _P]),
     'lvae_elbo_loss_bwd_anneal_f32': (C.c_int, [_P, _P, _L, _I, _P, _P, _P]),
+    'lvae_iw_loss_fwd_f32': (C.c_int, [_P, _P, _F, _I, _I, _P, _P, _P, _P, _P]),
+    'lvae_iw_loss_bwd_f32': (C.c_int, [_P, _P, _F, _I, _I, _P, _P, _P]),
+    'lvae_iw_loss_fwd_anneal_f32': (C.c_int, [_P, _P, _P, _L, _I, _I, _P, _P, _P, _P, _P]),
+    'lvae_iw_loss_bwd_anneal_f32': (C.c_int, [_P, _P, _P, _L, _I, _I, _P, _P, _P]),
+    'lvae_repeat_samples_fwd_f32': (C.c_int, [_P, _L, _I, _P, _P]),
+    'lvae_repeat_samples_bwd_f32': (C.c_int, [_P, _L, _I, _P, _P]),
     'lvae_iw_online_f32': (C.c_int, [_P, _P, _I, _I, _I, _P, _P, _P]),
     'lvae_eval_online_f32': (C.c_int, [_P, _P, _P, _P, _P, _I, _I, _I, _P]),
     'lvae_eval_totals_f64': (C.c_int, [_P, _I, _I, _I, _P, _P]),

@@ -75,7 +75,8 @@ def save_checkpoint(path, model, optimizer=None, summary=None):
     """Weights (reference layout), global step, Adamax state and the position of the Philox noise stream, so that a resumed run continues
     the original one bit for bit. With a `summary` (summary.TrainSummary) also 'summary': the open log window's accumulator as a list of
     floats, so that the run resumed in the middle of a window prints the train line of the uninterrupted one. A scheduled lr is a function
-    of the Adamax step and of the schedule, stored as 'lr_schedule' (`lr_schedule_record`)."""
+    of the Adamax step and of the schedule, stored as 'lr_schedule' (`lr_schedule_record`). 'iw_train_samples' notes the K of the objective
+    the run trained on (model.iw_train_samples; 1 = the ELBO), by the same rule: load_checkpoint does not touch the resumed run's own."""
     ck = {'model': state_dict_reference_layout(model), 'global_step': int(model.global_step)}
     if optimizer is not None:
         ck['optimizer'] = optimizer_state_by_name(model, optimizer)
@@ -84,6 +85,7 @@ def save_checkpoint(path, model, optimizer=None, summary=None):
             ck['ema_decay'] = optimizer.ema_decay
         if lr_schedule_record(optimizer) is not None:
             ck['lr_schedule'] = lr_schedule_record(optimizer)
+    ck['iw_train_samples'] = int(getattr(model, 'iw_train_samples', 1))   # what the file's run trained on; a resumed run uses its own flag
     nz = noise_state(model)
     if nz is not None:
         ck['noise'] = nz

@@ -201,6 +201,14 @@ __device__ __forceinline__ float normal_kl(float qmu, float qlv, float pmu, floa
   return 0.5f * (vr + t * t - 1.f - logf(vr));
 }
 
+// KL warm-up: beta = linear_anneal(step[0], 0, 1, anneal_steps) read on the device (experiment_manager.py:340-342), evaluated in double and
+// rounded once, as the host computes it. The ELBO loss (misc.hip) and the importance-weighted loss (iw_loss.hip) read the same beta.
+__device__ __forceinline__ float anneal_beta(const int64_t* step, int64_t anneal_steps) {
+  if (anneal_steps <= 0) return 1.f;
+  const double r = fmin(fmax((double)step[0] / (double)anneal_steps, 0.0), 1.0);
+  return (float)(0.0 + (1.0 - 0.0) * r);
+}
+
 __device__ __forceinline__ float wave_sum(float v) {
 #pragma unroll
   for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);

@@ -198,13 +198,8 @@ __global__ __launch_bounds__(256) void elbo_loss_bwd_kernel(const float* g_loss,
   if (blockIdx.x == 0 && threadIdx.x == 0) d_kl_loss[0] = g * beta;
 }
 
-// The same loss with beta = linear_anneal(step[0], 0, 1, anneal_steps) read on the device (KL warm-up, experiment_manager.py:340-342), so
-// that a captured step replays with the beta of the step it runs. Evaluated in double and rounded once, as the host computes it.
-__device__ __forceinline__ float anneal_beta(const int64_t* step, int64_t anneal_steps) {
-  if (anneal_steps <= 0) return 1.f;
-  const double r = fmin(fmax((double)step[0] / (double)anneal_steps, 0.0), 1.0);
-  return (float)(0.0 + (1.0 - 0.0) * r);
-}
+// The same loss with beta = linear_anneal(step[0], 0, 1, anneal_steps) read on the device (anneal_beta, lvae_common.h), so that a captured
+// step replays with the beta of the step it runs.
 
 __global__ __launch_bounds__(256) void elbo_loss_fwd_anneal_kernel(const float* __restrict__ ll, const float* __restrict__ kl_sep,
                                                                     const float* kl_loss, const int64_t* step, int64_t anneal_steps,

@@ -39,11 +39,37 @@ def global_step_counter(model):
     return c
 
 
-def forward_pass(model, x, beta=1.0, compute_l2=True, beta_anneal=0):
+def check_iw_objective(model, iw_samples):
+    """The K-sample importance-weighted bound needs per-row log weights ll - kl_sep with kl_sep the Monte-Carlo log q - log p; ValueError for
+    a model whose configuration makes the bound meaningless."""
+    iw_samples = int(iw_samples)
+    if iw_samples < 1:
+        raise ValueError("iw_samples must be at least 1, got %d" % iw_samples)
+    if iw_samples > 1:
+        if float(model.free_bits) >= 1e-6:
+            raise ValueError("iw_samples=%d with free_bits=%g: the free-bits clamp has no importance-weighted form; train the bound with "
+                             "free_bits=0" % (iw_samples, model.free_bits))
+        if any(layer.analytical_kl for layer in model.top_down_layers):
+            raise ValueError("iw_samples=%d with analytical_kl=True: the importance weights need the Monte-Carlo log q - log p of the drawn "
+                             "sample, not the analytical KL" % iw_samples)
+    return iw_samples
+
+
+def forward_pass(model, x, beta=1.0, compute_l2=True, beta_anneal=0, iw_samples=1):
     """LVAEExperiment.forward_pass (experiment/experiment_manager.py:322-367) on the HIP engine. beta_anneal != 0: the KL warm-up,
-    beta = linear_anneal(global step, 0, 1, beta_anneal) read on the device from `global_step_counter(model)` (`beta` is ignored)."""
-    mo = model(x)
-    if beta_anneal:
+    beta = linear_anneal(global step, 0, 1, beta_anneal) read on the device from `global_step_counter(model)` (`beta` is ignored).
+    iw_samples = K > 1 (engine-only): the loss is the K-sample importance-weighted bound, -mean_b logmeanexp_k(ll - beta kl_sep), over K
+    samples per image that share one bottom-up pass (LadderVAE.forward(n_samples=K)); `elbo`, `recons`, `kl` are means over the K * B rows
+    and `out` also carries `iw` (the bound at beta = 1), `ess` (the effective sample size of the weights) and `iw_weights`."""
+    iw_samples = check_iw_objective(model, iw_samples)
+    mo = model(x, n_samples=iw_samples) if iw_samples > 1 else model(x)
+    iw = None
+    if iw_samples > 1 and beta_anneal:
+        elbo_sep, loss, elbo, recons, iw, ess, w = ops.IwLossAnnealFn.apply(mo['ll'], mo['kl_sep'], global_step_counter(model), int(beta_anneal),
+                                                                            iw_samples)
+    elif iw_samples > 1:
+        elbo_sep, loss, elbo, recons, iw, ess, w = ops.IwLossFn.apply(mo['ll'], mo['kl_sep'], float(beta), iw_samples)
+    elif beta_anneal:
         elbo_sep, loss, elbo, recons = ops.ElboLossAnnealFn.apply(mo['ll'], mo['kl_sep'], mo['kl_loss'], global_step_counter(model),
                                                                   int(beta_anneal))
     else:
@@ -51,6 +77,8 @@ def forward_pass(model, x, beta=1.0, compute_l2=True, beta_anneal=0):
     out = {'loss': loss, 'elbo': elbo, 'elbo_sep': elbo_sep, 'kl': mo['kl'], 'recons': recons,
            'out_mean': mo['out_mean'], 'out_mode': mo['out_mode'], 'out_sample': mo['out_sample'],
            'likelihood_params': mo['likelihood_params'], 'kl_avg_layerwise': mo['kl_avg_layerwise']}
+    if iw is not None:
+        out.update(iw=iw, ess=ess, iw_weights=w)
     if compute_l2:
         with torch.no_grad():
             out['l2'] = K.l2norm(model.arena.params).view(())
@@ -62,8 +90,9 @@ class TrainStep:
     the device at the feed's cursor (eager steps and the captured step alike: gather | forward, backward, exchange, Adamax | cursor advance)."""
 
     def __init__(self, model, optimizer, beta=1.0, use_graph=True, allreduce=None, eager_warmup=2, async_wgrad=False,
-                 wgrad_streams=1, wgrad_group_rows=16384, beta_anneal=0, feed=None, summary=None):
+                 wgrad_streams=1, wgrad_group_rows=16384, beta_anneal=0, feed=None, summary=None, iw_samples=1):
         self.model, self.opt, self.beta = model, optimizer, beta
+        self.iw_samples = check_iw_objective(model, iw_samples)   # K > 1: train on the K-sample importance-weighted bound
         self.feed = feed
         self.summary = summary                # None: the step issues not one launch more
         self._grad_norm = None
@@ -108,7 +137,7 @@ class TrainStep:
                 x = self.feed.gather(self.static_x)   # first launch of a fed step
             self.opt.zero_grad()
             K.prepared.prepare_all()  # one launch: transformed weights of every Winograd convolution seen so far
-            out = forward_pass(self.model, x, self.beta, beta_anneal=self.beta_anneal)
+            out = forward_pass(self.model, x, self.beta, beta_anneal=self.beta_anneal, iw_samples=self.iw_samples)
             if self.allreduce is not None:
                 self.allreduce.begin_step()
             ops.set_wgrad_stream(self.side)
@@ -142,7 +171,8 @@ class TrainStep:
                         pass
             ops.set_wgrad_grouping(None)
             ops.set_wgrad_stream(None)
-        return {k: out[k].detach() for k in ('loss', 'elbo', 'recons', 'kl', 'l2', 'kl_avg_layerwise')}
+        keys = ('loss', 'elbo', 'recons', 'kl', 'l2', 'kl_avg_layerwise') + (('iw', 'ess') if self.iw_samples > 1 else ())
+        return {k: out[k].detach() for k in keys}
 
     def _fold(self, out):
         """The step's metrics and the norm of the gradient Adamax is about to apply (summed over ranks by now, scaled like Adamax scales it)

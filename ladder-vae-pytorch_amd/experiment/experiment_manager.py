@@ -112,6 +112,10 @@ def build_parser():
     p.add_argument('--lr-decay-steps', type=int, default=0, dest='lr_decay_steps', metavar='T')
     p.add_argument('--lr-min', type=float, default=0.0, dest='lr_min')
     p.add_argument('--lr-gamma', type=float, default=0.1, dest='lr_gamma')
+    p.add_argument('--iw-train-samples', type=int, default=1, dest='iw_train_samples', metavar='K',
+                   help='train on the K-sample importance-weighted bound instead of the ELBO: K samples per image share one bottom-up pass '
+                        '(--batch-size stays images per step); the train line adds the bound and the effective sample size of the weights. '
+                        'Not with --freebits or --analytical-kl. 1: the ELBO')
     p.add_argument('--latent-kl-threshold', type=float, default=0.01, dest='latent_kl_threshold', metavar='T')
     p.add_argument('--latent-var-threshold', type=float, default=0.01, dest='latent_var_threshold', metavar='T')
     return p
@@ -151,6 +155,14 @@ class LVAEExperiment:
             raise SystemExit("--lr-schedule %s needs --lr-decay-steps > 0" % args.lr_schedule)
         if getattr(args, 'lr_min', 0.0) > args.lr:
             raise SystemExit("--lr-min %g exceeds --lr %g" % (args.lr_min, args.lr))
+        iw = getattr(args, 'iw_train_samples', 1)
+        if iw < 1:
+            raise SystemExit("--iw-train-samples must be at least 1, got %d" % iw)
+        if iw > 1 and args.free_bits > 0:
+            raise SystemExit("--iw-train-samples %d cannot be combined with --freebits %g: the free-bits clamp has no importance-weighted form" % (iw, args.free_bits))
+        if iw > 1 and args.analytical_kl:
+            raise SystemExit("--iw-train-samples %d cannot be combined with --analytical-kl: the importance weights need the Monte-Carlo "
+                             "log q - log p of the drawn sample" % iw)
         assert args.weight_decay >= 0.0
         assert 0.0 <= args.dropout <= 1.0
         if args.dropout < 1e-5:
@@ -174,6 +186,8 @@ class LVAEExperiment:
         s += ',block=' + args.residual_type
         if args.beta_anneal != 0:
             s += ',b{}'.format(args.beta_anneal)
+        if getattr(args, 'iw_train_samples', 1) > 1:
+            s += ',iw{}'.format(args.iw_train_samples)
         s += ',{}'.format(args.nonlin)
         if args.free_bits > 0:
             s += ',freeb={}'.format(args.free_bits)
@@ -199,6 +213,7 @@ class LVAEExperiment:
                           no_initial_downscaling=a.no_initial_downscaling, analytical_kl=a.analytical_kl).to(self.device)
         model.noise = PhiloxNoise(seed=a.seed)
         model.compute_dtype = a.compute_dtype
+        model.iw_train_samples = getattr(a, 'iw_train_samples', 1)   # (noted in checkpoints: checkpoint.save_checkpoint)
         return model
 
     @staticmethod
@@ -222,7 +237,7 @@ class LVAEExperiment:
 
     def forward_pass(self, x, y=None):
         x = x.to(self.device, non_blocking=True)
-        return engine.forward_pass(self.model, x, self.beta())
+        return engine.forward_pass(self.model, x, self.beta(), iw_samples=getattr(self.args, 'iw_train_samples', 1))
 
     @classmethod
     def train_log_str(cls, summaries, step, epoch=None):
@@ -248,6 +263,8 @@ class LVAEExperiment:
     def get_metrics_dict(cls, results):
         d = {'loss/loss': results['loss'].item(), 'elbo/elbo': results['elbo'].item(),
              'elbo/recons': results['recons'].item(), 'elbo/kl': results['kl'].item(), 'l2/l2': results['l2'].item()}
+        if 'iw' in results:   # a step trained on the K-sample bound (--iw-train-samples): the bound at beta = 1, the weights' effective sample size
+            d['elbo/iw_train'], d['iw/ess'] = results['iw'].item(), results['ess'].item()
         if 'kl_avg_layerwise' in results:
             for i in range(len(results['kl_avg_layerwise'])):
                 d['kl_layers/kl_layer_{}'.format(i)] = results['kl_avg_layerwise'][i].item()

@@ -1105,6 +1105,56 @@ def elbo_loss_bwd_anneal(g_loss, step, anneal_steps, N):
     return d_ll, d_kl
 
 
+def _iw_out(ll, K_):
+    N = ll.numel()
+    if K_ < 1 or N % K_:
+        raise _C.LvaeHipError("importance-weighted loss: %d rows are not %d samples of a whole number of images" % (N, K_))
+    new = lambda n: torch.empty((n,), dtype=torch.float32, device=ll.device)
+    return N // K_, new(N), new(N), new(N // K_), new(5)
+
+
+def iw_loss_fwd(ll, kl_sep, beta, K_):
+    """ll, kl_sep (K*B,) sample-major. Returns elbo_sep (K*B,), w (K*B,), bound (B,), scalars [loss, elbo, recons, iw, ess]."""
+    B, elbo_sep, w, bound, scal = _iw_out(ll, K_)
+    call('lvae_iw_loss_fwd_f32', ptr(ll), ptr(kl_sep), float(beta), K_, B, ptr(elbo_sep), ptr(w), ptr(bound), ptr(scal), stream_ptr())
+    return elbo_sep, w, bound, scal
+
+
+def iw_loss_bwd(g_loss, w, beta, K_):
+    d_ll, d_kl = torch.empty_like(w), torch.empty_like(w)
+    call('lvae_iw_loss_bwd_f32', ptr(g_loss), ptr(w), float(beta), K_, w.numel() // K_, ptr(d_ll), ptr(d_kl), stream_ptr())
+    return d_ll, d_kl
+
+
+def iw_loss_fwd_anneal(ll, kl_sep, step, anneal_steps, K_):
+    """iw_loss_fwd with beta = linear_anneal(step[0], 0, 1, anneal_steps) read on the device (step: device int64[1])."""
+    B, elbo_sep, w, bound, scal = _iw_out(ll, K_)
+    call('lvae_iw_loss_fwd_anneal_f32', ptr(ll), ptr(kl_sep), ptr(step, (torch.int64,)), int(anneal_steps), K_, B, ptr(elbo_sep), ptr(w),
+         ptr(bound), ptr(scal), stream_ptr())
+    return elbo_sep, w, bound, scal
+
+
+def iw_loss_bwd_anneal(g_loss, w, step, anneal_steps, K_):
+    d_ll, d_kl = torch.empty_like(w), torch.empty_like(w)
+    call('lvae_iw_loss_bwd_anneal_f32', ptr(g_loss), ptr(w), ptr(step, (torch.int64,)), int(anneal_steps), K_, w.numel() // K_, ptr(d_ll),
+         ptr(d_kl), stream_ptr())
+    return d_ll, d_kl
+
+
+def repeat_samples(x, K_):
+    """(B, ...) contiguous -> (K*B, ...): K copies of x, sample-major."""
+    out = torch.empty((K_ * x.shape[0],) + tuple(x.shape[1:]), dtype=torch.float32, device=x.device)
+    call('lvae_repeat_samples_fwd_f32', ptr(x, (torch.float32,)), x.numel(), K_, ptr(out), stream_ptr())
+    return out
+
+
+def repeat_samples_bwd(dout, K_):
+    """(K*B, ...) contiguous -> (B, ...): the float32 sum over the K samples in ascending k."""
+    din = torch.empty((dout.shape[0] // K_,) + tuple(dout.shape[1:]), dtype=torch.float32, device=dout.device)
+    call('lvae_repeat_samples_bwd_f32', ptr(dout, (torch.float32,)), din.numel(), K_, ptr(din), stream_ptr())
+    return din
+
+
 # ----------------------------------------------------------------------------------------------------------------
 def iw_logmeanexp(elbo_sn):
     S, N = elbo_sn.shape

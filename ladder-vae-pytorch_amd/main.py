@@ -72,6 +72,12 @@ def lr_suffix(m):
     return '   lr: {:.3g}'.format(m['lr/lr']) if 'lr/lr' in m else ''
 
 
+def iw_suffix(m, k):
+    """What --iw-train-samples K > 1 appends to a train line: the K-sample bound (at beta = 1) and the effective sample size of the weights,
+    of the step the line falls due at."""
+    return '   IW({}): {:.5g}   ESS: {:.3g}'.format(k, m['elbo/iw_train'], m['iw/ess']) if 'elbo/iw_train' in m else ''
+
+
 IMG_NROWS = 8   # pictures of --ts-img-every: 8 x 8 samples, 32 input / reconstruction pairs
 
 
@@ -98,6 +104,9 @@ def main(argv=None):
         was = ck.get('lr_schedule') if isinstance(ck, dict) and 'model' in ck else None
         if rank == 0 and was != lr_schedule_record(opt):
             print('warning: %s was written with the lr schedule %s; continuing with %s' % (args.resume, was, lr_schedule_record(opt)))
+        was_iw = ck.get('iw_train_samples', 1) if isinstance(ck, dict) and 'model' in ck else 1
+        if rank == 0 and was_iw != args.iw_train_samples:
+            print('warning: %s was written with --iw-train-samples %d; continuing with %d' % (args.resume, was_iw, args.iw_train_samples))
         del ck
     model.noise.seed ^= rank * 0x9E3779B9
     model.train()
@@ -127,7 +136,7 @@ def main(argv=None):
     allreduce = ldist.GradAllReduce(arena.grads, segments=arena.segments) if world > 1 else None
     # --beta-anneal: beta is read on the device from a step counter the step advances itself, so the captured graph replays with it
     step_fn = TrainStep(model, opt, beta=1.0, use_graph=not args.no_graph, allreduce=allreduce, beta_anneal=args.beta_anneal,
-                        feed=feed, summary=summary)
+                        feed=feed, summary=summary, iw_samples=args.iw_train_samples)
     history = History(args.history) if args.history and rank == 0 else None
     # --latent-stats: the first sample of every test batch also folds each layer's posterior into a device accumulator
     latent = LatentStats(model, exp.device, args.latent_kl_threshold, args.latent_var_threshold) if args.latent_stats and tests is not None else None
@@ -182,7 +191,10 @@ def main(argv=None):
                 dt = time.time() - t0
                 if opt.schedule is not None:
                     m['lr/lr'] = opt.current_lr()      # of this step, not a window mean: the accumulator's layout stays as it is
-                print(exp.train_log_str(m, step) + train_line_suffix(m, summary.ranks) + lr_suffix(m) + '   [{:.0f} img/s]'.format(seen / dt))
+                if 'iw' in out:                        # likewise of this step (and of rank 0)
+                    m['elbo/iw_train'], m['iw/ess'] = out['iw'].item(), out['ess'].item()
+                print(exp.train_log_str(m, step) + train_line_suffix(m, summary.ranks) + lr_suffix(m) + '   [{:.0f} img/s]'.format(seen / dt)
+                      + iw_suffix(m, args.iw_train_samples))
                 if history is not None:
                     history.write(step, 'train', m, steps=m['steps'], nonfinite_steps=m['nonfinite_steps'])
             t0, seen = time.time(), 0
@@ -191,7 +203,7 @@ def main(argv=None):
             dt = time.time() - t0
             if opt.schedule is not None:
                 m['lr/lr'] = opt.current_lr()
-            print(exp.train_log_str(m, step) + lr_suffix(m) + '   [{:.0f} img/s]'.format(seen / dt))
+            print(exp.train_log_str(m, step) + lr_suffix(m) + '   [{:.0f} img/s]'.format(seen / dt) + iw_suffix(m, args.iw_train_samples))
             if history is not None:
                 history.write(step, 'train', m)
             t0, seen = time.time(), 0

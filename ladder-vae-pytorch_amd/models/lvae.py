@@ -172,27 +172,44 @@ class LadderVAE(nn.Module):
     def bn_modules(self):
         return [m for m in self.modules() if isinstance(m, BatchNorm2dParams)]
 
-    def _mask_plan(self, N):
-        """(number of Dropout2d draws of one training forward, N, C, p) when they all share one shape, else None."""
+    def _mask_plan(self, N, n_samples=1):
+        """(number of Dropout2d draws of one training forward, N, C, p) when they all share one shape, else None. With n_samples = K > 1 the
+        draws have two shapes and the plan is a list of two such groups in draw order: the bottom-up masks at N images, then the top-down
+        ones at K * N rows."""
         if not self.training or not self.dropout:
             return None
         if getattr(self, '_n_drop', None) is None:
             from ..lib.nn import ResidualBlock
-            self._n_drop = sum(sum(m._drops) for m in self.modules() if isinstance(m, ResidualBlock))
-        return (self._n_drop, N, self.n_filters, float(self.dropout))
+            drops = lambda root: sum(sum(m._drops) for m in root.modules() if isinstance(m, ResidualBlock))
+            self._n_drop = drops(self)
+            self._n_drop_bu = drops(self.first_bottom_up) + drops(self.bottom_up_layers)
+        if n_samples == 1:
+            return (self._n_drop, N, self.n_filters, float(self.dropout))
+        return [(self._n_drop_bu, N, self.n_filters, float(self.dropout)),
+                (self._n_drop - self._n_drop_bu, n_samples * N, self.n_filters, float(self.dropout))]
 
-    def _begin(self, ref_tensor, batch=None):
+    def _begin(self, ref_tensor, batch=None, n_samples=1):
         self.pack(ref_tensor.device if ref_tensor is not None else None)
         K.set_precision(self.compute_dtype)
-        self.noise.begin(next(self.parameters()).device, self._mask_plan(batch) if batch else None)
+        self.noise.begin(next(self.parameters()).device, self._mask_plan(batch, n_samples) if batch else None)
 
     # ------------------------------------------------------------------------------------------------------------
     # reference API
     # ------------------------------------------------------------------------------------------------------------
-    def forward(self, x):
+    def forward(self, x, n_samples=1):
+        """n_samples: engine-only keyword — K > 1 draws K importance samples per image (engine.forward_pass(iw_samples=K) trains on their
+        bound). The bottom-up pass is a deterministic function of the image and runs ONCE, on the B images; each level's output is repeated
+        for the K samples (ops.RepeatSamplesFn, whose backward sums their gradients) and the top-down pass, final_top_down, the crop and the
+        likelihood run on K * B rows, sample-major (row k * B + b). The dict keeps its 12 keys: `ll`, `kl_sep`, `z`, `kl_spatial` and `out_*`
+        have K * B rows; `kl`, `kl_avg_layerwise` and `logp` are means over all rows. Two consequences: BatchNorm normalises over the B images
+        going bottom-up and over the K * B rows going top-down, and the bottom-up Dropout2d masks are shared by the K samples of an image
+        (the top-down ones are drawn per row). n_samples = 1 draws, launches and returns exactly what a call without the keyword does."""
         if not x.is_cuda:
             raise K._C.LvaeHipError("LadderVAE (HIP engine) needs a GPU tensor; got %s" % x.device)
-        self._begin(x, batch=x.shape[0])
+        n_samples = int(n_samples)
+        if n_samples < 1:
+            raise ValueError("n_samples must be at least 1, got %d" % n_samples)
+        self._begin(x, batch=x.shape[0], n_samples=n_samples)
         img_size = x.size()[2:]
         x = x.contiguous().float()
         # NCHW image -> centred zero pad -> NHWC, one kernel (models/lvae.py:176, 317-325)
@@ -200,6 +217,10 @@ class LadderVAE(nn.Module):
         x_nhwc = x_pad if tuple(img_size) == tuple(x_pad.shape[1:3]) else K.pad_crop(x, True, img_size, False)
 
         bu_values = self._bottomup(x_pad)
+        if n_samples > 1:
+            # behind the fan-out of _bottomup, in front of the segment marks of _topdown: the gradient fan-in stays as it is
+            bu_values = [ops.RepeatSamplesFn.apply(b, n_samples) for b in bu_values]
+            x_nhwc = K.repeat_samples(x_nhwc, n_samples)
         out, td_data = self._topdown(bu_values)
         out = ops.CropFn.apply(out, tuple(int(s) for s in img_size)) if tuple(out.shape[1:3]) != tuple(img_size) else out
         out = self._mark(out, 'likelihood.')

@@ -16,22 +16,23 @@ class PhiloxNoise:
         self.seed = (int(seed) * 0x9E3779B97F4A7C15 + int(rank) * 0xD1B54A32D192ED03) & (2 ** 63 - 1)
         self.step = None
         self.site = 0
-        self._masks = None
+        self._groups = []     # [masks (count, N, C), (N, C, p)] per group of the mask plan, in draw order
+        self._group = 0
         self._mask_next = 0
-        self._mask_shape = None
 
     def begin(self, device, mask_plan=None):
         """mask_plan = (count, N, C, p): all Dropout2d keep-masks of this forward are drawn by ONE launch into a
-        (count, N, C) buffer and handed out in call order (306 tiny launches per CIFAR-15 step otherwise)."""
+        (count, N, C) buffer and handed out in call order (306 tiny launches per CIFAR-15 step otherwise). A list of such groups (a forward
+        whose masks have two shapes: LadderVAE.forward(n_samples=K)) is drawn with one launch per group and handed out group after group."""
         if self.step is None or self.step.device != device:
             self.step = torch.zeros(1, dtype=torch.int64, device=device)
         self.site = 0
-        self._masks = None
+        self._groups = []
+        self._group = 0
         self._mask_next = 0
-        if mask_plan is not None and mask_plan[0] > 0:
-            count, N, C, p = mask_plan
-            self._mask_shape = (N, C, p)
-            self._masks = self._fill((count, N, C), 'bernoulli', 1.0 - p, 1.0 / (1.0 - p), device)
+        for count, N, C, p in ([mask_plan] if isinstance(mask_plan, tuple) else (mask_plan or [])):
+            if count > 0:
+                self._groups.append((self._fill((count, N, C), 'bernoulli', 1.0 - p, 1.0 / (1.0 - p), device), (N, C, p)))
 
     def end(self):
         K.counter_advance(self.step, 1)
@@ -42,8 +43,10 @@ class PhiloxNoise:
                           self.site)
 
     def dropout_mask(self, N, C, p, device):
-        if self._masks is not None and self._mask_next < self._masks.shape[0] and self._mask_shape == (N, C, p):
-            m = self._masks[self._mask_next]
+        if self._group < len(self._groups) and self._mask_next >= self._groups[self._group][0].shape[0]:
+            self._group, self._mask_next = self._group + 1, 0   # this group is handed out: the next one's masks follow
+        if self._group < len(self._groups) and self._groups[self._group][1] == (N, C, p):
+            m = self._groups[self._group][0][self._mask_next]
             self._mask_next += 1
             return m
         return self._fill((N, C), 'bernoulli', 1.0 - p, 1.0 / (1.0 - p), device)

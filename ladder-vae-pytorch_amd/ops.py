@@ -676,3 +676,58 @@ class ElboLossAnnealFn(Function):
     def backward(ctx, g_sep, g_loss, g_elbo, g_recons):
         d_ll, d_kl = K.elbo_loss_bwd_anneal(_c(g_loss).view(1), ctx.step, ctx.anneal_steps, ctx.N)
         return d_ll, None, d_kl.view(()) if ctx.kl_dim0 else d_kl, None, None
+
+
+# ----------------------------------------------------------------------------------------------------------------
+# Training on the K-sample importance-weighted bound: rows are sample-major, row k*B + b is sample k of image b
+class IwLossFn(Function):
+    """ll, kl_sep (K*B,) -> elbo_sep (K*B,), scalars loss = -mean_b logmeanexp_k(ll - beta kl_sep), elbo, recons, iw (the bound at beta = 1),
+    ess, and the self-normalised weights w (K*B,) the backward scales the rows' gradients with."""
+
+    @staticmethod
+    def forward(ctx, ll, kl_sep, beta, n_samples):
+        ctx.beta, ctx.K = beta, n_samples
+        elbo_sep, w, bound, scal = K.iw_loss_fwd(ll, kl_sep, beta, n_samples)
+        ctx.save_for_backward(w)
+        loss, elbo, recons, iw, ess = scal[0], scal[1], scal[2], scal[3], scal[4]
+        ctx.mark_non_differentiable(elbo_sep, elbo, recons, iw, ess, w)   # only d(loss) is propagated
+        return elbo_sep, loss, elbo, recons, iw, ess, w
+
+    @staticmethod
+    def backward(ctx, g_sep, g_loss, g_elbo, g_recons, g_iw, g_ess, g_w):
+        (w,) = ctx.saved_tensors
+        d_ll, d_kl = K.iw_loss_bwd(_c(g_loss).view(1), w, ctx.beta, ctx.K)
+        return d_ll, d_kl, None, None
+
+
+class IwLossAnnealFn(Function):
+    """IwLossFn with beta = linear_anneal(step[0], 0, 1, anneal_steps) read on the device, as ElboLossAnnealFn reads it."""
+
+    @staticmethod
+    def forward(ctx, ll, kl_sep, step, anneal_steps, n_samples):
+        ctx.step, ctx.anneal_steps, ctx.K = step, int(anneal_steps), n_samples
+        elbo_sep, w, bound, scal = K.iw_loss_fwd_anneal(ll, kl_sep, step, anneal_steps, n_samples)
+        ctx.save_for_backward(w)
+        loss, elbo, recons, iw, ess = scal[0], scal[1], scal[2], scal[3], scal[4]
+        ctx.mark_non_differentiable(elbo_sep, elbo, recons, iw, ess, w)
+        return elbo_sep, loss, elbo, recons, iw, ess, w
+
+    @staticmethod
+    def backward(ctx, g_sep, g_loss, g_elbo, g_recons, g_iw, g_ess, g_w):
+        (w,) = ctx.saved_tensors
+        d_ll, d_kl = K.iw_loss_bwd_anneal(_c(g_loss).view(1), w, ctx.step, ctx.anneal_steps, ctx.K)
+        return d_ll, d_kl, None, None, None
+
+
+class RepeatSamplesFn(Function):
+    """(B, ...) -> (K*B, ...): a bottom-up level's output handed to the K samples of the top-down pass; backward sums the K gradients of
+    an image in ascending k with one launch. The output is a new tensor: a block's Handover does not travel with it."""
+
+    @staticmethod
+    def forward(ctx, x, n_samples):
+        ctx.K = n_samples
+        return K.repeat_samples(_c(x), n_samples)
+
+    @staticmethod
+    def backward(ctx, dout):
+        return K.repeat_samples_bwd(_c(dout), ctx.K), None
