@@ -727,7 +727,9 @@ extern "C" int lvae_affine_act_bwd_parts_f32(const float* parts, int32_t rows, c
   static const int parts_max_rows = (int)tune("LVAE_APPLY_PARTS_MAX_ROWS", 128);
   // ... except where few workgroups do the summing: the 8x8 level under LVAE_PREC_BF16 has 256 partial rows (64-pixel tiles) and 256 apply workgroups
   const bool few_wgs = rows <= 2 * parts_max_rows && M <= 16384;
-  if ((rows <= parts_max_rows || few_wgs) && vec_ok(C, x, dh, dx, add) && vec_ok(C, parts, drop) && 256 % (C / 4) == 0) {
+  // the parts kernel keeps its coefficients in cf[2][256] and fills them with one thread per channel: C <= 256 (256 % 128 == 256 % 256 == 0
+  // would let C = 512 and 1024 in)
+  if ((rows <= parts_max_rows || few_wgs) && C <= 256 && vec_ok(C, x, dh, dx, add) && vec_ok(C, parts, drop) && 256 % (C / 4) == 0) {
     const RowMap rm = row_map(C, 4);
     int grid = grid_for(M, rm.rpp * 4);
     // round 4: 256 partial rows summed by a CAPPED grid (the redundant sums shrink with the grid) — 33.51 ms base, 33.84 uncapped (1024
