@@ -511,6 +511,17 @@ int lvae_normal_stochastic_bwd_f32(const float* p, int32_t p_bcast, const float*
                                    const float* g_ks, int32_t N, int32_t HW, int32_t Z, int32_t mode,
                                    int32_t analytical_kl, float* dp, float* dq, void* stream);
 
+/* Tempered draw from the prior (sampling only; no backward): for row n, t_n = row_temperature ? row_temperature[n] : temperature,
+ * z = mu + (t_n * exp(lv/2)) * eps, and z = mu exactly where t_n == 0 (a branch: eps is not read, an infinite sigma gives no NaN).
+ * logprob_p[n] = sum over the row of log N(z; mu, exp(lv)) under the UNTEMPERED prior, in a fixed order (deterministic).
+ * p [N|1,HW,2Z] and p_bcast as above; eps, z [N,HW,Z]; row_temperature [N] on the device or NULL. eps may be NULL only when
+ * row_temperature is NULL and temperature == 0. LVAE_EINVAL: a missing pointer, N, HW or Z <= 0 (or a row past 32-bit indexing), a
+ * negative or non-finite `temperature`; per-row values are the caller's responsibility. 16-byte loads and stores when Z % 4 == 0 and
+ * p, eps, z are 16-byte aligned, else a scalar map. */
+int lvae_normal_prior_sample_f32(const float* p, int32_t p_bcast, const float* eps, float temperature,
+                                 const float* row_temperature, int32_t N, int32_t HW, int32_t Z, float* z, float* logprob_p,
+                                 void* stream);
+
 /* `kl_elementwise` of NormalStochasticBlock2d.forward (lib/stochastic.py:88-91,108) and kl_normal_mc (lib/stochastic.py:209-226):
  * out[n,pix,c] = log q(z) - log p(z)  (analytical_kl = 0)  or  KL(q || p)  (analytical_kl = 1).  p, q [N|1,HW,2Z] (mu | logvar on
  * the channel axis; *_bcast = 1: one row set shared by the batch), z, out [N,HW,Z]. The backward writes dp, dq [N,HW,2Z] (the

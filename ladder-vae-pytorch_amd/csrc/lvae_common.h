@@ -201,6 +201,15 @@ __device__ __forceinline__ float normal_kl(float qmu, float qlv, float pmu, floa
   return 0.5f * (vr + t * t - 1.f - logf(vr));
 }
 
+// log N(z; mu, exp(lv)) of one element, as torch.distributions.Normal(mu, exp(lv/2)).log_prob(z) forms it (var = std^2, log std = log(std)):
+// what the stochastic block (stochastic.hip) and the tempered prior draw (prior_sample.hip) sum into logprob_p / logprob_q
+constexpr float kLogSqrt2Pi = 0.91893853320467274178f;
+__device__ __forceinline__ float normal_logprob(float z, float mu, float lv) {
+  const float sd = expf(0.5f * lv);
+  const float d = z - mu;
+  return -(d * d) / (2.f * sd * sd) - logf(sd) - kLogSqrt2Pi;
+}
+
 // KL warm-up: beta = linear_anneal(step[0], 0, 1, anneal_steps) read on the device (experiment_manager.py:340-342), evaluated in double and
 // rounded once, as the host computes it. The ELBO loss (misc.hip) and the importance-weighted loss (iw_loss.hip) read the same beta.
 __device__ __forceinline__ float anneal_beta(const int64_t* step, int64_t anneal_steps) {

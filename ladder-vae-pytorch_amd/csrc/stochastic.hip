@@ -6,21 +6,12 @@
 
 namespace lvae {
 
-constexpr float kLogSqrt2Pi = 0.91893853320467274178f;
-
 struct StochArgs {
   const float* p;
   const float* q;
   const float* eps;
   int p_bcast, N, HW, Z, mode, analytical;
 };
-
-__device__ __forceinline__ float normal_logprob(float z, float mu, float lv) {
-  // torch.distributions.Normal(mu, exp(lv/2)).log_prob(z): var = std^2, log std = log(std)
-  const float sd = expf(0.5f * lv);
-  const float d = z - mu;
-  return -(d * d) / (2.f * sd * sd) - logf(sd) - kLogSqrt2Pi;
-}
 
 __global__ __launch_bounds__(256) void stoch_fwd_kernel(StochArgs a, float* __restrict__ z_out, float* logprob_p,
                                                          float* logprob_q, float* kl_samplewise, float* kl_spatial) {

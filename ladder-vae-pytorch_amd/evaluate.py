@@ -10,12 +10,16 @@ the absent boilr.eval.BaseOfflineEvaluator / VAEExperimentManager.test_procedure
     (with `optimizer=` an averaging Adamax: computed from the averaged weights);
   * `prior_samples(model, n)` and `inspect_layer_repr(model, n)` — evaluate.py:34-45, 95-114, as arrays;
   * `reconstructions(model, x)` — inputs beside what the model makes of them (boilr's generate_and_save_reconstructions, restated);
+  * `conditional_samples(model, x, k, K)` — K variations per image that keep its top k latents (LadderVAE.sample_conditional);
   * `image_pass(model, nrows, x, step)` — the trainer's pictures (--ts-img-every): a grid of prior samples and a grid of input /
     reconstruction pairs, formed on the device (images.py), on a noise stream of their own, leaving training untouched.
 
 CLI: python -m lvae_amd.evaluate --synthetic --ll --ll-samples 100 --ps --layer-repr --recons --img-dir DIR  <model flags of main.py>
      --ps and --layer-repr write prior_samples.npy and layer_repr_<i>.npy; with --img-dir DIR they also write the reference's pictures
      DIR/samples_0.png and DIR/sample_mode_layer<i>.png (grids of 12 x 12), and --recons writes DIR/reconstructions.png (72 pairs).
+     --cond-samples [--cond-layers k ...] [--cond-variations K] writes cond_samples_top<k>.npy (n, 1 + K, C, H, W) for the first 12
+     evaluation images, column 0 the input, and with --img-dir DIR/cond_samples_top<k>.png (one row per image).
+     --temperature T [T ...] (one value, or one per layer, bottom first) tempers the prior draws of --ps and --cond-samples.
 """
 import os
 
@@ -305,12 +309,27 @@ def test_pass(model, batches, n_samples, noise=None, process_group=None, use_gra
 
 
 @torch.no_grad()
-def prior_samples(model, n_imgs):
-    """evaluate.py:34-36: unconditional samples, (n, C, H, W) in [0, 1]."""
+def prior_samples(model, n_imgs, temperature=None):
+    """evaluate.py:34-36: unconditional samples, (n, C, H, W) in [0, 1]. temperature: as in LadderVAE.sample_prior (None: the plain call)."""
     was_training = model.training
     model.eval()
     try:
-        return model.sample_prior(n_imgs)
+        return model.sample_prior(n_imgs, temperature=temperature)
+    finally:
+        model.train(was_training)
+
+
+@torch.no_grad()
+def conditional_samples(model, x, n_top_layers, n_samples, temperature=None, use_mode=False):
+    """K = n_samples variations of every image of the NCHW batch x that keep its top n_top_layers latents (LadderVAE.sample_conditional,
+    eval mode) -> (x, pictures), both on the device: pictures (K * B, C, H, W), sample-major, the likelihood's mean where it has one and
+    its sample otherwise (the rule of `reconstructions`). Noise comes from `model.noise`."""
+    was_training = model.training
+    model.eval()
+    try:
+        x = x.to(next(model.parameters()).device).contiguous().float()
+        out = model.sample_conditional(x, n_top_layers, n_samples, temperature=temperature, use_mode=use_mode)
+        return x, (out['mean'] if out['mean'] is not None else out['sample'])
     finally:
         model.train(was_training)
 
@@ -403,6 +422,13 @@ def build_eval_parser():
     # (--img-dir DIR is a flag of build_parser: here samples_0.png with --ps, sample_mode_layer<i>.png with --layer-repr)
     p.add_argument('--recons', action='store_true', help='inputs beside their reconstructions -> DIR/reconstructions.png (needs --img-dir)')
     # (--latent-stats and its two thresholds are flags of build_parser: here with --ll, and the arrays go to latent_stats.npz)
+    p.add_argument('--temperature', type=float, nargs='+', default=None, metavar='T',
+                   help='temperature of the prior draws of --ps and --cond-samples: one value, or one per layer (bottom layer first)')
+    p.add_argument('--cond-samples', action='store_true', dest='cond_samples',
+                   help='variations of the evaluation images that keep their top k latents -> cond_samples_top<k>.npy')
+    p.add_argument('--cond-layers', type=int, nargs='+', default=None, dest='cond_layers', metavar='k',
+                   help='the k of --cond-samples (default: every k from 0 to the number of layers)')
+    p.add_argument('--cond-variations', type=int, default=7, dest='cond_variations', metavar='K', help='variations per image and k')
     return p
 
 
@@ -413,6 +439,18 @@ def parse_eval_args(argv=None):
         p.error('--recons needs --img-dir DIR: the picture is written there')
     if args.latent_stats and not args.ll:
         p.error('--latent-stats needs --ll: the statistics are folded during the log-likelihood pass')
+    L = len(args.z_dims)
+    if args.cond_layers is None:
+        args.cond_layers = list(range(L + 1))
+    elif any(k < 0 or k > L for k in args.cond_layers):
+        p.error('--cond-layers takes values from 0 to %d (the number of layers), got %s' % (L, args.cond_layers))
+    if args.cond_variations < 1:
+        p.error('--cond-variations must be at least 1, got %d' % args.cond_variations)
+    if args.temperature is not None:
+        if len(args.temperature) not in (1, L):
+            p.error('--temperature takes one value or one per layer (%d), got %d' % (L, len(args.temperature)))
+        if any(not 0.0 <= t < float('inf') for t in args.temperature):
+            p.error('--temperature takes finite values >= 0, got %s' % args.temperature)
     return args
 
 
@@ -439,7 +477,8 @@ def main(argv=None):
             load_checkpoint(args.checkpoint, model)
     if args.img_dir:
         os.makedirs(args.img_dir, exist_ok=True)
-    if args.ll or args.recons:
+    temperature = None if args.temperature is None else (args.temperature[0] if len(args.temperature) == 1 else args.temperature)
+    if args.ll or args.recons or args.cond_samples:
         gen = torch.Generator().manual_seed(args.seed)
         if args.data_npz:
             data = torch.from_numpy(np.load(args.data_npz)['data']).float()
@@ -460,15 +499,23 @@ def main(argv=None):
             save_npz('latent_stats.npz', res['latent_arrays'], lat.kl_threshold, lat.var_threshold, res['n_images'])
         print(line)
     if args.ps:
-        np.save('prior_samples.npy', prior_samples(model, 64).cpu().numpy())
+        np.save('prior_samples.npy', prior_samples(model, 64, temperature).cpu().numpy())
     if args.layer_repr:
         for i, s in enumerate(inspect_layer_repr(model, 8)):
             np.save('layer_repr_%d.npy' % i, s.cpu().numpy())
+    if args.cond_samples:  # one row per image: the input, then its K variations
+        n, nv = min(IMG_GRID_N, int(data.shape[0])), args.cond_variations
+        for k in args.cond_layers:
+            xin, pics = conditional_samples(model, data[:n], k, nv, temperature)
+            rows = torch.cat((xin.unsqueeze(1), pics.view(nv, n, *pics.shape[1:]).transpose(0, 1)), 1).contiguous()
+            np.save('cond_samples_top%d.npy' % k, rows.cpu().numpy())
+            if args.img_dir:
+                write_png(os.path.join(args.img_dir, 'cond_samples_top%d.png' % k), image_grid(rows.view(-1, *rows.shape[2:]), 1 + nv))
     if not args.img_dir:
         return
     # the reference's pictures, after everything above so that the arrays do not depend on --img-dir
     if args.ps:            # evaluate.py:34-36
-        write_png(os.path.join(args.img_dir, 'samples_0.png'), image_grid(prior_samples(model, IMG_GRID_N ** 2), IMG_GRID_N))
+        write_png(os.path.join(args.img_dir, 'samples_0.png'), image_grid(prior_samples(model, IMG_GRID_N ** 2, temperature), IMG_GRID_N))
     if args.recons:        # evaluate.py:39-41, from the first images of the evaluation data
         xin, rec = reconstructions(model, data[:IMG_GRID_N ** 2 // 2])
         write_png(os.path.join(args.img_dir, 'reconstructions.png'), image_grid(xin, IMG_GRID_N, second=rec))

@@ -934,6 +934,22 @@ def normal_stochastic_fwd(p, q, eps_or_z, mode, analytical_kl, Z, N, rows=None):
     return z, small[0], small[1], small[2], ks
 
 
+def normal_prior_sample(p, eps, Z, N, temperature, row_temperature=None, rows=None):
+    """Tempered draw from the prior p (N|1,H,W,2Z): z = mu + (t * sigma) * eps, z = mu exactly where t == 0; log p(z) under the untempered
+    prior. temperature: the scalar t; row_temperature: a device float tensor (N,) that replaces it row by row. eps (N,H,W,Z) may be None
+    only with a scalar temperature of 0. rows: as in normal_stochastic_fwd (only the logprob_p row is written). Returns (z, logprob_p)."""
+    p_bcast = int(p.shape[0] == 1 and N > 1)
+    _, H, W, _ = p.shape
+    if row_temperature is not None and (row_temperature.dtype != torch.float32 or tuple(row_temperature.shape) != (N,)):
+        raise ValueError("row_temperature must be a float32 tensor of shape (%d,), got %s %s"
+                         % (N, row_temperature.dtype, tuple(row_temperature.shape)))
+    z = torch.empty((N, H, W, Z), dtype=torch.float32, device=p.device)
+    lp = rows[0] if rows is not None else torch.empty((N,), dtype=torch.float32, device=p.device)
+    call('lvae_normal_prior_sample_f32', ptr(p), p_bcast, ptr(eps), float(temperature),
+         ptr(None if row_temperature is None else row_temperature.contiguous()), N, H * W, Z, ptr(z), ptr(lp), stream_ptr())
+    return z, lp
+
+
 def normal_stochastic_bwd(p, q, eps, z, dz, g_lp, g_lq, g_kl, g_ks, mode, analytical_kl, Z):
     N, H, W, _ = z.shape
     p_bcast = int(p.shape[0] == 1 and N > 1)

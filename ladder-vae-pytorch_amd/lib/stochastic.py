@@ -25,10 +25,17 @@ class NormalStochasticBlock2d(nn.Module):
         self.conv_out = Conv2dParams(c_vars, c_out, kernel, padding=pad)
 
     def forward(self, p_params, q_params=None, forced_latent=None, use_mode=False, force_constant_output=False,
-                analytical_kl=False, noise=None, n_img=None, need_kl_elementwise=True, rows=None, stats=None):
+                analytical_kl=False, noise=None, n_img=None, need_kl_elementwise=True, rows=None, stats=None, temperature=None):
         """need_kl_elementwise=False (engine-only keyword, used by TopDownLayer which drops that key, models/lvae_layers.py:163-170):
-        skip the pass that materialises `kl_elementwise` (lib/stochastic.py:88-91); the per-sample and per-pixel sums do not need it."""
+        skip the pass that materialises `kl_elementwise` (lib/stochastic.py:88-91); the per-sample and per-pixel sums do not need it.
+        temperature (engine-only keyword): None or 1.0 is the pass without it. Any other value draws z = mu_p + (t * sigma_p) * eps from the
+        prior (lvae_normal_prior_sample_f32; `logprob_p` stays that of the untempered prior): a float, where 0.0 draws no noise and gives
+        z = mu_p exactly, or a device float tensor (N,) of per-row temperatures. Sampling only: no q_params, forced_latent or use_mode
+        beside it, and no backward."""
         assert (forced_latent is None) or (not use_mode)
+        tempered = temperature is not None and (torch.is_tensor(temperature) or float(temperature) != 1.0)
+        if tempered and (q_params is not None or forced_latent is not None or use_mode):
+            raise ValueError("temperature applies to a draw from the prior: it cannot be combined with q_params, forced_latent or use_mode")
         if self.transform_p_params:
             p_params = self.conv_in_p(p_params)
         else:
@@ -39,6 +46,8 @@ class NormalStochasticBlock2d(nn.Module):
         N = ref.shape[0] if n_img is None else n_img
         H, W = ref.shape[1], ref.shape[2]
         dev = ref.device
+        if tempered:
+            return self._tempered(p_params, temperature, force_constant_output, noise, N, H, W, rows)
         if forced_latent is not None:
             mode, src = 2, forced_latent.contiguous()
         elif use_mode:
@@ -67,6 +76,26 @@ class NormalStochasticBlock2d(nn.Module):
             if need_kl_elementwise:
                 data['kl_elementwise'] = ops.KlElementwiseFn.apply(z, p_params, q_params, bool(analytical_kl))
         return out, data
+
+    def _tempered(self, p_params, temperature, force_constant_output, noise, N, H, W, rows):
+        """The prior draw of forward() at a temperature: same dict, same force_constant_output, one `normal` draw unless the scalar is 0."""
+        if torch.is_grad_enabled() and p_params.requires_grad:
+            raise RuntimeError("a tempered prior draw has no backward; run it under torch.no_grad()")
+        p_params = p_params.detach()
+        if torch.is_tensor(temperature):   # (kernels.normal_prior_sample checks its type and shape, the binding its device)
+            scalar, row_t = 1.0, temperature
+        else:
+            scalar, row_t = float(temperature), None
+            if not (0.0 <= scalar < float('inf')):
+                raise ValueError("temperature must be a finite number >= 0, got %r" % (temperature,))
+        eps = None if row_t is None and scalar == 0.0 else noise.normal((N, H, W, self.c_vars), p_params.device)
+        z, logprob_p = K.normal_prior_sample(p_params, eps, self.c_vars, N, scalar, row_t, rows=rows)
+        if force_constant_output:   # lib/stochastic.py:71-73
+            z = z[0:1].expand_as(z).contiguous()
+            p_params = p_params[0:1].expand(N, -1, -1, -1).contiguous()
+        out = self.conv_out(z)
+        return out, {'z': z, 'p_params': p_params, 'q_params': None, 'logprob_p': logprob_p, 'logprob_q': None,
+                     'kl_elementwise': None, 'kl_samplewise': None, 'kl_spatial': None}
 
 
 def kl_normal_mc(z, p_mulv, q_mulv):

@@ -15,6 +15,8 @@ Differences by design (not by omission):
 The boilr helpers the reference imports (pad/crop, Interpolate, free_bits_kl) are restated — parity unpinned
 (SURVEY.md §8c).
 """
+import numbers
+
 import numpy as np
 import torch
 from torch import nn
@@ -32,6 +34,27 @@ from .lvae_layers import BottomUpDeterministicResBlock, BottomUpLayer, TopDownDe
 def _nchw(t):
     """NHWC engine tensor -> logical NCHW view (no copy)."""
     return None if t is None else t.permute(0, 3, 1, 2)
+
+
+def layer_temperatures(L, value):
+    """The `temperature` argument of sample_prior / sample_conditional as a list of L entries indexed like z_dims (layer 0 is the bottom):
+    None -> L times None; a number -> L copies; a sequence of L numbers -> kept, as floats; a tensor (per-row temperatures, checked where
+    they are used) -> the same tensor at every layer. ValueError for a wrong length and for a negative or non-finite number; the values of
+    a tensor live on the device and are NOT validated, here or later: they are the caller's responsibility."""
+    if value is None or torch.is_tensor(value):
+        return [value] * L
+    values = [value] * L if isinstance(value, numbers.Real) else list(value)
+    if len(values) != L:
+        raise ValueError("temperature has %d values for %d layers: give one, or one per layer" % (len(values), L))
+    values = [float(v) for v in values]
+    for v in values:
+        if not 0.0 <= v < float('inf'):   # (NaN fails both comparisons)
+            raise ValueError("a temperature must be a finite number >= 0, got %r" % (v,))
+    return values
+
+
+def _untempered(temps):
+    return all(t is None or (not torch.is_tensor(t) and t == 1.0) for t in temps)
 
 
 class LadderVAE(nn.Module):
@@ -327,6 +350,38 @@ class LadderVAE(nn.Module):
                 out = mod(out, self.noise)
         return out, {'z': z, 'kl': kl, 'kl_spatial': kl_spatial, 'logprob_p': logprob_p}
 
+    def _topdown_mixed(self, bu_values, n_top, n_imgs, n_samples, temps, mode_layers=(), constant_layers=(), use_mode=False):
+        """The sampling sibling of _topdown (which stays all-posterior or all-prior): layers L-1 .. L-n_top run in inference mode on the
+        n_imgs rows of bu_values, by the code path of forward() (with use_mode at the posterior mean, drawing nothing); what they hand down
+        is repeated to n_samples * n_imgs rows, sample-major (K.repeat_samples; no launch for one sample), and layers L-n_top-1 .. 0 draw
+        from their prior there at temps[i] (None: the plain draw). With n_top = L the repeat sits in front of final_top_down; with
+        n_top = 0 nothing is handed down and the top layer broadcasts its prior over the n_samples * n_imgs rows itself.
+        Returns (out NHWC with n_samples * n_imgs rows, [z NHWC per layer])."""
+        L = self.n_layers
+        rows = int(n_samples) * int(n_imgs)
+        z = [None] * L
+        out = None
+        for i in reversed(range(L)):
+            if i >= L - n_top:
+                out, _, aux = self.top_down_layers[i](out, skip_connection_input=out, inference_mode=True, bu_value=bu_values[i],
+                                                      use_mode=use_mode, noise=self.noise)
+            else:
+                if out is not None and i == L - n_top - 1 and n_samples > 1:
+                    out = K.repeat_samples(out, n_samples)
+                in_mode = i in mode_layers
+                out, _, aux = self.top_down_layers[i](out, skip_connection_input=out, inference_mode=False, n_img_prior=rows,
+                                                      use_mode=in_mode, force_constant_output=i in constant_layers,
+                                                      noise=self.noise, temperature=None if in_mode else temps[i])
+            z[i] = aux['z']
+        if n_top == L and n_samples > 1:
+            out = K.repeat_samples(out, n_samples)
+        for mod in self.final_top_down:
+            if isinstance(mod, Placeholder):
+                out = ops.UpsampleFn.apply(out)
+            else:
+                out = mod(out, self.noise)
+        return out, z
+
     def topdown_pass(self, bu_values=None, n_img_prior=None, mode_layers=None, constant_layers=None,
                      forced_latent=None):
         """models/lvae.py:229-315 (NCHW in / NCHW out wrapper of the engine's NHWC pass)."""
@@ -354,15 +409,61 @@ class LadderVAE(nn.Module):
                 len(size), size))
         return list(((s - 1) // dwnsc + 1) * dwnsc for s in size)
 
-    def sample_prior(self, n_imgs, mode_layers=None, constant_layers=None):
-        """models/lvae.py:351-362."""
+    def sample_prior(self, n_imgs, mode_layers=None, constant_layers=None, temperature=None):
+        """models/lvae.py:351-362. temperature: engine-only keyword — z = mu_p + t * sigma_p * eps at every layer that samples: a float,
+        a sequence of L floats indexed like z_dims, or a device float tensor (n_imgs,) of per-row temperatures used at every layer. A layer
+        in mode_layers ignores its temperature; a layer at 0.0 draws no noise. None or 1.0 is the call without the keyword, bit for bit."""
+        temps = layer_temperatures(self.n_layers, temperature)
         self._begin(None)
-        out, _ = self._topdown(n_img_prior=n_imgs, mode_layers=mode_layers, constant_layers=constant_layers)
+        if _untempered(temps):
+            out, _ = self._topdown(n_img_prior=n_imgs, mode_layers=mode_layers, constant_layers=constant_layers)
+        else:
+            out, _ = self._topdown_mixed(None, 0, n_imgs, 1, temps, mode_layers or (), constant_layers or ())
         if tuple(out.shape[1:3]) != tuple(self.img_shape):
             out = ops.CropFn.apply(out, tuple(self.img_shape))
         _, likelihood_data = self.likelihood(out, None, self.noise)
         self.noise.end()
         return _nchw(likelihood_data['sample'])
+
+    def sample_conditional(self, x, n_top_layers, n_samples=1, temperature=None, use_mode=False):
+        """Engine-only: images that share the top k = n_top_layers latents of x. The k top layers take z from the posterior of x (as
+        forward() does; with use_mode its mean), the layers below are sampled from the prior K = n_samples times per image at
+        `temperature` (as in sample_prior), then final_top_down, the crop and the likelihood without a target. x (B, C, H, W); k = 0 is
+        K * B prior samples (no bottom-up pass: x only gives B), k = L is K likelihood draws of one reconstruction pass. Rows are
+        sample-major (row k * B + b). Obeys the module's train / eval mode, like sample_prior.
+
+        Noise, in this order: one `normal` draw per layer that samples, top to bottom, of shape (rows, h, w, Z) with rows = B for a
+        posterior layer and K * B for a prior layer (none for a posterior layer under use_mode, none for a prior layer at temperature 0.0),
+        then the likelihood's draws.
+
+        Returns {'sample', 'mean', 'mode'} (NCHW, K * B rows; None where the likelihood has none), 'likelihood_params', and 'z': L NCHW
+        tensors, B rows for the posterior layers and K * B rows for the prior layers."""
+        if not x.is_cuda:
+            raise K._C.LvaeHipError("LadderVAE (HIP engine) needs a GPU tensor; got %s" % x.device)
+        L = self.n_layers
+        if x.dim() != 4:
+            raise ValueError("x must be (B, C, H, W), got %s" % (tuple(x.shape),))
+        n_top, n_samples = int(n_top_layers), int(n_samples)
+        if not 0 <= n_top <= L:
+            raise ValueError("n_top_layers must be in 0..%d, got %d" % (L, n_top))
+        if n_samples < 1:
+            raise ValueError("n_samples must be at least 1, got %d" % n_samples)
+        temps = layer_temperatures(L, temperature)
+        self._begin(x)
+        img_size = tuple(int(s) for s in x.shape[2:])
+        bu_values = None
+        if n_top > 0:
+            x_pad = K.pad_crop(x.contiguous().float(), True, self.get_padded_size(x.size()), False)
+            bu_values = self._bottomup(x_pad)
+        out, z = self._topdown_mixed(bu_values, n_top, x.shape[0], n_samples, temps, use_mode=use_mode)
+        if tuple(out.shape[1:3]) != img_size:
+            out = ops.CropFn.apply(out, img_size)
+        _, info = self.likelihood(out, None, self.noise)
+        self.noise.end()
+        params = info['params']
+        params = {k: _nchw(v) for k, v in params.items()} if isinstance(params, dict) else _nchw(params)
+        return {'sample': _nchw(info['sample']), 'mean': _nchw(info['mean']), 'mode': _nchw(info['mode']),
+                'likelihood_params': params, 'z': [_nchw(t) for t in z]}
 
     def get_top_prior_param_shape(self, n_imgs=1):
         """models/lvae.py:364-372."""

@@ -153,7 +153,8 @@ class TopDownLayer(nn.Module):
                                                                    res_block_type=res_block_type)
 
     def forward(self, input_=None, skip_connection_input=None, inference_mode=False, bu_value=None, n_img_prior=None,
-                forced_latent=None, use_mode=False, force_constant_output=False, noise=None, rows=None, stats=None):
+                forced_latent=None, use_mode=False, force_constant_output=False, noise=None, rows=None, stats=None, temperature=None):
+        """temperature: engine-only keyword, handed to the stochastic block (a tempered draw from the prior: generative mode only)."""
         inputs_none = input_ is None and skip_connection_input is None
         if self.is_top_layer and not inputs_none:
             raise ValueError("In top layer, inputs should be None")
@@ -178,7 +179,7 @@ class TopDownLayer(nn.Module):
         x, data_stoch = self.stochastic(p_params=p_params, q_params=q_params, forced_latent=forced_latent,
                                         use_mode=use_mode, force_constant_output=force_constant_output,
                                         analytical_kl=self.analytical_kl, noise=noise, n_img=n_img,
-                                        need_kl_elementwise=False, rows=rows, stats=stats)
+                                        need_kl_elementwise=False, rows=rows, stats=stats, temperature=temperature)
         if self.stochastic_skip and not self.is_top_layer:
             x = self.skip_connection_merger(x, skip_connection_input, noise)
         x_pre_residual = x
