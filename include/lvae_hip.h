@@ -145,7 +145,7 @@ typedef struct lvae_conv_desc {
   uint8_t reserved_;      /* 0 */
 } lvae_conv_desc;
 
-/* Kernel choice: lvae_conv2d_f32 / _bf16 choose one kernel per descriptor (pos -> bf16 direct -> Winograd -> halo -> 1x1 -> generic,
+/* Kernel choice: lvae_conv2d_f32 / _bf16 choose one kernel per descriptor (pos -> bf16 direct -> Winograd -> halo -> 1x1 -> stride-2 pos -> generic,
  * made on the descriptor without its in_fold), and every query below (_workspace, _variant, _stats_rows, _folds_bn_finalize,
  * _stats_buffer_rows, lvae_resblock_bf16_storage) answers for exactly the kernel the launch takes. A variant that reads a scratch buffer
  * needs d->workspace present, at least lvae_conv2d_workspace(d) bytes and 16-byte aligned; otherwise the choice (and every answer)
@@ -176,6 +176,10 @@ enum {
   LVAE_VARIANT_SIX_DIRECT = 6    /* direct 3x3, six-product form (form LVAE_FORM_SIX_PRODUCT_DIRECT) */
 };
 int32_t lvae_conv2d_variant(const lvae_conv_desc* d);
+/* 1 when lvae_conv2d_f32 runs `d` as given on a position-major kernel (GEMM rows = 32 images at one output position): the stride-1 one
+ * of the <= 4x4 levels (LVAE_VARIANT_POS) or the stride-2 / transposed one (3x3, pad 1, one source of at most 64 channels, fp32 storage;
+ * its variant is LVAE_VARIANT_DIRECT like the generic kernel's, which this query tells apart). 0 otherwise. Host only, no launch. */
+int32_t lvae_conv2d_position_major(const lvae_conv_desc* d);
 /* 1 when a residual block whose 3x3 convolutions look like `d` (a FORWARD descriptor: 64 -> 64 channels, precision LVAE_PREC_BF16, its
  * workspace attached) can keep its internal tensors in bf16: forward, dgrad and weight gradient of the convolution, the GateLayer2d
  * forward and its fused backward, and the BatchNorm-backward apply all have a bf16-storage form for N x H x W. 0 otherwise. */

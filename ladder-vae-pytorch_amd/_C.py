@@ -95,6 +95,7 @@ SIGNATURES = {
     'lvae_conv1x1_dgrad_cat_ok': (_I, [C.POINTER(ConvDesc), _I]),
     'lvae_conv2d_stats_rows': (_I, [C.POINTER(ConvDesc)]),
     'lvae_conv2d_variant': (_I, [C.POINTER(ConvDesc)]),
+    'lvae_conv2d_position_major': (_I, [C.POINTER(ConvDesc)]),
     'lvae_resblock_bf16_storage': (_I, [C.POINTER(ConvDesc)]),
     'lvae_conv2d_folds_bn_finalize': (_I, [C.POINTER(ConvDesc)]),
     'lvae_conv2d_stats_buffer_rows': (_I, [C.POINTER(ConvDesc)]),

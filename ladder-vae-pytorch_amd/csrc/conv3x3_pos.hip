@@ -16,6 +16,8 @@
 // the partial sums the producing kernel's epilogue left (lvae_bn_finalize_parts_f32 as a prologue: 64 loads per thread while the
 // operand loads are in flight, instead of a 5 us launch in a dependent chain); workgroup 0 publishes (scale, shift, mean, rstd)
 // for the backward and updates the running statistics.
+//
+// The stride-2 and transposed 3x3 convolutions run the same scheme in conv3x3_resample.hip (a kernel of its own: no statistics, no fold).
 #include "bn_stats.h"
 #include "lvae_host.h"
 

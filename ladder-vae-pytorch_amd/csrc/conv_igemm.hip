@@ -343,14 +343,14 @@ int conv_desc_check(const lvae_conv_desc* d, const char* who) {
 
 static bool aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
 
-enum { ROUTE_POS, ROUTE_BF16, ROUTE_WINO, ROUTE_HALO, ROUTE_1X1, ROUTE_GENERIC };
+enum { ROUTE_POS, ROUTE_BF16, ROUTE_WINO, ROUTE_HALO, ROUTE_1X1, ROUTE_RESAMPLE, ROUTE_GENERIC };
 
 struct ConvRoute {
   int kind = ROUTE_GENERIC;
   ConvPlan plan;  // the generic kernel: LVAE_VARIANT_DIRECT, no statistics, no fold, no workspace
 };
 
-// The kernel of a forward / dgrad convolution, chosen once in the order pos -> bf16 direct -> Winograd -> halo -> 1x1 -> generic. Every
+// The kernel of a forward / dgrad convolution, chosen once in the order pos -> bf16 direct -> Winograd -> halo -> 1x1 -> stride-2 pos -> generic. Every
 // lvae_conv2d_* query and the launch read this. The choice is made on the descriptor without its in_fold (a kernel that folds the
 // BatchNorm finalize takes it; lvae_conv2d_f32 refuses it otherwise). assume_ws: answer for a sized, 16-byte aligned workspace instead of
 // d's own (lvae_conv2d_workspace).
@@ -365,6 +365,7 @@ static ConvRoute conv_route(const lvae_conv_desc* d, bool assume_ws = false) {
   else if (conv3x3_wino_plan(&t, assume_ws, r.plan)) r.kind = ROUTE_WINO;
   else if (conv3x3_halo_plan(&t, r.plan)) r.kind = ROUTE_HALO;
   else if (conv1x1_plan(&t, PwForm{}, r.plan)) r.kind = ROUTE_1X1;
+  else if (conv3x3_resample_plan(&t, r.plan)) r.kind = ROUTE_RESAMPLE;
   return r;
 }
 
@@ -375,6 +376,12 @@ using namespace lvae;
 extern "C" size_t lvae_conv2d_workspace(const lvae_conv_desc* d) { return d ? conv_route(d, true).plan.workspace : 0; }
 
 extern "C" int32_t lvae_conv2d_variant(const lvae_conv_desc* d) { return d ? conv_route(d).plan.variant : LVAE_VARIANT_DIRECT; }
+
+extern "C" int32_t lvae_conv2d_position_major(const lvae_conv_desc* d) {
+  if (d == nullptr) return 0;
+  const int kind = conv_route(d).kind;
+  return kind == ROUTE_POS || kind == ROUTE_RESAMPLE ? 1 : 0;
+}
 
 extern "C" int32_t lvae_resblock_bf16_storage(const lvae_conv_desc* d) {
   if (d == nullptr || d->precision != LVAE_PREC_BF16 || d->C1 != 64 || d->C2 != 0 || d->Cout != 64 || d->gather != LVAE_GATHER_CONV) return 0;
@@ -433,6 +440,7 @@ extern "C" int lvae_conv2d_f32(const lvae_conv_desc* d, void* stream) {
     case ROUTE_WINO: return conv3x3_wino_launch(d, s);
     case ROUTE_HALO: return conv3x3_halo_launch(d, s);
     case ROUTE_1X1: return conv1x1_launch(d, PwForm{}, s);
+    case ROUTE_RESAMPLE: return conv3x3_resample_launch(d, s);
   }
   ConvArgs a;
   a.d = *d;

@@ -66,6 +66,10 @@ int conv3x3_halo_launch(const lvae_conv_desc* d, hipStream_t s);
 bool conv3x3_pos_plan(const lvae_conv_desc* d, ConvPlan& p);
 int conv3x3_pos_launch(const lvae_conv_desc* d, hipStream_t s);
 
+// conv3x3_resample.hip: the stride-2 and transposed 3x3 convolutions, position-major (LVAE_VARIANT_DIRECT, no rows, no fold, no workspace)
+bool conv3x3_resample_plan(const lvae_conv_desc* d, ConvPlan& p);
+int conv3x3_resample_launch(const lvae_conv_desc* d, hipStream_t s);
+
 // conv3x3_wino.hip
 bool conv3x3_wino_plan(const lvae_conv_desc* d, bool assume_ws, ConvPlan& p);
 int conv3x3_wino_launch(const lvae_conv_desc* d, hipStream_t s);
