@@ -769,6 +769,50 @@ int lvae_lr_schedule_at(const lvae_lr_schedule* schedule, uint64_t n, float* lr)
 int lvae_adamax_sched_step_f32(float* p, const float* g, float* exp_avg, float* exp_inf, const float* mask, int64_t n,
                                const lvae_lr_schedule* schedule, float beta1, float beta2, float eps, float weight_decay,
                                const float* gscale, const uint64_t* step_count, float* ema, float decay, float* lr_out, void* stream);
+/* The gradient guard: clip the gradient by its global norm and / or leave a step out, decided on the device between the gradient exchange
+ * and Adamax, so that a captured step replays the decision. lvae_grad_guard_f32 takes the arena's norm and writes this struct (device
+ * memory, 8-byte aligned, 32 bytes); the guarded Adamax, lvae_counter_advance_unless and lvae_multi_copy_f32 read it.
+ *   norm     sqrt(sum g^2), bit for bit lvae_l2norm_f32's value (before gscale_in)
+ *   scale    what Adamax multiplies the gradient by: gscale_in * min(1, max_norm / (norm * gscale_in + 1e-6)), the quotient formed in double
+ *            and the product rounded to float once; gscale_in itself without clipping; 0 on a skipped step
+ *   skip     1: this step is left out, 0: it is applied
+ *   clipped  applied steps with norm * gscale_in > max_norm since the struct was zeroed (cumulative)
+ *   skipped  steps left out since then (cumulative) */
+typedef struct lvae_grad_guard_state {
+  float norm;
+  float scale;
+  int32_t skip;
+  int32_t reserved_;
+  uint64_t clipped;
+  uint64_t skipped;
+} lvae_grad_guard_state;
+/* g [n]; gscale_in: device float[1] or NULL (= 1), the factor Adamax would apply; workspace as for lvae_l2norm_f32. With e = norm * gscale_in
+ * (formed in fp32: the number lvae_summary_fold_f64 adds to its grad slot) the step is skipped when e is not finite (a NaN or Inf anywhere
+ * in g, or a sum of squares beyond fp32) or when skip_threshold >= 0 and e > skip_threshold (0 skips every non-zero gradient, +Inf only
+ * the non-finite ones; a negative threshold: non-finite ones only, too). max_norm <= 0, NaN or Inf: no clipping. A step is counted as
+ * clipped when it is applied and e > max_norm (e == max_norm still gets the factor max_norm / (max_norm + 1e-6), as from
+ * torch.nn.utils.clip_grad_norm_). Two launches: the partial sums of lvae_l2norm_f32, then one workgroup that adds them in the same order,
+ * decides, and writes the struct with plain stores from one thread (no atomics). */
+int lvae_grad_guard_f32(const float* g, int64_t n, const float* gscale_in, float max_norm, float skip_threshold,
+                        lvae_grad_guard_state* state, void* workspace, size_t workspace_bytes, void* stream);
+/* The Adamax step under a guard: with guard->skip set every thread returns before its first store (p, exp_avg, exp_inf, ema and lr_out
+ * keep their bits); otherwise the gradient is multiplied by guard->scale and every output is bit for bit that of the unguarded entry point
+ * of the same options called with gscale -> scale. schedule: NULL (the step runs at `lr`) or a schedule as for lvae_adamax_sched_step_f32
+ * (`lr` is then ignored); ema and lr_out optional as there. There is no gscale argument: guard->scale holds it. Advance the step counter
+ * with lvae_counter_advance_unless(step_count, 1, &guard->skip). */
+int lvae_adamax_guarded_step_f32(float* p, const float* g, float* exp_avg, float* exp_inf, const float* mask, int64_t n, float lr,
+                                 const lvae_lr_schedule* schedule, float beta1, float beta2, float eps, float weight_decay,
+                                 const uint64_t* step_count, float* ema, float decay, float* lr_out,
+                                 const lvae_grad_guard_state* guard, void* stream);
+/* table: device array of n_entries {dst, src, n}; entry e is copied, dst[0:n] = src[0:n], by workgroup e, when flag == NULL or
+ * flag[0] == want (flag: device int32[1], e.g. &guard->skip). The guarded step saves every BatchNorm running statistic into one shadow
+ * buffer with it before the forward pass and puts them back after the guard on a skipped step. Entries must not overlap each other. */
+typedef struct lvae_copy_entry {
+  float* dst;
+  const float* src;
+  int64_t n;
+} lvae_copy_entry;
+int lvae_multi_copy_f32(const lvae_copy_entry* table, int32_t n_entries, const int32_t* flag, int32_t want, void* stream);
 /* a[0:n] <-> b[0:n] in one pass (16-byte aligned, not overlapping): the averaged weights exchanged IN PLACE with the trainable prefix of
  * the parameter arena for a test pass and back, so captured graphs and parameter views keep their addresses. */
 int lvae_swap_f32(float* a, float* b, int64_t n, void* stream);
@@ -784,6 +828,8 @@ int lvae_l2norm_f32(const float* x, int64_t n, float* out, void* workspace, size
 int lvae_rng_fill_f32(float* out, int64_t n, int32_t kind, float lo, float hi, uint64_t seed, const uint64_t* offset,
                       uint64_t stream_id, void* stream);
 int lvae_counter_advance(uint64_t* counter, uint64_t by, void* stream);
+/* counter[0] += by unless flag[0] != 0 (flag: device int32[1]): the Adamax step counter of a guarded step, which stands still on a skipped one. */
+int lvae_counter_advance_unless(uint64_t* counter, uint64_t by, const int32_t* flag, void* stream);
 /* out[0:n] = value (16-byte aligned out). replaces: optimizer.zero_grad() of boilr's training loop on the flat gradient arena. */
 int lvae_fill_f32(float* out, int64_t n, float value, void* stream);
 

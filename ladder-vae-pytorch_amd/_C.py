@@ -75,6 +75,17 @@ class LrScheduleStruct(C.Structure):
                 ('warmup_steps', C.c_int64), ('decay_steps', C.c_int64)]
 
 
+class GradGuardState(C.Structure):
+    """mirror of struct lvae_grad_guard_state (device memory: the mirror gives the layout optim.GradGuard's views follow)"""
+    _fields_ = [('norm', C.c_float), ('scale', C.c_float), ('skip', C.c_int32), ('reserved_', C.c_int32), ('clipped', C.c_uint64),
+                ('skipped', C.c_uint64)]
+
+
+class CopyEntry(C.Structure):
+    """mirror of struct lvae_copy_entry"""
+    _fields_ = [('dst', C.c_void_p), ('src', C.c_void_p), ('n', C.c_int64)]
+
+
 LR_KINDS = {'constant': 0, 'cosine': 1, 'linear': 2, 'step': 3, 'exp': 4}   # LVAE_LR_*
 
 RB_PRO_AFFINE, RB_PRO_BN_APPLY, RB_PRO_GATE_BWD = 0, 1, 2
@@ -184,11 +195,15 @@ SIGNATURES = {
     'lvae_adamax_ema_step_f32': (C.c_int, [_P, _P, _P, _P, _P, _L, _F, _F, _F, _F, _F, _P, _P, _P, _F, _P]),
     'lvae_lr_schedule_at': (C.c_int, [C.POINTER(LrScheduleStruct), _U, C.POINTER(C.c_float)]),
     'lvae_adamax_sched_step_f32': (C.c_int, [_P, _P, _P, _P, _P, _L, C.POINTER(LrScheduleStruct), _F, _F, _F, _F, _P, _P, _P, _F, _P, _P]),
+    'lvae_grad_guard_f32': (C.c_int, [_P, _L, _P, _F, _F, _P, _P, _Z, _P]),
+    'lvae_adamax_guarded_step_f32': (C.c_int, [_P, _P, _P, _P, _P, _L, _F, C.POINTER(LrScheduleStruct), _F, _F, _F, _F, _P, _P, _F, _P, _P, _P]),
+    'lvae_multi_copy_f32': (C.c_int, [_P, _I, _P, _I, _P]),
     'lvae_swap_f32': (C.c_int, [_P, _P, _L, _P]),
     'lvae_sumsq_workspace': (_Z, [_L]),
     'lvae_l2norm_f32': (C.c_int, [_P, _L, _P, _P, _Z, _P]),
     'lvae_rng_fill_f32': (C.c_int, [_P, _L, _I, _F, _F, _U, _P, _U, _P]),
     'lvae_counter_advance': (C.c_int, [_P, _U, _P]),
+    'lvae_counter_advance_unless': (C.c_int, [_P, _U, _P, _P]),
     'lvae_fill_f32': (C.c_int, [_P, _L, _F, _P]),
     'lvae_allreduce_unique_id': (C.c_int, [C.c_char_p, _P]),
     'lvae_allreduce_init': (C.c_int, [C.c_char_p, _P, _I, _I, C.POINTER(C.c_void_p)]),

@@ -76,7 +76,8 @@ def save_checkpoint(path, model, optimizer=None, summary=None):
     the original one bit for bit. With a `summary` (summary.TrainSummary) also 'summary': the open log window's accumulator as a list of
     floats, so that the run resumed in the middle of a window prints the train line of the uninterrupted one. A scheduled lr is a function
     of the Adamax step and of the schedule, stored as 'lr_schedule' (`lr_schedule_record`). 'iw_train_samples' notes the K of the objective
-    the run trained on (model.iw_train_samples; 1 = the ELBO), by the same rule: load_checkpoint does not touch the resumed run's own."""
+    the run trained on (model.iw_train_samples; 1 = the ELBO), by the same rule: load_checkpoint does not touch the resumed run's own.
+    A guarded optimizer adds 'grad_guard' (GradGuard.state_dict: its limits and the cumulative clipped / skipped counts)."""
     ck = {'model': state_dict_reference_layout(model), 'global_step': int(model.global_step)}
     if optimizer is not None:
         ck['optimizer'] = optimizer_state_by_name(model, optimizer)
@@ -85,6 +86,8 @@ def save_checkpoint(path, model, optimizer=None, summary=None):
             ck['ema_decay'] = optimizer.ema_decay
         if lr_schedule_record(optimizer) is not None:
             ck['lr_schedule'] = lr_schedule_record(optimizer)
+        if getattr(optimizer, 'guard', None) is not None:
+            ck['grad_guard'] = optimizer.guard.state_dict()
     ck['iw_train_samples'] = int(getattr(model, 'iw_train_samples', 1))   # what the file's run trained on; a resumed run uses its own flag
     nz = noise_state(model)
     if nz is not None:
@@ -103,7 +106,8 @@ def load_checkpoint(path, model, optimizer=None, summary=None):
     """Loads a file written by `save_checkpoint` (with the noise stream's position and the device global-step counter when it holds
     them), or a bare reference `state_dict` file. Load before a TrainStep captures its graph: the graph keeps the counters it saw.
     An averaging optimizer gets its average from the file's 'ema'; from a file without one the average starts at the loaded weights.
-    A `summary` gets the file's open log window; from a file without one it starts an empty window."""
+    A `summary` gets the file's open log window; from a file without one it starts an empty window. A guarded optimizer continues the
+    file's clipped / skipped counts under its own limits; from a file without 'grad_guard' it keeps the counts it has."""
     ck = torch.load(path, map_location='cpu')
     sd = ck['model'] if isinstance(ck, dict) and 'model' in ck else ck
     model.load_state_dict(sd)
@@ -137,6 +141,8 @@ def load_checkpoint(path, model, optimizer=None, summary=None):
                 view.copy_(ck['ema'][name])
         else:
             optimizer.ema.copy_(arena.params[:arena.n_train])
+    if optimizer is not None and getattr(optimizer, 'guard', None) is not None and isinstance(ck, dict) and 'grad_guard' in ck:
+        optimizer.guard.load_state_dict(ck['grad_guard'])
     if summary is not None:
         if isinstance(ck, dict) and 'model' in ck and 'summary' in ck:
             summary.load_state(ck['summary'])

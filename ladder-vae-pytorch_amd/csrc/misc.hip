@@ -270,13 +270,20 @@ __global__ __launch_bounds__(256) void iw_online_kernel(const float* __restrict_
 // ramp d = min(decay, (1 + n) / (10 + n)) over the n completed steps read from the device counter (a replayed graph follows the ramp).
 // SCHED: lr is not the host's value but the schedule's at the n completed steps of the same counter (lr_schedule.h; the schedule is constant
 // over a run, so a captured launch may keep it), and block 0 leaves the lr it applied in lr_out (optional) for the log.
-template <bool EMA, bool SCHED>
+// GUARD: the step is under a gradient guard (grad_guard_final_kernel below): on a skipped step every thread returns before its first store,
+// lr_out included; otherwise the gradient factor is the guard's scale in the place of gscale[0].
+template <bool EMA, bool SCHED, bool GUARD = false>
 __global__ __launch_bounds__(256) void adamax_kernel(float* __restrict__ p, const float* __restrict__ g,
                                                       float* __restrict__ m, float* __restrict__ u,
                                                       const float* __restrict__ mask, int64_t n4, float lr, float b1,
                                                       float b2, float eps, float wd, const float* gscale,
                                                       const uint64_t* step_count, float* __restrict__ ema, float decay,
-                                                      lvae_lr_schedule sched, float* lr_out) {
+                                                      lvae_lr_schedule sched, float* lr_out,
+                                                      const lvae_grad_guard_state* guard) {
+  if (GUARD) {
+    if (guard->skip) return;
+    gscale = &guard->scale;
+  }
   if (SCHED) {
     lr = lr_schedule_eval(sched, step_count[0]);
     if (lr_out && blockIdx.x == 0 && threadIdx.x == 0) lr_out[0] = lr;
@@ -345,6 +352,30 @@ __global__ __launch_bounds__(256) void sumsq_final_kernel(const float* partial, 
   if (threadIdx.x == 0) out[0] = sqrtf(acc);
 }
 
+// The gradient guard's decision: sumsq_final_kernel's sum (same order, so the same norm bit for bit), then thread 0 clips, decides and counts.
+// e = norm * gscale is the norm of the gradient Adamax would apply. A NaN or Inf in the arena, or a sum beyond fp32, makes e non-finite.
+__global__ __launch_bounds__(256) void grad_guard_final_kernel(const float* partial, int cnt, const float* gscale_in, float max_norm,
+                                                                float skip_threshold, lvae_grad_guard_state* st) {
+  __shared__ float red[4];
+  float acc = 0.f;
+  for (int i = threadIdx.x; i < cnt; i += 256) acc += partial[i];
+  acc = block_sum_256(acc, red);
+  if (threadIdx.x != 0) return;
+  const float norm = sqrtf(acc);
+  const float gs = gscale_in ? gscale_in[0] : 1.f;
+  const float e = norm * gs;
+  const bool clip_on = max_norm > 0.f && max_norm <= 3.402823466e38f;   // (false for NaN and Inf)
+  const bool skip = !(fabsf(e) <= 3.402823466e38f) || (skip_threshold >= 0.f && e > skip_threshold);
+  float scale = gs;
+  if (clip_on) scale = (float)((double)gs * fmin(1.0, (double)max_norm / ((double)e + 1e-6)));
+  st->norm = norm;
+  st->scale = skip ? 0.f : scale;
+  st->skip = skip ? 1 : 0;
+  st->reserved_ = 0;
+  if (skip) st->skipped = st->skipped + 1;
+  else if (clip_on && e > max_norm) st->clipped = st->clipped + 1;
+}
+
 // ---------------------------------------------------------------------------------------------------------
 // Philox4x32-10
 // ---------------------------------------------------------------------------------------------------------
@@ -401,6 +432,17 @@ __global__ __launch_bounds__(256) void rng_fill_kernel(float* __restrict__ out, 
 
 __global__ void counter_advance_kernel(uint64_t* c, uint64_t by) {
   if (threadIdx.x == 0 && blockIdx.x == 0) c[0] += by;
+}
+
+__global__ void counter_advance_unless_kernel(uint64_t* c, uint64_t by, const int32_t* flag) {
+  if (threadIdx.x == 0 && blockIdx.x == 0 && flag[0] == 0) c[0] += by;
+}
+
+// workgroup e copies entry e of the table, or nothing when the flag says otherwise (the whole grid takes the same branch)
+__global__ __launch_bounds__(256) void multi_copy_kernel(const lvae_copy_entry* __restrict__ table, const int32_t* flag, int32_t want) {
+  if (flag && flag[0] != want) return;
+  const lvae_copy_entry en = table[blockIdx.x];
+  for (int64_t i = threadIdx.x; i < en.n; i += 256) en.dst[i] = en.src[i];
 }
 
 }  // namespace lvae
@@ -499,7 +541,7 @@ extern "C" int lvae_adamax_step_f32(float* p, const float* g, float* exp_avg, fl
   LVAE_REQUIRE(n % 4 == 0, LVAE_EALIGN, "lvae_adamax_step_f32: arena length %lld must be a multiple of 4", (long long)n);
   hipLaunchKernelGGL((adamax_kernel<false, false>), dim3(grid_for(n / 4, 256)), dim3(256), 0, (hipStream_t)stream, p, g, exp_avg,
                      exp_inf, mask, n / 4, lr, beta1, beta2, eps, weight_decay, gscale, step_count, (float*)nullptr, 0.f,
-                     lvae_lr_schedule{}, (float*)nullptr);
+                     lvae_lr_schedule{}, (float*)nullptr, (const lvae_grad_guard_state*)nullptr);
   LVAE_LAUNCH_CHECK("adamax_step");
   return 0;
 }
@@ -513,7 +555,7 @@ extern "C" int lvae_adamax_ema_step_f32(float* p, const float* g, float* exp_avg
   LVAE_REQUIRE((reinterpret_cast<uintptr_t>(ema) & 15) == 0, LVAE_EALIGN, "lvae_adamax_ema_step_f32: misaligned ema");
   hipLaunchKernelGGL((adamax_kernel<true, false>), dim3(grid_for(n / 4, 256)), dim3(256), 0, (hipStream_t)stream, p, g, exp_avg,
                      exp_inf, mask, n / 4, lr, beta1, beta2, eps, weight_decay, gscale, step_count, ema, decay, lvae_lr_schedule{},
-                     (float*)nullptr);
+                     (float*)nullptr, (const lvae_grad_guard_state*)nullptr);
   LVAE_LAUNCH_CHECK("adamax_ema_step");
   return 0;
 }
@@ -551,12 +593,43 @@ extern "C" int lvae_adamax_sched_step_f32(float* p, const float* g, float* exp_a
     LVAE_REQUIRE(decay >= 0.f && decay < 1.f, LVAE_EINVAL, "lvae_adamax_sched_step_f32: decay %g outside [0, 1)", (double)decay);
     LVAE_REQUIRE((reinterpret_cast<uintptr_t>(ema) & 15) == 0, LVAE_EALIGN, "lvae_adamax_sched_step_f32: misaligned ema");
     hipLaunchKernelGGL((adamax_kernel<true, true>), grid, dim3(256), 0, (hipStream_t)stream, p, g, exp_avg, exp_inf, mask, n / 4, 0.f,
-                       beta1, beta2, eps, weight_decay, gscale, step_count, ema, decay, *schedule, lr_out);
+                       beta1, beta2, eps, weight_decay, gscale, step_count, ema, decay, *schedule, lr_out, (const lvae_grad_guard_state*)nullptr);
   } else {
     hipLaunchKernelGGL((adamax_kernel<false, true>), grid, dim3(256), 0, (hipStream_t)stream, p, g, exp_avg, exp_inf, mask, n / 4, 0.f,
-                       beta1, beta2, eps, weight_decay, gscale, step_count, (float*)nullptr, 0.f, *schedule, lr_out);
+                       beta1, beta2, eps, weight_decay, gscale, step_count, (float*)nullptr, 0.f, *schedule, lr_out,
+                       (const lvae_grad_guard_state*)nullptr);
   }
   LVAE_LAUNCH_CHECK("adamax_sched_step");
+  return 0;
+}
+
+extern "C" int lvae_adamax_guarded_step_f32(float* p, const float* g, float* exp_avg, float* exp_inf, const float* mask, int64_t n, float lr,
+                                            const lvae_lr_schedule* schedule, float beta1, float beta2, float eps, float weight_decay,
+                                            const uint64_t* step_count, float* ema, float decay, float* lr_out,
+                                            const lvae_grad_guard_state* guard, void* stream) {
+  LVAE_REQUIRE(p && g && exp_avg && exp_inf && step_count && guard && n > 0, LVAE_EINVAL, "lvae_adamax_guarded_step_f32: bad args");
+  if (schedule)
+    if (int rc = lr_schedule_valid(schedule, "lvae_adamax_guarded_step_f32")) return rc;
+  LVAE_REQUIRE(n % 4 == 0, LVAE_EALIGN, "lvae_adamax_guarded_step_f32: arena length %lld must be a multiple of 4", (long long)n);
+  LVAE_REQUIRE((reinterpret_cast<uintptr_t>(guard) & 7) == 0, LVAE_EALIGN, "lvae_adamax_guarded_step_f32: misaligned guard state");
+  if (ema) {
+    LVAE_REQUIRE(decay >= 0.f && decay < 1.f, LVAE_EINVAL, "lvae_adamax_guarded_step_f32: decay %g outside [0, 1)", (double)decay);
+    LVAE_REQUIRE((reinterpret_cast<uintptr_t>(ema) & 15) == 0, LVAE_EALIGN, "lvae_adamax_guarded_step_f32: misaligned ema");
+  }
+  const dim3 grid(grid_for(n / 4, 256));
+  const lvae_lr_schedule sched = schedule ? *schedule : lvae_lr_schedule{};
+  const float* no_gscale = nullptr;
+  float* no_lr_out = nullptr;
+#define LVAE_GUARDED_ADAMAX(EMA, SCHED)                                                                                              \
+  hipLaunchKernelGGL((adamax_kernel<EMA, SCHED, true>), grid, dim3(256), 0, (hipStream_t)stream, p, g, exp_avg, exp_inf, mask, n / 4, \
+                     SCHED ? 0.f : lr, beta1, beta2, eps, weight_decay, no_gscale, step_count, EMA ? ema : (float*)nullptr,           \
+                     EMA ? decay : 0.f, sched, SCHED ? lr_out : no_lr_out, guard)
+  if (ema && schedule) LVAE_GUARDED_ADAMAX(true, true);
+  else if (ema) LVAE_GUARDED_ADAMAX(true, false);
+  else if (schedule) LVAE_GUARDED_ADAMAX(false, true);
+  else LVAE_GUARDED_ADAMAX(false, false);
+#undef LVAE_GUARDED_ADAMAX
+  LVAE_LAUNCH_CHECK("adamax_guarded_step");
   return 0;
 }
 
@@ -583,6 +656,29 @@ extern "C" int lvae_l2norm_f32(const float* x, int64_t n, float* out, void* work
   LVAE_LAUNCH_CHECK("sumsq_partial");
   hipLaunchKernelGGL(sumsq_final_kernel, dim3(1), dim3(256), 0, s, static_cast<const float*>(workspace), g, out);
   LVAE_LAUNCH_CHECK("sumsq_final");
+  return 0;
+}
+
+extern "C" int lvae_grad_guard_f32(const float* g, int64_t n, const float* gscale_in, float max_norm, float skip_threshold,
+                                   lvae_grad_guard_state* state, void* workspace, size_t workspace_bytes, void* stream) {
+  LVAE_REQUIRE(g && state && workspace && n > 0, LVAE_EINVAL, "lvae_grad_guard_f32: bad args");
+  LVAE_REQUIRE(workspace_bytes >= lvae_sumsq_workspace(n), LVAE_EWORKSPACE, "lvae_grad_guard_f32: workspace");
+  LVAE_REQUIRE((reinterpret_cast<uintptr_t>(state) & 7) == 0, LVAE_EALIGN, "lvae_grad_guard_f32: misaligned state");
+  const int blocks = grid_for(n, 256 * 8);   // lvae_l2norm_f32's grid: the same partial sums
+  hipStream_t s = (hipStream_t)stream;
+  hipLaunchKernelGGL(sumsq_partial_kernel, dim3(blocks), dim3(256), 0, s, g, n, static_cast<float*>(workspace));
+  LVAE_LAUNCH_CHECK("sumsq_partial");
+  hipLaunchKernelGGL(grad_guard_final_kernel, dim3(1), dim3(256), 0, s, static_cast<const float*>(workspace), blocks, gscale_in, max_norm,
+                     skip_threshold, state);
+  LVAE_LAUNCH_CHECK("grad_guard_final");
+  return 0;
+}
+
+extern "C" int lvae_multi_copy_f32(const lvae_copy_entry* table, int32_t n_entries, const int32_t* flag, int32_t want, void* stream) {
+  LVAE_REQUIRE(table && n_entries > 0, LVAE_EINVAL, "lvae_multi_copy_f32: bad args");
+  LVAE_REQUIRE((reinterpret_cast<uintptr_t>(table) & 7) == 0, LVAE_EALIGN, "lvae_multi_copy_f32: misaligned table");
+  hipLaunchKernelGGL(multi_copy_kernel, dim3(n_entries), dim3(256), 0, (hipStream_t)stream, table, flag, want);
+  LVAE_LAUNCH_CHECK("multi_copy");
   return 0;
 }
 
@@ -614,6 +710,13 @@ extern "C" int lvae_counter_advance(uint64_t* counter, uint64_t by, void* stream
   LVAE_REQUIRE(counter != nullptr, LVAE_EINVAL, "lvae_counter_advance: null counter");
   hipLaunchKernelGGL(counter_advance_kernel, dim3(1), dim3(64), 0, (hipStream_t)stream, counter, by);
   LVAE_LAUNCH_CHECK("counter_advance");
+  return 0;
+}
+
+extern "C" int lvae_counter_advance_unless(uint64_t* counter, uint64_t by, const int32_t* flag, void* stream) {
+  LVAE_REQUIRE(counter != nullptr && flag != nullptr, LVAE_EINVAL, "lvae_counter_advance_unless: null counter or flag");
+  hipLaunchKernelGGL(counter_advance_unless_kernel, dim3(1), dim3(64), 0, (hipStream_t)stream, counter, by, flag);
+  LVAE_LAUNCH_CHECK("counter_advance_unless");
   return 0;
 }
 

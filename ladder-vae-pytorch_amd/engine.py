@@ -10,6 +10,10 @@ With a `feed` (data.DeviceDataset) the step also forms its own batch: a gather f
 and the advance of the feed's cursor its last, so the replayed graph takes nothing from the host but an index table once per epoch.
 With a `summary` (summary.TrainSummary) the step also folds its own metrics and the norm of the final gradient into the log window's
 device accumulator, immediately before Adamax: two more launches, captured with the rest.
+With a guard on the optimizer (optim.GradGuard) the step saves the BatchNorm running statistics before the forward pass, and immediately
+before Adamax takes the gradient's norm, decides whether the step is clipped or skipped and, if skipped, puts the statistics back; the
+summary then reads the guard's norm instead of taking it again. A skipped step still counts as a step of the run: the global step, the beta
+warm-up, the data cursor, the noise stream and num_batches_tracked advance; the model and the optimizer keep their bits.
 """
 import os
 import sys
@@ -126,6 +130,9 @@ class TrainStep:
                 self.overlap, self.fallback_reason = False, why
         if self.overlap:
             model.grad_tracker = allreduce   # the model's segment markers report to it during backward
+        if getattr(optimizer, 'guard', None) is not None:
+            optimizer._state()
+            optimizer.guard.attach(model)    # state, shadow and copy tables exist before anything is captured
         if feed is not None:
             feed.attach(model)               # cursor = model.global_step: a resumed run continues in the middle of its epoch
             self.static_x = feed.new_batch()
@@ -135,6 +142,8 @@ class TrainStep:
         try:
             if self.feed is not None:
                 x = self.feed.gather(self.static_x)   # first launch of a fed step
+            if getattr(self.opt, 'guard', None) is not None:
+                self.opt.guard.save_bn(self.model)    # a skipped step puts them back (_fold)
             self.opt.zero_grad()
             K.prepared.prepare_all()  # one launch: transformed weights of every Winograd convolution seen so far
             out = forward_pass(self.model, x, self.beta, beta_anneal=self.beta_anneal, iw_samples=self.iw_samples)
@@ -177,6 +186,14 @@ class TrainStep:
     def _fold(self, out):
         """The step's metrics and the norm of the gradient Adamax is about to apply (summed over ranks by now, scaled like Adamax scales it)
         into the log window. Called immediately before every `self.opt.step()`; captured with it."""
+        guard = getattr(self.opt, 'guard', None)
+        if guard is not None:
+            # the same place is the guard's: norm, decision, and the BatchNorm statistics of a skipped step back where they were
+            guard.check(self.model.arena.grads, self.opt.gscale)
+            guard.restore_bn()
+            if self.summary is not None:
+                self.summary.fold(out, guard.norm, self.opt.gscale)
+            return
         if self.summary is None:
             return
         grads = self.model.arena.grads
@@ -299,7 +316,8 @@ class AutoExchangeStep:
     'overlap' (completion-ordered 8 MB buckets on the side stream during backward, one graph) — on one shared communicator, runs
     `trial_steps` timed steps of each after its warm-up / capture steps (all of them REAL training steps: both forms compute the same
     update), reduces the times with MAX over ranks (dist.FormSelector) and continues with the faster form; the other form's graph is dropped.
-    LVAE_DDP_MODE=split|overlap skips the trial. `timings_ms` / `chosen` go into bench.py's line (config.grad_exchange_ab)."""
+    LVAE_DDP_MODE=split|overlap skips the trial. `timings_ms` / `chosen` go into bench.py's line (config.grad_exchange_ab).
+    A gradient guard is the optimizer's (`optimizer.guard`), so both forms run under the same one: one shadow, one pair of counters."""
 
     def __init__(self, model, optimizer, flat_grads, segments, group=None, trial_steps=3, forms=None, feed=None, summary=None,
                  **step_kwargs):

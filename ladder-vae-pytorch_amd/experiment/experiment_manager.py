@@ -17,7 +17,7 @@ import torch
 from .. import engine
 from ..models.lvae import LadderVAE
 from ..noise import PhiloxNoise
-from ..optim import Adamax, LrSchedule
+from ..optim import Adamax, GradGuard, LrSchedule
 
 DATASETS = {
     # name: (color_ch, (H, W), default likelihood)  — experiment/data.py:32-97, experiment_manager.py:279-288
@@ -116,6 +116,12 @@ def build_parser():
                    help='train on the K-sample importance-weighted bound instead of the ELBO: K samples per image share one bottom-up pass '
                         '(--batch-size stays images per step); the train line adds the bound and the effective sample size of the weights. '
                         'Not with --freebits or --analytical-kl. 1: the ELBO')
+    p.add_argument('--max-grad-norm', type=float, default=None, dest='max_grad_norm', metavar='G',
+                   help='clip the gradient to the global L2 norm G before the optimizer step (the factor of torch.nn.utils.clip_grad_norm_), '
+                        'decided on the device inside the captured step; steps with a non-finite gradient are then skipped. Off by default')
+    p.add_argument('--grad-skip-threshold', type=float, default=None, dest='grad_skip_threshold', metavar='T',
+                   help='skip every step whose gradient norm exceeds T or is not finite: weights, optimizer state, average and BatchNorm '
+                        'statistics stay as they were, the run moves on to the next batch. inf: skip non-finite steps only. Off by default')
     p.add_argument('--latent-kl-threshold', type=float, default=0.01, dest='latent_kl_threshold', metavar='T')
     p.add_argument('--latent-var-threshold', type=float, default=0.01, dest='latent_var_threshold', metavar='T')
     return p
@@ -163,6 +169,11 @@ class LVAEExperiment:
         if iw > 1 and args.analytical_kl:
             raise SystemExit("--iw-train-samples %d cannot be combined with --analytical-kl: the importance weights need the Monte-Carlo "
                              "log q - log p of the drawn sample" % iw)
+        g, t = getattr(args, 'max_grad_norm', None), getattr(args, 'grad_skip_threshold', None)
+        if g is not None and not (g > 0.0 and g != float('inf')):
+            raise SystemExit("--max-grad-norm must be a positive finite number, got %g" % g)
+        if t is not None and not t >= 0.0:
+            raise SystemExit("--grad-skip-threshold must not be negative, got %g" % t)
         assert args.weight_decay >= 0.0
         assert 0.0 <= args.dropout <= 1.0
         if args.dropout < 1e-5:
@@ -197,6 +208,10 @@ class LVAEExperiment:
             s += ',learnp'
         if args.weight_decay > 0.0:
             s += ',wd={}'.format(args.weight_decay)
+        if getattr(args, 'max_grad_norm', None) is not None:
+            s += ',clip{:g}'.format(args.max_grad_norm)
+        if getattr(args, 'grad_skip_threshold', None) is not None:
+            s += ',skip{:g}'.format(args.grad_skip_threshold)
         s += ',seed{}'.format(args.seed)
         if len(args.additional_descr) > 0:
             s += ',' + args.additional_descr
@@ -226,9 +241,15 @@ class LVAEExperiment:
         except ValueError as e:
             raise SystemExit(str(e))
 
+    @staticmethod
+    def _make_guard(args):
+        """The GradGuard of --max-grad-norm / --grad-skip-threshold; None (the plain step) without either."""
+        g, t = getattr(args, 'max_grad_norm', None), getattr(args, 'grad_skip_threshold', None)
+        return None if g is None and t is None else GradGuard(max_norm=g, skip_threshold=t)
+
     def _make_optimizer(self):
         return Adamax(self.model, lr=self.args.lr, weight_decay=self.args.weight_decay, ema_decay=getattr(self.args, 'ema_decay', 0.0),
-                      schedule=self._make_schedule(self.args))
+                      schedule=self._make_schedule(self.args), guard=self._make_guard(self.args))
 
     def beta(self):
         if self.args.beta_anneal != 0:

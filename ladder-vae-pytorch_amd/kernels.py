@@ -1341,6 +1341,48 @@ def adamax_sched_step(p, g, exp_avg, exp_inf, mask, schedule, beta1, beta2, eps,
     prepared.weights_written()
 
 
+def grad_guard(g, gscale, max_norm, skip_threshold, state):
+    """The gradient guard's decision for the arena `g` into `state` (device int64[4] laid out as struct lvae_grad_guard_state: norm, scale,
+    skip flag, cumulative clipped / skipped counts). max_norm <= 0: no clipping; skip_threshold < 0: only non-finite steps are skipped.
+    Two launches (the partial sums of l2norm, then the decision)."""
+    if state.dtype != torch.int64 or state.numel() * 8 != C.sizeof(_C.GradGuardState) or not state.is_contiguous():
+        raise _C.LvaeHipError("grad_guard: the state is a contiguous device int64[%d]" % (C.sizeof(_C.GradGuardState) // 8))
+    ws = workspace(_C.load().lvae_sumsq_workspace(g.numel()), g.device)
+    call('lvae_grad_guard_f32', ptr(g, (torch.float32,)), g.numel(), ptr(gscale, (torch.float32,)), float(max_norm), float(skip_threshold),
+         ptr(state, (torch.int64,)), ws.data_ptr(), ws.numel(), stream_ptr())
+
+
+def adamax_guarded_step(p, g, exp_avg, exp_inf, mask, lr, schedule, beta1, beta2, eps, weight_decay, step_count, ema, decay, lr_out, state):
+    """The Adamax step of a guarded training step: nothing at all when state's skip flag is set, else adamax_step / adamax_ema_step /
+    adamax_sched_step (`schedule` None or a struct, `ema` None or a buffer) with the guard's scale in the place of gscale."""
+    if ema is not None and ema.numel() != p.numel():
+        raise _C.LvaeHipError("ema has %d elements, the parameters %d" % (ema.numel(), p.numel()))
+    call('lvae_adamax_guarded_step_f32', ptr(p), ptr(g), ptr(exp_avg), ptr(exp_inf), ptr(mask), p.numel(), float(lr),
+         None if schedule is None else C.byref(schedule), beta1, beta2, eps, weight_decay, step_count.data_ptr(), ptr(ema), float(decay),
+         ptr(lr_out, (torch.float32,)), ptr(state, (torch.int64,)), stream_ptr())
+    prepared.weights_written()
+
+
+def copy_table(pairs, device):
+    """[(dst, src)] pairs of contiguous fp32 device tensors of equal length -> the device table multi_copy takes (int64 [len][3]: struct
+    lvae_copy_entry). The caller keeps the tensors alive and in place for as long as the table is used."""
+    rows = []
+    for dst, src in pairs:
+        if dst.numel() != src.numel() or not (dst.is_contiguous() and src.is_contiguous()):
+            raise _C.LvaeHipError("copy_table: an entry needs two contiguous buffers of one length")
+        rows.append([ptr(dst, (torch.float32,)), ptr(src, (torch.float32,)), dst.numel()])
+    if not rows:
+        raise _C.LvaeHipError("copy_table: no entries")
+    return torch.tensor(rows, dtype=torch.int64).to(device)
+
+
+def multi_copy(table, flag=None, want=0):
+    """Every entry of a copy_table in one launch (one workgroup per entry); with `flag` (device int32[1]) only when flag[0] == want."""
+    if table.dtype != torch.int64 or table.dim() != 2 or table.shape[1] != 3 or not table.is_contiguous():
+        raise _C.LvaeHipError("multi_copy: the table is a contiguous device int64 [entries][3]")
+    call('lvae_multi_copy_f32', ptr(table, (torch.int64,)), table.shape[0], ptr(flag, (torch.int32,)), int(want), stream_ptr())
+
+
 def swap(a, b):
     """a <-> b in place, one pass (two contiguous fp32 buffers of one length). The caller says when weights moved (weights_written)."""
     if a.numel() != b.numel() or not (a.is_contiguous() and b.is_contiguous()):
@@ -1367,6 +1409,11 @@ def rng_fill(out, kind, lo, hi, seed, offset, stream_id):
 
 def counter_advance(counter, by=1):
     call('lvae_counter_advance', counter.data_ptr(), int(by), stream_ptr())
+
+
+def counter_advance_unless(counter, by, flag):
+    """counter += by unless flag[0] != 0 (device int32[1]: the gradient guard's skip flag)."""
+    call('lvae_counter_advance_unless', counter.data_ptr(), int(by), ptr(flag, (torch.int32,)), stream_ptr())
 
 
 def batch_gather(table, channels_last, out, index=None, cursor=None, steps_per_epoch=0, global_batch=0, lo=0, base=0):

@@ -72,6 +72,25 @@ def lr_suffix(m):
     return '   lr: {:.3g}'.format(m['lr/lr']) if 'lr/lr' in m else ''
 
 
+def guard_suffix(m):
+    """What a gradient guard appends to a train line: the norm of the gradient of the step the line falls due at (with --window-summaries
+    the window's mean is already there) and the steps clipped / skipped since the previous train line."""
+    if 'grad/clipped' not in m:
+        return ''
+    s = '   grad: {:.3g}'.format(m['grad/norm']) if 'grad/norm' in m else ''
+    return s + '   clipped: {}   skipped: {}'.format(m['grad/clipped'], m['grad/skipped'])
+
+
+def guard_metrics(guard, gscale, seen, m, with_norm):
+    """Adds the guard's numbers to the metrics of a train line (one device-to-host read each); -> the cumulative counts, for the next line."""
+    now = guard.counts()
+    m['grad/clipped'], m['grad/skipped'] = now[0] - seen[0], now[1] - seen[1]
+    if with_norm:
+        # (the product in fp32, as the summary's grad slot and the guard's decision form it)
+        m['grad/norm'] = float(np.float32(guard.norm.item()) * np.float32(1.0 if gscale is None else gscale.item()))
+    return now
+
+
 def iw_suffix(m, k):
     """What --iw-train-samples K > 1 appends to a train line: the K-sample bound (at beta = 1) and the effective sample size of the weights,
     of the step the line falls due at."""
@@ -104,6 +123,11 @@ def main(argv=None):
         was = ck.get('lr_schedule') if isinstance(ck, dict) and 'model' in ck else None
         if rank == 0 and was != lr_schedule_record(opt):
             print('warning: %s was written with the lr schedule %s; continuing with %s' % (args.resume, was, lr_schedule_record(opt)))
+        was_guard = ck.get('grad_guard') if isinstance(ck, dict) and 'model' in ck else None
+        if rank == 0 and opt.guard is not None and was_guard is not None and \
+                {k: was_guard.get(k) for k in ('max_norm', 'skip_threshold')} != opt.guard.limits():
+            print('warning: %s was written with the gradient limits %s; continuing with %s'
+                  % (args.resume, {k: was_guard.get(k) for k in ('max_norm', 'skip_threshold')}, opt.guard.limits()))
         was_iw = ck.get('iw_train_samples', 1) if isinstance(ck, dict) and 'model' in ck else 1
         if rank == 0 and was_iw != args.iw_train_samples:
             print('warning: %s was written with --iw-train-samples %d; continuing with %d' % (args.resume, was_iw, args.iw_train_samples))
@@ -138,6 +162,7 @@ def main(argv=None):
     step_fn = TrainStep(model, opt, beta=1.0, use_graph=not args.no_graph, allreduce=allreduce, beta_anneal=args.beta_anneal,
                         feed=feed, summary=summary, iw_samples=args.iw_train_samples)
     history = History(args.history) if args.history and rank == 0 else None
+    guard_seen = opt.guard.counts() if opt.guard is not None else None   # (after --resume: the file's counts)
     # --latent-stats: the first sample of every test batch also folds each layer's posterior into a device accumulator
     latent = LatentStats(model, exp.device, args.latent_kl_threshold, args.latent_var_threshold) if args.latent_stats and tests is not None else None
     if rank == 0:
@@ -193,8 +218,10 @@ def main(argv=None):
                     m['lr/lr'] = opt.current_lr()      # of this step, not a window mean: the accumulator's layout stays as it is
                 if 'iw' in out:                        # likewise of this step (and of rank 0)
                     m['elbo/iw_train'], m['iw/ess'] = out['iw'].item(), out['ess'].item()
+                if opt.guard is not None:              # every rank decides alike: rank 0's counts are the run's
+                    guard_seen = guard_metrics(opt.guard, opt.gscale, guard_seen, m, False)
                 print(exp.train_log_str(m, step) + train_line_suffix(m, summary.ranks) + lr_suffix(m) + '   [{:.0f} img/s]'.format(seen / dt)
-                      + iw_suffix(m, args.iw_train_samples))
+                      + iw_suffix(m, args.iw_train_samples) + guard_suffix(m))
                 if history is not None:
                     history.write(step, 'train', m, steps=m['steps'], nonfinite_steps=m['nonfinite_steps'])
             t0, seen = time.time(), 0
@@ -203,7 +230,10 @@ def main(argv=None):
             dt = time.time() - t0
             if opt.schedule is not None:
                 m['lr/lr'] = opt.current_lr()
-            print(exp.train_log_str(m, step) + lr_suffix(m) + '   [{:.0f} img/s]'.format(seen / dt) + iw_suffix(m, args.iw_train_samples))
+            if opt.guard is not None:
+                guard_seen = guard_metrics(opt.guard, opt.gscale, guard_seen, m, True)
+            print(exp.train_log_str(m, step) + lr_suffix(m) + '   [{:.0f} img/s]'.format(seen / dt) + iw_suffix(m, args.iw_train_samples)
+                  + guard_suffix(m))
             if history is not None:
                 history.write(step, 'train', m)
             t0, seen = time.time(), 0

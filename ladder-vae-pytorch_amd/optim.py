@@ -6,8 +6,13 @@ ELBO / importance-weighted bound is normally reported from; `swap_ema()` puts it
 
 With a `schedule` (LrSchedule) the kernel computes the learning rate itself from the device step counter, so a captured step replays along
 warm-up and decay; `lr_now` holds the rate of the last step.
+
+With a `guard` (GradGuard) the step is preceded by a look at the gradient's norm on the device: the gradient is clipped to `max_norm`, and a
+step whose norm is not finite or exceeds `skip_threshold` is left out as if it had not happened (parameters, exp_avg, exp_inf, the step
+counter, the average and lr_now keep their bits), all of it inside the captured step.
 """
 import contextlib
+import math
 
 import numpy as np
 import torch
@@ -64,8 +69,98 @@ class LrSchedule:
         return 'LrSchedule(%s)' % ', '.join('%s=%r' % kv for kv in self.state_dict().items())
 
 
+class GradGuard:
+    """Clip the gradient arena to the global norm `max_norm` (torch.nn.utils.clip_grad_norm_'s factor min(1, G / (norm + 1e-6))) and leave
+    out every step whose norm is not finite or exceeds `skip_threshold`; None switches either off (non-finite steps are always left out).
+    `norm` is the L2 norm of the arena after the gradient exchange times the optimizer's gscale, the number a train line prints as `grad:`.
+    Owns the device struct lvae_grad_guard_state (`state`: int64[4]; views `norm`, `scale`, `skip`; cumulative `clipped` / `skipped`
+    counters) and, once attached to a model, a shadow of every BatchNorm running statistic with the two copy tables that save and restore
+    them: the forward pass of a step that is then skipped has already moved them."""
+
+    def __init__(self, max_norm=None, skip_threshold=None):
+        if max_norm is not None:
+            max_norm = float(max_norm)
+            if not (max_norm > 0.0 and math.isfinite(max_norm)):
+                raise ValueError("max_norm must be a positive finite number (None: no clipping), got %r" % (max_norm,))
+        if skip_threshold is not None:
+            skip_threshold = float(skip_threshold)
+            if not skip_threshold >= 0.0:
+                raise ValueError("skip_threshold must not be negative or NaN (None or inf: skip non-finite steps only), got %r"
+                                 % (skip_threshold,))
+        self.max_norm, self.skip_threshold = max_norm, skip_threshold
+        self.state = None            # device int64[4]: struct lvae_grad_guard_state
+        self.norm = self.scale = self.skip = None
+        self.checked = False         # check() ran for the step Adamax.step() is about to apply
+        self._counts0 = (0, 0)       # counters to start from (load_state_dict before the state exists)
+        self._bn_key = self._shadow = self._save = self._restore = None
+
+    def limits(self):
+        return {'max_norm': self.max_norm, 'skip_threshold': self.skip_threshold}
+
+    def _alloc(self, device):
+        if self.state is None or self.state.device != device:
+            counts = self.counts() if self.state is not None else self._counts0
+            self.state = torch.tensor([0, 0, counts[0], counts[1]], dtype=torch.int64).to(device)
+            f, i = self.state.view(torch.float32), self.state.view(torch.int32)
+            self.norm, self.scale, self.skip = f[0:1], f[1:2], i[2:3]
+        return self.state
+
+    def check(self, grads, gscale=None):
+        """Takes the norm of `grads` and decides this step (two launches). Before Adamax.step(), which runs it itself if nobody has."""
+        self._alloc(grads.device)
+        K.grad_guard(grads, gscale, self.max_norm or 0.0, -1.0 if self.skip_threshold is None else self.skip_threshold, self.state)
+        self.checked = True
+
+    def attach(self, model):
+        """Builds the shadow of the model's BatchNorm running statistics and the save / restore tables (again if the buffers have moved)."""
+        self._alloc(next(model.parameters()).device)
+        bufs = [b for bn in model.bn_modules() for b in (bn.running_mean, bn.running_var)]
+        key = tuple(b.data_ptr() for b in bufs)
+        if key == self._bn_key:
+            return
+        self._bn_key, self._shadow, self._save, self._restore = key, None, None, None
+        if not bufs:
+            return
+        dev = bufs[0].device
+        self._shadow = torch.zeros(sum(b.numel() for b in bufs), dtype=torch.float32, device=dev)
+        parts = torch.split(self._shadow, [b.numel() for b in bufs])
+        self._save = K.copy_table(list(zip(parts, bufs)), dev)
+        self._restore = K.copy_table(list(zip(bufs, parts)), dev)
+
+    def save_bn(self, model):
+        """Head of a guarded step: every running_mean / running_var into the shadow (one launch)."""
+        self.attach(model)
+        if self._save is not None:
+            K.multi_copy(self._save)
+
+    def restore_bn(self):
+        """After check(): the shadow back into the running statistics if this step is skipped (one launch either way)."""
+        if self._restore is not None:
+            K.multi_copy(self._restore, self.skip, 1)
+
+    def counts(self):
+        """(clipped, skipped) steps so far: one device-to-host read."""
+        if self.state is None:
+            return self._counts0
+        c = self.state[2:4].tolist()
+        return int(c[0]), int(c[1])
+
+    def state_dict(self):
+        clipped, skipped = self.counts()
+        return dict(self.limits(), clipped=clipped, skipped=skipped)
+
+    def load_state_dict(self, sd):
+        """Continues the counters of `sd`. The limits stay this guard's own (a resumed run uses the limits it was started with)."""
+        self._counts0 = (int(sd['clipped']), int(sd['skipped']))
+        if self.state is not None:
+            self.state[2:4] = torch.tensor(self._counts0, dtype=torch.int64)
+
+    def __repr__(self):
+        return 'GradGuard(max_norm=%r, skip_threshold=%r)' % (self.max_norm, self.skip_threshold)
+
+
 class Adamax:
-    def __init__(self, model, lr=3e-4, betas=(0.9, 0.999), eps=1e-8, weight_decay=0.0, ema_decay=0.0, schedule=None):
+    def __init__(self, model, lr=3e-4, betas=(0.9, 0.999), eps=1e-8, weight_decay=0.0, ema_decay=0.0, schedule=None, guard=None):
         self.model = model
         self.lr, self.betas, self.eps, self.weight_decay = float(lr), (float(betas[0]), float(betas[1])), float(eps), float(weight_decay)
         self.ema_decay = float(ema_decay)
@@ -77,6 +172,7 @@ class Adamax:
         self.schedule = schedule   # LrSchedule or None: `lr` itself at every step
         self._sched = None if schedule is None else schedule.struct(self.lr)
         self.lr_now = None  # device float[1] with a schedule: the lr the last step applied
+        self.guard = guard  # GradGuard or None: clip / skip decided on the device before the update
         self._arena = None
         self._swapped = False
 
@@ -98,6 +194,8 @@ class Adamax:
         self._state().zero_grad()
 
     def step(self):
+        if self.guard is not None:
+            return self._guarded_step()
         if self.schedule is not None:
             return self._scheduled_step()
         arena = self._state()
@@ -119,6 +217,21 @@ class Adamax:
         K.adamax_sched_step(arena.params[:arena.n_train], arena.grads, self.exp_avg, self.exp_inf, None, self._sched, self.betas[0],
                             self.betas[1], self.eps, self.weight_decay, self.gscale, self.step_count, self.ema, self.ema_decay, self.lr_now)
         K.counter_advance(self.step_count, 1)
+
+    def _guarded_step(self):
+        """step() under the guard's decision for this gradient (engine.TrainStep has taken it by now; taken here otherwise): with or without
+        the average, with or without a schedule. A skipped step leaves the step counter where it is."""
+        arena = self._state()
+        if self._swapped:
+            raise RuntimeError("Adamax.step() inside swap_ema(): the parameters hold the average")
+        guard = self.guard
+        if not guard.checked:
+            guard.check(arena.grads, self.gscale)
+        guard.checked = False
+        K.adamax_guarded_step(arena.params[:arena.n_train], arena.grads, self.exp_avg, self.exp_inf, None, self.lr, self._sched,
+                              self.betas[0], self.betas[1], self.eps, self.weight_decay, self.step_count, self.ema, self.ema_decay,
+                              self.lr_now, guard.state)
+        K.counter_advance_unless(self.step_count, 1, guard.skip)
 
     @contextlib.contextmanager
     def swap_ema(self):
