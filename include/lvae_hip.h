@@ -515,6 +515,52 @@ int lvae_normal_stochastic_bwd_f32(const float* p, int32_t p_bcast, const float*
                                    const float* g_ks, int32_t N, int32_t HW, int32_t Z, int32_t mode,
                                    int32_t analytical_kl, float* dp, float* dq, void* stream);
 
+/* The whole block of the low-resolution levels in one launch (csrc/stoch_img.hip), forward: p_params = conv_in_p(x_p),
+ * q_params = conv_in_q(x_q), the elementwise core above, out = conv_out(z). Every tensor the one-kernel-per-op form writes is written:
+ *   conv_p   : x = x_p [N,H,W,64], y = p_params [N,H,W,2Z], w / bias of conv_in_p. conv_p.w == NULL: the block has no conv_in_p (top layer);
+ *              p_params is then `p_given` ([N,H,W,2Z], or [1,H,W,2Z] with p_bcast = 1) and is only read
+ *   conv_q   : x = x_q [N,H,W,64], y = q_params [N,H,W,2Z]
+ *   conv_out : x = z [N,H,W,Z] (WRITTEN by this launch), y = out [N,H,W,64]
+ * each a forward descriptor as lvae_conv2d_f32 takes it (LVAE_GATHER_CONV, 3x3, stride 1, pad 1, no input / output transform, no
+ * statistics), with workspace = lvae_stoch_block_workspace(d) bytes of pre-split weights private to the weight view: filled by the launch
+ * itself unless workspace_ready, or by lvae_conv2d_prepare_weights from a table entry written by lvae_stoch_block_prepare_entry.
+ * eps, mode, analytical_kl and the four reductions as lvae_normal_stochastic_fwd_f32 (kl_spatial may be NULL; sums in a fixed order).
+ * Arithmetic: six exact bf16-piece products per fp32 product (as LVAE_FORM_SIX_PRODUCT) whatever `precision` says.
+ * lvae_stoch_block_ok(b) == 1 exactly when the launch takes b: 3x3 / stride 1 / pad 1, 64 input channels, Z = 32, H*W a divisor of 64 (and
+ * the tile's patch within the LDS), fp32 tensors, 16-byte aligned operands and weight views, q present, mode 0..2. Otherwise compose lvae_conv2d_f32 and the core.
+ * replaces: lib/stochastic.py:45-99 between the two residual chains of a top-down layer. */
+typedef struct lvae_stoch_block {
+  lvae_conv_desc conv_p, conv_q, conv_out;
+  const float* p_given;
+  int32_t p_bcast;
+  int32_t mode, analytical_kl;
+  const float* eps;
+  float *logprob_p, *logprob_q, *kl_samplewise, *kl_spatial;
+} lvae_stoch_block;
+int32_t lvae_stoch_block_ok(const lvae_stoch_block* b);
+size_t lvae_stoch_block_workspace(const lvae_conv_desc* d);
+int lvae_stoch_block_prepare_entry(const lvae_conv_desc* d, void* entry);
+int lvae_stoch_block_fwd_f32(const lvae_stoch_block* b, void* stream);
+/* Its backward from d_out in one launch: dz = dgrad(conv_out)(d_out) (+ dz, the upstream gradient of z itself, or NULL) never reaches memory;
+ * dp, dq by the formulas of lvae_normal_stochastic_bwd_f32 with its g_lp / g_lq / g_kl / g_ks (each may be NULL); then the two input gradients.
+ *   dgrad_out : x = d_out [N,H,W,64]; y unused
+ *   dgrad_q   : x = dq [N,H,W,2Z] (WRITTEN by this launch: the weight gradients read it), y = d x_q [N,H,W,64]
+ *   dgrad_p   : x = dp [N,H,W,2Z] (WRITTEN), y = d x_p [N,H,W,64]. dgrad_p.w == NULL: no conv_in_p; only dp is written (the caller sums it
+ *               over the batch where p was broadcast)
+ * each a dgrad descriptor as lvae_conv2d_f32 takes it (LVAE_GATHER_TRANSPOSED, C1 = the convolution's output channels, Cout = its input
+ * channels, w_sk / w_sn swapped), with workspace / workspace_ready as in the forward (lvae_stoch_block_workspace / _prepare_entry; private to
+ * the weight view AND the direction). p (p_bcast), q, z, eps, mode, analytical_kl: what the forward used and wrote.
+ * lvae_stoch_block_bwd_ok(b) == 1 exactly when the launch takes b (the forward's conditions). */
+typedef struct lvae_stoch_block_bwd {
+  lvae_conv_desc dgrad_out, dgrad_q, dgrad_p;
+  const float* p;
+  int32_t p_bcast;
+  int32_t mode, analytical_kl;
+  const float *q, *z, *eps, *dz, *g_lp, *g_lq, *g_kl, *g_ks;
+} lvae_stoch_block_bwd;
+int32_t lvae_stoch_block_bwd_ok(const lvae_stoch_block_bwd* b);
+int lvae_stoch_block_bwd_f32(const lvae_stoch_block_bwd* b, void* stream);
+
 /* Tempered draw from the prior (sampling only; no backward): for row n, t_n = row_temperature ? row_temperature[n] : temperature,
  * z = mu + (t_n * exp(lv/2)) * eps, and z = mu exactly where t_n == 0 (a branch: eps is not read, an infinite sigma gives no NaN).
  * logprob_p[n] = sum over the row of log N(z; mu, exp(lv)) under the UNTEMPERED prior, in a fixed order (deterministic).

@@ -69,6 +69,20 @@ class RbExt(C.Structure):
                 ('ap_out', C.c_void_p)]
 
 
+class StochBlock(C.Structure):
+    """mirror of struct lvae_stoch_block"""
+    _fields_ = [('conv_p', ConvDesc), ('conv_q', ConvDesc), ('conv_out', ConvDesc), ('p_given', C.c_void_p), ('p_bcast', C.c_int32),
+                ('mode', C.c_int32), ('analytical_kl', C.c_int32), ('eps', C.c_void_p), ('logprob_p', C.c_void_p), ('logprob_q', C.c_void_p),
+                ('kl_samplewise', C.c_void_p), ('kl_spatial', C.c_void_p)]
+
+
+class StochBlockBwd(C.Structure):
+    """mirror of struct lvae_stoch_block_bwd"""
+    _fields_ = [('dgrad_out', ConvDesc), ('dgrad_q', ConvDesc), ('dgrad_p', ConvDesc), ('p', C.c_void_p), ('p_bcast', C.c_int32),
+                ('mode', C.c_int32), ('analytical_kl', C.c_int32), ('q', C.c_void_p), ('z', C.c_void_p), ('eps', C.c_void_p), ('dz', C.c_void_p),
+                ('g_lp', C.c_void_p), ('g_lq', C.c_void_p), ('g_kl', C.c_void_p), ('g_ks', C.c_void_p)]
+
+
 class LrScheduleStruct(C.Structure):
     """mirror of struct lvae_lr_schedule"""
     _fields_ = [('base_lr', C.c_float), ('min_lr', C.c_float), ('gamma', C.c_float), ('kind', C.c_int32),
@@ -154,6 +168,12 @@ SIGNATURES = {
     'lvae_colsum_f32': (C.c_int, [_P, _L, _L, _P, _I, _P]),
     'lvae_normal_stochastic_fwd_f32': (C.c_int, [_P, _I, _P, _P, _I, _I, _I, _I, _I, _P, _P, _P, _P, _P, _P]),
     'lvae_normal_stochastic_bwd_f32': (C.c_int, [_P, _I, _P, _P, _P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _P, _P, _P]),
+    'lvae_stoch_block_ok': (_I, [C.POINTER(StochBlock)]),
+    'lvae_stoch_block_workspace': (_Z, [C.POINTER(ConvDesc)]),
+    'lvae_stoch_block_prepare_entry': (C.c_int, [C.POINTER(ConvDesc), _P]),
+    'lvae_stoch_block_fwd_f32': (C.c_int, [C.POINTER(StochBlock), _P]),
+    'lvae_stoch_block_bwd_ok': (_I, [C.POINTER(StochBlockBwd)]),
+    'lvae_stoch_block_bwd_f32': (C.c_int, [C.POINTER(StochBlockBwd), _P]),
     'lvae_normal_prior_sample_f32': (C.c_int, [_P, _I, _P, _F, _P, _I, _I, _I, _P, _P, _P]),
     'lvae_kl_elementwise_fwd_f32': (C.c_int, [_P, _I, _P, _I, _P, _I, _I, _I, _I, _P, _P]),
     'lvae_kl_elementwise_bwd_f32': (C.c_int, [_P, _I, _P, _I, _P, _P, _I, _I, _I, _I, _P, _P, _P, _P]),

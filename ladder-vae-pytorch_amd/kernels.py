@@ -934,6 +934,121 @@ def normal_stochastic_fwd(p, q, eps_or_z, mode, analytical_kl, Z, N, rows=None):
     return z, small[0], small[1], small[2], ks
 
 
+# Fused stochastic block of the low-resolution levels (csrc/stoch_img.hip, lvae_stoch_block_fwd_f32)
+def _stoch_block_desc(x_p, cv_p, p_given, x_q, cv_q, cv_out, eps_or_z, mode, analytical_kl, N, attach=True):
+    """The lvae_stoch_block of one call, without output tensors; None where Python alone can tell that the fused launch does not apply.
+    cv_*: (weight, ConvGeom, bias) of conv_in_p (None: the block has none and p_given is p_params), conv_in_q, conv_out. attach: register the
+    three weights' pre-split planes (a query must not register weights the caller may never run through this kernel)."""
+    if _ddi is not None or x_q is None or x_q.dim() != 4 or x_q.dtype != torch.float32 or not x_q.is_contiguous():
+        return None
+    _, H, W, _ = x_q.shape
+    b = _C.StochBlock()
+    keep = []
+    for name, cv, x, cin in (('conv_p', cv_p, x_p, None), ('conv_q', cv_q, x_q, None), ('conv_out', cv_out, None, cv_out[1].Cin)):
+        if cv is None:
+            continue
+        w, g, bias = cv
+        if g.transposed or (x is not None and (x.dim() != 4 or x.dtype != torch.float32 or not x.is_contiguous() or tuple(x.shape[:3]) != (N, H, W))):
+            return None
+        d = ConvDesc()
+        d.x = ptr(x)
+        d.C1 = x.shape[3] if x is not None else cin
+        d.w, d.w_stap, d.w_sk, d.w_sn, d.bias = ptr(w), g.s_tap, g.s_ci, g.s_co, ptr(bias)
+        d.N, d.H, d.W, d.OH, d.OW, d.Cout = N, H, W, H, W, g.Cout
+        d.KH, d.KW, d.stride, d.pad, d.gather, d.precision = g.KH, g.KW, g.stride, g.pad, GATHER_CONV, precision
+        if d.C1 != g.Cin:
+            return None
+        if attach:
+            need = _C.load().lvae_stoch_block_workspace(C.byref(d))
+            if not need:
+                return None
+            prepared.attach(d, w, x_q.device, need, 'lvae_stoch_block_prepare_entry')
+            keep.append(d._ws_tensor)
+        setattr(b, name, d)
+    if cv_p is None:
+        if p_given is None or p_given.dim() != 4 or p_given.dtype != torch.float32 or not p_given.is_contiguous() or tuple(p_given.shape[1:3]) != (H, W):
+            return None
+        b.p_given, b.p_bcast = ptr(p_given), int(p_given.shape[0] == 1 and N > 1)
+        if p_given.shape[0] not in (1, N) or p_given.shape[3] != cv_q[1].Cout:
+            return None
+    b.mode, b.analytical_kl, b.eps = mode, int(bool(analytical_kl)), ptr(eps_or_z)
+    b._keep = keep
+    return b
+
+
+def stoch_block_ok(x_p, cv_p, p_given, x_q, cv_q, cv_out, mode, N):
+    """True when stoch_block_fwd takes this call (lvae_stoch_block_ok): 3x3 / stride 1 / pad 1 convolutions, 64 input channels, Z = 32, H*W a
+    divisor of 64, fp32 NHWC tensors, 16-byte aligned operands and weight views, q present, mode 0..2."""
+    b = _stoch_block_desc(x_p, cv_p, p_given, x_q, cv_q, cv_out, None, mode, False, N, attach=False)
+    return b is not None and bool(_C.load().lvae_stoch_block_ok(C.byref(b)))
+
+
+def stoch_block_fwd(x_p, cv_p, p_given, x_q, cv_q, cv_out, eps_or_z, mode, analytical_kl, N, rows=None):
+    """The stochastic block of a low-resolution level in one launch: p_params = conv_in_p(x_p) (or p_given), q_params = conv_in_q(x_q), the
+    core of normal_stochastic_fwd, out = conv_out(z). Returns (out, z, p_params, q_params, logprob_p, logprob_q, kl_samplewise, kl_spatial);
+    rows as in normal_stochastic_fwd. Only where stoch_block_ok()."""
+    b = _stoch_block_desc(x_p, cv_p, p_given, x_q, cv_q, cv_out, eps_or_z, mode, analytical_kl, N)
+    if b is None:
+        raise _C.LvaeHipError("stoch_block_fwd: not a call of the fused stochastic block (ask stoch_block_ok first)")
+    _, H, W, _ = x_q.shape
+    dev, Z = x_q.device, cv_out[1].Cin
+    q_params = torch.empty((N, H, W, cv_q[1].Cout), dtype=torch.float32, device=dev)
+    p_params = torch.empty_like(q_params) if cv_p is not None else p_given
+    z = torch.empty((N, H, W, Z), dtype=torch.float32, device=dev)
+    out = torch.empty((N, H, W, cv_out[1].Cout), dtype=torch.float32, device=dev)
+    small = torch.empty((3, N), dtype=torch.float32, device=dev)
+    if rows is not None:
+        small = [rows[0], small[1], rows[1]]
+    ks = torch.empty((N, H, W), dtype=torch.float32, device=dev)
+    if cv_p is not None:
+        b.conv_p.y = ptr(p_params)
+    b.conv_q.y, b.conv_out.x, b.conv_out.y = ptr(q_params), ptr(z), ptr(out)
+    b.logprob_p, b.logprob_q, b.kl_samplewise, b.kl_spatial = ptr(small[0]), ptr(small[1]), ptr(small[2]), ptr(ks)
+    call('lvae_stoch_block_fwd_f32', C.byref(b), stream_ptr())
+    return out, z, p_params, q_params, small[0], small[1], small[2], ks
+
+
+def stoch_block_bwd(d_out, cv_p, cv_q, cv_out, p, q, z, eps, dz, g_lp, g_lq, g_kl, g_ks, mode, analytical_kl):
+    """Backward of stoch_block_fwd from d_out in one launch (lvae_stoch_block_bwd_f32): dgrad of conv_out, the core's backward, the dgrads of
+    conv_in_q and conv_in_p (cv_p None: the block has none). p, q, z, eps: what the forward used and wrote; dz, g_*: upstream gradients, each
+    may be None. Returns (dp, dq, d x_p | None, d x_q), or None where the launch does not take the call (the caller composes it)."""
+    if _ddi is not None or any(t is None or t.dtype != torch.float32 or not t.is_contiguous() for t in (d_out, p, q, z)):
+        return None
+    N, H, W, _ = z.shape
+    dev = z.device
+    b = _C.StochBlockBwd()
+    keep = []
+    dq = torch.empty_like(q)
+    dp = torch.empty_like(q)
+    dxq = torch.empty((N, H, W, cv_q[1].Cin), dtype=torch.float32, device=dev)
+    dxp = torch.empty((N, H, W, cv_p[1].Cin), dtype=torch.float32, device=dev) if cv_p is not None else None
+    for name, cv, x, y in (('dgrad_out', cv_out, d_out, None), ('dgrad_q', cv_q, dq, dxq), ('dgrad_p', cv_p, dp, dxp)):
+        d = ConvDesc()
+        d.x, d.y = ptr(x), ptr(y)
+        if cv is not None:
+            w, g, _ = cv
+            if g.transposed or tuple(x.shape) != (N, H, W, g.Cout):
+                return None
+            d.C1, d.Cout = g.Cout, g.Cin
+            d.w, d.w_stap, d.w_sk, d.w_sn = ptr(w), g.s_tap, g.s_co, g.s_ci
+            d.N, d.H, d.W, d.OH, d.OW = N, H, W, H, W
+            d.KH, d.KW, d.stride, d.pad, d.gather, d.precision = g.KH, g.KW, g.stride, g.pad, GATHER_TRANSPOSED, precision
+            need = _C.load().lvae_stoch_block_workspace(C.byref(d))
+            if not need:
+                return None
+            prepared.attach(d, w, dev, need, 'lvae_stoch_block_prepare_entry')
+            keep.append(d._ws_tensor)
+        setattr(b, name, d)
+    b.p, b.p_bcast, b.q, b.z, b.eps, b.dz = ptr(p), int(p.shape[0] == 1 and N > 1), ptr(q), ptr(z), ptr(eps), ptr(dz)
+    b.g_lp, b.g_lq, b.g_kl, b.g_ks = ptr(g_lp), ptr(g_lq), ptr(g_kl), ptr(g_ks)
+    b.mode, b.analytical_kl = mode, int(bool(analytical_kl))
+    if not _C.load().lvae_stoch_block_bwd_ok(C.byref(b)):
+        return None
+    call('lvae_stoch_block_bwd_f32', C.byref(b), stream_ptr())
+    del keep
+    return dp, dq, dxp, dxq
+
+
 def normal_prior_sample(p, eps, Z, N, temperature, row_temperature=None, rows=None):
     """Tempered draw from the prior p (N|1,H,W,2Z): z = mu + (t * sigma) * eps, z = mu exactly where t == 0; log p(z) under the untempered
     prior. temperature: the scalar t; row_temperature: a device float tensor (N,) that replaces it row by row. eps (N,H,W,Z) may be None

@@ -7,6 +7,7 @@ from torch import nn
 
 from .. import kernels as K
 from .. import ops
+from .. import resblock as RB
 from .nn import Conv2dParams
 
 
@@ -36,10 +37,14 @@ class NormalStochasticBlock2d(nn.Module):
         tempered = temperature is not None and (torch.is_tensor(temperature) or float(temperature) != 1.0)
         if tempered and (q_params is not None or forced_latent is not None or use_mode):
             raise ValueError("temperature applies to a draw from the prior: it cannot be combined with q_params, forced_latent or use_mode")
+        if not self.transform_p_params:
+            assert p_params.size(3) == 2 * self.c_vars
+        if q_params is not None and not tempered and not need_kl_elementwise and not force_constant_output and RB.switches.stoch_block:
+            fused = self._fused(p_params, q_params, forced_latent, use_mode, analytical_kl, noise, n_img, rows, stats)
+            if fused is not None:
+                return fused
         if self.transform_p_params:
             p_params = self.conv_in_p(p_params)
-        else:
-            assert p_params.size(3) == 2 * self.c_vars
         if q_params is not None:
             q_params = self.conv_in_q(q_params)
         ref = q_params if q_params is not None else p_params
@@ -76,6 +81,29 @@ class NormalStochasticBlock2d(nn.Module):
             if need_kl_elementwise:
                 data['kl_elementwise'] = ops.KlElementwiseFn.apply(z, p_params, q_params, bool(analytical_kl))
         return out, data
+
+    def _fused(self, p_in, q_in, forced_latent, use_mode, analytical_kl, noise, n_img, rows, stats):
+        """forward() on the low-resolution levels: the two input convolutions, the elementwise core and conv_out in one launch
+        (ops.StochBlockFn) where the library takes the call (lvae_stoch_block_ok), else None. Declined here or there: no q_params, tempered
+        draws, need_kl_elementwise, force_constant_output, levels above 8x8, other channel counts."""
+        has_p = self.transform_p_params
+        N = q_in.shape[0] if n_img is None else n_img
+        cv = lambda m: (m.weight, m.geom(), m.bias)
+        mode = 2 if forced_latent is not None else 1 if use_mode else 0
+        if not K.stoch_block_ok(p_in if has_p else None, cv(self.conv_in_p) if has_p else None, None if has_p else p_in, q_in,
+                                cv(self.conv_in_q), cv(self.conv_out), mode, N):
+            return None
+        H, W = q_in.shape[1], q_in.shape[2]
+        src = forced_latent.contiguous() if mode == 2 else None if mode == 1 else noise.normal((N, H, W, self.c_vars), q_in.device)
+        params = [t for m in ((self.conv_in_p,) if has_p else ()) + (self.conv_in_q, self.conv_out) for t in (m.weight, m.bias)]
+        outs = ops.StochBlockFn.apply(p_in if has_p else None, None if has_p else p_in, q_in, src, self, mode, bool(analytical_kl), N, rows, *params)
+        out, z, q_params, lp, lq, kl, ks = outs[:7]
+        p_params = outs[7] if has_p else p_in
+        if stats is not None:
+            with torch.no_grad():
+                K.latent_stats_fold(p_params.detach(), q_params.detach(), stats, N)
+        return out, {'z': z, 'p_params': p_params, 'q_params': q_params, 'logprob_p': lp, 'logprob_q': lq, 'kl_elementwise': None,
+                     'kl_samplewise': kl, 'kl_spatial': ks}
 
     def _tempered(self, p_params, temperature, force_constant_output, noise, N, H, W, rows):
         """The prior draw of forward() at a temperature: same dict, same force_constant_output, one `normal` draw unless the scalar is 0."""

@@ -421,6 +421,65 @@ class NormalStochFn(Function):
         return dp, dq, None, None, None, None, None, None
 
 
+class StochBlockFn(Function):
+    """The whole NormalStochasticBlock2d of a low-resolution level (lib/stochastic.py:45-99) as ONE autograd node whose forward is one launch
+    (csrc/stoch_img.hip): p_params = conv_in_p(x_p) (top layer: p_given as it is), q_params = conv_in_q(x_q), the core of NormalStochFn,
+    out = conv_out(z). Returns out, z, q_params, logprob_p, logprob_q, kl_samplewise, kl_spatial [, p_params]. The backward runs the chain
+    from d_out in one launch too (lvae_stoch_block_bwd_f32) or — where that declines, or an upstream gradient of p_params / q_params exists —
+    the launches the separate nodes ran (dgrad of conv_out, the core's backward, the two dgrads); either way it hands (x, dy) of the three
+    convolutions to the weight-gradient queue as ConvFn does."""
+
+    @staticmethod
+    def forward(ctx, x_p, p_given, x_q, noise, blk, mode, analytical, N, rows, *params):
+        cv = lambda m: (m.weight, m.geom(), m.bias)
+        has_p = x_p is not None
+        out, z, p, q, lp, lq, kl, ks = K.stoch_block_fwd(x_p, cv(blk.conv_in_p) if has_p else None, p_given, x_q, cv(blk.conv_in_q), cv(blk.conv_out),
+                                                         noise, mode, analytical, N, rows=rows)
+        ctx.set_materialize_grads(False)  # unused outputs arrive as None (the kernels take NULL) instead of zero-filled tensors
+        ctx.blk, ctx.mode, ctx.analytical, ctx.has_p = blk, mode, analytical, has_p
+        ctx.p_bcast = p.shape[0] == 1 and N > 1
+        ctx.save_for_backward(x_p, p, x_q, q, noise if mode == 0 else None, z)
+        return (out, z, q, lp, lq, kl, ks) + ((p,) if has_p else ())
+
+    @staticmethod
+    def backward(ctx, d_out, dz, dq_out, g_lp, g_lq, g_kl, g_ks, dp_out=None):
+        x_p, p, x_q, q, eps, z = ctx.saved_tensors
+        none = (None,) * len(ctx.needs_input_grad)
+        if all(g is None for g in (d_out, dz, dq_out, g_lp, g_lq, g_kl, g_ks, dp_out)):
+            return none
+        cc = lambda t: None if t is None else _c(t)
+        cv = lambda m: None if m is None else (m.weight, m.geom(), m.bias)
+        co, cq, cp = ctx.blk.conv_out, ctx.blk.conv_in_q, ctx.blk.conv_in_p if ctx.has_p else None
+        hw = (z.shape[1], z.shape[2])
+        d_out, dz, g = cc(d_out), cc(dz), (cc(g_lp), cc(g_lq), cc(g_kl), cc(g_ks))
+        one = None
+        if d_out is not None and dq_out is None and dp_out is None and RB.switches.stoch_block_bwd:
+            one = K.stoch_block_bwd(d_out, cv(cp), cv(cq), cv(co), p, q, z, eps, dz, *g, ctx.mode, ctx.analytical)
+        if one is not None:
+            dp, dq, dx_p, dx_q = one
+        else:
+            if d_out is not None:
+                dzc = K.conv2d_dgrad(d_out, co.weight, co.geom(), hw)
+                dz = dzc if dz is None else K.add(dzc, dz)
+            dp, dq = K.normal_stochastic_bwd(p, q, eps, z, dz, *g, ctx.mode, ctx.analytical, z.shape[3])
+            if dq_out is not None:
+                dq = K.add(dq, _c(dq_out))
+            if dp_out is not None:
+                dp = K.add(dp, _c(dp_out))
+            dx_q = K.conv2d_dgrad(dq, cq.weight, cq.geom(), hw) if ctx.needs_input_grad[2] else None
+            dx_p = K.conv2d_dgrad(dp, cp.weight, cp.geom(), hw) if cp is not None and ctx.needs_input_grad[0] else None
+        for m, x, dy in ((co, z, d_out), (cq, x_q, dq), (cp, x_p, dp)):
+            if m is not None and dy is not None and m.weight.requires_grad:
+                wgrad(x, dy, m.weight, m.geom(), grad_buf(m.weight), grad_buf(m.bias))
+        dpg = None
+        if cp is None and ctx.needs_input_grad[1]:   # the given p_params: a broadcast parameter's gradient is summed over the batch
+            dpg = dp
+            if ctx.p_bcast:
+                dpg = torch.empty_like(p)
+                K.colsum(dp.view(dp.shape[0], -1), dpg.view(-1), False)
+        return (dx_p, dpg, dx_q) + none[3:]
+
+
 class KlElementwiseFn(Function):
     """`kl_elementwise` of lib/stochastic.py:88-91 / kl_normal_mc :209-226 as a differentiable node (off the training path)."""
 

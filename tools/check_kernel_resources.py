@@ -1,6 +1,7 @@
 """Static resource check of every gfx950 kernel in csrc/ (ADVICE r4): compiles each .hip to assembly (device only, no GPU needed) and
 lists, per kernel, VGPRs, spilled VGPRs and scratch bytes. Exits non-zero when a kernel that must not spill does:
-  * every rb_conv_kernel instantiation (resblock_img.hip: one wave per SIMD, each spill is on the critical path of a dependent chain),
+  * every rb_conv_kernel / stoch_img_*_kernel instantiation (resblock_img.hip, stoch_img.hip: one wave per SIMD, each spill is on the critical
+    path of a dependent chain),
   * the 256-pixel Winograd kernels and the persistent gate kernels.
     python tools/check_kernel_resources.py [file.hip ...]          (default: the files named below; ~1 minute per file)
 """
@@ -12,8 +13,8 @@ import tempfile
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 CSRC = os.path.join(ROOT, 'ladder-vae-pytorch_amd', 'csrc')
-DEFAULT = ['resblock_img.hip', 'conv3x3_wino.hip', 'conv1x1_gate_bwd_fused.hip', 'conv1x1_gate_fwd.hip', 'conv_wgrad_img.hip', 'conv3x3_bf16.hip']
-MUST_NOT_SPILL = ('rb_conv_kernel', 'conv3x3_wino2_kernel', 'conv1x1_gate_bwd_fused_bf16_kernel', 'conv1x1_gate_fwd_kernel', 'wgrad_img_kernel')
+DEFAULT = ['resblock_img.hip', 'stoch_img.hip', 'conv3x3_wino.hip', 'conv1x1_gate_bwd_fused.hip', 'conv1x1_gate_fwd.hip', 'conv_wgrad_img.hip', 'conv3x3_bf16.hip']
+MUST_NOT_SPILL = ('rb_conv_kernel', 'stoch_img_fwd_kernel', 'stoch_img_bwd_kernel', 'conv3x3_wino2_kernel', 'conv1x1_gate_bwd_fused_bf16_kernel', 'conv1x1_gate_fwd_kernel', 'wgrad_img_kernel')
 
 
 def kernels_of(path):
