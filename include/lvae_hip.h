@@ -572,6 +572,24 @@ int lvae_normal_prior_sample_f32(const float* p, int32_t p_bcast, const float* e
                                  const float* row_temperature, int32_t N, int32_t HW, int32_t Z, float* z, float* logprob_p,
                                  void* stream);
 
+/* Interpolation between two sets of latent rows (sampling only; no backward). za, zb [B,n] contiguous rows, t [T] on the device (any
+ * finite value is legal, extrapolation uses the same formulas; the values are NOT validated: they are the caller's responsibility, like a
+ * per-row temperature), out [T*B,n] step-major: row j*B + b = wa * za[b] + wc * zb[b] for step t[j].
+ *   mode 0 (lerp):  wa = 1 - t, wc = t.
+ *   mode 1 (slerp): wa = sin((1 - t) W) / sin W, wc = sin(t W) / sin W on the unnormalised rows, W = 2 atan2(|a^ - c^|, |a^ + c^|) the angle
+ *                   between the rows (a^, c^ the rows over their norms), never acos of a cosine. FALLBACK: a pair with |a| == 0, |c| == 0 or
+ *                   sin W < 1e-6 (a zero row, parallel rows, antipodal rows) takes the lerp coefficients at every step.
+ * The row sums, W and both coefficients are evaluated in double in a fixed order (no float atomics: the result does not depend on launch
+ * timing); each coefficient is rounded once to float and the two products and their sum are float. t == 0 writes za[b] and t == 1 writes
+ * zb[b] bit for bit in both modes (a branch: the other row may hold Inf or NaN).
+ * workspace: lvae_latent_interp_workspace(B, T) bytes (the [B][T][2] coefficients), owned by the caller. 16-byte loads and stores when
+ * n % 4 == 0 and za, zb, out are 16-byte aligned, else a scalar map. Nothing is launched or written on an error: LVAE_EINVAL for a null za,
+ * zb, t or out, B, n or T <= 0, T*B rows past 32-bit or T*B*n past 64-bit indexing, a mode outside {0, 1}; LVAE_EWORKSPACE for a workspace
+ * that is missing or smaller than the query. */
+size_t lvae_latent_interp_workspace(int32_t B, int32_t T);
+int lvae_latent_interp_f32(const float* za, const float* zb, const float* t, int32_t B, int64_t n, int32_t T, int32_t mode, float* out,
+                           void* workspace, size_t workspace_bytes, void* stream);
+
 /* `kl_elementwise` of NormalStochasticBlock2d.forward (lib/stochastic.py:88-91,108) and kl_normal_mc (lib/stochastic.py:209-226):
  * out[n,pix,c] = log q(z) - log p(z)  (analytical_kl = 0)  or  KL(q || p)  (analytical_kl = 1).  p, q [N|1,HW,2Z] (mu | logvar on
  * the channel axis; *_bcast = 1: one row set shared by the batch), z, out [N,HW,Z]. The backward writes dp, dq [N,HW,2Z] (the

@@ -175,6 +175,8 @@ SIGNATURES = {
     'lvae_stoch_block_bwd_ok': (_I, [C.POINTER(StochBlockBwd)]),
     'lvae_stoch_block_bwd_f32': (C.c_int, [C.POINTER(StochBlockBwd), _P]),
     'lvae_normal_prior_sample_f32': (C.c_int, [_P, _I, _P, _F, _P, _I, _I, _I, _P, _P, _P]),
+    'lvae_latent_interp_workspace': (_Z, [_I, _I]),
+    'lvae_latent_interp_f32': (C.c_int, [_P, _P, _P, _I, _L, _I, _I, _P, _P, _Z, _P]),
     'lvae_kl_elementwise_fwd_f32': (C.c_int, [_P, _I, _P, _I, _P, _I, _I, _I, _I, _P, _P]),
     'lvae_kl_elementwise_bwd_f32': (C.c_int, [_P, _I, _P, _I, _P, _P, _I, _I, _I, _I, _P, _P, _P, _P]),
     'lvae_bernoulli_fwd_f32': (C.c_int, [_P, _P, _P, _I, _L, _P, _P, _P, _P, _P, _P]),

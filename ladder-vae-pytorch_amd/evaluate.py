@@ -11,6 +11,8 @@ the absent boilr.eval.BaseOfflineEvaluator / VAEExperimentManager.test_procedure
   * `prior_samples(model, n)` and `inspect_layer_repr(model, n)` — evaluate.py:34-45, 95-114, as arrays;
   * `reconstructions(model, x)` — inputs beside what the model makes of them (boilr's generate_and_save_reconstructions, restated);
   * `conditional_samples(model, x, k, K)` — K variations per image that keep its top k latents (LadderVAE.sample_conditional);
+  * `interpolations(model, x_a, x_b, T, k, mode)` — T steps between two images in the latents of their top k layers, spherical or linear
+    (LadderVAE.interpolate);
   * `image_pass(model, nrows, x, step)` — the trainer's pictures (--ts-img-every): a grid of prior samples and a grid of input /
     reconstruction pairs, formed on the device (images.py), on a noise stream of their own, leaving training untouched.
 
@@ -19,7 +21,10 @@ CLI: python -m lvae_amd.evaluate --synthetic --ll --ll-samples 100 --ps --layer-
      DIR/samples_0.png and DIR/sample_mode_layer<i>.png (grids of 12 x 12), and --recons writes DIR/reconstructions.png (72 pairs).
      --cond-samples [--cond-layers k ...] [--cond-variations K] writes cond_samples_top<k>.npy (n, 1 + K, C, H, W) for the first 12
      evaluation images, column 0 the input, and with --img-dir DIR/cond_samples_top<k>.png (one row per image).
-     --temperature T [T ...] (one value, or one per layer, bottom first) tempers the prior draws of --ps and --cond-samples.
+     --interp [--interp-layers k ...] [--interp-steps T] [--interp-mode slerp|lerp] writes interp_top<k>.npy (pairs, T + 2, C, H, W) for the
+     pairs (2i, 2i + 1) of the first 24 evaluation images: column 0 is x_a, columns 1..T the steps, the last column x_b; with --img-dir
+     DIR/interp_top<k>.png (one row per pair). k defaults to the number of layers.
+     --temperature T [T ...] (one value, or one per layer, bottom first) tempers the prior draws of --ps, --cond-samples and --interp.
 """
 import os
 
@@ -335,6 +340,22 @@ def conditional_samples(model, x, n_top_layers, n_samples, temperature=None, use
 
 
 @torch.no_grad()
+def interpolations(model, x_a, x_b, n_steps=8, n_top_layers=None, mode='slerp', temperature=None):
+    """The path between the images of the NCHW batches x_a and x_b in the latents of the top n_top_layers layers (LadderVAE.interpolate at
+    the posterior means, eval mode) -> (x_a, x_b, pictures), all on the device: pictures (T * B, C, H, W), step-major, the likelihood's mean
+    where it has one and its sample otherwise (the rule of `reconstructions`). Noise comes from `model.noise`."""
+    was_training = model.training
+    model.eval()
+    try:
+        dev = next(model.parameters()).device
+        x_a, x_b = x_a.to(dev).contiguous().float(), x_b.to(dev).contiguous().float()
+        out = model.interpolate(x_a, x_b, n_steps=n_steps, n_top_layers=n_top_layers, mode=mode, temperature=temperature)
+        return x_a, x_b, (out['mean'] if out['mean'] is not None else out['sample'])
+    finally:
+        model.train(was_training)
+
+
+@torch.no_grad()
 def inspect_layer_repr(model, n=8):
     """evaluate.py:95-114: for every layer i, n calls of `sample_prior(n, mode_layers=range(i), constant_layers=range(i+1, L))`
     concatenated — each call (one row of the reference's image grid) draws the layers above i once for its whole batch, samples
@@ -423,12 +444,18 @@ def build_eval_parser():
     p.add_argument('--recons', action='store_true', help='inputs beside their reconstructions -> DIR/reconstructions.png (needs --img-dir)')
     # (--latent-stats and its two thresholds are flags of build_parser: here with --ll, and the arrays go to latent_stats.npz)
     p.add_argument('--temperature', type=float, nargs='+', default=None, metavar='T',
-                   help='temperature of the prior draws of --ps and --cond-samples: one value, or one per layer (bottom layer first)')
+                   help='temperature of the prior draws of --ps, --cond-samples and --interp: one value, or one per layer (bottom layer first)')
     p.add_argument('--cond-samples', action='store_true', dest='cond_samples',
                    help='variations of the evaluation images that keep their top k latents -> cond_samples_top<k>.npy')
     p.add_argument('--cond-layers', type=int, nargs='+', default=None, dest='cond_layers', metavar='k',
                    help='the k of --cond-samples (default: every k from 0 to the number of layers)')
     p.add_argument('--cond-variations', type=int, default=7, dest='cond_variations', metavar='K', help='variations per image and k')
+    p.add_argument('--interp', action='store_true',
+                   help='paths between pairs of evaluation images in the latents of their top k layers -> interp_top<k>.npy')
+    p.add_argument('--interp-layers', type=int, nargs='+', default=None, dest='interp_layers', metavar='k',
+                   help='the k of --interp (default: the number of layers)')
+    p.add_argument('--interp-steps', type=int, default=8, dest='interp_steps', metavar='T', help='steps of a path, both ends included')
+    p.add_argument('--interp-mode', choices=('slerp', 'lerp'), default='slerp', dest='interp_mode', help='spherical or linear')
     return p
 
 
@@ -446,6 +473,12 @@ def parse_eval_args(argv=None):
         p.error('--cond-layers takes values from 0 to %d (the number of layers), got %s' % (L, args.cond_layers))
     if args.cond_variations < 1:
         p.error('--cond-variations must be at least 1, got %d' % args.cond_variations)
+    if args.interp_layers is None:
+        args.interp_layers = [L]
+    elif any(k < 1 or k > L for k in args.interp_layers):
+        p.error('--interp-layers takes values from 1 to %d (the number of layers), got %s' % (L, args.interp_layers))
+    if args.interp_steps < 1:
+        p.error('--interp-steps must be at least 1, got %d' % args.interp_steps)
     if args.temperature is not None:
         if len(args.temperature) not in (1, L):
             p.error('--temperature takes one value or one per layer (%d), got %d' % (L, len(args.temperature)))
@@ -478,7 +511,7 @@ def main(argv=None):
     if args.img_dir:
         os.makedirs(args.img_dir, exist_ok=True)
     temperature = None if args.temperature is None else (args.temperature[0] if len(args.temperature) == 1 else args.temperature)
-    if args.ll or args.recons or args.cond_samples:
+    if args.ll or args.recons or args.cond_samples or args.interp:
         gen = torch.Generator().manual_seed(args.seed)
         if args.data_npz:
             data = torch.from_numpy(np.load(args.data_npz)['data']).float()
@@ -511,6 +544,16 @@ def main(argv=None):
             np.save('cond_samples_top%d.npy' % k, rows.cpu().numpy())
             if args.img_dir:
                 write_png(os.path.join(args.img_dir, 'cond_samples_top%d.png' % k), image_grid(rows.view(-1, *rows.shape[2:]), 1 + nv))
+    if args.interp:  # one row per pair of images (2i, 2i + 1): x_a, the T steps, x_b
+        n, nt = min(IMG_GRID_N, int(data.shape[0]) // 2), args.interp_steps
+        if n < 1:
+            raise SystemExit('--interp needs at least two evaluation images')
+        for k in args.interp_layers:
+            xa, xb, pics = interpolations(model, data[0:2 * n:2], data[1:2 * n:2], nt, k, args.interp_mode, temperature)
+            rows = torch.cat((xa.unsqueeze(1), pics.view(nt, n, *pics.shape[1:]).transpose(0, 1), xb.unsqueeze(1)), 1).contiguous()
+            np.save('interp_top%d.npy' % k, rows.cpu().numpy())
+            if args.img_dir:
+                write_png(os.path.join(args.img_dir, 'interp_top%d.png' % k), image_grid(rows.view(-1, *rows.shape[2:]), nt + 2))
     if not args.img_dir:
         return
     # the reference's pictures, after everything above so that the arrays do not depend on --img-dir

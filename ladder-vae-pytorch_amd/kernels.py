@@ -1065,6 +1065,31 @@ def normal_prior_sample(p, eps, Z, N, temperature, row_temperature=None, rows=No
     return z, lp
 
 
+INTERP_MODES = {'lerp': 0, 'slerp': 1}
+
+
+def latent_interp(za, zb, t, mode='slerp'):
+    """The path between the rows of za and zb (B, ...), both contiguous float32 and of one shape, at the steps t, a device float32 tensor
+    (T,) that is NOT validated: -> (T * B, ...), step-major (row j * B + b). mode 'lerp': (1 - t) a + t c; 'slerp': spherical, with the
+    angle between the two rows as lvae_latent_interp_f32 forms it (a zero, parallel or antipodal pair falls back to lerp). t == 0 and
+    t == 1 give the rows of za / zb bit for bit. ValueError for a shape mismatch or an unknown mode."""
+    if mode not in INTERP_MODES:
+        raise ValueError("mode must be 'slerp' or 'lerp', got %r" % (mode,))
+    if tuple(za.shape) != tuple(zb.shape) or za.dim() < 1:
+        raise ValueError("za and zb must have one shape (B, ...), got %s and %s" % (tuple(za.shape), tuple(zb.shape)))
+    if t.dim() != 1:
+        raise ValueError("t must have shape (T,), got %s" % (tuple(t.shape),))
+    pa, pb, pt = ptr(za, (torch.float32,)), ptr(zb, (torch.float32,)), ptr(t, (torch.float32,))   # (CPU tensors are refused here)
+    if not (za.is_contiguous() and zb.is_contiguous() and t.is_contiguous()):
+        raise _C.LvaeHipError("latent_interp: za, zb and t must be contiguous, got strides %s, %s, %s" % (za.stride(), zb.stride(), t.stride()))
+    B, T = int(za.shape[0]), int(t.shape[0])
+    n = za.numel() // B if B > 0 else 0
+    out = torch.empty((T * B,) + tuple(za.shape[1:]), dtype=torch.float32, device=za.device)
+    ws = workspace(_C.load().lvae_latent_interp_workspace(B, T), za.device)
+    call('lvae_latent_interp_f32', pa, pb, pt, B, n, T, INTERP_MODES[mode], ptr(out), ws.data_ptr(), ws.numel(), stream_ptr())
+    return out
+
+
 def normal_stochastic_bwd(p, q, eps, z, dz, g_lp, g_lq, g_kl, g_ks, mode, analytical_kl, Z):
     N, H, W, _ = z.shape
     p_bcast = int(p.shape[0] == 1 and N > 1)

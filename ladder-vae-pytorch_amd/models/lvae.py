@@ -10,7 +10,8 @@ Differences by design (not by omission):
     (the reference never differentiates it: it is a logged metric, experiment/experiment_manager.py does not read it);
   * every arithmetic op is a hand-written gfx950 kernel from liblvae_hip.so; the model refuses to run on CPU;
   * parameters live in one flat arena (arena.py); their gradients are accumulated in place by the wgrad kernels;
-  * noise comes from `self.noise` (noise.PhiloxNoise on device; noise.TapeNoise to replay the reference's draws).
+  * noise comes from `self.noise` (noise.PhiloxNoise on device; noise.TapeNoise to replay the reference's draws);
+  * engine-only methods beside the reference's: `sample_conditional`, `encode`, `decode`, `interpolate` (forward only).
 
 The boilr helpers the reference imports (pad/crop, Interpolate, free_bits_kl) are restated — parity unpinned
 (SURVEY.md §8c).
@@ -55,6 +56,26 @@ def layer_temperatures(L, value):
 
 def _untempered(temps):
     return all(t is None or (not torch.is_tensor(t) and t == 1.0) for t in temps)
+
+
+class _SharedDraws:
+    """Round a noise source, for the decoding half of LadderVAE.interpolate: a `normal` draw of T * B rows (a prior layer's eps) is ONE draw
+    of B rows from the source, repeated for the T steps (K.repeat_samples: step-major, no launch for one step). Every other draw passes
+    through."""
+
+    def __init__(self, src, B, T):
+        self.src, self.B, self.T = src, int(B), int(T)
+
+    def normal(self, shape_nhwc, device):
+        assert shape_nhwc[0] == self.T * self.B, (tuple(shape_nhwc), self.T, self.B)
+        eps = self.src.normal((self.B,) + tuple(shape_nhwc[1:]), device)
+        return eps if self.T == 1 else K.repeat_samples(eps, self.T)
+
+    def dropout_mask(self, N, C, p, device):
+        return self.src.dropout_mask(N, C, p, device)
+
+    def uniform(self, shape, lo, hi, device, channel_last=True):
+        return self.src.uniform(shape, lo, hi, device, channel_last)
 
 
 class LadderVAE(nn.Module):
@@ -464,6 +485,153 @@ class LadderVAE(nn.Module):
         params = {k: _nchw(v) for k, v in params.items()} if isinstance(params, dict) else _nchw(params)
         return {'sample': _nchw(info['sample']), 'mean': _nchw(info['mean']), 'mode': _nchw(info['mode']),
                 'likelihood_params': params, 'z': [_nchw(t) for t in z]}
+
+    # ------------------------------------------------------------------------------------------------------------
+    # engine-only: encode / decode / interpolate (forward only: run them under torch.no_grad())
+    # ------------------------------------------------------------------------------------------------------------
+    def _top_k(self, n_top_layers):
+        k = self.n_layers if n_top_layers is None else int(n_top_layers)
+        if not 1 <= k <= self.n_layers:
+            raise ValueError("n_top_layers must be in 1..%d, got %d" % (self.n_layers, k))
+        return k
+
+    def _encode(self, x, n_top, use_mode):
+        """Bottom-up pass of the NCHW batch x, then layers L-1 .. L-n_top in inference mode by the code path of forward() (the posterior
+        branch of _topdown_mixed); the layers below launch nothing. Returns [z NHWC, or None below L-n_top]. Between _begin and noise.end."""
+        L = self.n_layers
+        x_pad = K.pad_crop(x.contiguous().float(), True, self.get_padded_size(x.size()), False)
+        bu_values = self._bottomup(x_pad)
+        z = [None] * L
+        out = None
+        for i in reversed(range(L - n_top, L)):
+            out, _, aux = self.top_down_layers[i](out, skip_connection_input=out, inference_mode=True, bu_value=bu_values[i],
+                                                  use_mode=use_mode, noise=self.noise)
+            z[i] = aux['z']
+        return z
+
+    def _decode(self, forced, rows, temps, noise):
+        """Generative pass on `rows` rows: layer i takes forced[i] (NHWC, through forced_latent) where it is given and draws from its prior
+        at temps[i] (from `noise`) where it is None; then final_top_down. Returns (out NHWC, [z NHWC per layer])."""
+        z = [None] * self.n_layers
+        out = None
+        for i in reversed(range(self.n_layers)):
+            kw = dict(temperature=temps[i]) if forced[i] is None else dict(forced_latent=forced[i])
+            out, _, aux = self.top_down_layers[i](out, skip_connection_input=out, inference_mode=False, n_img_prior=rows, noise=noise, **kw)
+            z[i] = aux['z']
+        for mod in self.final_top_down:
+            if isinstance(mod, Placeholder):
+                out = ops.UpsampleFn.apply(out)
+            else:
+                out = mod(out, noise)
+        return out, z
+
+    def _pictures(self, out, img_size, z):
+        """crop, likelihood without a target, noise.end() -> the dict of sample_conditional"""
+        if tuple(out.shape[1:3]) != tuple(img_size):
+            out = ops.CropFn.apply(out, tuple(img_size))
+        _, info = self.likelihood(out, None, self.noise)
+        self.noise.end()
+        params = info['params']
+        params = {k: _nchw(v) for k, v in params.items()} if isinstance(params, dict) else _nchw(params)
+        return {'sample': _nchw(info['sample']), 'mean': _nchw(info['mean']), 'mode': _nchw(info['mode']),
+                'likelihood_params': params, 'z': [_nchw(t) for t in z]}
+
+    def encode(self, x, n_top_layers=None, use_mode=True):
+        """Engine-only: the latents of the top k = n_top_layers layers (None: all L) of the NCHW batch x, from its posterior as forward()
+        draws them; with use_mode (the default) the posterior means, drawing no noise. Returns a list of L entries indexed like z_dims: NCHW
+        z for layers L-k .. L-1, None below (those layers launch nothing). k = 0 is a ValueError: there is nothing to encode. Noise (use_mode
+        False only): one `normal` draw per encoded layer, top to bottom. Obeys the module's train / eval mode."""
+        if not x.is_cuda:
+            raise K._C.LvaeHipError("LadderVAE (HIP engine) needs a GPU tensor; got %s" % x.device)
+        if x.dim() != 4:
+            raise ValueError("x must be (B, C, H, W), got %s" % (tuple(x.shape),))
+        n_top = self._top_k(n_top_layers)
+        self._begin(x)
+        z = self._encode(x, n_top, use_mode)
+        self.noise.end()
+        return [_nchw(t) for t in z]
+
+    def _forced_rows(self, z, what):
+        """z: a list of L NCHW tensors or None -> ([NHWC contiguous or None], their common row count or None)"""
+        L = self.n_layers
+        z = list(z)
+        if len(z) != L:
+            raise ValueError("%s must have one entry per layer (%d), got %d" % (what, L, len(z)))
+        rows, forced = None, [None] * L
+        for i, t in enumerate(z):
+            if t is None:
+                continue
+            if not t.is_cuda:
+                raise K._C.LvaeHipError("LadderVAE (HIP engine) needs GPU tensors; %s[%d] is on %s" % (what, i, t.device))
+            if t.dim() != 4 or t.shape[1] != self.z_dims[i]:
+                raise ValueError("%s[%d] must be (N, %d, h, w), got %s" % (what, i, self.z_dims[i], tuple(t.shape)))
+            if rows is not None and t.shape[0] != rows:
+                raise ValueError("the entries of %s disagree about the number of rows: %d and %d" % (what, rows, t.shape[0]))
+            rows = int(t.shape[0])
+            forced[i] = t.float().permute(0, 2, 3, 1).contiguous()   # (no copy for what encode() returned)
+        return forced, rows
+
+    def decode(self, z, n_imgs=None, temperature=None):
+        """Engine-only: pictures from latents. z: a list of L entries indexed like z_dims, each an NCHW tensor or None. A given layer is
+        forced (forced_latent, generative mode); a None layer is drawn from its prior at `temperature`, by the rules of sample_prior (a float,
+        L floats, or a device tensor of per-row temperatures; 0.0 draws no noise). A forced layer below a sampled one is legal. The number of
+        rows is that of the forced tensors; n_imgs is needed only when every entry is None (ValueError when it is missing then, and when it
+        contradicts the forced tensors). Noise: one `normal` draw per layer that samples, top to bottom, then the likelihood's draws. Returns
+        the dict of sample_conditional: 'sample', 'mean', 'mode', 'likelihood_params', 'z' (all L layers). Obeys train / eval mode."""
+        forced, rows = self._forced_rows(z, 'z')
+        if rows is None:
+            if n_imgs is None:
+                raise ValueError("n_imgs is needed when no layer is forced")
+            rows = int(n_imgs)
+            if rows < 1:
+                raise ValueError("n_imgs must be at least 1, got %d" % rows)
+        elif n_imgs is not None and int(n_imgs) != rows:
+            raise ValueError("n_imgs = %d, but the forced latents have %d rows" % (int(n_imgs), rows))
+        temps = layer_temperatures(self.n_layers, temperature)
+        self._begin(next((t for t in forced if t is not None), None))
+        out, zs = self._decode(forced, rows, temps, self.noise)
+        return self._pictures(out, self.img_shape, zs)
+
+    def interpolate(self, x_a, x_b, n_steps=8, n_top_layers=None, mode='slerp', t=None, use_mode=True, temperature=None):
+        """Engine-only: the path between the images of x_a and x_b (B, C, H, W) in the latents of the top k = n_top_layers layers (None: all
+        L). The 2B rows [x_a; x_b] are encoded in one bottom-up pass and the top k layers run on them in inference mode, so each endpoint's
+        chain is conditioned on its own latents (use_mode, the default: the posterior means). Per layer i >= L-k one launch
+        (kernels.latent_interp) moves z from x_a's to x_b's at the steps t, spherically (mode 'slerp') or linearly ('lerp'): t defaults to
+        linspace(0, 1, n_steps); a float32 device tensor (T,) is taken as it is (any finite value, not validated). The T * B rows, step-major
+        (row j * B + b), are then decoded with those layers forced; the layers below draw from their prior at `temperature` (as in
+        sample_prior) ONCE per pair: the (B, h, w, Z) draw is repeated for the T steps, so a pair's pictures differ only through the
+        interpolated latents. Then final_top_down, the crop and the likelihood without a target.
+
+        Noise, in this order: with use_mode False one `normal` draw of 2B rows per posterior layer, top to bottom; one `normal` draw of B
+        rows per prior layer that samples (none at temperature 0.0); the likelihood's draws on T * B rows.
+
+        Returns the dict of decode() plus 'z_a', 'z_b' (the endpoints' NCHW latents per layer, None below L-k) and 't'. Obeys the module's
+        train / eval mode like sample_conditional; eval is what is meant: BatchNorm in train mode would couple the 2B rows."""
+        if not (x_a.is_cuda and x_b.is_cuda):
+            raise K._C.LvaeHipError("LadderVAE (HIP engine) needs GPU tensors; got %s and %s" % (x_a.device, x_b.device))
+        if x_a.dim() != 4 or tuple(x_a.shape) != tuple(x_b.shape):
+            raise ValueError("x_a and x_b must have one shape (B, C, H, W), got %s and %s" % (tuple(x_a.shape), tuple(x_b.shape)))
+        if mode not in K.INTERP_MODES:
+            raise ValueError("mode must be 'slerp' or 'lerp', got %r" % (mode,))
+        L, B = self.n_layers, int(x_a.shape[0])
+        n_top = self._top_k(n_top_layers)
+        if t is None:
+            if int(n_steps) < 1:
+                raise ValueError("n_steps must be at least 1, got %d" % int(n_steps))
+            t = torch.linspace(0.0, 1.0, int(n_steps), dtype=torch.float32, device=x_a.device)
+        elif not torch.is_tensor(t) or t.dim() != 1 or t.shape[0] < 1 or t.dtype != torch.float32:
+            raise ValueError("t must be a float32 device tensor of shape (T,)")
+        T = int(t.shape[0])
+        temps = layer_temperatures(L, temperature)
+        self._begin(x_a)
+        z_ab = self._encode(torch.cat((x_a, x_b)), n_top, use_mode)
+        z_a = [None if v is None else v[:B] for v in z_ab]   # (row slices of a contiguous tensor: contiguous)
+        z_b = [None if v is None else v[B:] for v in z_ab]
+        forced = [None if v is None else K.latent_interp(z_a[i], z_b[i], t, mode) for i, v in enumerate(z_ab)]
+        out, zs = self._decode(forced, T * B, temps, _SharedDraws(self.noise, B, T))
+        res = self._pictures(out, x_a.shape[2:], zs)
+        res.update(z_a=[_nchw(v) for v in z_a], z_b=[_nchw(v) for v in z_b], t=t)
+        return res
 
     def get_top_prior_param_shape(self, n_imgs=1):
         """models/lvae.py:364-372."""
