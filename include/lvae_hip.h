@@ -628,6 +628,41 @@ int lvae_gaussian_fwd_f32(const float* params, const float* x, const float* eps,
  * dll_draw [N,P,2C] optional: gradient w.r.t. the RAW conv output. */
 int lvae_discr_logistic_fwd_f32(const float* raw, const float* x, const float* u, int32_t N, int64_t P, int32_t C, float* mean,
                                 float* logscale, float* sample, float* ll, float* dll_draw, void* stream);
+/* Masked forms of the four heads above: score an image on the pixels it has, and complete it.
+ * mask [N,HW] bytes, one flag per PIXEL shared by its colour channels (the DMoL colours of a pixel are coupled: a per-channel flag has no
+ * meaning there); non-zero (any of 1..255) = observed. filled [N,HW,C] or NULL. Every other argument is that of the unmasked form; the
+ * Bernoulli form also takes C, because its P = HW*C does not say where a pixel ends (LVAE_EINVAL unless C > 0 and P % C == 0), and the
+ * DMoL form takes `sample`, the output of lvae_dmol_sample_f32 on the same l and uniforms (the draw of the unmasked path, made by the launch
+ * the head issues anyway), from which it writes filled inside the ll launch; `sample` may be NULL when filled is.
+ *   ll[n]   the sum of the unmasked kernel's per-element terms over the observed pixels of image n, in the same fixed order (the kernels
+ *           are the unmasked ones instantiated with a mask: the thread map and the reduction order are theirs). No pixel observed: +0.0f.
+ *   dll     exactly +0.0f at every parameter of a missing pixel: a branch, not a product. x is NOT READ at a missing pixel (it may hold
+ *           NaN there), and parameters that are NaN or Inf at a missing pixel leave ll and every other dll element as they were.
+ *   mean, mode, logscale, sample: written at every pixel as by the unmasked form, from the same noise.
+ *   filled  x where observed, the head's sample where missing (from the same u / eps, so it needs them even when `sample` is NULL).
+ *           filled MAY ALIAS x (in-place completion): each thread reads its element of x before it writes that element of filled, and no
+ *           thread reads another's. It may not alias any other argument.
+ * With every pixel observed ll, dll and the pictures are bit for bit those of the unmasked entry point, and filled == x.
+ * Nothing is launched or written on an error: LVAE_EINVAL for a null mask, a null x or ll, and everything the unmasked form refuses;
+ * LVAE_EWORKSPACE as in lvae_dmol_ll_fwd_f32 (workspace: lvae_dmol_workspace(N, HW) bytes). */
+int lvae_bernoulli_masked_fwd_f32(const float* logits, const float* x, const float* u, int32_t N, int64_t P, int32_t C, float* mean,
+                                  float* mode, float* sample, float* ll, float* dll_dlogits, const uint8_t* mask, float* filled,
+                                  void* stream);
+int lvae_dmol_ll_masked_fwd_f32(const float* l, const float* x, int32_t N, int32_t HW, int32_t nmix, float* ll, float* dll_dl,
+                                void* workspace, size_t workspace_bytes, const uint8_t* mask, const float* sample, float* filled,
+                                void* stream);
+int lvae_gaussian_masked_fwd_f32(const float* params, const float* x, const float* eps, int32_t N, int64_t P, int32_t C, float* sample,
+                                 float* ll, float* dll_dparams, const uint8_t* mask, float* filled, void* stream);
+int lvae_discr_logistic_masked_fwd_f32(const float* raw, const float* x, const float* u, int32_t N, int64_t P, int32_t C, float* mean,
+                                       float* logscale, float* sample, float* ll, float* dll_draw, const uint8_t* mask, float* filled,
+                                       void* stream);
+/* out = mask ? a : (b ? b : b_value), element by element, exactly (a select: the value not taken may be NaN). mask [N,HW] as above; a, b
+ * (or NULL: the scalar b_value everywhere) and out are [N,C,HW] when nchw != 0, else [N,HW,C]. out MAY ALIAS a or b: each thread reads its
+ * elements before it writes them. 16-byte loads and stores when a, b and out are 16-byte aligned and HW % 4 == 0 (nchw) or N*HW*C % 4 == 0
+ * (channel-last), else a scalar map. Nothing is launched or written on an error: LVAE_EINVAL for a null a, mask or out, N, C or HW <= 0,
+ * N*C*HW past 64-bit byte offsets. */
+int lvae_mask_select_f32(const float* a, const float* b, float b_value, const uint8_t* mask, int32_t N, int32_t C, int64_t HW,
+                         int32_t nchw, float* out, void* stream);
 /* out[n, i] = g[n] * a[n, i]  (chain rule through a per-sample scalar; backward of the two heads above) */
 int lvae_scale_per_sample_f32(const float* a, const float* g, int32_t N, int64_t P, float* out, void* stream);
 

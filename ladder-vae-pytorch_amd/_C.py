@@ -185,6 +185,11 @@ SIGNATURES = {
     'lvae_dmol_sample_f32': (C.c_int, [_P, _P, _P, _I, _I, _I, _P, _P]),
     'lvae_gaussian_fwd_f32': (C.c_int, [_P, _P, _P, _I, _L, _I, _P, _P, _P, _P]),
     'lvae_discr_logistic_fwd_f32': (C.c_int, [_P, _P, _P, _I, _L, _I, _P, _P, _P, _P, _P, _P]),
+    'lvae_bernoulli_masked_fwd_f32': (C.c_int, [_P, _P, _P, _I, _L, _I, _P, _P, _P, _P, _P, _P, _P, _P]),
+    'lvae_dmol_ll_masked_fwd_f32': (C.c_int, [_P, _P, _I, _I, _I, _P, _P, _P, _Z, _P, _P, _P, _P]),
+    'lvae_gaussian_masked_fwd_f32': (C.c_int, [_P, _P, _P, _I, _L, _I, _P, _P, _P, _P, _P, _P]),
+    'lvae_discr_logistic_masked_fwd_f32': (C.c_int, [_P, _P, _P, _I, _L, _I, _P, _P, _P, _P, _P, _P, _P, _P]),
+    'lvae_mask_select_f32': (C.c_int, [_P, _P, _F, _P, _I, _I, _L, _I, _P, _P]),
     'lvae_scale_per_sample_f32': (C.c_int, [_P, _P, _I, _L, _P, _P]),
     'lvae_upsample2x_fwd_f32': (C.c_int, [_P, _I, _I, _I, _I, _P, _P]),
     'lvae_upsample2x_bwd_f32': (C.c_int, [_P, _I, _I, _I, _I, _P, _P]),

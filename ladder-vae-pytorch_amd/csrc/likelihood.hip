@@ -2,6 +2,8 @@
 // logistics (log-likelihood with its analytic parameter gradient, and the Gumbel-max / logistic sampler).
 // The DMoL kernels stage the 100 parameters of each pixel through LDS with coalesced 16-B global accesses and
 // then work one pixel per lane on a padded row (stride 101 floats -> conflict-free column walks).
+// Every head is a template on MASKED: the lvae_*_masked_fwd_f32 entry points score the observed pixels of a partly observed image and fill
+// in the missing ones with the head's draw (same thread map, same order of every sum); lvae_mask_select_f32 picks between two pictures.
 #include "lvae_common.h"
 
 namespace lvae {
@@ -9,9 +11,15 @@ namespace lvae {
 // ---------------------------------------------------------------------------------------------------------
 // Bernoulli (lib/likelihoods.py:60-78, 385-388)
 // ---------------------------------------------------------------------------------------------------------
-__global__ __launch_bounds__(256) void bernoulli_fwd_kernel(const float* __restrict__ logits, const float* __restrict__ x,
+// MASKED (the lvae_*_masked_fwd_f32 entry points, here and in the three kernels below): `mask` holds one flag per pixel, [N][HW], non-zero =
+// observed. A missing pixel adds nothing to ll, its dll is +0.0f by a branch (x is not read there; the parameters may be anything), and
+// `filled` (optional) takes x where observed and the head's draw where missing. x carries no __restrict__: filled may be x itself, and a
+// thread reads its element before it writes it. The thread map and the order of the sum are those of the unmasked instantiation.
+template <bool MASKED>
+__global__ __launch_bounds__(256) void bernoulli_fwd_kernel(const float* __restrict__ logits, const float* x,
                                                              const float* __restrict__ u, int64_t P, float* mean,
-                                                             float* mode, float* sample, float* ll, float* dll) {
+                                                             float* mode, float* sample, float* ll, float* dll,
+                                                             const uint8_t* __restrict__ mask, int C, float* filled) {
   __shared__ float red[4];
   const int n = blockIdx.x;
   const size_t base = (size_t)n * P;
@@ -22,8 +30,14 @@ __global__ __launch_bounds__(256) void bernoulli_fwd_kernel(const float* __restr
     if (mean) mean[base + i] = m;
     if (mode) mode[base + i] = rintf(m);  // torch.round: half to even
     if (sample) sample[base + i] = u[base + i] < m ? 1.f : 0.f;
+    if (MASKED && !mask[(base + i) / C]) {  // P = HW * C: the flat pixel index over the batch
+      if (dll) dll[base + i] = 0.f;
+      if (filled) filled[base + i] = u[base + i] < m ? 1.f : 0.f;
+      continue;
+    }
     if (x) {
       const float xv = x[base + i];
+      if (MASKED && filled) filled[base + i] = xv;
       // F.binary_cross_entropy clamps each log term at -100. log(m) = lg - log1p(exp(lg)) is lg itself below -20 (the correction is under 2.1e-9);
       // taken from m it jumped from -87.3 to the clamp, because the hardware reciprocal in sigmoidf_ returns 0 once 1 / (1 + exp(-lg)) is denormal.
       // (log(1 - m) reaches the clamp from lg = 17 on, where m rounds to 1, as the fp32 reference's does.)
@@ -84,10 +98,13 @@ __device__ __forceinline__ ColourTerm dmol_colour(float x, float mean, float ls_
   return r;
 }
 
-template <int NMIX, int DM_PIX>  // DM_PIX pixels per workgroup: 128 while their parameter rows fit the 64 KB of static LDS, else 64
-__global__ __launch_bounds__(DM_PIX) void dmol_ll_kernel(const float* __restrict__ l, const float* __restrict__ x,
+// MASKED: mask [npix]; a missing pixel's ll_pix is +0.0f (the row sum then runs over the same HW slots in the same order), its dl row is
+// zeros, and filled [npix][3] (optional) takes `drawn` there (the output of dmol_sample_kernel on the same parameters) and x elsewhere.
+template <int NMIX, int DM_PIX, bool MASKED>  // DM_PIX pixels per workgroup: 128 while their parameter rows fit the 64 KB of static LDS, else 64
+__global__ __launch_bounds__(DM_PIX) void dmol_ll_kernel(const float* __restrict__ l, const float* x,
                                                           int64_t npix, float* __restrict__ ll_pix,
-                                                          float* __restrict__ dl) {
+                                                          float* __restrict__ dl, const uint8_t* __restrict__ mask,
+                                                          const float* __restrict__ drawn, float* filled) {
   constexpr int NP = 10 * NMIX, NPS = NP + 1;  // parameters per pixel, padded LDS row
   __shared__ float buf[DM_PIX * NPS];
   const int t = threadIdx.x;
@@ -97,10 +114,23 @@ __global__ __launch_bounds__(DM_PIX) void dmol_ll_kernel(const float* __restrict
   const float* src = l + p0 * NP;
   for (int i = t; i < cnt * NP; i += DM_PIX) buf[(i / NP) * NPS + (i % NP)] = src[i];
   __syncthreads();
-  if (t < cnt) {
+  if (MASKED && t < cnt && !mask[p0 + t]) {
     float* row = buf + t * NPS;
     const int64_t pix = p0 + t;
-    const float x0 = 2.f * x[pix * 3 + 0] - 1.f, x1 = 2.f * x[pix * 3 + 1] - 1.f, x2 = 2.f * x[pix * 3 + 2] - 1.f;
+    ll_pix[pix] = 0.f;
+    if (dl) {
+      for (int k = 0; k < NP; ++k) row[k] = 0.f;
+    }
+    if (filled) {
+      const float s0 = drawn[pix * 3 + 0], s1 = drawn[pix * 3 + 1], s2 = drawn[pix * 3 + 2];
+      filled[pix * 3 + 0] = s0, filled[pix * 3 + 1] = s1, filled[pix * 3 + 2] = s2;
+    }
+  } else if (t < cnt) {
+    float* row = buf + t * NPS;
+    const int64_t pix = p0 + t;
+    const float xr0 = x[pix * 3 + 0], xr1 = x[pix * 3 + 1], xr2 = x[pix * 3 + 2];
+    if (MASKED && filled) filled[pix * 3 + 0] = xr0, filled[pix * 3 + 1] = xr1, filled[pix * 3 + 2] = xr2;
+    const float x0 = 2.f * xr0 - 1.f, x1 = 2.f * xr1 - 1.f, x2 = 2.f * xr2 - 1.f;
     float lpk[NMIX];
     float lmax = -INFINITY;
 #pragma unroll
@@ -213,9 +243,11 @@ __global__ __launch_bounds__(256) void dmol_sample_kernel(const float* __restric
 // ---------------------------------------------------------------------------------------------------------
 // Gaussian head (lib/likelihoods.py:81-114, log_normal :391-411). params [N][P][2C] = (mean | logvar) per pixel.
 // ---------------------------------------------------------------------------------------------------------
-__global__ __launch_bounds__(256) void gaussian_fwd_kernel(const float* __restrict__ params, const float* __restrict__ x,
+template <bool MASKED>
+__global__ __launch_bounds__(256) void gaussian_fwd_kernel(const float* __restrict__ params, const float* x,
                                                             const float* __restrict__ eps, int64_t P, int C, float* sample,
-                                                            float* ll, float* dll) {
+                                                            float* ll, float* dll, const uint8_t* __restrict__ mask,
+                                                            float* filled) {
   __shared__ float red[4];
   const int n = blockIdx.x;
   const int64_t per = P * C;
@@ -226,8 +258,15 @@ __global__ __launch_bounds__(256) void gaussian_fwd_kernel(const float* __restri
     const size_t pb = ((size_t)n * P + pix) * 2 * C;
     const float mean = params[pb + c], lv = params[pb + C + c];
     if (sample) sample[(size_t)n * per + i] = mean + expf(0.5f * lv) * eps[(size_t)n * per + i];
+    if (MASKED && !mask[(size_t)n * P + pix]) {
+      if (dll) dll[pb + c] = 0.f, dll[pb + C + c] = 0.f;
+      if (filled) filled[(size_t)n * per + i] = mean + expf(0.5f * lv) * eps[(size_t)n * per + i];
+      continue;
+    }
     if (x) {
-      const float d = x[(size_t)n * per + i] - mean, iv = expf(-lv);
+      const float xv = x[(size_t)n * per + i];
+      if (MASKED && filled) filled[(size_t)n * per + i] = xv;
+      const float d = xv - mean, iv = expf(-lv);
       acc += -0.5f * (d * d * iv + lv + 1.8378770664093453f);  // log(2*pi)
       if (dll) {
         dll[pb + c] = d * iv;
@@ -245,10 +284,11 @@ __global__ __launch_bounds__(256) void gaussian_fwd_kernel(const float* __restri
 // Discretized logistic head (lib/likelihoods.py:117-180, log_discretized_logistic :233-288), 256 bins.
 // raw [N][P][2C] = (mean_raw | log_scale_raw); outputs mean = mean_raw + 0.5, logscale = max(ls_raw - 1, -7).
 // ---------------------------------------------------------------------------------------------------------
-__global__ __launch_bounds__(256) void discr_logistic_fwd_kernel(const float* __restrict__ raw, const float* __restrict__ x,
+template <bool MASKED>
+__global__ __launch_bounds__(256) void discr_logistic_fwd_kernel(const float* __restrict__ raw, const float* x,
                                                                   const float* __restrict__ u, int64_t P, int C,
                                                                   float* mean_out, float* ls_out, float* sample, float* ll,
-                                                                  float* dll) {
+                                                                  float* dll, const uint8_t* __restrict__ mask, float* filled) {
   __shared__ float red[4];
   const int n = blockIdx.x;
   const int64_t per = P * C;
@@ -268,8 +308,18 @@ __global__ __launch_bounds__(256) void discr_logistic_fwd_kernel(const float* __
       const float uu = u[oi];
       sample[oi] = fminf(fmaxf(mean + scale * (logf(uu) - logf(1.f - uu)), 0.f), 1.f);
     }
+    if (MASKED && !mask[(size_t)n * P + pix]) {
+      if (dll) dll[pb + c] = 0.f, dll[pb + C + c] = 0.f;
+      if (filled) {
+        const float uu = u[oi];
+        filled[oi] = fminf(fmaxf(mean + scale * (logf(uu) - logf(1.f - uu)), 0.f), 1.f);
+      }
+      continue;
+    }
     if (x) {
-      const float xs = x[oi] * (255.f / 256.f) + 1.f / 512.f;
+      const float xv = x[oi];
+      if (MASKED && filled) filled[oi] = xv;
+      const float xs = xv * (255.f / 256.f) + 1.f / 512.f;
       const float xq = floorf(xs * nb) / nb;
       const bool has_plus = xq < (nb - 1.f) / nb, has_minus = xq >= 1.f / nb;
       const float a = (xq + 1.f / nb - mean) / scale, b = (xq - mean) / scale;
@@ -296,6 +346,38 @@ __global__ __launch_bounds__(256) void scale_per_sample_kernel(const float* __re
     out[i] = a[i] * g[i / P];
 }
 
+// out = mask ? a : (b ? b : b_value), one flag per pixel. total = N * C * HW elements; NCHW: element e sits at pixel (e / (C * HW)) * HW + e % HW,
+// NHWC: at pixel e / C. out may be a or b: a thread reads its elements before it writes them (no __restrict__ on the three).
+template <bool NCHW>
+__device__ __forceinline__ int64_t select_pixel(int64_t e, int64_t C, int64_t HW) {
+  return NCHW ? (e / (C * HW)) * HW + e % HW : e / C;
+}
+
+template <bool NCHW>  // total % 4 == 0 (NCHW: HW % 4 == 0, so a group stays inside one plane) and 16-byte aligned a, b, out
+__global__ __launch_bounds__(256) void mask_select_v4_kernel(const float* a, const float* b, float b_value,
+                                                              const uint8_t* __restrict__ mask, int64_t C, int64_t HW,
+                                                              int64_t total4, float* out) {
+  for (int64_t g = (int64_t)blockIdx.x * 256 + threadIdx.x; g < total4; g += (int64_t)gridDim.x * 256) {
+    const f32x4 va = reinterpret_cast<const f32x4*>(a)[g];
+    f32x4 vb = f32x4{b_value, b_value, b_value, b_value};
+    if (b) vb = reinterpret_cast<const f32x4*>(b)[g];
+    f32x4 r;
+#pragma unroll
+    for (int q = 0; q < 4; ++q) r[q] = mask[select_pixel<NCHW>(4 * g + q, C, HW)] ? va[q] : vb[q];
+    reinterpret_cast<f32x4*>(out)[g] = r;
+  }
+}
+
+template <bool NCHW>  // any size, any alignment
+__global__ __launch_bounds__(256) void mask_select_kernel(const float* a, const float* b, float b_value,
+                                                           const uint8_t* __restrict__ mask, int64_t C, int64_t HW, int64_t total,
+                                                           float* out) {
+  for (int64_t e = (int64_t)blockIdx.x * 256 + threadIdx.x; e < total; e += (int64_t)gridDim.x * 256) {
+    const float va = a[e], vb = b ? b[e] : b_value;
+    out[e] = mask[select_pixel<NCHW>(e, C, HW)] ? va : vb;
+  }
+}
+
 }  // namespace lvae
 
 using namespace lvae;
@@ -306,9 +388,23 @@ extern "C" int lvae_bernoulli_fwd_f32(const float* logits, const float* x, const
   LVAE_REQUIRE(logits && N > 0 && P > 0, LVAE_EINVAL, "lvae_bernoulli_fwd_f32: bad args");
   LVAE_REQUIRE(!sample || u, LVAE_EINVAL, "lvae_bernoulli_fwd_f32: sample needs uniforms");
   LVAE_REQUIRE(!x || ll, LVAE_EINVAL, "lvae_bernoulli_fwd_f32: x given but ll is null");
-  hipLaunchKernelGGL(bernoulli_fwd_kernel, dim3(N), dim3(256), 0, (hipStream_t)stream, logits, x, u, P, mean, mode, sample,
-                     ll, dll_dlogits);
+  hipLaunchKernelGGL(bernoulli_fwd_kernel<false>, dim3(N), dim3(256), 0, (hipStream_t)stream, logits, x, u, P, mean, mode, sample,
+                     ll, dll_dlogits, (const uint8_t*)nullptr, 1, (float*)nullptr);
   LVAE_LAUNCH_CHECK("bernoulli_fwd");
+  return 0;
+}
+
+extern "C" int lvae_bernoulli_masked_fwd_f32(const float* logits, const float* x, const float* u, int32_t N, int64_t P, int32_t C,
+                                             float* mean, float* mode, float* sample, float* ll, float* dll_dlogits,
+                                             const uint8_t* mask, float* filled, void* stream) {
+  LVAE_REQUIRE(logits && N > 0 && P > 0, LVAE_EINVAL, "lvae_bernoulli_masked_fwd_f32: bad args");
+  LVAE_REQUIRE(C > 0 && P % C == 0, LVAE_EINVAL, "lvae_bernoulli_masked_fwd_f32: P = %lld is not H*W pixels of C = %d channels", (long long)P, C);
+  LVAE_REQUIRE(mask, LVAE_EINVAL, "lvae_bernoulli_masked_fwd_f32: mask is null");
+  LVAE_REQUIRE(x && ll, LVAE_EINVAL, "lvae_bernoulli_masked_fwd_f32: x and ll are needed");
+  LVAE_REQUIRE((!sample && !filled) || u, LVAE_EINVAL, "lvae_bernoulli_masked_fwd_f32: sample and filled need uniforms");
+  hipLaunchKernelGGL(bernoulli_fwd_kernel<true>, dim3(N), dim3(256), 0, (hipStream_t)stream, logits, x, u, P, mean, mode, sample,
+                     ll, dll_dlogits, mask, (int)C, filled);
+  LVAE_LAUNCH_CHECK("bernoulli_masked_fwd");
   return 0;
 }
 
@@ -326,19 +422,18 @@ static bool dmol_supported(int nmix) {
   }
 }
 
-extern "C" int lvae_dmol_ll_fwd_f32(const float* l, const float* x, int32_t N, int32_t HW, int32_t nmix, float* ll,
-                                    float* dll_dl, void* workspace, size_t workspace_bytes, void* stream) {
-  LVAE_REQUIRE(l && x && ll && workspace && N > 0 && HW > 0, LVAE_EINVAL, "lvae_dmol_ll_fwd_f32: bad args");
-  LVAE_REQUIRE(dmol_supported(nmix), LVAE_EINVAL, "lvae_dmol_ll_fwd_f32: %d mixture components: instantiated for 1-6, 8, 10, 12, 16, 20", nmix);
-  LVAE_REQUIRE(workspace_bytes >= lvae_dmol_workspace(N, HW), LVAE_EWORKSPACE, "lvae_dmol_ll_fwd_f32: workspace");
+// the two launches of both DMoL entry points (arguments checked by the caller)
+template <bool MASKED>
+static int dmol_ll_launch(const float* l, const float* x, int32_t N, int32_t HW, int32_t nmix, float* ll, float* dll_dl, void* workspace,
+                          const uint8_t* mask, const float* drawn, float* filled, hipStream_t s) {
   const int64_t npix = (int64_t)N * HW;
-  hipStream_t s = (hipStream_t)stream;
   float* ll_pix = static_cast<float*>(workspace);
   switch (nmix) {
 #define X(n)                                                                                                                         \
   case n: {                                                                                                                          \
     constexpr int PIX = (128 * (10 * n + 1) * 4 <= 64 * 1024) ? 128 : 64;                                                            \
-    hipLaunchKernelGGL((dmol_ll_kernel<n, PIX>), dim3((unsigned)((npix + PIX - 1) / PIX)), dim3(PIX), 0, s, l, x, npix, ll_pix, dll_dl); \
+    hipLaunchKernelGGL((dmol_ll_kernel<n, PIX, MASKED>), dim3((unsigned)((npix + PIX - 1) / PIX)), dim3(PIX), 0, s, l, x, npix, ll_pix, \
+                       dll_dl, mask, drawn, filled);                                                                                 \
   } break;
     LVAE_DMOL_COUNTS(X)
 #undef X
@@ -347,6 +442,25 @@ extern "C" int lvae_dmol_ll_fwd_f32(const float* l, const float* x, int32_t N, i
   hipLaunchKernelGGL(rowsum_kernel, dim3(N), dim3(256), 0, s, ll_pix, (int64_t)HW, ll);
   LVAE_LAUNCH_CHECK("dmol_rowsum");
   return 0;
+}
+
+extern "C" int lvae_dmol_ll_fwd_f32(const float* l, const float* x, int32_t N, int32_t HW, int32_t nmix, float* ll,
+                                    float* dll_dl, void* workspace, size_t workspace_bytes, void* stream) {
+  LVAE_REQUIRE(l && x && ll && workspace && N > 0 && HW > 0, LVAE_EINVAL, "lvae_dmol_ll_fwd_f32: bad args");
+  LVAE_REQUIRE(dmol_supported(nmix), LVAE_EINVAL, "lvae_dmol_ll_fwd_f32: %d mixture components: instantiated for 1-6, 8, 10, 12, 16, 20", nmix);
+  LVAE_REQUIRE(workspace_bytes >= lvae_dmol_workspace(N, HW), LVAE_EWORKSPACE, "lvae_dmol_ll_fwd_f32: workspace");
+  return dmol_ll_launch<false>(l, x, N, HW, nmix, ll, dll_dl, workspace, nullptr, nullptr, nullptr, (hipStream_t)stream);
+}
+
+extern "C" int lvae_dmol_ll_masked_fwd_f32(const float* l, const float* x, int32_t N, int32_t HW, int32_t nmix, float* ll,
+                                           float* dll_dl, void* workspace, size_t workspace_bytes, const uint8_t* mask,
+                                           const float* sample, float* filled, void* stream) {
+  LVAE_REQUIRE(l && x && ll && workspace && N > 0 && HW > 0, LVAE_EINVAL, "lvae_dmol_ll_masked_fwd_f32: bad args");
+  LVAE_REQUIRE(mask, LVAE_EINVAL, "lvae_dmol_ll_masked_fwd_f32: mask is null");
+  LVAE_REQUIRE(!filled || sample, LVAE_EINVAL, "lvae_dmol_ll_masked_fwd_f32: filled needs the draw of lvae_dmol_sample_f32");
+  LVAE_REQUIRE(dmol_supported(nmix), LVAE_EINVAL, "lvae_dmol_ll_masked_fwd_f32: %d mixture components: instantiated for 1-6, 8, 10, 12, 16, 20", nmix);
+  LVAE_REQUIRE(workspace_bytes >= lvae_dmol_workspace(N, HW), LVAE_EWORKSPACE, "lvae_dmol_ll_masked_fwd_f32: workspace");
+  return dmol_ll_launch<true>(l, x, N, HW, nmix, ll, dll_dl, workspace, mask, sample, filled, (hipStream_t)stream);
 }
 
 extern "C" int lvae_dmol_sample_f32(const float* l, const float* u_mix, const float* u_log, int32_t N, int32_t HW,
@@ -378,9 +492,22 @@ extern "C" int lvae_gaussian_fwd_f32(const float* params, const float* x, const 
   LVAE_REQUIRE(params && N > 0 && P > 0 && C > 0, LVAE_EINVAL, "lvae_gaussian_fwd_f32: bad args");
   LVAE_REQUIRE(!sample || eps, LVAE_EINVAL, "lvae_gaussian_fwd_f32: sample needs eps");
   LVAE_REQUIRE(!x || ll, LVAE_EINVAL, "lvae_gaussian_fwd_f32: x given but ll is null");
-  hipLaunchKernelGGL(gaussian_fwd_kernel, dim3(N), dim3(256), 0, (hipStream_t)stream, params, x, eps, P, C, sample, ll,
-                     dll_dparams);
+  hipLaunchKernelGGL(gaussian_fwd_kernel<false>, dim3(N), dim3(256), 0, (hipStream_t)stream, params, x, eps, P, C, sample, ll,
+                     dll_dparams, (const uint8_t*)nullptr, (float*)nullptr);
   LVAE_LAUNCH_CHECK("gaussian_fwd");
+  return 0;
+}
+
+extern "C" int lvae_gaussian_masked_fwd_f32(const float* params, const float* x, const float* eps, int32_t N, int64_t P, int32_t C,
+                                            float* sample, float* ll, float* dll_dparams, const uint8_t* mask, float* filled,
+                                            void* stream) {
+  LVAE_REQUIRE(params && N > 0 && P > 0 && C > 0, LVAE_EINVAL, "lvae_gaussian_masked_fwd_f32: bad args");
+  LVAE_REQUIRE(mask, LVAE_EINVAL, "lvae_gaussian_masked_fwd_f32: mask is null");
+  LVAE_REQUIRE(x && ll, LVAE_EINVAL, "lvae_gaussian_masked_fwd_f32: x and ll are needed");
+  LVAE_REQUIRE((!sample && !filled) || eps, LVAE_EINVAL, "lvae_gaussian_masked_fwd_f32: sample and filled need eps");
+  hipLaunchKernelGGL(gaussian_fwd_kernel<true>, dim3(N), dim3(256), 0, (hipStream_t)stream, params, x, eps, P, C, sample, ll,
+                     dll_dparams, mask, filled);
+  LVAE_LAUNCH_CHECK("gaussian_masked_fwd");
   return 0;
 }
 
@@ -390,8 +517,42 @@ extern "C" int lvae_discr_logistic_fwd_f32(const float* raw, const float* x, con
   LVAE_REQUIRE(raw && N > 0 && P > 0 && C > 0, LVAE_EINVAL, "lvae_discr_logistic_fwd_f32: bad args");
   LVAE_REQUIRE(!sample || u, LVAE_EINVAL, "lvae_discr_logistic_fwd_f32: sample needs uniforms");
   LVAE_REQUIRE(!x || ll, LVAE_EINVAL, "lvae_discr_logistic_fwd_f32: x given but ll is null");
-  hipLaunchKernelGGL(discr_logistic_fwd_kernel, dim3(N), dim3(256), 0, (hipStream_t)stream, raw, x, u, P, C, mean, logscale,
-                     sample, ll, dll_draw);
+  hipLaunchKernelGGL(discr_logistic_fwd_kernel<false>, dim3(N), dim3(256), 0, (hipStream_t)stream, raw, x, u, P, C, mean, logscale,
+                     sample, ll, dll_draw, (const uint8_t*)nullptr, (float*)nullptr);
   LVAE_LAUNCH_CHECK("discr_logistic_fwd");
+  return 0;
+}
+
+extern "C" int lvae_discr_logistic_masked_fwd_f32(const float* raw, const float* x, const float* u, int32_t N, int64_t P, int32_t C,
+                                                  float* mean, float* logscale, float* sample, float* ll, float* dll_draw,
+                                                  const uint8_t* mask, float* filled, void* stream) {
+  LVAE_REQUIRE(raw && N > 0 && P > 0 && C > 0, LVAE_EINVAL, "lvae_discr_logistic_masked_fwd_f32: bad args");
+  LVAE_REQUIRE(mask, LVAE_EINVAL, "lvae_discr_logistic_masked_fwd_f32: mask is null");
+  LVAE_REQUIRE(x && ll, LVAE_EINVAL, "lvae_discr_logistic_masked_fwd_f32: x and ll are needed");
+  LVAE_REQUIRE((!sample && !filled) || u, LVAE_EINVAL, "lvae_discr_logistic_masked_fwd_f32: sample and filled need uniforms");
+  hipLaunchKernelGGL(discr_logistic_fwd_kernel<true>, dim3(N), dim3(256), 0, (hipStream_t)stream, raw, x, u, P, C, mean, logscale,
+                     sample, ll, dll_draw, mask, filled);
+  LVAE_LAUNCH_CHECK("discr_logistic_masked_fwd");
+  return 0;
+}
+
+extern "C" int lvae_mask_select_f32(const float* a, const float* b, float b_value, const uint8_t* mask, int32_t N, int32_t C, int64_t HW,
+                                    int32_t nchw, float* out, void* stream) {
+  LVAE_REQUIRE(a && mask && out, LVAE_EINVAL, "lvae_mask_select_f32: a, mask or out missing");
+  LVAE_REQUIRE(N > 0 && C > 0 && HW > 0, LVAE_EINVAL, "lvae_mask_select_f32: N %d, C %d, HW %lld", N, C, (long long)HW);
+  LVAE_REQUIRE(HW <= (INT64_MAX >> 3) / ((int64_t)N * C), LVAE_EINVAL, "lvae_mask_select_f32: %d x %d x %lld exceeds 64-bit byte offsets", N, C,
+               (long long)HW);
+  const int64_t total = (int64_t)N * C * HW;
+  const bool v4 = (nchw ? HW % 4 == 0 : total % 4 == 0) && al16(a) && al16_or_null(b) && al16(out);
+  hipStream_t s = (hipStream_t)stream;
+  if (v4) {
+    const int64_t total4 = total / 4;
+    if (nchw) hipLaunchKernelGGL(mask_select_v4_kernel<true>, dim3(grid_for(total4, 256)), dim3(256), 0, s, a, b, b_value, mask, (int64_t)C, HW, total4, out);
+    else hipLaunchKernelGGL(mask_select_v4_kernel<false>, dim3(grid_for(total4, 256)), dim3(256), 0, s, a, b, b_value, mask, (int64_t)C, HW, total4, out);
+  } else {
+    if (nchw) hipLaunchKernelGGL(mask_select_kernel<true>, dim3(grid_for(total, 256)), dim3(256), 0, s, a, b, b_value, mask, (int64_t)C, HW, total, out);
+    else hipLaunchKernelGGL(mask_select_kernel<false>, dim3(grid_for(total, 256)), dim3(256), 0, s, a, b, b_value, mask, (int64_t)C, HW, total, out);
+  }
+  LVAE_LAUNCH_CHECK("mask_select");
   return 0;
 }

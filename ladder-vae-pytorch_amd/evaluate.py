@@ -13,6 +13,8 @@ the absent boilr.eval.BaseOfflineEvaluator / VAEExperimentManager.test_procedure
   * `conditional_samples(model, x, k, K)` — K variations per image that keep its top k latents (LadderVAE.sample_conditional);
   * `interpolations(model, x_a, x_b, T, k, mode)` — T steps between two images in the latents of their top k layers, spherical or linear
     (LadderVAE.interpolate);
+  * `make_mask(kind, frac, shape, seed)` and `inpaintings(model, x, mask, n_iters, init, final)` — a mask of observed pixels on the host,
+    and the images completed under it by the pseudo-Gibbs chain (LadderVAE.inpaint);
   * `image_pass(model, nrows, x, step)` — the trainer's pictures (--ts-img-every): a grid of prior samples and a grid of input /
     reconstruction pairs, formed on the device (images.py), on a noise stream of their own, leaving training untouched.
 
@@ -24,6 +26,11 @@ CLI: python -m lvae_amd.evaluate --synthetic --ll --ll-samples 100 --ps --layer-
      --interp [--interp-layers k ...] [--interp-steps T] [--interp-mode slerp|lerp] writes interp_top<k>.npy (pairs, T + 2, C, H, W) for the
      pairs (2i, 2i + 1) of the first 24 evaluation images: column 0 is x_a, columns 1..T the steps, the last column x_b; with --img-dir
      DIR/interp_top<k>.png (one row per pair). k defaults to the number of layers.
+     --inpaint [--inpaint-mask KIND ...] [--inpaint-frac F] [--inpaint-iters N] [--inpaint-init zeros|mean|noise] [--inpaint-final
+     sample|mean] writes inpaint_<kind>.npy (n, 3, C, H, W) for the first 12 evaluation images: the image, what the model was shown (the
+     missing pixels at 0.5) and the completion; with --img-dir DIR/inpaint_<kind>.png (one row per image). KIND: left, right, top, bottom
+     (that strip is hidden), center (a box), random (each pixel with probability F). One line per kind: the mean squared error on the
+     missing pixels of the initial fill and of the completion, and the mean ll of the observed pixels in the first and the last round.
      --temperature T [T ...] (one value, or one per layer, bottom first) tempers the prior draws of --ps, --cond-samples and --interp.
 """
 import os
@@ -355,6 +362,54 @@ def interpolations(model, x_a, x_b, n_steps=8, n_top_layers=None, mode='slerp', 
         model.train(was_training)
 
 
+MASK_KINDS = ('left', 'right', 'top', 'bottom', 'center', 'random')
+
+
+def make_mask(kind, frac, shape, seed=0):
+    """A mask of OBSERVED pixels on the host: bool, `shape` = (..., H, W), True = observed. `left`, `right`, `top`, `bottom` hide that strip
+    of round(frac * W) columns / round(frac * H) rows; `center` hides the centred round(frac * H) x round(frac * W) box; `random` hides each
+    pixel independently with probability frac, from torch.Generator().manual_seed(seed). ValueError for an unknown kind, a frac outside
+    [0, 1] or a shape of fewer than two dimensions."""
+    if kind not in MASK_KINDS:
+        raise ValueError("mask kind must be one of %s, got %r" % (MASK_KINDS, kind))
+    frac = float(frac)
+    if not 0.0 <= frac <= 1.0:
+        raise ValueError("frac must be in [0, 1], got %r" % (frac,))
+    shape = tuple(int(s) for s in shape)
+    if len(shape) < 2:
+        raise ValueError("shape must end in (H, W), got %s" % (shape,))
+    H, W = shape[-2:]
+    if kind == 'random':
+        return torch.rand(shape, generator=torch.Generator().manual_seed(int(seed))) >= frac
+    mask = torch.ones(shape, dtype=torch.bool)
+    h, w = int(round(frac * H)), int(round(frac * W))
+    if kind == 'left':
+        mask[..., :, :w] = False
+    elif kind == 'right':
+        mask[..., :, W - w:] = False
+    elif kind == 'top':
+        mask[..., :h, :] = False
+    elif kind == 'bottom':
+        mask[..., H - h:, :] = False
+    else:
+        top, left = (H - h) // 2, (W - w) // 2
+        mask[..., top:top + h, left:left + w] = False
+    return mask
+
+
+@torch.no_grad()
+def inpaintings(model, x, mask, n_iters=10, init='zeros', final='sample', use_graph=None):
+    """The images of the NCHW batch x completed where mask (bool or uint8, (B,H,W) or (B,1,H,W); True = observed) hides them
+    (LadderVAE.inpaint) -> (x, shown, completed, ll_observed, first), all on the device: `shown` is what the model was given to look at, x
+    with the missing pixels at 0.5 (a picture for the eye: the chain itself starts from `first`, x with `init` at the missing pixels);
+    ll_observed (n_iters, B). Noise: `model.noise`."""
+    dev = next(model.parameters()).device
+    x, mask = x.to(dev).contiguous().float(), mask.to(dev)
+    out = model.inpaint(x, mask, n_iters=n_iters, init=init, final=final, return_history=True, use_graph=use_graph)
+    m = K.pixel_mask(mask, x.shape[0], x.shape[2], x.shape[3], dev)
+    return x, K.mask_select(x, 0.5, m, True), out['completed'], out['ll_observed'], out['history'][0]
+
+
 @torch.no_grad()
 def inspect_layer_repr(model, n=8):
     """evaluate.py:95-114: for every layer i, n calls of `sample_prior(n, mode_layers=range(i), constant_layers=range(i+1, L))`
@@ -456,6 +511,15 @@ def build_eval_parser():
                    help='the k of --interp (default: the number of layers)')
     p.add_argument('--interp-steps', type=int, default=8, dest='interp_steps', metavar='T', help='steps of a path, both ends included')
     p.add_argument('--interp-mode', choices=('slerp', 'lerp'), default='slerp', dest='interp_mode', help='spherical or linear')
+    p.add_argument('--inpaint', action='store_true', help='complete the hidden part of the evaluation images -> inpaint_<kind>.npy')
+    p.add_argument('--inpaint-mask', nargs='+', default=['left'], dest='inpaint_mask', metavar='KIND',
+                   help='what is hidden: %s' % ', '.join(MASK_KINDS))
+    p.add_argument('--inpaint-frac', type=float, default=0.5, dest='inpaint_frac', metavar='F', help='the hidden share, in (0, 1)')
+    p.add_argument('--inpaint-iters', type=int, default=10, dest='inpaint_iters', metavar='N', help='rounds of the chain')
+    p.add_argument('--inpaint-init', choices=('zeros', 'mean', 'noise'), default='zeros', dest='inpaint_init',
+                   help='the first completion at the missing pixels')
+    p.add_argument('--inpaint-final', choices=('sample', 'mean'), default='sample', dest='inpaint_final',
+                   help="the missing pixels after the last round: the draw, or the likelihood's mean")
     return p
 
 
@@ -479,6 +543,16 @@ def parse_eval_args(argv=None):
         p.error('--interp-layers takes values from 1 to %d (the number of layers), got %s' % (L, args.interp_layers))
     if args.interp_steps < 1:
         p.error('--interp-steps must be at least 1, got %d' % args.interp_steps)
+    if any(k not in MASK_KINDS for k in args.inpaint_mask):
+        p.error('--inpaint-mask takes %s, got %s' % (', '.join(MASK_KINDS), args.inpaint_mask))
+    if not 0.0 < args.inpaint_frac < 1.0:
+        p.error('--inpaint-frac must be inside (0, 1), got %r' % args.inpaint_frac)
+    if args.inpaint_iters < 1:
+        p.error('--inpaint-iters must be at least 1, got %d' % args.inpaint_iters)
+    if args.inpaint_final == 'mean':
+        from .experiment.experiment_manager import DATASETS
+        if (args.likelihood or DATASETS[args.dataset_name][2]) == 'discr_log_mix':
+            p.error("--inpaint-final mean: the discretized logistic mixture has no mean")
     if args.temperature is not None:
         if len(args.temperature) not in (1, L):
             p.error('--temperature takes one value or one per layer (%d), got %d' % (L, len(args.temperature)))
@@ -511,7 +585,7 @@ def main(argv=None):
     if args.img_dir:
         os.makedirs(args.img_dir, exist_ok=True)
     temperature = None if args.temperature is None else (args.temperature[0] if len(args.temperature) == 1 else args.temperature)
-    if args.ll or args.recons or args.cond_samples or args.interp:
+    if args.ll or args.recons or args.cond_samples or args.interp or args.inpaint:
         gen = torch.Generator().manual_seed(args.seed)
         if args.data_npz:
             data = torch.from_numpy(np.load(args.data_npz)['data']).float()
@@ -554,6 +628,23 @@ def main(argv=None):
             np.save('interp_top%d.npy' % k, rows.cpu().numpy())
             if args.img_dir:
                 write_png(os.path.join(args.img_dir, 'interp_top%d.png' % k), image_grid(rows.view(-1, *rows.shape[2:]), nt + 2))
+    if args.inpaint:  # one row per image: the image, what the model was shown, the completion
+        n = min(IMG_GRID_N, int(data.shape[0]))
+        for j, kind in enumerate(args.inpaint_mask):
+            mask = make_mask(kind, args.inpaint_frac, (n,) + tuple(data.shape[2:]), args.seed + j)
+            xin, shown, done, ll_obs, first = inpaintings(model, data[:n], mask, args.inpaint_iters, args.inpaint_init, args.inpaint_final)
+            rows = torch.stack((xin, shown, done), 1).contiguous()
+            np.save('inpaint_%s.npy' % kind, rows.cpu().numpy())
+            if args.img_dir:
+                write_png(os.path.join(args.img_dir, 'inpaint_%s.png' % kind), image_grid(rows.view(-1, *rows.shape[2:]), 3))
+            hidden = (~mask)[:, None].expand_as(data[:n])
+            truth = data[:n].float()[hidden].double()
+            mse0 = float(((first.cpu()[hidden].double() - truth) ** 2).mean()) if truth.numel() else float('nan')
+            mse1 = float(((done.cpu()[hidden].double() - truth) ** 2).mean()) if truth.numel() else float('nan')
+            ll_obs = ll_obs.cpu().double()
+            print('inpaint %s (hidden %.3f, %d rounds): mse on the missing pixels %.5g (initial fill) -> %.5g (completion); '
+                  'll_observed %.5g (first round) -> %.5g (last round)'
+                  % (kind, float((~mask).float().mean()), args.inpaint_iters, mse0, mse1, float(ll_obs[0].mean()), float(ll_obs[-1].mean())))
     if not args.img_dir:
         return
     # the reference's pictures, after everything above so that the arrays do not depend on --img-dir

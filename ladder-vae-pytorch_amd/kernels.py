@@ -1174,6 +1174,115 @@ def discr_logistic_fwd(raw, x, u, need_grad):
     return mean, ls, sample, ll, dll
 
 
+def pixel_mask(mask, N, H, W, device):
+    """The (N,H,W) uint8 tensor the masked kernels read (non-zero = observed) from a bool or uint8 mask of shape (N,H,W) or (N,1,H,W) on
+    `device`; no copy for a contiguous one (bool is reinterpreted). ValueError for another shape, dtype or device."""
+    if not torch.is_tensor(mask) or mask.dtype not in (torch.bool, torch.uint8):
+        raise ValueError("mask must be a bool or uint8 tensor, got %s" % (mask.dtype if torch.is_tensor(mask) else type(mask).__name__))
+    if tuple(mask.shape) not in ((N, H, W), (N, 1, H, W)):
+        raise ValueError("mask must be (%d, %d, %d) or (%d, 1, %d, %d), got %s" % (N, H, W, N, H, W, tuple(mask.shape)))
+    if mask.device != torch.device(device):
+        raise ValueError("mask is on %s, the images on %s" % (mask.device, device))
+    mask = mask.reshape(N, H, W).contiguous()
+    return mask.view(torch.uint8) if mask.dtype == torch.bool else mask
+
+
+def _filled_buf(filled, like):
+    """The `filled` output of a masked head: a new tensor shaped like x, or the caller's (x itself: in-place completion)."""
+    if filled is None:
+        return torch.empty_like(like)
+    if tuple(filled.shape) != tuple(like.shape) or not filled.is_contiguous():
+        raise _C.LvaeHipError("filled must be contiguous and shaped like x %s, got %s" % (tuple(like.shape), tuple(filled.shape)))
+    return filled
+
+
+def _chk_masked(x, mask, N, H, W):
+    if x is None:
+        raise ValueError("a mask needs the image x it belongs to")
+    if mask.dtype != torch.uint8 or tuple(mask.shape) != (N, H, W) or not mask.is_contiguous():
+        raise ValueError("mask must be a contiguous uint8 (%d, %d, %d) tensor (kernels.pixel_mask makes one), got %s %s"
+                         % (N, H, W, mask.dtype, tuple(mask.shape)))
+
+
+def bernoulli_masked_fwd(logits, x, u, mask, need_grad, filled=None):
+    """bernoulli_fwd on the observed pixels: mask (N,H,W) uint8, non-zero = observed. Returns mean, mode, sample, ll, dll | None, filled
+    (x where observed, the sample where missing; `filled` may be x)."""
+    N, H, W, Cn = logits.shape
+    _chk_masked(x, mask, N, H, W)
+    mean, mode, sample = torch.empty_like(logits), torch.empty_like(logits), torch.empty_like(logits)
+    ll = torch.empty((N,), dtype=torch.float32, device=logits.device)
+    dll = torch.empty_like(logits) if need_grad else None
+    filled = _filled_buf(filled, x)
+    call('lvae_bernoulli_masked_fwd_f32', ptr(logits), ptr(x), ptr(u), N, H * W * Cn, Cn, ptr(mean), ptr(mode), ptr(sample), ptr(ll),
+         ptr(dll), ptr(mask), ptr(filled), stream_ptr())
+    return mean, mode, sample, ll, dll, filled
+
+
+def dmol_ll_masked_fwd(l, x, mask, sample, need_grad, filled=None):
+    """dmol_ll_fwd on the observed pixels; sample: dmol_sample(l, ...) of the same parameters. Returns ll (N,), dll_dl | None, filled."""
+    N, H, W, Cp = l.shape
+    _chk_masked(x, mask, N, H, W)
+    ll = torch.empty((N,), dtype=torch.float32, device=l.device)
+    dl = torch.empty_like(l) if need_grad else None
+    filled = _filled_buf(filled, x)
+    ws = workspace(_C.load().lvae_dmol_workspace(N, H * W), l.device)
+    call('lvae_dmol_ll_masked_fwd_f32', ptr(l), ptr(x), N, H * W, Cp // 10, ptr(ll), ptr(dl), ws.data_ptr(), ws.numel(), ptr(mask),
+         ptr(sample), ptr(filled), stream_ptr())
+    return ll, dl, filled
+
+
+def gaussian_masked_fwd(params, x, eps, mask, need_grad, filled=None):
+    """gaussian_fwd on the observed pixels. Returns sample, ll, dll_dparams | None, filled."""
+    N, H, W, C2 = params.shape
+    Cn = C2 // 2
+    _chk_masked(x, mask, N, H, W)
+    sample = torch.empty((N, H, W, Cn), dtype=torch.float32, device=params.device)
+    ll = torch.empty((N,), dtype=torch.float32, device=params.device)
+    dll = torch.empty_like(params) if need_grad else None
+    filled = _filled_buf(filled, x)
+    call('lvae_gaussian_masked_fwd_f32', ptr(params), ptr(x), ptr(eps), N, H * W, Cn, ptr(sample), ptr(ll), ptr(dll), ptr(mask),
+         ptr(filled), stream_ptr())
+    return sample, ll, dll, filled
+
+
+def discr_logistic_masked_fwd(raw, x, u, mask, need_grad, filled=None):
+    """discr_logistic_fwd on the observed pixels. Returns mean, logscale, sample, ll, dll_draw | None, filled."""
+    N, H, W, C2 = raw.shape
+    Cn = C2 // 2
+    _chk_masked(x, mask, N, H, W)
+    mk = lambda: torch.empty((N, H, W, Cn), dtype=torch.float32, device=raw.device)
+    mean, ls, sample = mk(), mk(), mk()
+    ll = torch.empty((N,), dtype=torch.float32, device=raw.device)
+    dll = torch.empty_like(raw) if need_grad else None
+    filled = _filled_buf(filled, x)
+    call('lvae_discr_logistic_masked_fwd_f32', ptr(raw), ptr(x), ptr(u), N, H * W, Cn, ptr(mean), ptr(ls), ptr(sample), ptr(ll), ptr(dll),
+         ptr(mask), ptr(filled), stream_ptr())
+    return mean, ls, sample, ll, dll, filled
+
+
+def mask_select(a, b, mask, nchw, out=None):
+    """out = mask ? a : b, exactly. a: contiguous float32 (N,C,H,W) when nchw else (N,H,W,C); b: a tensor of a's shape or a number (that
+    value everywhere); mask (N,H,W) uint8, non-zero = take a. out: None (a new tensor), or a or b themselves (in place)."""
+    if nchw:
+        N, Cn, H, W = a.shape
+    else:
+        N, H, W, Cn = a.shape
+    if mask.dtype != torch.uint8 or tuple(mask.shape) != (N, H, W) or not mask.is_contiguous():
+        raise ValueError("mask must be a contiguous uint8 (%d, %d, %d) tensor, got %s %s" % (N, H, W, mask.dtype, tuple(mask.shape)))
+    tensor_b = torch.is_tensor(b)
+    if tensor_b and tuple(b.shape) != tuple(a.shape):
+        raise ValueError("a and b must have one shape, got %s and %s" % (tuple(a.shape), tuple(b.shape)))
+    if not a.is_contiguous() or (tensor_b and not b.is_contiguous()):
+        raise _C.LvaeHipError("mask_select: a and b must be contiguous")
+    if out is None:
+        out = torch.empty_like(a)
+    elif tuple(out.shape) != tuple(a.shape) or not out.is_contiguous():
+        raise _C.LvaeHipError("mask_select: out must be contiguous and shaped like a")
+    call('lvae_mask_select_f32', ptr(a, (torch.float32,)), ptr(b, (torch.float32,)) if tensor_b else None, 0.0 if tensor_b else float(b),
+         ptr(mask, (torch.uint8,)), N, Cn, H * W, int(bool(nchw)), ptr(out, (torch.float32,)), stream_ptr())
+    return out
+
+
 def scale_per_sample(a, g):
     N = a.shape[0]
     out = torch.empty_like(a)

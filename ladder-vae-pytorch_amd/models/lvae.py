@@ -11,7 +11,8 @@ Differences by design (not by omission):
   * every arithmetic op is a hand-written gfx950 kernel from liblvae_hip.so; the model refuses to run on CPU;
   * parameters live in one flat arena (arena.py); their gradients are accumulated in place by the wgrad kernels;
   * noise comes from `self.noise` (noise.PhiloxNoise on device; noise.TapeNoise to replay the reference's draws);
-  * engine-only methods beside the reference's: `sample_conditional`, `encode`, `decode`, `interpolate` (forward only).
+  * engine-only methods beside the reference's: `sample_conditional`, `encode`, `decode`, `interpolate`, `inpaint` (forward only), and
+    the `mask` keyword of forward(): the ELBO of the observed pixels of a partly observed image.
 
 The boilr helpers the reference imports (pad/crop, Interpolate, free_bits_kl) are restated — parity unpinned
 (SURVEY.md §8c).
@@ -240,8 +241,16 @@ class LadderVAE(nn.Module):
     # ------------------------------------------------------------------------------------------------------------
     # reference API
     # ------------------------------------------------------------------------------------------------------------
-    def forward(self, x, n_samples=1):
-        """n_samples: engine-only keyword — K > 1 draws K importance samples per image (engine.forward_pass(iw_samples=K) trains on their
+    def forward(self, x, n_samples=1, mask=None, mask_fill=0.0):
+        """mask, mask_fill: engine-only keywords — the ELBO of a partly observed image. mask: bool or uint8, (B,H,W) or (B,1,H,W), on the
+        device of x; non-zero = observed, one flag per pixel for all its colours. The encoder sees x where observed and mask_fill (a finite
+        number, or a (B,C,H,W) tensor) where missing: one select launch in front of the pad; x itself is read nowhere else, so what it holds
+        under a hidden pixel changes no output bit. `ll`, and through it the loss and every gradient, counts the observed pixels only (the
+        masked likelihood kernels: the gradient at a missing pixel's parameters is exactly zero). The dict gains a 13th key, `out_filled`
+        (NCHW): x where observed, the likelihood's sample where missing. ValueError for a mask of the wrong shape, dtype or device, a
+        non-finite mask_fill, and n_samples > 1 with a mask. mask=None issues exactly the launches of a call without the keyword.
+
+        n_samples: engine-only keyword — K > 1 draws K importance samples per image (engine.forward_pass(iw_samples=K) trains on their
         bound). The bottom-up pass is a deterministic function of the image and runs ONCE, on the B images; each level's output is repeated
         for the K samples (ops.RepeatSamplesFn, whose backward sums their gradients) and the top-down pass, final_top_down, the crop and the
         likelihood run on K * B rows, sample-major (row k * B + b). The dict keeps its 12 keys: `ll`, `kl_sep`, `z`, `kl_spatial` and `out_*`
@@ -253,9 +262,18 @@ class LadderVAE(nn.Module):
         n_samples = int(n_samples)
         if n_samples < 1:
             raise ValueError("n_samples must be at least 1, got %d" % n_samples)
+        if mask is not None:
+            if n_samples > 1:
+                raise ValueError("a mask together with n_samples > 1 is not supported")
+            if x.dim() != 4:
+                raise ValueError("x must be (B, C, H, W), got %s" % (tuple(x.shape),))
+            mask = K.pixel_mask(mask, x.shape[0], x.shape[2], x.shape[3], x.device)
+            mask_fill = self._mask_fill(mask_fill, x, 'mask_fill')
         self._begin(x, batch=x.shape[0], n_samples=n_samples)
         img_size = x.size()[2:]
         x = x.contiguous().float()
+        if mask is not None:
+            x = K.mask_select(x, mask_fill, mask, True)   # from here on the truth under a hidden pixel is gone
         # NCHW image -> centred zero pad -> NHWC, one kernel (models/lvae.py:176, 317-325)
         x_pad = K.pad_crop(x, True, self.get_padded_size(x.size()), False)
         x_nhwc = x_pad if tuple(img_size) == tuple(x_pad.shape[1:3]) else K.pad_crop(x, True, img_size, False)
@@ -268,7 +286,10 @@ class LadderVAE(nn.Module):
         out, td_data = self._topdown(bu_values)
         out = ops.CropFn.apply(out, tuple(int(s) for s in img_size)) if tuple(out.shape[1:3]) != tuple(img_size) else out
         out = self._mark(out, 'likelihood.')
-        ll, likelihood_info = self.likelihood(out, x_nhwc, self.noise)
+        if mask is None:
+            ll, likelihood_info = self.likelihood(out, x_nhwc, self.noise)
+        else:
+            ll, likelihood_info = self.likelihood(out, x_nhwc, self.noise, mask=mask)
 
         kl_ln = ops.StackFn.apply(*td_data['kl'])  # (L, N)
         kl_sep, kl_avg_layerwise, kl_loss, kl = ops.KLBookFn.apply(kl_ln, float(self.free_bits))
@@ -279,7 +300,7 @@ class LadderVAE(nn.Module):
             params = {k: _nchw(v) for k, v in params.items()}
         else:
             params = _nchw(params)
-        return {
+        res = {
             'll': ll,
             'z': [_nchw(z) for z in td_data['z']],
             'kl': kl,
@@ -293,6 +314,25 @@ class LadderVAE(nn.Module):
             'out_sample': _nchw(likelihood_info['sample']),
             'likelihood_params': params,
         }
+        if mask is not None:
+            res['out_filled'] = _nchw(likelihood_info['filled'])
+        return res
+
+    @staticmethod
+    def _mask_fill(fill, x, what):
+        """A fill for the missing pixels of the NCHW batch x: a finite number (returned as a float) or a tensor of x's shape on its device
+        (returned contiguous float32). ValueError otherwise."""
+        if torch.is_tensor(fill) and fill.dim() > 0:
+            if tuple(fill.shape) != tuple(x.shape) or fill.device != x.device:
+                raise ValueError("%s must be a number or a %s tensor on %s, got %s on %s" % (what, tuple(x.shape), x.device, tuple(fill.shape), fill.device))
+            return fill.contiguous().float()
+        try:
+            fill = float(fill)
+        except (TypeError, ValueError):
+            raise ValueError("%s must be a number or a %s tensor, got %r" % (what, tuple(x.shape), fill))
+        if not np.isfinite(fill):
+            raise ValueError("%s must be finite, got %r" % (what, fill))
+        return fill
 
     def _bottomup(self, x):
         stem, _, block = self.first_bottom_up
@@ -632,6 +672,112 @@ class LadderVAE(nn.Module):
         res = self._pictures(out, x_a.shape[2:], zs)
         res.update(z_a=[_nchw(v) for v in z_a], z_b=[_nchw(v) for v in z_b], t=t)
         return res
+
+    INPAINT_INITS = ('zeros', 'mean', 'noise')
+
+    @torch.no_grad()
+    def inpaint(self, x, mask, n_iters=10, init='zeros', final='sample', return_history=False, use_graph=None):
+        """Engine-only: complete the missing pixels of the NCHW batch x by the pseudo-Gibbs chain of Rezende, Mohamed & Wierstra 2014
+        (appendix F). mask as in forward(): non-zero = observed. Eval mode under no_grad; the training flag is restored.
+
+        The completion is kept NHWC. It starts as x where observed and `init` where missing: 'zeros', 'mean' (0.5), 'noise' (one uniform
+        [0, 1) draw of x's shape, NCHW on a tape, from the model's noise source) or a (B,C,H,W) tensor. One round pads it, runs the
+        bottom-up pass, the top-down pass and the crop, and then the masked likelihood head with `filled` written over the completion: the
+        observed pixels keep x, the missing ones take a draw from p(x|z). What x holds under a hidden pixel is never read. final='mean'
+        replaces the missing pixels by the head's mean of the last round (one select launch); ValueError for the logistic mixture, which
+        has none.
+
+        Noise: begin / the 'noise' draw if any / end once, then per round begin, the draws of forward() in its order, end.
+        use_graph=None: as in evaluate.iw_log_likelihood — with PhiloxNoise and n_iters >= 8 two rounds run eagerly (they count), one round
+        is captured as a hipGraph and replayed for the rest, with a device copy of that round's ll (and history frame) between replays and
+        no host wait; a noise tape always runs eagerly. Eager and replayed runs from one noise position agree bit for bit.
+
+        Returns {'completed' (B,C,H,W): observed pixels bit for bit those of x; 'll_observed' (n_iters, B): each round's masked ll, of the
+        completion that ENTERED the round; with return_history 'history' (n_iters + 1, B, C, H, W), frame 0 the initial fill (final='mean'
+        changes `completed` only)}."""
+        if not x.is_cuda:
+            raise K._C.LvaeHipError("LadderVAE (HIP engine) needs a GPU tensor; got %s" % x.device)
+        if x.dim() != 4:
+            raise ValueError("x must be (B, C, H, W), got %s" % (tuple(x.shape),))
+        n_iters = int(n_iters)
+        if n_iters < 1:
+            raise ValueError("n_iters must be at least 1, got %d" % n_iters)
+        if final not in ('sample', 'mean'):
+            raise ValueError("final must be 'sample' or 'mean', got %r" % (final,))
+        if final == 'mean' and isinstance(self.likelihood, DiscretizedLogisticMixLikelihood):
+            raise ValueError("final='mean': the discretized logistic mixture has no mean")
+        B, C, H, W = (int(s) for s in x.shape)
+        dev = x.device
+        mask = K.pixel_mask(mask, B, H, W, dev)
+        if isinstance(init, str):
+            if init not in self.INPAINT_INITS:
+                raise ValueError("init must be one of %s or a (B, C, H, W) tensor, got %r" % (self.INPAINT_INITS, init))
+        else:
+            init = self._mask_fill(init, x, 'init')
+            if not torch.is_tensor(init):
+                raise ValueError("init must be one of %s or a (B, C, H, W) tensor" % (self.INPAINT_INITS,))
+        if use_graph is None:
+            use_graph = isinstance(self.noise, PhiloxNoise) and n_iters >= 8
+        elif use_graph and not isinstance(self.noise, PhiloxNoise):
+            raise ValueError("use_graph needs on-device noise (PhiloxNoise): a noise tape runs eagerly")
+        use_graph = bool(use_graph) and n_iters > 2   # (the two eager rounds are all there is otherwise)
+        was_training = self.training
+        self.eval()
+        try:
+            self._begin(x)
+            img_size, padded = (H, W), self.get_padded_size(x.size())
+            cur = K.pad_crop(x.contiguous().float(), True, img_size, False)   # NHWC
+            if torch.is_tensor(init):
+                fill = K.pad_crop(init, True, img_size, False)
+            elif init == 'noise':
+                fill = self.noise.uniform((B, H, W, C), 0.0, 1.0, dev, channel_last=False)
+            else:
+                fill = 0.5 if init == 'mean' else 0.0
+            K.mask_select(cur, fill, mask, False, out=cur)
+            self.noise.end()
+            ll_obs = torch.empty((n_iters, B), dtype=torch.float32, device=dev)
+            hist = torch.empty((n_iters + 1, B, C, H, W), dtype=torch.float32, device=dev) if return_history else None
+            if hist is not None:
+                hist[0].copy_(K.pad_crop(cur, False, img_size, True))
+
+            def one_round():
+                self.noise.begin(dev)                 # every round: same call sites, next RNG step
+                out, _ = self._topdown(self._bottomup(K.pad_crop(cur, False, padded, False)))
+                if tuple(out.shape[1:3]) != img_size:
+                    out = ops.CropFn.apply(out, img_size)
+                ll, info = self.likelihood(out, cur, self.noise, mask=mask, filled_out=cur)
+                frame = K.pad_crop(cur, False, img_size, True) if hist is not None else None
+                self.noise.end()
+                return ll, info, frame
+
+            def keep(r, ll, frame):                   # device copies in stream order; the host does not wait
+                ll_obs[r].copy_(ll)
+                if hist is not None:
+                    hist[r + 1].copy_(frame)
+
+            if use_graph:
+                for r in range(2):                    # eager: allocator warm-up (these count as rounds)
+                    ll, info, frame = one_round()
+                    keep(r, ll, frame)
+                torch.cuda.synchronize()
+                graph = torch.cuda.CUDAGraph()
+                with torch.cuda.graph(graph, capture_error_mode='thread_local'):
+                    ll, info, frame = one_round()
+                for r in range(2, n_iters):
+                    graph.replay()
+                    keep(r, ll, frame)
+            else:
+                for r in range(n_iters):
+                    ll, info, frame = one_round()
+                    keep(r, ll, frame)
+            if final == 'mean':
+                K.mask_select(cur, info['mean'].contiguous(), mask, False, out=cur)
+            res = {'completed': K.pad_crop(cur, False, img_size, True), 'll_observed': ll_obs}
+            if hist is not None:
+                res['history'] = hist
+            return res
+        finally:
+            self.train(was_training)
 
     def get_top_prior_param_shape(self, n_imgs=1):
         """models/lvae.py:364-372."""

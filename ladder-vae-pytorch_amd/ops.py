@@ -576,6 +576,77 @@ class DmolFn(Function):
         return K.scale_per_sample(dl, _c(g_ll)), None
 
 
+# Masked counterparts of the four heads (a likelihood on the observed pixels; kernels.*_masked_fwd): mask (N,H,W) uint8, non-zero = observed.
+# The saved dll is the masked one (+0.0 at every parameter of a missing pixel), so the backward is that of the unmasked head. `filled` (x
+# where observed, the head's draw where missing) is the last output and carries no gradient; filled_out, when given, is the buffer it is
+# written to: x itself completes x in place (LadderVAE.inpaint, under no_grad).
+def _filled_out(ctx, filled_out):
+    if filled_out is not None:
+        ctx.mark_dirty(filled_out)
+
+
+class BernoulliMaskedFn(Function):
+    @staticmethod
+    def forward(ctx, logits, x, u, mask, filled_out=None):
+        _filled_out(ctx, filled_out)
+        mean, mode, sample, ll, dll, filled = K.bernoulli_masked_fwd(logits, x, u, mask, True, filled_out)
+        ctx.save_for_backward(dll)
+        ctx.mark_non_differentiable(mode, sample, filled)
+        return ll, mean, mode, sample, filled
+
+    @staticmethod
+    def backward(ctx, g_ll, g_mean, g_mode, g_sample, g_filled):
+        (dll,) = ctx.saved_tensors
+        return K.scale_per_sample(dll, _c(g_ll)), None, None, None, None
+
+
+class GaussianMaskedFn(Function):
+    @staticmethod
+    def forward(ctx, params, x, eps, mask, filled_out=None):
+        _filled_out(ctx, filled_out)
+        sample, ll, dll, filled = K.gaussian_masked_fwd(params, x, eps, mask, True, filled_out)
+        ctx.save_for_backward(dll)
+        ctx.mark_non_differentiable(sample, filled)
+        return ll, sample, filled
+
+    @staticmethod
+    def backward(ctx, g_ll, g_sample, g_filled):
+        (dll,) = ctx.saved_tensors
+        return K.scale_per_sample(dll, _c(g_ll)), None, None, None, None
+
+
+class DiscrLogisticMaskedFn(Function):
+    @staticmethod
+    def forward(ctx, raw, x, u, mask, filled_out=None):
+        _filled_out(ctx, filled_out)
+        mean, ls, sample, ll, dll, filled = K.discr_logistic_masked_fwd(raw, x, u, mask, True, filled_out)
+        ctx.save_for_backward(dll)
+        ctx.mark_non_differentiable(mean, ls, sample, filled)
+        return ll, mean, ls, sample, filled
+
+    @staticmethod
+    def backward(ctx, g_ll, g_mean, g_ls, g_sample, g_filled):
+        (dll,) = ctx.saved_tensors
+        return K.scale_per_sample(dll, _c(g_ll)), None, None, None, None
+
+
+class DmolMaskedFn(Function):
+    """sample: K.dmol_sample of the same parameters (the head's draw), from which the missing pixels of `filled` are taken."""
+
+    @staticmethod
+    def forward(ctx, l, x, mask, sample, filled_out=None):
+        _filled_out(ctx, filled_out)
+        ll, dl, filled = K.dmol_ll_masked_fwd(l, x, mask, sample, True, filled_out)
+        ctx.save_for_backward(dl)
+        ctx.mark_non_differentiable(filled)
+        return ll, filled
+
+    @staticmethod
+    def backward(ctx, g_ll, g_filled):
+        (dl,) = ctx.saved_tensors
+        return K.scale_per_sample(dl, _c(g_ll)), None, None, None, None
+
+
 class SegmentMarkFn(Function):
     """Identity in forward. Its backward runs after every backward node of the model segment that starts at this tensor has been
     issued: the deferred (grouped) weight gradients of that segment are flushed and the gradient exchange is told the segment's slice
