@@ -821,6 +821,26 @@ int lvae_batch_gather_f32(const void* src, int32_t src_kind, int32_t src_hwc, in
                           int64_t base, int32_t n_rows, float* out, void* stream);
 
 /* ------------------------------------------------------------------------------------------------------------
+ * Nearest neighbours of samples in a table held in HBM (csrc/neighbours.hip; neighbours.NeighbourIndex). Evaluation only.
+ * ---------------------------------------------------------------------------------------------------------- */
+/* For each of the Q query rows (float32 [Q][D], contiguous) the k rows of `table` ([N][D] contiguous; table_kind LVAE_FEED_U8, an element
+ * meaning (float)v / 255.0f as in lvae_batch_gather_f32, or LVAE_FEED_F32) of least squared L2 distance:
+ *   dist = sum_i (q_i - t_i)^2, the difference taken first, accumulated in fp32 in one order per D (never |q|^2 + |t|^2 - 2 q.t), so a
+ *   query equal to a row gives exactly 0.0f, and a pair's bits depend on the two rows, D and table_kind alone: not on Q, N, k, exclude,
+ *   or the position and alignment of either row.
+ * index_out / dist_out [Q][k]: ascending by (distance, row), so equal distances go to the lower row; a NaN distance ranks after +inf,
+ * then by row. With fewer than k eligible rows the trailing slots hold (-1, +inf). exclude: NULL, or device int32 [Q], a row this query
+ * skips (an entry outside [0, N), -1 by convention, skips nothing and is never used as an address). The element order inside a row is
+ * the caller's business as long as queries and table agree. Limits: 1 <= k <= 32, Q >= 1, 1 <= N <= INT32_MAX, D >= 1, Q*k <= INT32_MAX.
+ * workspace: lvae_nn_l2_workspace(Q, N, k) bytes (0 for sizes outside the limits), 8-byte aligned, owned by the caller; it holds the k
+ * best of each group of table rows per query and stays far below Q*N floats. Two launches, no float atomics, no host wait. Nothing is
+ * launched or written on an error: LVAE_EINVAL for a null queries, table, index_out or dist_out, a size outside the limits or an unknown
+ * kind; LVAE_EWORKSPACE for a missing or short workspace; LVAE_EALIGN for a workspace off 8 bytes or a float32 / int32 buffer off 4. */
+size_t lvae_nn_l2_workspace(int32_t Q, int64_t N, int32_t k);
+int lvae_nn_l2_f32(const float* queries, int32_t Q, const void* table, int32_t table_kind, int64_t N, int64_t D, const int32_t* exclude,
+                   int32_t k, int32_t* index_out, float* dist_out, void* workspace, size_t workspace_bytes, void* stream);
+
+/* ------------------------------------------------------------------------------------------------------------
  * Optimiser and norms over the flat parameter arena — torch.optim.Adamax at experiment_manager.py:76-81 and the
  * L2 loop at experiment_manager.py:346-350.
  * ---------------------------------------------------------------------------------------------------------- */

@@ -217,6 +217,8 @@ SIGNATURES = {
     'lvae_image_border_count_f32': (C.c_int, [_P, _I, _P, _I, _I, _I, _I, _I, _F, _P, _P]),
     'lvae_image_grid_u8': (C.c_int, [_P, _I, _P, _I, _I, _I, _I, _I, _I, _P, _F, _P, _L, _P]),
     'lvae_batch_gather_f32': (C.c_int, [_P, _I, _I, _I, _I, _I, _I, _P, _P, _I, _I, _I, _L, _I, _P, _P]),
+    'lvae_nn_l2_workspace': (_Z, [_I, _L, _I]),
+    'lvae_nn_l2_f32': (C.c_int, [_P, _I, _P, _I, _L, _L, _P, _I, _P, _P, _P, _Z, _P]),
     'lvae_iw_logmeanexp_f32': (C.c_int, [_P, _I, _I, _P, _P]),
     'lvae_adamax_step_f32': (C.c_int, [_P, _P, _P, _P, _P, _L, _F, _F, _F, _F, _F, _P, _P, _P]),
     'lvae_adamax_ema_step_f32': (C.c_int, [_P, _P, _P, _P, _P, _L, _F, _F, _F, _F, _F, _P, _P, _P, _F, _P]),

@@ -17,9 +17,6 @@ struct FeedArgs {
   int f32, hwc, vec;
 };
 
-// torch's u8.float().div_(255.0): an IEEE division, never a multiplication by a rounded reciprocal
-__device__ __forceinline__ float byte_to_unit(unsigned v) { return __fdiv_rn((float)v, 255.0f); }
-
 // Element e (CHW order) of image `img`, from either layout and either storage type.
 __device__ __forceinline__ float feed_elem(const FeedArgs& a, size_t img, int e) {
   const int c = e / a.HW, hw = e - c * a.HW;

@@ -110,6 +110,10 @@ __device__ __forceinline__ void kernarg_warmup() {
 #endif
 }
 
+// A uint8 image value as float32 in [0, 1], as torch's u8.float().div_(255.0): an IEEE division, never a multiplication by a rounded
+// reciprocal. The batch gather (batch_feed.hip) and the neighbour search (neighbours.hip) read the same table with it.
+__device__ __forceinline__ float byte_to_unit(unsigned v) { return __fdiv_rn((float)v, 255.0f); }
+
 constexpr float kSeluAlpha = 1.6732632423543772848170429916717f;
 constexpr float kSeluScale = 1.0507009873554804934193349852946f;
 

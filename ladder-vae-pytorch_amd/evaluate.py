@@ -15,6 +15,8 @@ the absent boilr.eval.BaseOfflineEvaluator / VAEExperimentManager.test_procedure
     (LadderVAE.interpolate);
   * `make_mask(kind, frac, shape, seed)` and `inpaintings(model, x, mask, n_iters, init, final)` — a mask of observed pixels on the host,
     and the images completed under it by the pseudo-Gibbs chain (LadderVAE.inpaint);
+  * `nearest_neighbours(model, table, queries, k, space)` — query images beside their nearest table images, in the pixels or in the latents
+    of the top k layers (neighbours.py), and how close samples lie to the table against how close held-out images do;
   * `image_pass(model, nrows, x, step)` — the trainer's pictures (--ts-img-every): a grid of prior samples and a grid of input /
     reconstruction pairs, formed on the device (images.py), on a noise stream of their own, leaving training untouched.
 
@@ -31,6 +33,11 @@ CLI: python -m lvae_amd.evaluate --synthetic --ll --ll-samples 100 --ps --layer-
      missing pixels at 0.5) and the completion; with --img-dir DIR/inpaint_<kind>.png (one row per image). KIND: left, right, top, bottom
      (that strip is hidden), center (a box), random (each pixel with probability F). One line per kind: the mean squared error on the
      missing pixels of the initial fill and of the completion, and the mean ll of the observed pixels in the first and the last round.
+     --nn [--nn-k K] [--nn-space pixel|latent] [--nn-layers k] [--nn-table FILE.npz | --nn-table-size N] writes, for 12 prior samples and
+     for the first 12 evaluation images, nn_<space>_<samples|heldout>.npy (12, 1 + K, C, H, W): column 0 the query, then its K nearest
+     table images (exact squared L2 search on the device, neighbours.NeighbourIndex), with nn_<...>_index.npy and nn_<...>_dist.npy
+     (12, K); with --img-dir DIR/nn_<...>.png (one row per query). One line: neighbours.closeness_summary over 144 samples and up to
+     1000 evaluation images. The table is key 'data' of FILE.npz, or N synthetic images drawn from seed + 1.
      --temperature T [T ...] (one value, or one per layer, bottom first) tempers the prior draws of --ps, --cond-samples and --interp.
 """
 import os
@@ -444,6 +451,38 @@ def reconstructions(model, x):
         model.train(was_training)
 
 
+@torch.no_grad()
+def nearest_neighbours(model, table, queries, k, space='pixel', n_top_layers=None, shown=12, batch_size=256):
+    """Each query image beside its k nearest images of `table` (a device tensor (N, C, H, W), uint8 or float32, searched where it lies).
+    queries: {name: NCHW images, host or device}. space 'pixel': squared L2 distance between images; 'latent': between the posterior means
+    of the top n_top_layers layers (neighbours.latent_features of table and queries). Returns {name: {'rows' (n, 1 + k, C, H, W): the first
+    `shown` queries, each followed by its neighbours, nearest first; 'index' (n, k); 'dist' (n, k); 'nearest': every query's nearest
+    distance}, 'summary': neighbours.closeness_summary of the first two query sets' nearest distances}."""
+    from .neighbours import NeighbourIndex, closeness_summary, latent_features
+    if space not in ('pixel', 'latent'):
+        raise ValueError("space must be 'pixel' or 'latent', got %r" % (space,))
+    pixels = NeighbourIndex(table)
+    dev = table.device
+    if space == 'latent':
+        feats = torch.cat([latent_features(model, pixels.rows(torch.arange(lo, min(lo + batch_size, pixels.N), device=dev)), n_top_layers,
+                                           batch_size) for lo in range(0, pixels.N, batch_size)])
+        search = NeighbourIndex(feats)
+    else:
+        search = pixels
+    res = {}
+    for name, x in queries.items():
+        x = x.to(dev).contiguous().float()
+        q = latent_features(model, x, n_top_layers, batch_size) if space == 'latent' else x
+        index, dist = search.query(q, k)
+        n = min(int(shown), int(x.shape[0]))
+        rows = torch.cat((x[:n].unsqueeze(1), pixels.rows(index[:n])), 1).contiguous()
+        res[name] = {'rows': rows, 'index': index[:n], 'dist': dist[:n], 'nearest': dist[:, 0]}
+    names = list(queries)
+    if len(names) >= 2:
+        res['summary'] = closeness_summary(res[names[0]]['nearest'], res[names[1]]['nearest'])
+    return res
+
+
 IMAGE_NOISE_TAG = 0x1A6E5      # the picture noise stream's seed is the model's seed with these bits flipped
 IMAGE_NOISE_STRIDE = 1 << 20   # and its counter starts at step * this: the pictures of two steps never share a draw
 
@@ -520,7 +559,27 @@ def build_eval_parser():
                    help='the first completion at the missing pixels')
     p.add_argument('--inpaint-final', choices=('sample', 'mean'), default='sample', dest='inpaint_final',
                    help="the missing pixels after the last round: the draw, or the likelihood's mean")
+    p.add_argument('--nn', action='store_true',
+                   help='prior samples and evaluation images beside their nearest table images -> nn_<space>_<samples|heldout>.npy')
+    p.add_argument('--nn-k', type=int, default=7, dest='nn_k', metavar='K', help='neighbours per query, 1 to %d' % K.NN_MAX_K)
+    p.add_argument('--nn-space', choices=('pixel', 'latent'), default='pixel', dest='nn_space',
+                   help='where the distance is taken: the pixels, or the posterior means of the top --nn-layers layers')
+    p.add_argument('--nn-layers', type=int, default=None, dest='nn_layers', metavar='k',
+                   help='the top layers of --nn-space latent (default: the number of layers)')
+    p.add_argument('--nn-table', type=str, default='', dest='nn_table', metavar='FILE.npz',
+                   help="the images searched: key 'data', uint8 or float (N, C, H, W); default: a seeded synthetic set")
+    p.add_argument('--nn-table-size', type=int, default=4096, dest='nn_table_size', metavar='N',
+                   help='images of the synthetic table (drawn from seed + 1) when there is no --nn-table')
     return p
+
+
+def _nn_table_shape(path):
+    """(N, C, H, W) of the 'data' array of an .npz without reading the array (the .npy header inside the archive)."""
+    import zipfile
+    with zipfile.ZipFile(path) as z, z.open('data.npy') as f:
+        version = np.lib.format.read_magic(f)
+        shape, _, _ = np.lib.format.read_array_header_1_0(f) if version == (1, 0) else np.lib.format.read_array_header_2_0(f)
+    return tuple(int(s) for s in shape)
 
 
 def parse_eval_args(argv=None):
@@ -558,6 +617,25 @@ def parse_eval_args(argv=None):
             p.error('--temperature takes one value or one per layer (%d), got %d' % (L, len(args.temperature)))
         if any(not 0.0 <= t < float('inf') for t in args.temperature):
             p.error('--temperature takes finite values >= 0, got %s' % args.temperature)
+    if not 1 <= args.nn_k <= K.NN_MAX_K:
+        p.error('--nn-k takes values from 1 to %d, got %d' % (K.NN_MAX_K, args.nn_k))
+    if args.nn_layers is None:
+        args.nn_layers = L
+    elif not 1 <= args.nn_layers <= L:
+        p.error('--nn-layers takes values from 1 to %d (the number of layers), got %d' % (L, args.nn_layers))
+    if args.nn_table_size < 1:
+        p.error('--nn-table-size must be at least 1, got %d' % args.nn_table_size)
+    if args.nn and args.nn_table:
+        from .experiment.experiment_manager import DATASETS
+        try:
+            shape = _nn_table_shape(args.nn_table)
+        except (OSError, KeyError, ValueError) as e:
+            p.error("--nn-table %s: no readable 'data' array (%s)" % (args.nn_table, e))
+        if len(shape) != 4 or shape[0] < 1:
+            p.error("--nn-table: 'data' must be (N, C, H, W), got %s" % (shape,))
+        color_ch, img_size, _ = DATASETS[args.dataset_name]
+        if args.nn_space == 'latent' and shape[1:] != (color_ch,) + tuple(img_size):
+            p.error('--nn-space latent: the table holds images of %s, the model encodes %s' % (shape[1:], (color_ch,) + tuple(img_size)))
     return args
 
 
@@ -585,7 +663,7 @@ def main(argv=None):
     if args.img_dir:
         os.makedirs(args.img_dir, exist_ok=True)
     temperature = None if args.temperature is None else (args.temperature[0] if len(args.temperature) == 1 else args.temperature)
-    if args.ll or args.recons or args.cond_samples or args.interp or args.inpaint:
+    if args.ll or args.recons or args.cond_samples or args.interp or args.inpaint or args.nn:
         gen = torch.Generator().manual_seed(args.seed)
         if args.data_npz:
             data = torch.from_numpy(np.load(args.data_npz)['data']).float()
@@ -645,6 +723,28 @@ def main(argv=None):
             print('inpaint %s (hidden %.3f, %d rounds): mse on the missing pixels %.5g (initial fill) -> %.5g (completion); '
                   'll_observed %.5g (first round) -> %.5g (last round)'
                   % (kind, float((~mask).float().mean()), args.inpaint_iters, mse0, mse1, float(ll_obs[0].mean()), float(ll_obs[-1].mean())))
+    if args.nn:  # one row per query: the query, then its K nearest table images, nearest first
+        from .data import device_storage
+        from .neighbours import closeness_line
+        if args.nn_table:
+            table = torch.from_numpy(np.load(args.nn_table)['data'])
+        else:
+            table = synthetic_batch(exp, args.nn_table_size, torch.Generator().manual_seed(args.seed + 1))
+        if tuple(table.shape[1:]) != tuple(data.shape[1:]):
+            raise SystemExit('--nn: the table holds images of %s, the queries are %s' % (tuple(table.shape[1:]), tuple(data.shape[1:])))
+        table = device_storage(table)[0].to(exp.device)
+        samples = prior_samples(model, IMG_GRID_N ** 2, temperature)
+        res = nearest_neighbours(model, table, {'samples': samples, 'heldout': data[:1000]}, args.nn_k, args.nn_space, args.nn_layers,
+                                 shown=IMG_GRID_N)
+        for name in ('samples', 'heldout'):
+            stem = 'nn_%s_%s' % (args.nn_space, name)
+            np.save(stem + '.npy', res[name]['rows'].cpu().numpy())
+            np.save(stem + '_index.npy', res[name]['index'].cpu().numpy())
+            np.save(stem + '_dist.npy', res[name]['dist'].cpu().numpy())
+            if args.img_dir:
+                rows = res[name]['rows']
+                write_png(os.path.join(args.img_dir, stem + '.png'), image_grid(rows.view(-1, *rows.shape[2:]).contiguous(), 1 + args.nn_k))
+        print(closeness_line(args.nn_space, res['summary']))
     if not args.img_dir:
         return
     # the reference's pictures, after everything above so that the arrays do not depend on --img-dir

@@ -1684,3 +1684,30 @@ def batch_gather(table, channels_last, out, index=None, cursor=None, steps_per_e
          H, W, ptr(index, (torch.int32,)), ptr(cursor, (torch.int64,)), int(steps_per_epoch), int(global_batch), int(lo), int(base), n,
          ptr(out, (torch.float32,)), stream_ptr())
     return out
+
+
+NN_MAX_K = 32
+
+
+def nn_l2(queries, table, k, exclude=None):
+    """The k rows of `table` ((N, D) contiguous uint8, a value meaning v / 255, or float32) nearest to each row of `queries` ((Q, D)
+    contiguous float32) by squared L2 distance -> (index int32 (Q, k), dist float32 (Q, k)), ascending by (distance, row); slots without
+    an eligible row hold (-1, +inf). exclude: None, or a device int32 tensor (Q,) naming a row each query skips (-1: none). The distance
+    is sum (q - t)^2 with the difference taken first: a query equal to a row gives exactly 0, and a pair's bits do not depend on Q, N, k
+    or exclude (lvae_nn_l2_f32). Two launches on the current stream, no host wait."""
+    pq, pt = ptr(queries, (torch.float32,)), ptr(table, (torch.uint8, torch.float32))   # (CPU tensors are refused here)
+    if queries.dim() != 2 or table.dim() != 2 or queries.shape[1] != table.shape[1] or not (queries.is_contiguous() and table.is_contiguous()):
+        raise _C.LvaeHipError("nn_l2: queries (Q, D) and table (N, D) must be contiguous and share D, got %s strides %s and %s strides %s"
+                              % (tuple(queries.shape), queries.stride(), tuple(table.shape), table.stride()))
+    Q, D = (int(s) for s in queries.shape)
+    N = int(table.shape[0])
+    if not 1 <= int(k) <= NN_MAX_K:
+        raise ValueError("k must be between 1 and %d, got %r" % (NN_MAX_K, k))
+    if exclude is not None and (exclude.dtype != torch.int32 or tuple(exclude.shape) != (Q,) or not exclude.is_contiguous()):
+        raise _C.LvaeHipError("nn_l2: exclude must be a contiguous int32 tensor of shape (%d,), got %s %s" % (Q, exclude.dtype, tuple(exclude.shape)))
+    index = torch.empty((Q, int(k)), dtype=torch.int32, device=queries.device)
+    dist = torch.empty((Q, int(k)), dtype=torch.float32, device=queries.device)
+    ws = workspace(_C.load().lvae_nn_l2_workspace(Q, N, int(k)), queries.device)
+    call('lvae_nn_l2_f32', pq, Q, pt, _C.FEED_U8 if table.dtype == torch.uint8 else _C.FEED_F32, N, D, ptr(exclude, (torch.int32,)), int(k),
+         ptr(index, (torch.int32,)), ptr(dist, (torch.float32,)), ws.data_ptr(), ws.numel(), stream_ptr())
+    return index, dist
