@@ -47,6 +47,30 @@ import torch
 
 from . import kernels as K
 from . import ops
+from .passes import eval_mode, replay_loop
+
+
+def _test_bottom_up(model, x):
+    """Eval-mode bottom-up of one NCHW batch (no noise drawn; sample independent, so once per batch) -> (bottom-up values, NHWC image
+    for the likelihood)."""
+    model._begin(x)
+    bu_values, x_nhwc, _ = model._encode_image(x)
+    model.noise.end()
+    return bu_values, x_nhwc
+
+
+def _elbo_sample(model, bu_values, x_nhwc, zero, latent_stats=None):
+    """One top-down sample of an evaluation pass: noise.begin, top-down pass, crop, likelihood, KL bookkeeping -> (elbo_sep, ll, kl_sep,
+    kl_avg), per image. The caller folds them into its running state (iw_online or eval_online: they accumulate in different precisions)
+    and then calls model.noise.end(). With latent_stats (a latent.LatentStats) every stochastic layer also folds its p and q parameters
+    into it; the noise drawn is the same either way."""
+    model.noise.begin(x_nhwc.device)                 # every sample: same call sites, next RNG step
+    out, td = model._topdown(bu_values, latent_stats=latent_stats)
+    ll, _ = model.likelihood(model._crop(out, x_nhwc.shape[1:3]), x_nhwc, model.noise)
+    kl_ln = ops.StackFn.apply(*td['kl'])
+    kl_sep, kl_avg, _ = K.kl_bookkeeping_fwd(kl_ln, float(model.free_bits))
+    elbo_sep, _ = K.elbo_loss_fwd(ll, kl_sep, zero, 1.0)
+    return elbo_sep, ll, kl_sep, kl_avg
 
 
 @torch.no_grad()
@@ -54,61 +78,30 @@ def iw_log_likelihood(model, x, n_samples, use_graph=None):
     """Returns (iw_bound (N,), elbo_mean (N,)): the S-sample importance-weighted bound and the mean single-sample ELBO.
 
     The bottom-up pass runs once; one sample = top-down pass + likelihood + KL bookkeeping + an ONLINE update of the per-image
-    (max, sum exp, sum) state. With on-device Philox noise that sample is captured once as a hipGraph and replayed (the RNG
-    step counter is advanced inside the graph): ~1.5 k launches x S without host work, which is what makes S = 1000 practical.
+    (max, sum exp, sum) state. With on-device Philox noise that sample is captured once as a hipGraph and replayed (passes.replay_loop;
+    the RNG step counter is advanced inside the graph): ~1.5 k launches x S without host work, which is what makes S = 1000 practical.
     use_graph=None: graph when the noise source is PhiloxNoise and S >= 8; a replayed noise tape (parity tests) runs eagerly."""
     from .noise import PhiloxNoise
-    was_training = model.training
-    model.eval()
-    try:
+    with eval_mode(model):
         if not x.is_cuda:
             raise K._C.LvaeHipError("iw_log_likelihood needs a GPU tensor")
-        model._begin(x)
-        img_size = tuple(int(s) for s in x.shape[2:])
-        x = x.contiguous().float()
-        x_pad = K.pad_crop(x, True, model.get_padded_size(x.size()), False)
-        x_nhwc = x_pad if img_size == tuple(x_pad.shape[1:3]) else K.pad_crop(x, True, img_size, False)
-        bu_values = model._bottomup(x_pad)           # once: sample independent in eval mode
-        model.noise.end()
+        bu_values, x_nhwc = _test_bottom_up(model, x)
         N, dev = x.shape[0], x.device
         state = torch.empty((3, N), dtype=torch.float32, device=dev)
         zero = torch.zeros(1, device=dev)
         K.iw_online(state, 0)
 
         def one_sample():
-            model.noise.begin(dev)                   # every sample: same call sites, next RNG step
-            out, td = model._topdown(bu_values)
-            if tuple(out.shape[1:3]) != img_size:
-                out = ops.CropFn.apply(out, img_size)
-            ll, _ = model.likelihood(out, x_nhwc, model.noise)
-            kl_ln = ops.StackFn.apply(*td['kl'])
-            kl_sep, _, _ = K.kl_bookkeeping_fwd(kl_ln, float(model.free_bits))
-            elbo_sep, _ = K.elbo_loss_fwd(ll, kl_sep, zero, 1.0)
-            K.iw_online(state, 1, elbo=elbo_sep)
+            K.iw_online(state, 1, elbo=_elbo_sample(model, bu_values, x_nhwc, zero)[0])
             model.noise.end()
 
         if use_graph is None:
             use_graph = isinstance(model.noise, PhiloxNoise) and n_samples >= 8
-        done = 0
-        if use_graph:
-            for _ in range(2):                        # eager: allocator warm-up (these count as samples)
-                one_sample()
-            done = 2
-            torch.cuda.synchronize()
-            graph = torch.cuda.CUDAGraph()
-            with torch.cuda.graph(graph, capture_error_mode='thread_local'):
-                one_sample()
-            for _ in range(done, n_samples):
-                graph.replay()
-        else:
-            for _ in range(n_samples):
-                one_sample()
+        replay_loop(one_sample, n_samples, use_graph)
         iw = torch.empty((N,), dtype=torch.float32, device=dev)
         mean = torch.empty((N,), dtype=torch.float32, device=dev)
         K.iw_online(state, 2, S=n_samples, iw=iw, mean=mean)
         return iw, mean
-    finally:
-        model.train(was_training)
 
 
 def reduce_eval_sums(tot, process_group=None):
@@ -155,29 +148,9 @@ class _EvalWeights:
         return False
 
 
-def _test_bottom_up(model, x):
-    """Eval-mode bottom-up of one NCHW batch (no noise drawn) -> (bottom-up values, NHWC image for the likelihood)."""
-    model._begin(x)
-    img_size = tuple(int(s) for s in x.shape[2:])
-    x_pad = K.pad_crop(x, True, model.get_padded_size(x.size()), False)
-    x_nhwc = x_pad if img_size == tuple(x_pad.shape[1:3]) else K.pad_crop(x, True, img_size, False)
-    bu_values = model._bottomup(x_pad)
-    model.noise.end()
-    return bu_values, x_nhwc
-
-
 def _test_sample(model, bu_values, x_nhwc, state, zero, latent_stats=None):
-    """One top-down sample + likelihood + KL bookkeeping, folded into the per-image state (lvae_eval_online_f32). With latent_stats (a
-    latent.LatentStats) every stochastic layer also folds its p and q parameters into it; the noise drawn is the same either way."""
-    model.noise.begin(x_nhwc.device)
-    out, td = model._topdown(bu_values, latent_stats=latent_stats)
-    if tuple(out.shape[1:3]) != tuple(x_nhwc.shape[1:3]):
-        out = ops.CropFn.apply(out, tuple(x_nhwc.shape[1:3]))
-    ll, _ = model.likelihood(out, x_nhwc, model.noise)
-    kl_ln = ops.StackFn.apply(*td['kl'])
-    kl_sep, kl_avg, _ = K.kl_bookkeeping_fwd(kl_ln, float(model.free_bits))
-    elbo_sep, _ = K.elbo_loss_fwd(ll, kl_sep, zero, 1.0)
-    K.eval_online(state, model.n_layers, 1, elbo_sep, ll, kl_sep, kl_avg)
+    """_elbo_sample, folded into the per-image state of a test pass (lvae_eval_online_f32)."""
+    K.eval_online(state, model.n_layers, 1, *_elbo_sample(model, bu_values, x_nhwc, zero, latent_stats))
     model.noise.end()
 
 
@@ -280,10 +253,7 @@ def test_pass(model, batches, n_samples, noise=None, process_group=None, use_gra
     totals = torch.zeros(5 + L, dtype=torch.float64, device=dev)
     if latent_stats is not None:
         latent_stats.reset()
-    train_noise, was_training = model.noise, model.training
-    model.eval()
-    model.noise = noise
-    try:
+    with eval_mode(model, noise):
         if use_graph:
             plans = model.__dict__.setdefault('_test_graphs', {})
             for x in batches:
@@ -309,9 +279,6 @@ def test_pass(model, batches, n_samples, noise=None, process_group=None, use_gra
                         latent_stats.count(x.shape[0])
                     K.eval_totals(state, L, n_samples, totals)
             torch.cuda.current_stream(dev).synchronize()   # (the registered scratch buffers of this pass may go now)
-    finally:
-        model.noise = train_noise
-        model.train(was_training)
     tot = reduce_eval_sums(totals, process_group).cpu().tolist()
     n = tot[4]
     res = {'elbo/elbo': tot[1] / n, 'elbo/recons': tot[2] / n, 'elbo/kl': tot[3] / n}
@@ -330,12 +297,8 @@ def test_pass(model, batches, n_samples, noise=None, process_group=None, use_gra
 @torch.no_grad()
 def prior_samples(model, n_imgs, temperature=None):
     """evaluate.py:34-36: unconditional samples, (n, C, H, W) in [0, 1]. temperature: as in LadderVAE.sample_prior (None: the plain call)."""
-    was_training = model.training
-    model.eval()
-    try:
+    with eval_mode(model):
         return model.sample_prior(n_imgs, temperature=temperature)
-    finally:
-        model.train(was_training)
 
 
 @torch.no_grad()
@@ -343,14 +306,10 @@ def conditional_samples(model, x, n_top_layers, n_samples, temperature=None, use
     """K = n_samples variations of every image of the NCHW batch x that keep its top n_top_layers latents (LadderVAE.sample_conditional,
     eval mode) -> (x, pictures), both on the device: pictures (K * B, C, H, W), sample-major, the likelihood's mean where it has one and
     its sample otherwise (the rule of `reconstructions`). Noise comes from `model.noise`."""
-    was_training = model.training
-    model.eval()
-    try:
+    with eval_mode(model):
         x = x.to(next(model.parameters()).device).contiguous().float()
         out = model.sample_conditional(x, n_top_layers, n_samples, temperature=temperature, use_mode=use_mode)
         return x, (out['mean'] if out['mean'] is not None else out['sample'])
-    finally:
-        model.train(was_training)
 
 
 @torch.no_grad()
@@ -358,15 +317,11 @@ def interpolations(model, x_a, x_b, n_steps=8, n_top_layers=None, mode='slerp', 
     """The path between the images of the NCHW batches x_a and x_b in the latents of the top n_top_layers layers (LadderVAE.interpolate at
     the posterior means, eval mode) -> (x_a, x_b, pictures), all on the device: pictures (T * B, C, H, W), step-major, the likelihood's mean
     where it has one and its sample otherwise (the rule of `reconstructions`). Noise comes from `model.noise`."""
-    was_training = model.training
-    model.eval()
-    try:
+    with eval_mode(model):
         dev = next(model.parameters()).device
         x_a, x_b = x_a.to(dev).contiguous().float(), x_b.to(dev).contiguous().float()
         out = model.interpolate(x_a, x_b, n_steps=n_steps, n_top_layers=n_top_layers, mode=mode, temperature=temperature)
         return x_a, x_b, (out['mean'] if out['mean'] is not None else out['sample'])
-    finally:
-        model.train(was_training)
 
 
 MASK_KINDS = ('left', 'right', 'top', 'bottom', 'center', 'random')
@@ -423,9 +378,7 @@ def inspect_layer_repr(model, n=8):
     concatenated — each call (one row of the reference's image grid) draws the layers above i once for its whole batch, samples
     layer i per image and takes the mode below, so a row shows what layer i encodes. Returns a list of L tensors (n*n, C, H, W);
     the reference writes each as a PNG grid with nrow = n (images.image_grid + write_png; the CLI does so under --img-dir)."""
-    was_training = model.training
-    model.eval()
-    try:
+    with eval_mode(model):
         out = []
         for i in range(model.n_layers):
             mode_layers = range(i)
@@ -433,22 +386,16 @@ def inspect_layer_repr(model, n=8):
             rows = [model.sample_prior(n, mode_layers=mode_layers, constant_layers=constant_layers) for _ in range(n)]
             out.append(torch.cat(rows))
         return out
-    finally:
-        model.train(was_training)
 
 
 @torch.no_grad()
 def reconstructions(model, x):
     """One eval-mode forward pass of the NCHW batch x -> (x, recon), both NCHW on the device: recon is the likelihood's mean where it has
     one and its sample otherwise (the logistic mixture has no mean), boilr's order of preference. Noise comes from `model.noise`."""
-    was_training = model.training
-    model.eval()
-    try:
+    with eval_mode(model):
         x = x.to(next(model.parameters()).device).contiguous().float()
         out = model(x)
         return x, (out['out_mean'] if out['out_mean'] is not None else out['out_sample'])
-    finally:
-        model.train(was_training)
 
 
 @torch.no_grad()
@@ -506,11 +453,8 @@ def image_pass(model, nrows, x=None, step=0, optimizer=None):
     noise.seed = (model.noise.seed if isinstance(model.noise, PhiloxNoise) else 0) ^ IMAGE_NOISE_TAG
     noise.step = torch.full((1,), int(step) * IMAGE_NOISE_STRIDE, dtype=torch.int64, device=dev)
     nrows = int(nrows)
-    train_noise, was_training = model.noise, model.training
-    model.eval()
-    model.noise = noise
     keep = []
-    try:
+    with eval_mode(model, noise):
         with _EvalWeights(keep):
             sample_grid = image_grid(model.sample_prior(nrows * nrows), nrows)
             recon_grid = None
@@ -519,9 +463,6 @@ def image_pass(model, nrows, x=None, step=0, optimizer=None):
                 xin, rec = reconstructions(model, x[:n])
                 recon_grid = image_grid(xin, nrows, second=rec)
         torch.cuda.current_stream(dev).synchronize()   # (the registered scratch buffers of this pass may go now)
-    finally:
-        model.noise = train_noise
-        model.train(was_training)
     return sample_grid, recon_grid
 
 

@@ -14,10 +14,16 @@ Differences by design (not by omission):
   * engine-only methods beside the reference's: `sample_conditional`, `encode`, `decode`, `interpolate`, `inpaint` (forward only), and
     the `mask` keyword of forward(): the ELBO of the observed pixels of a partly observed image.
 
+Every pass, the reference's and the engine's own, is built from four private pieces: `_encode_image` (image -> pad -> NHWC -> bottom-up),
+`_walk` (THE top-down loop: one call site of TopDownLayer, driven by a per-layer list of `LayerZ` that says where each z comes from, with
+the one seam where rows are repeated for K samples, then `_final_top_down`), `_pictures` (crop -> likelihood without a target -> NCHW
+dict) and, for the loops that run a round many times, passes.replay_loop. The public methods check arguments and build the list.
+
 The boilr helpers the reference imports (pad/crop, Interpolate, free_bits_kl) are restated — parity unpinned
 (SURVEY.md §8c).
 """
 import numbers
+from collections import namedtuple
 
 import numpy as np
 import torch
@@ -30,12 +36,25 @@ from ..lib.likelihoods import (BernoulliLikelihood, DiscretizedLogisticLikelihoo
                                GaussianLikelihood)
 from ..lib.nn import BatchNorm2dParams, Conv2dParams, Placeholder, act_name
 from ..noise import PhiloxNoise
+from ..passes import eval_mode, replay_loop
 from .lvae_layers import BottomUpDeterministicResBlock, BottomUpLayer, TopDownDeterministicResBlock, TopDownLayer
 
 
 def _nchw(t):
     """NHWC engine tensor -> logical NCHW view (no copy)."""
     return None if t is None else t.permute(0, 3, 1, 2)
+
+
+def _nchw_params(params):
+    """The `params` entry of a likelihood's info (a tensor, or a dict of them) as NCHW views."""
+    return {k: _nchw(v) for k, v in params.items()} if isinstance(params, dict) else _nchw(params)
+
+
+# Where one layer's z comes from, for LadderVAE._walk. posterior: inference mode (needs the layer's bottom-up value), else generative mode.
+# use_mode: the mean instead of a draw. constant: force_constant_output. temperature: of a prior draw (None: the plain draw; not with
+# use_mode or forced). forced: an NHWC z to take instead (forced_latent). last: the walk stops behind this layer: the layers below launch
+# nothing (their entries are not read) and the tail is not run.
+LayerZ = namedtuple('LayerZ', 'posterior use_mode constant temperature forced last', defaults=(False, False, False, None, None, False))
 
 
 def layer_temperatures(L, value):
@@ -270,22 +289,15 @@ class LadderVAE(nn.Module):
             mask = K.pixel_mask(mask, x.shape[0], x.shape[2], x.shape[3], x.device)
             mask_fill = self._mask_fill(mask_fill, x, 'mask_fill')
         self._begin(x, batch=x.shape[0], n_samples=n_samples)
-        img_size = x.size()[2:]
-        x = x.contiguous().float()
         if mask is not None:
-            x = K.mask_select(x, mask_fill, mask, True)   # from here on the truth under a hidden pixel is gone
-        # NCHW image -> centred zero pad -> NHWC, one kernel (models/lvae.py:176, 317-325)
-        x_pad = K.pad_crop(x, True, self.get_padded_size(x.size()), False)
-        x_nhwc = x_pad if tuple(img_size) == tuple(x_pad.shape[1:3]) else K.pad_crop(x, True, img_size, False)
-
-        bu_values = self._bottomup(x_pad)
+            x = K.mask_select(x.contiguous().float(), mask_fill, mask, True)   # from here on the truth under a hidden pixel is gone
+        bu_values, x_nhwc, img_size = self._encode_image(x)
         if n_samples > 1:
-            # behind the fan-out of _bottomup, in front of the segment marks of _topdown: the gradient fan-in stays as it is
+            # behind the fan-out of _bottomup, in front of the segment marks of _walk: the gradient fan-in stays as it is
             bu_values = [ops.RepeatSamplesFn.apply(b, n_samples) for b in bu_values]
             x_nhwc = K.repeat_samples(x_nhwc, n_samples)
         out, td_data = self._topdown(bu_values)
-        out = ops.CropFn.apply(out, tuple(int(s) for s in img_size)) if tuple(out.shape[1:3]) != tuple(img_size) else out
-        out = self._mark(out, 'likelihood.')
+        out = self._mark(self._crop(out, img_size), 'likelihood.')
         if mask is None:
             ll, likelihood_info = self.likelihood(out, x_nhwc, self.noise)
         else:
@@ -295,11 +307,6 @@ class LadderVAE(nn.Module):
         kl_sep, kl_avg_layerwise, kl_loss, kl = ops.KLBookFn.apply(kl_ln, float(self.free_bits))
         self.noise.end()
 
-        params = likelihood_info['params']
-        if isinstance(params, dict):
-            params = {k: _nchw(v) for k, v in params.items()}
-        else:
-            params = _nchw(params)
         res = {
             'll': ll,
             'z': [_nchw(z) for z in td_data['z']],
@@ -312,7 +319,7 @@ class LadderVAE(nn.Module):
             'out_mean': _nchw(likelihood_info['mean']),
             'out_mode': _nchw(likelihood_info['mode']),
             'out_sample': _nchw(likelihood_info['sample']),
-            'likelihood_params': params,
+            'likelihood_params': _nchw_params(likelihood_info['params']),
         }
         if mask is not None:
             res['out_filled'] = _nchw(likelihood_info['filled'])
@@ -348,6 +355,26 @@ class LadderVAE(nn.Module):
             bu_values.append(x_td)
         return bu_values
 
+    def _encode_image(self, x, nchw=True, need_image=True):
+        """The image prelude of every pass that looks at pictures: x (NCHW; with nchw=False an NHWC engine tensor) contiguous float32 ->
+        centred zero pad to the padded size, as NHWC, one kernel (models/lvae.py:176, 317-325) -> bottom-up pass. Returns (bu_values,
+        x_nhwc, img_size): x_nhwc is the unpadded NHWC image the likelihood compares with (the padded tensor itself when nothing was
+        padded, else one more copy launch; None with need_image=False, which issues no launch for it), img_size = (H, W). Between
+        _begin and noise.end()."""
+        x = x.contiguous().float()
+        img_size = tuple(int(s) for s in (x.shape[2:] if nchw else x.shape[1:3]))
+        x_pad = K.pad_crop(x, nchw, self.get_padded_size(img_size), False)
+        x_nhwc = None
+        if need_image:
+            x_nhwc = x_pad if img_size == tuple(x_pad.shape[1:3]) else K.pad_crop(x, nchw, img_size, False)
+        return self._bottomup(x_pad), x_nhwc, img_size
+
+    @staticmethod
+    def _crop(out, img_size):
+        """NHWC centre crop to img_size; no launch when it has that size already."""
+        img_size = tuple(int(s) for s in img_size)
+        return out if tuple(out.shape[1:3]) == img_size else ops.CropFn.apply(out, img_size)
+
     def bottomup_pass(self, x):
         """models/lvae.py:216-227. x: padded image (N,C,Hp,Wp); returns the list of per-level NCHW feature maps."""
         self._begin(x)
@@ -356,92 +383,77 @@ class LadderVAE(nn.Module):
         self.noise.end()  # the next call draws fresh dropout masks
         return out
 
-    def _topdown(self, bu_values=None, n_img_prior=None, mode_layers=None, constant_layers=None, forced_latent=None, latent_stats=None):
-        """latent_stats: engine-only keyword — a latent.LatentStats whose slot i the stochastic block of layer i folds its (mu | logvar)
-        tensors into (inference mode only); None issues exactly the launches of a pass without it."""
-        if mode_layers is None:
-            mode_layers = []
-        if constant_layers is None:
-            constant_layers = []
-        prior_experiment = len(mode_layers) > 0 or len(constant_layers) > 0
-        inference_mode = bu_values is not None
-        if inference_mode != (n_img_prior is None):
-            raise RuntimeError("Number of images for top-down generation has to be given if and only if we're "
-                               "not doing inference")
-        if inference_mode and prior_experiment:
-            raise RuntimeError("Prior experiments (e.g. sampling from mode) are not compatible with inference mode")
-        z = [None] * self.n_layers
-        kl = [None] * self.n_layers
-        kl_spatial = [None] * self.n_layers
-        if forced_latent is None:
-            forced_latent = [None] * self.n_layers
+    def _walk(self, plan, bu_values=None, rows=None, noise=None, mats=None, latent_stats=None, n_samples=1):
+        """The one top-down walk, layers L-1 .. 0 and then final_top_down; every public method builds `plan` and calls it.
+
+        plan: L LayerZ entries indexed like z_dims (layer 0 is the bottom), saying where each layer's z comes from. A posterior layer runs
+        in inference mode on bu_values[i], by the code path of forward(); every other layer runs in generative mode on `rows` rows and takes
+        its noise from `noise` (default self.noise). An entry with `last` is the one way to stop: the walk ends behind that layer,
+        everything below it launches nothing, the tail is not run and `out` is None (encode(): with all L layers, layer 0 is the last).
+        mats: an optional (lp_mat, kl_mat) pair of [L][rows] matrices; the stochastic kernel of layer i writes its per-sample log p(z)
+        and KL straight into rows i, and `logprob_p` is their sum of row means (models/lvae.py:301; a metric, without a graph). Without
+        it the kernel wrapper allocates and `logprob_p` is None: the walk invents no matrices for a caller that has none.
+        latent_stats: a latent.LatentStats whose slot i the stochastic block of a posterior layer i folds its (mu | logvar) tensors
+        into; None issues exactly the launches of a pass without it.
+        n_samples = K: the one seam where what the posterior layers hand down, on B rows, is repeated to the K * B rows of what follows,
+        sample-major (K.repeat_samples): in front of the first prior layer below a posterior one, or in front of final_top_down when
+        every layer is posterior. A plan without a posterior layer has no seam (the top layer broadcasts its prior over `rows` itself),
+        and K = 1 launches nothing.
+        Segment marks: the walk always calls _mark at every layer and in front of the tail, whoever calls it; _mark is the identity
+        without a gradient tracker or without grad, so the sampling paths issue nothing for it and forward() keeps its graph node for node.
+
+        Returns (out NHWC, {'z', 'kl', 'kl_spatial': per layer, None where the layer has none or did not run; 'logprob_p'})."""
+        L = self.n_layers
+        noise = self.noise if noise is None else noise
+        z, kl, kl_spatial = [None] * L, [None] * L, [None] * L
+        data = {'z': z, 'kl': kl, 'kl_spatial': kl_spatial, 'logprob_p': None}
         out = None
-        # per-layer, per-sample log p(z) and KL are written by the stochastic kernels straight into the rows of two [L][N] matrices
-        n_rows = bu_values[0].shape[0] if inference_mode else int(n_img_prior)
-        dev = next(self.parameters()).device
-        lp_mat = torch.empty((self.n_layers, n_rows), dtype=torch.float32, device=dev)
-        kl_mat = torch.empty((self.n_layers, n_rows), dtype=torch.float32, device=dev)
-        for i in reversed(range(self.n_layers)):
-            try:
-                bu_value = bu_values[i]
-            except TypeError:
-                bu_value = None
-            fl = forced_latent[i]
-            if fl is not None:
-                fl = fl.permute(0, 2, 3, 1).contiguous()
+        for i in reversed(range(L)):
+            src = plan[i]
+            bu_value = bu_values[i] if src.posterior else None
+            if n_samples > 1 and not src.posterior and i + 1 < L and plan[i + 1].posterior:
+                out = K.repeat_samples(out, n_samples)
             if out is not None:
                 out = self._mark(out, 'top_down_layers.%d.' % i)
             elif bu_value is not None:
                 bu_value = self._mark(bu_value, 'top_down_layers.%d.' % i)
-            out, _, aux = self.top_down_layers[i](out, skip_connection_input=out, inference_mode=inference_mode,
-                                                  bu_value=bu_value, n_img_prior=n_img_prior, use_mode=i in mode_layers,
-                                                  force_constant_output=i in constant_layers, forced_latent=fl,
-                                                  noise=self.noise, rows=(lp_mat[i], kl_mat[i]),
-                                                  stats=None if latent_stats is None else latent_stats.slot(i))
-            z[i] = aux['z']
-            kl[i] = aux['kl_samplewise']
-            kl_spatial[i] = aux['kl_spatial']
-        with torch.no_grad():  # models/lvae.py:301: sum over layers of the batch-mean log p(z); a metric (returned without a graph)
-            logprob_p = K.sum_of_row_means(lp_mat).view(())
-        out = self._mark(out, 'final_top_down.')
-        for mod in self.final_top_down:
-            if isinstance(mod, Placeholder):
-                out = ops.UpsampleFn.apply(out)
-            else:
-                out = mod(out, self.noise)
-        return out, {'z': z, 'kl': kl, 'kl_spatial': kl_spatial, 'logprob_p': logprob_p}
-
-    def _topdown_mixed(self, bu_values, n_top, n_imgs, n_samples, temps, mode_layers=(), constant_layers=(), use_mode=False):
-        """The sampling sibling of _topdown (which stays all-posterior or all-prior): layers L-1 .. L-n_top run in inference mode on the
-        n_imgs rows of bu_values, by the code path of forward() (with use_mode at the posterior mean, drawing nothing); what they hand down
-        is repeated to n_samples * n_imgs rows, sample-major (K.repeat_samples; no launch for one sample), and layers L-n_top-1 .. 0 draw
-        from their prior there at temps[i] (None: the plain draw). With n_top = L the repeat sits in front of final_top_down; with
-        n_top = 0 nothing is handed down and the top layer broadcasts its prior over the n_samples * n_imgs rows itself.
-        Returns (out NHWC with n_samples * n_imgs rows, [z NHWC per layer])."""
-        L = self.n_layers
-        rows = int(n_samples) * int(n_imgs)
-        z = [None] * L
-        out = None
-        for i in reversed(range(L)):
-            if i >= L - n_top:
-                out, _, aux = self.top_down_layers[i](out, skip_connection_input=out, inference_mode=True, bu_value=bu_values[i],
-                                                      use_mode=use_mode, noise=self.noise)
-            else:
-                if out is not None and i == L - n_top - 1 and n_samples > 1:
-                    out = K.repeat_samples(out, n_samples)
-                in_mode = i in mode_layers
-                out, _, aux = self.top_down_layers[i](out, skip_connection_input=out, inference_mode=False, n_img_prior=rows,
-                                                      use_mode=in_mode, force_constant_output=i in constant_layers,
-                                                      noise=self.noise, temperature=None if in_mode else temps[i])
-            z[i] = aux['z']
-        if n_top == L and n_samples > 1:
+            out, _, aux = self.top_down_layers[i](out, skip_connection_input=out, inference_mode=src.posterior, bu_value=bu_value,
+                                                  n_img_prior=None if src.posterior else rows, use_mode=src.use_mode,
+                                                  force_constant_output=src.constant, forced_latent=src.forced, noise=noise,
+                                                  rows=None if mats is None else (mats[0][i], mats[1][i]),
+                                                  stats=None if latent_stats is None else latent_stats.slot(i),
+                                                  temperature=src.temperature)
+            z[i], kl[i], kl_spatial[i] = aux['z'], aux['kl_samplewise'], aux['kl_spatial']
+            if src.last:
+                return None, data
+        if mats is not None:
+            with torch.no_grad():
+                data['logprob_p'] = K.sum_of_row_means(mats[0]).view(())
+        if n_samples > 1 and plan[0].posterior:
             out = K.repeat_samples(out, n_samples)
+        return self._final_top_down(self._mark(out, 'final_top_down.'), noise), data
+
+    def _final_top_down(self, out, noise):
         for mod in self.final_top_down:
-            if isinstance(mod, Placeholder):
-                out = ops.UpsampleFn.apply(out)
-            else:
-                out = mod(out, self.noise)
-        return out, z
+            out = ops.UpsampleFn.apply(out) if isinstance(mod, Placeholder) else mod(out, noise)
+        return out
+
+    def _topdown(self, bu_values=None, n_img_prior=None, mode_layers=None, constant_layers=None, forced_latent=None, latent_stats=None):
+        """The reference's pass (models/lvae.py:229-315) as a plan for _walk: all-posterior on NHWC bu_values or all-prior on n_img_prior
+        rows, forced_latent NCHW per layer or None, with the [L][N] matrices that give `logprob_p`. latent_stats: as in _walk."""
+        mode_layers = [] if mode_layers is None else mode_layers
+        constant_layers = [] if constant_layers is None else constant_layers
+        inference_mode = bu_values is not None
+        if inference_mode != (n_img_prior is None):
+            raise RuntimeError("Number of images for top-down generation has to be given if and only if we're "
+                               "not doing inference")
+        if inference_mode and (len(mode_layers) > 0 or len(constant_layers) > 0):
+            raise RuntimeError("Prior experiments (e.g. sampling from mode) are not compatible with inference mode")
+        forced = [None if fl is None else fl.permute(0, 2, 3, 1).contiguous() for fl in forced_latent or [None] * self.n_layers]
+        plan = [LayerZ(inference_mode, i in mode_layers, i in constant_layers, None, forced[i]) for i in range(self.n_layers)]
+        n_rows = bu_values[0].shape[0] if inference_mode else int(n_img_prior)
+        mats = tuple(torch.empty((self.n_layers, n_rows), dtype=torch.float32, device=next(self.parameters()).device) for _ in range(2))
+        return self._walk(plan, bu_values, n_img_prior, mats=mats, latent_stats=latent_stats)
 
     def topdown_pass(self, bu_values=None, n_img_prior=None, mode_layers=None, constant_layers=None,
                      forced_latent=None):
@@ -476,15 +488,13 @@ class LadderVAE(nn.Module):
         in mode_layers ignores its temperature; a layer at 0.0 draws no noise. None or 1.0 is the call without the keyword, bit for bit."""
         temps = layer_temperatures(self.n_layers, temperature)
         self._begin(None)
-        if _untempered(temps):
-            out, _ = self._topdown(n_img_prior=n_imgs, mode_layers=mode_layers, constant_layers=constant_layers)
+        if _untempered(temps):   # the reference's call, with its matrices
+            out, data = self._topdown(n_img_prior=n_imgs, mode_layers=mode_layers, constant_layers=constant_layers)
         else:
-            out, _ = self._topdown_mixed(None, 0, n_imgs, 1, temps, mode_layers or (), constant_layers or ())
-        if tuple(out.shape[1:3]) != tuple(self.img_shape):
-            out = ops.CropFn.apply(out, tuple(self.img_shape))
-        _, likelihood_data = self.likelihood(out, None, self.noise)
-        self.noise.end()
-        return _nchw(likelihood_data['sample'])
+            in_mode, constant = mode_layers or (), constant_layers or ()
+            plan = [LayerZ(False, i in in_mode, i in constant, None if i in in_mode else t) for i, t in enumerate(temps)]
+            out, data = self._walk(plan, rows=int(n_imgs))
+        return self._pictures(out, self.img_shape, data['z'])['sample']
 
     def sample_conditional(self, x, n_top_layers, n_samples=1, temperature=None, use_mode=False):
         """Engine-only: images that share the top k = n_top_layers latents of x. The k top layers take z from the posterior of x (as
@@ -511,20 +521,10 @@ class LadderVAE(nn.Module):
             raise ValueError("n_samples must be at least 1, got %d" % n_samples)
         temps = layer_temperatures(L, temperature)
         self._begin(x)
-        img_size = tuple(int(s) for s in x.shape[2:])
-        bu_values = None
-        if n_top > 0:
-            x_pad = K.pad_crop(x.contiguous().float(), True, self.get_padded_size(x.size()), False)
-            bu_values = self._bottomup(x_pad)
-        out, z = self._topdown_mixed(bu_values, n_top, x.shape[0], n_samples, temps, use_mode=use_mode)
-        if tuple(out.shape[1:3]) != img_size:
-            out = ops.CropFn.apply(out, img_size)
-        _, info = self.likelihood(out, None, self.noise)
-        self.noise.end()
-        params = info['params']
-        params = {k: _nchw(v) for k, v in params.items()} if isinstance(params, dict) else _nchw(params)
-        return {'sample': _nchw(info['sample']), 'mean': _nchw(info['mean']), 'mode': _nchw(info['mode']),
-                'likelihood_params': params, 'z': [_nchw(t) for t in z]}
+        bu_values = self._encode_image(x, need_image=False)[0] if n_top > 0 else None
+        plan = [LayerZ(True, use_mode) if i >= L - n_top else LayerZ(temperature=t) for i, t in enumerate(temps)]
+        out, data = self._walk(plan, bu_values, n_samples * int(x.shape[0]), n_samples=n_samples)
+        return self._pictures(out, x.shape[2:], data['z'])
 
     # ------------------------------------------------------------------------------------------------------------
     # engine-only: encode / decode / interpolate (forward only: run them under torch.no_grad())
@@ -535,46 +535,21 @@ class LadderVAE(nn.Module):
             raise ValueError("n_top_layers must be in 1..%d, got %d" % (self.n_layers, k))
         return k
 
-    def _encode(self, x, n_top, use_mode):
-        """Bottom-up pass of the NCHW batch x, then layers L-1 .. L-n_top in inference mode by the code path of forward() (the posterior
-        branch of _topdown_mixed); the layers below launch nothing. Returns [z NHWC, or None below L-n_top]. Between _begin and noise.end."""
-        L = self.n_layers
-        x_pad = K.pad_crop(x.contiguous().float(), True, self.get_padded_size(x.size()), False)
-        bu_values = self._bottomup(x_pad)
-        z = [None] * L
-        out = None
-        for i in reversed(range(L - n_top, L)):
-            out, _, aux = self.top_down_layers[i](out, skip_connection_input=out, inference_mode=True, bu_value=bu_values[i],
-                                                  use_mode=use_mode, noise=self.noise)
-            z[i] = aux['z']
-        return z
-
-    def _decode(self, forced, rows, temps, noise):
-        """Generative pass on `rows` rows: layer i takes forced[i] (NHWC, through forced_latent) where it is given and draws from its prior
-        at temps[i] (from `noise`) where it is None; then final_top_down. Returns (out NHWC, [z NHWC per layer])."""
-        z = [None] * self.n_layers
-        out = None
-        for i in reversed(range(self.n_layers)):
-            kw = dict(temperature=temps[i]) if forced[i] is None else dict(forced_latent=forced[i])
-            out, _, aux = self.top_down_layers[i](out, skip_connection_input=out, inference_mode=False, n_img_prior=rows, noise=noise, **kw)
-            z[i] = aux['z']
-        for mod in self.final_top_down:
-            if isinstance(mod, Placeholder):
-                out = ops.UpsampleFn.apply(out)
-            else:
-                out = mod(out, noise)
-        return out, z
-
     def _pictures(self, out, img_size, z):
-        """crop, likelihood without a target, noise.end() -> the dict of sample_conditional"""
-        if tuple(out.shape[1:3]) != tuple(img_size):
-            out = ops.CropFn.apply(out, tuple(img_size))
-        _, info = self.likelihood(out, None, self.noise)
+        """The tail of every pass that makes pictures: crop, likelihood without a target, noise.end() -> the dict of sample_conditional"""
+        _, info = self.likelihood(self._crop(out, img_size), None, self.noise)
         self.noise.end()
-        params = info['params']
-        params = {k: _nchw(v) for k, v in params.items()} if isinstance(params, dict) else _nchw(params)
         return {'sample': _nchw(info['sample']), 'mean': _nchw(info['mean']), 'mode': _nchw(info['mode']),
-                'likelihood_params': params, 'z': [_nchw(t) for t in z]}
+                'likelihood_params': _nchw_params(info['params']), 'z': [_nchw(t) for t in z]}
+
+    def _posterior_plan(self, n_top, use_mode):
+        """Layers L-1 .. L-n_top from the posterior (with use_mode its mean); the walk stops behind layer L-n_top."""
+        return [LayerZ(True, use_mode, last=i == self.n_layers - n_top) for i in range(self.n_layers)]
+
+    @staticmethod
+    def _forced_plan(forced, temps):
+        """Generative mode: layer i takes forced[i] (NHWC) where it is given and draws from its prior at temps[i] where it is None."""
+        return [LayerZ(temperature=t) if f is None else LayerZ(forced=f) for f, t in zip(forced, temps)]
 
     def encode(self, x, n_top_layers=None, use_mode=True):
         """Engine-only: the latents of the top k = n_top_layers layers (None: all L) of the NCHW batch x, from its posterior as forward()
@@ -587,9 +562,9 @@ class LadderVAE(nn.Module):
             raise ValueError("x must be (B, C, H, W), got %s" % (tuple(x.shape),))
         n_top = self._top_k(n_top_layers)
         self._begin(x)
-        z = self._encode(x, n_top, use_mode)
+        _, data = self._walk(self._posterior_plan(n_top, use_mode), self._encode_image(x, need_image=False)[0])
         self.noise.end()
-        return [_nchw(t) for t in z]
+        return [_nchw(t) for t in data['z']]
 
     def _forced_rows(self, z, what):
         """z: a list of L NCHW tensors or None -> ([NHWC contiguous or None], their common row count or None)"""
@@ -629,8 +604,8 @@ class LadderVAE(nn.Module):
             raise ValueError("n_imgs = %d, but the forced latents have %d rows" % (int(n_imgs), rows))
         temps = layer_temperatures(self.n_layers, temperature)
         self._begin(next((t for t in forced if t is not None), None))
-        out, zs = self._decode(forced, rows, temps, self.noise)
-        return self._pictures(out, self.img_shape, zs)
+        out, data = self._walk(self._forced_plan(forced, temps), rows=rows)
+        return self._pictures(out, self.img_shape, data['z'])
 
     def interpolate(self, x_a, x_b, n_steps=8, n_top_layers=None, mode='slerp', t=None, use_mode=True, temperature=None):
         """Engine-only: the path between the images of x_a and x_b (B, C, H, W) in the latents of the top k = n_top_layers layers (None: all
@@ -664,12 +639,13 @@ class LadderVAE(nn.Module):
         T = int(t.shape[0])
         temps = layer_temperatures(L, temperature)
         self._begin(x_a)
-        z_ab = self._encode(torch.cat((x_a, x_b)), n_top, use_mode)
+        bu_values = self._encode_image(torch.cat((x_a, x_b)), need_image=False)[0]
+        z_ab = self._walk(self._posterior_plan(n_top, use_mode), bu_values)[1]['z']
         z_a = [None if v is None else v[:B] for v in z_ab]   # (row slices of a contiguous tensor: contiguous)
         z_b = [None if v is None else v[B:] for v in z_ab]
         forced = [None if v is None else K.latent_interp(z_a[i], z_b[i], t, mode) for i, v in enumerate(z_ab)]
-        out, zs = self._decode(forced, T * B, temps, _SharedDraws(self.noise, B, T))
-        res = self._pictures(out, x_a.shape[2:], zs)
+        out, data = self._walk(self._forced_plan(forced, temps), rows=T * B, noise=_SharedDraws(self.noise, B, T))
+        res = self._pictures(out, x_a.shape[2:], data['z'])
         res.update(z_a=[_nchw(v) for v in z_a], z_b=[_nchw(v) for v in z_b], t=t)
         return res
 
@@ -688,9 +664,10 @@ class LadderVAE(nn.Module):
         has none.
 
         Noise: begin / the 'noise' draw if any / end once, then per round begin, the draws of forward() in its order, end.
-        use_graph=None: as in evaluate.iw_log_likelihood — with PhiloxNoise and n_iters >= 8 two rounds run eagerly (they count), one round
-        is captured as a hipGraph and replayed for the rest, with a device copy of that round's ll (and history frame) between replays and
-        no host wait; a noise tape always runs eagerly. Eager and replayed runs from one noise position agree bit for bit.
+        use_graph=None: the loop of evaluate.iw_log_likelihood (passes.replay_loop) — with PhiloxNoise and n_iters >= 8 two rounds run
+        eagerly (they count), one round is captured as a hipGraph and replayed for the rest, with a device copy of that round's ll (and
+        history frame) between replays and no host wait; a noise tape always runs eagerly. Eager and replayed runs from one noise
+        position agree bit for bit.
 
         Returns {'completed' (B,C,H,W): observed pixels bit for bit those of x; 'll_observed' (n_iters, B): each round's masked ll, of the
         completion that ENTERED the round; with return_history 'history' (n_iters + 1, B, C, H, W), frame 0 the initial fill (final='mean'
@@ -721,11 +698,9 @@ class LadderVAE(nn.Module):
         elif use_graph and not isinstance(self.noise, PhiloxNoise):
             raise ValueError("use_graph needs on-device noise (PhiloxNoise): a noise tape runs eagerly")
         use_graph = bool(use_graph) and n_iters > 2   # (the two eager rounds are all there is otherwise)
-        was_training = self.training
-        self.eval()
-        try:
+        with eval_mode(self):
             self._begin(x)
-            img_size, padded = (H, W), self.get_padded_size(x.size())
+            img_size = (H, W)
             cur = K.pad_crop(x.contiguous().float(), True, img_size, False)   # NHWC
             if torch.is_tensor(init):
                 fill = K.pad_crop(init, True, img_size, False)
@@ -742,42 +717,24 @@ class LadderVAE(nn.Module):
 
             def one_round():
                 self.noise.begin(dev)                 # every round: same call sites, next RNG step
-                out, _ = self._topdown(self._bottomup(K.pad_crop(cur, False, padded, False)))
-                if tuple(out.shape[1:3]) != img_size:
-                    out = ops.CropFn.apply(out, img_size)
-                ll, info = self.likelihood(out, cur, self.noise, mask=mask, filled_out=cur)
+                out, _ = self._topdown(self._encode_image(cur, nchw=False, need_image=False)[0])
+                ll, info = self.likelihood(self._crop(out, img_size), cur, self.noise, mask=mask, filled_out=cur)
                 frame = K.pad_crop(cur, False, img_size, True) if hist is not None else None
                 self.noise.end()
                 return ll, info, frame
 
-            def keep(r, ll, frame):                   # device copies in stream order; the host does not wait
-                ll_obs[r].copy_(ll)
+            def keep(r, res):                         # device copies in stream order; the host does not wait
+                ll_obs[r].copy_(res[0])
                 if hist is not None:
-                    hist[r + 1].copy_(frame)
+                    hist[r + 1].copy_(res[2])
 
-            if use_graph:
-                for r in range(2):                    # eager: allocator warm-up (these count as rounds)
-                    ll, info, frame = one_round()
-                    keep(r, ll, frame)
-                torch.cuda.synchronize()
-                graph = torch.cuda.CUDAGraph()
-                with torch.cuda.graph(graph, capture_error_mode='thread_local'):
-                    ll, info, frame = one_round()
-                for r in range(2, n_iters):
-                    graph.replay()
-                    keep(r, ll, frame)
-            else:
-                for r in range(n_iters):
-                    ll, info, frame = one_round()
-                    keep(r, ll, frame)
+            _, info, _ = replay_loop(one_round, n_iters, use_graph, keep)
             if final == 'mean':
                 K.mask_select(cur, info['mean'].contiguous(), mask, False, out=cur)
             res = {'completed': K.pad_crop(cur, False, img_size, True), 'll_observed': ll_obs}
             if hist is not None:
                 res['history'] = hist
             return res
-        finally:
-            self.train(was_training)
 
     def get_top_prior_param_shape(self, n_imgs=1):
         """models/lvae.py:364-372."""

@@ -13,6 +13,7 @@ import numpy as np
 import torch
 
 from . import kernels as K
+from .passes import eval_mode
 
 QUERY_ROWS = 4096   # rows per search call of a long query set (the results do not depend on the cut)
 
@@ -103,17 +104,13 @@ def latent_features(model, images, n_top_layers=None, batch_size=256):
     """(N, Dz) float32 on the device: per image the posterior means of the top k = n_top_layers layers (None: all), each flattened (C, H, W)
     and concatenated top layer first. model.encode in eval mode, batch_size images at a time; images: NCHW, host or device."""
     dev = next(model.parameters()).device
-    was_training = model.training
-    model.eval()
-    try:
+    with eval_mode(model):
         out = []
         for lo in range(0, int(images.shape[0]), int(batch_size)):
             x = images[lo:lo + int(batch_size)].to(dev).contiguous().float()
             z = model.encode(x, n_top_layers)
             out.append(torch.cat([t.reshape(t.shape[0], -1) for t in reversed(z) if t is not None], 1))
         return torch.cat(out).contiguous()
-    finally:
-        model.train(was_training)
 
 
 def closeness_summary(d_samples, d_heldout):
