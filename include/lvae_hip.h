@@ -400,6 +400,21 @@ int lvae_conv2d_wgrad_bf16(const lvae_conv_desc* d, const float* dy, float* dw, 
 int32_t lvae_conv2d_wgrad_apply_ok(const lvae_conv_desc* d);
 int lvae_conv2d_wgrad_apply_f32(const lvae_conv_desc* d, const lvae_bn_apply* ap, float* dw, float* db, void* workspace,
                                 size_t workspace_bytes, void* stream);
+/* Both weight gradients of a residual block in one launch and one slab reduce: A = the block's first convolution with the apply `ap` in
+ * front, exactly as lvae_conv2d_wgrad_apply_f32(a, ap, dw_a, db_a, ...), B = its second convolution with a real dy, exactly as
+ * lvae_conv2d_wgrad_f32(b, dy_b, dw_b, db_b, ...). The two share the chip: each gradient is summed over about half as many partial slabs as
+ * alone (A gets the larger share, its chunks cost more), so results differ from the two single calls by the summation order only; they are
+ * reproducible from run to run. lvae_conv2d_wgrad_pair_ok(a, b) != 0 exactly when both descriptors take the Winograd family, A has
+ * lvae_conv2d_wgrad_apply_ok, both have the same geometry (N, H, W, kernel, channels) with Cout == 64, and both are fp32 in arithmetic and
+ * storage. The queries read plans only: host only, no launch. lvae_conv2d_wgrad_pair_schedule writes sched[6] = ranges, chunks per range
+ * and workgroups of A, then of B (a chunk = 16 Winograd tiles; range r of a problem takes chunks [r * cpr, min(total, (r + 1) * cpr)) of
+ * its N * H * W / 64) and returns lvae_conv2d_wgrad_pair_ok. workspace: lvae_conv2d_wgrad_pair_workspace(a, b) bytes, 16-byte aligned like
+ * dy_b and the operands of ap. */
+int32_t lvae_conv2d_wgrad_pair_ok(const lvae_conv_desc* a, const lvae_conv_desc* b);
+size_t lvae_conv2d_wgrad_pair_workspace(const lvae_conv_desc* a, const lvae_conv_desc* b);
+int32_t lvae_conv2d_wgrad_pair_schedule(const lvae_conv_desc* a, const lvae_conv_desc* b, int32_t* sched);
+int lvae_conv2d_wgrad_pair_f32(const lvae_conv_desc* a, const lvae_bn_apply* ap, const lvae_conv_desc* b, const float* dy_b, float* dw_a,
+                               float* db_a, float* dw_b, float* db_b, void* workspace, size_t workspace_bytes, void* stream);
 /* Which kernel family lvae_conv2d_wgrad_f32 (and the grouped call) runs for `d` (d->x_dtype / y_dtype = the storage types of x / dy):
  * diagnostics for the parity tests and the profiles. */
 enum {

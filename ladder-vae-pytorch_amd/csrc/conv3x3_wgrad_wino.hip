@@ -41,7 +41,7 @@ constexpr int WG_DS = 80;  // dy pixel stride (floats, 64 channels + pad): 2 pix
 template <int TPR>  // Winograd tiles per image row (W / 2): 4, 8 or 16; a chunk is 16 tiles = 16 / TPR tile rows
 __global__ __launch_bounds__(512, 2) void conv_wgrad_wino_kernel(WgWinoArgs a) {
   kernarg_warmup<sizeof(WgWinoArgs)>();
-  const int nwg_ = gridDim.x;
+  const int nwg_ = gridDim.x, bid_ = blockIdx.x;
   constexpr bool AP = false;
   const lvae_bn_apply ap = lvae_bn_apply{};
 #include "conv3x3_wgrad_wino_body.inc"
@@ -57,7 +57,7 @@ __global__ __launch_bounds__(512, 2) void conv_wgrad_wino_ap_kernel(WgWinoApArgs
   kernarg_warmup<sizeof(WgWinoApArgs)>();
   const WgWinoArgs& a = g.w;
   const lvae_bn_apply& ap = g.ap;
-  const int nwg_ = gridDim.x;
+  const int nwg_ = gridDim.x, bid_ = blockIdx.x;
   constexpr bool AP = true;
 #include "conv3x3_wgrad_wino_body.inc"
 }
@@ -74,9 +74,39 @@ __global__ __launch_bounds__(512, 2) void conv_wgrad_wino_grouped_kernel(WgWinoG
   const WgWinoArgs& a = g.p[blockIdx.y];
   const int nwg_ = a.nranges * a.ncog * 2;
   if ((int)blockIdx.x >= nwg_) return;  // uniform per workgroup, before any barrier
+  const int bid_ = blockIdx.x;
   constexpr bool AP = false;
   const lvae_bn_apply ap = lvae_bn_apply{};
 #include "conv3x3_wgrad_wino_body.inc"
+}
+
+// The two gradients of one residual block in one launch: problem A (conv1) forms its dY with the BatchNorm-backward apply in front, as
+// conv_wgrad_wino_ap_kernel does, problem B (conv2) has a real dY. Workgroups [0, nwg_a) are A's, the rest B's; each problem has its own
+// range split (wg_wino_pair_plan), its own XCD remap and its own "workgroup 0" / "input-channel block 0" roles, all from the problem-local
+// index. Half the ranges per gradient and twice the chunks per workgroup: half the slab traffic, one prologue and one epilogue per CU.
+struct WgWinoPairArgs {
+  WgWinoArgs a, b;
+  lvae_bn_apply ap;
+  int nwg_a, pad_;
+};
+static_assert(sizeof(WgWinoPairArgs) <= 4096, "kernel argument block");
+
+template <int TPR>
+__global__ __launch_bounds__(512, 2) void conv_wgrad_wino_pair_kernel(WgWinoPairArgs g) {
+  kernarg_warmup<(sizeof(WgWinoPairArgs) < 1024 ? sizeof(WgWinoPairArgs) : 1024)>();
+  if ((int)blockIdx.x < g.nwg_a) {  // uniform per workgroup, before any barrier
+    const WgWinoArgs& a = g.a;
+    const lvae_bn_apply& ap = g.ap;
+    const int nwg_ = g.nwg_a, bid_ = blockIdx.x;
+    constexpr bool AP = true;
+#include "conv3x3_wgrad_wino_body.inc"
+  } else {
+    const WgWinoArgs& a = g.b;
+    const lvae_bn_apply ap = lvae_bn_apply{};
+    const int nwg_ = (int)gridDim.x - g.nwg_a, bid_ = (int)blockIdx.x - g.nwg_a;
+    constexpr bool AP = false;
+#include "conv3x3_wgrad_wino_body.inc"
+  }
 }
 
 struct WinoReduceArgs {
@@ -89,6 +119,9 @@ struct WinoReduceArgs {
 };
 struct WinoReduceGroup {
   WinoReduceArgs p[kWgradWinoGroup];
+};
+struct WinoReducePair {
+  WinoReduceArgs p[2];
 };
 
 // dw[tap(a,b)][ci][co] += (G^T (sum_ranges slab) G)[a][b], 1024-thread workgroups, ranges summed in eight slices (slice = range mod 8,
@@ -167,6 +200,14 @@ __global__ __launch_bounds__(1024) void conv_wgrad_wino_reduce_kernel(WinoReduce
   wino_reduce_body<true>(a, blockIdx.x, red, red_b);
 }
 
+// the two gradients of a pair launch (blockIdx.y = problem), each in the HALF form over its own range count
+__global__ __launch_bounds__(1024) void conv_wgrad_wino_reduce_pair_kernel(WinoReducePair g) {
+  kernarg_warmup<sizeof(WinoReducePair)>();
+  __shared__ __attribute__((aligned(16))) float red[8 * 16 * 32];
+  __shared__ float red_b[16][64];
+  wino_reduce_body<true>(g.p[blockIdx.y], blockIdx.x, red, red_b);
+}
+
 __global__ __launch_bounds__(1024) void conv_wgrad_wino_reduce_grouped_kernel(WinoReduceGroup g) {
   kernarg_warmup<(sizeof(WinoReduceGroup) < 1024 ? sizeof(WinoReduceGroup) : 1024)>();
   const WinoReduceArgs& a = g.p[blockIdx.y];
@@ -176,7 +217,8 @@ __global__ __launch_bounds__(1024) void conv_wgrad_wino_reduce_grouped_kernel(Wi
   wino_reduce_body<false>(a, blockIdx.x, red, red_b);
 }
 
-static bool wg_wino_plan(const lvae_conv_desc* d, WgWinoArgs& a) {
+// budget: the ranges this gradient may spread over (x 2 input-channel blocks = its workgroups): 128 when it has the chip to itself
+static bool wg_wino_plan(const lvae_conv_desc* d, WgWinoArgs& a, int budget = 128) {
   static const bool off = tune("LVAE_DISABLE_WINO_WGRAD", 0) != 0 || tune("LVAE_DISABLE_WINO", 0) != 0;  // A/B switch (tuning builds only)
   if (off) return false;
   if (d->KH != 3 || d->KW != 3 || d->stride != 1 || d->pad != 1 || d->gather != LVAE_GATHER_CONV) return false;
@@ -192,7 +234,7 @@ static bool wg_wino_plan(const lvae_conv_desc* d, WgWinoArgs& a) {
   a.ncog = (d->Cout + 63) / 64;
   a.cpi = (d->H / 2) / tr;
   a.total_chunks = d->N * a.cpi;
-  int nranges = 128 / a.ncog;  // 256 workgroups with the two input-channel blocks
+  int nranges = budget / a.ncog;  // 128: 256 workgroups with the two input-channel blocks
   if (nranges < 1) nranges = 1;
   static const int min_cpr = (int)tune("LVAE_WINO_WGRAD_MIN_CPR", 4);
   if (nranges > a.total_chunks / min_cpr) nranges = a.total_chunks / min_cpr;  // slab traffic: at least min_cpr chunks per slab
@@ -214,6 +256,41 @@ bool conv_wgrad_wino_plan(const lvae_conv_desc* d, WgradPlan& p) {
   return true;
 }
 
+// The pair launch shares 128 ranges (256 workgroups, one per CU) between conv1's gradient with the apply in front (A) and conv2's (B).
+// A's chunks cost more (dy1 is formed from dh2 and y1 while a chunk is staged), so an even split would leave B's CUs idle: A gets
+// kWgWinoPairRangesA of the 128. At 256x16x16 (1,024 chunks) that is 74 ranges of 14 chunks against 54 of 19. Measured at that shape, back
+// to back in a captured graph (tools/wgrad_pair_bench.py, a tuning build sweeping the constant): 68 -> 80.6 us per pair, 70 and 72 -> 76.9,
+// 74 -> 73.4, 76 -> 75.5, 78 -> 78.7, 80 -> 81.2, against 89.6 us for the two single launches (A 53.0, B 41.0 with their reduces: 58 : 42
+// after the reduce, as the in-step rows 47.0 / 34.6 us suggested). profiles/wgrad_pair_ab.txt has the table.
+constexpr int kWgWinoPairRangesA = 74;
+static int wg_wino_pair_ranges_a() {
+  static const int v = (int)std::min<int64_t>(127, std::max<int64_t>(1, tune("LVAE_WINO_PAIR_RANGES_A", kWgWinoPairRangesA)));  // (swept in tuning builds only)
+  return v;
+}
+
+// The split itself. Ranges that one problem cannot use — its least chunks per range, or the rounding of its range length — go to the
+// other: B is planned with what A left, then A again with what B left (at the family's minimum of 16,384 pixels both end at 64 ranges of
+// 4 chunks, the single launches' own split, and the chip is full).
+static bool wg_wino_pair_split(const lvae_conv_desc* da, const lvae_conv_desc* db, WgWinoArgs& a, WgWinoArgs& b) {
+  if (!wg_wino_plan(da, a, wg_wino_pair_ranges_a()) || a.ncog != 1 || a.nranges >= 128) return false;
+  if (!wg_wino_plan(db, b, 128 - a.nranges) || b.ncog != 1) return false;
+  return wg_wino_plan(da, a, 128 - b.nranges);
+}
+
+// both gradients of a pair as the pair launch splits them (the caller has checked that the pair is one: conv_wgrad.hip); sched = ranges,
+// chunks per range and workgroups of A, then of B
+bool conv_wgrad_wino_pair_plan(const lvae_conv_desc* da, const lvae_conv_desc* db, WgradPlan& pa, WgradPlan& pb, int32_t* sched) {
+  WgWinoArgs a, b;
+  if (!wg_wino_pair_split(da, db, a, b)) return false;
+  pa.set_slabs(a.nranges, (size_t)2 * 16 * 32 * 64, 64);
+  pb.set_slabs(b.nranges, (size_t)2 * 16 * 32 * 64, 64);
+  if (sched) {
+    const int32_t v[6] = {a.nranges, a.cpr, a.nranges * 2, b.nranges, b.cpr, b.nranges * 2};
+    std::copy(v, v + 6, sched);
+  }
+  return true;
+}
+
 // f(tiles per row) with the value as a compile-time constant
 template <typename F>
 static int with_tpr(int W, F f) {
@@ -229,14 +306,17 @@ static size_t wg_wino_lds(int W) {
 }
 
 // the kernel arguments and the slab reduce of one gradient (dy null: formed by a deferred apply); returns the kernel's workgroups
-static int wino_fill(const WgradOp& o, WgWinoArgs& a, WinoReduceArgs& r) {
-  wg_wino_plan(o.d, a);
+static int wino_fill_planned(const WgradOp& o, WgWinoArgs& a, WinoReduceArgs& r) {   // a: planned (wg_wino_plan / wg_wino_pair_split)
   a.d = *o.d;
   a.dy = o.dy;
   a.slab_w = o.slab_w();
   a.slab_b = o.slab_b();
   r = WinoReduceArgs{a.slab_w, a.slab_b, a.nranges, a.ncog, o.d->Cout, 0, o.d->w_stap, o.d->w_sk, o.d->w_sn, o.dw, o.db};
   return a.nranges * a.ncog * 2;
+}
+static int wino_fill(const WgradOp& o, WgWinoArgs& a, WinoReduceArgs& r) {
+  wg_wino_plan(o.d, a);
+  return wino_fill_planned(o, a, r);
 }
 
 // one gradient of a plan with apply_ok whose dY is ap's result (16-byte aligned workspace and ap operands: the entry point checked them)
@@ -253,6 +333,26 @@ int conv_wgrad_wino_apply_launch(const WgradOp& o, const lvae_bn_apply* ap, hipS
   if (rc) return rc;
   hipLaunchKernelGGL(conv_wgrad_wino_reduce_kernel, dim3(128 * r.ncog), dim3(1024), 0, s, r);
   LVAE_LAUNCH_CHECK("conv_wgrad_wino_reduce");
+  return 0;
+}
+
+// the pair of conv_wgrad_wino_pair_plan: a.plan / b.plan are that function's, ap forms A's dY (operands checked by the entry point)
+int conv_wgrad_wino_pair_launch(const WgradOp& a, const lvae_bn_apply* ap, const WgradOp& b, hipStream_t s) {
+  WgWinoPairArgs g;
+  WinoReducePair rg;
+  wg_wino_pair_split(a.d, b.d, g.a, g.b);
+  g.nwg_a = wino_fill_planned(a, g.a, rg.p[0]);
+  const int nwg_b = wino_fill_planned(b, g.b, rg.p[1]);
+  g.ap = *ap;
+  g.pad_ = 0;
+  auto launch = [&](auto tpr) {
+    return launch_lds<conv_wgrad_wino_pair_kernel<decltype(tpr)::value>>("conv_wgrad_wino_pair", dim3(g.nwg_a + nwg_b), dim3(512), wg_wino_lds(a.d->W),
+                                                                         160 * 1024, s, g);
+  };
+  const int rc = a.d->W == 16 ? launch(std::integral_constant<int, 8>{}) : launch(std::integral_constant<int, 16>{});   // apply_ok: W = 16 or 32
+  if (rc) return rc;
+  hipLaunchKernelGGL(conv_wgrad_wino_reduce_pair_kernel, dim3(128, 2), dim3(1024), 0, s, rg);
+  LVAE_LAUNCH_CHECK("conv_wgrad_wino_reduce_pair");
   return 0;
 }
 

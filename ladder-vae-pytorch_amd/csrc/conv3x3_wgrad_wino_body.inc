@@ -1,5 +1,6 @@
-// Body of conv_wgrad_wino_kernel / conv_wgrad_wino_grouped_kernel / conv_wgrad_wino_ap_kernel (textually included, see
-// conv3x3_wgrad_halo_body.inc). Expects: template parameter TPR; `a` (WgWinoArgs); `nwg_` = workgroups of this problem; constexpr bool AP and
+// Body of conv_wgrad_wino_kernel / conv_wgrad_wino_grouped_kernel / conv_wgrad_wino_ap_kernel / conv_wgrad_wino_pair_kernel (textually included,
+// see conv3x3_wgrad_halo_body.inc). Expects: template parameter TPR; `a` (WgWinoArgs); `nwg_` = workgroups of this problem and `bid_` = this
+// workgroup's index among them (blockIdx.x except in the pair kernel, whose second problem starts behind the first); constexpr bool AP and
 // `ap` (lvae_bn_apply): with AP the dY operand does not exist yet — it is dy = BN'(ap.dh; ap.x) * ap.drop, the BatchNorm-backward apply
 // that would otherwise run as a launch of its own in front of this one (round 5): the kernel reduces the producer's partial rows, forms dy
 // while it stages a chunk and (the input-channel block 0 workgroups) stores it to ap.out for the dgrad that follows. Cout == 64 only.
@@ -11,7 +12,7 @@
   const lvae_conv_desc& d = a.d;
   const int t = threadIdx.x, lane = t & 63, wave = t >> 6;
   const int li = lane & 31, lh = lane >> 5, pi = wave & 3, kg = wave >> 2;
-  int bid = blockIdx.x;
+  int bid = bid_;
   {
     const int nwg = nwg_, xcd = bid & 7, q = nwg >> 3, r = nwg & 7;
     bid = (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + (bid >> 3);
@@ -87,7 +88,7 @@
       const BnBwdChannel r = bn_bwd_finish(sa, sb, ap.M);
       Cf[256 + t] = r.c1;
       Cf[320 + t] = r.c2;
-      if (blockIdx.x == 0) {
+      if (bid_ == 0) {
         if (ap.dbeta) ap.dbeta[t] += r.dbeta;
         if (ap.dgamma) ap.dgamma[t] += r.dgamma;
       }

@@ -647,6 +647,60 @@ extern "C" int lvae_conv2d_wgrad_apply_f32(const lvae_conv_desc* d, const lvae_b
   return conv_wgrad_wino_apply_launch(o, ap, (hipStream_t)stream);
 }
 
+// The pair of a residual block (A = conv1 with the apply in front, B = conv2): both routed to the Winograd family, A with apply_ok, one
+// geometry, 64 output channels, fp32 arithmetic and storage. Reads plans only; pa / pb come back as the pair launch splits them.
+static bool wgrad_pair_route(const lvae_conv_desc* a, const lvae_conv_desc* b, WgradPlan& pa, WgradPlan& pb, int32_t* sched) {
+  if (!a || !b) return false;
+  pa = wgrad_route(a, true, true);
+  pb = wgrad_route(b, true, true);
+  if (pa.variant != LVAE_WGRAD_VARIANT_WINO || pb.variant != LVAE_WGRAD_VARIANT_WINO || !pa.apply_ok) return false;
+  const bool same = a->N == b->N && a->H == b->H && a->W == b->W && a->OH == b->OH && a->OW == b->OW && a->C1 == b->C1 && a->C2 == b->C2 &&
+                    a->KH == b->KH && a->KW == b->KW && a->stride == b->stride && a->pad == b->pad && a->gather == b->gather;
+  const auto f32 = [](const lvae_conv_desc* d) { return d->precision == LVAE_PREC_F32 && d->x_dtype == LVAE_DT_F32 && d->y_dtype == LVAE_DT_F32; };
+  if (!same || a->Cout != 64 || b->Cout != 64 || !f32(a) || !f32(b)) return false;
+  return conv_wgrad_wino_pair_plan(a, b, pa, pb, sched);
+}
+// a gradient's 256-byte aligned piece of a workspace that several share (the pair below, the grouped call)
+static size_t wgrad_piece(const WgradPlan& aligned) { return (aligned.workspace + 255) / 256 * 256; }
+
+extern "C" int32_t lvae_conv2d_wgrad_pair_ok(const lvae_conv_desc* a, const lvae_conv_desc* b) {
+  WgradPlan pa, pb;
+  return wgrad_pair_route(a, b, pa, pb, nullptr) ? 1 : 0;
+}
+
+extern "C" size_t lvae_conv2d_wgrad_pair_workspace(const lvae_conv_desc* a, const lvae_conv_desc* b) {
+  WgradPlan pa, pb;
+  return wgrad_pair_route(a, b, pa, pb, nullptr) ? wgrad_piece(pa) + wgrad_piece(pb) : 0;
+}
+
+extern "C" int32_t lvae_conv2d_wgrad_pair_schedule(const lvae_conv_desc* a, const lvae_conv_desc* b, int32_t* sched) {
+  WgradPlan pa, pb;
+  return sched && wgrad_pair_route(a, b, pa, pb, sched) ? 1 : 0;
+}
+
+extern "C" int lvae_conv2d_wgrad_pair_f32(const lvae_conv_desc* a, const lvae_bn_apply* ap, const lvae_conv_desc* b, const float* dy_b,
+                                          float* dw_a, float* db_a, float* dw_b, float* db_b, void* workspace, size_t workspace_bytes,
+                                          void* stream) {
+  const char* who = "lvae_conv2d_wgrad_pair_f32";
+  int rc = conv_desc_check(a, who);
+  if (!rc) rc = conv_desc_check(b, who);
+  if (rc) return rc;
+  WgradPlan pa, pb;
+  LVAE_REQUIRE(wgrad_pair_route(a, b, pa, pb, nullptr), LVAE_EINVAL,
+               "%s: not a pair (two Winograd-domain fp32 weight gradients of 64 -> 64 layers of one geometry, W = 16 or 32, fp32 storage; "
+               "lvae_conv2d_wgrad_pair_ok): use lvae_conv2d_wgrad_apply_f32 + lvae_conv2d_wgrad_f32", who);
+  LVAE_REQUIRE(ap && ap->parts && ap->rows > 0 && ap->M == (int64_t)a->N * a->H * a->W && ap->coef && ap->dh && ap->x && ap->out && ap->add == nullptr &&
+                   ap->dh_bf16 == 0 && dy_b && dw_a && dw_b && workspace,
+               LVAE_EINVAL, "%s: needs parts / rows, M = N*H*W, the coefficient block, fp32 dh, x and out, no add; dy of B, both dw, workspace", who);
+  const size_t piece_a = wgrad_piece(pa), need = piece_a + wgrad_piece(pb);
+  LVAE_REQUIRE(workspace_bytes >= need, LVAE_EWORKSPACE, "%s: workspace %zu < %zu", who, workspace_bytes, need);
+  const void* const operand[] = {workspace, ap->parts, ap->coef, ap->dh, ap->x, ap->out, ap->drop, dy_b};
+  const char* const name[] = {"workspace", "ap->parts", "ap->coef", "ap->dh", "ap->x", "ap->out", "ap->drop", "dy_b"};
+  for (int i = 0; i < 8; ++i) LVAE_REQUIRE(al16_or_null(operand[i]), LVAE_EALIGN, "%s: %s must be 16-byte aligned", who, name[i]);
+  const WgradOp oa{a, pa, nullptr, dw_a, db_a, workspace}, ob{b, pb, dy_b, dw_b, db_b, static_cast<char*>(workspace) + piece_a};
+  return conv_wgrad_wino_pair_launch(oa, ap, ob, (hipStream_t)stream);
+}
+
 extern "C" int lvae_conv2d_wgrad_bf16(const lvae_conv_desc* d, const float* dy, float* dw, float* db, void* workspace,
                                       size_t workspace_bytes, void* stream) {
   LVAE_REQUIRE(d != nullptr, LVAE_EINVAL, "lvae_conv2d_wgrad_bf16: null descriptor");
@@ -657,7 +711,6 @@ extern "C" int lvae_conv2d_wgrad_bf16(const lvae_conv_desc* d, const float* dy, 
 
 // n independent weight gradients; same result as n calls of lvae_conv2d_wgrad_f32. Every entry is routed once (again only where its dy or
 // its workspace is not 16-byte aligned) and owns a 256-byte aligned piece of the workspace; wgrad_schedule says which entries share a launch.
-static size_t wgrad_piece(const WgradPlan& aligned) { return (aligned.workspace + 255) / 256 * 256; }
 
 extern "C" size_t lvae_conv2d_wgrad_grouped_workspace(const lvae_conv_desc* descs, int32_t n) {
   size_t tot = 0;

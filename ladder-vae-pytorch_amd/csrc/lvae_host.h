@@ -132,6 +132,11 @@ int conv_wgrad_tile_launch(const WgradOp* o, int n, hipStream_t s);  // n = 1: t
 bool conv_wgrad_wino_plan(const lvae_conv_desc* d, WgradPlan& p);
 int conv_wgrad_wino_launch(const WgradOp* o, int n, hipStream_t s);  // n = 1: the single kernel, else the grouped one
 int conv_wgrad_wino_apply_launch(const WgradOp& o, const lvae_bn_apply* ap, hipStream_t s);
+// The two gradients of a residual block as one launch pair (A: apply_ok, with ap in front; B: a real dy), for two routed Winograd plans of
+// one geometry with 64 output channels: the plan re-splits the ranges between them (pa / pb: slabs and workspace of each; sched, if not
+// null: ranges, chunks per range, workgroups of A, then of B), the launch runs that split.
+bool conv_wgrad_wino_pair_plan(const lvae_conv_desc* da, const lvae_conv_desc* db, WgradPlan& pa, WgradPlan& pb, int32_t* sched);
+int conv_wgrad_wino_pair_launch(const WgradOp& a, const lvae_bn_apply* ap, const WgradOp& b, hipStream_t s);
 
 // conv1x1_wgrad.hip
 bool conv1x1_wgrad_plan(const lvae_conv_desc* d, WgradPlan& p);

@@ -723,6 +723,59 @@ def conv2d_wgrad_apply(x, weight, g, dweight, dbias, parts, dh, xbn, coef0, act,
     return dy
 
 
+def _wgrad_pair_descs(x_a, w_a, g_a, x_b, w_b, g_b, in_a=(None, None, None), in_b=(None, None, None)):
+    """The descriptors of a residual block's two weight gradients (A: conv1 on x_a, B: conv2 on x_b), None where the shapes cannot be a pair."""
+    if precision != PREC_F32 or _ddi is not None or g_a.transposed or g_b.transposed:
+        return None
+    if x_a.dim() != 4 or x_b.dim() != 4:
+        return None
+    N, H, W, _ = x_a.shape
+    d_a = _desc(g_a, w_a, x_a, None, N, H, W, H, W, g_a.Cout, g_a.s_ci, g_a.s_co, GATHER_CONV, None, *in_a)
+    N, H, W, _ = x_b.shape
+    d_b = _desc(g_b, w_b, x_b, None, N, H, W, H, W, g_b.Cout, g_b.s_ci, g_b.s_co, GATHER_CONV, None, *in_b)
+    return d_a, d_b
+
+
+def conv2d_wgrad_pair_ok(x_a, w_a, g_a, x_b, w_b, g_b):
+    """True when conv2d_wgrad_pair takes the two 3x3 convolutions of a residual block (conv1 = (w_a, g_a) on x_a, conv2 = (w_b, g_b) on x_b)."""
+    ds = _wgrad_pair_descs(x_a, w_a, g_a, x_b, w_b, g_b)
+    return ds is not None and bool(_C.load().lvae_conv2d_wgrad_pair_ok(C.byref(ds[0]), C.byref(ds[1])))
+
+
+def conv2d_wgrad_pair_schedule(x_a, w_a, g_a, x_b, w_b, g_b):
+    """((ranges, chunks per range, workgroups) of A, the same of B) as the pair launch splits the chip, or None where it declines. No launch."""
+    ds = _wgrad_pair_descs(x_a, w_a, g_a, x_b, w_b, g_b)
+    out = (C.c_int32 * 6)()
+    if ds is None or not _C.load().lvae_conv2d_wgrad_pair_schedule(C.byref(ds[0]), C.byref(ds[1]), out):
+        return None
+    return tuple(out[:3]), tuple(out[3:])
+
+
+def conv2d_wgrad_pair(x, weight, g, dweight, dbias, parts, dh, xbn, coef0, act, dgamma, dbeta, dy_b, weight_b, g_b, dweight_b, dbias_b,
+                      drop=None, in_scale=None, in_shift=None, in_act=None, in_scale_b=None, in_shift_b=None, in_act_b=None, out=None):
+    """conv2d_wgrad_apply(x, weight, g, dweight, dbias, parts, dh, xbn, ...) and conv2d_wgrad(xbn, dy_b, weight_b, g_b, dweight_b, dbias_b,
+    in_scale_b ...) of one residual block as one launch and one slab reduce (conv2 reads the tensor whose BatchNorm conv1's apply
+    differentiates). Returns the stored dy of A (out: written into this tensor instead of a new one). Only where conv2d_wgrad_pair_ok()."""
+    _chk_nhwc(x, 'x')
+    _chk_nhwc(xbn, 'xbn')
+    _chk_nhwc(dy_b, 'dy_b')
+    N, H, W, _ = x.shape
+    if tuple(dweight.stride()) != tuple(weight.stride()) or tuple(dweight_b.stride()) != tuple(weight_b.stride()):
+        raise _C.LvaeHipError("conv2d_wgrad_pair: gradient strides differ from weight strides")
+    ds = _wgrad_pair_descs(x, weight, g, xbn, weight_b, g_b, (in_scale, in_shift, in_act), (in_scale_b, in_shift_b, in_act_b))
+    if ds is None:
+        raise _C.LvaeHipError("conv2d_wgrad_pair: not a pair (fp32 precision, plain convolutions)")
+    d_a, d_b = ds
+    d_b.y_dtype = _dt(dy_b)
+    need = _C.load().lvae_conv2d_wgrad_pair_workspace(C.byref(d_a), C.byref(d_b))
+    ws = workspace(need, x.device)
+    dy = out if out is not None else torch.empty((N, H, W, g.Cout), dtype=torch.float32, device=x.device)
+    ap = _C.BnApply(ptr(parts), parts.shape[0], ACT[act], N * H * W, ptr(coef0), ptr(dh), ptr(xbn), None, ptr(dgamma), ptr(dbeta), ptr(dy), 0, 0, ptr(drop))
+    call('lvae_conv2d_wgrad_pair_f32', C.byref(d_a), C.byref(ap), C.byref(d_b), ptr_dt(dy_b), ptr(dweight), ptr(dbias), ptr(dweight_b), ptr(dbias_b),
+         ws.data_ptr(), ws.numel(), stream_ptr())
+    return dy
+
+
 def conv1x1_dgrad_cat(dy, weight, g, C1):
     """Both halves of the input gradient of a 1x1 / stride-1 convolution whose input was the channel concat (x [.., C1], x2 [.., Cin - C1]),
     in one launch: returns (dx, dx2), or None when the shape is not the single-shot 1x1 kernel's (the caller launches one dgrad per half)."""

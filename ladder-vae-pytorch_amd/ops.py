@@ -252,14 +252,25 @@ class ResBlockFn(Function):
         else:
             dy2 = _bwd_gate(blk, plan, dout, y2, ab, m2)
             cv1, bn2 = blk.conv1, blk.bn2
-            dh2, parts2 = _bwd_half(ctx, blk.conv2, bn2, y1, dy2, coef2)
+            cv2 = blk.conv2
+            # the pair: conv2's weight gradient waits for conv1's launch (nothing reads it before the end of the block)
+            paired = (plan.wgrad_pair and _side['stream'] is None and dy2.dtype == torch.float32 and bn2 is not None and ctx.training and
+                      K.bn_coef_block(*coef2))
+            dh2, parts2 = _bwd_half(ctx, cv2, bn2, y1, dy2, coef2, wgrad_done=paired)
             absorbed = (plan.wgrad_absorbs_apply and parts2 is not None and _side['stream'] is None and dh2.dtype == torch.float32)
-            if absorbed:
+            if paired and absorbed:
+                dy1 = K.conv2d_wgrad_pair(x, cv1.weight, cv1.geom(), grad_buf(cv1.weight), grad_buf(cv1.bias), parts2, dh2, y1, sc2, act,
+                                          grad_buf(bn2.weight), grad_buf(bn2.bias), dy2, cv2.weight, cv2.geom(), grad_buf(cv2.weight),
+                                          grad_buf(cv2.bias), drop=m1, in_scale=sc1, in_shift=sh1, in_act=act, in_scale_b=sc2, in_shift_b=sh2,
+                                          in_act_b=act)
+            elif absorbed:
                 # >= 16x16 levels (fp32): the BatchNorm-2 apply runs inside conv1's weight-gradient kernel, which needs its result as an operand
                 # anyway (and stores it for the dgrad below): one launch, its finalize and one tensor pass less
                 dy1 = K.conv2d_wgrad_apply(x, cv1.weight, cv1.geom(), grad_buf(cv1.weight), grad_buf(cv1.bias), parts2, dh2, y1, sc2, act,
                                            grad_buf(bn2.weight), grad_buf(bn2.bias), drop=m1, in_scale=sc1, in_shift=sh1, in_act=act)
             else:
+                if paired:   # the dgrad left no partial sums after all: conv2's gradient as a launch of its own, late
+                    wgrad(y1, dy2, cv2.weight, cv2.geom(), grad_buf(cv2.weight), grad_buf(cv2.bias), in_scale=sc2, in_shift=sh2, in_act=act)
                 dy1 = _bwd_apply(ctx, bn2, parts2, dh2, y1, coef2, drop=m1, out_bf16=plan.bf16_internals)
             dh1, parts1 = _bwd_half(ctx, cv1, blk.bn1, x, dy1, coef1, wgrad_done=absorbed)
         if parts1 is not None and ctx.defer is not None and (dh1.dtype == torch.float32 or ctx.defer[1] == 'any-dh') and K.bn_coef_block(*coef1):

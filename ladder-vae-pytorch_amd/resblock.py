@@ -19,6 +19,8 @@ class Switches:
         self.dgrad_cat = on('LVAE_DGRAD_CAT')                         # both halves of a channel concat's input gradient from one launch
         self.wgrad_apply = on('LVAE_WGRAD_APPLY')                     # conv1's weight gradient absorbs the BatchNorm-2 apply ...
         self.wgrad_apply_maxw = int(env.get('LVAE_WGRAD_APPLY_MAXW', '16'))   # ... up to this width: 32x32 measured +0.09 ms (profiles/r05_wgrad_apply_ab.txt)
+        self.wgrad_pair = on('LVAE_WGRAD_PAIR')                       # ... and conv2's weight gradient rides in the same launch (kernels.conv2d_wgrad_pair) ...
+        self.wgrad_pair_maxw = int(env.get('LVAE_WGRAD_PAIR_MAXW', '16'))     # ... up to this width (profiles/wgrad_pair_ab.txt)
         self.gate_stats = env.get('LVAE_NO_GATE_STATS') is None       # the gate epilogue writes the next block's BatchNorm partials
         self.defer_apply = on('LVAE_DEFER_APPLY')                     # a block leaves its last BatchNorm apply to its producer (BlockPlan.accepts)
         self.defer_apply_large = on('LVAE_DEFER_APPLY_LARGE')         # ... also into the persistent gate-backward kernel of the >= 16x16 levels
@@ -49,6 +51,7 @@ class BlockPlan(NamedTuple):
     gate_stats: bool            # the gate epilogue writes the BatchNorm partials of the block output (the next block's input)
     backward: Optional[str]
     wgrad_absorbs_apply: bool   # conv1's weight-gradient kernel may form the BatchNorm-2 apply itself (ResBlockFn.backward has the run-time rest)
+    wgrad_pair: bool            # ... and the block's two weight gradients go out as a pair, in that launch (same run-time rest)
     accepts: Optional[str]      # deferred BatchNorm-1 apply of the NEXT block that this block's first backward launch can absorb:
                                 # None | 'f32-dh' (only with an fp32 dh) | 'any-dh'. The one place that says so; tagged() publishes it.
 
@@ -70,7 +73,7 @@ def plan_block(blk, x, training):
     else:
         forward = 'per-op' if gate is not None else 'ungated'
     gate_stats = gate is not None and training and bn1 is not None and bn1.running_mean is not None and sw.gate_stats
-    backward, accepts, absorbs = None, None, False
+    backward, accepts, absorbs, pair = None, None, False, False
     if grad and whole_bwd:
         backward, accepts = 'whole-image', 'f32-dh'
     elif grad:
@@ -82,7 +85,9 @@ def plan_block(blk, x, training):
                 accepts = 'any-dh'
         absorbs = bool(training and bn2 is not None and sw.wgrad_apply and not s16 and cv1.weight.requires_grad and
                        x.shape[2] <= sw.wgrad_apply_maxw and K.conv2d_wgrad_apply_ok(x, cv1.weight, cv1.geom()))
-    return BlockPlan(forward, s16, gate_stats, backward, absorbs, accepts)
+        pair = bool(absorbs and sw.wgrad_pair and cv2.weight.requires_grad and x.shape[2] <= sw.wgrad_pair_maxw and
+                    K.conv2d_wgrad_pair_ok(x, cv1.weight, cv1.geom(), x, cv2.weight, cv2.geom()))   # (conv2's input has conv1's output shape = x's: 64 -> 64)
+    return BlockPlan(forward, s16, gate_stats, backward, absorbs, pair, accepts)
 
 
 class Handover(NamedTuple):
