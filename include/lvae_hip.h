@@ -278,6 +278,20 @@ int32_t lvae_conv1x1_gate_bwd_wgrad_apply_ok(const lvae_conv_desc* d);
 int lvae_conv1x1_gate_bwd_wgrad_f32(const lvae_conv_desc* d, const float* dout, const float* ab, const float* y, int32_t act,
                                     float* dw, int64_t dw_sk, int64_t dw_sn, float* db, void* workspace, size_t workspace_bytes,
                                     const lvae_bn_apply* ap, void* stream);
+/* The same launch WITHOUT the saved pre-activations (fp32 six-product form only): where the forward was lvae_resblock_conv_f32 with the
+ * gate epilogue of the 256-pixel Winograd kernel and ext->ab == NULL, ab = conv1x1(y) + gate_bias was never written. The kernel forms it
+ * again per 64-pixel tile from y (which it stages anyway for the weight gradient) and the gate weights pre-split for the FORWARD direction:
+ * gate_ws / gate_ws_bytes / gate_ws_ready exactly as in lvae_rb_ext for that forward call (lvae_resblock_gate_workspace() bytes of the
+ * 64 -> 128 descriptor; not ready: written here first from gate_w, element (ci, co) at gate_w[ci*gate_w_sk + co*gate_w_sn]), in the
+ * forward's accumulation order: the recomputed values are the forward's bit for bit, and so is every result. gate_bias [128] or NULL.
+ * `d`, dout, y, act, dw .. ap as for lvae_conv1x1_gate_bwd_wgrad_f32 (same workspace). lvae_conv1x1_gate_bwd_wgrad_recompute_ok(d): 1
+ * when it takes `d` (with or without `ap`): lvae_conv1x1_gate_bwd_wgrad_apply_ok(d), fp32-stored tensors, precision LVAE_PREC_F32, form
+ * not LVAE_FORM_F32_MFMA. Host only, no launch. */
+int32_t lvae_conv1x1_gate_bwd_wgrad_recompute_ok(const lvae_conv_desc* d);
+int lvae_conv1x1_gate_bwd_wgrad_recompute_f32(const lvae_conv_desc* d, const float* dout, const float* y, int32_t act, void* gate_ws,
+                                              int64_t gate_ws_bytes, int32_t gate_ws_ready, const float* gate_w, int64_t gate_w_sk,
+                                              int64_t gate_w_sn, const float* gate_bias, float* dw, int64_t dw_sk, int64_t dw_sn,
+                                              float* db, void* workspace, size_t workspace_bytes, const lvae_bn_apply* ap, void* stream);
 
 /* ------------------------------------------------------------------------------------------------------------
  * Fused residual-block kernels of the low-resolution levels (H*W a divisor of 64: 8x8, 4x4, 2x2 ...), "whole-image tiles"

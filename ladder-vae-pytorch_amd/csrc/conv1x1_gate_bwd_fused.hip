@@ -42,6 +42,8 @@ struct GbfArgs {
   int M, ohw, ntiles, act;
   int in_bf16, dx_bf16;  // storage of ab and y (lvae_conv_desc.x_dtype) and of dx (y_dtype); dout is fp32. bf16-operand kernel only.
   lvae_bn_apply ap;      // deferred BatchNorm-backward apply that produces dout (ap.parts == nullptr: dout is given)
+  const __bf16* gws;     // RC: the gate weights pre-split for the FORWARD, [4 k-steps][4 column tiles][3 pieces][64 lanes][8] (ab is null)
+  const float* gbias;    // RC: gate bias [128] or null
 };
 
 constexpr int GB_LDA = 132;  // dab / weight row pitch (floats): conflict-free ds_read_b128 (as conv1x1.hip)
@@ -210,16 +212,24 @@ constexpr size_t gbb_lds(int split) {
 // ELU: both activation ids of the launch are LVAE_ACT_ELU (the model's default), known at compile time. With run-time ids every one of the
 // staging loop's 16 per-element activation calls is a chain of scalar compares and taken branches (the emitted staging segment of the
 // round-4 kernel held ~300 branch instructions; resblock_img.hip found the same in round 4).
-template <int SPLIT, bool S16 = false, bool AP = false, bool ELU = false>
+// RC (six-product form only): ab was never stored. The forward's gate section (conv3x3_wino2_kernel<true>) formed it from the y tile and the
+// pre-split gate planes a.gws; this kernel holds the same y pieces in Ys (same split, same pitch) and repeats that GEMM per tile: eight
+// waves, one 32 x 32 block of the [64 px][128] tile each, k-step outside and PieceOrder<3> inside - the forward's order per accumulator,
+// so the recomputed pre-activations are the forward's bit for bit. The fp32 tile goes through the dab plane region (dead between tiles)
+// into the registers that otherwise hold the prefetched ab rows. One 33.5 MB read per launch at 256x16x16 (and the forward's write) less
+// against 24 bf16 MFMAs per wave and three LDS barriers per tile.
+template <int SPLIT, bool S16 = false, bool AP = false, bool ELU = false, bool RC = false>
 __global__ __launch_bounds__(512) void conv1x1_gate_bwd_fused_bf16_kernel(GbfArgs a) {
   kernarg_warmup<sizeof(GbfArgs)>();
 #ifdef LVAE_GBF_DBG  // compile-time phase-skip mask of the profiling builds (tools/gbf_ab.sh); never defined in the product
   constexpr int dbg = LVAE_GBF_DBG;  // 1: no global loads, 2: no MFMAs, 4: no global stores, 8: no gate derivative arithmetic
+                                     // RC: 16: no recompute MFMAs, 32: no trip of the recomputed tile through LDS (and its two barriers)
 #else
   constexpr int dbg = 0;
 #endif
   const int gact = ELU ? LVAE_ACT_ELU : a.act, apact = ELU ? LVAE_ACT_ELU : a.ap.act;
   static_assert(SPLIT == 1 || !S16, "bf16 storage exists for the bf16-operand form only");
+  static_assert(!RC || (SPLIT == 3 && !S16), "the recomputed pre-activations exist in the six-product form only");
   extern __shared__ __attribute__((aligned(16))) unsigned char smem_raw[];
   constexpr int A_PLANE = 64 * GBB_LDA, Y_PLANE = 64 * GBB_LDY;
   __bf16* As = reinterpret_cast<__bf16*>(smem_raw);                 // [SPLIT][64 px][136]: dab tile
@@ -321,8 +331,10 @@ __global__ __launch_bounds__(512) void conv1x1_gate_bwd_fused_bf16_kernel(GbfArg
     } else {
       pg[u] = *reinterpret_cast<const f32x4*>(a.dout + mc * 64 + c4);
     }
-    pa[u] = load4_dt(a.ab, mc * 128 + c4, a.in_bf16 != 0);
-    pb[u] = load4_dt(a.ab, mc * 128 + 64 + c4, a.in_bf16 != 0);
+    if (!RC) {
+      pa[u] = load4_dt(a.ab, mc * 128 + c4, a.in_bf16 != 0);
+      pb[u] = load4_dt(a.ab, mc * 128 + 64 + c4, a.in_bf16 != 0);
+    }
     py[u] = load4_dt(a.y, mc * 64 + c4, a.in_bf16 != 0);
   };
   auto prefetch = [&](int tile) {
@@ -370,6 +382,23 @@ __global__ __launch_bounds__(512) void conv1x1_gate_bwd_fused_bf16_kernel(GbfArg
   const int trow = 8 * (G >> 1) + (i16 >> 2), tch = 16 * (G & 1) + 4 * (i16 & 3);
   using PO = PieceOrder<SPLIT>;   // the loops with an instrument branch (dbg & 2) index the shared piece order themselves
 
+  // RC: this wave's block of the pre-activation tile (pixel rows 32 rrb .., column tile rct of {a0, a1, b0, b1}), its B fragments of the
+  // four k-steps (plain loads: the compiler tracks them) and this thread's bias values
+  const int rrb = wave >> 2, rct = wave & 3;
+  bf16x8 gq[RC ? 4 : 1][SPLIT];
+  f32x4 gba = zero4, gbb = zero4;
+  if (RC) {
+    const __bf16* gws = a.gws + lane * 8;
+#pragma unroll
+    for (int s4 = 0; s4 < 4; ++s4)
+#pragma unroll
+      for (int q = 0; q < SPLIT; ++q) gq[s4][q] = *reinterpret_cast<const bf16x8*>(gws + ((size_t)(s4 * 4 + rct) * SPLIT + q) * 512);
+    if (a.gbias) {
+      gba = *reinterpret_cast<const f32x4*>(a.gbias + c4);
+      gbb = *reinterpret_cast<const f32x4*>(a.gbias + 64 + c4);
+    }
+  }
+
   int tile = blockIdx.x;
   if (tile < a.ntiles) prefetch(tile);
   for (; tile < a.ntiles; tile += gridDim.x) {
@@ -403,7 +432,50 @@ __global__ __launch_bounds__(512) void conv1x1_gate_bwd_fused_bf16_kernel(GbfArg
       *reinterpret_cast<bf16x8*>(As + r8 * GBB_LDA + c8) = to_bf16x8(lo[0], lo[1]);
       *reinterpret_cast<bf16x8*>(As + r8 * GBB_LDA + 64 + c8) = to_bf16x8(hi[0], hi[1]);
       *reinterpret_cast<bf16x8*>(Ys + r8 * GBB_LDY + c8) = yv;
-    } else
+    } else {
+    if (RC) {
+      // ---- the y pieces first, then ab = y . Wg + bias as the forward formed it
+#pragma unroll
+      for (int u = 0; u < IT; ++u) {
+        const int r = r0 + 32 * u;
+        bf16x4 pyv[SPLIT];
+        split4<SPLIT>(m0 + r < a.M ? py[u] : zero4, pyv);
+#pragma unroll
+        for (int q = 0; q < SPLIT; ++q) *reinterpret_cast<bf16x4*>(Ys + q * Y_PLANE + r * GBB_LDY + c4) = pyv[q];
+      }
+      lds_barrier();
+      f32x16 accq;
+#pragma unroll
+      for (int r = 0; r < 16; ++r) accq[r] = 0.f;
+#pragma unroll
+      for (int s4 = 0; s4 < 4; ++s4) {
+        bf16x8 af[SPLIT];
+#pragma unroll
+        for (int q = 0; q < SPLIT; ++q)
+          af[q] = *reinterpret_cast<const bf16x8*>(Ys + q * Y_PLANE + (rrb * 32 + li) * GBB_LDY + 16 * s4 + 8 * lh);
+#pragma unroll
+        for (int k = 0; k < PO::N; ++k) { if (dbg & 16) accq[k] += (float)af[PO::A[k]][0] * (float)gq[RC ? s4 : 0][PO::B[k]][1]; else accq = __builtin_amdgcn_mfma_f32_32x32x16_bf16(af[PO::A[k]], gq[RC ? s4 : 0][PO::B[k]], accq, 0, 0, 0); }
+      }
+      if (dbg & 32) {
+#pragma unroll
+        for (int u = 0; u < IT; ++u) {
+          pa[u] = gba + accq[u];
+          pb[u] = gbb + accq[2 + u];
+        }
+      } else {
+      float* Qs = reinterpret_cast<float*>(As);   // [64 px][132] floats = 33,792 B of the dab planes' 52,224 B (dead until the staging below)
+#pragma unroll
+      for (int r = 0; r < 16; ++r) Qs[(rrb * 32 + (r & 3) + 8 * (r >> 2) + 4 * lh) * GB_LDA + rct * 32 + li] = accq[r];
+      lds_barrier();
+#pragma unroll
+      for (int u = 0; u < IT; ++u) {
+        const int r = r0 + 32 * u;
+        pa[u] = *reinterpret_cast<const f32x4*>(Qs + r * GB_LDA + c4) + gba;
+        pb[u] = *reinterpret_cast<const f32x4*>(Qs + r * GB_LDA + 64 + c4) + gbb;
+      }
+      lds_barrier();   // every thread has its rows: the staging below overwrites the tile with the dab planes
+      }
+    }
 #pragma unroll
     for (int u = 0; u < IT; ++u) {
       const int r = r0 + 32 * u;
@@ -436,8 +508,9 @@ __global__ __launch_bounds__(512) void conv1x1_gate_bwd_fused_bf16_kernel(GbfArg
       for (int q = 0; q < SPLIT; ++q) {
         *reinterpret_cast<bf16x4*>(As + q * A_PLANE + r * GBB_LDA + c4) = pl[q];
         *reinterpret_cast<bf16x4*>(As + q * A_PLANE + r * GBB_LDA + 64 + c4) = ph[q];
-        *reinterpret_cast<bf16x4*>(Ys + q * Y_PLANE + r * GBB_LDY + c4) = pyv[q];
+        if (!RC) *reinterpret_cast<bf16x4*>(Ys + q * Y_PLANE + r * GBB_LDY + c4) = pyv[q];
       }
+    }
     }
     if (S16 && tile + (int)gridDim.x < a.ntiles) prefetch(tile + gridDim.x);
     lds_barrier();  // the dab / y tiles are published; the prefetched rows stay in flight
@@ -579,16 +652,37 @@ bool conv1x1_gate_bwd_fused_plan(const lvae_conv_desc* d, bool with_apply, ConvP
   return true;
 }
 
+// The recompute form (RC) of a planned descriptor: the six-product fp32 kernel on fp32-stored tensors. What its entry point checks besides:
+// the forward-direction gate planes (resblock_gate_ws_bytes of the 64 -> 128 convolution, three pieces).
+static bool gbf_recompute_plan(const lvae_conv_desc* d, bool with_apply, ConvPlan& p) {
+  static const bool off = tune("LVAE_DISABLE_GATE_RECOMPUTE", 0) != 0;  // A/B switch (tuning builds only)
+  if (off || !conv1x1_gate_bwd_fused_plan(d, with_apply, p)) return false;
+  return d->precision == LVAE_PREC_F32 && d->form != LVAE_FORM_F32_MFMA && d->x_dtype != LVAE_DT_BF16 && d->y_dtype != LVAE_DT_BF16;
+}
+static size_t gbf_planes_bytes() {
+  lvae_conv_desc g = lvae_conv_desc{};
+  g.C1 = 64;
+  g.Cout = 128;
+  return resblock_gate_ws_bytes(&g, 3);
+}
+
 #define GBF_REQUIRE_AL16(p) LVAE_REQUIRE(al16_or_null(p), LVAE_EALIGN, "lvae_conv1x1_gate_bwd_wgrad_f32: " #p " must be 16-byte aligned")
 
-// runs the planned kernel; checks only the alignment of the operands the plan cannot see
+// runs the planned kernel; checks only the alignment of the operands the plan cannot see. ab null: the recompute form of a descriptor
+// gbf_recompute_plan took, with the forward's gate planes gws (written) and the gate bias.
 static int conv1x1_gate_bwd_fused_launch(const lvae_conv_desc* d, const float* dout, const float* ab, const float* y, int act, float* dw,
-                                         int64_t dw_sk, int64_t dw_sn, float* db, void* workspace, const lvae_bn_apply* ap, hipStream_t s) {
+                                         int64_t dw_sk, int64_t dw_sn, float* db, void* workspace, const lvae_bn_apply* ap, hipStream_t s,
+                                         const void* gws = nullptr, const float* gbias = nullptr) {
   GBF_REQUIRE_AL16(dout);
   GBF_REQUIRE_AL16(ab);
   GBF_REQUIRE_AL16(y);
   GBF_REQUIRE_AL16(workspace);
+  GBF_REQUIRE_AL16(gws);
+  GBF_REQUIRE_AL16(gbias);
+  const bool rcp = ab == nullptr;
   GbfArgs a;
+  a.gws = static_cast<const __bf16*>(gws);
+  a.gbias = gbias;
   a.ap = lvae_bn_apply{};
   if (ap != nullptr && ap->parts != nullptr) {
     GBF_REQUIRE_AL16(ap->parts);
@@ -638,6 +732,10 @@ static int conv1x1_gate_bwd_fused_launch(const lvae_conv_desc* d, const float* d
     constexpr size_t lds3 = gbb_lds(3);
     int rc;
     if (f32_mfma) rc = launch_lds<conv1x1_gate_bwd_fused_kernel>(name, grid, block, lds, (int)lds, s, a);
+    else if (rcp && with_ap && elu) rc = launch_lds<conv1x1_gate_bwd_fused_bf16_kernel<3, false, true, true, true>>(name, grid, block, lds3, (int)lds3, s, a);
+    else if (rcp && with_ap) rc = launch_lds<conv1x1_gate_bwd_fused_bf16_kernel<3, false, true, false, true>>(name, grid, block, lds3, (int)lds3, s, a);
+    else if (rcp && elu) rc = launch_lds<conv1x1_gate_bwd_fused_bf16_kernel<3, false, false, true, true>>(name, grid, block, lds3, (int)lds3, s, a);
+    else if (rcp) rc = launch_lds<conv1x1_gate_bwd_fused_bf16_kernel<3, false, false, false, true>>(name, grid, block, lds3, (int)lds3, s, a);
     else if (with_ap && elu) rc = launch_lds<conv1x1_gate_bwd_fused_bf16_kernel<3, false, true, true>>(name, grid, block, lds3, (int)lds3, s, a);
     else if (with_ap) rc = launch_lds<conv1x1_gate_bwd_fused_bf16_kernel<3, false, true, false>>(name, grid, block, lds3, (int)lds3, s, a);
     else if (elu) rc = launch_lds<conv1x1_gate_bwd_fused_bf16_kernel<3, false, false, true>>(name, grid, block, lds3, (int)lds3, s, a);
@@ -679,4 +777,38 @@ extern "C" int lvae_conv1x1_gate_bwd_wgrad_f32(const lvae_conv_desc* d, const fl
                "LVAE_FORM_F32_MFMA); use lvae_conv1x1_gate_bwd_f32 + lvae_conv2d_wgrad_f32");
   LVAE_REQUIRE(workspace_bytes >= p.workspace, LVAE_EWORKSPACE, "lvae_conv1x1_gate_bwd_wgrad_f32: workspace %zu < %zu", workspace_bytes, p.workspace);
   return conv1x1_gate_bwd_fused_launch(d, dout, ab, y, act, dw, dw_sk, dw_sn, db, workspace, ap, (hipStream_t)stream);
+}
+
+extern "C" int32_t lvae_conv1x1_gate_bwd_wgrad_recompute_ok(const lvae_conv_desc* d) {
+  ConvPlan p;
+  return gbf_recompute_plan(d, false, p) && gbf_recompute_plan(d, true, p) ? 1 : 0;
+}
+
+extern "C" int lvae_conv1x1_gate_bwd_wgrad_recompute_f32(const lvae_conv_desc* d, const float* dout, const float* y, int32_t act, void* gate_ws,
+                                                         int64_t gate_ws_bytes, int32_t gate_ws_ready, const float* gate_w, int64_t gate_w_sk,
+                                                         int64_t gate_w_sn, const float* gate_bias, float* dw, int64_t dw_sk, int64_t dw_sn,
+                                                         float* db, void* workspace, size_t workspace_bytes, const lvae_bn_apply* ap,
+                                                         void* stream) {
+  const char* who = "lvae_conv1x1_gate_bwd_wgrad_recompute_f32";
+  const bool with_ap = ap != nullptr && ap->parts != nullptr;
+  LVAE_REQUIRE(d && (dout || with_ap) && y && d->y && dw && workspace, LVAE_EINVAL, "%s: null pointer", who);
+  if (with_ap)
+    LVAE_REQUIRE(ap->rows > 0 && ap->M == (int64_t)d->N * d->H * d->W && ap->coef && ap->dh && ap->x && ap->out, LVAE_EINVAL,
+                 "%s: deferred apply needs parts / rows, M = N*H*W, the coefficient block, dh, x and out", who);
+  ConvPlan p;
+  LVAE_REQUIRE(gbf_recompute_plan(d, with_ap, p), LVAE_EINVAL,
+               "%s: not supported (needs what lvae_conv1x1_gate_bwd_wgrad_f32 needs, fp32 tensors, precision LVAE_PREC_F32 and not "
+               "LVAE_FORM_F32_MFMA: lvae_conv1x1_gate_bwd_wgrad_recompute_ok)", who);
+  LVAE_REQUIRE(workspace_bytes >= p.workspace, LVAE_EWORKSPACE, "%s: workspace %zu < %zu", who, workspace_bytes, p.workspace);
+  LVAE_REQUIRE(gate_ws != nullptr && al16_or_null(gate_ws) && gate_ws_bytes >= 0 && (size_t)gate_ws_bytes >= gbf_planes_bytes() &&
+                   (gate_ws_ready || gate_w != nullptr),
+               LVAE_EWORKSPACE, "%s: gate_ws missing or smaller than lvae_resblock_gate_workspace() of the forward gate, or not ready and no gate_w", who);
+  if (!gate_ws_ready) {  // the planes of the forward direction (64 -> 128), as lvae_resblock_conv_f32 writes them for its gate epilogue
+    lvae_conv_desc g = lvae_conv_desc{};
+    g.w = gate_w; g.w_sk = gate_w_sk; g.w_sn = gate_w_sn; g.precision = LVAE_PREC_F32; g.C1 = 64; g.Cout = 128;
+    g.workspace = gate_ws; g.workspace_bytes = gate_ws_bytes;
+    const int rc = resblock_gate_prepare_single(&g, 3, (hipStream_t)stream);
+    if (rc) return rc;
+  }
+  return conv1x1_gate_bwd_fused_launch(d, dout, nullptr, y, act, dw, dw_sk, dw_sn, db, workspace, ap, (hipStream_t)stream, gate_ws, gate_bias);
 }

@@ -111,7 +111,9 @@ int conv1x1_launch(const lvae_conv_desc* d, const PwForm& f, hipStream_t s);
 bool conv1x1_gate_fwd_plan(const lvae_conv_desc* d, ConvPlan& p);
 int conv1x1_gate_fwd_launch(const lvae_conv_desc* d, const ConvPlan& p, const float* res, float* out, int act, hipStream_t s);
 
-// conv1x1_gate_bwd_fused.hip: the persistent gate backward (p.workspace = its slabs); with_apply: with a deferred lvae_bn_apply
+// conv1x1_gate_bwd_fused.hip: the persistent gate backward (p.workspace = its slabs); with_apply: with a deferred lvae_bn_apply.
+// (Its recompute form, lvae_conv1x1_gate_bwd_wgrad_recompute_*, adds conditions to this plan inside that file and fills the forward's gate
+// planes through resblock_gate_prepare_single above: no declaration of its own here.)
 bool conv1x1_gate_bwd_fused_plan(const lvae_conv_desc* d, bool with_apply, ConvPlan& p);
 
 // conv_wgrad.hip

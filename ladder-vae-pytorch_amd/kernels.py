@@ -424,6 +424,41 @@ def conv1x1_gate_bwd_wgrad(dout, ab, y, weight, g, act, dweight, dbias, out_scal
     return dx
 
 
+def gate_bwd_recompute_ok(x_like, weight, g, dweight=None):
+    """True when conv1x1_gate_bwd_wgrad_recompute takes the gate convolution (weight, g) on tensors shaped like x_like (N,H,W,C), with or
+    without a deferred apply: the fp32 six-product form of the persistent gate backward, fp32-stored tensors."""
+    d = _gate_bwd_fused_desc(x_like, weight, g, dweight)
+    return d is not None and x_like.dtype == torch.float32 and bool(_C.load().lvae_conv1x1_gate_bwd_wgrad_recompute_ok(C.byref(d)))
+
+
+def conv1x1_gate_bwd_wgrad_recompute(dout, y, weight, g, bias, act, dweight, dbias, out_scale=None, apply=None):
+    """conv1x1_gate_bwd_wgrad without the saved pre-activations: the kernel forms ab = conv1x1(y) + bias again per tile, from y and the gate
+    weights as rb_conv_gate(..., want_ab=False) pre-split them, in the forward's accumulation order (the same bits). Returns dx, and
+    accumulates into dweight / dbias; None when the shape is not supported. apply: as for conv1x1_gate_bwd_wgrad."""
+    _chk_nhwc(dout, 'dout')
+    N, H, W, Cn = dout.shape
+    if g.Cout != 2 * Cn or tuple(dweight.stride()) != tuple(weight.stride()) or y.dtype != torch.float32:
+        return None
+    dx = torch.empty((N, H, W, g.Cin), dtype=torch.float32, device=dout.device)
+    d = _desc(g, weight, y, None, N, H, W, H, W, g.Cin, g.s_co, g.s_ci, GATHER_TRANSPOSED, out_scale=out_scale, y=dx)
+    d.C1 = g.Cout
+    lib = _C.load()
+    need = lib.lvae_conv1x1_gate_bwd_wgrad_workspace(C.byref(d))
+    if not need or not lib.lvae_conv1x1_gate_bwd_wgrad_recompute_ok(C.byref(d)):
+        return None
+    e = RbExt()
+    _rb_gate_ws(e, weight, g, dout.device, False)   # the forward's planes: the buffer (and its ready flag) the forward launch used
+    ws = workspace(need, dout.device)
+    ap = None
+    if apply is not None:
+        ap = _C.BnApply(ptr(apply.parts), apply.parts.shape[0], ACT[apply.act], N * H * W, ptr(apply.coef0), ptr_dt(apply.dh), ptr(apply.x),
+                        ptr(apply.add), ptr(apply.dgamma), ptr(apply.dbeta), ptr(apply.out), int(apply.dh.dtype == torch.bfloat16), 0)
+    call('lvae_conv1x1_gate_bwd_wgrad_recompute_f32', C.byref(d), ptr(dout), ptr(y), ACT[act], e.gate_ws, e.gate_ws_bytes, e.gate_ws_ready,
+         e.gate_w, e.gate_w_sk, e.gate_w_sn, ptr(bias), ptr(dweight), g.s_ci, g.s_co, ptr(dbias), ws.data_ptr(), ws.numel(),
+         C.byref(ap) if ap is not None else None, stream_ptr())
+    return dx
+
+
 # ----------------------------------------------------------------------------------------------------------------
 # Fused residual-block launches of the low-resolution levels (csrc/resblock_img.hip, lvae_resblock_conv_f32)
 def _rb_desc(x_like, weight, g, dgrad, y=None, bias=None, in_scale=None, in_shift=None, in_act=None, out_scale=None):
@@ -549,15 +584,19 @@ def rb_gate_rows(x, weight, g, whole_image=True):
 
 
 def rb_conv_gate(x, weight, g, bias, in_act, out_scale, gate_w, gate_g, gate_bias, res, act, in_bn=None, coef=None, stats_pivot=None,
-                 prefetch=None):
+                 prefetch=None, want_ab=True):
     """Second half of a gated residual block in one launch: y2 = (conv3x3(act(BN(x))) + bias) * out_scale, ab = conv1x1(y2) + gate_bias,
-    out = act(a) * sigmoid(b) + res, BatchNorm partials of out around stats_pivot. Returns (y2, ab, out, StatParts | None, coef)."""
+    out = act(a) * sigmoid(b) + res, BatchNorm partials of out around stats_pivot. Returns (y2, ab, out, StatParts | None, coef).
+    want_ab=False: ab is not stored and comes back as None (for a backward that forms it again, conv1x1_gate_bwd_wgrad_recompute; the
+    Winograd kernel's gate epilogue only)."""
     N, H, W, _ = x.shape
     dev = x.device
     y = torch.empty((N, H, W, g.Cout), dtype=torch.float32, device=dev)
-    ab = torch.empty((N, H, W, gate_g.Cout), dtype=torch.float32, device=dev)
     out = torch.empty((N, H, W, gate_g.Cout // 2), dtype=torch.float32, device=dev)
     d, need = _rb_desc(x, weight, g, False, y, bias, None, None, in_act, out_scale)
+    if need and not want_ab:
+        raise _C.LvaeHipError("rb_conv_gate: the whole-image kernels always store ab")
+    ab = torch.empty((N, H, W, gate_g.Cout), dtype=torch.float32, device=dev) if want_ab else None
     can_fold = True
     if not need:   # not a whole-image shape: the Winograd kernel with the gate behind it (its own transformed weights)
         _conv_ws(d, weight, dev)

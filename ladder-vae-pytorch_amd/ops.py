@@ -198,7 +198,8 @@ def _fwd_fused_gate(call, x, blk, m1, m2, training):
     call.out_pivot = coef1[2].detach() if call.plan.gate_stats else None   # this block's own batch mean: inside the data range of the residual stream
     y2, ab, out, call.out_parts, coef2 = K.rb_conv_gate(y1, cv2.weight, cv2.geom(), cv2.bias, act, m2, gate.weight, gate.geom(), gate.bias, x, act,
                                                         in_bn=in_bn, coef=coef2, stats_pivot=call.out_pivot,
-                                                        prefetch=st.next_ranges('fwd') if whole else None)
+                                                        prefetch=st.next_ranges('fwd') if whole else None,
+                                                        want_ab=not call.plan.recompute_ab)
     return y1, y2, ab, out, coef1, coef2
 
 
@@ -229,7 +230,9 @@ class ResBlockFn(Function):
         y1 = drop1(conv1(act(bn1(x))))
         y2 = drop2(conv2(act(bn2(y1))))
         out = gate(conv1x1(y2)) + x      or  y2 + x
-    Saved for backward: x, y1, y2, ab and the BN coefficients; act(bn(.)) is recomputed inside the wgrad loader."""
+    Saved for backward: x, y1, y2, ab and the BN coefficients; act(bn(.)) is recomputed inside the wgrad loader. With plan.recompute_ab
+    (fp32 'wino-gate' blocks with the persistent gate backward) ab is neither stored nor saved (None): that backward kernel forms it again
+    from y2, bit for bit as the forward did."""
 
     @staticmethod
     def forward(ctx, x, blk, m1, m2, training, call, *params):
@@ -305,8 +308,12 @@ def _bwd_gate(blk, plan, dout, y2, ab, m2):
     gw = gate.weight
     if plan.backward == 'persistent-gate':
         # large levels: gate derivative, dgrad and the gate convolution's weight gradient in one persistent kernel
-        dy2 = K.conv1x1_gate_bwd_wgrad(dout, ab, y2, gw, gate.geom(), act, grad_buf(gw), grad_buf(gate.bias), out_scale=m2, out_bf16=s16,
-                                       apply=blk.sched.take_pending(dout))
+        if plan.recompute_ab:
+            dy2 = K.conv1x1_gate_bwd_wgrad_recompute(dout, y2, gw, gate.geom(), gate.bias, act, grad_buf(gw), grad_buf(gate.bias), out_scale=m2,
+                                                     apply=blk.sched.take_pending(dout))
+        else:
+            dy2 = K.conv1x1_gate_bwd_wgrad(dout, ab, y2, gw, gate.geom(), act, grad_buf(gw), grad_buf(gate.bias), out_scale=m2, out_bf16=s16,
+                                           apply=blk.sched.take_pending(dout))
         if dy2 is None:
             raise K._C.LvaeHipError("residual block: the persistent gate backward the block was planned with did not take this shape")
         return dy2

@@ -31,6 +31,8 @@ class Switches:
         self.rb_gate_large = on('LVAE_RB_GATE_LARGE')                 # conv2 + gate in one launch at the >= 16x16 levels (Winograd kernel)
         self.stoch_block = on('LVAE_STOCH_BLOCK')                     # the stochastic block of the <= 8x8 levels in one forward launch (ops.StochBlockFn)
         self.stoch_block_bwd = on('LVAE_STOCH_BLOCK_BWD')             # ... and its backward in one launch
+        self.gate_recompute = on('LVAE_GATE_RECOMPUTE')               # 'wino-gate' blocks do not store ab; the persistent gate backward forms it again ...
+        self.gate_recompute_maxw = int(env.get('LVAE_GATE_RECOMPUTE_MAXW', '16'))   # ... up to this width: 32x32 measured -0.09 ms, inside the run-to-run range (profiles/gate_recompute_ab.txt)
 
 
 switches = Switches(os.environ)
@@ -54,6 +56,7 @@ class BlockPlan(NamedTuple):
     wgrad_pair: bool            # ... and the block's two weight gradients go out as a pair, in that launch (same run-time rest)
     accepts: Optional[str]      # deferred BatchNorm-1 apply of the NEXT block that this block's first backward launch can absorb:
                                 # None | 'f32-dh' (only with an fp32 dh) | 'any-dh'. The one place that says so; tagged() publishes it.
+    recompute_ab: bool = False  # the forward stores no gate pre-activations: the persistent gate backward forms them again from y2
 
 
 def plan_block(blk, x, training):
@@ -87,7 +90,9 @@ def plan_block(blk, x, training):
                        x.shape[2] <= sw.wgrad_apply_maxw and K.conv2d_wgrad_apply_ok(x, cv1.weight, cv1.geom()))
         pair = bool(absorbs and sw.wgrad_pair and cv2.weight.requires_grad and x.shape[2] <= sw.wgrad_pair_maxw and
                     K.conv2d_wgrad_pair_ok(x, cv1.weight, cv1.geom(), x, cv2.weight, cv2.geom()))   # (conv2's input has conv1's output shape = x's: 64 -> 64)
-    return BlockPlan(forward, s16, gate_stats, backward, absorbs, pair, accepts)
+    recompute = bool(forward == 'wino-gate' and backward == 'persistent-gate' and not s16 and sw.gate_recompute and
+                     x.shape[2] <= sw.gate_recompute_maxw and K.gate_bwd_recompute_ok(x, gate.weight, gate.geom(), gate.weight.grad))
+    return BlockPlan(forward, s16, gate_stats, backward, absorbs, pair, accepts, recompute)
 
 
 class Handover(NamedTuple):
