@@ -952,6 +952,27 @@ int lvae_adamax_guarded_step_f32(float* p, const float* g, float* exp_avg, float
                                  const lvae_lr_schedule* schedule, float beta1, float beta2, float eps, float weight_decay,
                                  const uint64_t* step_count, float* ema, float decay, float* lr_out,
                                  const lvae_grad_guard_state* guard, void* stream);
+/* A second update rule over the same arena: torch.optim.Adam / torch.optim.AdamW in the single-tensor form (no amsgrad, no maximize), one
+ * entry point for every combination the four Adamax entry points cover. exp_avg_sq [n] is the second moment. With n = step_count[0] and
+ * t = n + 1 the step's scalars are formed in double from the exact integer counter and the double betas and rounded to float once:
+ *   bc1 = 1 - beta1^t, bc2 = 1 - beta2^t, step_size = (float)(lr / bc1), rs = (float)sqrt(bc2)
+ * (1 - 0.999f misses 1 - 0.999 by 1.3e-5, which an fp32 bias correction would carry straight into the first update), and so are the
+ * element loop's constants (float)(1 - beta1), (float)beta2, (float)(1 - beta2), the floats torch's own scalars round to. lr is the
+ * argument, or the schedule's value at n when `schedule` is given (NULL: none; `lr` is then used). Per element not frozen by `mask`:
+ *   gg = g * gs;  if !decoupled: gg += weight_decay * p           (L2 decay, torch.optim.Adam)
+ *   if decoupled: p *= (float)(1 - (double)lr * weight_decay)     (torch.optim.AdamW: not scaled by gs; a frozen element does not decay)
+ *   m += (gg - m) * (1 - beta1);  v = v * beta2 + (1 - beta2) * gg * gg
+ *   p -= step_size * m / (sqrt(v) / rs + eps)                     (IEEE sqrt and division)
+ * and, with ema (NULL: none), the average's line and ramp of lvae_adamax_ema_step_f32; p, exp_avg and exp_avg_sq are bit for bit those
+ * of the call without it. gs is gscale[0] (NULL: 1). guard (NULL: none) has the meaning it has in lvae_adamax_guarded_step_f32: with
+ * guard->skip set every thread returns before its first store, lr_out included; otherwise gs is guard->scale. Giving both guard and gscale
+ * is LVAE_EINVAL. lr_out: device float[1] or NULL, receives the rate applied, with a schedule or without. LVAE_EINVAL also for a beta
+ * outside [0, 1), a negative eps or weight_decay, a decay outside [0, 1) with ema, an invalid schedule; LVAE_EALIGN for n % 4 != 0, an ema
+ * off 16 bytes or a guard off 8. Advance the counter as after the Adamax entry points. */
+int lvae_adam_step_f32(float* p, const float* g, float* exp_avg, float* exp_avg_sq, const float* mask, int64_t n, float lr,
+                       const lvae_lr_schedule* schedule /* or NULL */, double beta1, double beta2, float eps, float weight_decay,
+                       int32_t decoupled, const float* gscale /* or NULL */, const uint64_t* step_count, float* ema /* or NULL */,
+                       float decay, float* lr_out /* or NULL */, const lvae_grad_guard_state* guard /* or NULL */, void* stream);
 /* table: device array of n_entries {dst, src, n}; entry e is copied, dst[0:n] = src[0:n], by workgroup e, when flag == NULL or
  * flag[0] == want (flag: device int32[1], e.g. &guard->skip). The guarded step saves every BatchNorm running statistic into one shadow
  * buffer with it before the forward pass and puts them back after the guard on a skipped step. Entries must not overlap each other. */

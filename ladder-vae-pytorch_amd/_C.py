@@ -233,6 +233,8 @@ SIGNATURES = {
     'lvae_adamax_sched_step_f32': (C.c_int, [_P, _P, _P, _P, _P, _L, C.POINTER(LrScheduleStruct), _F, _F, _F, _F, _P, _P, _P, _F, _P, _P]),
     'lvae_grad_guard_f32': (C.c_int, [_P, _L, _P, _F, _F, _P, _P, _Z, _P]),
     'lvae_adamax_guarded_step_f32': (C.c_int, [_P, _P, _P, _P, _P, _L, _F, C.POINTER(LrScheduleStruct), _F, _F, _F, _F, _P, _P, _F, _P, _P, _P]),
+    'lvae_adam_step_f32': (C.c_int, [_P, _P, _P, _P, _P, _L, _F, C.POINTER(LrScheduleStruct), C.c_double, C.c_double, _F, _F, _I, _P, _P, _P,
+                                     _F, _P, _P, _P]),
     'lvae_multi_copy_f32': (C.c_int, [_P, _I, _P, _I, _P]),
     'lvae_swap_f32': (C.c_int, [_P, _P, _L, _P]),
     'lvae_sumsq_workspace': (_Z, [_L]),

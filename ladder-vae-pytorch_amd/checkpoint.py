@@ -4,11 +4,14 @@ The reference saves `model.state_dict()` through boilr (absent). The key scheme 
 identical, but its parameters are strided views of one flat arena; `state_dict_reference_layout` returns plain contiguous
 CPU tensors in the reference's memory layout, so a file written here loads into the reference's `LadderVAE` with
 `load_state_dict` and vice versa. Optimiser state is stored per parameter name (torch.optim.Adamax names: exp_avg,
-exp_inf) so it can be re-attached to either implementation. When the optimizer keeps an exponential moving average of the weights, the file
+exp_inf; torch.optim.Adam / AdamW names under those rules: exp_avg, exp_avg_sq) with the rule's name under 'rule', so it can be
+re-attached to either implementation. When the optimizer keeps an exponential moving average of the weights, the file
 also holds `'ema'`: a second complete state dict of the same keys, shapes and layout whose trainable parameters are the averages (buffers
 and frozen parameters as in `'model'`), so the averaged weights load into the reference's `LadderVAE` the same way.
 """
 import torch
+
+from .optim import RULES, check_rule
 
 
 def state_dict_reference_layout(model):
@@ -17,9 +20,11 @@ def state_dict_reference_layout(model):
 
 
 def optimizer_state_by_name(model, optimizer):
-    """{'step': int, 'state': {param_name: {'exp_avg', 'exp_inf'}}} in the parameters' logical shapes."""
+    """{'rule': 'adamax' | 'adam' | 'adamw', 'step': int, 'state': {param_name: {'exp_avg', second moment}}} in the parameters' logical
+    shapes, the second moment under torch's own name for the rule: 'exp_inf' (Adamax) or 'exp_avg_sq' (Adam, AdamW)."""
     arena = model.pack()
     optimizer._state()
+    second = RULES[optimizer.rule]
     out = {}
     named = dict(model.named_parameters())
     for name, (off, n) in arena.slots.items():
@@ -28,9 +33,9 @@ def optimizer_state_by_name(model, optimizer):
             continue
         # same strides as the parameter view -> same logical element order
         m = torch.as_strided(optimizer.exp_avg, p.shape, p.stride(), off).detach().cpu().contiguous().clone()
-        u = torch.as_strided(optimizer.exp_inf, p.shape, p.stride(), off).detach().cpu().contiguous().clone()
-        out[name] = {'exp_avg': m, 'exp_inf': u}
-    return {'step': int(optimizer.step_count.item()), 'state': out, 'lr': optimizer.lr, 'betas': optimizer.betas,
+        u = torch.as_strided(getattr(optimizer, second), p.shape, p.stride(), off).detach().cpu().contiguous().clone()
+        out[name] = {'exp_avg': m, second: u}
+    return {'rule': optimizer.rule, 'step': int(optimizer.step_count.item()), 'state': out, 'lr': optimizer.lr, 'betas': optimizer.betas,
             'eps': optimizer.eps, 'weight_decay': optimizer.weight_decay}
 
 
@@ -71,6 +76,22 @@ def lr_schedule_record(optimizer):
     return None if sched is None else dict(sched.state_dict(), base_lr=optimizer.lr)
 
 
+def optimizer_rule_record(ck):
+    """The update rule of a loaded file's optimizer state ('adamax' for a file from before there was a second rule); None without one."""
+    if not (isinstance(ck, dict) and 'optimizer' in ck):
+        return None
+    return ck['optimizer'].get('rule', 'adamax')
+
+
+def rule_warning(path, ck, optimizer):
+    """The line a resumed run prints when the file's rule is not the optimizer's own but shares its state (adam <-> adamw: the decay
+    differs, the moments do not; the optimizer's rule is the one that runs). None when there is nothing to say."""
+    was = optimizer_rule_record(ck)
+    if was is None or was == optimizer.rule:
+        return None
+    return 'warning: %s was written with the update rule %s; continuing with %s' % (path, was, optimizer.rule)
+
+
 def save_checkpoint(path, model, optimizer=None, summary=None):
     """Weights (reference layout), global step, Adamax state and the position of the Philox noise stream, so that a resumed run continues
     the original one bit for bit. With a `summary` (summary.TrainSummary) also 'summary': the open log window's accumulator as a list of
@@ -107,9 +128,14 @@ def load_checkpoint(path, model, optimizer=None, summary=None):
     them), or a bare reference `state_dict` file. Load before a TrainStep captures its graph: the graph keeps the counters it saw.
     An averaging optimizer gets its average from the file's 'ema'; from a file without one the average starts at the loaded weights.
     A `summary` gets the file's open log window; from a file without one it starts an empty window. A guarded optimizer continues the
-    file's clipped / skipped counts under its own limits; from a file without 'grad_guard' it keeps the counts it has."""
+    file's clipped / skipped counts under its own limits; from a file without 'grad_guard' it keeps the counts it has. The optimizer
+    state must be of the optimizer's own kind: adam and adamw share theirs (`rule_warning` has the line to print), a file without 'rule'
+    is Adamax's, and exp_inf against exp_avg_sq is a ValueError naming both rules, raised before anything is loaded."""
     ck = torch.load(path, map_location='cpu')
     sd = ck['model'] if isinstance(ck, dict) and 'model' in ck else ck
+    second = None
+    if optimizer is not None and isinstance(ck, dict) and 'optimizer' in ck:
+        second = check_rule(optimizer_rule_record(ck), optimizer.rule)   # (refused before anything is loaded)
     model.load_state_dict(sd)
     if isinstance(ck, dict) and 'model' in ck:
         model.global_step = int(ck.get('global_step', model.global_step))
@@ -131,7 +157,7 @@ def load_checkpoint(path, model, optimizer=None, summary=None):
             off, n = arena.slots[name]
             p = named[name]
             torch.as_strided(optimizer.exp_avg, p.shape, p.stride(), off).copy_(st['exp_avg'])
-            torch.as_strided(optimizer.exp_inf, p.shape, p.stride(), off).copy_(st['exp_inf'])
+            torch.as_strided(getattr(optimizer, second), p.shape, p.stride(), off).copy_(st[second])
         optimizer.step_count.fill_(int(ck['optimizer']['step']))
     if optimizer is not None and getattr(optimizer, 'ema_decay', 0.0) > 0.0:
         arena = model.pack()

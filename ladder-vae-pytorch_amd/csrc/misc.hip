@@ -272,6 +272,34 @@ __global__ __launch_bounds__(256) void iw_online_kernel(const float* __restrict_
 // over a run, so a captured launch may keep it), and block 0 leaves the lr it applied in lr_out (optional) for the log.
 // GUARD: the step is under a gradient guard (grad_guard_final_kernel below): on a skipped step every thread returns before its first store,
 // lr_out included; otherwise the gradient factor is the guard's scale in the place of gscale[0].
+// What every update rule reads from the device before its loop, written once: the guard's decision, the rate, the gradient factor and the
+// weight 1 - d of the average. false: the step is skipped and the caller returns before its first store. `report`: block 0 leaves the rate in
+// lr_out (when given). The flags are compile-time constants in adamax_kernel and uniform scalars in adam_kernel.
+struct step_head {
+  float lr, gs, w;
+};
+__device__ __forceinline__ bool step_prologue(bool ema_on, bool sched_on, bool guard_on, bool report, float lr, const float* gscale,
+                                              const uint64_t* step_count, float decay, const lvae_lr_schedule& sched, float* lr_out,
+                                              const lvae_grad_guard_state* guard, step_head& h) {
+  if (guard_on) {
+    if (guard->skip) return false;
+    gscale = &guard->scale;
+  }
+  if (sched_on) lr = lr_schedule_eval(sched, step_count[0]);
+  if (report && lr_out && blockIdx.x == 0 && threadIdx.x == 0) lr_out[0] = lr;
+  h.lr = lr;
+  h.gs = gscale ? gscale[0] : 1.f;
+  h.w = 0.f;   // 1 - d
+  if (ema_on) {
+    const float n = (float)step_count[0];
+    h.w = 1.f - fminf(decay, (1.f + n) / (10.f + n));
+  }
+  return true;
+}
+
+// the average's line: ema += (p_new - ema) * (1 - d)
+__device__ __forceinline__ float ema_lerp(float e, float p_new, float w) { return e + (p_new - e) * w; }
+
 template <bool EMA, bool SCHED, bool GUARD = false>
 __global__ __launch_bounds__(256) void adamax_kernel(float* __restrict__ p, const float* __restrict__ g,
                                                       float* __restrict__ m, float* __restrict__ u,
@@ -280,22 +308,11 @@ __global__ __launch_bounds__(256) void adamax_kernel(float* __restrict__ p, cons
                                                       const uint64_t* step_count, float* __restrict__ ema, float decay,
                                                       lvae_lr_schedule sched, float* lr_out,
                                                       const lvae_grad_guard_state* guard) {
-  if (GUARD) {
-    if (guard->skip) return;
-    gscale = &guard->scale;
-  }
-  if (SCHED) {
-    lr = lr_schedule_eval(sched, step_count[0]);
-    if (lr_out && blockIdx.x == 0 && threadIdx.x == 0) lr_out[0] = lr;
-  }
+  step_head h;
+  if (!step_prologue(EMA, SCHED, GUARD, SCHED, lr, gscale, step_count, decay, sched, lr_out, guard, h)) return;
   const float step = (float)(step_count[0] + 1);
-  const float clr = lr / (1.f - powf(b1, step));
-  const float gs = gscale ? gscale[0] : 1.f;
-  float w = 0.f;   // 1 - d
-  if (EMA) {
-    const float n = (float)step_count[0];
-    w = 1.f - fminf(decay, (1.f + n) / (10.f + n));
-  }
+  const float clr = h.lr / (1.f - powf(b1, step));
+  const float gs = h.gs, w = h.w;
   for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < n4; i += (int64_t)gridDim.x * 256) {
     f32x4 pv = reinterpret_cast<f32x4*>(p)[i], gv = reinterpret_cast<const f32x4*>(g)[i];
     f32x4 mv = reinterpret_cast<f32x4*>(m)[i], uv = reinterpret_cast<f32x4*>(u)[i];
@@ -311,11 +328,57 @@ __global__ __launch_bounds__(256) void adamax_kernel(float* __restrict__ p, cons
       mv[j] = mv[j] + (gg - mv[j]) * (1.f - b1);  // lerp, as torch
       uv[j] = fmaxf(uv[j] * b2, fabsf(gg) + eps);
       pv[j] -= clr * mv[j] / uv[j];
-      if (EMA) ev[j] = ev[j] + (pv[j] - ev[j]) * w;
+      if (EMA) ev[j] = ema_lerp(ev[j], pv[j], w);
     }
     reinterpret_cast<f32x4*>(p)[i] = pv;
     reinterpret_cast<f32x4*>(m)[i] = mv;
     reinterpret_cast<f32x4*>(u)[i] = uv;
+    if (EMA) reinterpret_cast<f32x4*>(ema)[i] = ev;
+  }
+}
+
+// Adam / AdamW over the flat arena (torch.optim.Adam / AdamW, single-tensor form, no amsgrad): the same sweep with a second moment in the
+// place of the infinity norm. The step's scalars are formed in double from the exact integer counter and the double betas and rounded to
+// float once (the idiom of lr_schedule.h): 1 - 0.999f already misses 1 - 0.999 by 1.3e-5, which would go straight into the first update.
+// decoupled: the decay multiplies the parameter by 1 - lr * wd (AdamW) instead of entering the gradient; the gradient factor does not scale
+// it and a frozen element does not decay. Schedule, guard, average and lr_out are optional at run time (uniform scalars).
+template <bool EMA>
+__global__ __launch_bounds__(256) void adam_kernel(float* __restrict__ p, const float* __restrict__ g, float* __restrict__ m,
+                                                    float* __restrict__ v, const float* __restrict__ mask, int64_t n4, float lr, double b1,
+                                                    double b2, float eps, float wd, int decoupled, const float* gscale,
+                                                    const uint64_t* step_count, float* __restrict__ ema, float decay,
+                                                    lvae_lr_schedule sched, int sched_on, float* lr_out,
+                                                    const lvae_grad_guard_state* guard) {
+  step_head h;
+  if (!step_prologue(EMA, sched_on != 0, guard != nullptr, true, lr, gscale, step_count, decay, sched, lr_out, guard, h)) return;
+  const double t = (double)(step_count[0] + 1);
+  const float step_size = (float)((double)h.lr / (1.0 - pow(b1, t)));
+  const float rs = (float)sqrt(1.0 - pow(b2, t));
+  const float omb1 = (float)(1.0 - b1), b2f = (float)b2, omb2 = (float)(1.0 - b2);   // the floats torch's scalars round to
+  const float l2 = decoupled ? 0.f : wd;
+  const float keep = (float)(1.0 - (double)h.lr * (double)wd);
+  const float gs = h.gs, w = h.w;
+  for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < n4; i += (int64_t)gridDim.x * 256) {
+    f32x4 pv = reinterpret_cast<f32x4*>(p)[i], gv = reinterpret_cast<const f32x4*>(g)[i];
+    f32x4 mv = reinterpret_cast<f32x4*>(m)[i], vv = reinterpret_cast<f32x4*>(v)[i];
+    f32x4 mk = {1.f, 1.f, 1.f, 1.f};
+    if (mask) mk = reinterpret_cast<const f32x4*>(mask)[i];
+    f32x4 ev = {0.f, 0.f, 0.f, 0.f};
+    if (EMA) ev = reinterpret_cast<f32x4*>(ema)[i];
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+      if (mk[j] == 0.f) continue;
+      float gg = gv[j] * gs;
+      if (l2 != 0.f) gg += l2 * pv[j];
+      if (decoupled) pv[j] *= keep;
+      mv[j] = mv[j] + (gg - mv[j]) * omb1;  // lerp, as torch
+      vv[j] = vv[j] * b2f + omb2 * gg * gg;
+      pv[j] -= step_size * mv[j] / (sqrtf(vv[j]) / rs + eps);
+      if (EMA) ev[j] = ema_lerp(ev[j], pv[j], w);
+    }
+    reinterpret_cast<f32x4*>(p)[i] = pv;
+    reinterpret_cast<f32x4*>(m)[i] = mv;
+    reinterpret_cast<f32x4*>(v)[i] = vv;
     if (EMA) reinterpret_cast<f32x4*>(ema)[i] = ev;
   }
 }
@@ -630,6 +693,37 @@ extern "C" int lvae_adamax_guarded_step_f32(float* p, const float* g, float* exp
   else LVAE_GUARDED_ADAMAX(false, false);
 #undef LVAE_GUARDED_ADAMAX
   LVAE_LAUNCH_CHECK("adamax_guarded_step");
+  return 0;
+}
+
+extern "C" int lvae_adam_step_f32(float* p, const float* g, float* exp_avg, float* exp_avg_sq, const float* mask, int64_t n, float lr,
+                                  const lvae_lr_schedule* schedule, double beta1, double beta2, float eps, float weight_decay,
+                                  int32_t decoupled, const float* gscale, const uint64_t* step_count, float* ema, float decay,
+                                  float* lr_out, const lvae_grad_guard_state* guard, void* stream) {
+  LVAE_REQUIRE(p && g && exp_avg && exp_avg_sq && step_count && n > 0, LVAE_EINVAL, "lvae_adam_step_f32: bad args");
+  LVAE_REQUIRE(!(guard && gscale), LVAE_EINVAL, "lvae_adam_step_f32: a guarded step takes its gradient factor from guard->scale, not gscale");
+  LVAE_REQUIRE(beta1 >= 0.0 && beta1 < 1.0 && beta2 >= 0.0 && beta2 < 1.0, LVAE_EINVAL, "lvae_adam_step_f32: betas (%g, %g) outside [0, 1)",
+               beta1, beta2);
+  LVAE_REQUIRE(eps >= 0.f && weight_decay >= 0.f, LVAE_EINVAL, "lvae_adam_step_f32: eps %g and weight_decay %g must not be negative",
+               (double)eps, (double)weight_decay);
+  if (schedule)
+    if (int rc = lr_schedule_valid(schedule, "lvae_adam_step_f32")) return rc;
+  LVAE_REQUIRE(n % 4 == 0, LVAE_EALIGN, "lvae_adam_step_f32: arena length %lld must be a multiple of 4", (long long)n);
+  LVAE_REQUIRE((reinterpret_cast<uintptr_t>(guard) & 7) == 0, LVAE_EALIGN, "lvae_adam_step_f32: misaligned guard state");
+  if (ema) {
+    LVAE_REQUIRE(decay >= 0.f && decay < 1.f, LVAE_EINVAL, "lvae_adam_step_f32: decay %g outside [0, 1)", (double)decay);
+    LVAE_REQUIRE((reinterpret_cast<uintptr_t>(ema) & 15) == 0, LVAE_EALIGN, "lvae_adam_step_f32: misaligned ema");
+  }
+  const dim3 grid(grid_for(n / 4, 256));
+  const lvae_lr_schedule sched = schedule ? *schedule : lvae_lr_schedule{};
+  if (ema)
+    hipLaunchKernelGGL((adam_kernel<true>), grid, dim3(256), 0, (hipStream_t)stream, p, g, exp_avg, exp_avg_sq, mask, n / 4, lr, beta1,
+                       beta2, eps, weight_decay, decoupled ? 1 : 0, gscale, step_count, ema, decay, sched, schedule ? 1 : 0, lr_out, guard);
+  else
+    hipLaunchKernelGGL((adam_kernel<false>), grid, dim3(256), 0, (hipStream_t)stream, p, g, exp_avg, exp_avg_sq, mask, n / 4, lr, beta1,
+                       beta2, eps, weight_decay, decoupled ? 1 : 0, gscale, step_count, (float*)nullptr, 0.f, sched, schedule ? 1 : 0, lr_out,
+                       guard);
+  LVAE_LAUNCH_CHECK("adam_step");
   return 0;
 }
 

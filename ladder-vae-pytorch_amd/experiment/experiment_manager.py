@@ -17,7 +17,7 @@ import torch
 from .. import engine
 from ..models.lvae import LadderVAE
 from ..noise import PhiloxNoise
-from ..optim import Adamax, GradGuard, LrSchedule
+from ..optim import Adam, AdamW, Adamax, GradGuard, LrSchedule
 
 DATASETS = {
     # name: (color_ch, (H, W), default likelihood)  — experiment/data.py:32-97, experiment_manager.py:279-288
@@ -122,6 +122,11 @@ def build_parser():
     p.add_argument('--grad-skip-threshold', type=float, default=None, dest='grad_skip_threshold', metavar='T',
                    help='skip every step whose gradient norm exceeds T or is not finite: weights, optimizer state, average and BatchNorm '
                         'statistics stay as they were, the run moves on to the next batch. inf: skip non-finite steps only. Off by default')
+    p.add_argument('--optimizer', type=str, choices=['adamax', 'adam', 'adamw'], default='adamax',
+                   help="the update rule, on the same arena, average, schedule and guard: adamax (the reference's), adam (--wd is L2 decay "
+                        'added to the gradient) or adamw (--wd is decoupled decay: the weights shrink by lr * wd per step)')
+    p.add_argument('--betas', type=float, nargs=2, default=[0.9, 0.999], metavar=('B1', 'B2'), help='the moments\' decay rates, for every rule')
+    p.add_argument('--opt-eps', type=float, default=1e-8, dest='opt_eps', metavar='E', help='the eps of the update rule, for every rule')
     p.add_argument('--latent-kl-threshold', type=float, default=0.01, dest='latent_kl_threshold', metavar='T')
     p.add_argument('--latent-var-threshold', type=float, default=0.01, dest='latent_var_threshold', metavar='T')
     return p
@@ -174,6 +179,11 @@ class LVAEExperiment:
             raise SystemExit("--max-grad-norm must be a positive finite number, got %g" % g)
         if t is not None and not t >= 0.0:
             raise SystemExit("--grad-skip-threshold must not be negative, got %g" % t)
+        betas = getattr(args, 'betas', [0.9, 0.999])
+        if len(betas) != 2 or not all(0.0 <= b < 1.0 for b in betas):
+            raise SystemExit("--betas must be two numbers in [0, 1), got %s" % ' '.join('%g' % b for b in betas))
+        if not getattr(args, 'opt_eps', 1e-8) >= 0.0:
+            raise SystemExit("--opt-eps must not be negative, got %g" % args.opt_eps)
         assert args.weight_decay >= 0.0
         assert 0.0 <= args.dropout <= 1.0
         if args.dropout < 1e-5:
@@ -208,6 +218,10 @@ class LVAEExperiment:
             s += ',learnp'
         if args.weight_decay > 0.0:
             s += ',wd={}'.format(args.weight_decay)
+        if getattr(args, 'optimizer', 'adamax') != 'adamax':
+            s += ',' + args.optimizer
+        if list(getattr(args, 'betas', [0.9, 0.999])) != [0.9, 0.999]:
+            s += ',b{:g}-{:g}'.format(*args.betas)
         if getattr(args, 'max_grad_norm', None) is not None:
             s += ',clip{:g}'.format(args.max_grad_norm)
         if getattr(args, 'grad_skip_threshold', None) is not None:
@@ -248,8 +262,11 @@ class LVAEExperiment:
         return None if g is None and t is None else GradGuard(max_norm=g, skip_threshold=t)
 
     def _make_optimizer(self):
-        return Adamax(self.model, lr=self.args.lr, weight_decay=self.args.weight_decay, ema_decay=getattr(self.args, 'ema_decay', 0.0),
-                      schedule=self._make_schedule(self.args), guard=self._make_guard(self.args))
+        a = self.args
+        rule = {'adamax': Adamax, 'adam': Adam, 'adamw': AdamW}[getattr(a, 'optimizer', 'adamax')]
+        return rule(self.model, lr=a.lr, betas=tuple(getattr(a, 'betas', (0.9, 0.999))), eps=getattr(a, 'opt_eps', 1e-8),
+                    weight_decay=a.weight_decay, ema_decay=getattr(a, 'ema_decay', 0.0), schedule=self._make_schedule(a),
+                    guard=self._make_guard(a))
 
     def beta(self):
         if self.args.beta_anneal != 0:

@@ -1704,6 +1704,21 @@ def adamax_guarded_step(p, g, exp_avg, exp_inf, mask, lr, schedule, beta1, beta2
     prepared.weights_written()
 
 
+def adam_step(p, g, exp_avg, exp_avg_sq, mask, lr, schedule, beta1, beta2, eps, weight_decay, decoupled, gscale, step_count, ema=None,
+              decay=0.0, lr_out=None, state=None):
+    """One torch.optim.Adam (`decoupled` False: L2 decay) or AdamW (True: decoupled decay) step over the arena, every option in one entry
+    point: `schedule` None or a struct, `ema` None or a buffer, `state` None or a guard's state (then without `gscale`: the guard's scale
+    stands in its place, and a skipped step stores nothing), `lr_out` (device float[1], optional) receives the lr applied. The betas go
+    down as doubles: the kernel forms the bias corrections in double from the device step counter."""
+    if ema is not None and ema.numel() != p.numel():
+        raise _C.LvaeHipError("ema has %d elements, the parameters %d" % (ema.numel(), p.numel()))
+    call('lvae_adam_step_f32', ptr(p), ptr(g), ptr(exp_avg), ptr(exp_avg_sq), ptr(mask), p.numel(), float(lr),
+         None if schedule is None else C.byref(schedule), float(beta1), float(beta2), float(eps), float(weight_decay), int(bool(decoupled)),
+         ptr(gscale, (torch.float32,)), step_count.data_ptr(), ptr(ema), float(decay), ptr(lr_out, (torch.float32,)),
+         ptr(state, (torch.int64,)), stream_ptr())
+    prepared.weights_written()
+
+
 def copy_table(pairs, device):
     """[(dst, src)] pairs of contiguous fp32 device tensors of equal length -> the device table multi_copy takes (int64 [len][3]: struct
     lvae_copy_entry). The caller keeps the tensors alive and in place for as long as the table is used."""

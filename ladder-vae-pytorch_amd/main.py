@@ -117,9 +117,11 @@ def main(argv=None):
     # --window-summaries: every step folds its metrics into a device accumulator; a train line is the mean since the previous one
     summary = TrainSummary(len(args.z_dims), exp.device) if args.window_summaries else None
     if args.resume:
-        from .checkpoint import load_checkpoint
-        # (weights, Adamax state and average, global step, the rank-0 noise stream's position and the open log window)
+        from .checkpoint import load_checkpoint, rule_warning
+        # (weights, optimizer state and average, global step, the rank-0 noise stream's position and the open log window)
         ck = load_checkpoint(args.resume, model, opt, summary=summary)
+        if rank == 0 and rule_warning(args.resume, ck, opt):
+            print(rule_warning(args.resume, ck, opt))
         was = ck.get('lr_schedule') if isinstance(ck, dict) and 'model' in ck else None
         if rank == 0 and was != lr_schedule_record(opt):
             print('warning: %s was written with the lr schedule %s; continuing with %s' % (args.resume, was, lr_schedule_record(opt)))

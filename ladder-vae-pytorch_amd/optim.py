@@ -10,6 +10,9 @@ warm-up and decay; `lr_now` holds the rate of the last step.
 With a `guard` (GradGuard) the step is preceded by a look at the gradient's norm on the device: the gradient is clipped to `max_norm`, and a
 step whose norm is not finite or exceeds `skip_threshold` is left out as if it had not happened (parameters, exp_avg, exp_inf, the step
 counter, the average and lr_now keep their bits), all of it inside the captured step.
+
+`Adam` / `AdamW` are a second update rule on the same arena (torch.optim.Adam with L2 decay, torch.optim.AdamW with decoupled decay) with the
+same average, schedule and guard: `ArenaOptimizer` holds what does not depend on the rule, each rule launches its own kernel.
 """
 import contextlib
 import math
@@ -159,14 +162,23 @@ class GradGuard:
         return 'GradGuard(max_norm=%r, skip_threshold=%r)' % (self.max_norm, self.skip_threshold)
 
 
-class Adamax:
-    def __init__(self, model, lr=3e-4, betas=(0.9, 0.999), eps=1e-8, weight_decay=0.0, ema_decay=0.0, schedule=None, guard=None):
+RULES = {'adamax': 'exp_inf', 'adam': 'exp_avg_sq', 'adamw': 'exp_avg_sq'}   # rule -> the name of its second moment (torch's own)
+
+
+class ArenaOptimizer:
+    """What does not depend on the update rule: the state over the flat arena (exp_avg, the rule's second moment under torch's name for it,
+    step counter, average, lr_now), zero_grad, swap_ema, current_lr, the guard's hand-shake and the counter's advance. A rule names itself
+    (`rule`, a key of RULES) and launches its kernel in `_update(arena, guard_state)`."""
+    rule = None
+
+    def __init__(self, model, lr, betas, eps, weight_decay, ema_decay, schedule, guard):
         self.model = model
         self.lr, self.betas, self.eps, self.weight_decay = float(lr), (float(betas[0]), float(betas[1])), float(eps), float(weight_decay)
         self.ema_decay = float(ema_decay)
         if not 0.0 <= self.ema_decay < 1.0:
             raise ValueError("ema_decay must lie in [0, 1), got %r" % (ema_decay,))
-        self.exp_avg = self.exp_inf = self.step_count = None
+        self.exp_avg = self.step_count = None
+        setattr(self, RULES[self.rule], None)
         self.ema = None     # float32 [arena.n_train] when ema_decay > 0: the averaged trainable prefix, in the arena's layout
         self.gscale = None  # device float[1]: 1/world_size after a SUM all-reduce
         self.schedule = schedule   # LrSchedule or None: `lr` itself at every step
@@ -181,7 +193,7 @@ class Adamax:
         if self._arena is not arena:
             dev = arena.params.device
             self.exp_avg = torch.zeros(arena.n_train, dtype=torch.float32, device=dev)
-            self.exp_inf = torch.zeros(arena.n_train, dtype=torch.float32, device=dev)
+            setattr(self, RULES[self.rule], torch.zeros(arena.n_train, dtype=torch.float32, device=dev))
             self.step_count = torch.zeros(1, dtype=torch.int64, device=dev)
             if self.ema_decay > 0.0:
                 self.ema = arena.params[:arena.n_train].detach().clone()
@@ -194,44 +206,27 @@ class Adamax:
         self._state().zero_grad()
 
     def step(self):
-        if self.guard is not None:
-            return self._guarded_step()
-        if self.schedule is not None:
-            return self._scheduled_step()
-        arena = self._state()
-        if self.ema is None:
-            K.adamax_step(arena.params[:arena.n_train], arena.grads, self.exp_avg, self.exp_inf, None, self.lr, self.betas[0],
-                          self.betas[1], self.eps, self.weight_decay, self.gscale, self.step_count)
-        else:
-            if self._swapped:
-                raise RuntimeError("Adamax.step() inside swap_ema(): the parameters hold the average")
-            K.adamax_ema_step(arena.params[:arena.n_train], arena.grads, self.exp_avg, self.exp_inf, None, self.lr, self.betas[0],
-                              self.betas[1], self.eps, self.weight_decay, self.gscale, self.step_count, self.ema, self.ema_decay)
-        K.counter_advance(self.step_count, 1)
-
-    def _scheduled_step(self):
-        """step() with the lr of the schedule at the device step counter, with the average or without; the lr applied is left in lr_now."""
+        """One update of the trainable prefix. With a schedule the lr is the schedule's at the device step counter and the lr applied is left
+        in lr_now. With a guard the step runs under the guard's decision for this gradient (engine.TrainStep has taken it by now; taken here
+        otherwise), and a skipped step leaves the step counter where it is."""
         arena = self._state()
         if self._swapped:
-            raise RuntimeError("Adamax.step() inside swap_ema(): the parameters hold the average")
-        K.adamax_sched_step(arena.params[:arena.n_train], arena.grads, self.exp_avg, self.exp_inf, None, self._sched, self.betas[0],
-                            self.betas[1], self.eps, self.weight_decay, self.gscale, self.step_count, self.ema, self.ema_decay, self.lr_now)
-        K.counter_advance(self.step_count, 1)
-
-    def _guarded_step(self):
-        """step() under the guard's decision for this gradient (engine.TrainStep has taken it by now; taken here otherwise): with or without
-        the average, with or without a schedule. A skipped step leaves the step counter where it is."""
-        arena = self._state()
-        if self._swapped:
-            raise RuntimeError("Adamax.step() inside swap_ema(): the parameters hold the average")
+            raise RuntimeError("%s.step() inside swap_ema(): the parameters hold the average" % type(self).__name__)
         guard = self.guard
+        if guard is None:
+            self._update(arena, None)
+            K.counter_advance(self.step_count, 1)
+            return
         if not guard.checked:
             guard.check(arena.grads, self.gscale)
         guard.checked = False
-        K.adamax_guarded_step(arena.params[:arena.n_train], arena.grads, self.exp_avg, self.exp_inf, None, self.lr, self._sched,
-                              self.betas[0], self.betas[1], self.eps, self.weight_decay, self.step_count, self.ema, self.ema_decay,
-                              self.lr_now, guard.state)
+        self._update(arena, guard.state)
         K.counter_advance_unless(self.step_count, 1, guard.skip)
+
+    def _update(self, arena, guard_state):
+        """The rule's kernel over arena.params[:arena.n_train] and arena.grads; `guard_state` is None or the checked guard's state, whose
+        scale then stands in the place of gscale."""
+        raise NotImplementedError
 
     @contextlib.contextmanager
     def swap_ema(self):
@@ -257,7 +252,8 @@ class Adamax:
 
     def state_dict(self):
         self._state()
-        sd = {'exp_avg': self.exp_avg, 'exp_inf': self.exp_inf, 'step': self.step_count, 'lr': self.lr,
+        second = RULES[self.rule]
+        sd = {'rule': self.rule, 'exp_avg': self.exp_avg, second: getattr(self, second), 'step': self.step_count, 'lr': self.lr,
               'betas': self.betas, 'eps': self.eps, 'weight_decay': self.weight_decay}
         if self.ema is not None:
             sd['ema'], sd['ema_decay'] = self.ema, self.ema_decay
@@ -273,9 +269,79 @@ class Adamax:
         return float(self.lr_now.item())
 
     def load_state_dict(self, sd):
+        """The state of `state_dict()`. A dict without 'rule' is Adamax's; adam and adamw share their state; a second moment of the other
+        kind (exp_inf against exp_avg_sq) is refused."""
+        second = check_rule(sd.get('rule', 'adamax'), self.rule)
         self._state()
         self.exp_avg.copy_(sd['exp_avg'])
-        self.exp_inf.copy_(sd['exp_inf'])
+        getattr(self, second).copy_(sd[second])
         self.step_count.copy_(sd['step'])
         if self.ema is not None and 'ema' in sd:
             self.ema.copy_(sd['ema'])
+
+
+def check_rule(was, now):
+    """The name of the second moment that state written under the rule `was` and an optimizer of the rule `now` share; ValueError naming
+    both rules when they keep different ones."""
+    if was not in RULES:
+        raise ValueError("unknown update rule %r in the saved state (one of %s)" % (was, ', '.join(RULES)))
+    if RULES[was] != RULES[now]:
+        raise ValueError("the saved state is %s's (second moment %s); this optimizer runs %s (second moment %s)"
+                         % (was, RULES[was], now, RULES[now]))
+    return RULES[now]
+
+
+class Adamax(ArenaOptimizer):
+    """torch.optim.Adamax with L2 decay, the reference's rule."""
+    rule = 'adamax'
+
+    def __init__(self, model, lr=3e-4, betas=(0.9, 0.999), eps=1e-8, weight_decay=0.0, ema_decay=0.0, schedule=None, guard=None):
+        super().__init__(model, lr, betas, eps, weight_decay, ema_decay, schedule, guard)
+
+    def _update(self, arena, guard_state):
+        p, b1, b2 = arena.params[:arena.n_train], self.betas[0], self.betas[1]
+        if guard_state is not None:
+            K.adamax_guarded_step(p, arena.grads, self.exp_avg, self.exp_inf, None, self.lr, self._sched, b1, b2, self.eps,
+                                  self.weight_decay, self.step_count, self.ema, self.ema_decay, self.lr_now, guard_state)
+        elif self.schedule is not None:
+            K.adamax_sched_step(p, arena.grads, self.exp_avg, self.exp_inf, None, self._sched, b1, b2, self.eps, self.weight_decay,
+                                self.gscale, self.step_count, self.ema, self.ema_decay, self.lr_now)
+        elif self.ema is None:
+            K.adamax_step(p, arena.grads, self.exp_avg, self.exp_inf, None, self.lr, b1, b2, self.eps, self.weight_decay, self.gscale,
+                          self.step_count)
+        else:
+            K.adamax_ema_step(p, arena.grads, self.exp_avg, self.exp_inf, None, self.lr, b1, b2, self.eps, self.weight_decay, self.gscale,
+                              self.step_count, self.ema, self.ema_decay)
+
+
+class Adam(ArenaOptimizer):
+    """torch.optim.Adam over the arena (single-tensor form, no amsgrad): `weight_decay` is L2 decay added to the gradient, or with
+    `decoupled_weight_decay` torch.optim.AdamW's p *= 1 - lr * weight_decay. Decay applies to every trainable element. One kernel for every
+    combination of average, schedule and guard (lvae_adam_step_f32); the bias corrections are formed in double on the device."""
+
+    def __init__(self, model, lr=1e-3, betas=(0.9, 0.999), eps=1e-8, weight_decay=0.0, decoupled_weight_decay=False, ema_decay=0.0,
+                 schedule=None, guard=None):
+        self.decoupled = bool(decoupled_weight_decay)
+        self.rule = 'adamw' if self.decoupled else 'adam'
+        if not float(lr) >= 0.0:
+            raise ValueError("lr must not be negative, got %r" % (lr,))
+        if len(betas) != 2 or not all(0.0 <= float(b) < 1.0 for b in betas):
+            raise ValueError("betas must be two numbers in [0, 1), got %r" % (betas,))
+        if not float(eps) >= 0.0:
+            raise ValueError("eps must not be negative, got %r" % (eps,))
+        if not float(weight_decay) >= 0.0:
+            raise ValueError("weight_decay must not be negative, got %r" % (weight_decay,))
+        super().__init__(model, lr, betas, eps, weight_decay, ema_decay, schedule, guard)
+
+    def _update(self, arena, guard_state):
+        K.adam_step(arena.params[:arena.n_train], arena.grads, self.exp_avg, self.exp_avg_sq, None, self.lr, self._sched, self.betas[0],
+                    self.betas[1], self.eps, self.weight_decay, self.decoupled, None if guard_state is not None else self.gscale,
+                    self.step_count, self.ema, self.ema_decay, self.lr_now, guard_state)
+
+
+class AdamW(Adam):
+    """Adam with decoupled decay and torch.optim.AdamW's default of 1e-2."""
+
+    def __init__(self, model, lr=1e-3, betas=(0.9, 0.999), eps=1e-8, weight_decay=1e-2, decoupled_weight_decay=True, ema_decay=0.0,
+                 schedule=None, guard=None):
+        super().__init__(model, lr, betas, eps, weight_decay, decoupled_weight_decay, ema_decay, schedule, guard)
