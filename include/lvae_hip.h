@@ -429,6 +429,25 @@ size_t lvae_conv2d_wgrad_pair_workspace(const lvae_conv_desc* a, const lvae_conv
 int32_t lvae_conv2d_wgrad_pair_schedule(const lvae_conv_desc* a, const lvae_conv_desc* b, int32_t* sched);
 int lvae_conv2d_wgrad_pair_f32(const lvae_conv_desc* a, const lvae_bn_apply* ap, const lvae_conv_desc* b, const float* dy_b, float* dw_a,
                                float* db_a, float* dw_b, float* db_b, void* workspace, size_t workspace_bytes, void* stream);
+/* n = 1 to 3 independent weight gradients in the Winograd domain in one launch and one slab reduce (the convolutions of a stochastic
+ * layer at the 16x16 level: conv_out 32 -> 64, conv_in_q and conv_in_p 64 -> 64): same results as n calls of lvae_conv2d_wgrad_f32 up to
+ * the summation order and, for a gradient lvae_conv2d_wgrad_f32 runs in another family, the kernel's arithmetic; reproducible from run to
+ * run. Here, and only here, the family also takes 32 input channels (one block of input channels, one workgroup per range):
+ * lvae_conv2d_wgrad_f32, the grouped call and their queries keep the kernel they have always chosen for such a gradient. n = 1 runs one
+ * gradient by itself on this family. lvae_conv2d_wgrad_shared_ok != 0
+ * exactly when every descriptor has a shape of the Winograd family (3x3, stride 1, pad 1, 32 or 64 input channels), all have one N, H and W, at
+ * most 64 output channels, fp32 arithmetic and storage, and no gradient has a deferred apply in front (aps: NULL, or n pointers that
+ * are all NULL; a gradient whose dy lvae_bn_apply still has to form goes out with lvae_conv2d_wgrad_pair_f32 / _apply_f32). An explicit
+ * request: the pixel limit of the grouped call's Winograd groups does not apply. The chip's 256 workgroups are split so that every problem
+ * has ranges of the same number of chunks, a range taking two workgroups with 64 input channels and one with 32;
+ * lvae_conv2d_wgrad_shared_schedule writes sched[3 * n] = ranges, chunks per range and workgroups of each problem in turn (chunks and
+ * ranges as for the pair) and returns lvae_conv2d_wgrad_shared_ok. The queries read plans only: host only, no launch.
+ * workspace: lvae_conv2d_wgrad_shared_workspace(descs, n) bytes, 16-byte aligned like every dy[i]. No two entries may share a dw. */
+int32_t lvae_conv2d_wgrad_shared_ok(const lvae_conv_desc* descs, const lvae_bn_apply* const* aps, int32_t n);
+size_t lvae_conv2d_wgrad_shared_workspace(const lvae_conv_desc* descs, int32_t n);
+int32_t lvae_conv2d_wgrad_shared_schedule(const lvae_conv_desc* descs, const lvae_bn_apply* const* aps, int32_t n, int32_t* sched);
+int lvae_conv2d_wgrad_shared_f32(const lvae_conv_desc* descs, const float* const* dy, float* const* dw, float* const* db, int32_t n,
+                                 void* workspace, size_t workspace_bytes, void* stream);
 /* Which kernel family lvae_conv2d_wgrad_f32 (and the grouped call) runs for `d` (d->x_dtype / y_dtype = the storage types of x / dy):
  * diagnostics for the parity tests and the profiles. */
 enum {

@@ -155,6 +155,10 @@ SIGNATURES = {
     'lvae_conv2d_wgrad_pair_workspace': (_Z, [C.POINTER(ConvDesc), C.POINTER(ConvDesc)]),
     'lvae_conv2d_wgrad_pair_schedule': (_I, [C.POINTER(ConvDesc), C.POINTER(ConvDesc), C.POINTER(_I)]),
     'lvae_conv2d_wgrad_pair_f32': (C.c_int, [C.POINTER(ConvDesc), C.POINTER(BnApply), C.POINTER(ConvDesc), _P, _P, _P, _P, _P, _P, _Z, _P]),
+    'lvae_conv2d_wgrad_shared_ok': (_I, [C.POINTER(ConvDesc), _P, _I]),
+    'lvae_conv2d_wgrad_shared_workspace': (_Z, [C.POINTER(ConvDesc), _I]),
+    'lvae_conv2d_wgrad_shared_schedule': (_I, [C.POINTER(ConvDesc), _P, _I, C.POINTER(_I)]),
+    'lvae_conv2d_wgrad_shared_f32': (C.c_int, [C.POINTER(ConvDesc), _P, _P, _P, _I, _P, _Z, _P]),
     'lvae_conv2d_wgrad_grouped_workspace': (_Z, [C.POINTER(ConvDesc), _I]),
     'lvae_conv2d_wgrad_grouped_f32': (C.c_int, [C.POINTER(ConvDesc), _P, _P, _P, _I, _P, _Z, _P]),
     'lvae_conv2d_wgrad_grouped_schedule': (_I, [C.POINTER(ConvDesc), _I, C.POINTER(_I)]),

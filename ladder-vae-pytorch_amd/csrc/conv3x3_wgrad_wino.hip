@@ -29,10 +29,11 @@ namespace lvae {
 struct WgWinoArgs {
   lvae_conv_desc d;
   const float* dy;
-  float* slab_w;  // [nranges][2 ci blocks][ncog][32 ci][16 positions][64 co]: 4 KB contiguous per input channel
+  float* slab_w;  // [nranges][ncib ci blocks][ncog][32 ci][16 positions][64 co]: 4 KB contiguous per input channel
   float* slab_b;  // [nranges][ncog][64] or nullptr
   int nranges, ncog, cpr, total_chunks, cpi;
   uint32_t m_cpi;
+  int ncib, pad_;  // blocks of 32 input channels: C1 / 32 = 1 or 2
 };
 
 constexpr int WG_XS = 48;  // x halo pixel stride (floats, 32 channels + pad): 2 pixels = 96 = 32 mod 64 banks
@@ -72,7 +73,7 @@ template <int TPR>
 __global__ __launch_bounds__(512, 2) void conv_wgrad_wino_grouped_kernel(WgWinoGroup g) {
   kernarg_warmup<(sizeof(WgWinoGroup) < 1024 ? sizeof(WgWinoGroup) : 1024)>();
   const WgWinoArgs& a = g.p[blockIdx.y];
-  const int nwg_ = a.nranges * a.ncog * 2;
+  const int nwg_ = a.nranges * a.ncog * a.ncib;
   if ((int)blockIdx.x >= nwg_) return;  // uniform per workgroup, before any barrier
   const int bid_ = blockIdx.x;
   constexpr bool AP = false;
@@ -109,10 +110,31 @@ __global__ __launch_bounds__(512, 2) void conv_wgrad_wino_pair_kernel(WgWinoPair
   }
 }
 
+// Two or three problems with a real dY and one image width (the gradients of a stochastic layer's convolutions: 32 -> 64 and 64 -> 64) in
+// one launch: the single kernel's body behind a workgroup-uniform problem select. Problem i owns the workgroups [first[i], first[i + 1])
+// (first[n] = the grid) and has its own range split (wg_wino_shared_split), XCD remap and "workgroup 0" roles from the problem-local index.
+constexpr int kWgWinoShared = kWgradWinoShared;
+struct WgWinoSharedArgs {
+  WgWinoArgs p[kWgWinoShared];
+  int first[kWgWinoShared + 1];
+};
+static_assert(sizeof(WgWinoSharedArgs) <= 4096, "kernel argument block");
+
+template <int TPR>
+__global__ __launch_bounds__(512, 2) void conv_wgrad_wino_shared_kernel(WgWinoSharedArgs g) {
+  kernarg_warmup<(sizeof(WgWinoSharedArgs) < 1024 ? sizeof(WgWinoSharedArgs) : 1024)>();
+  const int sel = (int)blockIdx.x < g.first[1] ? 0 : ((int)blockIdx.x < g.first[2] ? 1 : 2);   // uniform per workgroup
+  const WgWinoArgs& a = g.p[sel];
+  const int nwg_ = g.first[sel + 1] - g.first[sel], bid_ = (int)blockIdx.x - g.first[sel];
+  constexpr bool AP = false;
+  const lvae_bn_apply ap = lvae_bn_apply{};
+#include "conv3x3_wgrad_wino_body.inc"
+}
+
 struct WinoReduceArgs {
   const float* slab_w;
   const float* slab_b;
-  int nranges, ncog, Cout, pad_;
+  int nranges, ncog, Cout, ncib;
   int64_t stap, sk, sn;
   float* dw;
   float* db;
@@ -122,6 +144,9 @@ struct WinoReduceGroup {
 };
 struct WinoReducePair {
   WinoReduceArgs p[2];
+};
+struct WinoReduceShared {
+  WinoReduceArgs p[kWgWinoShared];
 };
 
 // dw[tap(a,b)][ci][co] += (G^T (sum_ranges slab) G)[a][b], 1024-thread workgroups, ranges summed in eight slices (slice = range mod 8,
@@ -140,7 +165,7 @@ __device__ __forceinline__ void wino_reduce_body(const WinoReduceArgs& a, int bx
   const int t = threadIdx.x;
   const int q = HALF ? (t & 7) : (t & 15), p = HALF ? ((t >> 3) & 15) : ((t >> 4) & 15), rs = HALF ? (t >> 7) : (t >> 8);
   const float* src = a.slab_w + ((((size_t)(ci >> 5) * ncog + cog) * 32 + (ci & 31)) * 16 + p) * 64 + half * 32 + q * 4;
-  const size_t rstride = (size_t)2 * ncog * 32 * 16 * 64;
+  const size_t rstride = (size_t)a.ncib * ncog * 32 * 16 * 64;
   // slab rows p = 4 i + b, b < 3: the producer has applied the column half of G^T dU G (row 4 i + 3 is never written)
   f32x4 s = {0.f, 0.f, 0.f, 0.f};
   if ((p & 3) != 3) {
@@ -208,21 +233,37 @@ __global__ __launch_bounds__(1024) void conv_wgrad_wino_reduce_pair_kernel(WinoR
   wino_reduce_body<true>(g.p[blockIdx.y], blockIdx.x, red, red_b);
 }
 
+// the gradients of a shared launch (blockIdx.y = problem), each in the HALF form over its own range count and input channels
+__global__ __launch_bounds__(1024) void conv_wgrad_wino_reduce_shared_kernel(WinoReduceShared g) {
+  kernarg_warmup<sizeof(WinoReduceShared)>();
+  const WinoReduceArgs& a = g.p[blockIdx.y];
+  if ((int)blockIdx.x >= 64 * a.ncib * a.ncog) return;   // uniform per workgroup, before any barrier
+  __shared__ __attribute__((aligned(16))) float red[8 * 16 * 32];
+  __shared__ float red_b[16][64];
+  wino_reduce_body<true>(a, blockIdx.x, red, red_b);
+}
+
 __global__ __launch_bounds__(1024) void conv_wgrad_wino_reduce_grouped_kernel(WinoReduceGroup g) {
   kernarg_warmup<(sizeof(WinoReduceGroup) < 1024 ? sizeof(WinoReduceGroup) : 1024)>();
   const WinoReduceArgs& a = g.p[blockIdx.y];
-  if ((int)blockIdx.x >= 64 * a.ncog) return;   // uniform per workgroup, before any barrier
+  if ((int)blockIdx.x >= 32 * a.ncib * a.ncog) return;   // uniform per workgroup, before any barrier
   __shared__ __attribute__((aligned(16))) float red[8 * 16 * 64];
   __shared__ float red_b[16][64];
   wino_reduce_body<false>(a, blockIdx.x, red, red_b);
 }
 
-// budget: the ranges this gradient may spread over (x 2 input-channel blocks = its workgroups): 128 when it has the chip to itself
+static int wg_wino_min_cpr() {   // slab traffic: at least this many chunks per slab
+  static const int v = (int)std::max<int64_t>(1, tune("LVAE_WINO_WGRAD_MIN_CPR", 4));
+  return v;
+}
+
+// budget: the ranges this gradient may spread over, counted for two input-channel blocks (budget x 2 = its workgroups: a 32-channel problem,
+// one workgroup per range, spreads over twice as many): 128 when it has the chip to itself
 static bool wg_wino_plan(const lvae_conv_desc* d, WgWinoArgs& a, int budget = 128) {
   static const bool off = tune("LVAE_DISABLE_WINO_WGRAD", 0) != 0 || tune("LVAE_DISABLE_WINO", 0) != 0;  // A/B switch (tuning builds only)
   if (off) return false;
   if (d->KH != 3 || d->KW != 3 || d->stride != 1 || d->pad != 1 || d->gather != LVAE_GATHER_CONV) return false;
-  if (d->C1 != 64 || d->C2 != 0 || d->x2 != nullptr || d->Cout % 4 != 0 || d->Cout > 256) return false;
+  if ((d->C1 != 64 && d->C1 != 32) || d->C2 != 0 || d->x2 != nullptr || d->Cout % 4 != 0 || d->Cout > 256) return false;
   if (d->OH != d->H || d->OW != d->W || (d->H & 1)) return false;
   if (d->W != 8 && d->W != 16 && d->W != 32) return false;
   const int tpr = d->W / 2, tr = 16 / tpr;
@@ -232,11 +273,13 @@ static bool wg_wino_plan(const lvae_conv_desc* d, WgWinoArgs& a, int budget = 12
   static const int64_t min_m = tune("LVAE_WINO_WGRAD_MIN_M", 256 * 64);
   if (M < min_m || M * 256 >= ((int64_t)1 << 31)) return false;
   a.ncog = (d->Cout + 63) / 64;
+  a.ncib = d->C1 / 32;
+  a.pad_ = 0;
   a.cpi = (d->H / 2) / tr;
   a.total_chunks = d->N * a.cpi;
-  int nranges = budget / a.ncog;  // 128: 256 workgroups with the two input-channel blocks
+  int nranges = 2 * budget / (a.ncog * a.ncib);  // 128 of 64 channels: 256 workgroups with the two input-channel blocks
   if (nranges < 1) nranges = 1;
-  static const int min_cpr = (int)tune("LVAE_WINO_WGRAD_MIN_CPR", 4);
+  const int min_cpr = wg_wino_min_cpr();
   if (nranges > a.total_chunks / min_cpr) nranges = a.total_chunks / min_cpr;  // slab traffic: at least min_cpr chunks per slab
   if (nranges < 1) nranges = 1;
   a.cpr = (a.total_chunks + nranges - 1) / nranges;
@@ -245,14 +288,17 @@ static bool wg_wino_plan(const lvae_conv_desc* d, WgWinoArgs& a, int budget = 12
   return true;
 }
 
+// The family's row of the routing table: 64 input channels only. A 32-channel gradient keeps the kernel the table has always given it
+// (lvae_conv2d_wgrad_f32 and the grouped call are unchanged for it); it enters this family on the explicit request of
+// lvae_conv2d_wgrad_shared_f32 alone, which plans through wg_wino_plan.
 // group key: the image width (one kernel instantiation per width); problems of at least LVAE_WINO_GROUP_MAX_M pixels fill the chip alone
 bool conv_wgrad_wino_plan(const lvae_conv_desc* d, WgradPlan& p) {
   static const int64_t group_max_m = tune("LVAE_WINO_GROUP_MAX_M", 65536);
   WgWinoArgs a;
-  if (!wg_wino_plan(d, a)) return false;
+  if (d->C1 != 64 || !wg_wino_plan(d, a)) return false;
   p.group = (int64_t)d->N * d->H * d->W < group_max_m ? d->W : -1;
-  p.set_slabs(a.nranges, (size_t)a.ncog * 2 * 16 * 32 * 64, (size_t)a.ncog * 64);
-  p.apply_ok = d->precision == LVAE_PREC_F32 && d->Cout == 64 && (d->W == 16 || d->W == 32) && d->x_dtype == LVAE_DT_F32 && d->y_dtype == LVAE_DT_F32;
+  p.set_slabs(a.nranges, (size_t)a.ncog * a.ncib * 16 * 32 * 64, (size_t)a.ncog * 64);
+  p.apply_ok = d->precision == LVAE_PREC_F32 && d->C1 == 64 && d->Cout == 64 && (d->W == 16 || d->W == 32) && d->x_dtype == LVAE_DT_F32 && d->y_dtype == LVAE_DT_F32;
   return true;
 }
 
@@ -272,6 +318,7 @@ static int wg_wino_pair_ranges_a() {
 // other: B is planned with what A left, then A again with what B left (at the family's minimum of 16,384 pixels both end at 64 ranges of
 // 4 chunks, the single launches' own split, and the chip is full).
 static bool wg_wino_pair_split(const lvae_conv_desc* da, const lvae_conv_desc* db, WgWinoArgs& a, WgWinoArgs& b) {
+  if (da->C1 != 64 || db->C1 != 64) return false;   // (the caller's apply_ok says so too)
   if (!wg_wino_plan(da, a, wg_wino_pair_ranges_a()) || a.ncog != 1 || a.nranges >= 128) return false;
   if (!wg_wino_plan(db, b, 128 - a.nranges) || b.ncog != 1) return false;
   return wg_wino_plan(da, a, 128 - b.nranges);
@@ -287,6 +334,48 @@ bool conv_wgrad_wino_pair_plan(const lvae_conv_desc* da, const lvae_conv_desc* d
   if (sched) {
     const int32_t v[6] = {a.nranges, a.cpr, a.nranges * 2, b.nranges, b.cpr, b.nranges * 2};
     std::copy(v, v + 6, sched);
+  }
+  return true;
+}
+
+// The shared launch's split of the 256 workgroups: every problem gets ranges of the same length c, the least c (from the least chunks per
+// range up) at which all ranges fit, a range of a 64-channel problem taking two workgroups and one of a 32-channel problem one. The chunks
+// per workgroup are then equal over the problems up to each problem's short last range, and a problem that cannot use a share of its own
+// (few chunks) leaves it to the others by construction. At 256x16x16 with {32, 64, 64} channels: 5 x ceil(1024 / c) <= 256 from c = 21,
+// 49 ranges per problem, 245 workgroups (20 chunks per workgroup would take 260). One problem alone (n = 1: how a 32-channel gradient is
+// run, and tested, by itself) gets what wg_wino_plan gives a gradient that has the chip: 256 ranges of 4 chunks with 32 input channels,
+// 128 of 8 with 64.
+static bool wg_wino_shared_split(const lvae_conv_desc* const* d, int n, WgWinoArgs* a) {
+  if (n < 1 || n > kWgWinoShared) return false;
+  int max_chunks = 1;
+  for (int i = 0; i < n; ++i) {
+    if (!wg_wino_plan(d[i], a[i]) || a[i].ncog != 1 || d[i]->W != d[0]->W) return false;
+    max_chunks = std::max(max_chunks, a[i].total_chunks);
+  }
+  for (int c = wg_wino_min_cpr(); c <= max_chunks; ++c) {
+    int wgs = 0;
+    for (int i = 0; i < n; ++i) wgs += a[i].ncib * ((a[i].total_chunks + c - 1) / c);
+    if (wgs > 256) continue;
+    for (int i = 0; i < n; ++i) {
+      a[i].cpr = std::min(c, a[i].total_chunks);
+      a[i].nranges = (a[i].total_chunks + a[i].cpr - 1) / a[i].cpr;
+    }
+    return true;
+  }
+  return false;
+}
+
+// the gradients of a shared launch as it splits them; sched = ranges, chunks per range and workgroups of each problem in turn
+bool conv_wgrad_wino_shared_plan(const lvae_conv_desc* const* d, int n, WgradPlan* p, int32_t* sched) {
+  WgWinoArgs a[kWgWinoShared];
+  if (!wg_wino_shared_split(d, n, a)) return false;
+  for (int i = 0; i < n; ++i) {
+    p[i].set_slabs(a[i].nranges, (size_t)a[i].ncib * 16 * 32 * 64, 64);
+    if (sched) {
+      sched[3 * i] = a[i].nranges;
+      sched[3 * i + 1] = a[i].cpr;
+      sched[3 * i + 2] = a[i].nranges * a[i].ncib;
+    }
   }
   return true;
 }
@@ -311,8 +400,8 @@ static int wino_fill_planned(const WgradOp& o, WgWinoArgs& a, WinoReduceArgs& r)
   a.dy = o.dy;
   a.slab_w = o.slab_w();
   a.slab_b = o.slab_b();
-  r = WinoReduceArgs{a.slab_w, a.slab_b, a.nranges, a.ncog, o.d->Cout, 0, o.d->w_stap, o.d->w_sk, o.d->w_sn, o.dw, o.db};
-  return a.nranges * a.ncog * 2;
+  r = WinoReduceArgs{a.slab_w, a.slab_b, a.nranges, a.ncog, o.d->Cout, a.ncib, o.d->w_stap, o.d->w_sk, o.d->w_sn, o.dw, o.db};
+  return a.nranges * a.ncog * a.ncib;
 }
 static int wino_fill(const WgradOp& o, WgWinoArgs& a, WinoReduceArgs& r) {
   wg_wino_plan(o.d, a);
@@ -356,6 +445,33 @@ int conv_wgrad_wino_pair_launch(const WgradOp& a, const lvae_bn_apply* ap, const
   return 0;
 }
 
+// the n gradients of conv_wgrad_wino_shared_plan (o[i].plan: that function's; real, 16-byte aligned dy and workspaces: the entry point
+// checked them)
+int conv_wgrad_wino_shared_launch(const WgradOp* o, int n, hipStream_t s) {
+  WgWinoSharedArgs g;
+  WinoReduceShared rg;
+  const lvae_conv_desc* d[kWgWinoShared];
+  for (int i = 0; i < n; ++i) d[i] = o[i].d;
+  if (!wg_wino_shared_split(d, n, g.p)) return LVAE_EINVAL;
+  g.first[0] = 0;
+  for (int i = 0; i < kWgWinoShared; ++i) {
+    if (i < n) {
+      g.first[i + 1] = g.first[i] + wino_fill_planned(o[i], g.p[i], rg.p[i]);
+    } else {   // no workgroup selects it
+      g.p[i] = g.p[0];
+      g.first[i + 1] = g.first[i];
+    }
+  }
+  const size_t lds = wg_wino_lds(o->d->W);
+  const int rc = with_tpr(o->d->W, [&](auto tpr) {
+    return launch_lds<conv_wgrad_wino_shared_kernel<decltype(tpr)::value>>("conv_wgrad_wino_shared", dim3(g.first[n]), dim3(512), lds, 160 * 1024, s, g);
+  });
+  if (rc) return rc;
+  hipLaunchKernelGGL(conv_wgrad_wino_reduce_shared_kernel, dim3(128, n), dim3(1024), 0, s, rg);
+  LVAE_LAUNCH_CHECK("conv_wgrad_wino_reduce_shared");
+  return 0;
+}
+
 // n <= kWgradWinoGroup gradients of one plan.group, each with its own workspace (16-byte aligned dy and workspace: the route checked
 // them). One gradient runs the single kernel and the half-workgroup reduce, several the grouped kernel and the grouped reduce.
 int conv_wgrad_wino_launch(const WgradOp* o, int n, hipStream_t s) {
@@ -377,7 +493,7 @@ int conv_wgrad_wino_launch(const WgradOp* o, int n, hipStream_t s) {
     return launch_lds<conv_wgrad_wino_grouped_kernel<T>>("conv_wgrad_wino_grouped", dim3(max_wgs, n), dim3(512), lds, 160 * 1024, s, g);
   });
   if (rc) return rc;
-  if (n == 1) hipLaunchKernelGGL(conv_wgrad_wino_reduce_kernel, dim3(128 * max_ncog), dim3(1024), 0, s, rg.p[0]);
+  if (n == 1) hipLaunchKernelGGL(conv_wgrad_wino_reduce_kernel, dim3(64 * g.p[0].ncib * max_ncog), dim3(1024), 0, s, rg.p[0]);
   else hipLaunchKernelGGL(conv_wgrad_wino_reduce_grouped_kernel, dim3(64 * max_ncog, n), dim3(1024), 0, s, rg);
   LVAE_LAUNCH_CHECK(n == 1 ? "conv_wgrad_wino_reduce" : "conv_wgrad_wino_reduce_grouped");
   return 0;

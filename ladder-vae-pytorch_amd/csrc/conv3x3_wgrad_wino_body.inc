@@ -1,9 +1,12 @@
-// Body of conv_wgrad_wino_kernel / conv_wgrad_wino_grouped_kernel / conv_wgrad_wino_ap_kernel / conv_wgrad_wino_pair_kernel (textually included,
+// Body of conv_wgrad_wino_kernel / conv_wgrad_wino_grouped_kernel / conv_wgrad_wino_ap_kernel / conv_wgrad_wino_pair_kernel /
+// conv_wgrad_wino_shared_kernel (textually included,
 // see conv3x3_wgrad_halo_body.inc). Expects: template parameter TPR; `a` (WgWinoArgs); `nwg_` = workgroups of this problem and `bid_` = this
-// workgroup's index among them (blockIdx.x except in the pair kernel, whose second problem starts behind the first); constexpr bool AP and
+// workgroup's index among them (blockIdx.x except in the pair and shared kernels, whose later problems start behind the first); constexpr bool AP and
 // `ap` (lvae_bn_apply): with AP the dY operand does not exist yet — it is dy = BN'(ap.dh; ap.x) * ap.drop, the BatchNorm-backward apply
 // that would otherwise run as a launch of its own in front of this one (round 5): the kernel reduces the producer's partial rows, forms dy
 // while it stages a chunk and (the input-channel block 0 workgroups) stores it to ap.out for the dgrad that follows. Cout == 64 only.
+// a.ncib = blocks of 32 input channels of the problem (C1 / 32: 1 or 2; with AP always 2): the workgroup's block, the owner of the bias
+// partial (block 0) and the slab index [range][ncib][ncog] come from it, and C1 = 32 * ncib is x's pixel stride.
   extern __shared__ __attribute__((aligned(16))) float smem[];
   constexpr int W = 2 * TPR, HW2 = W + 2, TR = 16 / TPR, HROWS = 2 * TR + 2;
   constexpr int HP = HROWS * HW2;                      // halo pixels of a chunk
@@ -17,7 +20,8 @@
     const int nwg = nwg_, xcd = bid & 7, q = nwg >> 3, r = nwg & 7;
     bid = (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + (bid >> 3);
   }
-  const int cib = bid & 1, cog = (bid >> 1) % a.ncog, range = (bid >> 1) / a.ncog;
+  const int ncib = AP ? 2 : a.ncib, xcs = 32 * ncib;   // xcs: x's pixel stride (floats)
+  const int cib = bid & (ncib - 1), cog = (bid >> (ncib - 1)) % a.ncog, range = (bid >> (ncib - 1)) / a.ncog;
   const int c_begin = range * a.cpr;
   const int c_end = min(a.total_chunks, c_begin + a.cpr);
   const f32x4 zero4 = {0.f, 0.f, 0.f, 0.f};
@@ -38,7 +42,7 @@
     const int hx = px - hy * HW2;
     in = px < HP;
     col_ok = (hx >= 1) & (hx <= W);
-    rel = (hy * W + hx) * 64 + cib * 32 + xc4;  // relative to the pixel (row oh0 - 1, column -1) of the image
+    rel = (hy * W + hx) * xcs + cib * 32 + xc4;  // relative to the pixel (row oh0 - 1, column -1) of the image
   };
   if (!AP) {
 #pragma unroll
@@ -100,7 +104,7 @@
   auto load_chunk = [&](int c) {
     const int n = fastdiv(c, a.m_cpi), cr = c - n * a.cpi;
     const int oh0 = cr * (2 * TR);
-    const float* xb = d.x + ((int64_t)(n * d.H + oh0 - 1) * W - 1) * 64;
+    const float* xb = d.x + ((int64_t)(n * d.H + oh0 - 1) * W - 1) * xcs;
     xok = 0;
 #pragma unroll
     for (int u = 0; u < XSLOTS; ++u) {
@@ -300,7 +304,7 @@
   // The wave holds a whole position row i = pi: the column half of G^T dU G is applied HERE, before the slab is written (linear, so it
   // commutes with the sum over slabs): 3 rows per (ci, i) instead of 4 = 25 % less slab traffic for the kernel and for the reduce;
   // row 4 i + 3 of the slab stays unwritten and unread. The reduce applies the row half.  G^T = [[1,.5,.5,0],[0,.5,-.5,0],[0,.5,.5,1]]
-  float* slab = a.slab_w + (size_t)((range * 2 + cib) * a.ncog + cog) * 32 * 16 * 64 + 4 * pi * 64;
+  float* slab = a.slab_w + (size_t)((range * ncib + cib) * a.ncog + cog) * 32 * 16 * 64 + 4 * pi * 64;
   auto finish = [&](auto hsel) {
     constexpr int h = decltype(hsel)::value;
 #pragma unroll

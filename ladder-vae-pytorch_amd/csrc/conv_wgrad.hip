@@ -701,6 +701,72 @@ extern "C" int lvae_conv2d_wgrad_pair_f32(const lvae_conv_desc* a, const lvae_bn
   return conv_wgrad_wino_pair_launch(oa, ap, ob, (hipStream_t)stream);
 }
 
+// The shared launch of n = 1 to 3 gradients that each have a real dy (aps, if not null: the deferred apply in front of each, all null —
+// a gradient whose dy an apply still has to form belongs to the pair launch): all shapes of the Winograd family, one N, H, W, at most 64
+// output channels, fp32 arithmetic and storage. The call is an explicit request for that family: neither the table's order (the 8x8 level's
+// single gradients go to the whole-image family first) nor the grouped call's pixel limit is asked. Reads plans only; p[i] come back as the
+// shared launch splits them.
+static bool wgrad_shared_route(const lvae_conv_desc* descs, const lvae_bn_apply* const* aps, int32_t n, WgradPlan* p, int32_t* sched) {
+  if (!descs || n < 1 || n > kWgradWinoShared) return false;
+  const lvae_conv_desc* d[kWgradWinoShared];
+  for (int i = 0; i < n; ++i) {
+    d[i] = &descs[i];
+    if (aps && aps[i]) return false;
+    p[i] = WgradPlan{};
+    p[i].variant = LVAE_WGRAD_VARIANT_WINO;
+    if (d[i]->Cout > 64) return false;
+    if (d[i]->precision != LVAE_PREC_F32 || d[i]->x_dtype != LVAE_DT_F32 || d[i]->y_dtype != LVAE_DT_F32) return false;
+    if (d[i]->N != d[0]->N || d[i]->H != d[0]->H || d[i]->W != d[0]->W) return false;
+  }
+  return conv_wgrad_wino_shared_plan(d, n, p, sched);
+}
+
+extern "C" int32_t lvae_conv2d_wgrad_shared_ok(const lvae_conv_desc* descs, const lvae_bn_apply* const* aps, int32_t n) {
+  WgradPlan p[kWgradWinoShared];
+  return wgrad_shared_route(descs, aps, n, p, nullptr) ? 1 : 0;
+}
+
+extern "C" size_t lvae_conv2d_wgrad_shared_workspace(const lvae_conv_desc* descs, int32_t n) {
+  WgradPlan p[kWgradWinoShared];
+  if (!wgrad_shared_route(descs, nullptr, n, p, nullptr)) return 0;
+  size_t tot = 0;
+  for (int i = 0; i < n; ++i) tot += wgrad_piece(p[i]);
+  return tot;
+}
+
+extern "C" int32_t lvae_conv2d_wgrad_shared_schedule(const lvae_conv_desc* descs, const lvae_bn_apply* const* aps, int32_t n, int32_t* sched) {
+  WgradPlan p[kWgradWinoShared];
+  return sched && wgrad_shared_route(descs, aps, n, p, sched) ? 1 : 0;
+}
+
+extern "C" int lvae_conv2d_wgrad_shared_f32(const lvae_conv_desc* descs, const float* const* dy, float* const* dw, float* const* db, int32_t n,
+                                            void* workspace, size_t workspace_bytes, void* stream) {
+  const char* who = "lvae_conv2d_wgrad_shared_f32";
+  LVAE_REQUIRE(descs && dy && dw && db && n >= 1 && n <= kWgradWinoShared && workspace, LVAE_EINVAL, "%s: bad arguments (1 to 3 gradients)", who);
+  for (int i = 0; i < n; ++i) {
+    const int rc = conv_desc_check(&descs[i], who);
+    if (rc) return rc;
+    LVAE_REQUIRE(dy[i] && dw[i], LVAE_EINVAL, "%s: null dy/dw at %d (a gradient whose dy an apply has yet to form is not taken here)", who, i);
+  }
+  WgradPlan p[kWgradWinoShared];
+  LVAE_REQUIRE(wgrad_shared_route(descs, nullptr, n, p, nullptr), LVAE_EINVAL,
+               "%s: not a shared launch (1 to 3 Winograd-domain fp32 weight gradients of one N, H, W with 32 or 64 input and at most 64 output "
+               "channels, fp32 storage; lvae_conv2d_wgrad_shared_ok): use lvae_conv2d_wgrad_f32 per gradient", who);
+  size_t need = 0;
+  for (int i = 0; i < n; ++i) need += wgrad_piece(p[i]);
+  LVAE_REQUIRE(workspace_bytes >= need, LVAE_EWORKSPACE, "%s: workspace %zu < %zu", who, workspace_bytes, need);
+  LVAE_REQUIRE(al16(workspace), LVAE_EALIGN, "%s: workspace must be 16-byte aligned", who);
+  WgradOp ops[kWgradWinoShared];
+  char* ws = static_cast<char*>(workspace);
+  for (int i = 0; i < n; ++i) {
+    LVAE_REQUIRE(al16(dy[i]), LVAE_EALIGN, "%s: dy[%d] must be 16-byte aligned", who, i);
+    for (int j = 0; j < i; ++j) LVAE_REQUIRE(dw[i] != dw[j], LVAE_EINVAL, "%s: entries %d and %d accumulate into one dw", who, j, i);
+    ops[i] = WgradOp{&descs[i], p[i], dy[i], dw[i], db[i], ws};
+    ws += wgrad_piece(p[i]);
+  }
+  return conv_wgrad_wino_shared_launch(ops, n, (hipStream_t)stream);
+}
+
 extern "C" int lvae_conv2d_wgrad_bf16(const lvae_conv_desc* d, const float* dy, float* dw, float* db, void* workspace,
                                       size_t workspace_bytes, void* stream) {
   LVAE_REQUIRE(d != nullptr, LVAE_EINVAL, "lvae_conv2d_wgrad_bf16: null descriptor");

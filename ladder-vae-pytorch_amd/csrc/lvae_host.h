@@ -139,6 +139,12 @@ int conv_wgrad_wino_apply_launch(const WgradOp& o, const lvae_bn_apply* ap, hipS
 // null: ranges, chunks per range, workgroups of A, then of B), the launch runs that split.
 bool conv_wgrad_wino_pair_plan(const lvae_conv_desc* da, const lvae_conv_desc* db, WgradPlan& pa, WgradPlan& pb, int32_t* sched);
 int conv_wgrad_wino_pair_launch(const WgradOp& a, const lvae_bn_apply* ap, const WgradOp& b, hipStream_t s);
+// n = 1 to 3 gradients with a real dy, shapes of the Winograd family of one image width with at most 64 output channels and 32 or 64 input
+// channels (32: here only, conv_wgrad_wino_plan declines them), as one launch and one slab reduce: the plan splits the chip's workgroups between them (p[i]: slabs and workspace of each;
+// sched, if not null: ranges, chunks per range, workgroups of each in turn), the launch runs that split.
+constexpr int kWgradWinoShared = 3;
+bool conv_wgrad_wino_shared_plan(const lvae_conv_desc* const* d, int n, WgradPlan* p, int32_t* sched);
+int conv_wgrad_wino_shared_launch(const WgradOp* o, int n, hipStream_t s);
 
 // conv1x1_wgrad.hip
 bool conv1x1_wgrad_plan(const lvae_conv_desc* d, WgradPlan& p);

@@ -849,9 +849,8 @@ def conv2d_wgrad(x, dy, weight, g, dweight, dbias=None, x2=None, in_scale=None, 
     call('lvae_conv2d_wgrad_f32', C.byref(d), ptr_dt(dy), ptr(dweight), ptr(dbias), ws.data_ptr(), ws.numel(), stream_ptr())   # dy's type: d.y_dtype
 
 
-def conv2d_wgrad_grouped(items):
-    """items: list of (x, dy, weight, g, dweight, dbias, kw) exactly as for conv2d_wgrad (kw: x2 / in_scale / in_shift /
-    in_act). One C call; gradients that share a kernel variant are launched together."""
+def _wgrad_item_arrays(items, who):
+    """The descriptor array and the dy / dw / db pointer arrays of (x, dy, weight, g, dweight, dbias, kw) entries."""
     n = len(items)
     descs = (ConvDesc * n)()
     dys, dws, dbs = (C.c_void_p * n)(), (C.c_void_p * n)(), (C.c_void_p * n)()
@@ -859,14 +858,70 @@ def conv2d_wgrad_grouped(items):
         _chk_nhwc(x, 'x')
         _chk_nhwc(dy, 'dy')
         if tuple(dweight.stride()) != tuple(weight.stride()):
-            raise _C.LvaeHipError("conv2d_wgrad_grouped: gradient strides %s differ from weight strides %s" %
-                                  (tuple(dweight.stride()), tuple(weight.stride())))
+            raise _C.LvaeHipError("%s: gradient strides %s differ from weight strides %s" %
+                                  (who, tuple(dweight.stride()), tuple(weight.stride())))
         N, H, W, _ = x.shape
         d = _desc(g, weight, x, kw.get('x2'), N, H, W, dy.shape[1], dy.shape[2], g.Cout, g.s_ci, g.s_co,
                   GATHER_TRANSPOSED if g.transposed else GATHER_CONV, None, kw.get('in_scale'), kw.get('in_shift'), kw.get('in_act'))
         d.y_dtype = _dt(dy)
         C.memmove(C.byref(descs, i * C.sizeof(ConvDesc)), C.byref(d), C.sizeof(ConvDesc))
         dys[i], dws[i], dbs[i] = ptr_dt(dy), ptr(dweight), ptr(dbias)
+    return descs, dys, dws, dbs
+
+
+def _wgrad_shared_descs(convs):
+    """The descriptors of (x, weight, g) stride-1 'same' convolutions with fp32 dy, None where they cannot share a launch anyway."""
+    if precision != PREC_F32 or _ddi is not None or not 1 <= len(convs) <= 3:
+        return None
+    descs = (ConvDesc * len(convs))()
+    for i, (x, weight, g) in enumerate(convs):
+        if x.dim() != 4 or x.dtype != torch.float32 or g.transposed:
+            return None
+        N, H, W, _ = x.shape
+        d = _desc(g, weight, x, None, N, H, W, H, W, g.Cout, g.s_ci, g.s_co, GATHER_CONV)
+        C.memmove(C.byref(descs, i * C.sizeof(ConvDesc)), C.byref(d), C.sizeof(ConvDesc))
+    return descs
+
+
+def conv2d_wgrad_shared_ok(convs, routed=False):
+    """True when conv2d_wgrad_shared takes the weight gradients of these 1 to 3 convolutions, each (x, weight, g), in one launch (the 3x3
+    convolutions of a stochastic layer at the 16x16 level: the Winograd-domain fp32 weight gradient, one N, H, W). routed: only where
+    the 64-channel gradients among them — there has to be one — run in that kernel family alone too (the 8x8 level's go to the
+    whole-image kernel and stay there); a 32-channel gradient enters the family through this launch only."""
+    descs = _wgrad_shared_descs(convs)
+    if descs is None or not _C.load().lvae_conv2d_wgrad_shared_ok(descs, None, len(convs)):
+        return False
+    if not routed:
+        return True
+    wide = [i for i in range(len(convs)) if descs[i].C1 == 64]
+    return bool(wide) and all(_C.load().lvae_conv2d_wgrad_variant(C.byref(descs[i])) == _C.WGRAD_VARIANT_WINO for i in wide)
+
+
+def conv2d_wgrad_shared_schedule(convs):
+    """((ranges, chunks per range, workgroups) of each problem) as the shared launch splits the chip, or None where it declines. No launch."""
+    descs = _wgrad_shared_descs(convs)
+    out = (C.c_int32 * (3 * len(convs)))()
+    if descs is None or not _C.load().lvae_conv2d_wgrad_shared_schedule(descs, None, len(convs), out):
+        return None
+    return tuple(tuple(out[3 * i:3 * i + 3]) for i in range(len(convs)))
+
+
+def conv2d_wgrad_shared(items):
+    """conv2d_wgrad of 1 to 3 entries (x, dy, weight, g, dweight, dbias, kw), kw: in_scale / in_shift / in_act, as one launch and one slab
+    reduce. Only where conv2d_wgrad_shared_ok()."""
+    n = len(items)
+    descs, dys, dws, dbs = _wgrad_item_arrays(items, 'conv2d_wgrad_shared')
+    need = _C.load().lvae_conv2d_wgrad_shared_workspace(descs, n)
+    ws = workspace(need, items[0][0].device)
+    call('lvae_conv2d_wgrad_shared_f32', descs, C.cast(dys, C.c_void_p), C.cast(dws, C.c_void_p), C.cast(dbs, C.c_void_p), n,
+         ws.data_ptr(), ws.numel(), stream_ptr())
+
+
+def conv2d_wgrad_grouped(items):
+    """items: list of (x, dy, weight, g, dweight, dbias, kw) exactly as for conv2d_wgrad (kw: x2 / in_scale / in_shift /
+    in_act). One C call; gradients that share a kernel variant are launched together."""
+    n = len(items)
+    descs, dys, dws, dbs = _wgrad_item_arrays(items, 'conv2d_wgrad_grouped')
     need = _C.load().lvae_conv2d_wgrad_grouped_workspace(descs, n)
     ws = workspace(need, items[0][0].device)
     call('lvae_conv2d_wgrad_grouped_f32', descs, C.cast(dys, C.c_void_p), C.cast(dws, C.c_void_p), C.cast(dbs, C.c_void_p), n,

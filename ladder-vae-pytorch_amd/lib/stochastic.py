@@ -43,10 +43,16 @@ class NormalStochasticBlock2d(nn.Module):
             fused = self._fused(p_params, q_params, forced_latent, use_mode, analytical_kl, noise, n_img, rows, stats)
             if fused is not None:
                 return fused
+        # the layer's weight gradients as one launch where the library shares it (ops.WgradShare: training passes of the 16x16 level)
+        share = None
+        if q_params is not None and not tempered and not force_constant_output:
+            ins = ([(p_params, self.conv_in_p)] if self.transform_p_params else []) + [(q_params, self.conv_in_q)]
+            z_like = q_params.detach()[..., :self.c_vars]   # conv_out's input: z has q_params' rows and c_vars channels (only its shape is read)
+            share = ops.WgradShare.plan(ins + [(z_like, self.conv_out)])
         if self.transform_p_params:
-            p_params = self.conv_in_p(p_params)
+            p_params = ops.conv(p_params, self.conv_in_p, share=share and (share, True))
         if q_params is not None:
-            q_params = self.conv_in_q(q_params)
+            q_params = ops.conv(q_params, self.conv_in_q, share=share and (share, True))
         ref = q_params if q_params is not None else p_params
         N = ref.shape[0] if n_img is None else n_img
         H, W = ref.shape[1], ref.shape[2]
@@ -73,7 +79,7 @@ class NormalStochasticBlock2d(nn.Module):
                 raise RuntimeError("force_constant_output is a sampling-time option; run it under torch.no_grad()")
             z = z[0:1].expand_as(z).contiguous()
             p_params = p_params[0:1].expand(N, -1, -1, -1).contiguous()
-        out = self.conv_out(z)
+        out = ops.conv(z, self.conv_out, share=share and (share, False))
         data = {'z': z, 'p_params': p_params, 'q_params': q_params, 'logprob_p': outs[1], 'logprob_q': None,
                 'kl_elementwise': None, 'kl_samplewise': None, 'kl_spatial': None}
         if q_params is not None:

@@ -110,16 +110,51 @@ def wgrad(x, dy, w, g, dw, db, **kw):
             t.record_stream(st)  # the caching allocator must not recycle these blocks before the side kernel ran
 
 
+class WgradShare:
+    """The weight gradients of one stochastic layer call (lib/stochastic.py: conv_out, conv_in_q and, below the top layer, conv_in_p), which
+    are independent of each other and of the backward chain: each convolution's backward node hands its (x, dy) in instead of launching,
+    and the arrival of the last input convolution issues all of them as one shared launch (kernels.conv2d_wgrad_shared). conv_out's node
+    runs first if it runs at all and the core's backward feeds both input convolutions, so waiting for those covers every order autograd
+    takes; what has arrived when they have is issued, alone or through wgrad() where the launch declines (a side stream, bf16 operands)."""
+
+    def __init__(self, n_in):
+        self.items, self.wait = [], n_in
+
+    @staticmethod
+    def plan(convs):
+        """A WgradShare for these (x, Conv2dParams) calls — the input convolutions first, conv_out last — where the library shares their
+        gradients' launch (fp32, one N, H, W of the Winograd family: the 16x16 level at batch 256), else None."""
+        if not (RB.switches.wgrad_shared and torch.is_grad_enabled() and all(m.weight.requires_grad for _, m in convs)):
+            return None
+        if not K.conv2d_wgrad_shared_ok([(x, m.weight, m.geom()) for x, m in convs], routed=True):
+            return None
+        return WgradShare(len(convs) - 1)
+
+    def add(self, item, is_input):
+        self.items.append(item)
+        self.wait -= int(is_input)
+        if self.wait > 0:
+            return
+        items, self.items = self.items, []
+        if (len(items) >= 2 and _side['stream'] is None and all(it[1].dtype == torch.float32 for it in items) and
+                K.conv2d_wgrad_shared_ok([(it[0], it[2], it[3]) for it in items])):
+            K.conv2d_wgrad_shared(items)
+        else:
+            for x, dy, w, g, dw, db, kw in items:
+                wgrad(x, dy, w, g, dw, db, **kw)
+
+
 # ----------------------------------------------------------------------------------------------------------------
 class ConvFn(Function):
     """y = out_act(conv(cat(x, x2)) + bias); call sites: stem, pre_conv (strided / transposed), merge 1x1,
-    stochastic convs, likelihood head. `mod` is the parameter holder (lib.nn.Conv2dParams)."""
+    stochastic convs, likelihood head. `mod` is the parameter holder (lib.nn.Conv2dParams). share: None, or (WgradShare, is an input
+    convolution of its layer): the weight gradient goes out with the layer's others."""
 
     @staticmethod
-    def forward(ctx, x, x2, mod, out_act, weight, bias):
+    def forward(ctx, x, x2, mod, out_act, weight, bias, share=None):
         g = mod.geom()
         y = K.conv2d(x, weight, g, bias=bias, x2=x2, out_act=out_act)
-        ctx.mod, ctx.out_act, ctx.g = mod, out_act, g
+        ctx.mod, ctx.out_act, ctx.g, ctx.share = mod, out_act, g, share
         ctx.has_x2 = x2 is not None
         ctx.save_for_backward(x, x2, y if out_act else None)
         return y
@@ -133,7 +168,11 @@ class ConvFn(Function):
             dy = K.act_bwd_from_out(dy, y, ctx.out_act)
         w = mod.weight
         if w.requires_grad:
-            wgrad(x, dy, w, g, grad_buf(w), grad_buf(mod.bias) if mod.bias is not None else None, x2=x2)
+            db = grad_buf(mod.bias) if mod.bias is not None else None
+            if ctx.share is not None and x2 is None:
+                ctx.share[0].add((x, dy, w, g, grad_buf(w), db, {}), ctx.share[1])
+            else:
+                wgrad(x, dy, w, g, grad_buf(w), db, x2=x2)
         dx = dx2 = None
         hw = (x.shape[1], x.shape[2])
         if x2 is None:
@@ -149,11 +188,11 @@ class ConvFn(Function):
                     dx = K.conv2d_dgrad(dy, w, g, hw, ci_range=(0, C1))
                 if ctx.needs_input_grad[1]:
                     dx2 = K.conv2d_dgrad(dy, w, g, hw, ci_range=(C1, g.Cin))
-        return dx, dx2, None, None, None, None
+        return dx, dx2, None, None, None, None, None
 
 
-def conv(x, mod, x2=None, out_act=None):
-    return ConvFn.apply(x, x2, mod, out_act, mod.weight, mod.bias)
+def conv(x, mod, x2=None, out_act=None, share=None):
+    return ConvFn.apply(x, x2, mod, out_act, mod.weight, mod.bias, share)
 
 
 # ----------------------------------------------------------------------------------------------------------------

@@ -21,6 +21,7 @@ class Switches:
         self.wgrad_apply_maxw = int(env.get('LVAE_WGRAD_APPLY_MAXW', '16'))   # ... up to this width: 32x32 measured +0.09 ms (profiles/r05_wgrad_apply_ab.txt)
         self.wgrad_pair = on('LVAE_WGRAD_PAIR')                       # ... and conv2's weight gradient rides in the same launch (kernels.conv2d_wgrad_pair) ...
         self.wgrad_pair_maxw = int(env.get('LVAE_WGRAD_PAIR_MAXW', '16'))     # ... up to this width (profiles/wgrad_pair_ab.txt)
+        self.wgrad_shared = on('LVAE_WGRAD_SHARED')                   # a 16x16 stochastic layer's weight gradients go out as one launch (ops.WgradShare; profiles/wgrad_shared_ab.txt)
         self.gate_stats = env.get('LVAE_NO_GATE_STATS') is None       # the gate epilogue writes the next block's BatchNorm partials
         self.defer_apply = on('LVAE_DEFER_APPLY')                     # a block leaves its last BatchNorm apply to its producer (BlockPlan.accepts)
         self.defer_apply_large = on('LVAE_DEFER_APPLY_LARGE')         # ... also into the persistent gate-backward kernel of the >= 16x16 levels
