@@ -293,6 +293,26 @@ int lvae_conv1x1_gate_bwd_wgrad_recompute_f32(const lvae_conv_desc* d, const flo
                                               int64_t gate_w_sn, const float* gate_bias, float* dw, int64_t dw_sk, int64_t dw_sn,
                                               float* db, void* workspace, size_t workspace_bytes, const lvae_bn_apply* ap, void* stream);
 
+/* The whole backward of a 1x1 / stride-1 convolution over a 64 + 64 channel concat with 64 output channels (MergeLayer /
+ * SkipConnectionMerger) as ONE persistent kernel plus the fixed-order slab reduce: both halves of the input gradient (what
+ * lvae_conv1x1_dgrad_cat_f32 writes) AND the weight / bias gradient (what lvae_conv2d_wgrad_f32 accumulates), fp32-equivalent (six bf16-piece
+ * products per product). `d` describes the dgrad over the concat exactly as for lvae_conv1x1_dgrad_cat_f32 with split = 64: d->x = dy
+ * [N,H,W,64], C1 = 64, Cout = 128, transposed weight strides with w_sk == 1; d->y is not used. x1, x2 [N,H,W,64]: the two inputs of the
+ * forward; dx1, dx2 [N,H,W,64]: their gradients (overwritten); dweight: the weight's own layout, element (ci, co) at
+ * dweight[ci*d->w_sn + co*d->w_sk], accumulated; dbias [64] or NULL, accumulated. `ap` (NULL or ap->parts NULL: none): dy does not exist
+ * yet but is the deferred BatchNorm-backward apply of the residual block that read the convolution's output, as for
+ * lvae_conv1x1_gate_bwd_wgrad_f32 (fp32 dh, no drop); d->x is then not read, and the formed dy is stored only where ap->out is not NULL.
+ * max_workgroups: 0 = one per 64-pixel tile up to 256; a positive value caps the grid further (a workgroup then loops over several tiles).
+ * lvae_conv1x1_cat_bwd_workspace(d, split): bytes of scratch the call needs at any max_workgroups, 0 when it does not take `d` (anything
+ * but the shape above, split != 64, a dy or weight pointer off 16 bytes, bf16 storage, precision LVAE_PREC_BF16, form LVAE_FORM_F32_MFMA);
+ * lvae_conv1x1_cat_bwd_apply_ok(d, split): 1 when it takes `d` with a deferred apply. Both assume the operands outside the descriptor
+ * 16-byte aligned; host only, no launch. A call that is not taken launches and writes nothing: LVAE_EINVAL (shape), LVAE_EWORKSPACE
+ * (workspace_bytes below the query), LVAE_EALIGN (an operand outside the descriptor off 16 bytes). */
+size_t lvae_conv1x1_cat_bwd_workspace(const lvae_conv_desc* d, int32_t split);
+int32_t lvae_conv1x1_cat_bwd_apply_ok(const lvae_conv_desc* d, int32_t split);
+int lvae_conv1x1_cat_bwd_f32(const lvae_conv_desc* d, const float* x1, const float* x2, float* dx1, float* dx2, float* dweight, float* dbias,
+                             const lvae_bn_apply* ap, void* workspace, size_t workspace_bytes, int32_t max_workgroups, void* stream);
+
 /* ------------------------------------------------------------------------------------------------------------
  * Fused residual-block kernels of the low-resolution levels (H*W a divisor of 64: 8x8, 4x4, 2x2 ...), "whole-image tiles"
  * (csrc/resblock_img.hip). A workgroup's 64 / 128 GEMM rows are whole images, so the 3x3 convolution of `d` (64 -> 64 channels,

@@ -138,6 +138,9 @@ SIGNATURES = {
     'lvae_conv1x1_gate_bwd_wgrad_recompute_ok': (_I, [C.POINTER(ConvDesc)]),
     'lvae_conv1x1_gate_bwd_wgrad_recompute_f32': (C.c_int, [C.POINTER(ConvDesc), _P, _P, _I, _P, _L, _I, _P, _L, _L, _P, _P, _L, _L, _P, _P, _Z,
                                                             C.POINTER(BnApply), _P]),
+    'lvae_conv1x1_cat_bwd_workspace': (_Z, [C.POINTER(ConvDesc), _I]),
+    'lvae_conv1x1_cat_bwd_apply_ok': (_I, [C.POINTER(ConvDesc), _I]),
+    'lvae_conv1x1_cat_bwd_f32': (C.c_int, [C.POINTER(ConvDesc), _P, _P, _P, _P, _P, _P, C.POINTER(BnApply), _P, _Z, _I, _P]),
     'lvae_resblock_gate_workspace': (_Z, [C.POINTER(ConvDesc)]),
     'lvae_resblock_gate_prepare_entry': (C.c_int, [C.POINTER(ConvDesc), _P]),
     'lvae_resblock_conv_rows': (_I, [C.POINTER(ConvDesc)]),

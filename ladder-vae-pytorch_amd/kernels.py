@@ -831,6 +831,61 @@ def conv1x1_dgrad_cat(dy, weight, g, C1):
     return dx, dx2
 
 
+def _cat_bwd_desc(dy_like, weight, g, C1, dweight):
+    """The dgrad view over the concat that the persistent merge backward is asked about, for the 1x1 convolution (weight, g) whose output
+    (and output gradient) is shaped like dy_like (N,H,W,Cout); None where Python alone can tell that it does not apply."""
+    if _ddi is not None or dy_like.dim() != 4 or g.transposed or dy_like.dtype != torch.float32 or not 0 < C1 < g.Cin:
+        return None
+    if dweight is not None and tuple(dweight.stride()) != tuple(weight.stride()):
+        return None
+    N, H, W, _ = dy_like.shape
+    return _desc(g, weight, dy_like, None, N, H, W, H, W, g.Cin, g.s_co, g.s_ci, GATHER_TRANSPOSED)
+
+
+def cat_bwd_ws(dy_like, weight, g, C1, dweight=None):
+    """Scratch bytes conv1x1_cat_bwd needs for the merge convolution (weight, g) with an output shaped like dy_like; 0: not taken."""
+    d = _cat_bwd_desc(dy_like, weight, g, C1, dweight)
+    return int(_C.load().lvae_conv1x1_cat_bwd_workspace(C.byref(d), C1)) if d is not None else 0
+
+
+def cat_bwd_apply_ok(dy_like, weight, g, C1, dweight=None):
+    """True when conv1x1_cat_bwd takes the merge convolution (weight, g) with a deferred BatchNorm-backward apply (PendingApply) as its dy."""
+    d = _cat_bwd_desc(dy_like, weight, g, C1, dweight)
+    return d is not None and bool(_C.load().lvae_conv1x1_cat_bwd_apply_ok(C.byref(d), C1))
+
+
+def conv1x1_cat_bwd(dy, x, x2, weight, g, dweight, dbias, apply=None, store_dy=False, max_workgroups=0, scratch=None):
+    """The whole backward of a 1x1 convolution over the channel concat (x, x2) in one persistent kernel (+ its slab reduce): returns (dx, dx2)
+    and accumulates into dweight / dbias; None, with nothing launched or written, when the library does not take it (the caller runs
+    conv2d_wgrad + conv1x1_dgrad_cat). apply (PendingApply): dy does not exist yet (dy is apply.out, unwritten); the kernel forms it from
+    the deferred BatchNorm-backward apply and stores it to apply.out only with store_dy. max_workgroups caps the grid (0: default);
+    scratch: a uint8 buffer to use instead of the shared workspace (too small: None)."""
+    _chk_nhwc(dy, 'dy')
+    C1 = x.shape[3]
+    d = _cat_bwd_desc(dy, weight, g, C1, dweight)
+    if d is None or x.dtype != torch.float32 or x2 is None or x2.dtype != torch.float32 or tuple(x.shape[:3]) != tuple(dy.shape[:3]) or \
+            tuple(x2.shape[:3]) != tuple(dy.shape[:3]) or x2.shape[3] != g.Cin - C1 or not (x.is_contiguous() and x2.is_contiguous()):
+        return None
+    lib = _C.load()
+    need = lib.lvae_conv1x1_cat_bwd_workspace(C.byref(d), C1)
+    if not need or (apply is not None and (not lib.lvae_conv1x1_cat_bwd_apply_ok(C.byref(d), C1) or apply.dh.dtype != torch.float32)):
+        return None
+    ws = scratch if scratch is not None else workspace(need, dy.device)
+    if ws.numel() < need or ws.data_ptr() % 16 or any(t is not None and t.data_ptr() % 16 for t in (x, x2)):
+        return None
+    N, H, W, _ = dy.shape
+    ap = None
+    if apply is not None:
+        d.x = None
+        ap = _C.BnApply(ptr(apply.parts), apply.parts.shape[0], ACT[apply.act], N * H * W, ptr(apply.coef0), ptr(apply.dh), ptr(apply.x),
+                        ptr(apply.add), ptr(apply.dgamma), ptr(apply.dbeta), ptr(apply.out) if store_dy else None, 0, 0)
+    dx = torch.empty((N, H, W, C1), dtype=torch.float32, device=dy.device)
+    dx2 = torch.empty((N, H, W, g.Cin - C1), dtype=torch.float32, device=dy.device)
+    call('lvae_conv1x1_cat_bwd_f32', C.byref(d), ptr(x), ptr(x2), ptr(dx), ptr(dx2), ptr(dweight), ptr(dbias),
+         C.byref(ap) if ap is not None else None, ws.data_ptr(), ws.numel(), int(max_workgroups), stream_ptr())
+    return dx, dx2
+
+
 def conv2d_wgrad(x, dy, weight, g, dweight, dbias=None, x2=None, in_scale=None, in_shift=None, in_act=None):
     """dweight += d/dw, dbias += d/db for the convolution of `conv2d` with the same fused input transform.
     dweight must have the same strides as weight (a view of the gradient arena)."""

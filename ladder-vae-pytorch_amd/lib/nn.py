@@ -58,6 +58,7 @@ class Conv2dParams(nn.Module):
             init.uniform_(self.bias, -bound, bound)
         self._geom = None
         self._geom_key = None
+        self.__dict__['sched'] = resblock.BlockState()   # a merge 1x1 takes the deferred apply of the block behind it (ops.ConvFn): no parameter, buffer or submodule
 
     def geom(self):
         key = (self.weight.data_ptr(), tuple(self.weight.stride()))

@@ -164,9 +164,24 @@ class ConvFn(Function):
         x, x2, y = ctx.saved_tensors
         mod, g = ctx.mod, ctx.g
         dy = _c(dy)
+        w = mod.weight
+        if x2 is not None:
+            # merge / skip 1x1: dgrad of both halves and the weight gradient in one persistent launch, which also forms a dy that the
+            # residual block behind the merge left as a PendingApply (merge_announces); anything it does not take goes the old way
+            st = getattr(mod, 'sched', None)
+            pend = st.take_pending(dy) if st is not None else None
+            if (RB.switches.merge_bwd_fused and not ctx.out_act and w.requires_grad and ctx.needs_input_grad[0] and ctx.needs_input_grad[1] and
+                    _side['stream'] is None and dy.dtype == torch.float32 and
+                    dy.shape[0] * dy.shape[1] * dy.shape[2] >= RB.switches.merge_bwd_min_rows):
+                both = K.conv1x1_cat_bwd(dy, x, x2, w, g, grad_buf(w), grad_buf(mod.bias) if mod.bias is not None else None, apply=pend)
+                if both is not None:
+                    return both + (None,) * 5
+            if pend is not None:   # never dropped: the apply the block did not launch runs here, into the tensor the block returned
+                C = pend.coef0.numel()
+                sc, sh, mean, rstd = torch.as_strided(pend.coef0, (4, C), (C, 1)).unbind(0)
+                K.affine_act_bwd_parts(pend.parts, pend.dh, pend.x, sc, sh, pend.act, mean, rstd, pend.dgamma, pend.dbeta, add=pend.add, out=pend.out)
         if ctx.out_act:
             dy = K.act_bwd_from_out(dy, y, ctx.out_act)
-        w = mod.weight
         if w.requires_grad:
             db = grad_buf(mod.bias) if mod.bias is not None else None
             if ctx.share is not None and x2 is None:
@@ -191,8 +206,27 @@ class ConvFn(Function):
         return dx, dx2, None, None, None, None, None
 
 
+def merge_announces(x, x2, mod, y, out_act):
+    """True when the backward of this convolution over the concat (x, x2) with output y will be the persistent merge backward and can form
+    its own dy: the residual block that reads y may then leave its last BatchNorm apply to it (RB.Handover, as between two blocks)."""
+    sw = RB.switches
+    if not (sw.merge_bwd_fused and x2 is not None and out_act is None and mod.training and torch.is_grad_enabled()):
+        return False
+    if not (mod.weight.requires_grad and x.requires_grad and x2.requires_grad and y.dtype == torch.float32):
+        return False
+    if y.shape[0] * y.shape[1] * y.shape[2] < sw.merge_bwd_min_rows:
+        return False
+    return K.cat_bwd_apply_ok(y, mod.weight, mod.geom(), x.shape[3], mod.weight.grad)
+
+
 def conv(x, mod, x2=None, out_act=None, share=None):
-    return ConvFn.apply(x, x2, mod, out_act, mod.weight, mod.bias, share)
+    st = getattr(mod, 'sched', None)
+    if st is not None:
+        st.pending = None   # (left behind by a backward pass that was abandoned)
+    y = ConvFn.apply(x, x2, mod, out_act, mod.weight, mod.bias, share)
+    if st is not None and merge_announces(x, x2, mod, y, out_act):
+        y._lvae_handover = RB.Handover(None, None, st, 'any-dh')
+    return y
 
 
 # ----------------------------------------------------------------------------------------------------------------

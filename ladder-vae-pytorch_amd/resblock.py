@@ -22,7 +22,9 @@ class Switches:
         self.wgrad_pair = on('LVAE_WGRAD_PAIR')                       # ... and conv2's weight gradient rides in the same launch (kernels.conv2d_wgrad_pair) ...
         self.wgrad_pair_maxw = int(env.get('LVAE_WGRAD_PAIR_MAXW', '16'))     # ... up to this width (profiles/wgrad_pair_ab.txt)
         self.wgrad_shared = on('LVAE_WGRAD_SHARED')                   # a 16x16 stochastic layer's weight gradients go out as one launch (ops.WgradShare; profiles/wgrad_shared_ab.txt)
-        self.gate_stats = env.get('LVAE_NO_GATE_STATS') is None       # the gate epilogue writes the next block's BatchNorm partials
+        self.merge_bwd_fused = on('LVAE_MERGE_BWD_FUSED')             # a merge / skip 1x1's dgrad, weight gradient and the deferred apply before them in one persistent launch ...
+        self.merge_bwd_min_rows = int(env.get('LVAE_MERGE_BWD_MIN_ROWS', '65536'))   # ... from this many pixels (N*H*W) up: the 16x16 level at batch 256; below, the weight gradient rides the grouped launches (16384 measured -0.125 ms but not routed: profiles/merge_bwd_ab.txt, `routing`)
+        self.gate_stats = env.get('LVAE_NO_GATE_STATS') is None      # the gate epilogue writes the next block's BatchNorm partials
         self.defer_apply = on('LVAE_DEFER_APPLY')                     # a block leaves its last BatchNorm apply to its producer (BlockPlan.accepts)
         self.defer_apply_large = on('LVAE_DEFER_APPLY_LARGE')         # ... also into the persistent gate-backward kernel of the >= 16x16 levels
         # Which blocks take the whole-image launches (measured per level at batch 256, tools/rb_bench.py: forward old -> fused 41 -> 31 us at
