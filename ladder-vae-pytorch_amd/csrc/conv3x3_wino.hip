@@ -581,6 +581,12 @@ __global__ __launch_bounds__(256, MT == 1 ? 2 : 1) void conv3x3_wino_kernel(Wino
 //     (pair 0: M0 + M1, M1; pair 1: M2, -M2 - M3) and the store pass adds them while it forms Y = A^T R. The eight partial arrays of one
 //     32-tile block are 139 KB of LDS, so the two blocks go through the exchange one after the other (the first block's stores drain
 //     while the second block is exchanged).
+//   * memory order of the epilogue: its stores are write-through stores in inline asm (store_wt4), which the compiler's wait bookkeeping
+//     does not see, and a wave's memory counter retires in order. So every global read of the epilogue (bias, statistics coefficients,
+//     the Dropout2d mask and stats_x rows of BOTH blocks) is requested around block 0's exchange, branch-free (rows that are not wanted
+//     read a dummy address and are replaced afterwards), and closed once (close_load) in front of the first store; every barrier behind
+//     it is lds_barrier(). Between the first and the last store no wave waits for memory: 0 full drains behind a write-through store in
+//     the compiled code, where there were 5 (profiles/wino2_epilogue_isa.txt, profiles/wino2_epilogue_ab.txt).
 // Eligibility (wino2_tile): six-product form, exactly 64 tiles per workgroup whose blocks are the first and second 128 pixels of the
 // workgroup's pixel tile, and at least 256 such workgroups; everything else keeps conv3x3_wino_kernel.
 // ------------------------------------------------------------------------------------------------------------------------------------
@@ -596,6 +602,12 @@ constexpr int W2_LDS_R = 8 * 2 * 32 * WLDO * 4;  // bytes of the partial-sum exc
 // the matching 32 b-columns}), and a second pass stores ab, out = act(a) * sigmoid(b) + x and the BatchNorm partials of out. There is no
 // BatchNorm between conv2 and the gate, so nothing crosses workgroups: the 85 MB gate launch of a 256x16x16 block (25 us in the step)
 // becomes ~50 MB of stores and one residual read inside a launch that is already there.
+// Memory order as above, within 256 VGPRs: the wave's gate weights (96 VGPRs) are requested ONCE, where block 0's exchange has freed
+// acc[0], and kept for block 1; bias, gate bias and the statistics pivot wait in s_coef between their uses; block 0's mask and residual
+// rows are requested in front of the exchange. What does not fit beside the gate weights, the gate accumulators and acc[1] are the 32
+// VGPRs of block 1's mask and residual rows (66 spilled VGPRs when they are requested with block 0's): they are requested in front of
+// block 1's exchange, where the gate accumulators have died, and closed behind its barrier. That wait, the only one behind a store,
+// covers block 0's gate stores, which have had the exchange to drain.
 template <bool GATE>
 __global__ __launch_bounds__(512) void conv3x3_wino2_kernel(WinoArgs a) {
   kernarg_warmup<sizeof(WinoArgs)>();
@@ -640,7 +652,8 @@ __global__ __launch_bounds__(512) void conv3x3_wino2_kernel(WinoArgs a) {
     // slots beyond the patch write to a dump row of their own behind it (the LDS allocation is sized by the epilogue's exchange, far larger)
     hlds[u] = px < a.halo_px ? px * WLDA + hc4 : a.halo_px * WLDA + 4 * t;
   }
-  __shared__ __attribute__((aligned(16))) float s_coef[128];  // scale[64], shift[64] of a folded BatchNorm finalize
+  // scale[64], shift[64] of a folded BatchNorm finalize; GATE: behind the loop the epilogue's per-channel rows bias[64], g_bias[128], g_pivot[64]
+  __shared__ __attribute__((aligned(16))) float s_coef[GATE ? 256 : 128];
   const bool folded = a.f.parts != nullptr;
   const bool bn_in = d.in_scale != nullptr || folded;
   f32x4 hreg[SLOTS];
@@ -832,19 +845,96 @@ __global__ __launch_bounds__(512) void conv3x3_wino2_kernel(WinoArgs a) {
   // pair 0 holds (M0, M1) -> (M0 + M1, M1); pair 1 holds (M2, M3) -> (M2, -M2 - M3). Accumulator register r <-> tile (r&3) + 8(r>>2) + 4lh.
   float* Rs = smem;  // [wave][b][32 tiles][WLDO]
   const int c4 = (t % C4N) * 4, col = co0 + c4;
-  f32x4 st1 = zero4, st2 = zero4, piv, bsh, bmu, brs;  // BatchNorm partials of the stored values (d.stats_out)
-  stats_load_coef4(d.stats_pivot, d.Cout, col, d.stats_out != nullptr, d.stats_mode == LVAE_STATS_BN_BWD, piv, bsh, bmu, brs);
-  f32x4 bias = zero4;
-  if (d.bias && col < d.Cout) bias = *reinterpret_cast<const f32x4*>(d.bias + col);
+  f32x4 st1 = zero4, st2 = zero4;  // BatchNorm partials of the stored values (d.stats_out)
   const int thw = a.TH * a.TW;
   const int nvalid = min(a.NI, d.N - n0) * thw;
   float* yb = d.y + ((size_t)(n0 * d.H + oh0) * d.W) * d.Cout + col;
+  // Everything the epilogue reads from memory is requested BEFORE the kernel's first write-through store and closed (close_load) in
+  // front of it: the wave's memory counter retires in order, so a load issued behind such a store, or one the compiler still has open
+  // when the store goes out, can only be waited for together with the store's trip to memory (tools/wino2_stats_cost.py: the
+  // BatchNorm-backward sums cost 27.6 vs 21.2 us per dgrad launch when their x rows were loaded row by row between the stores).
+  // Between the blocks only LDS crosses waves, so every barrier from here on is lds_barrier(). One exception, GATE only: the rows of
+  // block 1 do not fit beside the gate weights, the gate accumulators and acc[1] (see the header comment); they are requested where the
+  // gate accumulators of block 0 have died, in front of block 1's exchange, and closed behind it.
+  const int prow0 = t / C4N;                                       // this thread's rows of a block: prow0 + PG q
+  const size_t grow0 = (size_t)(n0 * d.H + oh0) * d.W;             // global pixel row of the workgroup's row 0
+  const int gwm = wave >> 1, gwn = wave & 1;                       // GATE: this wave's 32 rows, its a-half column tile (b-half: 2 + gwn)
+  const bool want_sx = !GATE && d.stats_out != nullptr && d.stats_mode == LVAE_STATS_BN_BWD && col < d.Cout;
+  // Straight-line, as store_slice: a row that is not wanted is loaded from a dummy address (the head of x) and replaced when it is closed,
+  // so no lane branch and no wait of its own stands between the requests.
+  const bool want_aux = GATE ? a.g_res != nullptr : want_sx;
+  const float* const dummy = d.x + c4;
+  // (the address goes through an empty asm: left in sight, the compiler loads from both addresses under a lane branch and selects)
+  auto pick = [&](bool want, const float* p) {
+    const float* r = want ? p : dummy;
+    asm("" : "+v"(r));
+    return (const __attribute__((address_space(1))) f32x4*)(uintptr_t)r;  // still global memory: no flat load, which would count as LDS traffic too
+  };
+  // the values of stats_load_coef4 (bn_stats.h) and the bias, requested the same way
+  // (GATE takes no statistics of y2: its partials are those of `out`, around g_pivot)
+  const bool want_piv = !GATE && d.stats_out != nullptr && col < d.Cout, want_bwd = want_piv && d.stats_mode == LVAE_STATS_BN_BWD;
+  const bool want_bias = d.bias != nullptr && col < d.Cout;
+  f32x4 piv = zero4, bsh = zero4, bmu = zero4, brs = zero4;
+  if (!GATE) {
+    piv = *pick(want_piv, d.stats_pivot + col);
+    bsh = *pick(want_bwd, d.stats_pivot + d.Cout + col);
+    bmu = *pick(want_bwd, d.stats_pivot + 2 * d.Cout + col);
+    brs = *pick(want_bwd, d.stats_pivot + 3 * d.Cout + col);
+  }
+  f32x4 bias = *pick(want_bias, d.bias + col);
+  const bool want_msk = d.out_scale != nullptr && col < d.Cout;
+  f32x4 msk[2][128 / PG], aux[2][128 / PG];  // Dropout2d mask rows; stats_x rows of the BatchNorm-backward sums | GATE: residual rows
+  int rpc[2][128 / PG], rimg[2][128 / PG];   // row and image of each request, ahead of the requests (fastdiv branches on its magic)
+  auto index_rows = [&](int m) {
+#pragma unroll
+    for (int q = 0; q < 128 / PG; ++q) {
+      const int p = 128 * m + prow0 + PG * q;
+      rpc[m][q] = p < nvalid ? p : 0;
+      rimg[m][q] = fastdiv(rpc[m][q], a.m_thw);
+    }
+  };
+  index_rows(0);
+  if (!GATE) index_rows(1);
+  auto load_rows = [&](int m) {
+#pragma unroll
+    for (int q = 0; q < 128 / PG; ++q) {
+      const int pc = rpc[m][q];
+      const float* ap = GATE ? a.g_res + (grow0 + pc) * 64 + c4 : d.stats_x + (size_t)((n0 * d.H + oh0) * d.W + pc) * d.Cout + col;
+      aux[m][q] = *pick(want_aux, ap);
+      const int imgq = rimg[m][q];
+      msk[m][q] = *pick(want_msk, d.out_scale + (size_t)(n0 + imgq) * d.Cout + col);
+    }
+  };
+  auto close_rows = [&](int m) {
+#pragma unroll
+    for (int q = 0; q < 128 / PG; ++q) {
+      close_load(aux[m][q]);
+      close_load(msk[m][q]);
+      const bool keep = want_aux && (!GATE || 128 * m + prow0 + PG * q < nvalid);
+#pragma unroll
+      for (int e = 0; e < 4; ++e) {
+        aux[m][q][e] = keep ? aux[m][q][e] : 0.f;
+        msk[m][q][e] = want_msk ? msk[m][q][e] : 1.f;
+      }
+    }
+  };
+  bf16x8 gqa[GATE ? 4 : 1][3], gqb[GATE ? 4 : 1][3];  // GATE: the wave's gate weights, loaded once for both blocks
+  // GATE: the gate's bias halves and the pivot of its statistics (16 registers with the bias, which do not fit beside the gate weights:
+  // once closed they wait in s_coef, dead since the barrier behind the loop, and are read back where they are used)
+  const bool want_gb = GATE && a.g_bias != nullptr, want_gp = GATE && a.g_stats != nullptr;
+  f32x4 gba0 = *pick(want_gb, a.g_bias + c4);
+  f32x4 gbb0 = *pick(want_gb, a.g_bias + 64 + c4);
+  f32x4 gpiv0 = *pick(want_gp, a.g_pivot + c4);
+  load_rows(0);
 #pragma unroll
   for (int m = 0; m < 2; ++m) {
     if (m) {
       WINO_STAMP(5);
-      if (GATE) lds_barrier();  // (the gate pass of block 0 has read its tile; its write-through stores drain meanwhile)
-      else __syncthreads();     // the store pass of block 0 has read its partial sums
+      lds_barrier();  // the last pass of block 0 has read its LDS area; its write-through stores drain meanwhile
+      if (GATE) {
+        index_rows(1);
+        load_rows(1);
+      }
     }
 #pragma unroll
     for (int h = 0; h < NH; ++h)
@@ -858,31 +948,82 @@ __global__ __launch_bounds__(512) void conv3x3_wino2_kernel(WinoArgs a) {
         o[0] = r0;
         o[32 * WLDO] = r1;
       }
-    __syncthreads();
+    if (m == 0) {  // acc[0] is dead: its registers take what is left to request
+      if (GATE) {
+        const __bf16* gws = a.g_ws + lane * 8;
+#pragma unroll
+        for (int s4 = 0; s4 < 4; ++s4)
+#pragma unroll
+          for (int k = 0; k < 3; ++k) {
+            gqa[s4][k] = *reinterpret_cast<const bf16x8*>(gws + ((size_t)(s4 * 4 + gwn) * 3 + k) * 512);
+            gqb[s4][k] = *reinterpret_cast<const bf16x8*>(gws + ((size_t)(s4 * 4 + 2 + gwn) * 3 + k) * 512);
+          }
+      } else {
+        load_rows(1);
+      }
+    }
+    lds_barrier();
     if (m == 0) WINO_STAMP(4); else WINO_STAMP(6);
+    if (m == 0) {  // the one wait for memory of the epilogue, in front of the first store
+      if (!GATE) {
+        close_load(piv);
+        close_load(bsh);
+        close_load(bmu);
+        close_load(brs);
+        close_load(bias);
+#pragma unroll
+        for (int e = 0; e < 4; ++e) {
+          piv[e] = want_piv ? piv[e] : 0.f;
+          bsh[e] = want_bwd ? bsh[e] : piv[e];
+          bmu[e] = want_bwd ? bmu[e] : piv[e];
+          brs[e] = want_bwd ? brs[e] : piv[e];
+          bias[e] = want_bias ? bias[e] : 0.f;
+        }
+      }
+      close_rows(0);
+      if (GATE) {
+        // the per-channel rows go into s_coef for the later passes (published by the barrier behind this store pass, which itself
+        // takes the bias from the register)
+        close_load(bias);
+        close_load(gba0);
+        close_load(gbb0);
+        close_load(gpiv0);
+#pragma unroll
+        for (int e = 0; e < 4; ++e) {
+          bias[e] = want_bias ? bias[e] : 0.f;
+          gba0[e] = want_gb ? gba0[e] : 0.f;
+          gbb0[e] = want_gb ? gbb0[e] : 0.f;
+          gpiv0[e] = want_gp ? gpiv0[e] : 0.f;
+        }
+        if (prow0 == 0) {
+          *reinterpret_cast<f32x4*>(s_coef + c4) = bias;
+          *reinterpret_cast<f32x4*>(s_coef + 64 + c4) = gba0;
+          *reinterpret_cast<f32x4*>(s_coef + 128 + c4) = gbb0;
+          *reinterpret_cast<f32x4*>(s_coef + 192 + c4) = gpiv0;
+        }
+#pragma unroll
+        for (int s4 = 0; s4 < 4; ++s4)
+#pragma unroll
+          for (int k = 0; k < 3; ++k) {
+            close_load(gqa[s4][k]);
+            close_load(gqb[s4][k]);
+          }
+      } else {
+        close_rows(1);
+      }
+    } else if (GATE) {
+      close_rows(1);
+    }
     f32x4 gy[GATE ? 128 / PG : 1];   // GATE: this thread's rows of y2 (zero for rows past the batch)
     if (GATE) {
 #pragma unroll
       for (int q = 0; q < 128 / PG; ++q) gy[q] = zero4;
     }
-    // Everything this pass reads from memory is requested BEFORE its first store: the wave's memory counter retires in order, so a load
-    // issued behind a write-through store can only be waited for together with that store's trip to memory (tools/wino2_stats_cost.py:
-    // the BatchNorm-backward sums cost 27.6 vs 21.2 us per dgrad launch when their x rows were loaded row by row between the stores).
-    const bool want_sx = !GATE && d.stats_out != nullptr && d.stats_mode == LVAE_STATS_BN_BWD && col < d.Cout;
-    f32x4 sxr[128 / PG], msk[128 / PG];
-#pragma unroll
-    for (int q = 0; q < 128 / PG; ++q) {
-      const int p = 128 * m + t / C4N + PG * q;
-      const int pc = p < nvalid ? p : 0;
-      sxr[q] = want_sx ? *reinterpret_cast<const f32x4*>(d.stats_x + (size_t)((n0 * d.H + oh0) * d.W + pc) * d.Cout + col) : zero4;
-      const int imgq = fastdiv(pc, a.m_thw);
-      msk[q] = (d.out_scale != nullptr && col < d.Cout) ? *reinterpret_cast<const f32x4*>(d.out_scale + (size_t)(n0 + imgq) * d.Cout + col)
-                                                         : f32x4{1.f, 1.f, 1.f, 1.f};
-    }
+    if (GATE && m == 1) bias = *reinterpret_cast<const f32x4*>(s_coef + c4);
     if (col < d.Cout) {
 #pragma unroll
       for (int q = 0; q < 128 / PG; ++q) {
-        const int p = 128 * m + t / C4N + PG * q;
+        const int p = 128 * m + prow0 + PG * q;
         if (p < nvalid) {
           const int img = fastdiv(p, a.m_thw), pr = p - img * thw;
           const int oy = fastdiv(pr, a.m_tw), ox = pr - oy * a.TW;
@@ -896,14 +1037,14 @@ __global__ __launch_bounds__(512) void conv3x3_wino2_kernel(WinoArgs a) {
           for (int k = 0; k < 3; ++k)
             Rr[k] = *reinterpret_cast<const f32x4*>(rp + (2 * (i0 + k)) * WS) + *reinterpret_cast<const f32x4*>(rp + (2 * (i0 + k) + 1) * WS);
           f32x4 v = (oy & 1) ? (Rr[0] - Rr[1] - Rr[2]) : (Rr[0] + Rr[1] + Rr[2]);
-          v = (v + bias) * msk[q];
+          v = (v + bias) * msk[m][q];
           v = act_fwd4(v, d.out_act);
           if (!(dbg & 4) || v[0] == 12345.678f) store_wt4(yb + (size_t)p * d.Cout, v);
           if (GATE) {
             gy[q] = v;
           } else if (d.stats_mode == LVAE_STATS_BN_BWD) {
             if (d.stats_out) {
-              const f32x4 xv = sxr[q];
+              const f32x4 xv = aux[m][q];
               stats_bwd_accum4(v, xv, piv, bsh, bmu, brs, d.stats_act, st1, st2);
             }
           } else {
@@ -914,28 +1055,7 @@ __global__ __launch_bounds__(512) void conv3x3_wino2_kernel(WinoArgs a) {
     }
     if (GATE) {
       constexpr int LDKG = 72, G_PLANE = 128 * LDKG, LDG = 132;   // bf16 row pitch of the y2 planes; float row pitch of the pre-activations
-      const size_t grow = (size_t)(n0 * d.H + oh0) * d.W + 128 * m;   // global pixel row of this block's row 0
-      const int prow0 = t / C4N;                                       // this thread's rows: prow0 + PG q
-      // gate weights of this wave (a-half column tile gwn, b-half tile 2 + gwn) and the residual rows: requested before the barriers
-      const int gwm = wave >> 1, gwn = wave & 1;
-      bf16x8 gqa[4][3], gqb[4][3];
-      {
-        const __bf16* gws = a.g_ws + lane * 8;
-#pragma unroll
-        for (int s4 = 0; s4 < 4; ++s4)
-#pragma unroll
-          for (int k = 0; k < 3; ++k) {
-            gqa[s4][k] = *reinterpret_cast<const bf16x8*>(gws + ((size_t)(s4 * 4 + gwn) * 3 + k) * 512);
-            gqb[s4][k] = *reinterpret_cast<const bf16x8*>(gws + ((size_t)(s4 * 4 + 2 + gwn) * 3 + k) * 512);
-          }
-      }
-      f32x4 gres[128 / PG];
-#pragma unroll
-      for (int q = 0; q < 128 / PG; ++q) {
-        const int pl = prow0 + PG * q;
-        const bool okr = 128 * m + pl < nvalid;
-        gres[q] = (a.g_res != nullptr && okr) ? *reinterpret_cast<const f32x4*>(a.g_res + (grow + pl) * 64 + c4) : zero4;
-      }
+      const size_t grow = grow0 + 128 * m;                         // global pixel row of this block's row 0
       lds_barrier();   // the store pass has read the partial sums: the area becomes the y2 planes [3][128][72] bf16
       __bf16* Gs = reinterpret_cast<__bf16*>(smem);
 #pragma unroll
@@ -969,12 +1089,8 @@ __global__ __launch_bounds__(512) void conv3x3_wino2_kernel(WinoArgs a) {
         Qs[row * LDG + 64 + gwn * 32 + li] = accb[r];
       }
       lds_barrier();
-      f32x4 gba = zero4, gbb = zero4, gpiv = zero4;
-      if (a.g_bias) {
-        gba = *reinterpret_cast<const f32x4*>(a.g_bias + c4);
-        gbb = *reinterpret_cast<const f32x4*>(a.g_bias + 64 + c4);
-      }
-      if (a.g_stats) gpiv = *reinterpret_cast<const f32x4*>(a.g_pivot + c4);
+      const f32x4 gba = *reinterpret_cast<const f32x4*>(s_coef + 64 + c4), gbb = *reinterpret_cast<const f32x4*>(s_coef + 128 + c4);
+      const f32x4 gpiv = *reinterpret_cast<const f32x4*>(s_coef + 192 + c4);
 #pragma unroll
       for (int q = 0; q < 128 / PG; ++q) {
         const int pl = prow0 + PG * q;
@@ -988,7 +1104,7 @@ __global__ __launch_bounds__(512) void conv3x3_wino2_kernel(WinoArgs a) {
           f32x4 o = act_fwd4(av, a.g_act);
 #pragma unroll
           for (int j = 0; j < 4; ++j) o[j] *= sigmoidf_(bv[j]);
-          o += gres[q];
+          o += aux[m][q];
           store_wt4(a.g_out + (grow + pl) * 64 + c4, o);
           stats_fwd_accum4(o, gpiv, st1, st2);
         }

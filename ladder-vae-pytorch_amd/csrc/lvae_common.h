@@ -89,6 +89,13 @@ __device__ __forceinline__ void store_wt4(float* p, f32x4 v) {
 // goes through LDS, only the LDS counter has to drain.
 __device__ __forceinline__ void lds_barrier() { asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory"); }
 
+// Closes an early global load in front of inline-asm stores. The compiler counts its own loads but not the stores of store_wt4, so a
+// load that is still open in its books when such a store is issued gets its wait wherever the value is first touched afterwards: as
+// vmcnt(0) behind the store, which the wave's in-order memory counter turns into a wait for the store's trip to memory. Passing the
+// value through an empty asm makes the compiler place the wait here, where only loads are outstanding; no instruction is emitted.
+template <class T>
+__device__ __forceinline__ void close_load(T& v) { asm volatile("" : "+v"(v)); }
+
 // Kernel-argument warm-up. A launch's argument block is private to it (cold in the scalar cache and in L2), and hipcc reads a large block
 // piecemeal, where a field is first used: several dependent s_load -> s_waitcnt pairs spread over the prologue, each a possible miss to
 // memory. One scalar load per 64-byte line up front turns them into ONE round trip; the results are never used. -DLVAE_KERNARG_WARM=0
