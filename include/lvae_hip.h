@@ -848,6 +848,18 @@ int lvae_latent_stats_finalize_f64(const double* sums, int64_t U, int64_t n_imag
 int lvae_summary_fold_f64(const float* loss, const float* elbo, const float* recons, const float* kl, const float* l2,
                           const float* grad_norm, const float* gscale, const float* kl_layers, int32_t L, double* acc, void* stream);
 int lvae_summary_take_f64(double* acc, int32_t n, double* out, void* stream);
+/* Gradient accumulation: the mean of a step's metrics over its M micro-passes. One launch of one wave at the end of every micro-pass adds
+ * that pass's fp32 scalars, widened to double exactly, into acc (device double [7 + L], 8-byte aligned, zero before the first pass):
+ *   [0] loss   [1] elbo   [2] recons   [3] kl   [4] l2   [5] iw   [6] ess   [7 + l] kl_layers[l], 0 <= l < L <= 64
+ * and advances count (device int64[1], zero before the first pass). iw and ess may be NULL (their slots then hold 0); kl_layers may be NULL
+ * when L = 0. The M-th call writes out[s] = (float)(acc[s] / M) for every slot (out: device float [7 + L], untouched by the calls before
+ * it) and clears acc and count, so the next step starts from zero without a launch of its own. A NaN or Inf of any pass reaches the mean
+ * of its slot and no other. Each slot belongs to one thread, plain loads and stores, no atomics: the same passes give the same bits,
+ * launched eagerly or replayed. M < 1, L outside [0, 64] or a null required pointer: LVAE_EINVAL; misaligned: LVAE_EALIGN; nothing
+ * launched. No allocation, no synchronisation. */
+int lvae_micro_fold_f64(const float* loss, const float* elbo, const float* recons, const float* kl, const float* l2, const float* iw,
+                        const float* ess, const float* kl_layers, int32_t L, int32_t M, double* acc, int64_t* count, float* out,
+                        void* stream);
 
 /* ------------------------------------------------------------------------------------------------------------
  * Picture grids — torchvision's make_grid (padding 2) + save_image and boilr's img_grid_pad_value, restated from their published

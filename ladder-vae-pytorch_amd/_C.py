@@ -228,6 +228,7 @@ SIGNATURES = {
     'lvae_latent_stats_finalize_f64': (C.c_int, [_P, _L, _L, C.c_double, C.c_double, _P, _P, _P]),
     'lvae_summary_fold_f64': (C.c_int, [_P, _P, _P, _P, _P, _P, _P, _P, _I, _P, _P]),
     'lvae_summary_take_f64': (C.c_int, [_P, _I, _P, _P]),
+    'lvae_micro_fold_f64': (C.c_int, [_P, _P, _P, _P, _P, _P, _P, _P, _I, _I, _P, _P, _P, _P]),
     'lvae_image_border_count_f32': (C.c_int, [_P, _I, _P, _I, _I, _I, _I, _I, _F, _P, _P]),
     'lvae_image_grid_u8': (C.c_int, [_P, _I, _P, _I, _I, _I, _I, _I, _I, _P, _F, _P, _L, _P]),
     'lvae_batch_gather_f32': (C.c_int, [_P, _I, _I, _I, _I, _I, _I, _P, _P, _I, _I, _I, _L, _I, _P, _P]),

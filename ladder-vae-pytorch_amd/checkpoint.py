@@ -92,13 +92,20 @@ def rule_warning(path, ck, optimizer):
     return 'warning: %s was written with the update rule %s; continuing with %s' % (path, was, optimizer.rule)
 
 
+def accum_steps_record(ck):
+    """The micro-batches per optimizer step of a loaded file's run: its 'accum_steps', 1 for a file from before there was one (or a bare
+    state_dict)."""
+    return int(ck.get('accum_steps', 1)) if isinstance(ck, dict) and 'model' in ck else 1
+
+
 def save_checkpoint(path, model, optimizer=None, summary=None):
     """Weights (reference layout), global step, Adamax state and the position of the Philox noise stream, so that a resumed run continues
     the original one bit for bit. With a `summary` (summary.TrainSummary) also 'summary': the open log window's accumulator as a list of
     floats, so that the run resumed in the middle of a window prints the train line of the uninterrupted one. A scheduled lr is a function
     of the Adamax step and of the schedule, stored as 'lr_schedule' (`lr_schedule_record`). 'iw_train_samples' notes the K of the objective
     the run trained on (model.iw_train_samples; 1 = the ELBO), by the same rule: load_checkpoint does not touch the resumed run's own.
-    A guarded optimizer adds 'grad_guard' (GradGuard.state_dict: its limits and the cumulative clipped / skipped counts)."""
+    A guarded optimizer adds 'grad_guard' (GradGuard.state_dict: its limits and the cumulative clipped / skipped counts). 'accum_steps' notes
+    the micro-batches per optimizer step (model.accum_steps; `accum_steps_record` reads it back, 1 from a file without the key)."""
     ck = {'model': state_dict_reference_layout(model), 'global_step': int(model.global_step)}
     if optimizer is not None:
         ck['optimizer'] = optimizer_state_by_name(model, optimizer)
@@ -110,6 +117,7 @@ def save_checkpoint(path, model, optimizer=None, summary=None):
         if getattr(optimizer, 'guard', None) is not None:
             ck['grad_guard'] = optimizer.guard.state_dict()
     ck['iw_train_samples'] = int(getattr(model, 'iw_train_samples', 1))   # what the file's run trained on; a resumed run uses its own flag
+    ck['accum_steps'] = int(getattr(model, 'accum_steps', 1))             # micro-batches per optimizer step, by the same rule
     nz = noise_state(model)
     if nz is not None:
         ck['noise'] = nz

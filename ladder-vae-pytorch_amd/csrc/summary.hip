@@ -2,6 +2,8 @@
 // folds its fp32 scalars into a small double accumulator with ONE launch of one wave, inside the captured step; a log line takes the
 // accumulator (copy out and clear) once. Every value is widened to double exactly and added to its own slot by the one thread that owns
 // the slot, so a window's sum is the sequential float64 sum of the per-step float32 values in step order, whatever the launch mode.
+// A step accumulated over M micro-passes keeps the means of its metrics the same way (micro_fold_kernel): one wave per micro-pass, the
+// M-th of which writes the means and clears the accumulator.
 #include "lvae_common.h"
 
 namespace lvae {
@@ -45,6 +47,42 @@ __global__ __launch_bounds__(64) void summary_take_kernel(double* __restrict__ a
   }
 }
 
+constexpr int kMicroFixed = 7;      // [loss, elbo, recons, kl, l2, iw, ess]
+
+// One micro-pass of an accumulated step: acc (double) [7 + L] += this pass's fp32 scalars, count[0] += 1; on the M-th call
+// out[s] = (float)(acc[s] / M), acc[s] = 0 and count[0] = 0. Thread i owns slot i (with L > 57 also slot i + 64) of acc and out and no
+// other. Every thread reads the pass counter before the barrier and thread 0 alone writes it after, so all of them decide alike.
+__global__ __launch_bounds__(64) void micro_fold_kernel(const float* __restrict__ loss, const float* __restrict__ elbo,
+                                                        const float* __restrict__ recons, const float* __restrict__ kl,
+                                                        const float* __restrict__ l2, const float* __restrict__ iw,
+                                                        const float* __restrict__ ess, const float* __restrict__ kl_layers, int L, int M,
+                                                        double* __restrict__ acc, long long* __restrict__ count, float* __restrict__ out) {
+  const long long pass = count[0] + 1;
+  const bool last = pass >= (long long)M;
+  __syncthreads();
+  for (int s = threadIdx.x; s < kMicroFixed + L; s += 64) {
+    float v;
+    switch (s) {
+      case 0: v = loss[0]; break;
+      case 1: v = elbo[0]; break;
+      case 2: v = recons[0]; break;
+      case 3: v = kl[0]; break;
+      case 4: v = l2[0]; break;
+      case 5: v = iw ? iw[0] : 0.f; break;
+      case 6: v = ess ? ess[0] : 0.f; break;
+      default: v = kl_layers[s - kMicroFixed]; break;
+    }
+    const double a = acc[s] + (double)v;
+    if (last) {
+      out[s] = (float)(a / (double)M);
+      acc[s] = 0.0;
+    } else {
+      acc[s] = a;
+    }
+  }
+  if (threadIdx.x == 0) count[0] = last ? 0 : pass;
+}
+
 inline bool al4(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 3) == 0; }
 inline bool al8(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 7) == 0; }
 
@@ -75,5 +113,22 @@ extern "C" int lvae_summary_take_f64(double* acc, int32_t n, double* out, void* 
   LVAE_REQUIRE(al8(acc) && al8(out), LVAE_EALIGN, "lvae_summary_take_f64: a buffer is not 8-byte aligned");
   hipLaunchKernelGGL(summary_take_kernel, dim3(1), dim3(64), 0, (hipStream_t)stream, acc, (int)n, out);
   LVAE_LAUNCH_CHECK("summary_take");
+  return 0;
+}
+
+extern "C" int lvae_micro_fold_f64(const float* loss, const float* elbo, const float* recons, const float* kl, const float* l2,
+                                   const float* iw, const float* ess, const float* kl_layers, int32_t L, int32_t M, double* acc,
+                                   int64_t* count, float* out, void* stream) {
+  LVAE_REQUIRE(M >= 1, LVAE_EINVAL, "lvae_micro_fold_f64: M = %d micro-passes per step (at least 1)", (int)M);
+  LVAE_REQUIRE(L >= 0 && L <= kSummaryMaxL, LVAE_EINVAL, "lvae_micro_fold_f64: L = %d outside [0, %d]", (int)L, kSummaryMaxL);
+  LVAE_REQUIRE(loss && elbo && recons && kl && l2 && acc && count && out, LVAE_EINVAL,
+               "lvae_micro_fold_f64: null scalar, accumulator, counter or output");
+  LVAE_REQUIRE(L == 0 || kl_layers, LVAE_EINVAL, "lvae_micro_fold_f64: kl_layers missing for L = %d", (int)L);
+  LVAE_REQUIRE(al4(loss) && al4(elbo) && al4(recons) && al4(kl) && al4(l2) && al4(iw) && al4(ess) && al4(kl_layers) && al4(out),
+               LVAE_EALIGN, "lvae_micro_fold_f64: a float pointer is not 4-byte aligned");
+  LVAE_REQUIRE(al8(acc) && al8(count), LVAE_EALIGN, "lvae_micro_fold_f64: the accumulator or the counter is not 8-byte aligned");
+  hipLaunchKernelGGL(micro_fold_kernel, dim3(1), dim3(64), 0, (hipStream_t)stream, loss, elbo, recons, kl, l2, iw, ess, kl_layers, (int)L,
+                     (int)M, acc, reinterpret_cast<long long*>(count), out);
+  LVAE_LAUNCH_CHECK("micro_fold");
   return 0;
 }

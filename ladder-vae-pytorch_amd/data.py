@@ -233,7 +233,9 @@ class DeviceDataset:
     loader); epoch e visits epoch_permutation(seed, e, N)[:steps_per_epoch * batch_size].
 
     On the device: the image table, an int32 index table with the current epoch's order, and `cursor`, an int64[1] holding the number of
-    completed steps. A training step gathers through (index table, cursor) and advances the cursor as its last launch; before a step that
+    completed steps (of completed micro-batches when a step accumulates over several: `attach(model, micro)`; `step`, `steps_per_epoch`
+    and `indices` then count micro-batches, `step_indices` / `step_epoch` optimizer steps). A training step gathers through (index table,
+    cursor) and advances the cursor as its last launch; before a step that
     begins a new epoch the host replaces the index table with a copy ordered on the step's stream (`before_step`), so a captured graph
     keeps the addresses it baked in. Host-side queries (`indices`, sizes) need no GPU; device memory is taken on first use."""
 
@@ -255,6 +257,7 @@ class DeviceDataset:
                 raise ValueError("%d images do not fill one batch of %d" % (self.N, self.batch_size))
             self.lo, self.hi = shard_batch(self.batch_size, rank, world)
             self.steps_per_epoch = self.N // self.batch_size
+        self.micro = 1                  # batches of batch_size per optimizer step (attach): > 1 when the step accumulates over micro-batches
         self.table = self.index = self.cursor = None
         self._index_epoch = None        # the epoch whose order the device index table holds (or will, once the queued copy has run)
         self._perm = (None, None)
@@ -287,6 +290,26 @@ class DeviceDataset:
         pos = (int(step) - 1) % self.steps_per_epoch
         return self._order(self.epoch_of(step))[pos * self.batch_size:(pos + 1) * self.batch_size].clone()
 
+    def step_indices(self, step, micro=None):
+        """The image numbers optimizer step `step` (1-based) consumes when every step takes `micro` batches (default: what `attach` was
+        told): the `indices` of its micro-batches (step - 1) * micro + 1 ... step * micro, concatenated. An epoch may end inside a step."""
+        m = self.micro if micro is None else int(micro)
+        if m < 1:
+            raise ValueError("a step takes at least one batch, got %d" % m)
+        if step < 1:
+            raise ValueError("steps count from 1")
+        return torch.cat([self.indices((int(step) - 1) * m + j + 1) for j in range(m)])
+
+    def step_epoch(self, step, micro=None):
+        """0-based epoch of the FIRST micro-batch of optimizer step `step` (1-based): the epoch --max-epochs compares."""
+        m = self.micro if micro is None else int(micro)
+        return self.epoch_of((int(step) - 1) * m + 1)
+
+    def cursor_at(self, global_step, micro=None):
+        """Where the cursor stands after `global_step` completed optimizer steps of `micro` batches each (what `attach` writes)."""
+        m = self.micro if micro is None else int(micro)
+        return int(global_step) * m
+
     # ---- device side -----------------------------------------------------------------------------------------------
     def _dev(self):
         if self.table is None:
@@ -316,13 +339,18 @@ class DeviceDataset:
         self._stage_done[k].record(torch.cuda.current_stream(self.device))
         self._index_epoch = epoch
 
-    def attach(self, model):
-        """Start (or, after a resume, continue) feeding `model`: the cursor takes model.global_step, the completed steps."""
+    def attach(self, model, micro=1):
+        """Start (or, after a resume, continue) feeding `model`, `micro` batches per optimizer step: the cursor takes
+        model.global_step * micro, the batches the completed steps consumed."""
+        micro = int(micro)
+        if micro < 1:
+            raise ValueError("a step takes at least one batch, got %d" % micro)
+        self.micro = micro
         self._dev()
         if self.cursor is None:
             self.cursor = torch.empty(1, dtype=torch.int64, device=self.device)
-        self.cursor.fill_(int(model.global_step))
-        self._load_index(int(model.global_step) // self.steps_per_epoch)
+        self.cursor.fill_(self.cursor_at(model.global_step))
+        self._load_index(self.cursor_at(model.global_step) // self.steps_per_epoch)
         return self
 
     def before_step(self, completed_steps):

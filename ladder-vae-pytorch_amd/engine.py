@@ -14,6 +14,9 @@ With a guard on the optimizer (optim.GradGuard) the step saves the BatchNorm run
 before Adamax takes the gradient's norm, decides whether the step is clipped or skipped and, if skipped, puts the statistics back; the
 summary then reads the guard's norm instead of taking it again. A skipped step still counts as a step of the run: the global step, the beta
 warm-up, the data cursor, the noise stream and num_batches_tracked advance; the model and the optimizer keep their bits.
+With accum_steps = M > 1 one optimizer step consumes M micro-batches: zero_grad [+ the guard's save] once | gather, forward, backward, the
+fold of the pass's metrics into their means (kernels.micro_fold) and the cursor advance, M times | the exchange (split form) once | guard,
+summary, optimizer and beta counter once. Captured, these are three graphs in one pool, the middle one replayed M times.
 """
 import os
 import sys
@@ -59,6 +62,18 @@ def check_iw_objective(model, iw_samples):
     return iw_samples
 
 
+def micro_slices(rows, accum_steps):
+    """The rows of one optimizer step cut into `accum_steps` equal micro-batches, in order: [(lo, hi), ...]. ValueError when accum_steps < 1
+    or the rows do not divide by it (a pure function: no tensor, no device)."""
+    rows, m = int(rows), int(accum_steps)
+    if m < 1:
+        raise ValueError("accum_steps must be at least 1, got %d" % m)
+    if rows < m or rows % m:
+        raise ValueError("a step of %d rows cannot be cut into %d equal micro-batches" % (rows, m))
+    per = rows // m
+    return [(j * per, (j + 1) * per) for j in range(m)]
+
+
 def forward_pass(model, x, beta=1.0, compute_l2=True, beta_anneal=0, iw_samples=1):
     """LVAEExperiment.forward_pass (experiment/experiment_manager.py:322-367) on the HIP engine. beta_anneal != 0: the KL warm-up,
     beta = linear_anneal(global step, 0, 1, beta_anneal) read on the device from `global_step_counter(model)` (`beta` is ignored).
@@ -94,8 +109,11 @@ class TrainStep:
     the device at the feed's cursor (eager steps and the captured step alike: gather | forward, backward, exchange, Adamax | cursor advance)."""
 
     def __init__(self, model, optimizer, beta=1.0, use_graph=True, allreduce=None, eager_warmup=2, async_wgrad=False,
-                 wgrad_streams=1, wgrad_group_rows=16384, beta_anneal=0, feed=None, summary=None, iw_samples=1):
+                 wgrad_streams=1, wgrad_group_rows=16384, beta_anneal=0, feed=None, summary=None, iw_samples=1, accum_steps=1):
         self.model, self.opt, self.beta = model, optimizer, beta
+        self.accum = int(accum_steps)         # M > 1: one optimizer step over M micro-batches (prologue | M micro-passes | exchange | epilogue)
+        if self.accum < 1:
+            raise ValueError("accum_steps must be at least 1, got %d" % self.accum)
         self.iw_samples = check_iw_objective(model, iw_samples)   # K > 1: train on the K-sample importance-weighted bound
         self.feed = feed
         self.summary = summary                # None: the step issues not one launch more
@@ -106,7 +124,7 @@ class TrainStep:
         self.use_graph, self.allreduce = use_graph, allreduce
         self.wgrad_group_rows = wgrad_group_rows
         self.eager_left = eager_warmup if use_graph else -1
-        self.graph_a = self.graph_b = None
+        self.graph_a = self.graph_b = self.graph_p = None
         self.fallback_reason = None
         self.static_x = None
         self.static_out = None
@@ -120,6 +138,23 @@ class TrainStep:
             self.use_graph, self.eager_left = False, -1   # gloo stages device buffers through the host: cannot be part of a graph
         self.trace = os.environ.get('LVAE_STEP_TRACE') == '1'   # diagnosis only: host-synchronised phase times on stderr
         self.overlap = allreduce is not None and allreduce.active and allreduce.overlap
+        if self.overlap and self.accum > 1:
+            raise ValueError("accum_steps=%d needs the gradient exchange in split form (one exchange after the last micro-pass); the "
+                             "overlapped form (LVAE_DDP_MODE=overlap) would exchange every micro-pass: use LVAE_DDP_MODE=split" % self.accum)
+        if self.accum > 1:
+            # the arena holds the SUM over the M micro-passes (and, after the exchange, over the ranks): the guard's norm, the summary's
+            # grad and the update all scale it by this one device float, so they see the mean over the M * batch-size images
+            optimizer._state()
+            world = allreduce.world if allreduce is not None else 1
+            optimizer.gscale = torch.full((1,), 1.0 / (self.accum * world), dtype=torch.float32, device=dev)
+            n = K.MICRO_FIXED + len(model.top_down_layers)
+            self._macc = torch.zeros(n, dtype=torch.float64, device=dev)     # lvae_micro_fold_f64: sums of the passes so far,
+            self._mcount = torch.zeros(1, dtype=torch.int64, device=dev)     # how many there were,
+            self._mean = torch.zeros(n, dtype=torch.float32, device=dev)     # and the means of the last complete step
+            names = ('loss', 'elbo', 'recons', 'kl', 'l2') + (('iw', 'ess') if self.iw_samples > 1 else ())
+            slot = {'loss': 0, 'elbo': 1, 'recons': 2, 'kl': 3, 'l2': 4, 'iw': 5, 'ess': 6}
+            self._mean_out = {k: self._mean[slot[k]] for k in names}
+            self._mean_out['kl_avg_layerwise'] = self._mean[K.MICRO_FIXED:]
         if self.overlap and self.use_graph:
             # can the exchange be part of the step graph? If not, the same process continues with the exchange
             # outside the graphs: fwd+bwd graph | eager all-reduce | Adamax graph
@@ -134,17 +169,20 @@ class TrainStep:
             optimizer._state()
             optimizer.guard.attach(model)    # state, shadow and copy tables exist before anything is captured
         if feed is not None:
-            feed.attach(model)               # cursor = model.global_step: a resumed run continues in the middle of its epoch
+            feed.attach(model, self.accum)   # cursor = model.global_step * M: a resumed run continues in the middle of its epoch
             self.static_x = feed.new_batch()
 
-    def _fwd_bwd(self, x):
+    def _fwd_bwd(self, x, micro=False):
+        """One forward and backward pass. micro: a micro-pass of an accumulated step, which neither clears the arena nor saves the BatchNorm
+        statistics (the prologue did) nor advances the beta counter (the epilogue will), and ends in micro_fold and the feed's advance."""
         done = False
         try:
             if self.feed is not None:
                 x = self.feed.gather(self.static_x)   # first launch of a fed step
-            if getattr(self.opt, 'guard', None) is not None:
+            if getattr(self.opt, 'guard', None) is not None and not micro:
                 self.opt.guard.save_bn(self.model)    # a skipped step puts them back (_fold)
-            self.opt.zero_grad()
+            if not micro:
+                self.opt.zero_grad()
             K.prepared.prepare_all()  # one launch: transformed weights of every Winograd convolution seen so far
             out = forward_pass(self.model, x, self.beta, beta_anneal=self.beta_anneal, iw_samples=self.iw_samples)
             if self.allreduce is not None:
@@ -159,8 +197,13 @@ class TrainStep:
             ops.join_wgrad_stream()
             if self.overlap:
                 self.allreduce.finish()  # last bucket + join: the gradients are summed over ranks from here on
-            if self.beta_anneal:
+            if self.beta_anneal and not micro:
                 K.counter_advance(global_step_counter(self.model), 1)   # the next step's beta; inside the graph when captured
+            if micro:
+                K.micro_fold(out['loss'], out['elbo'], out['recons'], out['kl'], out['l2'], out['kl_avg_layerwise'], self.accum,
+                             self._macc, self._mcount, self._mean, iw=out.get('iw'), ess=out.get('ess'))
+                if self.feed is not None:
+                    self.feed.advance()   # the cursor counts micro-batches
             done = True
         finally:
             if not done:
@@ -210,6 +253,93 @@ class TrainStep:
         if self.feed is not None:
             self.feed.advance()   # last launch: a step abandoned before this point leaves the cursor where it was
         return out
+
+    # ---- accum_steps = M > 1 ------------------------------------------------------------------------------------------------------
+    def _prologue(self):
+        self.opt.zero_grad()
+        if getattr(self.opt, 'guard', None) is not None:
+            self.opt.guard.save_bn(self.model)    # the statistics from before the first micro-pass: a skipped step puts them back
+
+    def _epilogue(self):
+        self._fold(self._mean_out)                # guard, BatchNorm restore and log window read the means over the micro-passes
+        self.opt.step()
+        if self.beta_anneal:
+            K.counter_advance(global_step_counter(self.model), 1)
+
+    def _capture_accum(self, x0):
+        """Three graphs in one pool: the prologue, ONE micro-pass (replayed M times) and the epilogue; the exchange runs between the last
+        two, outside them."""
+        if self.feed is None:
+            self.static_x = torch.empty_like(x0)
+        torch.cuda.synchronize()
+        self.graph_p, self.graph_a, self.graph_b = torch.cuda.CUDAGraph(), torch.cuda.CUDAGraph(), torch.cuda.CUDAGraph()
+        with torch.cuda.graph(self.graph_p, capture_error_mode='thread_local'):
+            self._prologue()
+        with torch.cuda.graph(self.graph_a, pool=self.graph_p.pool(), capture_error_mode='thread_local'):
+            self._fwd_bwd(self.static_x, micro=True)
+        with torch.cuda.graph(self.graph_b, pool=self.graph_p.pool(), capture_error_mode='thread_local'):
+            self._epilogue()
+        self._bns = self.model.bn_modules()
+        self._table_ref = K.prepared.pin_current()
+
+    def _abandon(self, completed, bns, pend0):
+        """An accumulated step was given up (a failed capture, an exception in a micro-pass): no graph, no host counter and no device
+        counter of the step's own keeps anything of it. Runs outside any capture."""
+        self.graph_p = self.graph_a = self.graph_b = None
+        self.static_out = None
+        self._table_ref = None
+        for bn, p0 in zip(bns, pend0):
+            bn._pending = p0
+        self.model.global_step = completed
+        if not torch.cuda.is_current_stream_capturing():
+            self._macc.zero_()
+            self._mcount.zero_()
+            if self.feed is not None and self.feed.cursor is not None:
+                self.feed.cursor.fill_(completed * self.accum)
+
+    def _accum_step(self, x):
+        m, model, feed = self.accum, self.model, self.feed
+        # (cut before anything is counted: rows that do not divide by M raise here)
+        parts = None if feed is not None else [x[lo:hi] for lo, hi in micro_slices(x.shape[0], m)]
+        if self.beta_anneal:
+            global_step_counter(model)
+        completed = model.global_step
+        bns = model.bn_modules()
+        pend0 = [bn._pending for bn in bns]
+        model.global_step += 1
+        try:
+            if not self.use_graph or self.eager_left > 0:
+                self.eager_left -= 1
+                self._prologue()
+                for j in range(m):
+                    if feed is not None:
+                        feed.before_step(completed * m + j)   # an epoch may end inside a step
+                    self._fwd_bwd(None if parts is None else parts[j], micro=True)
+                if self.allreduce is not None:
+                    self.allreduce.run()
+                self._epilogue()
+                return self._mean_out
+            just_captured = self.graph_a is None
+            if just_captured:
+                self._capture_accum(None if parts is None else parts[0])   # the Python micro-pass ran once: one BN forward is counted
+            self.graph_p.replay()
+            for j in range(m):
+                if feed is not None:
+                    feed.before_step(completed * m + j)
+                else:
+                    self.static_x.copy_(parts[j], non_blocking=True)
+                self.graph_a.replay()
+            if self.allreduce is not None:
+                self.allreduce.run()
+            self.graph_b.replay()
+            K.prepared.weights_written()
+            if model.training:
+                for bn in self._bns:
+                    bn._pending += m - (1 if just_captured else 0)
+            return self._mean_out
+        except BaseException:
+            self._abandon(completed, bns, pend0)
+            raise
 
     def _capture(self, x):
         if self.feed is None:
@@ -281,6 +411,8 @@ class TrainStep:
     def __call__(self, x=None):
         if (x is None) == (self.feed is None):
             raise ValueError("a step takes its batch either as x or from feed=, not both and not neither")
+        if self.accum > 1:
+            return self._accum_step(x)
         if self.beta_anneal:
             global_step_counter(self.model)   # (created before this step is counted: it holds the number of COMPLETED steps)
         if self.feed is not None:
@@ -324,6 +456,8 @@ class AutoExchangeStep:
         from . import dist as ldist
         self.model = model
         env = os.environ.get('LVAE_DDP_MODE')
+        if forms is None and env != 'overlap' and int(step_kwargs.get('accum_steps', 1)) > 1:
+            forms = ['split']   # accumulated steps exchange once, after the last micro-pass: there is no second form to try
         forms = list(forms) if forms is not None else ([env] if env in ('split', 'overlap') else ['split', 'overlap'])
         self.ars, self.steps = {}, {}
         comm = None
@@ -387,7 +521,7 @@ class AutoExchangeStep:
             self.timings_ms = self.selector.timings_ms
             for f in list(self.steps):
                 if f != self.chosen:   # the loser's graphs (and their memory pools) go
-                    self.steps[f].graph_a = self.steps[f].graph_b = None
+                    self.steps[f].graph_a = self.steps[f].graph_b = self.steps[f].graph_p = None
                     self.steps[f].static_out = None
             self._arm(self.chosen)
             print('[lvae] gradient exchange: %s' % self.exchange_description(), file=sys.stderr, flush=True)

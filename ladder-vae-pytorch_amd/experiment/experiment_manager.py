@@ -116,6 +116,10 @@ def build_parser():
                    help='train on the K-sample importance-weighted bound instead of the ELBO: K samples per image share one bottom-up pass '
                         '(--batch-size stays images per step); the train line adds the bound and the effective sample size of the weights. '
                         'Not with --freebits or --analytical-kl. 1: the ELBO')
+    p.add_argument('--accum-steps', type=int, default=1, dest='accum_steps', metavar='M',
+                   help='every optimizer step consumes M micro-batches of --batch-size images: the gradient applied is the mean over all '
+                        'M * batch-size images, BatchNorm normalises over one micro-batch, and steps (--log-every, the lr schedule, beta '
+                        'warm-up, test and checkpoint cadence) count optimizer steps. 1: one batch per step')
     p.add_argument('--max-grad-norm', type=float, default=None, dest='max_grad_norm', metavar='G',
                    help='clip the gradient to the global L2 norm G before the optimizer step (the factor of torch.nn.utils.clip_grad_norm_), '
                         'decided on the device inside the captured step; steps with a non-finite gradient are then skipped. Off by default')
@@ -174,6 +178,8 @@ class LVAEExperiment:
         if iw > 1 and args.analytical_kl:
             raise SystemExit("--iw-train-samples %d cannot be combined with --analytical-kl: the importance weights need the Monte-Carlo "
                              "log q - log p of the drawn sample" % iw)
+        if getattr(args, 'accum_steps', 1) < 1:
+            raise SystemExit("--accum-steps must be at least 1, got %d" % args.accum_steps)
         g, t = getattr(args, 'max_grad_norm', None), getattr(args, 'grad_skip_threshold', None)
         if g is not None and not (g > 0.0 and g != float('inf')):
             raise SystemExit("--max-grad-norm must be a positive finite number, got %g" % g)
@@ -209,6 +215,8 @@ class LVAEExperiment:
             s += ',b{}'.format(args.beta_anneal)
         if getattr(args, 'iw_train_samples', 1) > 1:
             s += ',iw{}'.format(args.iw_train_samples)
+        if getattr(args, 'accum_steps', 1) > 1:
+            s += ',acc{}'.format(args.accum_steps)
         s += ',{}'.format(args.nonlin)
         if args.free_bits > 0:
             s += ',freeb={}'.format(args.free_bits)
@@ -243,6 +251,7 @@ class LVAEExperiment:
         model.noise = PhiloxNoise(seed=a.seed)
         model.compute_dtype = a.compute_dtype
         model.iw_train_samples = getattr(a, 'iw_train_samples', 1)   # (noted in checkpoints: checkpoint.save_checkpoint)
+        model.accum_steps = getattr(a, 'accum_steps', 1)             # (likewise)
         return model
 
     @staticmethod

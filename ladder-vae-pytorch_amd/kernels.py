@@ -1700,6 +1700,26 @@ def summary_take(acc, out):
     return out
 
 
+MICRO_FIXED = 7   # slots of lvae_micro_fold_f64's accumulator before the per-layer KLs: loss, elbo, recons, kl, l2, iw, ess
+
+
+def micro_fold(loss, elbo, recons, kl, l2, kl_layers, m, acc, count, out, iw=None, ess=None):
+    """One micro-pass of a step accumulated over `m`: acc float64 (7 + L) += the pass's fp32 scalars (device tensors of one element;
+    kl_layers (L,); iw / ess or None), count int64 (1,) += 1. The m-th call writes the means (float)(acc / m) into out float32 (7 + L) and
+    clears acc and count; out is untouched before it. One launch of one wave; captured micro-passes replay it."""
+    L = acc.numel() - MICRO_FIXED
+    n_kl = 0 if kl_layers is None else kl_layers.numel()
+    if acc.dim() != 1 or n_kl != L or (n_kl and not kl_layers.is_contiguous()):
+        raise _C.LvaeHipError("micro_fold: the accumulator has %d slots, which is not 7 + %d contiguous per-layer KLs" % (acc.numel(), n_kl))
+    if out.numel() != acc.numel() or not out.is_contiguous() or not acc.is_contiguous() or count.numel() != 1:
+        raise _C.LvaeHipError("micro_fold: %d means into an output of %d, or a counter of %d elements" % (acc.numel(), out.numel(), count.numel()))
+    f32 = (torch.float32,)
+    call('lvae_micro_fold_f64', ptr(loss, f32), ptr(elbo, f32), ptr(recons, f32), ptr(kl, f32), ptr(l2, f32), ptr(iw, f32), ptr(ess, f32),
+         ptr(kl_layers, f32) if n_kl else None, L, int(m), ptr(acc, (torch.float64,)), ptr(count, (torch.int64,)), ptr(out, f32),
+         stream_ptr())
+    return out
+
+
 def _img_src(t, name):
     """(tensor, nhwc flag, (n, C, H, W)) of an image set given in the NCHW convention: NCHW contiguous, or the NCHW view of an NHWC
     contiguous buffer (what the model returns). No copy, no layout change."""

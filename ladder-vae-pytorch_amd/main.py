@@ -133,6 +133,9 @@ def main(argv=None):
         was_iw = ck.get('iw_train_samples', 1) if isinstance(ck, dict) and 'model' in ck else 1
         if rank == 0 and was_iw != args.iw_train_samples:
             print('warning: %s was written with --iw-train-samples %d; continuing with %d' % (args.resume, was_iw, args.iw_train_samples))
+        from .checkpoint import accum_steps_record
+        if rank == 0 and accum_steps_record(ck) != args.accum_steps:
+            print('warning: %s was written with --accum-steps %d; continuing with %d' % (args.resume, accum_steps_record(ck), args.accum_steps))
         del ck
     model.noise.seed ^= rank * 0x9E3779B9
     model.train()
@@ -159,10 +162,13 @@ def main(argv=None):
         if rank == 0:
             print('data-dependent init: %d convolutions rescaled' % n)
     ldist.broadcast_flat(arena.params)
-    allreduce = ldist.GradAllReduce(arena.grads, segments=arena.segments) if world > 1 else None
+    accum = args.accum_steps
+    # (an accumulated step exchanges once, after its last micro-pass: the split form, unless LVAE_DDP_MODE insists, which TrainStep refuses)
+    ar_mode = 'split' if accum > 1 and os.environ.get('LVAE_DDP_MODE') is None else None
+    allreduce = ldist.GradAllReduce(arena.grads, segments=arena.segments, mode=ar_mode) if world > 1 else None
     # --beta-anneal: beta is read on the device from a step counter the step advances itself, so the captured graph replays with it
     step_fn = TrainStep(model, opt, beta=1.0, use_graph=not args.no_graph, allreduce=allreduce, beta_anneal=args.beta_anneal,
-                        feed=feed, summary=summary, iw_samples=args.iw_train_samples)
+                        feed=feed, summary=summary, iw_samples=args.iw_train_samples, accum_steps=accum)
     history = History(args.history) if args.history and rank == 0 else None
     guard_seen = opt.guard.counts() if opt.guard is not None else None   # (after --resume: the file's counts)
     # --latent-stats: the first sample of every test batch also folds each layer's posterior into a device accumulator
@@ -181,37 +187,47 @@ def main(argv=None):
         print('device data: %d images, %.1f MB as %s in device memory, %d steps per epoch' % (feed.N, feed.nbytes / 1e6, feed.kind,
                                                                                           feed.steps_per_epoch))
     if not (loader is not None or data is not None):
-        for _ in range(first - 1):                     # the synthetic batches the resumed steps already consumed
+        for _ in range((first - 1) * accum):           # the synthetic batches the resumed steps already consumed
             synthetic_batch(exp, per_rank, gen)
     batches = None
     epoch = 0
     t0, seen = time.time(), 0
     for step in range(first, steps + 1):
         if feed is not None:
-            epoch = feed.epoch_of(step)
+            epoch = feed.step_epoch(step, accum)       # of the step's first micro-batch
             if epoch >= args.max_epochs:
                 break
         elif loader is not None:
-            if batches is None:
-                batches = iter(loader.train)
-            try:
-                xb = next(batches)[0]
-            except StopIteration:                      # next epoch: reshuffled by the DataLoader
-                epoch += 1
-                if epoch >= args.max_epochs:
-                    break
-                batches = iter(loader.train)
-                xb = next(batches)[0]
             lo, hi = ldist.shard_batch(args.batch_size, rank, world)
-            x = xb[lo:hi]
+            xs = []
+            for _ in range(accum):                     # one optimizer step: `accum` batches of --batch-size
+                if batches is None:
+                    batches = iter(loader.train)
+                try:
+                    xb = next(batches)[0]
+                except StopIteration:                  # next epoch: reshuffled by the DataLoader
+                    epoch += 1
+                    if epoch >= args.max_epochs:
+                        break
+                    batches = iter(loader.train)
+                    xb = next(batches)[0]
+                xs.append(xb[lo:hi])
+            if len(xs) < accum:
+                break
+            x = xs[0] if accum == 1 else torch.cat(xs)
         elif data is not None:
-            idx = torch.randint(0, data.shape[0], (args.batch_size,), generator=torch.Generator().manual_seed(args.seed + step))
             lo, hi = ldist.shard_batch(args.batch_size, rank, world)
-            x = data[idx[lo:hi]]
+            if accum == 1:
+                idx = torch.randint(0, data.shape[0], (args.batch_size,), generator=torch.Generator().manual_seed(args.seed + step))
+                x = data[idx[lo:hi]]
+            else:                                      # micro-batch j of step s is the batch a plain run draws at its step (s - 1) * M + j
+                x = torch.cat([data[torch.randint(0, data.shape[0], (args.batch_size,),
+                                                  generator=torch.Generator().manual_seed(args.seed + (step - 1) * accum + j + 1))[lo:hi]]
+                               for j in range(accum)])
         else:
-            x = synthetic_batch(exp, per_rank, gen)
+            x = synthetic_batch(exp, per_rank, gen) if accum == 1 else torch.cat([synthetic_batch(exp, per_rank, gen) for _ in range(accum)])
         out = step_fn() if feed is not None else step_fn(x.to(exp.device, non_blocking=True))
-        seen += args.batch_size
+        seen += args.batch_size * accum
         if summary is not None and (step % args.log_every == 0 or step == steps):
             m = summary.take()                         # a collective: every rank takes its window, rank 0 prints the mean over all
             if rank == 0:
@@ -242,7 +258,7 @@ def main(argv=None):
         n_samples, ckpt = sched.at(step)
         if n_samples:
             if data is not None and loader is None and feed is None:
-                epoch = step * args.batch_size // data.shape[0]
+                epoch = step * args.batch_size * accum // data.shape[0]
             res = test_pass(model, tests(), n_samples, optimizer=opt, latent_stats=latent)   # (--ema-decay: on the averaged weights)
             if rank == 0:
                 line = exp.test_log_str(res, step, epoch)
