@@ -391,6 +391,12 @@ typedef struct lvae_rb_ext {
   float* ap_dgamma;
   float* ap_dbeta;
   float* ap_out;
+  /* Workgroups per tile of an LVAE_RB_EPI_PLAIN launch: 0 = the library decides (two, each computing one 32-channel half of the tile's
+   * output, where 32-pixel tiles in the six-product form leave at least half the CUs without a workgroup: the 4x4 and 2x2 levels at batch
+   * 256), 1 = one, 2 = two wherever that kernel exists (32-pixel tiles, plain epilogue, LVAE_PREC_F32). Speed only: y, the statistics
+   * rows and everything the prologue stores are bit for bit the same, and lvae_resblock_conv_rows(d) does not change.
+   * lvae_resblock_conv_nsplit(d, ext) answers what a launch would use (0: shape not supported). */
+  int32_t nsplit;
 } lvae_rb_ext;
 /* Pre-split copy of a gate weight for lvae_resblock_conv_f32: `g` describes the 1x1 convolution in the direction it is used (forward:
  * C1 = 64, Cout = 128, w_sk / w_sn = strides of the input / gate channel; backward: C1 = 128, Cout = 64, strides swapped); only C1, Cout, w,
@@ -398,6 +404,7 @@ typedef struct lvae_rb_ext {
 size_t lvae_resblock_gate_workspace(const lvae_conv_desc* g);
 int lvae_resblock_gate_prepare_entry(const lvae_conv_desc* g, void* entry);
 int32_t lvae_resblock_conv_rows(const lvae_conv_desc* d);
+int32_t lvae_resblock_conv_nsplit(const lvae_conv_desc* d, const lvae_rb_ext* ext);
 /* Rows of out_stats (= workgroups) of an LVAE_RB_EPI_GATE launch. Besides the whole-image shapes (= lvae_resblock_conv_rows) the forward
  * conv + gate fusion exists for the shapes of the 256-pixel six-product Winograd kernel (fp32, 64 -> 64 channels: the 16x16 and 32x32 levels at
  * batch 256; lvae_conv2d_variant(d) == LVAE_VARIANT_WINO_SIX with at least 256 workgroups): attach THAT kernel's workspace

@@ -66,7 +66,7 @@ class RbExt(C.Structure):
                 ('pf_ptr', C.c_void_p * 2), ('pf_bytes', C.c_int64 * 2),
                 ('ap_parts', C.c_void_p), ('ap_rows', C.c_int32), ('ap_act', C.c_int32), ('ap_M', C.c_int64), ('ap_coef', C.c_void_p),
                 ('ap_dh', C.c_void_p), ('ap_x', C.c_void_p), ('ap_add', C.c_void_p), ('ap_dgamma', C.c_void_p), ('ap_dbeta', C.c_void_p),
-                ('ap_out', C.c_void_p)]
+                ('ap_out', C.c_void_p), ('nsplit', C.c_int32)]
 
 
 class StochBlock(C.Structure):
@@ -144,6 +144,7 @@ SIGNATURES = {
     'lvae_resblock_gate_workspace': (_Z, [C.POINTER(ConvDesc)]),
     'lvae_resblock_gate_prepare_entry': (C.c_int, [C.POINTER(ConvDesc), _P]),
     'lvae_resblock_conv_rows': (_I, [C.POINTER(ConvDesc)]),
+    'lvae_resblock_conv_nsplit': (_I, [C.POINTER(ConvDesc), C.POINTER(RbExt)]),
     'lvae_resblock_conv_gate_rows': (_I, [C.POINTER(ConvDesc)]),
     'lvae_resblock_conv_workspace': (_Z, [C.POINTER(ConvDesc)]),
     'lvae_resblock_conv_prepare_entry': (C.c_int, [C.POINTER(ConvDesc), _P]),

@@ -133,9 +133,18 @@ __device__ __forceinline__ void rb_parts_finish(const float* __restrict__ parts,
 // of the block that ran just before (that block's input IS this block's output), deferred into this prologue: dout = BN'(ap_dh; ap_x) +
 // ap_add from the partial sums ap_parts, formed on the fly and stored to ap_out (this block's own final apply reads it as its `add`).
 // One launch (7-8.6 us of a dependent chain) per residual block less.
-template <int SPLIT, int MI, int PRO, int EPI, bool ELU, bool AP = false>
+// NS (1 | 2): workgroups per tile. With NS == 2 (32-pixel tiles, plain epilogue: the 4x4 and 2x2 levels, whose tiles fill at most half the
+// CUs) workgroup 2 * tile + half computes ONE 32-channel half of the tile's output: half the B fragments, half the reduction loop's MFMAs,
+// half the partial tiles. The prologue runs in both (either half needs all 64 input channels; the second runs on a CU that was idle), but
+// everything it writes ONCE per tile (xt_out, dab, ap_out) is written by half 0 and everything written once per launch (coefficients,
+// running statistics, dgamma / dbeta) by (tile 0, half 0). The k-split over the waves, os_sum's order and the thread -> (row, channel) map
+// of the store pass are those of NS == 1 (the threads of the other half's channels sit the pass out), so y and the statistics rows are
+// bit for bit what one workgroup writes.
+template <int SPLIT, int MI, int PRO, int EPI, bool ELU, bool AP = false, int NS = 1>
 __global__ __launch_bounds__(256) void rb_conv_kernel(RbArgs a) {
   static_assert(MI == 1 || MI == 2, "32- or 64-pixel tiles (MI 32-row blocks)");
+  static_assert(NS == 1 || (NS == 2 && MI == 1 && EPI == LVAE_RB_EPI_PLAIN), "two workgroups per tile: 32-pixel tiles with the plain epilogue");
+  constexpr int NH = 2 / NS;   // 32-channel output halves per workgroup
   static_assert(!AP || PRO == LVAE_RB_PRO_GATE_BWD, "the deferred apply feeds the gate-backward prologue");
   constexpr int BM = 32 * MI, LDK = RB_LDK, LDO = RB_LDO, NQ = BM / 16;
   constexpr int OS_BYTES = BM * LDO * 4;
@@ -156,8 +165,11 @@ __global__ __launch_bounds__(256) void rb_conv_kernel(RbArgs a) {
   // dgrad GEMM (N = 64) runs on waves 0 / 1 and the gate forward's (N = 128) gives each wave ONE 32-column tile
   const int wm = MI == 2 ? wave >> 1 : 0, wn = wave & 1, li = lane & 31, lh = lane >> 5;
   const bool g1_on = MI == 2 || wave < 2;
-  const int bid = blockIdx.x;
-  const int n0 = bid * a.NI, HW = a.HW;
+  const int bid = blockIdx.x;                                 // place in the grid (NS workgroups per tile)
+  const int tile = NS == 2 ? bid >> 1 : bid, half = NS == 2 ? bid & 1 : 0;
+  const bool once = half == 0;                                // writes what a tile's prologue stores
+  const bool mine = NS == 1 || ((t & 15) >> 3) == half;      // this thread's channels c4 .. c4 + 3 are in the workgroup's output half
+  const int n0 = tile * a.NI, HW = a.HW;
   const int nvalid = min(BM, (d.N - n0) * HW);  // pixel rows of this tile that exist
   const size_t row0 = (size_t)n0 * HW;          // global pixel row of tile row 0 (whole images: tile rows are consecutive pixels)
   const int c4 = (t & 15) * 4, p0 = t >> 4;     // staging / store map: thread -> rows p0 + 16 q, channels c4 .. c4 + 3
@@ -166,15 +178,14 @@ __global__ __launch_bounds__(256) void rb_conv_kernel(RbArgs a) {
 
   // ---- 3x3 weights: this wave's B fragments of tap `tap` (k block = wave): both 32-channel halves, one 16-byte load per plane and half
   constexpr int RING = SPLIT == 1 ? 9 : 3;   // bf16 operands: the whole slice (72 registers); six-product form: three taps ahead
-  bf16x8 bq[RING][2][SPLIT];
-  const __bf16* wp_lane = a.Wp + (size_t)wave * SPLIT * 1024 + (size_t)lane * 8;
-  auto load_b = [&](int tap, bf16x8 (&r)[2][SPLIT]) {
+  bf16x8 bq[RING][NH][SPLIT];
+  const __bf16* wp_lane = a.Wp + (size_t)wave * SPLIT * 1024 + (size_t)lane * 8 + (NS == 2 ? half * 512 : 0);
+  auto load_b = [&](int tap, bf16x8 (&r)[NH][SPLIT]) {
     const __bf16* src = wp_lane + (size_t)tap * 4 * SPLIT * 1024;
 #pragma unroll
-    for (int p = 0; p < SPLIT; ++p) {
-      r[0][p] = *reinterpret_cast<const bf16x8*>(src + p * 1024);
-      r[1][p] = *reinterpret_cast<const bf16x8*>(src + p * 1024 + 512);
-    }
+    for (int p = 0; p < SPLIT; ++p)
+#pragma unroll
+      for (int nh = 0; nh < NH; ++nh) r[nh][p] = *reinterpret_cast<const bf16x8*>(src + p * 1024 + nh * 512);
   };
   RB_STAMP_DECL;
 #ifdef LVAE_RB_DBG_REPS
@@ -201,7 +212,7 @@ __global__ __launch_bounds__(256) void rb_conv_kernel(RbArgs a) {
   auto pf_issue = [&]() {
 #pragma unroll
     for (int k = 0; k < 2; ++k) {
-      const int per_xcd = (a.nwg + 7) >> 3, part = bid >> 3;
+      const int per_xcd = (a.nwg * NS + 7) >> 3, part = bid >> 3;
       const int lines = e.pf_ptr[k] != nullptr ? (int)((e.pf_bytes[k] + 127) >> 7) : 0, per = (lines + per_xcd - 1) / per_xcd;
       const int lo = part * per, hi = min(lo + per, lines);
       const char* base = static_cast<const char*>(e.pf_ptr[k]) + (size_t)(lo + t) * 128;   // ranges are far below 2 GB: 32-bit line arithmetic
@@ -268,7 +279,7 @@ __global__ __launch_bounds__(256) void rb_conv_kernel(RbArgs a) {
     const bool lead = t < 64 && f.parts != nullptr;
     const float pivot = lead ? f.parts[((size_t)f.rows * 2) * 64 + t] : 0.f;  // the producer's pivot, stored behind its partial rows
     const float gam = lead && f.gamma ? f.gamma[t] : 1.f, bet = lead && f.beta ? f.beta[t] : 0.f;
-    const bool upd = lead && bid == 0 && f.running_mean != nullptr;
+    const bool upd = lead && bid == 0 && f.running_mean != nullptr;   // (bid 0 = tile 0, half 0)
     const float rm0 = upd ? f.running_mean[t] : 0.f, rv0 = upd ? f.running_var[t] : 0.f;
     f32x4 xv[NQ];
 #pragma unroll
@@ -342,7 +353,7 @@ __global__ __launch_bounds__(256) void rb_conv_kernel(RbArgs a) {
       const f32x4 g = gv[q] * act_grad4(xv[q] * sc + sh, bwd_act);
       f32x4 v = bn_bwd_apply(g, xv[q], c1, c2, mu, rs, sc) * dm[q];
       if (!ok[q]) v = zero4;
-      if (ok[q] && e.xt_out) store_wt4(e.xt_out + grow[q] * 64 + c4, v);
+      if (ok[q] && once && e.xt_out) store_wt4(e.xt_out + grow[q] * 64 + c4, v);
       put_interior(q, v);
     }
   }
@@ -388,7 +399,7 @@ __global__ __launch_bounds__(256) void rb_conv_kernel(RbArgs a) {
         const f32x4 g = go[q] * act_grad4(xa[q] * sc + sh, ap_act);
         const f32x4 v = bn_bwd_apply(g, xa[q], c1, c2, mu, rs, sc) + ad[q];
         go[q] = v;
-        if (ok[q]) store_wt4(e.ap_out + grow[q] * 64 + c4, v);
+        if (ok[q] && once) store_wt4(e.ap_out + grow[q] * 64 + c4, v);
       }
     } else {
       pf_issue();
@@ -424,7 +435,7 @@ __global__ __launch_bounds__(256) void rb_conv_kernel(RbArgs a) {
       da = da * act_grad4(aa[q], gate_act);
       db = db * act_fwd4(aa[q], gate_act);
       if (!ok[q]) da = db = zero4;
-      if (ok[q] && e.dab) {
+      if (ok[q] && once && e.dab) {
         store_wt4(e.dab + grow[q] * 128 + c4, da);
         store_wt4(e.dab + grow[q] * 128 + 64 + c4, db);
       }
@@ -464,7 +475,7 @@ __global__ __launch_bounds__(256) void rb_conv_kernel(RbArgs a) {
       const int p = p0 + 16 * q;
       f32x4 v = *reinterpret_cast<const f32x4*>(Os1 + p * LDO + c4) * dm[q];
       if (!ok[q]) v = zero4;
-      if (ok[q] && e.xt_out) store_wt4(e.xt_out + grow[q] * 64 + c4, v);
+      if (ok[q] && once && e.xt_out) store_wt4(e.xt_out + grow[q] * 64 + c4, v);
       put_interior(q, v);
     }
     zero_ring();
@@ -518,11 +529,11 @@ __global__ __launch_bounds__(256) void rb_conv_kernel(RbArgs a) {
     const int ty = fastdiv(r, a.m_w), tx = r - ty * d.W;
     hbase[mb] = ((img * a.halo_h + ty) * a.halo_w + tx) * LDK + wave * 16 + 8 * lh;
   }
-  f32x16 acc[MI][2];   // [row block][channel half]
+  f32x16 acc[MI][NH];   // [row block][channel half]
 #pragma unroll
   for (int mb = 0; mb < MI; ++mb)
 #pragma unroll
-    for (int nh = 0; nh < 2; ++nh)
+    for (int nh = 0; nh < NH; ++nh)
 #pragma unroll
       for (int r = 0; r < 16; ++r) acc[mb][nh][r] = 0.f;
 
@@ -552,7 +563,7 @@ __global__ __launch_bounds__(256) void rb_conv_kernel(RbArgs a) {
 #pragma unroll
       for (int mb = 0; mb < MI; ++mb)
 #pragma unroll
-        for (int nh = 0; nh < 2; ++nh) acc[mb][nh] = mfma_pieces<SPLIT>(af[cur][mb], bq[tap % RING][nh], acc[mb][nh]);
+        for (int nh = 0; nh < NH; ++nh) acc[mb][nh] = mfma_pieces<SPLIT>(af[cur][mb], bq[tap % RING][nh], acc[mb][nh]);
       if (tap + RING < 9) load_b(tap + RING, bq[tap % RING]);
     }
   }
@@ -583,10 +594,10 @@ __global__ __launch_bounds__(256) void rb_conv_kernel(RbArgs a) {
 #pragma unroll
   for (int mb = 0; mb < MI; ++mb)
 #pragma unroll
-    for (int nh = 0; nh < 2; ++nh)
+    for (int nh = 0; nh < NH; ++nh)
 #pragma unroll
       for (int r = 0; r < 16; ++r)
-        Os[wave * OSW + (mb * 32 + (r & 3) + 8 * (r >> 2) + 4 * lh) * LDO + nh * 32 + li] = acc[mb][nh][r];
+        Os[wave * OSW + (mb * 32 + (r & 3) + 8 * (r >> 2) + 4 * lh) * LDO + (NS == 2 ? half : nh) * 32 + li] = acc[mb][nh][r];
   lds_barrier();
   RB_STAMP(5);
   auto os_sum = [&](int p) {
@@ -607,8 +618,8 @@ __global__ __launch_bounds__(256) void rb_conv_kernel(RbArgs a) {
 #pragma unroll
     for (int q = 0; q < NQ; ++q) {
       const int p = p0 + 16 * q;
-      const f32x4 v = (os_sum(p) + ep_bias) * ep_mask[q];
-      if (ok[q]) {
+      const f32x4 v = (os_sum(p) + ep_bias) * ep_mask[q];   // (NS == 2: the other half's columns of Os hold stale bytes; `mine` keeps them out)
+      if (ok[q] && mine) {
         store_wt4(d.y + grow[q] * 64 + c4, v);
         if (stats_out) {
           if (stats_fwd) {
@@ -699,8 +710,10 @@ __global__ __launch_bounds__(256) void rb_conv_kernel(RbArgs a) {
       float v = 0.f;
 #pragma unroll
       for (int r = 0; r < 16; ++r) v += red[which * 1024 + r * 64 + c];
-      stats_out[((size_t)bid * 2 + which) * 64 + c] = v;
-      if (bid == 0 && which == 0 && stats_fwd) stats_out[((size_t)a.nwg * 2) * 64 + c] = stats_pivot[c];
+      if (NS == 1 || (c >> 5) == half) {   // this workgroup's channels of the tile's row; tile 0 adds the pivot, each half its own channels
+        stats_out[((size_t)tile * 2 + which) * 64 + c] = v;
+        if (tile == 0 && which == 0 && stats_fwd) stats_out[((size_t)a.nwg * 2) * 64 + c] = stats_pivot[c];
+      }
     }
   }
   RB_STAMP(7);
@@ -732,6 +745,17 @@ static int rb_mi(const lvae_conv_desc* d) {
   const int HW = d->H * d->W;
   if (HW <= 16 && 32 % HW == 0 && ((int64_t)d->N * HW + 63) / 64 <= 128) return 1;
   return 2;
+}
+
+// Workgroups per tile: 2 — each computes one 32-channel half of the tile's output (rb_conv_kernel, NS) — where the plain epilogue runs on
+// 32-pixel tiles in the six-product form and the doubled grid still fits the CUs rb_mi() counted (2 * tiles <= 256: the 4x4 and 2x2 levels
+// at batch 256, 128 -> 256 and 32 -> 64 workgroups). The reduction loop is MFMA-bound at one wave per SIMD, so only more CUs shorten it.
+// Not for the gate epilogue (its 1x1 GEMM needs all 64 channels of y2 in one workgroup) nor for bf16 operands (a third of the MFMAs per
+// tap: not measured). `force` = lvae_rb_ext.nsplit: 1 keeps one workgroup per tile, 2 splits wherever the kernel exists (MI 1, plain
+// epilogue, six-product form), whatever the grid.
+static int rb_nsplit(const RbArgs& a, int split, int mi, int epi, int force) {
+  if (mi != 1 || epi != LVAE_RB_EPI_PLAIN || split != 3 || force == 1) return 1;
+  return force == 2 || 2 * (int64_t)a.nwg <= 256 ? 2 : 1;
 }
 
 static size_t rb_lds_bytes(int split, int mi, int halo_px, int pro, int epi) {
@@ -779,9 +803,9 @@ static bool rb_plan(const lvae_conv_desc* d, RbArgs& a, int& mi) {
   return rb_lds_bytes(rb_split(d), mi, a.halo_px, LVAE_RB_PRO_GATE_BWD, LVAE_RB_EPI_GATE) <= 160 * 1024;
 }
 
-template <int SPLIT, int MI, int PRO, int EPI, bool ELU, bool AP = false>
+template <int SPLIT, int MI, int PRO, int EPI, bool ELU, bool AP = false, int NS = 1>
 static int rb_launch(const RbArgs& a, hipStream_t s) {
-  return launch_lds<rb_conv_kernel<SPLIT, MI, PRO, EPI, ELU, AP>>("resblock_conv", dim3(a.nwg), dim3(256), rb_lds_bytes(SPLIT, MI, a.halo_px, PRO, EPI), 160 * 1024, s, a);
+  return launch_lds<rb_conv_kernel<SPLIT, MI, PRO, EPI, ELU, AP, NS>>("resblock_conv", dim3(a.nwg * NS), dim3(256), rb_lds_bytes(SPLIT, MI, a.halo_px, PRO, EPI), 160 * 1024, s, a);
 }
 
 // every activation id this launch will look at is ELU (ids of features the launch does not use are ignored)
@@ -798,8 +822,16 @@ static bool rb_all_elu(const RbArgs& a) {
 }
 
 template <int SPLIT, int MI, bool ELU>
-static int rb_dispatch2(const RbArgs& a, hipStream_t s) {
+static int rb_dispatch2(const RbArgs& a, int nsplit, hipStream_t s) {
   const int pro = a.e.prologue, epi = a.e.epilogue;
+  if constexpr (SPLIT == 3 && MI == 1) {
+    if (nsplit == 2) {   // rb_nsplit(): plain epilogue
+      if (pro == LVAE_RB_PRO_AFFINE) return rb_launch<SPLIT, MI, LVAE_RB_PRO_AFFINE, LVAE_RB_EPI_PLAIN, ELU, false, 2>(a, s);
+      if (pro == LVAE_RB_PRO_BN_APPLY) return rb_launch<SPLIT, MI, LVAE_RB_PRO_BN_APPLY, LVAE_RB_EPI_PLAIN, ELU, false, 2>(a, s);
+      if (a.e.ap_parts != nullptr) return rb_launch<SPLIT, MI, LVAE_RB_PRO_GATE_BWD, LVAE_RB_EPI_PLAIN, ELU, true, 2>(a, s);
+      return rb_launch<SPLIT, MI, LVAE_RB_PRO_GATE_BWD, LVAE_RB_EPI_PLAIN, ELU, false, 2>(a, s);
+    }
+  }
   if (pro == LVAE_RB_PRO_AFFINE) return epi == LVAE_RB_EPI_GATE ? rb_launch<SPLIT, MI, LVAE_RB_PRO_AFFINE, LVAE_RB_EPI_GATE, ELU>(a, s)
                                                                   : rb_launch<SPLIT, MI, LVAE_RB_PRO_AFFINE, LVAE_RB_EPI_PLAIN, ELU>(a, s);
   if (pro == LVAE_RB_PRO_BN_APPLY) return rb_launch<SPLIT, MI, LVAE_RB_PRO_BN_APPLY, LVAE_RB_EPI_PLAIN, ELU>(a, s);
@@ -808,8 +840,8 @@ static int rb_dispatch2(const RbArgs& a, hipStream_t s) {
 }
 
 template <int SPLIT, int MI>
-static int rb_dispatch(const RbArgs& a, hipStream_t s) {
-  return rb_all_elu(a) ? rb_dispatch2<SPLIT, MI, true>(a, s) : rb_dispatch2<SPLIT, MI, false>(a, s);
+static int rb_dispatch(const RbArgs& a, int nsplit, hipStream_t s) {
+  return rb_all_elu(a) ? rb_dispatch2<SPLIT, MI, true>(a, nsplit, s) : rb_dispatch2<SPLIT, MI, false>(a, nsplit, s);
 }
 
 }  // namespace lvae
@@ -839,6 +871,13 @@ extern "C" int32_t lvae_resblock_conv_rows(const lvae_conv_desc* d) {
   RbArgs a;
   int mi;
   return rb_plan(d, a, mi) ? a.nwg : 0;
+}
+
+extern "C" int32_t lvae_resblock_conv_nsplit(const lvae_conv_desc* d, const lvae_rb_ext* ext) {
+  RbArgs a;
+  int mi;
+  if (!rb_plan(d, a, mi)) return 0;
+  return rb_nsplit(a, rb_split(d), mi, ext != nullptr ? ext->epilogue : LVAE_RB_EPI_PLAIN, ext != nullptr ? ext->nsplit : 0);
 }
 
 extern "C" size_t lvae_resblock_conv_workspace(const lvae_conv_desc* d) {
@@ -952,8 +991,10 @@ extern "C" int lvae_resblock_conv_f32(const lvae_conv_desc* d, const lvae_rb_ext
   }
   a.Wp = static_cast<const __bf16*>(d->workspace);
   hipStream_t s = (hipStream_t)stream;
-  if (mi == 1) return split == 1 ? rb_dispatch<1, 1>(a, s) : rb_dispatch<3, 1>(a, s);
-  return split == 1 ? rb_dispatch<1, 2>(a, s) : rb_dispatch<3, 2>(a, s);
+  LVAE_REQUIRE(e.nsplit >= 0 && e.nsplit <= 2, LVAE_EINVAL, "lvae_resblock_conv_f32: nsplit must be 0 (the plan decides), 1 or 2");
+  const int nsplit = rb_nsplit(a, split, mi, epi, e.nsplit);
+  if (mi == 1) return split == 1 ? rb_dispatch<1, 1>(a, nsplit, s) : rb_dispatch<3, 1>(a, nsplit, s);
+  return split == 1 ? rb_dispatch<1, 2>(a, nsplit, s) : rb_dispatch<3, 2>(a, nsplit, s);
 }
 
 #ifdef LVAE_RB_DBG

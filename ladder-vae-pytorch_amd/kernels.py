@@ -548,9 +548,10 @@ def _rb_prefetch(e, prefetch):
         e.pf_ptr[i], e.pf_bytes[i] = rng[0], rng[1]
 
 
-def rb_conv(x, weight, g, bias, in_act, out_scale, in_bn=None, coef=None, stats_pivot=None, prefetch=None):
+def rb_conv(x, weight, g, bias, in_act, out_scale, in_bn=None, coef=None, stats_pivot=None, prefetch=None, nsplit=0):
     """y = (conv3x3(act(BN(x))) + bias) * out_scale with BatchNorm partials of y around stats_pivot (first half of a residual block).
-    in_bn = (StatParts, pivot, bn) or coef = (scale, shift, ...) given. Returns (y, StatParts | None, coef)."""
+    in_bn = (StatParts, pivot, bn) or coef = (scale, shift, ...) given. Returns (y, StatParts | None, coef).
+    nsplit (here and in rb_gate_dgrad / rb_apply_dgrad): workgroups per tile, lvae_rb_ext.nsplit (0: the library decides; speed only)."""
     N, H, W, _ = x.shape
     y = torch.empty((N, H, W, g.Cout), dtype=torch.float32, device=x.device)
     d, _ = _rb_desc(x, weight, g, False, y, bias, None, None, in_act, out_scale)
@@ -562,7 +563,7 @@ def rb_conv(x, weight, g, bias, in_act, out_scale, in_bn=None, coef=None, stats_
         parts = StatParts(buf, rows, True)
         d.stats_out, d.stats_pivot = ptr(buf), ptr(stats_pivot)
     e = RbExt()
-    e.prologue, e.epilogue = _C.RB_PRO_AFFINE, _C.RB_EPI_PLAIN
+    e.prologue, e.epilogue, e.nsplit = _C.RB_PRO_AFFINE, _C.RB_EPI_PLAIN, nsplit
     _rb_prefetch(e, prefetch)
     call('lvae_resblock_conv_f32', C.byref(d), C.byref(e), stream_ptr())
     del keep
@@ -638,7 +639,7 @@ class PendingApply:
         self.parts, self.dh, self.x, self.coef0, self.act, self.dgamma, self.dbeta, self.add, self.out = parts, dh, x, coef0, act, dgamma, dbeta, add, out
 
 
-def rb_gate_dgrad(dout, ab, gate_w, gate_g, act, drop, weight, g, bn_bwd, prefetch=None, apply=None):
+def rb_gate_dgrad(dout, ab, gate_w, gate_g, act, drop, weight, g, bn_bwd, prefetch=None, apply=None, nsplit=0):
     """Backward of rb_conv_gate up to the block's second BatchNorm in one launch: dab = gate'(dout, ab), dy2 = (dab . Wg^T) * drop,
     dh2 = dgrad3x3(dy2) with the BatchNorm-backward sums of bn_bwd = (y1, coef block row 0, act). Returns (dab, dy2, dh2, parts).
     apply (PendingApply): dout does not exist yet; the launch forms it in its prologue and stores it to apply.out (= dout's memory)."""
@@ -649,7 +650,7 @@ def rb_gate_dgrad(dout, ab, gate_w, gate_g, act, drop, weight, g, bn_bwd, prefet
     dh = torch.empty((N, H, W, g.Cin), dtype=torch.float32, device=dev)
     d, _ = _rb_desc(dout, weight, g, True, dh)
     e = RbExt()
-    e.prologue, e.epilogue = _C.RB_PRO_GATE_BWD, _C.RB_EPI_PLAIN
+    e.prologue, e.epilogue, e.nsplit = _C.RB_PRO_GATE_BWD, _C.RB_EPI_PLAIN, nsplit
     _rb_gate_ws(e, gate_w, gate_g, dev, True)
     e.act = ACT[act]
     e.dout, e.ab_in, e.dab, e.pro_drop, e.xt_out = ptr(dout), ptr(ab), ptr(dab), ptr(drop), ptr(dy2)
@@ -663,7 +664,7 @@ def rb_gate_dgrad(dout, ab, gate_w, gate_g, act, drop, weight, g, bn_bwd, prefet
     return dab, dy2, dh, parts
 
 
-def rb_apply_dgrad(parts_in, dh_in, x_bn, coef0, act, dgamma, dbeta, drop, weight, g, bn_bwd, prefetch=None):
+def rb_apply_dgrad(parts_in, dh_in, x_bn, coef0, act, dgamma, dbeta, drop, weight, g, bn_bwd, prefetch=None, nsplit=0):
     """BatchNorm backward (training mode; parts_in = the sums the producer of dh_in left) + Dropout2d mask + dgrad of the block's first
     convolution in one launch: dy1 = BN'(dh_in; x_bn) * drop, dh1 = dgrad3x3(dy1) with the sums of bn_bwd = (x, coef block row 0, act).
     coef0: row 0 of the (4, C) coefficient block of the BatchNorm being differentiated. Returns (dy1, dh1, parts)."""
@@ -673,7 +674,7 @@ def rb_apply_dgrad(parts_in, dh_in, x_bn, coef0, act, dgamma, dbeta, drop, weigh
     dh = torch.empty((N, H, W, g.Cin), dtype=torch.float32, device=dev)
     d, _ = _rb_desc(dh_in, weight, g, True, dh)
     e = RbExt()
-    e.prologue, e.epilogue = _C.RB_PRO_BN_APPLY, _C.RB_EPI_PLAIN
+    e.prologue, e.epilogue, e.nsplit = _C.RB_PRO_BN_APPLY, _C.RB_EPI_PLAIN, nsplit
     e.bwd_parts, e.bwd_rows, e.bwd_act, e.bwd_M = ptr(parts_in), parts_in.shape[0], ACT[act], N * H * W
     e.bwd_coef, e.bwd_x, e.dgamma, e.dbeta, e.pro_drop, e.xt_out = ptr(coef0), ptr(x_bn), ptr(dgamma), ptr(dbeta), ptr(drop), ptr(dy1)
     parts = _rb_bn_bwd(d, bn_bwd, dh)

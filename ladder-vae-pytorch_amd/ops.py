@@ -264,7 +264,8 @@ def _fwd_fused_gate(call, x, blk, m1, m2, training):
         in_bn, coef1 = _bn_of_half(x, blk.bn1, True, call.parts, call.pivot)
         st.link('fwd', K.rb_weight_ranges(x, cv1.weight, cv1.geom(), False))
         y1, parts2, coef1 = K.rb_conv(x, cv1.weight, cv1.geom(), cv1.bias, act, m1, in_bn=in_bn, coef=coef1, stats_pivot=bn2.running_mean,
-                                      prefetch=K.rb_weight_ranges(x, cv2.weight, cv2.geom(), False, gate=(gate.weight, gate.geom())))
+                                      prefetch=K.rb_weight_ranges(x, cv2.weight, cv2.geom(), False, gate=(gate.weight, gate.geom())),
+                                      nsplit=RB.switches.rb_nsplit)
     else:
         y1, parts2, coef1 = _conv_half(x, blk.bn1, cv1, act, m1, True, call.parts, call.pivot, bn2.running_mean, False)
     in_bn, coef2 = _bn_of_half(y1, bn2, True, parts2, bn2.running_mean)
@@ -363,12 +364,13 @@ def _bwd_whole_image(blk, dout, x, y1, y2, ab, coef1, coef2, m1, m2):
     gw, w2, w1 = gate.weight, cv2.weight, cv1.weight
     st.link('bwd', K.rb_weight_ranges(dout, w2, cv2.geom(), True, gate=(gw, gate.geom()), gate_bwd=True))
     dab, dy2, dh2, parts2 = K.rb_gate_dgrad(dout, ab, gw, gate.geom(), act, m2, w2, cv2.geom(), bn_bwd=(y1, coef2[0], act),
-                                            prefetch=K.rb_weight_ranges(dout, w1, cv1.geom(), True), apply=st.take_pending(dout))
+                                            prefetch=K.rb_weight_ranges(dout, w1, cv1.geom(), True), apply=st.take_pending(dout),
+                                            nsplit=RB.switches.rb_nsplit)
     if gw.requires_grad:
         wgrad(y2, dab, gw, gate.geom(), grad_buf(gw), grad_buf(gate.bias))
     wgrad(y1, dy2, w2, cv2.geom(), grad_buf(w2), grad_buf(cv2.bias), in_scale=coef2[0], in_shift=coef2[1], in_act=act)
     dy1, dh1, parts1 = K.rb_apply_dgrad(parts2, dh2, y1, coef2[0], act, grad_buf(bn2.weight), grad_buf(bn2.bias), m1, w1, cv1.geom(),
-                                        bn_bwd=(x, coef1[0], act), prefetch=st.next_ranges('bwd'))
+                                        bn_bwd=(x, coef1[0], act), prefetch=st.next_ranges('bwd'), nsplit=RB.switches.rb_nsplit)
     wgrad(x, dy1, w1, cv1.geom(), grad_buf(w1), grad_buf(cv1.bias), in_scale=coef1[0], in_shift=coef1[1], in_act=act)
     return dh1, parts1
 

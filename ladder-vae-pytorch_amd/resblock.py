@@ -31,6 +31,7 @@ class Switches:
         # 8x8, 33 -> 26 at 4x4, 22 -> 27 at 2x2, where the position-major kernels skip the taps outside the image; backward 60 -> 43,
         # 46 -> 33, 37 -> 33): forward from 16 pixels per image up, backward everywhere the kernels exist. 0 pixels = never.
         self.rb_fwd_min_hw, self.rb_bwd_min_hw = int(env.get('LVAE_RB_FWD_MIN_HW', '16')), int(env.get('LVAE_RB_BWD_MIN_HW', '1'))
+        self.rb_nsplit = int(env.get('LVAE_RB_NSPLIT', '0'))         # workgroups per tile of the whole-image plain launches (lvae_rb_ext.nsplit): 0 = the library decides (two at the 4x4 and 2x2 levels at batch 256: profiles/rb_nsplit_ab.txt), 1 = one, 2 = two wherever the kernel exists
         self.rb_gate_large = on('LVAE_RB_GATE_LARGE')                 # conv2 + gate in one launch at the >= 16x16 levels (Winograd kernel)
         self.stoch_block = on('LVAE_STOCH_BLOCK')                     # the stochastic block of the <= 8x8 levels in one forward launch (ops.StochBlockFn)
         self.stoch_block_bwd = on('LVAE_STOCH_BLOCK_BWD')             # ... and its backward in one launch

@@ -1,5 +1,6 @@
 """In-kernel phase stamps of rb_conv_kernel (needs the -DLVAE_RB_DBG library built by tools/rb_stamps.sh):
-python tools/rb_stamps.py <H> <path of lib_rb.so>  -> median s_memtime ticks per phase over the waves of one launch"""
+python tools/rb_stamps.py <H> <path of lib_rb.so> [nsplit]  -> median s_memtime ticks per phase over the waves of one launch
+(nsplit: lvae_rb_ext.nsplit of the three plain launches, 0 = the library decides)"""
 import ctypes
 import os
 import sys
@@ -14,6 +15,7 @@ _C.LIB_PATH = sys.argv[2]
 from lvae_amd import kernels as K
 
 H = int(sys.argv[1])
+NSPLIT = int(sys.argv[3]) if len(sys.argv) > 3 else 0
 B, C, dev = 256, 64, 'cuda'
 packed = lambda co, ci, k: torch.randn(k, k, ci, co, device=dev).permute(3, 2, 0, 1) * 0.05
 x, dout = torch.randn(B, H, H, C, device=dev), torch.randn(B, H, H, C, device=dev)
@@ -31,7 +33,7 @@ st = {}
 
 
 def conv1():
-    st['y1'], st['p2'], st['c1'] = K.rb_conv(x, w1, g1, b1, 'elu', m1, coef=coef1, stats_pivot=bn2.running_mean)
+    st['y1'], st['p2'], st['c1'] = K.rb_conv(x, w1, g1, b1, 'elu', m1, coef=coef1, stats_pivot=bn2.running_mean, nsplit=NSPLIT)
 
 
 def conv2_gate():
@@ -40,18 +42,18 @@ def conv2_gate():
 
 
 def gate_dgrad():
-    _, _, st['dh2'], st['bp2'] = K.rb_gate_dgrad(dout, st['ab'], wg, gg, 'elu', m2, w2, g2, bn_bwd=(st['y1'], st['c2'][0], 'elu'))
+    _, _, st['dh2'], st['bp2'] = K.rb_gate_dgrad(dout, st['ab'], wg, gg, 'elu', m2, w2, g2, bn_bwd=(st['y1'], st['c2'][0], 'elu'), nsplit=NSPLIT)
 
 
 def apply_dgrad():
-    K.rb_apply_dgrad(st['bp2'], st['dh2'], st['y1'], st['c2'][0], 'elu', dg, db, m1, w1, g1, bn_bwd=(x, st['c1'][0], 'elu'))
+    K.rb_apply_dgrad(st['bp2'], st['dh2'], st['y1'], st['c2'][0], 'elu', dg, db, m1, w1, g1, bn_bwd=(x, st['c1'][0], 'elu'), nsplit=NSPLIT)
 
 
 for fn in (conv1, conv2_gate, gate_dgrad, apply_dgrad):
     fn()
 K.prepared.prepare_all()
 lib = ctypes.CDLL(sys.argv[2])
-nwg = min(1024, K.rb_rows(x, w1, g1))
+tiles = K.rb_rows(x, w1, g1)
 names = ['0-1 loads + statistics fold', '1-2 staging (act, split, LDS) + ring', '2-3 barrier', '3-4 3x3 reduction loop', '4-5 barrier, partial tiles, barrier',
          '5-6 epilogue (sum, bias, mask, stores [, gate GEMM + stores])', '6-7 statistics rows']
 for name, fn in (('conv1 (plain, given coefficients)', conv1), ('conv2 + gate (folded finalize)', conv2_gate), ('gate-bwd + dgrad', gate_dgrad),
@@ -61,6 +63,7 @@ for name, fn in (('conv1 (plain, given coefficients)', conv1), ('conv2 + gate (f
     torch.cuda.synchronize()
     buf = np.zeros(1024 * 4 * 12, dtype=np.uint64)
     assert lib.lvae_debug_rb_stamps(buf.ctypes.data_as(ctypes.c_void_p), ctypes.c_size_t(buf.nbytes)) == 0
+    nwg = min(1024, tiles * (1 if name.startswith('conv2') or NSPLIT == 1 or H * H > 16 or 2 * tiles > 256 else 2))   # two workgroups per tile: rb_nsplit()
     s = buf.reshape(1024 * 4, 12)[:nwg * 4].astype(np.int64)
     t0 = s[:, 0].min()
     print('%s %dx%d (%d workgroups): launch spans %d ticks (first wave start -> last end stamp); wave start spread %d' % (
