@@ -1040,6 +1040,28 @@ typedef struct lvae_copy_entry {
   int64_t n;
 } lvae_copy_entry;
 int lvae_multi_copy_f32(const lvae_copy_entry* table, int32_t n_entries, const int32_t* flag, int32_t want, void* stream);
+/* BatchNorm recalibration (csrc/bn_recal.hip): running statistics re-estimated for the weights a pass is about to evaluate, by the
+ * momentum=None rule of torch.optim.swa_utils.update_bn. With momentum 1 a train-mode forward leaves each BatchNorm's batch mean and
+ * unbiased batch variance in its running statistics; a fold after every forward and one finish give their equal-weight means.
+ * table: device array of n_entries {stat, acc, n}, 8-byte aligned, laid out like lvae_copy_entry; entry e belongs to workgroup e and each
+ * element to one thread of it, so no result depends on the grid and no atomics touch the data. Entries must not overlap each other.
+ * count: device int64[2], zero before the first fold: count[0] is the number of folds since the last finish, count[1] belongs to finish
+ * (the ticket by which the workgroup that arrives last clears count[0]; it is 0 again when the launch ends).
+ *   lvae_bn_recal_fold_f64    acc[i] += (double)stat[i] for every element of every entry, then count[0] += 1: the sequential float64 sum
+ *                             of the float32 values, in launch order. A statistic nobody rewrote between folds adds the same value n
+ *                             times and comes back from finish bit for bit (n * v and its quotient by n are exact in double; only a
+ *                             -0.0 returns as +0.0).
+ *   lvae_bn_recal_finish_f32  stat[i] = (float)(acc[i] / count[0]) with count[0] read on the device, then acc[i] = 0 and count[0] = 0;
+ *                             flag[0] = 1 (device int32[1], otherwise left alone: the caller clears it) when a value written is not
+ *                             finite. With count[0] == 0 nothing is written. Both launches take their numbers from device memory, so
+ *                             they can sit in a captured graph that is replayed any number of times. */
+typedef struct lvae_bn_recal_entry {
+  float* stat;
+  double* acc;
+  int64_t n;
+} lvae_bn_recal_entry;
+int lvae_bn_recal_fold_f64(const lvae_bn_recal_entry* table, int32_t n_entries, int64_t* count, void* stream);
+int lvae_bn_recal_finish_f32(const lvae_bn_recal_entry* table, int32_t n_entries, int64_t* count, int32_t* flag, void* stream);
 /* a[0:n] <-> b[0:n] in one pass (16-byte aligned, not overlapping): the averaged weights exchanged IN PLACE with the trainable prefix of
  * the parameter arena for a test pass and back, so captured graphs and parameter views keep their addresses. */
 int lvae_swap_f32(float* a, float* b, int64_t n, void* stream);

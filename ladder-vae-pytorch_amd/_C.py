@@ -100,6 +100,11 @@ class CopyEntry(C.Structure):
     _fields_ = [('dst', C.c_void_p), ('src', C.c_void_p), ('n', C.c_int64)]
 
 
+class BnRecalEntry(C.Structure):
+    """mirror of struct lvae_bn_recal_entry"""
+    _fields_ = [('stat', C.c_void_p), ('acc', C.c_void_p), ('n', C.c_int64)]
+
+
 LR_KINDS = {'constant': 0, 'cosine': 1, 'linear': 2, 'step': 3, 'exp': 4}   # LVAE_LR_*
 
 RB_PRO_AFFINE, RB_PRO_BN_APPLY, RB_PRO_GATE_BWD = 0, 1, 2
@@ -245,6 +250,8 @@ SIGNATURES = {
     'lvae_adam_step_f32': (C.c_int, [_P, _P, _P, _P, _P, _L, _F, C.POINTER(LrScheduleStruct), C.c_double, C.c_double, _F, _F, _I, _P, _P, _P,
                                      _F, _P, _P, _P]),
     'lvae_multi_copy_f32': (C.c_int, [_P, _I, _P, _I, _P]),
+    'lvae_bn_recal_fold_f64': (C.c_int, [_P, _I, _P, _P]),
+    'lvae_bn_recal_finish_f32': (C.c_int, [_P, _I, _P, _P, _P]),
     'lvae_swap_f32': (C.c_int, [_P, _P, _L, _P]),
     'lvae_sumsq_workspace': (_Z, [_L]),
     'lvae_l2norm_f32': (C.c_int, [_P, _L, _P, _P, _Z, _P]),

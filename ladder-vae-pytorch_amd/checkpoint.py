@@ -98,20 +98,37 @@ def accum_steps_record(ck):
     return int(ck.get('accum_steps', 1)) if isinstance(ck, dict) and 'model' in ck else 1
 
 
-def save_checkpoint(path, model, optimizer=None, summary=None):
+def recalibrated_bn_buffers(model, optimizer, bn_recal):
+    """{key: CPU tensor} of every BatchNorm running_mean / running_var recalibrated for the AVERAGED weights on the batches bn_recal()
+    returns (recalibrate.recalibrated inside optimizer.swap_ema(), as a test pass under --ema-bn-batches does it): the parameters and the
+    live statistics are back, bit for bit, on return."""
+    from .lib.nn import BatchNorm2dParams
+    from .recalibrate import recalibrated
+    with optimizer.swap_ema(), recalibrated(model, bn_recal(), step=model.global_step):
+        return {k + '.' + name: getattr(m, name).detach().to('cpu').contiguous().clone()
+                for k, m in model.named_modules() if isinstance(m, BatchNorm2dParams) for name in ('running_mean', 'running_var')}
+
+
+def save_checkpoint(path, model, optimizer=None, summary=None, bn_recal=None):
     """Weights (reference layout), global step, Adamax state and the position of the Philox noise stream, so that a resumed run continues
     the original one bit for bit. With a `summary` (summary.TrainSummary) also 'summary': the open log window's accumulator as a list of
     floats, so that the run resumed in the middle of a window prints the train line of the uninterrupted one. A scheduled lr is a function
     of the Adamax step and of the schedule, stored as 'lr_schedule' (`lr_schedule_record`). 'iw_train_samples' notes the K of the objective
     the run trained on (model.iw_train_samples; 1 = the ELBO), by the same rule: load_checkpoint does not touch the resumed run's own.
     A guarded optimizer adds 'grad_guard' (GradGuard.state_dict: its limits and the cumulative clipped / skipped counts). 'accum_steps' notes
-    the micro-batches per optimizer step (model.accum_steps; `accum_steps_record` reads it back, 1 from a file without the key)."""
+    the micro-batches per optimizer step (model.accum_steps; `accum_steps_record` reads it back, 1 from a file without the key).
+    bn_recal (--ema-bn-batches; a callable returning image batches, used only with an averaging optimizer): the BatchNorm running statistics
+    of 'ema' are those recalibrated for the averaged weights (`recalibrated_bn_buffers`), so the dict a reference model loads is
+    self-consistent, and 'ema_bn_batches' notes the flag (model.ema_bn_batches). 'model', the optimizer state and a resumed run are untouched."""
     ck = {'model': state_dict_reference_layout(model), 'global_step': int(model.global_step)}
     if optimizer is not None:
         ck['optimizer'] = optimizer_state_by_name(model, optimizer)
         if getattr(optimizer, 'ema_decay', 0.0) > 0.0:
             ck['ema'] = ema_state_dict_reference_layout(model, optimizer)
             ck['ema_decay'] = optimizer.ema_decay
+            if bn_recal is not None:
+                ck['ema'].update(recalibrated_bn_buffers(model, optimizer, bn_recal))
+                ck['ema_bn_batches'] = int(getattr(model, 'ema_bn_batches', 0))
         if lr_schedule_record(optimizer) is not None:
             ck['lr_schedule'] = lr_schedule_record(optimizer)
         if getattr(optimizer, 'guard', None) is not None:

@@ -385,3 +385,29 @@ class DeviceDataset:
         table = self._dev()
         for base in range(0, self.N, int(n)):
             yield K.batch_gather(table, self.channels_last, self.new_batch(min(int(n), self.N - base)), base=base)
+
+
+def first_batches(images, n_batches, batch_size, channels_last=False):
+    """The first n_batches * batch_size images of a training set in STORED order, as float32 NCHW batches of batch_size: what BatchNorm
+    recalibration (recalibrate.py) runs the averaged weights on. The same on every rank and at every world size; no loader, cursor or
+    generator is consumed. images: a host tensor as `image_table` returns it (float NCHW; uint8 NCHW, or uint8 NHWC with channels_last:
+    a value means v / 255, the gather's rule), or a DeviceDataset, whose HBM table is read (one gather launch per batch). A set shorter
+    than n_batches * batch_size stops at its last whole batch; ValueError when it does not fill one. -> a list of batches."""
+    n_batches, batch_size = int(n_batches), int(batch_size)
+    if n_batches < 1 or batch_size < 1:
+        raise ValueError("first_batches needs at least one batch of at least one image, got %d x %d" % (n_batches, batch_size))
+    N = images.N if isinstance(images, DeviceDataset) else int(images.shape[0])
+    whole = min(n_batches, N // batch_size)
+    if whole < 1:
+        raise ValueError("%d images do not fill one batch of %d" % (N, batch_size))
+    if isinstance(images, DeviceDataset):
+        from . import kernels as K
+        table = images._dev()
+        return [K.batch_gather(table, images.channels_last, images.new_batch(batch_size), base=i * batch_size) for i in range(whole)]
+    out = []
+    for i in range(whole):
+        x = torch.as_tensor(images[i * batch_size:(i + 1) * batch_size])
+        if x.dtype == torch.uint8:
+            x = (x.permute(0, 3, 1, 2) if channels_last else x).float().div_(255.0)
+        out.append(x.float().contiguous())
+    return out

@@ -39,7 +39,11 @@ CLI: python -m lvae_amd.evaluate --synthetic --ll --ll-samples 100 --ps --layer-
      (12, K); with --img-dir DIR/nn_<...>.png (one row per query). One line: neighbours.closeness_summary over 144 samples and up to
      1000 evaluation images. The table is key 'data' of FILE.npz, or N synthetic images drawn from seed + 1.
      --temperature T [T ...] (one value, or one per layer, bottom first) tempers the prior draws of --ps, --cond-samples and --interp.
+     --recalibrate-bn data|prior [--recalibrate-batches N] re-estimates the BatchNorm running statistics once, before any output, for the
+     weights that were loaded (recalibrate.recalibrate_bn): on the first N (default 20) batches of --batch-size training images, or on N
+     train-mode top-down passes from the prior at --temperature (one value). One header line says which.
 """
+import contextlib
 import os
 
 import numpy as np
@@ -148,6 +152,14 @@ class _EvalWeights:
         return False
 
 
+def _bn_recal(model, source):
+    """The context of a pass on the averaged weights: nothing (None) without a source, else recalibrate.recalibrated on source()."""
+    if source is None:
+        return contextlib.nullcontext()
+    from .recalibrate import recalibrated
+    return recalibrated(model, source(), step=model.global_step)
+
+
 def _test_sample(model, bu_values, x_nhwc, state, zero, latent_stats=None):
     """_elbo_sample, folded into the per-image state of a test pass (lvae_eval_online_f32)."""
     K.eval_online(state, model.n_layers, 1, *_elbo_sample(model, bu_values, x_nhwc, zero, latent_stats))
@@ -215,7 +227,7 @@ class _TestGraphs:
 
 
 @torch.no_grad()
-def test_pass(model, batches, n_samples, noise=None, process_group=None, use_graph=None, optimizer=None, latent_stats=None):
+def test_pass(model, batches, n_samples, noise=None, process_group=None, use_graph=None, optimizer=None, latent_stats=None, bn_recal=None):
     """The reference's test summaries over an iterable of NCHW image batches (each rank passes ITS shard of the test set): means over images
     and samples of 'elbo/elbo', 'elbo/recons', 'elbo/kl', 'kl_layers/kl_layer_<i>', plus 'elbo/elbo_IW_<S>' when S > 1, and 'n_images'.
 
@@ -231,12 +243,17 @@ def test_pass(model, batches, n_samples, noise=None, process_group=None, use_gra
     latent_stats: a latent.LatentStats. The FIRST sample of every batch (one ancestral sample per image) also folds every layer's p and q
     parameters into it; the pass ends with its `take()` (a collective, like the all-reduce of the totals) and the result gains the
     'latent/*' counts and 'latent_arrays' (per layer 'kl', 'mu_mean', 'mu_var' as (Z, h, w) arrays). Every other key is bit for bit what the
-    pass returns without it: the folds draw no noise and write nothing the pass reads."""
+    pass returns without it: the folds draw no noise and write nothing the pass reads.
+    bn_recal (--ema-bn-batches; read only on the averaged weights): a callable returning image batches. Inside `swap_ema()` the BatchNorm
+    statistics are first recalibrated on them (recalibrate.recalibrated, its noise stream placed at model.global_step), the pass reads the
+    recalibrated statistics, and the live ones are back before the weights are; the result gains 'bn_recal/rounds'."""
     if optimizer is not None and getattr(optimizer, 'ema_decay', 0.0) > 0.0:
-        with optimizer.swap_ema():
+        with optimizer.swap_ema(), _bn_recal(model, bn_recal) as recal:
             res = test_pass(model, batches, n_samples, noise=noise, process_group=process_group, use_graph=use_graph,
                             latent_stats=latent_stats)
         res['weights'] = 'ema'
+        if recal is not None:
+            res['bn_recal/rounds'] = recal['rounds']
         return res
     from .noise import PhiloxNoise
     dev = next(model.parameters()).device
@@ -435,16 +452,17 @@ IMAGE_NOISE_STRIDE = 1 << 20   # and its counter starts at step * this: the pict
 
 
 @torch.no_grad()
-def image_pass(model, nrows, x=None, step=0, optimizer=None):
+def image_pass(model, nrows, x=None, step=0, optimizer=None, bn_recal=None):
     """The trainer's pictures -> (sample grid, reconstruction grid or None), uint8 (Hg, Wg, 3) device tensors (images.image_grid).
 
     The sample grid holds nrows^2 prior samples; with x (an NCHW batch) the reconstruction grid holds min(nrows^2 // 2, len(x)) input /
     reconstruction pairs, nrows pictures per row. Eval mode, convolutions transform their own weights (_EvalWeights), eager launches; with
     an averaging optimizer the pass runs on the averaged weights (`optimizer.swap_ema()`). Noise comes from a fresh PhiloxNoise made from
     the model's seed and `step`, never from `model.noise` or `model.test_noise`: the pictures of step N do not depend on what ran before,
-    so a resumed run writes the same ones. On return training mode, `model.noise` and the prepared-weight table are as they were."""
+    so a resumed run writes the same ones. On return training mode, `model.noise` and the prepared-weight table are as they were.
+    bn_recal: as in test_pass; the pictures of the averaged weights are then made with recalibrated BatchNorm statistics."""
     if optimizer is not None and getattr(optimizer, 'ema_decay', 0.0) > 0.0:
-        with optimizer.swap_ema():
+        with optimizer.swap_ema(), _bn_recal(model, bn_recal):
             return image_pass(model, nrows, x, step)
     from .images import image_grid
     from .noise import PhiloxNoise
@@ -480,6 +498,12 @@ def build_eval_parser():
     # (--latent-stats and its two thresholds are flags of build_parser: here with --ll, and the arrays go to latent_stats.npz)
     p.add_argument('--temperature', type=float, nargs='+', default=None, metavar='T',
                    help='temperature of the prior draws of --ps, --cond-samples and --interp: one value, or one per layer (bottom layer first)')
+    p.add_argument('--recalibrate-bn', choices=('data', 'prior'), default=None, dest='recalibrate_bn',
+                   help='re-estimate the BatchNorm running statistics once, before the requested outputs, for the weights that were loaded '
+                        '(with --ema: the averaged ones). data: on the first --recalibrate-batches batches of --batch-size images of the '
+                        "training split (key 'data' of --data-npz, or the data set of -d). prior: on that many train-mode top-down passes "
+                        'of --batch-size rows from the prior at --temperature (one value), for --ps, --layer-repr, --cond-samples, --interp, --nn')
+    p.add_argument('--recalibrate-batches', type=int, default=20, dest='recalibrate_batches', metavar='N')
     p.add_argument('--cond-samples', action='store_true', dest='cond_samples',
                    help='variations of the evaluation images that keep their top k latents -> cond_samples_top<k>.npy')
     p.add_argument('--cond-layers', type=int, nargs='+', default=None, dest='cond_layers', metavar='k',
@@ -558,6 +582,12 @@ def parse_eval_args(argv=None):
             p.error('--temperature takes one value or one per layer (%d), got %d' % (L, len(args.temperature)))
         if any(not 0.0 <= t < float('inf') for t in args.temperature):
             p.error('--temperature takes finite values >= 0, got %s' % args.temperature)
+    if args.recalibrate_bn is not None and args.recalibrate_batches < 1:
+        p.error('--recalibrate-batches must be at least 1, got %d' % args.recalibrate_batches)
+    if args.recalibrate_bn == 'data' and args.synthetic and not args.data_npz:
+        p.error('--recalibrate-bn data needs a training split (--data-npz FILE or a data set); --synthetic has none')
+    if args.recalibrate_bn == 'prior' and args.temperature is not None and len(args.temperature) != 1:
+        p.error('--recalibrate-bn prior takes one --temperature for all layers, got %d' % len(args.temperature))
     if not 1 <= args.nn_k <= K.NN_MAX_K:
         p.error('--nn-k takes values from 1 to %d, got %d' % (K.NN_MAX_K, args.nn_k))
     if args.nn_layers is None:
@@ -578,6 +608,36 @@ def parse_eval_args(argv=None):
         if args.nn_space == 'latent' and shape[1:] != (color_ch,) + tuple(img_size):
             p.error('--nn-space latent: the table holds images of %s, the model encodes %s' % (shape[1:], (color_ch,) + tuple(img_size)))
     return args
+
+
+def _recalibrate_from_args(exp, temperature):
+    """--recalibrate-bn of the command line -> the header line that says what the statistics were re-estimated on."""
+    from .recalibrate import recalibrate_bn
+    args, model = exp.args, exp.model
+    n, bs = args.recalibrate_batches, args.batch_size
+    weights = 'averaged weights' if args.ema else 'weights'
+    if args.recalibrate_bn == 'prior':
+        info = recalibrate_bn(model, n_prior=n, prior_batch=bs, temperature=temperature)
+        return ('BatchNorm recalibrated for the %s on the prior: %d top-down passes of %d rows at temperature %g (%d BatchNorm layers)'
+                % (weights, info['rounds'], bs, 1.0 if temperature is None else temperature, info['n_bn']))
+    from .data import first_batches
+    channels_last = False
+    if args.data_npz:
+        train = torch.from_numpy(np.load(args.data_npz)['data'])
+    else:
+        from .data import DatasetLoader
+        from .main import image_table
+        try:
+            train, channels_last = image_table(DatasetLoader(args).train.dataset)
+        except RuntimeError as e:
+            raise SystemExit('--recalibrate-bn data: no training split (%s)' % e)
+    try:
+        batches = first_batches(train, n, bs, channels_last)
+    except ValueError as e:
+        raise SystemExit('--recalibrate-bn data: %s' % e)
+    info = recalibrate_bn(model, batches)
+    return ('BatchNorm recalibrated for the %s on data: the first %d batches of %d training images (%d BatchNorm layers)'
+            % (weights, info['rounds'], bs, info['n_bn']))
 
 
 IMG_GRID_N = 12   # the reference's evaluate.py:24
@@ -604,6 +664,8 @@ def main(argv=None):
     if args.img_dir:
         os.makedirs(args.img_dir, exist_ok=True)
     temperature = None if args.temperature is None else (args.temperature[0] if len(args.temperature) == 1 else args.temperature)
+    if args.recalibrate_bn:   # once, before every output below, for the weights just loaded
+        print(_recalibrate_from_args(exp, temperature))
     if args.ll or args.recons or args.cond_samples or args.interp or args.inpaint or args.nn:
         gen = torch.Generator().manual_seed(args.seed)
         if args.data_npz:

@@ -95,6 +95,11 @@ def build_parser():
     p.add_argument('--ema-decay', type=_ema_decay, default=0.0, dest='ema_decay', metavar='D',
                    help='keep an exponential moving average of the weights inside the optimizer step (decay ramps up as min(D, (1+n)/(10+n))); '
                         'test and log-likelihood passes then use the averaged weights and checkpoints carry them. 0: off')
+    p.add_argument('--ema-bn-batches', type=int, default=0, dest='ema_bn_batches', metavar='N',
+                   help='with --ema-decay: before every test, log-likelihood and picture pass on the averaged weights, re-estimate the BatchNorm '
+                        'running statistics for them on the first N batches of --batch-size training images (train-mode forwards, equal-weight '
+                        'mean of the batch statistics), and put the live statistics back afterwards; checkpoints store the recalibrated '
+                        "statistics in their 'ema' entry. 0: off (the averaged weights are evaluated with the live weights' statistics)")
     p.add_argument('--window-summaries', action='store_true', dest='window_summaries',
                    help='the train line prints the mean of every step since the previous train line, over all ranks (summed on the device '
                         'inside the step), with the gradient norm and the number of non-finite steps, instead of the last step of rank 0')
@@ -178,6 +183,11 @@ class LVAEExperiment:
         if iw > 1 and args.analytical_kl:
             raise SystemExit("--iw-train-samples %d cannot be combined with --analytical-kl: the importance weights need the Monte-Carlo "
                              "log q - log p of the drawn sample" % iw)
+        bn_batches = getattr(args, 'ema_bn_batches', 0)
+        if bn_batches < 0:
+            raise SystemExit("--ema-bn-batches must not be negative, got %d" % bn_batches)
+        if bn_batches > 0 and not getattr(args, 'ema_decay', 0.0) > 0.0:
+            raise SystemExit("--ema-bn-batches %d recalibrates BatchNorm for the averaged weights: it needs --ema-decay > 0" % bn_batches)
         if getattr(args, 'accum_steps', 1) < 1:
             raise SystemExit("--accum-steps must be at least 1, got %d" % args.accum_steps)
         g, t = getattr(args, 'max_grad_norm', None), getattr(args, 'grad_skip_threshold', None)
@@ -252,6 +262,7 @@ class LVAEExperiment:
         model.compute_dtype = a.compute_dtype
         model.iw_train_samples = getattr(a, 'iw_train_samples', 1)   # (noted in checkpoints: checkpoint.save_checkpoint)
         model.accum_steps = getattr(a, 'accum_steps', 1)             # (likewise)
+        model.ema_bn_batches = getattr(a, 'ema_bn_batches', 0)       # (likewise, when it is not 0)
         return model
 
     @staticmethod
@@ -298,6 +309,8 @@ class LVAEExperiment:
             s += "[step {}, epoch {}]   ".format(step, epoch)
         if summaries.get('weights') == 'ema':
             s += "[averaged weights]   "
+        if summaries.get('bn_recal/rounds'):
+            s += "[BatchNorm recalibrated on {} batches]   ".format(summaries['bn_recal/rounds'])
         s += "ELBO {:.5g}   recons: {:.3g}   KL: {:.3g}".format(summaries['elbo/elbo'], summaries['elbo/recons'],
                                                                summaries['elbo/kl'])
         for k in summaries.keys():

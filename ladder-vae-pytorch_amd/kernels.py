@@ -1870,6 +1870,43 @@ def multi_copy(table, flag=None, want=0):
     call('lvae_multi_copy_f32', ptr(table, (torch.int64,)), table.shape[0], ptr(flag, (torch.int32,)), int(want), stream_ptr())
 
 
+def bn_recal_table(pairs, device):
+    """[(stat, acc)] pairs of contiguous device tensors of equal length, stat float32 and acc float64 -> the device table bn_recal_fold and
+    bn_recal_finish take (int64 [len][3]: struct lvae_bn_recal_entry). The caller keeps the tensors alive and in place for as long as the
+    table is used."""
+    rows = []
+    for stat, acc in pairs:
+        if stat.numel() != acc.numel() or stat.numel() < 1 or not (stat.is_contiguous() and acc.is_contiguous()):
+            raise _C.LvaeHipError("bn_recal_table: an entry needs two contiguous buffers of one length")
+        rows.append([ptr(stat, (torch.float32,)), ptr(acc, (torch.float64,)), stat.numel()])
+    if not rows:
+        raise _C.LvaeHipError("bn_recal_table: no entries")
+    return torch.tensor(rows, dtype=torch.int64).to(device)
+
+
+def _bn_recal_args(table, count, what):
+    if table.dtype != torch.int64 or table.dim() != 2 or table.shape[1] != 3 or not table.is_contiguous():
+        raise _C.LvaeHipError("%s: the table is a contiguous device int64 [entries][3]" % what)
+    if count.dtype != torch.int64 or count.numel() != 2 or not count.is_contiguous():
+        raise _C.LvaeHipError("%s: the count is a contiguous device int64[2] (folds so far, finish's ticket)" % what)
+
+
+def bn_recal_fold(table, count):
+    """acc += (double)stat for every entry of a bn_recal_table, count[0] += 1: one launch, one workgroup per entry."""
+    _bn_recal_args(table, count, 'bn_recal_fold')
+    call('lvae_bn_recal_fold_f64', ptr(table, (torch.int64,)), table.shape[0], ptr(count, (torch.int64,)), stream_ptr())
+
+
+def bn_recal_finish(table, count, flag):
+    """stat = (float)(acc / count[0]) for every entry, then the accumulators and the count are cleared: one launch. flag (device int32[1])
+    is set to 1 when a value written is not finite; the caller clears it."""
+    _bn_recal_args(table, count, 'bn_recal_finish')
+    if flag.dtype != torch.int32 or flag.numel() != 1:
+        raise _C.LvaeHipError("bn_recal_finish: the flag is a device int32[1]")
+    call('lvae_bn_recal_finish_f32', ptr(table, (torch.int64,)), table.shape[0], ptr(count, (torch.int64,)), ptr(flag, (torch.int32,)),
+         stream_ptr())
+
+
 def swap(a, b):
     """a <-> b in place, one pass (two contiguous fp32 buffers of one length). The caller says when weights moved (weights_written)."""
     if a.numel() != b.numel() or not (a.is_contiguous() and b.is_contiguous()):

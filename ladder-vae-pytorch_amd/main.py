@@ -67,6 +67,31 @@ def test_batches(exp, loader, npz, rank, world, on_device=False):
     return lambda: (data[i:i + bs] for i in range(0, data.shape[0], bs))
 
 
+def recal_batches(exp, loader, data, feed):
+    """--ema-bn-batches N: a callable returning the first N batches of --batch-size training images in stored order (data.first_batches), the
+    same on every rank and at every world size; None without the flag. From the HBM table under --device-data, else from the data set's
+    or the .npz's host tensor; under --synthetic the N batches rank 0 of a one-rank run trains on first, from a generator of their own.
+    Neither the loader, nor the device cursor, nor a training generator is consumed."""
+    args = exp.args
+    n = getattr(args, 'ema_bn_batches', 0)
+    if n <= 0:
+        return None
+    from .data import first_batches
+    channels_last = False
+    if feed is not None:
+        src = feed
+    elif loader is not None:
+        src, channels_last = image_table(loader.train.dataset)
+    elif data is not None:
+        src = data
+    else:
+        gen = torch.Generator().manual_seed(args.seed)
+        src = torch.cat([synthetic_batch(exp, args.batch_size, gen) for _ in range(n)])
+    if (src.N if feed is not None else int(src.shape[0])) < args.batch_size:
+        raise SystemExit('--ema-bn-batches: the training set does not fill one batch of %d' % args.batch_size)
+    return lambda: first_batches(src, n, args.batch_size, channels_last)
+
+
 def lr_suffix(m):
     """What a scheduled lr appends to a train line: the lr of the step the line falls due at."""
     return '   lr: {:.3g}'.format(m['lr/lr']) if 'lr/lr' in m else ''
@@ -153,6 +178,7 @@ def main(argv=None):
         # the whole training set in device memory; the step gathers its own batch, in an order that is a function of (--seed, step)
         imgs, channels_last = image_table(loader.train.dataset) if loader is not None else (data, False)
         feed = DeviceDataset(imgs, args.batch_size, args.seed, rank=rank, world=world, device=exp.device, channels_last=channels_last)
+    recal = recal_batches(exp, loader, data, feed)     # --ema-bn-batches: what the averaged weights' BatchNorm statistics are re-estimated on
     sched = TrainSchedule.from_args(args, tests is not None)
     if args.simple_data_dependent_init and not args.resume:
         # experiment_manager.py:61-72: the first batch_size training images (parity unpinned, see init.py)
@@ -259,7 +285,7 @@ def main(argv=None):
         if n_samples:
             if data is not None and loader is None and feed is None:
                 epoch = step * args.batch_size * accum // data.shape[0]
-            res = test_pass(model, tests(), n_samples, optimizer=opt, latent_stats=latent)   # (--ema-decay: on the averaged weights)
+            res = test_pass(model, tests(), n_samples, optimizer=opt, latent_stats=latent, bn_recal=recal)   # (--ema-decay: on the averaged weights)
             if rank == 0:
                 line = exp.test_log_str(res, step, epoch)
                 if latent is not None:
@@ -272,7 +298,7 @@ def main(argv=None):
             # boilr's sample_<step>.png / reconstruction_<step>.png; rank 0 alone, no collective. The reconstructions show the first test
             # batch of this rank's shard, so without a test split there are none
             x_img = next(iter(tests()), None) if tests is not None else None
-            sample_grid, recon_grid = image_pass(model, IMG_NROWS, x=x_img, step=step, optimizer=opt)
+            sample_grid, recon_grid = image_pass(model, IMG_NROWS, x=x_img, step=step, optimizer=opt, bn_recal=recal)
             os.makedirs(args.img_dir, exist_ok=True)
             write_png(os.path.join(args.img_dir, 'sample_%d.png' % step), sample_grid)
             if recon_grid is not None:
@@ -280,11 +306,11 @@ def main(argv=None):
             t0, seen = time.time(), 0                  # nor the pictures
         if ckpt and rank == 0:
             os.makedirs(args.checkpoint_dir, exist_ok=True)
-            save_checkpoint(checkpoint_path(args.checkpoint_dir, step), model, opt, summary=summary)
+            save_checkpoint(checkpoint_path(args.checkpoint_dir, step), model, opt, summary=summary, bn_recal=recal)
             for name in checkpoints_to_delete(os.listdir(args.checkpoint_dir), args.keep_checkpoint_max):
                 os.remove(os.path.join(args.checkpoint_dir, name))
     if args.save_checkpoint and rank == 0:
-        save_checkpoint(args.save_checkpoint, model, opt, summary=summary)
+        save_checkpoint(args.save_checkpoint, model, opt, summary=summary, bn_recal=recal)
     if history is not None:
         history.close()
     if world > 1:
