@@ -907,6 +907,37 @@ int lvae_batch_gather_f32(const void* src, int32_t src_kind, int32_t src_hwc, in
                           const int32_t* index, const int64_t* cursor, int32_t steps_per_epoch, int32_t B_global, int32_t lo,
                           int64_t base, int32_t n_rows, float* out, void* stream);
 
+/* The same gather with the batch augmented on the way (data.FeedAugment). The noise is stateless: Philox4x32-10 words (the generator of
+ * lvae_rng_fill_f32; oracle/philox_ref.py restates it) that are a pure function of (seed, P, g, output element), so no counter advances
+ * and nothing has to be saved for a resume to repeat them:
+ *   P = cursor[0] (the count of completed micro-batches, NOT taken modulo the epoch), or `position` when cursor == NULL (the row of the
+ *       index table is then position % steps_per_epoch); g = lo + r, the row's place in the GLOBAL batch; tag = LVAE_AUG_TAG_PIXEL.
+ *   With fixed != 0, or with index == NULL: P = 0, g = the image number (base + r without an index table), tag = LVAE_AUG_TAG_FIXED,
+ *       and no row is flipped: an image's noise then depends on the seed and its number alone.
+ *   Output element e (CHW order) of the row draws word e & 3 of the block with counter e >> 2, stream word g, step word (uint32)P and
+ *       key seed ^ (P >> 32 << 32) ^ tag; u = that word through the library's u01, in [2^-25, 1 - 2^-24].
+ *   hflip: the row is mirrored in W when bit 31 of word 0 of the block (counter 0, g, (uint32)P, key seed ^ (P >> 32 << 32) ^
+ *       LVAE_AUG_TAG_FLIP) is set. The draw belongs to the OUTPUT element: a flip changes only which source pixel is read.
+ *   LVAE_AUG_BINARIZE:   out = u < v ? 1.0f : 0.0f, v being what lvae_batch_gather_f32 writes (v = 0 never gives 1, v = 1 always does).
+ *   LVAE_AUG_DEQUANTIZE: out = fminf(((float)b + u) * 0.00390625f, 0x1.fffffep-1f) of the byte b, the sum and the product rounded
+ *       separately; uint8 tables only (LVAE_EINVAL for float32). The bound is reached: 255 + (1 - 2^-24) rounds to 256 in fp32.
+ * With mode = LVAE_AUG_NONE and hflip = 0 the output equals lvae_batch_gather_f32's bit for bit. A flipped row keeps the 16-byte store
+ * path when W is a multiple of 4 as well. position >= 0. */
+enum { LVAE_AUG_NONE = 0, LVAE_AUG_BINARIZE = 1, LVAE_AUG_DEQUANTIZE = 2 };
+#define LVAE_AUG_TAG_PIXEL 0xA1
+#define LVAE_AUG_TAG_FLIP 0xA2
+#define LVAE_AUG_TAG_FIXED 0xA3
+typedef struct lvae_feed_aug {
+  uint64_t seed;
+  int64_t position;
+  int32_t mode;
+  int32_t hflip;
+  int32_t fixed;
+} lvae_feed_aug;
+int lvae_batch_gather_aug_f32(const void* src, int32_t src_kind, int32_t src_hwc, int32_t N, int32_t C, int32_t H, int32_t W,
+                              const int32_t* index, const int64_t* cursor, int32_t steps_per_epoch, int32_t B_global, int32_t lo,
+                              int64_t base, int32_t n_rows, float* out, const lvae_feed_aug* aug, void* stream);
+
 /* ------------------------------------------------------------------------------------------------------------
  * Nearest neighbours of samples in a table held in HBM (csrc/neighbours.hip; neighbours.NeighbourIndex). Evaluation only.
  * ---------------------------------------------------------------------------------------------------------- */

@@ -19,6 +19,8 @@ VARIANT_DIRECT, VARIANT_POS, VARIANT_WINO_F32, VARIANT_WINO_SIX, VARIANT_BF16_DI
 GATE_PERSISTENT, GATE_SINGLE_SHOT = 1, 2   # lvae_conv1x1_gate_variant (0: none)
 WGRAD_VARIANT_GENERIC, WGRAD_VARIANT_IMG, WGRAD_VARIANT_BF16, WGRAD_VARIANT_WINO, WGRAD_VARIANT_DIRECT_1X1, WGRAD_VARIANT_TILE, WGRAD_VARIANT_THIN = range(7)
 FEED_U8, FEED_F32 = 0, 1
+AUG_NONE, AUG_BINARIZE, AUG_DEQUANTIZE = 0, 1, 2   # lvae_feed_aug.mode
+AUG_TAG_PIXEL, AUG_TAG_FLIP, AUG_TAG_FIXED = 0xA1, 0xA2, 0xA3
 FORM_AUTO, FORM_F32_MFMA, FORM_SIX_PRODUCT, FORM_SIX_PRODUCT_DIRECT = 0, 1, 2, 3
 
 
@@ -103,6 +105,11 @@ class CopyEntry(C.Structure):
 class BnRecalEntry(C.Structure):
     """mirror of struct lvae_bn_recal_entry"""
     _fields_ = [('stat', C.c_void_p), ('acc', C.c_void_p), ('n', C.c_int64)]
+
+
+class FeedAug(C.Structure):
+    """mirror of struct lvae_feed_aug"""
+    _fields_ = [('seed', C.c_uint64), ('position', C.c_int64), ('mode', C.c_int32), ('hflip', C.c_int32), ('fixed', C.c_int32)]
 
 
 LR_KINDS = {'constant': 0, 'cosine': 1, 'linear': 2, 'step': 3, 'exp': 4}   # LVAE_LR_*
@@ -238,6 +245,7 @@ SIGNATURES = {
     'lvae_image_border_count_f32': (C.c_int, [_P, _I, _P, _I, _I, _I, _I, _I, _F, _P, _P]),
     'lvae_image_grid_u8': (C.c_int, [_P, _I, _P, _I, _I, _I, _I, _I, _I, _P, _F, _P, _L, _P]),
     'lvae_batch_gather_f32': (C.c_int, [_P, _I, _I, _I, _I, _I, _I, _P, _P, _I, _I, _I, _L, _I, _P, _P]),
+    'lvae_batch_gather_aug_f32': (C.c_int, [_P, _I, _I, _I, _I, _I, _I, _P, _P, _I, _I, _I, _L, _I, _P, C.POINTER(FeedAug), _P]),
     'lvae_nn_l2_workspace': (_Z, [_I, _L, _I]),
     'lvae_nn_l2_f32': (C.c_int, [_P, _I, _P, _I, _L, _L, _P, _I, _P, _P, _P, _Z, _P]),
     'lvae_iw_logmeanexp_f32': (C.c_int, [_P, _I, _I, _P, _P]),

@@ -98,6 +98,12 @@ def accum_steps_record(ck):
     return int(ck.get('accum_steps', 1)) if isinstance(ck, dict) and 'model' in ck else 1
 
 
+def augment_record(ck):
+    """The feed augmentation of a loaded file's run: its 'augment' (FeedAugment.record() plus the data seed under 'seed'); None for a file
+    without the key (a run without augmentation, an older file, a bare state_dict)."""
+    return ck.get('augment') if isinstance(ck, dict) and 'model' in ck else None
+
+
 def recalibrated_bn_buffers(model, optimizer, bn_recal):
     """{key: CPU tensor} of every BatchNorm running_mean / running_var recalibrated for the AVERAGED weights on the batches bn_recal()
     returns (recalibrate.recalibrated inside optimizer.swap_ema(), as a test pass under --ema-bn-batches does it): the parameters and the
@@ -119,7 +125,9 @@ def save_checkpoint(path, model, optimizer=None, summary=None, bn_recal=None):
     the micro-batches per optimizer step (model.accum_steps; `accum_steps_record` reads it back, 1 from a file without the key).
     bn_recal (--ema-bn-batches; a callable returning image batches, used only with an averaging optimizer): the BatchNorm running statistics
     of 'ema' are those recalibrated for the averaged weights (`recalibrated_bn_buffers`), so the dict a reference model loads is
-    self-consistent, and 'ema_bn_batches' notes the flag (model.ema_bn_batches). 'model', the optimizer state and a resumed run are untouched."""
+    self-consistent, and 'ema_bn_batches' notes the flag (model.ema_bn_batches). 'model', the optimizer state and a resumed run are untouched.
+    'augment' notes what the device-fed gather did to the training batches (model.augment: data.FeedAugment.record() and the seed; absent
+    without augmentation). The noise is stateless, so it is a note like 'accum_steps': a resumed run uses its own flags."""
     ck = {'model': state_dict_reference_layout(model), 'global_step': int(model.global_step)}
     if optimizer is not None:
         ck['optimizer'] = optimizer_state_by_name(model, optimizer)
@@ -135,6 +143,8 @@ def save_checkpoint(path, model, optimizer=None, summary=None, bn_recal=None):
             ck['grad_guard'] = optimizer.guard.state_dict()
     ck['iw_train_samples'] = int(getattr(model, 'iw_train_samples', 1))   # what the file's run trained on; a resumed run uses its own flag
     ck['accum_steps'] = int(getattr(model, 'accum_steps', 1))             # micro-batches per optimizer step, by the same rule
+    if getattr(model, 'augment', None) is not None:
+        ck['augment'] = dict(model.augment)   # the feed's augmentation and its seed; a file without the key means none
     nz = noise_state(model)
     if nz is not None:
         ck['noise'] = nz

@@ -224,6 +224,57 @@ def device_storage(x):
     return x, 'float32'
 
 
+def aug_seed(seed):
+    """The seed of the feed's augmentation noise, from the run's data seed (kept apart from epoch_permutation's mix of the same seed)."""
+    return (int(seed) * 0x9E3779B97F4A7C15 + 0x5851F42D4C957F2D) & (2 ** 63 - 1)
+
+
+class FeedAugment:
+    """What the device-fed gather does to a training batch on its way (csrc/batch_feed.hip): binarize draws every pixel afresh as
+    Bernoulli(value) each time it is visited (dynamic binarization), hflip mirrors each row left-right with probability 1/2,
+    dequantize adds uniform noise below one 8-bit step: (b + u) / 256. The noise is a pure function of (seed, feed cursor, place in the
+    global batch, element): nothing advances, nothing has to be saved, and every world size sees the same images."""
+
+    def __init__(self, binarize=False, hflip=False, dequantize=False):
+        self.binarize, self.hflip, self.dequantize = bool(binarize), bool(hflip), bool(dequantize)
+        if self.binarize and self.dequantize:
+            raise ValueError("binarize and dequantize exclude each other: one makes 0/1 pixels, the other continuous ones")
+
+    @property
+    def mode(self):
+        return 'binarize' if self.binarize else 'dequantize' if self.dequantize else None
+
+    def __bool__(self):
+        return self.binarize or self.hflip or self.dequantize
+
+    def record(self):
+        """A plain dict for checkpoints and the run description."""
+        return {'binarize': self.binarize, 'hflip': self.hflip, 'dequantize': self.dequantize}
+
+    def describe(self):
+        """The run description's suffix: ',binarize' / ',hflip' / ',dequant' for what is on."""
+        return ''.join(s for on, s in ((self.binarize, ',binarize'), (self.hflip, ',hflip'), (self.dequantize, ',dequant')) if on)
+
+
+def binarize_fixed(images, seed, channels_last=False, chunk=4096):
+    """A host image set (float (N,C,H,W) with values in [0, 1], uint8 (N,C,H,W), or uint8 (N,H,W,C) with channels_last; a byte means
+    v / 255) -> a host uint8 (N,C,H,W) tensor of 0/1: pixel e of image i is 1 where the fixed draw of (aug_seed(seed), i, e) lies below
+    its value. One binarization per (seed, image number): independent of how the set is cut into batches, of rank and of world size, so
+    a test split binarized once gives the same lines everywhere. Runs the gather kernel over the set, `chunk` images a launch."""
+    from . import kernels as K
+    host, _ = device_storage(images)
+    N = int(host.shape[0])
+    chw = (host.shape[3], host.shape[1], host.shape[2]) if channels_last else tuple(host.shape[1:])
+    aug = K.feed_aug(aug_seed(seed), 'binarize', fixed=True)
+    out = torch.empty((N,) + tuple(chw), dtype=torch.uint8)
+    table = host.to(torch.device('cuda', torch.cuda.current_device()))
+    for base in range(0, N, int(chunk)):
+        n = min(int(chunk), N - base)
+        x = K.batch_gather_aug(table, channels_last, torch.empty((n,) + tuple(chw), dtype=torch.float32, device=table.device), aug, base=base)
+        out[base:base + n] = x.to(torch.uint8).cpu()
+    return out
+
+
 class DeviceDataset:
     """N images in device memory; the batch of global step s is rows indices(s)[lo:hi] of it, gathered by one HIP launch.
 
@@ -237,9 +288,13 @@ class DeviceDataset:
     and `indices` then count micro-batches, `step_indices` / `step_epoch` optimizer steps). A training step gathers through (index table,
     cursor) and advances the cursor as its last launch; before a step that
     begins a new epoch the host replaces the index table with a copy ordered on the step's stream (`before_step`), so a captured graph
-    keeps the addresses it baked in. Host-side queries (`indices`, sizes) need no GPU; device memory is taken on first use."""
+    keeps the addresses it baked in. Host-side queries (`indices`, sizes) need no GPU; device memory is taken on first use.
 
-    def __init__(self, images, batch_size, seed, rank=0, world=1, device=None, channels_last=False):
+    augment: a FeedAugment, or None. With one, `gather` and `batch` augment the batch in the gather launch, from noise that is a function
+    of (aug_seed(seed), cursor, place in the global batch, element); `batches` and `first_batches`, which read the set in storage order
+    for evaluation and recalibration, apply the per-image fixed binarization (`binarize_fixed`) when it binarizes, and nothing else."""
+
+    def __init__(self, images, batch_size, seed, rank=0, world=1, device=None, channels_last=False, augment=None):
         from .dist import shard_batch
         images = torch.as_tensor(images)
         if images.dim() != 4:
@@ -251,6 +306,9 @@ class DeviceDataset:
         self.N = int(images.shape[0])
         self.chw = (images.shape[3], images.shape[1], images.shape[2]) if channels_last else tuple(images.shape[1:])
         self.seed, self.rank, self.world, self.device = int(seed), int(rank), int(world), device
+        self.augment = augment if augment else None   # (a FeedAugment with nothing on is no augmentation)
+        if self.augment is not None and self.augment.dequantize and self.kind != 'uint8':
+            raise ValueError("dequantize needs 8-bit data: this image set is kept as float32 (not every value is k/255)")
         self.batch_size = None if batch_size is None else int(batch_size)
         if self.batch_size is not None:
             if self.batch_size < 1 or self.N < self.batch_size:
@@ -363,8 +421,25 @@ class DeviceDataset:
     def gather(self, out):
         """This rank's batch at the device cursor into `out` (one launch, capturable)."""
         from . import kernels as K
+        if self.augment is not None:
+            return K.batch_gather_aug(self.table, self.channels_last, out, self._aug(), index=self.index, cursor=self.cursor,
+                                      steps_per_epoch=self.steps_per_epoch, global_batch=self.batch_size, lo=self.lo)
         return K.batch_gather(self.table, self.channels_last, out, index=self.index, cursor=self.cursor,
                               steps_per_epoch=self.steps_per_epoch, global_batch=self.batch_size, lo=self.lo)
+
+    def _aug(self, fixed=False):
+        """The kernel's description of this set's augmentation; fixed: the per-image binarization alone (storage-order reads)."""
+        from . import kernels as K
+        if fixed:
+            return K.feed_aug(aug_seed(self.seed), 'binarize', fixed=True)
+        return K.feed_aug(aug_seed(self.seed), self.augment.mode, hflip=self.augment.hflip)
+
+    def _in_order(self, n, base):
+        """n images from image `base` on in storage order (fixed-binarized when the set binarizes)."""
+        from . import kernels as K
+        if self.augment is not None and self.augment.binarize:
+            return K.batch_gather_aug(self._dev(), self.channels_last, self.new_batch(n), self._aug(fixed=True), base=base)
+        return K.batch_gather(self._dev(), self.channels_last, self.new_batch(n), base=base)
 
     def advance(self):
         """The step is complete: cursor += 1 (one launch, capturable; the last of a step, so an abandoned step does not move it)."""
@@ -376,22 +451,24 @@ class DeviceDataset:
         from . import kernels as K
         self._load_index(self.epoch_of(step))
         pos = (int(step) - 1) % self.steps_per_epoch
-        return K.batch_gather(self.table, self.channels_last, self.new_batch(), index=self.index[pos * self.batch_size:(pos + 1) * self.batch_size],
+        index = self.index[pos * self.batch_size:(pos + 1) * self.batch_size]
+        if self.augment is not None:   # the noise of the cursor value that step reads: step - 1 completed micro-batches
+            return K.batch_gather_aug(self.table, self.channels_last, self.new_batch(), self._aug(), index=index, steps_per_epoch=1,
+                                      global_batch=self.batch_size, lo=self.lo, position=int(step) - 1)
+        return K.batch_gather(self.table, self.channels_last, self.new_batch(), index=index,
                               steps_per_epoch=1, global_batch=self.batch_size, lo=self.lo)
 
     def batches(self, n):
         """Consecutive device batches of n images in storage order, the last one short."""
-        from . import kernels as K
-        table = self._dev()
         for base in range(0, self.N, int(n)):
-            yield K.batch_gather(table, self.channels_last, self.new_batch(min(int(n), self.N - base)), base=base)
+            yield self._in_order(min(int(n), self.N - base), base)
 
 
 def first_batches(images, n_batches, batch_size, channels_last=False):
     """The first n_batches * batch_size images of a training set in STORED order, as float32 NCHW batches of batch_size: what BatchNorm
     recalibration (recalibrate.py) runs the averaged weights on. The same on every rank and at every world size; no loader, cursor or
     generator is consumed. images: a host tensor as `image_table` returns it (float NCHW; uint8 NCHW, or uint8 NHWC with channels_last:
-    a value means v / 255, the gather's rule), or a DeviceDataset, whose HBM table is read (one gather launch per batch). A set shorter
+    a value means v / 255, the gather's rule), or a DeviceDataset, whose HBM table is read (one gather launch per batch; a set that binarizes gives its fixed binarization). A set shorter
     than n_batches * batch_size stops at its last whole batch; ValueError when it does not fill one. -> a list of batches."""
     n_batches, batch_size = int(n_batches), int(batch_size)
     if n_batches < 1 or batch_size < 1:
@@ -401,9 +478,7 @@ def first_batches(images, n_batches, batch_size, channels_last=False):
     if whole < 1:
         raise ValueError("%d images do not fill one batch of %d" % (N, batch_size))
     if isinstance(images, DeviceDataset):
-        from . import kernels as K
-        table = images._dev()
-        return [K.batch_gather(table, images.channels_last, images.new_batch(batch_size), base=i * batch_size) for i in range(whole)]
+        return [images._in_order(batch_size, i * batch_size) for i in range(whole)]
     out = []
     for i in range(whole):
         x = torch.as_tensor(images[i * batch_size:(i + 1) * batch_size])

@@ -535,6 +535,9 @@ def build_eval_parser():
                    help="the images searched: key 'data', uint8 or float (N, C, H, W); default: a seeded synthetic set")
     p.add_argument('--nn-table-size', type=int, default=4096, dest='nn_table_size', metavar='N',
                    help='images of the synthetic table (drawn from seed + 1) when there is no --nn-table')
+    # (--binarize is a flag of build_parser: here it gives the evaluation images their fixed binarization, data.binarize_fixed)
+    p.add_argument('--binarize-seed', type=int, default=None, dest='binarize_seed', metavar='S',
+                   help="the seed of --binarize's fixed binarization (default: the one noted in --checkpoint's 'augment' record, else 0)")
     return p
 
 
@@ -550,6 +553,16 @@ def _nn_table_shape(path):
 def parse_eval_args(argv=None):
     p = build_eval_parser()
     args = p.parse_args(argv)
+    if args.hflip or args.dequantize:
+        p.error('--hflip and --dequantize augment training batches: evaluation has none (--binarize fixes a binarization of the images)')
+    # here --binarize is about the evaluation images, not about a device-fed training run: kept apart from the trainer's flag
+    args.eval_binarize, args.binarize = args.binarize, False
+    if args.eval_binarize:
+        from .experiment.experiment_manager import DATASETS
+        if (args.likelihood or DATASETS[args.dataset_name][2]) != 'bernoulli':
+            p.error('--binarize makes 0/1 images: it needs --likelihood bernoulli')
+    elif args.binarize_seed is not None:
+        p.error('--binarize-seed needs --binarize')
     if args.recons and not args.img_dir:
         p.error('--recons needs --img-dir DIR: the picture is written there')
     if args.latent_stats and not args.ll:
@@ -652,15 +665,16 @@ def main(argv=None):
         raise SystemExit('--ema needs --checkpoint FILE: the averaged weights are read from the file')
     exp = LVAEExperiment(args=args)
     model = exp.model
+    ck = None
     if args.checkpoint:
         from .checkpoint import load_checkpoint, load_ema_weights
         if args.ema:
             try:
-                load_ema_weights(args.checkpoint, model)
+                ck = load_ema_weights(args.checkpoint, model)
             except ValueError as e:
                 raise SystemExit(str(e))
         else:
-            load_checkpoint(args.checkpoint, model)
+            ck = load_checkpoint(args.checkpoint, model)
     if args.img_dir:
         os.makedirs(args.img_dir, exist_ok=True)
     temperature = None if args.temperature is None else (args.temperature[0] if len(args.temperature) == 1 else args.temperature)
@@ -672,6 +686,13 @@ def main(argv=None):
             data = torch.from_numpy(np.load(args.data_npz)['data']).float()
         else:
             data = synthetic_batch(exp, args.n_test, gen)
+        if args.eval_binarize:   # before any output: one binarization per (seed, image number), the one the run's test lines saw
+            from .checkpoint import augment_record
+            from .data import binarize_fixed
+            seed = args.binarize_seed if args.binarize_seed is not None else int((augment_record(ck) or {}).get('seed', 0))
+            data = binarize_fixed(data, seed).float()
+            print('evaluation images binarized: fixed, seed %d' % seed)
+    del ck
     if args.ll:
         bs = args.test_batch_size
         lat = None

@@ -92,6 +92,15 @@ def build_parser():
                    help='keep the training set (and the test split) in device memory and gather every batch inside the step; the data '
                         'order is then a function of --seed and the step, so runs with a data set repeat and --resume continues exactly. '
                         'With a data set (-d) or --data-npz; not with --synthetic')
+    p.add_argument('--binarize', action='store_true',
+                   help='with --device-data and the bernoulli likelihood: dynamic binarization, every grey pixel drawn afresh as Bernoulli(value) '
+                        'each time the gather visits it, inside the gather launch; test, data-dependent-init and recalibration images get one fixed '
+                        'binarization per image (a function of --seed and the image number)')
+    p.add_argument('--hflip', action='store_true',
+                   help='with --device-data: mirror each training image left-right with probability 1/2, inside the gather launch')
+    p.add_argument('--dequantize', action='store_true',
+                   help='with --device-data, 8-bit data and the gaussian likelihood: train on (b + u) / 256 with u uniform in (0, 1), added inside '
+                        'the gather launch')
     p.add_argument('--ema-decay', type=_ema_decay, default=0.0, dest='ema_decay', metavar='D',
                    help='keep an exponential moving average of the weights inside the optimizer step (decay ramps up as min(D, (1+n)/(10+n))); '
                         'test and log-likelihood passes then use the averaged weights and checkpoints carry them. 0: off')
@@ -171,6 +180,16 @@ class LVAEExperiment:
         if getattr(args, 'device_data', False) and args.synthetic:
             raise SystemExit("--device-data feeds the step from a data set kept in device memory; --synthetic has none "
                              "(use --device-data with -d DATASET or --data-npz FILE)")
+        aug = [f for f in ('binarize', 'hflip', 'dequantize') if getattr(args, f, False)]
+        if aug and not getattr(args, 'device_data', False):
+            raise SystemExit("--%s augments the batch inside the device-fed gather: it needs --device-data" % aug[0])
+        if 'binarize' in aug and 'dequantize' in aug:
+            raise SystemExit("--binarize and --dequantize exclude each other: one makes 0/1 pixels, the other continuous ones")
+        likelihood = args.likelihood if args.likelihood is not None else DATASETS[args.dataset_name][2]
+        if 'binarize' in aug and likelihood != 'bernoulli':
+            raise SystemExit("--binarize makes 0/1 images: it needs --likelihood bernoulli, not %s" % likelihood)
+        if 'dequantize' in aug and likelihood != 'gaussian':
+            raise SystemExit("--dequantize needs --likelihood gaussian, not %s: the discretized heads need the k/255 grid" % likelihood)
         if getattr(args, 'lr_schedule', 'constant') != 'constant' and args.lr_decay_steps <= 0:
             raise SystemExit("--lr-schedule %s needs --lr-decay-steps > 0" % args.lr_schedule)
         if getattr(args, 'lr_min', 0.0) > args.lr:
@@ -227,6 +246,9 @@ class LVAEExperiment:
             s += ',iw{}'.format(args.iw_train_samples)
         if getattr(args, 'accum_steps', 1) > 1:
             s += ',acc{}'.format(args.accum_steps)
+        for flag, word in (('binarize', ',binarize'), ('hflip', ',hflip'), ('dequantize', ',dequant')):
+            if getattr(args, flag, False):
+                s += word
         s += ',{}'.format(args.nonlin)
         if args.free_bits > 0:
             s += ',freeb={}'.format(args.free_bits)
@@ -263,7 +285,21 @@ class LVAEExperiment:
         model.iw_train_samples = getattr(a, 'iw_train_samples', 1)   # (noted in checkpoints: checkpoint.save_checkpoint)
         model.accum_steps = getattr(a, 'accum_steps', 1)             # (likewise)
         model.ema_bn_batches = getattr(a, 'ema_bn_batches', 0)       # (likewise, when it is not 0)
+        model.augment = self.augment_record(a)                        # (likewise, when there is one)
         return model
+
+    @staticmethod
+    def feed_augment(args):
+        """The data.FeedAugment of --binarize / --hflip / --dequantize; None without any."""
+        from ..data import FeedAugment
+        aug = FeedAugment(getattr(args, 'binarize', False), getattr(args, 'hflip', False), getattr(args, 'dequantize', False))
+        return aug if aug else None
+
+    @classmethod
+    def augment_record(cls, args):
+        """What a checkpoint notes under 'augment': the FeedAugment's record and the data seed its noise comes from; None without any."""
+        aug = cls.feed_augment(args)
+        return None if aug is None else dict(aug.record(), seed=int(args.seed))
 
     @staticmethod
     def _make_schedule(args):

@@ -1940,24 +1940,54 @@ def counter_advance_unless(counter, by, flag):
     call('lvae_counter_advance_unless', counter.data_ptr(), int(by), ptr(flag, (torch.int32,)), stream_ptr())
 
 
-def batch_gather(table, channels_last, out, index=None, cursor=None, steps_per_epoch=0, global_batch=0, lo=0, base=0):
-    """out (n, C, H, W) float32 <- n images of `table` (uint8 (N,C,H,W), uint8 (N,H,W,C) with channels_last, or float32 (N,C,H,W)).
-    With `index` (device int32 [steps_per_epoch * global_batch]) row r is image index[(cursor[0] % steps_per_epoch) * global_batch + lo + r]
-    (`cursor`: device int64[1] of completed steps, None = position 0); without it, image base + r. uint8 -> float32 as v / 255."""
+def _batch_gather_args(name, table, channels_last, out, index, steps_per_epoch, global_batch):
+    """The checks batch_gather and batch_gather_aug share -> (N, C, H, W, n)."""
     if table.dim() != 4 or table.dtype not in (torch.uint8, torch.float32) or not table.is_contiguous():
-        raise _C.LvaeHipError("batch_gather: the image table must be a contiguous 4-d uint8 or float32 tensor")
+        raise _C.LvaeHipError("%s: the image table must be a contiguous 4-d uint8 or float32 tensor" % name)
     N = table.shape[0]
     Cn, H, W = (table.shape[3], table.shape[1], table.shape[2]) if channels_last else tuple(table.shape[1:])
     n = out.shape[0]
     if out.dtype != torch.float32 or tuple(out.shape) != (n, Cn, H, W) or not out.is_contiguous():
-        raise _C.LvaeHipError("batch_gather: out must be contiguous float32 (n, %d, %d, %d), got %s %s" % (Cn, H, W, out.dtype,
-                                                                                                          tuple(out.shape)))
+        raise _C.LvaeHipError("%s: out must be contiguous float32 (n, %d, %d, %d), got %s %s" % (name, Cn, H, W, out.dtype,
+                                                                                                tuple(out.shape)))
     if index is not None and index.numel() != int(steps_per_epoch) * int(global_batch):
-        raise _C.LvaeHipError("batch_gather: the index table has %d entries, an epoch %d x %d" % (index.numel(), steps_per_epoch,
-                                                                                                 global_batch))
+        raise _C.LvaeHipError("%s: the index table has %d entries, an epoch %d x %d" % (name, index.numel(), steps_per_epoch,
+                                                                                       global_batch))
+    return N, Cn, H, W, n
+
+
+def batch_gather(table, channels_last, out, index=None, cursor=None, steps_per_epoch=0, global_batch=0, lo=0, base=0):
+    """out (n, C, H, W) float32 <- n images of `table` (uint8 (N,C,H,W), uint8 (N,H,W,C) with channels_last, or float32 (N,C,H,W)).
+    With `index` (device int32 [steps_per_epoch * global_batch]) row r is image index[(cursor[0] % steps_per_epoch) * global_batch + lo + r]
+    (`cursor`: device int64[1] of completed steps, None = position 0); without it, image base + r. uint8 -> float32 as v / 255."""
+    N, Cn, H, W, n = _batch_gather_args('batch_gather', table, channels_last, out, index, steps_per_epoch, global_batch)
     call('lvae_batch_gather_f32', ptr(table), _C.FEED_U8 if table.dtype == torch.uint8 else _C.FEED_F32, int(bool(channels_last)), N, Cn,
          H, W, ptr(index, (torch.int32,)), ptr(cursor, (torch.int64,)), int(steps_per_epoch), int(global_batch), int(lo), int(base), n,
          ptr(out, (torch.float32,)), stream_ptr())
+    return out
+
+
+AUG_MODES = {None: _C.AUG_NONE, 'none': _C.AUG_NONE, 'binarize': _C.AUG_BINARIZE, 'dequantize': _C.AUG_DEQUANTIZE}
+
+
+def feed_aug(seed, mode=None, hflip=False, fixed=False, position=0):
+    """An lvae_feed_aug: mode None | 'binarize' | 'dequantize', rows mirrored at random with hflip, the per-image `fixed` noise
+    (binarize_fixed), and the position that stands in for the cursor when a call has none."""
+    if mode not in AUG_MODES:
+        raise ValueError("feed augmentation mode %r (one of None, 'binarize', 'dequantize')" % (mode,))
+    return _C.FeedAug(int(seed) & (2 ** 64 - 1), int(position), AUG_MODES[mode], int(bool(hflip)), int(bool(fixed)))
+
+
+def batch_gather_aug(table, channels_last, out, aug, index=None, cursor=None, steps_per_epoch=0, global_batch=0, lo=0, base=0, position=0):
+    """batch_gather with the batch augmented in the same launch (lvae_batch_gather_aug_f32). aug: a `feed_aug` (its own position is
+    replaced by `position`): Bernoulli draws of every pixel ('binarize'), uniform noise below one 8-bit step ('dequantize', uint8
+    tables), rows mirrored in W (hflip). The noise is a pure function of (aug.seed, cursor[0] or `position`, lo + r, element), or with
+    aug.fixed / without an index table of (aug.seed, image number, element): the same call gives the same batch, eager or captured."""
+    N, Cn, H, W, n = _batch_gather_args('batch_gather_aug', table, channels_last, out, index, steps_per_epoch, global_batch)
+    a = _C.FeedAug(aug.seed, int(position), aug.mode, aug.hflip, aug.fixed)
+    call('lvae_batch_gather_aug_f32', ptr(table), _C.FEED_U8 if table.dtype == torch.uint8 else _C.FEED_F32, int(bool(channels_last)), N,
+         Cn, H, W, ptr(index, (torch.int32,)), ptr(cursor, (torch.int64,)), int(steps_per_epoch), int(global_batch), int(lo), int(base), n,
+         ptr(out, (torch.float32,)), C.byref(a), stream_ptr())
     return out
 
 

@@ -40,23 +40,33 @@ def image_table(dataset):
     return dataset.data, True
 
 
+def fixed_binarized(exp, images, channels_last=False):
+    """--binarize: a host image set with its one fixed binarization per image (data.binarize_fixed: a function of --seed and the image's
+    number in `images`), as float 0/1 NCHW; without the flag, `images` as they are. -> (images, channels_last)."""
+    if not getattr(exp.args, 'binarize', False):
+        return images, channels_last
+    from .data import binarize_fixed
+    return binarize_fixed(images, exp.args.seed, channels_last=channels_last).float(), False
+
+
 def test_batches(exp, loader, npz, rank, world, on_device=False):
     """A callable returning this rank's shard of the test set as an iterable of NCHW batches, or None when there is no test split
     (DatasetLoader.test, a 'test' key of --data-npz, or --synthetic-test N fixed seeded images). on_device (--device-data): the shard is
-    kept in device memory and the batches are gathered from it (data.DeviceDataset.batches)."""
+    kept in device memory and the batches are gathered from it (data.DeviceDataset.batches). Under --binarize the whole split gets its
+    fixed binarization first, before it is cut over the ranks: the test lines are the same at every world size."""
     args = exp.args
     bs = args.test_batch_size
     if loader is not None and getattr(loader, 'test', None) is not None:
         if on_device:
             # the same images per rank as below: every test batch is split over the ranks, in batches of one rank's part of a full one
-            imgs, channels_last = image_table(loader.test.dataset)
+            imgs, channels_last = fixed_binarized(exp, *image_table(loader.test.dataset))
             mine = torch.cat([_shard(imgs[i:i + bs], rank, world) for i in range(0, imgs.shape[0], bs)])
             per = max(1, _shard(imgs[:bs], rank, world).shape[0])
             ds = DeviceDataset(mine, None, args.seed, device=exp.device, channels_last=channels_last)
             return lambda: ds.batches(per)
         return lambda: (xs for xs in (_shard(b[0], rank, world) for b in loader.test) if xs.shape[0])
     if npz is not None and 'test' in npz:
-        data = _shard(torch.from_numpy(npz['test']).float(), rank, world)
+        data = _shard(fixed_binarized(exp, torch.from_numpy(npz['test']).float())[0], rank, world)
     elif args.synthetic and args.synthetic_test > 0:
         data = _shard(synthetic_batch(exp, args.synthetic_test, torch.Generator().manual_seed(args.seed + 7919)), rank, world)
     else:
@@ -89,6 +99,8 @@ def recal_batches(exp, loader, data, feed):
         src = torch.cat([synthetic_batch(exp, args.batch_size, gen) for _ in range(n)])
     if (src.N if feed is not None else int(src.shape[0])) < args.batch_size:
         raise SystemExit('--ema-bn-batches: the training set does not fill one batch of %d' % args.batch_size)
+    if feed is None and getattr(args, 'binarize', False):   # the images first_batches will read, fixed-binarized (a feed does that itself)
+        src, channels_last = fixed_binarized(exp, src[:n * args.batch_size], channels_last)
     return lambda: first_batches(src, n, args.batch_size, channels_last)
 
 
@@ -161,6 +173,10 @@ def main(argv=None):
         from .checkpoint import accum_steps_record
         if rank == 0 and accum_steps_record(ck) != args.accum_steps:
             print('warning: %s was written with --accum-steps %d; continuing with %d' % (args.resume, accum_steps_record(ck), args.accum_steps))
+        from .checkpoint import augment_record
+        if rank == 0 and augment_record(ck) != exp.augment_record(args):
+            print('warning: %s was written with the feed augmentation %s; continuing with %s' % (args.resume, augment_record(ck),
+                                                                                              exp.augment_record(args)))
         del ck
     model.noise.seed ^= rank * 0x9E3779B9
     model.train()
@@ -177,13 +193,16 @@ def main(argv=None):
             raise SystemExit('--batch-size must be divisible by the world size')
         # the whole training set in device memory; the step gathers its own batch, in an order that is a function of (--seed, step)
         imgs, channels_last = image_table(loader.train.dataset) if loader is not None else (data, False)
-        feed = DeviceDataset(imgs, args.batch_size, args.seed, rank=rank, world=world, device=exp.device, channels_last=channels_last)
+        # (--binarize / --hflip / --dequantize: the gather augments the batch it forms)
+        feed = DeviceDataset(imgs, args.batch_size, args.seed, rank=rank, world=world, device=exp.device, channels_last=channels_last,
+                             augment=exp.feed_augment(args))
     recal = recal_batches(exp, loader, data, feed)     # --ema-bn-batches: what the averaged weights' BatchNorm statistics are re-estimated on
     sched = TrainSchedule.from_args(args, tests is not None)
     if args.simple_data_dependent_init and not args.resume:
         # experiment_manager.py:61-72: the first batch_size training images (parity unpinned, see init.py)
         from .init import data_dependent_init
         x0 = loader.train.dataset.tensors[0][:args.batch_size] if loader is not None else data[:args.batch_size] if data is not None else synthetic_batch(exp, args.batch_size, torch.Generator().manual_seed(args.seed))
+        x0 = fixed_binarized(exp, x0)[0]               # --binarize: the init sees 0/1 images, as training will
         n = data_dependent_init(model, x0.to(exp.device))
         if rank == 0:
             print('data-dependent init: %d convolutions rescaled' % n)
