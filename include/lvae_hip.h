@@ -959,6 +959,46 @@ int lvae_nn_l2_f32(const float* queries, int32_t Q, const void* table, int32_t t
                    int32_t k, int32_t* index_out, float* dist_out, void* workspace, size_t workspace_bytes, void* stream);
 
 /* ------------------------------------------------------------------------------------------------------------
+ * Image quality of reconstructions: mean squared error, PSNR and SSIM per image (csrc/image_quality.hip; quality.ImageQuality).
+ * Evaluation only. The reference has nothing comparable; the yardstick is the published SSIM definition (Wang, Bovik, Sheikh &
+ * Simoncelli 2004) evaluated in float64 (tests/image_quality_ref.py).
+ * ---------------------------------------------------------------------------------------------------------- */
+/* a is the reference image set, b the one judged: fp32, N images of C channels (1 <= C <= 4) and H x W pixels (H, W >= 11), each NCHW
+ * contiguous (`*_nhwc` = 0, `*_ld` ignored) or channel-last with a pixel stride of `*_ld` floats (`*_ld` = 0 means C; `*_ld` > C reads a
+ * view such as the first C of 2C channels without a copy). Only 4-byte alignment is asked of a and b.
+ * mask: NULL, or [N][H][W] bytes; a pixel is COUNTED when (mask != 0) == (count_where != 0). With mask == NULL every pixel is counted.
+ * clamp != 0: both images are clamped to [0, data_range] before anything else (x < 0 ? 0 : x > R ? R : x, so a NaN stays a NaN).
+ * out [N][3] per image:
+ *   mse      the mean over counted pixels and all channels of (a - b)^2: the difference taken first, accumulated in fp32 in one fixed
+ *            order per (C, H, W). Uncounted pixels do not enter, so a NaN under the mask changes no bit of it. NaN when nothing is counted.
+ *   psnr_db  10 log10(data_range^2 / mse) (formed in double from the fp32 mse, rounded to fp32); +inf when mse == 0, NaN when mse is.
+ *   ssim     11 x 11 Gaussian window, sigma 1.5, the 121 weights normalised in double on the host and rounded to fp32; "valid" positions
+ *            only, (H - 10)(W - 10) per channel; C1 = (0.01 R)^2, C2 = (0.03 R)^2. Per position, with x_c the window's centre pixel,
+ *              mu = x_c + sum w (x - x_c)     var = sum w (x - mu)^2     cov = sum w (a - mu_a)(b - mu_b)
+ *              ssim = ((2 (mu_a mu_b) + C1)(2 cov + C2)) / (((mu_a^2 + mu_b^2) + C1)((var_a + var_b) + C2))
+ *            every product and sum of the ratio rounded separately. The second moments are centred on the window's own means, never
+ *            formed as E[x^2] - mu^2, and the mean is taken about the centre pixel, so a constant window has mu == x_c and variance 0.0f
+ *            exactly, and a == b bit for bit gives ssim == 1.0f, mse == 0.0f, psnr == +inf. The mean runs over channels and over the
+ *            positions whose CENTRE pixel is counted; the windows themselves read every pixel they cover, counted or not (a NaN under
+ *            the mask reaches the windows that cover it). NaN when no centre is counted.
+ * An image's three outputs depend on its own pixels, C, H, W, its mask and the flags alone: not on N, its place in the batch, the storage
+ * order, ld or alignment. One workgroup per (32 x 32 tile of positions, channel, image) reads its 42 x 42 pixels into LDS; its partial
+ * sums and counts go to workspace and a second launch adds them per image in (channel, tile) order. No atomics, no host wait.
+ * workspace: lvae_image_quality_workspace(N, C, H, W) bytes (0 for sizes outside the limits), 8-byte aligned.
+ * Nothing is launched or written on an error: LVAE_EINVAL for a null a, b or out, N <= 0, C outside [1, 4], H or W < 11 (or H, W > 32768),
+ * a non-zero ld < C, a non-finite or non-positive data_range; LVAE_EWORKSPACE for a missing or short workspace; LVAE_EALIGN for a
+ * workspace off 8 bytes.
+ * lvae_image_quality_fold_f64 adds a batch's [N][3] rows to sums (device double [5], 8-byte aligned), in ascending image order, each fp32
+ * value widened exactly: sums[0] += N, [1] += mse, [2] += psnr of the images whose psnr is not +inf, [3] += the count of images with
+ * mse == 0, [4] += ssim. A NaN is added as it is: it shows in the mean. One workgroup, fixed order, so eager and replayed runs agree bit
+ * for bit. Null pointer or N <= 0: LVAE_EINVAL; sums off 8 bytes: LVAE_EALIGN. */
+size_t lvae_image_quality_workspace(int32_t N, int32_t C, int32_t H, int32_t W);
+int lvae_image_quality_f32(const float* a, int32_t a_nhwc, int64_t a_ld, const float* b, int32_t b_nhwc, int64_t b_ld, const uint8_t* mask,
+                           int32_t count_where, int32_t N, int32_t C, int32_t H, int32_t W, float data_range, int32_t clamp, float* out,
+                           void* workspace, size_t workspace_bytes, void* stream);
+int lvae_image_quality_fold_f64(const float* per_image, int32_t N, double* sums, void* stream);
+
+/* ------------------------------------------------------------------------------------------------------------
  * Optimiser and norms over the flat parameter arena — torch.optim.Adamax at experiment_manager.py:76-81 and the
  * L2 loop at experiment_manager.py:346-350.
  * ---------------------------------------------------------------------------------------------------------- */

@@ -239,6 +239,9 @@ SIGNATURES = {
     'lvae_latent_stats_workspace': (_Z, [_I, _I, _I]),
     'lvae_latent_stats_fold_f32': (C.c_int, [_P, _I, _P, _I, _I, _I, _P, _P, _Z, _P]),
     'lvae_latent_stats_finalize_f64': (C.c_int, [_P, _L, _L, C.c_double, C.c_double, _P, _P, _P]),
+    'lvae_image_quality_workspace': (_Z, [_I, _I, _I, _I]),
+    'lvae_image_quality_f32': (C.c_int, [_P, _I, _L, _P, _I, _L, _P, _I, _I, _I, _I, _I, _F, _I, _P, _P, _Z, _P]),
+    'lvae_image_quality_fold_f64': (C.c_int, [_P, _I, _P, _P]),
     'lvae_summary_fold_f64': (C.c_int, [_P, _P, _P, _P, _P, _P, _P, _P, _I, _P, _P]),
     'lvae_summary_take_f64': (C.c_int, [_P, _I, _P, _P]),
     'lvae_micro_fold_f64': (C.c_int, [_P, _P, _P, _P, _P, _P, _P, _P, _I, _I, _P, _P, _P, _P]),

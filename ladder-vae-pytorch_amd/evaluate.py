@@ -17,6 +17,8 @@ the absent boilr.eval.BaseOfflineEvaluator / VAEExperimentManager.test_procedure
     and the images completed under it by the pseudo-Gibbs chain (LadderVAE.inpaint);
   * `nearest_neighbours(model, table, queries, k, space)` — query images beside their nearest table images, in the pixels or in the latents
     of the top k layers (neighbours.py), and how close samples lie to the table against how close held-out images do;
+  * `reconstruction_quality(model, batches)` and `quality_ladder(model, batches, temperature)` — mse, PSNR and SSIM of reconstructions,
+    and of images rebuilt from the posterior means of their top k layers for every k, measured on the device (quality.py);
   * `image_pass(model, nrows, x, step)` — the trainer's pictures (--ts-img-every): a grid of prior samples and a grid of input /
     reconstruction pairs, formed on the device (images.py), on a noise stream of their own, leaving training untouched.
 
@@ -39,6 +41,11 @@ CLI: python -m lvae_amd.evaluate --synthetic --ll --ll-samples 100 --ps --layer-
      (12, K); with --img-dir DIR/nn_<...>.png (one row per query). One line: neighbours.closeness_summary over 144 samples and up to
      1000 evaluation images. The table is key 'data' of FILE.npz, or N synthetic images drawn from seed + 1.
      --temperature T [T ...] (one value, or one per layer, bottom first) tempers the prior draws of --ps, --cond-samples and --interp.
+     --recons also prints the mean squared error, PSNR and SSIM of the reconstructions of ALL evaluation images; --inpaint's line ends in
+     the PSNR on the missing pixels and the SSIM at missing centres of the initial fill and of the completion; --ll --image-quality ends
+     the test line in PSNR and SSIM (quality.py: all measured on the device).
+     --quality-ladder [--temperature T] prints, for every k from 0 to L, mse, PSNR and SSIM of the images rebuilt from the posterior means
+     of their top k layers with the layers below at the prior (T = 0 by default: its mean), and writes quality_ladder.npy (L + 1, 3).
      --recalibrate-bn data|prior [--recalibrate-batches N] re-estimates the BatchNorm running statistics once, before any output, for the
      weights that were loaded (recalibrate.recalibrate_bn): on the first N (default 20) batches of --batch-size training images, or on N
      train-mode top-down passes from the prior at --temperature (one value). One header line says which.
@@ -63,14 +70,18 @@ def _test_bottom_up(model, x):
     return bu_values, x_nhwc
 
 
-def _elbo_sample(model, bu_values, x_nhwc, zero, latent_stats=None):
+def _elbo_sample(model, bu_values, x_nhwc, zero, latent_stats=None, image_quality=None):
     """One top-down sample of an evaluation pass: noise.begin, top-down pass, crop, likelihood, KL bookkeeping -> (elbo_sep, ll, kl_sep,
     kl_avg), per image. The caller folds them into its running state (iw_online or eval_online: they accumulate in different precisions)
     and then calls model.noise.end(). With latent_stats (a latent.LatentStats) every stochastic layer also folds its p and q parameters
-    into it; the noise drawn is the same either way."""
+    into it; the noise drawn is the same either way. With image_quality (a quality.ImageQuality) the head's mean, or its sample where it has
+    no mean (the order of `reconstructions`), is judged against x and folded into it, both as they lie here: cropped, channel-last, the
+    Gaussian head's mean as the strided view of its parameters (no copy)."""
     model.noise.begin(x_nhwc.device)                 # every sample: same call sites, next RNG step
     out, td = model._topdown(bu_values, latent_stats=latent_stats)
-    ll, _ = model.likelihood(model._crop(out, x_nhwc.shape[1:3]), x_nhwc, model.noise)
+    ll, head = model.likelihood(model._crop(out, x_nhwc.shape[1:3]), x_nhwc, model.noise)
+    if image_quality is not None:
+        image_quality.fold(x_nhwc, head['mean'] if head['mean'] is not None else head['sample'], channel_last=True)
     kl_ln = ops.StackFn.apply(*td['kl'])
     kl_sep, kl_avg, _ = K.kl_bookkeeping_fwd(kl_ln, float(model.free_bits))
     elbo_sep, _ = K.elbo_loss_fwd(ll, kl_sep, zero, 1.0)
@@ -160,22 +171,24 @@ def _bn_recal(model, source):
     return recalibrated(model, source(), step=model.global_step)
 
 
-def _test_sample(model, bu_values, x_nhwc, state, zero, latent_stats=None):
+def _test_sample(model, bu_values, x_nhwc, state, zero, latent_stats=None, image_quality=None):
     """_elbo_sample, folded into the per-image state of a test pass (lvae_eval_online_f32)."""
-    K.eval_online(state, model.n_layers, 1, *_elbo_sample(model, bu_values, x_nhwc, zero, latent_stats))
+    K.eval_online(state, model.n_layers, 1, *_elbo_sample(model, bu_values, x_nhwc, zero, latent_stats, image_quality))
     model.noise.end()
 
 
 class _TestGraphs:
     """The bottom-up pass and one sample of a test batch shape, captured once and replayed for every batch of that shape, in this and in
     later test passes. Static input x and per-image state; a capture stream of its own (so its scratch workspace is its own too).
-    With latent_stats a second sample graph, which also holds the L folds into that object's accumulator, is captured into the same pool:
-    the pass replays it for the first sample of a batch and the plain one for the rest."""
+    With latent_stats and / or image_quality a second sample graph, which also holds the folds into those objects' accumulators (the L folds
+    of the latent statistics, the quality launches), is captured into the same pool: the pass replays it for the first sample of a batch and
+    the plain one for the rest."""
 
-    def __init__(self, model, x, noise, latent_stats=None):
+    def __init__(self, model, x, noise, latent_stats=None, image_quality=None):
         from .noise import PhiloxNoise
         dev = x.device
-        self.noise, self.keep, self.latent_stats = noise, [], latent_stats
+        self.noise, self.keep, self.latent_stats, self.image_quality = noise, [], latent_stats, image_quality
+        hooks = [h for h in (latent_stats, image_quality) if h is not None]
         self.stream = torch.cuda.Stream(device=dev, priority=-1)
         self.stream.wait_stream(torch.cuda.current_stream(dev))
         L = model.n_layers
@@ -189,10 +202,11 @@ class _TestGraphs:
             bu, x_nhwc = _test_bottom_up(model, self.x)
             K.eval_online(self.state, L, 0)
             _test_sample(model, bu, x_nhwc, self.state, self.zero)
-            if latent_stats is not None:   # the folds' scratch grows here too; what this throw-away sample added is taken out again
-                sums = latent_stats.buf.clone()
-                _test_sample(model, bu, x_nhwc, self.state, self.zero, latent_stats)
-                latent_stats.buf.copy_(sums)
+            if hooks:   # the folds' scratch grows here too; what this throw-away sample added is taken out again
+                sums = [h.buf.clone() for h in hooks]
+                _test_sample(model, bu, x_nhwc, self.state, self.zero, latent_stats, image_quality)
+                for h, was in zip(hooks, sums):
+                    h.buf.copy_(was)
                 del sums
             model.noise = noise
             noise.begin(dev)          # its device step counter exists before the capture
@@ -205,10 +219,10 @@ class _TestGraphs:
             with torch.cuda.graph(self.g_sample, pool=self.g_bu.pool(), stream=self.stream, capture_error_mode='thread_local'):
                 _test_sample(model, self.bu, self.x_nhwc, self.state, self.zero)
             self.g_sample_stats = None
-            if latent_stats is not None:
+            if hooks:
                 self.g_sample_stats = torch.cuda.CUDAGraph()
                 with torch.cuda.graph(self.g_sample_stats, pool=self.g_bu.pool(), stream=self.stream, capture_error_mode='thread_local'):
-                    _test_sample(model, self.bu, self.x_nhwc, self.state, self.zero, latent_stats)
+                    _test_sample(model, self.bu, self.x_nhwc, self.state, self.zero, latent_stats, image_quality)
             self.keep.append(K.workspace(0, dev))   # the scratch buffer the captured launches use
 
     def run(self, x, n_samples, totals, L):
@@ -227,7 +241,8 @@ class _TestGraphs:
 
 
 @torch.no_grad()
-def test_pass(model, batches, n_samples, noise=None, process_group=None, use_graph=None, optimizer=None, latent_stats=None, bn_recal=None):
+def test_pass(model, batches, n_samples, noise=None, process_group=None, use_graph=None, optimizer=None, latent_stats=None, bn_recal=None,
+              image_quality=None):
     """The reference's test summaries over an iterable of NCHW image batches (each rank passes ITS shard of the test set): means over images
     and samples of 'elbo/elbo', 'elbo/recons', 'elbo/kl', 'kl_layers/kl_layer_<i>', plus 'elbo/elbo_IW_<S>' when S > 1, and 'n_images'.
 
@@ -244,13 +259,17 @@ def test_pass(model, batches, n_samples, noise=None, process_group=None, use_gra
     parameters into it; the pass ends with its `take()` (a collective, like the all-reduce of the totals) and the result gains the
     'latent/*' counts and 'latent_arrays' (per layer 'kl', 'mu_mean', 'mu_var' as (Z, h, w) arrays). Every other key is bit for bit what the
     pass returns without it: the folds draw no noise and write nothing the pass reads.
+    image_quality: a quality.ImageQuality. The FIRST sample of every batch also judges the head's mean (its sample where the head has no
+    mean) against x and folds mse, PSNR and SSIM into it; the pass ends with its `take()` (a collective) and the result gains the
+    'quality/*' means. Every other key is bit for bit what the pass returns without it, and without it the pass issues exactly the launches
+    it issues otherwise. One first-sample graph holds whichever of latent_stats and image_quality are present.
     bn_recal (--ema-bn-batches; read only on the averaged weights): a callable returning image batches. Inside `swap_ema()` the BatchNorm
     statistics are first recalibrated on them (recalibrate.recalibrated, its noise stream placed at model.global_step), the pass reads the
     recalibrated statistics, and the live ones are back before the weights are; the result gains 'bn_recal/rounds'."""
     if optimizer is not None and getattr(optimizer, 'ema_decay', 0.0) > 0.0:
         with optimizer.swap_ema(), _bn_recal(model, bn_recal) as recal:
             res = test_pass(model, batches, n_samples, noise=noise, process_group=process_group, use_graph=use_graph,
-                            latent_stats=latent_stats)
+                            latent_stats=latent_stats, image_quality=image_quality)
         res['weights'] = 'ema'
         if recal is not None:
             res['bn_recal/rounds'] = recal['rounds']
@@ -270,16 +289,18 @@ def test_pass(model, batches, n_samples, noise=None, process_group=None, use_gra
     totals = torch.zeros(5 + L, dtype=torch.float64, device=dev)
     if latent_stats is not None:
         latent_stats.reset()
+    if image_quality is not None:
+        image_quality.reset()
     with eval_mode(model, noise):
         if use_graph:
             plans = model.__dict__.setdefault('_test_graphs', {})
             for x in batches:
                 x = x.to(dev).contiguous().float()
                 key = (tuple(x.shape), id(noise), noise.seed, id(model.pack()), model.compute_dtype,
-                       None if latent_stats is None else id(latent_stats))
+                       None if latent_stats is None else id(latent_stats)) + (() if image_quality is None else (id(image_quality),))
                 plan = plans.get(key)
-                if plan is None or plan.noise is not noise or plan.latent_stats is not latent_stats:
-                    plan = plans[key] = _TestGraphs(model, x, noise, latent_stats)
+                if plan is None or plan.noise is not noise or plan.latent_stats is not latent_stats or plan.image_quality is not image_quality:
+                    plan = plans[key] = _TestGraphs(model, x, noise, latent_stats, image_quality)
                 plan.run(x, n_samples, totals, L)
         else:
             keep = []
@@ -291,7 +312,7 @@ def test_pass(model, batches, n_samples, noise=None, process_group=None, use_gra
                     K.eval_online(state, L, 0)
                     bu, x_nhwc = _test_bottom_up(model, x)
                     for s in range(n_samples):
-                        _test_sample(model, bu, x_nhwc, state, zero, latent_stats if s == 0 else None)
+                        _test_sample(model, bu, x_nhwc, state, zero, latent_stats if s == 0 else None, image_quality if s == 0 else None)
                     if latent_stats is not None:
                         latent_stats.count(x.shape[0])
                     K.eval_totals(state, L, n_samples, totals)
@@ -308,6 +329,8 @@ def test_pass(model, batches, n_samples, noise=None, process_group=None, use_gra
         lat = latent_stats.take(process_group)
         res.update((k, v) for k, v in lat.items() if k.startswith('latent/'))
         res['latent_arrays'] = lat['arrays']
+    if image_quality is not None:
+        res.update((k, v) for k, v in image_quality.take(process_group).items() if k.startswith('quality/'))
     return res
 
 
@@ -413,6 +436,38 @@ def reconstructions(model, x):
         x = x.to(next(model.parameters()).device).contiguous().float()
         out = model(x)
         return x, (out['out_mean'] if out['out_mean'] is not None else out['out_sample'])
+
+
+@torch.no_grad()
+def reconstruction_quality(model, batches):
+    """mse, PSNR and SSIM of `reconstructions` over an iterable of NCHW batches, folded on the device -> ImageQuality.take()'s dict."""
+    from .quality import ImageQuality
+    quality = ImageQuality(next(model.parameters()).device)
+    for x in batches:
+        quality.fold(*reconstructions(model, x))
+    return quality.take()
+
+
+@torch.no_grad()
+def quality_ladder(model, batches, temperature=0.0):
+    """Reconstruction quality as a function of how many top layers come from the posterior: for every k from 0 to L the top k layers take
+    their posterior means and the layers below draw from the prior at `temperature` (0.0, the default: the prior means, so the curve is
+    deterministic): LadderVAE.sample_conditional(x, k, 1, temperature, use_mode=True), batch by batch over `batches` (a sequence of NCHW
+    batches, walked once per k). The likelihood's mean, or its sample where it has none, is judged against x on the device
+    (quality.ImageQuality) -> float64 array (L + 1, 3): the means over images of mse, PSNR (over the images where it is finite) and SSIM."""
+    from .quality import ImageQuality
+    dev = next(model.parameters()).device
+    quality = ImageQuality(dev)
+    rows = np.empty((model.n_layers + 1, 3), dtype=np.float64)
+    with eval_mode(model):
+        for k in range(model.n_layers + 1):
+            for x in batches:
+                x = x.to(dev).contiguous().float()
+                out = model.sample_conditional(x, k, 1, temperature=temperature, use_mode=True)
+                quality.fold(x, out['mean'] if out['mean'] is not None else out['sample'])
+            res = quality.take()
+            rows[k] = res['quality/mse'], res['quality/psnr'], res['quality/ssim']
+    return rows
 
 
 @torch.no_grad()
@@ -524,6 +579,11 @@ def build_eval_parser():
                    help='the first completion at the missing pixels')
     p.add_argument('--inpaint-final', choices=('sample', 'mean'), default='sample', dest='inpaint_final',
                    help="the missing pixels after the last round: the draw, or the likelihood's mean")
+    p.add_argument('--quality-ladder', action='store_true', dest='quality_ladder',
+                   help='mse, PSNR and SSIM of the evaluation images rebuilt from the posterior means of their top k layers, the layers below '
+                        'at the prior (--temperature, one value; default 0: the prior mean), for every k from 0 to the number of layers '
+                        '-> one line per k and quality_ladder.npy (L + 1, 3)')
+    # (--image-quality is a flag of build_parser: here with --ll, PSNR and SSIM after the test line)
     p.add_argument('--nn', action='store_true',
                    help='prior samples and evaluation images beside their nearest table images -> nn_<space>_<samples|heldout>.npy')
     p.add_argument('--nn-k', type=int, default=7, dest='nn_k', metavar='K', help='neighbours per query, 1 to %d' % K.NN_MAX_K)
@@ -567,6 +627,10 @@ def parse_eval_args(argv=None):
         p.error('--recons needs --img-dir DIR: the picture is written there')
     if args.latent_stats and not args.ll:
         p.error('--latent-stats needs --ll: the statistics are folded during the log-likelihood pass')
+    if args.image_quality and not args.ll:
+        p.error('--image-quality needs --ll: the reconstructions are measured during the log-likelihood pass')
+    if args.quality_ladder and args.temperature is not None and len(args.temperature) != 1:
+        p.error('--quality-ladder takes one --temperature for all layers, got %d' % len(args.temperature))
     L = len(args.z_dims)
     if args.cond_layers is None:
         args.cond_layers = list(range(L + 1))
@@ -680,7 +744,7 @@ def main(argv=None):
     temperature = None if args.temperature is None else (args.temperature[0] if len(args.temperature) == 1 else args.temperature)
     if args.recalibrate_bn:   # once, before every output below, for the weights just loaded
         print(_recalibrate_from_args(exp, temperature))
-    if args.ll or args.recons or args.cond_samples or args.interp or args.inpaint or args.nn:
+    if args.ll or args.recons or args.cond_samples or args.interp or args.inpaint or args.nn or args.quality_ladder:
         gen = torch.Generator().manual_seed(args.seed)
         if args.data_npz:
             data = torch.from_numpy(np.load(args.data_npz)['data']).float()
@@ -699,13 +763,20 @@ def main(argv=None):
         if args.latent_stats:
             from .latent import LatentStats, latent_line_suffix, save_npz
             lat = LatentStats(model, exp.device, args.latent_kl_threshold, args.latent_var_threshold)
-        res = test_pass(model, (data[i:i + bs] for i in range(0, data.shape[0], bs)), args.loglikelihood_samples, latent_stats=lat)
+        qual = None
+        if args.image_quality:
+            from .quality import ImageQuality, quality_line_suffix
+            qual = ImageQuality(exp.device)
+        res = test_pass(model, (data[i:i + bs] for i in range(0, data.shape[0], bs)), args.loglikelihood_samples, latent_stats=lat,
+                        image_quality=qual)
         if args.ema:
             res['weights'] = 'ema'
         line = exp.test_log_str(res, model.global_step)
         if lat is not None:
             line += latent_line_suffix(res, lat.kl_threshold, lat.var_threshold)
             save_npz('latent_stats.npz', res['latent_arrays'], lat.kl_threshold, lat.var_threshold, res['n_images'])
+        if qual is not None:
+            line += quality_line_suffix(res)
         print(line)
     if args.ps:
         np.save('prior_samples.npy', prior_samples(model, 64, temperature).cpu().numpy())
@@ -731,6 +802,8 @@ def main(argv=None):
             if args.img_dir:
                 write_png(os.path.join(args.img_dir, 'interp_top%d.png' % k), image_grid(rows.view(-1, *rows.shape[2:]), nt + 2))
     if args.inpaint:  # one row per image: the image, what the model was shown, the completion
+        from .quality import ImageQuality
+        qual = ImageQuality(exp.device)
         n = min(IMG_GRID_N, int(data.shape[0]))
         for j, kind in enumerate(args.inpaint_mask):
             mask = make_mask(kind, args.inpaint_frac, (n,) + tuple(data.shape[2:]), args.seed + j)
@@ -744,9 +817,16 @@ def main(argv=None):
             mse0 = float(((first.cpu()[hidden].double() - truth) ** 2).mean()) if truth.numel() else float('nan')
             mse1 = float(((done.cpu()[hidden].double() - truth) ** 2).mean()) if truth.numel() else float('nan')
             ll_obs = ll_obs.cpu().double()
+            # on the device, over the missing pixels (SSIM: the windows whose centre is missing), means over the images
+            qual.fold(xin, first, mask.to(xin.device), count='missing')
+            q0 = qual.take()
+            qual.fold(xin, done, mask.to(xin.device), count='missing')
+            q1 = qual.take()
             print('inpaint %s (hidden %.3f, %d rounds): mse on the missing pixels %.5g (initial fill) -> %.5g (completion); '
-                  'll_observed %.5g (first round) -> %.5g (last round)'
-                  % (kind, float((~mask).float().mean()), args.inpaint_iters, mse0, mse1, float(ll_obs[0].mean()), float(ll_obs[-1].mean())))
+                  'll_observed %.5g (first round) -> %.5g (last round); PSNR on the missing pixels %.2f dB -> %.2f dB; '
+                  'SSIM at the missing centres %.4f -> %.4f'
+                  % (kind, float((~mask).float().mean()), args.inpaint_iters, mse0, mse1, float(ll_obs[0].mean()), float(ll_obs[-1].mean()),
+                     q0['quality/psnr'], q1['quality/psnr'], q0['quality/ssim'], q1['quality/ssim']))
     if args.nn:  # one row per query: the query, then its K nearest table images, nearest first
         from .data import device_storage
         from .neighbours import closeness_line
@@ -769,6 +849,12 @@ def main(argv=None):
                 rows = res[name]['rows']
                 write_png(os.path.join(args.img_dir, stem + '.png'), image_grid(rows.view(-1, *rows.shape[2:]).contiguous(), 1 + args.nn_k))
         print(closeness_line(args.nn_space, res['summary']))
+    if args.quality_ladder:  # one row per k: how much of an image its top k layers hold
+        bs = args.test_batch_size
+        rows = quality_ladder(model, [data[i:i + bs] for i in range(0, data.shape[0], bs)], 0.0 if temperature is None else temperature)
+        np.save('quality_ladder.npy', rows)
+        for k, (mse, psnr, ssim) in enumerate(rows):
+            print('quality ladder top %d of %d layers: mse %.5g   PSNR %.2f dB   SSIM %.4f' % (k, model.n_layers, mse, psnr, ssim))
     if not args.img_dir:
         return
     # the reference's pictures, after everything above so that the arrays do not depend on --img-dir
@@ -780,6 +866,11 @@ def main(argv=None):
     if args.layer_repr:    # evaluate.py:95-114
         for i, s in enumerate(inspect_layer_repr(model, IMG_GRID_N)):
             write_png(os.path.join(args.img_dir, 'sample_mode_layer%d.png' % i), image_grid(s.contiguous(), IMG_GRID_N))
+    if args.recons:        # after every picture, whose noise draws stay where they were: all evaluation images, not only the 72 shown
+        bs = args.test_batch_size
+        res = reconstruction_quality(model, (data[i:i + bs] for i in range(0, data.shape[0], bs)))
+        print('reconstructions of %d images: mse %.5g   PSNR %.2f dB (of the mean mse: %.2f dB)   SSIM %.4f'
+              % (res['n_images'], res['quality/mse'], res['quality/psnr'], res['quality/psnr_of_mean_mse'], res['quality/ssim']))
 
 
 if __name__ == '__main__':

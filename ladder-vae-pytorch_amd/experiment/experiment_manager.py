@@ -145,6 +145,10 @@ def build_parser():
                         'added to the gradient) or adamw (--wd is decoupled decay: the weights shrink by lr * wd per step)')
     p.add_argument('--betas', type=float, nargs=2, default=[0.9, 0.999], metavar=('B1', 'B2'), help='the moments\' decay rates, for every rule')
     p.add_argument('--opt-eps', type=float, default=1e-8, dest='opt_eps', metavar='E', help='the eps of the update rule, for every rule')
+    p.add_argument('--image-quality', action='store_true', dest='image_quality',
+                   help='every test / log-likelihood pass also measures its reconstructions against the test images on the device (the first '
+                        "sample of every batch: the likelihood's mean, or its sample where it has none): the mean PSNR and SSIM are printed "
+                        "after the test line and --history records the quality/* values")
     p.add_argument('--latent-kl-threshold', type=float, default=0.01, dest='latent_kl_threshold', metavar='T')
     p.add_argument('--latent-var-threshold', type=float, default=0.01, dest='latent_var_threshold', metavar='T')
     return p

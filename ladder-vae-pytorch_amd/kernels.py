@@ -1677,6 +1677,61 @@ def latent_stats_finalize(sums, n_images, kl_threshold, var_threshold, unit_out,
          ptr(layer_out, f64), stream_ptr())
 
 
+IQ_WINDOW = 11   # edge of the SSIM window: the smallest image lvae_image_quality_f32 takes
+
+
+def _iq_src(t, name, channel_last):
+    """(nhwc flag, pixel stride, (N, C, H, W)) of an image set for lvae_image_quality_f32: (N, C, H, W) by shape, or (N, H, W, C) with
+    channel_last; stored NCHW contiguous, or channel-last with a pixel stride of ld >= C floats (an NHWC buffer, its NCHW view, or the
+    first C channels of a wider NHWC buffer). No copy: another storage is an error."""
+    if not torch.is_tensor(t) or t.dim() != 4:
+        raise ValueError("%s: need a 4-d image tensor, got %s" % (name, tuple(t.shape) if torch.is_tensor(t) else type(t).__name__))
+    v = t.permute(0, 3, 1, 2) if channel_last else t
+    N, Cn, H, W = (int(s) for s in v.shape)
+    sn, sc, sh, sw = (int(s) for s in v.stride())
+    if (Cn == 1 or sc == H * W) and sh == W and sw == 1 and (N == 1 or sn == Cn * H * W):
+        return 0, 0, (N, Cn, H, W)
+    if (Cn == 1 or sc == 1) and sw >= Cn and sh == W * sw and (N == 1 or sn == H * W * sw):
+        return 1, sw, (N, Cn, H, W)
+    raise _C.LvaeHipError("%s: neither NCHW contiguous nor channel-last with one pixel stride (shape %s, strides %s)"
+                          % (name, tuple(t.shape), tuple(t.stride())))
+
+
+def image_quality(a, b, mask=None, count_where=1, data_range=1.0, clamp=True, channel_last=False, out=None):
+    """float32 (N, 3) on the device: per image the mse, the PSNR in dB and the SSIM of b judged against a (lvae_image_quality_f32 states
+    the formulas). a, b: float32 image sets of one shape, each in a storage _iq_src takes (they may differ in it). mask: None, or the
+    (N, H, W) uint8 tensor pixel_mask makes; a pixel is counted when (mask != 0) == (count_where != 0). Two launches, no allocation once
+    `out` is given and the scratch buffer of the stream is large enough."""
+    if not (torch.is_tensor(a) and torch.is_tensor(b)) or tuple(a.shape) != tuple(b.shape):
+        raise ValueError("image_quality: the two image sets differ in shape: %s and %s" % (tuple(getattr(a, 'shape', ())), tuple(getattr(b, 'shape', ()))))
+    a_nhwc, a_ld, (N, Cn, H, W) = _iq_src(a, 'a', channel_last)
+    b_nhwc, b_ld, _ = _iq_src(b, 'b', channel_last)
+    if H < IQ_WINDOW or W < IQ_WINDOW:
+        raise ValueError("image_quality: images of %d x %d are smaller than the %d x %d window" % (H, W, IQ_WINDOW, IQ_WINDOW))
+    f32 = (torch.float32,)
+    pa, pb = ptr(a, f32), ptr(b, f32)
+    if mask is not None:
+        _chk_masked(a, mask, N, H, W)
+    if out is None:
+        out = torch.empty((N, 3), dtype=torch.float32, device=a.device)
+    elif tuple(out.shape) != (N, 3) or not out.is_contiguous():
+        raise _C.LvaeHipError("image_quality: out must be a contiguous (%d, 3) tensor, got %s" % (N, tuple(out.shape)))
+    ws = workspace(_C.load().lvae_image_quality_workspace(N, Cn, H, W), a.device)
+    call('lvae_image_quality_f32', pa, a_nhwc, a_ld, pb, b_nhwc, b_ld, ptr(mask, (torch.uint8,)), int(bool(count_where)), N, Cn, H, W,
+         float(data_range), int(bool(clamp)), ptr(out, f32), ws.data_ptr(), ws.numel(), stream_ptr())
+    return out
+
+
+IQ_SUMS = 5   # lvae_image_quality_fold_f64's sums: images, sum mse, sum of the PSNRs that are not +inf, images with mse == 0, sum ssim
+
+
+def image_quality_fold(per_image, sums):
+    """sums: float64 (5,) += the (N, 3) rows of image_quality, in image order. One launch of one workgroup; captured passes replay it."""
+    if per_image.dim() != 2 or per_image.shape[1] != 3 or not per_image.is_contiguous() or sums.numel() != IQ_SUMS or not sums.is_contiguous():
+        raise _C.LvaeHipError("image_quality_fold: rows %s into sums of %d entries" % (tuple(per_image.shape), sums.numel()))
+    call('lvae_image_quality_fold_f64', ptr(per_image, (torch.float32,)), int(per_image.shape[0]), ptr(sums, (torch.float64,)), stream_ptr())
+
+
 SUMMARY_FIXED, SUMMARY_MAX_LAYERS = 8, 64   # slots of lvae_summary_fold_f64's accumulator before the per-layer KLs; the most layers it takes
 
 

@@ -17,6 +17,7 @@ from .evaluate import image_pass, test_pass
 from .experiment.experiment_manager import LVAEExperiment
 from .images import write_png
 from .latent import LatentStats, latent_line_suffix
+from .quality import ImageQuality, quality_line_suffix
 from .schedule import TrainSchedule, checkpoint_path, checkpoints_to_delete
 from .summary import History, TrainSummary, train_line_suffix
 
@@ -218,6 +219,8 @@ def main(argv=None):
     guard_seen = opt.guard.counts() if opt.guard is not None else None   # (after --resume: the file's counts)
     # --latent-stats: the first sample of every test batch also folds each layer's posterior into a device accumulator
     latent = LatentStats(model, exp.device, args.latent_kl_threshold, args.latent_var_threshold) if args.latent_stats and tests is not None else None
+    # --image-quality: the first sample of every test batch is also judged against its image (mse, PSNR, SSIM), summed on the device
+    quality = ImageQuality(exp.device) if args.image_quality and tests is not None else None
     if rank == 0:
         print(exp.run_description)
         print('parameters: %d   world size: %d   per-rank batch: %d' % (sum(p.numel() for p in model.parameters()), world,
@@ -304,11 +307,14 @@ def main(argv=None):
         if n_samples:
             if data is not None and loader is None and feed is None:
                 epoch = step * args.batch_size * accum // data.shape[0]
-            res = test_pass(model, tests(), n_samples, optimizer=opt, latent_stats=latent, bn_recal=recal)   # (--ema-decay: on the averaged weights)
+            # (--ema-decay: on the averaged weights)
+            res = test_pass(model, tests(), n_samples, optimizer=opt, latent_stats=latent, bn_recal=recal, image_quality=quality)
             if rank == 0:
                 line = exp.test_log_str(res, step, epoch)
                 if latent is not None:
                     line += latent_line_suffix(res, latent.kl_threshold, latent.var_threshold)
+                if quality is not None:
+                    line += quality_line_suffix(res)
                 print(line, flush=True)
                 if history is not None:
                     history.write(step, 'test', res, epoch=epoch)
