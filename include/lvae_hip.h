@@ -590,6 +590,28 @@ int lvae_normal_stochastic_bwd_f32(const float* p, int32_t p_bcast, const float*
                                    const float* g_ks, int32_t N, int32_t HW, int32_t Z, int32_t mode,
                                    int32_t analytical_kl, float* dp, float* dq, void* stream);
 
+/* The same core with the posterior given RELATIVE to the prior (csrc/stochastic_residual.hip; the residual normal of NVAE, Vahdat & Kautz
+ * 2020, section 3.2): d [N,HW,2Z] = (dmu | dlv) in the layout of q above, mu_q = mu_p + dmu, logvar_q = logvar_p + dlv. p, p_bcast, eps,
+ * mode, z and the four reductions are as in lvae_normal_stochastic_fwd_f32 (d is required: there is no posterior-free form; kl_spatial may
+ * be NULL). Every quantity is formed from the offset, never from the rounded sum: with s_q = exp(lv_p/2) exp(dlv/2), a = z - mu_p and
+ * u = (z - mu_q) / s_q,
+ *   mode 0: z = (mu_p + dmu) + s_q eps, a = dmu + s_q eps, u = eps;  mode 1: z = mu_p + dmu, a = dmu, u = 0;  mode 2: a = z - mu_p, u = (a - dmu) / s_q
+ *   log p = -a^2 exp(-lv_p)/2 - lv_p/2 - log sqrt(2 pi);  log q = -u^2/2 - (lv_p + dlv)/2 - log sqrt(2 pi)
+ *   analytical KL = (expm1(dlv) - dlv + dmu^2 exp(-lv_p)) / 2;  Monte-Carlo KL = (a^2 exp(-lv_p) - u^2)/2 - dlv/2
+ * q_out [N,HW,2Z] (may be NULL: nothing is written for it) receives (mu_p + dmu | logvar_p + dlv), each rounded once, for the consumers of
+ * absolute posterior parameters (lvae_latent_stats_fold_f32). Sums in a fixed order, no atomics: the same inputs give the same bits. */
+int lvae_normal_stochastic_res_fwd_f32(const float* p, int32_t p_bcast, const float* d, const float* eps, int32_t N,
+                                       int32_t HW, int32_t Z, int32_t mode, int32_t analytical_kl, float* z, float* q_out,
+                                       float* logprob_p, float* logprob_q, float* kl_samplewise, float* kl_spatial,
+                                       void* stream);
+/* Backward of the above; upstream gradients as in lvae_normal_stochastic_bwd_f32 (each may be NULL). z is read in mode 2 only, eps in mode 0
+ * only. Writes dd [N,HW,2Z], the gradient of the offset, and dp [N,HW,2Z], the TOTAL gradient of the prior parameters: their own terms plus
+ * what flows through q = p + d, formed per term on paper (the caller sums dp over N when p was broadcast). */
+int lvae_normal_stochastic_res_bwd_f32(const float* p, int32_t p_bcast, const float* d, const float* eps, const float* z,
+                                       const float* dz, const float* g_lp, const float* g_lq, const float* g_kl,
+                                       const float* g_ks, int32_t N, int32_t HW, int32_t Z, int32_t mode,
+                                       int32_t analytical_kl, float* dp, float* dd, void* stream);
+
 /* The whole block of the low-resolution levels in one launch (csrc/stoch_img.hip), forward: p_params = conv_in_p(x_p),
  * q_params = conv_in_q(x_q), the elementwise core above, out = conv_out(z). Every tensor the one-kernel-per-op form writes is written:
  *   conv_p   : x = x_p [N,H,W,64], y = p_params [N,H,W,2Z], w / bias of conv_in_p. conv_p.w == NULL: the block has no conv_in_p (top layer);

@@ -195,6 +195,8 @@ SIGNATURES = {
     'lvae_colsum_f32': (C.c_int, [_P, _L, _L, _P, _I, _P]),
     'lvae_normal_stochastic_fwd_f32': (C.c_int, [_P, _I, _P, _P, _I, _I, _I, _I, _I, _P, _P, _P, _P, _P, _P]),
     'lvae_normal_stochastic_bwd_f32': (C.c_int, [_P, _I, _P, _P, _P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _P, _P, _P]),
+    'lvae_normal_stochastic_res_fwd_f32': (C.c_int, [_P, _I, _P, _P, _I, _I, _I, _I, _I, _P, _P, _P, _P, _P, _P, _P]),
+    'lvae_normal_stochastic_res_bwd_f32': (C.c_int, [_P, _I, _P, _P, _P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _P, _P, _P]),
     'lvae_stoch_block_ok': (_I, [C.POINTER(StochBlock)]),
     'lvae_stoch_block_workspace': (_Z, [C.POINTER(ConvDesc)]),
     'lvae_stoch_block_prepare_entry': (C.c_int, [C.POINTER(ConvDesc), _P]),

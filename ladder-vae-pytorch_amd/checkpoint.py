@@ -143,6 +143,9 @@ def save_checkpoint(path, model, optimizer=None, summary=None, bn_recal=None):
             ck['grad_guard'] = optimizer.guard.state_dict()
     ck['iw_train_samples'] = int(getattr(model, 'iw_train_samples', 1))   # what the file's run trained on; a resumed run uses its own flag
     ck['accum_steps'] = int(getattr(model, 'accum_steps', 1))             # micro-batches per optimizer step, by the same rule
+    # whether conv_in_q predicts offsets from the prior (model.residual_posterior). The same weights mean a different model under the other
+    # setting, so unlike the notes above this one is checked on load (check_residual_posterior)
+    ck['residual_posterior'] = bool(getattr(model, 'residual_posterior', False))
     if getattr(model, 'augment', None) is not None:
         ck['augment'] = dict(model.augment)   # the feed's augmentation and its seed; a file without the key means none
     nz = noise_state(model)
@@ -158,6 +161,21 @@ def save_checkpoint(path, model, optimizer=None, summary=None, bn_recal=None):
     torch.save(ck, path)
 
 
+def residual_posterior_record(ck):
+    """Whether the file's weights parameterise posteriors relative to the prior; a file without the note (an older one, a bare state_dict)
+    is absolute."""
+    return bool(ck.get('residual_posterior', False)) if isinstance(ck, dict) and 'model' in ck else False
+
+
+def check_residual_posterior(path, ck, model):
+    """ValueError naming both settings unless the model reads conv_in_q's output the way the file's run did."""
+    word = lambda r: 'residual (--residual-posterior: offsets from the prior)' if r else 'absolute (no --residual-posterior)'
+    was, now = residual_posterior_record(ck), bool(getattr(model, 'residual_posterior', False))
+    if was != now:
+        raise ValueError("%s was written by a model whose posteriors are %s; this model's are %s. The same weights mean a different model "
+                         "under the other setting: set the flag as the file's run did" % (path, word(was), word(now)))
+
+
 def load_checkpoint(path, model, optimizer=None, summary=None):
     """Loads a file written by `save_checkpoint` (with the noise stream's position and the device global-step counter when it holds
     them), or a bare reference `state_dict` file. Load before a TrainStep captures its graph: the graph keeps the counters it saw.
@@ -168,6 +186,7 @@ def load_checkpoint(path, model, optimizer=None, summary=None):
     is Adamax's, and exp_inf against exp_avg_sq is a ValueError naming both rules, raised before anything is loaded."""
     ck = torch.load(path, map_location='cpu')
     sd = ck['model'] if isinstance(ck, dict) and 'model' in ck else ck
+    check_residual_posterior(path, ck, model)   # (a mismatching 'residual_posterior' note is refused before anything is loaded)
     second = None
     if optimizer is not None and isinstance(ck, dict) and 'optimizer' in ck:
         second = check_rule(optimizer_rule_record(ck), optimizer.rule)   # (refused before anything is loaded)
@@ -218,6 +237,7 @@ def load_ema_weights(path, model):
     ck = torch.load(path, map_location='cpu')
     if not (isinstance(ck, dict) and 'model' in ck and 'ema' in ck):
         raise ValueError("%s holds no averaged weights (no 'ema' entry): it was not written by a run with --ema-decay > 0" % path)
+    check_residual_posterior(path, ck, model)
     model.load_state_dict(ck['ema'])
     model.global_step = int(ck.get('global_step', model.global_step))
     return ck

@@ -731,7 +731,11 @@ def main(argv=None):
     model = exp.model
     ck = None
     if args.checkpoint:
-        from .checkpoint import load_checkpoint, load_ema_weights
+        from .checkpoint import load_checkpoint, load_ema_weights, residual_posterior_record
+        # the same weights mean a different model under the other setting: build the model the file describes, whatever the command line says
+        model.residual_posterior = residual_posterior_record(torch.load(args.checkpoint, map_location='cpu'))
+        if model.residual_posterior:
+            print('%s: residual posteriors (conv_in_q predicts offsets from the prior of its layer)' % args.checkpoint)
         if args.ema:
             try:
                 ck = load_ema_weights(args.checkpoint, model)

@@ -130,6 +130,10 @@ def build_parser():
                    help='train on the K-sample importance-weighted bound instead of the ELBO: K samples per image share one bottom-up pass '
                         '(--batch-size stays images per step); the train line adds the bound and the effective sample size of the weights. '
                         'Not with --freebits or --analytical-kl. 1: the ELBO')
+    p.add_argument('--residual-posterior', action='store_true', dest='residual_posterior',
+                   help="every layer's inference path predicts its posterior as an offset from the prior of the same layer (NVAE's residual "
+                        'normal): mu_q = mu_p + dmu, logvar_q = logvar_p + dlv, and the KL is formed from the offset. Same parameters and '
+                        'state_dict; checkpoints note the setting, and --resume under the other one is refused. Off by default')
     p.add_argument('--accum-steps', type=int, default=1, dest='accum_steps', metavar='M',
                    help='every optimizer step consumes M micro-batches of --batch-size images: the gradient applied is the mean over all '
                         'M * batch-size images, BatchNorm normalises over one micro-batch, and steps (--log-every, the lr schedule, beta '
@@ -250,6 +254,8 @@ class LVAEExperiment:
             s += ',iw{}'.format(args.iw_train_samples)
         if getattr(args, 'accum_steps', 1) > 1:
             s += ',acc{}'.format(args.accum_steps)
+        if getattr(args, 'residual_posterior', False):
+            s += ',resq'
         for flag, word in (('binarize', ',binarize'), ('hflip', ',hflip'), ('dequantize', ',dequant')):
             if getattr(args, flag, False):
                 s += word
@@ -286,6 +292,7 @@ class LVAEExperiment:
                           no_initial_downscaling=a.no_initial_downscaling, analytical_kl=a.analytical_kl).to(self.device)
         model.noise = PhiloxNoise(seed=a.seed)
         model.compute_dtype = a.compute_dtype
+        model.residual_posterior = getattr(a, 'residual_posterior', False)   # (noted in checkpoints and checked on load)
         model.iw_train_samples = getattr(a, 'iw_train_samples', 1)   # (noted in checkpoints: checkpoint.save_checkpoint)
         model.accum_steps = getattr(a, 'accum_steps', 1)             # (likewise)
         model.ema_bn_batches = getattr(a, 'ema_bn_batches', 0)       # (likewise, when it is not 0)

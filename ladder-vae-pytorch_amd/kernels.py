@@ -1137,6 +1137,35 @@ def normal_stochastic_fwd(p, q, eps_or_z, mode, analytical_kl, Z, N, rows=None):
     return z, small[0], small[1], small[2], ks
 
 
+def normal_stochastic_res_fwd(p, d, eps_or_z, mode, analytical_kl, Z, N, rows=None, need_q=True):
+    """The core with the posterior given as an offset from the prior (csrc/stochastic_residual.hip): p (N|1,H,W,2Z), d (N,H,W,2Z) =
+    (dmu | dlv). Returns z, logprob_p, logprob_q, kl_samplewise, kl_spatial as normal_stochastic_fwd (rows alike) and q_out (N,H,W,2Z) =
+    p + d, or None with need_q=False: the kernel then writes nothing for it."""
+    p_bcast = int(p.shape[0] == 1 and N > 1)
+    _, H, W, _ = p.shape
+    dev = p.device
+    z = torch.empty((N, H, W, Z), dtype=torch.float32, device=dev)
+    small = torch.empty((3, N), dtype=torch.float32, device=dev)
+    if rows is not None:
+        small = [rows[0], small[1], rows[1]]
+    ks = torch.empty((N, H, W), dtype=torch.float32, device=dev)
+    q_out = torch.empty((N, H, W, 2 * Z), dtype=torch.float32, device=dev) if need_q else None
+    call('lvae_normal_stochastic_res_fwd_f32', ptr(p), p_bcast, ptr(d), ptr(eps_or_z), N, H * W, Z, mode, int(bool(analytical_kl)),
+         ptr(z), ptr(q_out), ptr(small[0]), ptr(small[1]), ptr(small[2]), ptr(ks), stream_ptr())
+    return z, small[0], small[1], small[2], ks, q_out
+
+
+def normal_stochastic_res_bwd(p, d, eps, z, dz, g_lp, g_lq, g_kl, g_ks, mode, analytical_kl, Z):
+    """Returns dp, the total gradient of the prior parameters (N,H,W,2Z: the caller sums a broadcast p over N), and dd, the offset's."""
+    N, H, W, _ = d.shape
+    p_bcast = int(p.shape[0] == 1 and N > 1)
+    dp = torch.empty((N, H, W, 2 * Z), dtype=torch.float32, device=d.device)
+    dd = torch.empty_like(dp)
+    call('lvae_normal_stochastic_res_bwd_f32', ptr(p), p_bcast, ptr(d), ptr(eps), ptr(z), ptr(dz), ptr(g_lp), ptr(g_lq),
+         ptr(g_kl), ptr(g_ks), N, H * W, Z, mode, int(bool(analytical_kl)), ptr(dp), ptr(dd), stream_ptr())
+    return dp, dd
+
+
 # Fused stochastic block of the low-resolution levels (csrc/stoch_img.hip, lvae_stoch_block_fwd_f32)
 def _stoch_block_desc(x_p, cv_p, p_given, x_q, cv_q, cv_out, eps_or_z, mode, analytical_kl, N, attach=True):
     """The lvae_stoch_block of one call, without output tensors; None where Python alone can tell that the fused launch does not apply.

@@ -24,10 +24,19 @@ class NormalStochasticBlock2d(nn.Module):
             self.conv_in_p = Conv2dParams(c_in, 2 * c_vars, kernel, padding=pad)
         self.conv_in_q = Conv2dParams(c_in, 2 * c_vars, kernel, padding=pad)
         self.conv_out = Conv2dParams(c_vars, c_out, kernel, padding=pad)
+        # engine attribute (not a constructor argument of the reference; LadderVAE.residual_posterior sets it): conv_in_q predicts the
+        # posterior as an offset from the prior of this layer, mu_q = mu_p + dmu, logvar_q = logvar_p + dlv
+        self.residual_posterior = False
 
     def forward(self, p_params, q_params=None, forced_latent=None, use_mode=False, force_constant_output=False,
-                analytical_kl=False, noise=None, n_img=None, need_kl_elementwise=True, rows=None, stats=None, temperature=None):
-        """need_kl_elementwise=False (engine-only keyword, used by TopDownLayer which drops that key, models/lvae_layers.py:163-170):
+                analytical_kl=False, noise=None, n_img=None, need_kl_elementwise=True, rows=None, stats=None, temperature=None,
+                need_q_params=True):
+        """residual_posterior (attribute) with q_params given: conv_in_q's output is the offset d = (dmu | dlv) and the core is
+        ops.NormalStochResFn, which forms z, both log-probabilities and the KL from the offset; the two convolutions, the core and conv_out
+        run as separate launches (the one-launch block of the low-resolution levels is declined). `data['q_params']` is then q_out = p + d,
+        detached, or None with need_q_params=False (engine-only keyword: nothing is written for it), and `kl_elementwise` is the value
+        composed from (z, p_params, q_out), detached: the sums that carry gradient are the core's. Without q_params nothing changes.
+        need_kl_elementwise=False (engine-only keyword, used by TopDownLayer which drops that key, models/lvae_layers.py:163-170):
         skip the pass that materialises `kl_elementwise` (lib/stochastic.py:88-91); the per-sample and per-pixel sums do not need it.
         temperature (engine-only keyword): None or 1.0 is the pass without it. Any other value draws z = mu_p + (t * sigma_p) * eps from the
         prior (lvae_normal_prior_sample_f32; `logprob_p` stays that of the untempered prior): a float, where 0.0 draws no noise and gives
@@ -39,7 +48,9 @@ class NormalStochasticBlock2d(nn.Module):
             raise ValueError("temperature applies to a draw from the prior: it cannot be combined with q_params, forced_latent or use_mode")
         if not self.transform_p_params:
             assert p_params.size(3) == 2 * self.c_vars
-        if q_params is not None and not tempered and not need_kl_elementwise and not force_constant_output and RB.switches.stoch_block:
+        residual = self.residual_posterior and q_params is not None
+        if (q_params is not None and not residual and not tempered and not need_kl_elementwise and not force_constant_output
+                and RB.switches.stoch_block):
             fused = self._fused(p_params, q_params, forced_latent, use_mode, analytical_kl, noise, n_img, rows, stats)
             if fused is not None:
                 return fused
@@ -66,7 +77,13 @@ class NormalStochasticBlock2d(nn.Module):
         else:
             mode, src = 0, noise.normal((N, H, W, self.c_vars), dev)
         # rows: engine-only keyword — (N,) views the kernel writes log p(z) and the KL into (rows of the model's [L][N] matrices)
-        outs = ops.NormalStochFn.apply(p_params, q_params, src, mode, bool(analytical_kl), self.c_vars, N, rows)
+        if residual:
+            # q_params is the offset up to here; from here on it is q_out = p_params + d (None where nobody reads it)
+            outs = ops.NormalStochResFn.apply(p_params, q_params, src, mode, bool(analytical_kl), self.c_vars, N, rows,
+                                              bool(need_q_params or need_kl_elementwise or stats is not None))
+            q_params = outs[5]
+        else:
+            outs = ops.NormalStochFn.apply(p_params, q_params, src, mode, bool(analytical_kl), self.c_vars, N, rows)
         if stats is not None and q_params is not None:
             # stats: engine-only keyword — the float64 (3, U) sums of this layer's latent usage (latent.LatentStats.slot); a pure read of
             # the two parameter tensors, outside autograd
@@ -82,9 +99,12 @@ class NormalStochasticBlock2d(nn.Module):
         out = ops.conv(z, self.conv_out, share=share and (share, False))
         data = {'z': z, 'p_params': p_params, 'q_params': q_params, 'logprob_p': outs[1], 'logprob_q': None,
                 'kl_elementwise': None, 'kl_samplewise': None, 'kl_spatial': None}
-        if q_params is not None:
+        if residual or q_params is not None:
             data['logprob_q'], data['kl_samplewise'], data['kl_spatial'] = outs[2], outs[3], outs[4]
-            if need_kl_elementwise:
+            if need_kl_elementwise and residual:
+                with torch.no_grad():   # composed from the rounded q_out: a report, not the arithmetic of the sums above
+                    data['kl_elementwise'] = K.kl_elementwise_fwd(p_params.detach(), q_params, z.detach(), bool(analytical_kl))
+            elif need_kl_elementwise:
                 data['kl_elementwise'] = ops.KlElementwiseFn.apply(z, p_params, q_params, bool(analytical_kl))
         return out, data
 

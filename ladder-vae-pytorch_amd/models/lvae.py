@@ -180,6 +180,19 @@ class LadderVAE(nn.Module):
         self.compute_dtype = 'f32'
         self.grad_tracker = None  # dist.GradAllReduce when gradients are exchanged while backward runs (engine.TrainStep sets it)
 
+    @property
+    def residual_posterior(self):
+        """Engine attribute (not a constructor argument of the reference), set after construction like compute_dtype: every layer's
+        conv_in_q predicts its posterior as an offset from the prior of the same layer, mu_q = mu_p + dmu, logvar_q = logvar_p + dlv
+        (NVAE's residual normal; the top layer's prior is the broadcast top_prior_params). No parameter is added or renamed: the same
+        state_dict means a different model under the other setting, which is why checkpoints note it."""
+        return all(layer.stochastic.residual_posterior for layer in self.top_down_layers)
+
+    @residual_posterior.setter
+    def residual_posterior(self, value):
+        for layer in self.top_down_layers:
+            layer.stochastic.residual_posterior = bool(value)
+
     # ------------------------------------------------------------------------------------------------------------
     # engine plumbing
     # ------------------------------------------------------------------------------------------------------------

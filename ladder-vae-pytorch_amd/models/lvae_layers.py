@@ -179,7 +179,8 @@ class TopDownLayer(nn.Module):
         x, data_stoch = self.stochastic(p_params=p_params, q_params=q_params, forced_latent=forced_latent,
                                         use_mode=use_mode, force_constant_output=force_constant_output,
                                         analytical_kl=self.analytical_kl, noise=noise, n_img=n_img,
-                                        need_kl_elementwise=False, rows=rows, stats=stats, temperature=temperature)
+                                        need_kl_elementwise=False, rows=rows, stats=stats, temperature=temperature,
+                                        need_q_params=stats is not None)   # this layer drops the 'q_params' key: see `keys` below
         if self.stochastic_skip and not self.is_top_layer:
             x = self.skip_connection_merger(x, skip_connection_input, noise)
         x_pre_residual = x

@@ -514,6 +514,37 @@ class NormalStochFn(Function):
         return dp, dq, None, None, None, None, None, None
 
 
+class NormalStochResFn(Function):
+    """NormalStochFn with the posterior given as an offset from the prior, d = (dmu | dlv) in place of q (csrc/stochastic_residual.hip).
+    Returns z, logprob_p, logprob_q, kl_samplewise, kl_spatial, q_out; q_out = p + d is None with need_q=False and carries no gradient
+    (it serves the readers of absolute posterior parameters). The backward returns dp, the total gradient of the prior parameters, and dd."""
+
+    @staticmethod
+    def forward(ctx, p, d, noise, mode, analytical, Z, N, rows=None, need_q=True):
+        z, lp, lq, kl, ks, q_out = K.normal_stochastic_res_fwd(p, d, noise, mode, analytical, Z, N, rows=rows, need_q=need_q)
+        ctx.set_materialize_grads(False)  # unused outputs arrive as None (the kernel takes NULL) instead of zero-filled tensors
+        ctx.mode, ctx.analytical, ctx.Z = mode, analytical, Z
+        ctx.p_bcast = p.shape[0] == 1 and N > 1
+        ctx.save_for_backward(p, d, noise if mode == 0 else None, z if mode == 2 else None)
+        if q_out is not None:
+            ctx.mark_non_differentiable(q_out)
+        return z, lp, lq, kl, ks, q_out
+
+    @staticmethod
+    def backward(ctx, dz, g_lp, g_lq=None, g_kl=None, g_ks=None, g_q=None):
+        p, d, eps, z = ctx.saved_tensors
+        cc = lambda t: None if t is None else _c(t)
+        if dz is None and g_lp is None and g_lq is None and g_kl is None and g_ks is None:
+            return (None,) * 9
+        dp, dd = K.normal_stochastic_res_bwd(p, d, eps, z, cc(dz), cc(g_lp), cc(g_lq), cc(g_kl), cc(g_ks), ctx.mode,
+                                             ctx.analytical, ctx.Z)
+        if ctx.p_bcast:
+            red = torch.empty_like(p)
+            K.colsum(dp.view(dp.shape[0], -1), red.view(-1), False)
+            dp = red
+        return (dp, dd) + (None,) * 7
+
+
 class StochBlockFn(Function):
     """The whole NormalStochasticBlock2d of a low-resolution level (lib/stochastic.py:45-99) as ONE autograd node whose forward is one launch
     (csrc/stoch_img.hip): p_params = conv_in_p(x_p) (top layer: p_given as it is), q_params = conv_in_q(x_q), the core of NormalStochFn,
