@@ -578,6 +578,7 @@ int lvae_colsum_f32(const float* x, int64_t R, int64_t P, float* out, int32_t ac
  * p, q: [N,HW,2Z] (mu = channels [0,Z), logvar = [Z,2Z)); p may be batch-broadcast (p_bcast=1: [1,HW,2Z]); q may be
  * NULL (sample from p). mode: 0 = z = mu + exp(lv/2)*eps, 1 = z = mu (use_mode), 2 = z given (forced_latent).
  * outputs: z [N,HW,Z]; logprob_p, logprob_q, kl_samplewise [N]; kl_spatial [N,HW] (analytical, sum over Z).
+ * HW * Z * 2 > INT32_MAX: LVAE_EINVAL, forward and backward (a sample's elements are indexed with int).
  * ---------------------------------------------------------------------------------------------------------- */
 int lvae_normal_stochastic_fwd_f32(const float* p, int32_t p_bcast, const float* q, const float* eps, int32_t N,
                                    int32_t HW, int32_t Z, int32_t mode, int32_t analytical_kl, float* z,

@@ -213,7 +213,8 @@ __device__ __forceinline__ float normal_kl(float qmu, float qlv, float pmu, floa
 }
 
 // log N(z; mu, exp(lv)) of one element, as torch.distributions.Normal(mu, exp(lv/2)).log_prob(z) forms it (var = std^2, log std = log(std)):
-// what the stochastic block (stochastic.hip) and the tempered prior draw (prior_sample.hip) sum into logprob_p / logprob_q
+// what the stochastic core's absolute form (abs_terms, stoch_core.h: the stand-alone kernels of stochastic.hip and the fused block of
+// stoch_img.hip) and the tempered prior draw (prior_sample.hip) sum into logprob_p / logprob_q
 constexpr float kLogSqrt2Pi = 0.91893853320467274178f;
 __device__ __forceinline__ float normal_logprob(float z, float mu, float lv) {
   const float sd = expf(0.5f * lv);

@@ -3,7 +3,7 @@
 // function is normal_logprob of lvae_common.h, the one the stochastic block's forward uses. HBM-bound: reads p and eps once, writes z once.
 //
 // A row's sum has a fixed order and no float atomics, so one workgroup owns a row. What made the scalar stochastic forward slow
-// (stochastic.hip, in front of stoch_fwd_v4_kernel) was one dependent round trip per 256 elements of that row; here a workgroup is 1,024
+// (stoch_core.h, in front of stoch_fwd_v4_map) was one dependent round trip per 256 elements of that row; here a workgroup is 1,024
 // threads and every thread requests all the loads of an iteration before it uses the first: 8,192 elements (float4 map) or 4,096 (scalar
 // map) are in flight per round trip, so the 16x16x32 level is one trip and a 32x32x32 level four.
 #include "lvae_host.h"

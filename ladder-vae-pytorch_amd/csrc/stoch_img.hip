@@ -3,7 +3,7 @@
 //
 //   p_params = conv_in_p(x_p)            3x3, 64 -> 2Z   (the top layer has none: p_params is the given, broadcast parameter)
 //   q_params = conv_in_q(x_q)            3x3, 64 -> 2Z
-//   z, log p(z), log q(z), KL            the elementwise core of stochastic.hip (stoch_fwd_v4_kernel), per-image and per-pixel sums
+//   z, log p(z), log q(z), KL            the elementwise core, absolute form (abs_terms of stoch_core.h), per-image and per-pixel sums
 //   out      = conv_out(z)               3x3, Z -> 64
 //
 // and has no BatchNorm: nothing in it needs a value of another workgroup once a workgroup's tile is whole images (the halo of each 3x3
@@ -16,14 +16,15 @@
 //
 // Arithmetic: resblock_img.hip's — the tile's patch (zero ring included) as three exact bf16 piece planes in LDS, weights pre-split once
 // per step in MFMA fragment order and streamed from L2, six piece products per fp32 product on v_mfma_f32_32x32x16_bf16 (PieceOrder<3>),
-// whatever the descriptor's precision says: the block has no bf16-operand form. The elementwise core is stoch_fwd_v4_kernel's per-element
-// arithmetic (normal_logprob / normal_kl of lvae_common.h), unchanged.
+// whatever the descriptor's precision says: the block has no bf16-operand form. The elementwise core calls the element functions of
+// stoch_core.h that the stand-alone kernels of stochastic.hip call (abs_terms, abs_grads, stoch_weights); the thread map is this tile's.
 #include <string.h>
 
 #include <type_traits>
 
 #include "bf16_frag.h"
 #include "lvae_host.h"
+#include "stoch_core.h"
 
 namespace lvae {
 
@@ -116,7 +117,7 @@ __global__ __launch_bounds__(256) void stoch_img_fwd_kernel(StochImgArgs a) {
   lds_barrier();   // Ps / Qs complete; the partial tiles are read: the region becomes the patch of z
 
   // =====================================================================================================================
-  // elementwise core (stoch_fwd_v4_kernel's arithmetic): z -> memory and the patch; kl_spatial; per-row sums -> scr
+  // elementwise core (abs_terms per element): z -> memory and the patch; kl_spatial; per-row sums -> scr
   // =====================================================================================================================
   zero_ring();
 #pragma unroll
@@ -128,18 +129,12 @@ __global__ __launch_bounds__(256) void stoch_img_fwd_kernel(StochImgArgs a) {
     float kan = 0.f, s_lp = 0.f, s_lq = 0.f, s_kl = 0.f;
 #pragma unroll
     for (int j = 0; j < 4; ++j) {
-      float z;
-      if (a.mode == 0) z = qmu[j] + expf(0.5f * qlv[j]) * ev[u][j];
-      else if (a.mode == 1) z = qmu[j];
-      else z = ev[u][j];   // forced latent is passed through the eps pointer
-      zv[j] = z;
-      const float lp = normal_logprob(z, pmu[j], plv[j]);
-      const float lq = normal_logprob(z, qmu[j], qlv[j]);
-      const float k = normal_kl(qmu[j], qlv[j], pmu[j], plv[j]);
-      s_lp += lp;
-      s_lq += lq;
-      kan += k;
-      s_kl += a.analytical ? k : (lq - lp);
+      const StochTerms r = abs_terms(pmu[j], plv[j], qmu[j], qlv[j], ev[u][j], a.mode, a.analytical);
+      zv[j] = r.z;
+      s_lp += r.lp;
+      s_lq += r.lq;
+      kan += r.kan;
+      s_kl += r.kl;
     }
     if (!eok[u]) zv = zero4;
     if (eok[u]) store_wt4(a.z + erow[u] * Z + ec, zv);
@@ -184,8 +179,8 @@ __global__ __launch_bounds__(256) void stoch_img_fwd_kernel(StochImgArgs a) {
   }
 }
 
-// Backward of the same block from d_out, per tile: dz = dgrad(conv_out)(d_out) stays in LDS; the per-element formulas of stoch_bwd_kernel
-// (stochastic.hip) with the g_lp / g_lq / g_kl / g_ks rows give dp and dq, which are stored (the queued whole-image weight gradients read them
+// Backward of the same block from d_out, per tile: dz = dgrad(conv_out)(d_out) stays in LDS; the per-element backward of the absolute form
+// (abs_grads, stoch_core.h) with the g_lp / g_lq / g_kl / g_ks rows give dp and dq, which are stored (the queued whole-image weight gradients read them
 // as dy) and staged as patches for the two input-gradient convolutions. Without conv_in_p only dp is written (the caller sums a broadcast
 // parameter's gradient over the batch).
 template <int MI, bool HAS_P>
@@ -226,34 +221,21 @@ __global__ __launch_bounds__(256) void stoch_img_bwd_kernel(StochImgArgs a) {
   for (int u = 0; u < MI; ++u) dzv[u] = os_sum4_at(er0 + 32 * u, ec) + dzx[u];
   lds_barrier();   // the partial tiles are read: the region becomes the patch of dp (or dq)
 
-  // ---- elementwise backward (stoch_bwd_kernel's arithmetic): dp, dq -> memory; dp (dq without conv_in_p) -> the patch
+  // ---- elementwise backward (abs_grads per element): dp, dq -> memory; dp (dq without conv_in_p) -> the patch
   zero_ring();
   f32x4 dqm[MI], dql[MI];
 #pragma unroll
   for (int u = 0; u < MI; ++u) {
-    const float G_lp = glp[u] - (a.analytical ? 0.f : gkl[u]);
-    const float G_lq = glq[u] + (a.analytical ? 0.f : gkl[u]);
-    const float G_an = gks[u] + (a.analytical ? gkl[u] : 0.f);
+    float G_lp, G_lq, G_an;
+    stoch_weights(glp[u], glq[u], gkl[u], gks[u], a.analytical, G_lp, G_lq, G_an);
     f32x4 dpm, dpl;
 #pragma unroll
     for (int j = 0; j < 4; ++j) {
-      const float ivp = expf(-plv[u][j]);  // 1/sigma_p^2
-      const float dpz = zv[u][j] - pmu[u][j];
-      const float ivq = expf(-qlv[u][j]);
-      const float dqz = zv[u][j] - qmu[u][j];
-      const float Gz = dzv[u][j] - G_lp * dpz * ivp - G_lq * dqz * ivq;
-      const float dmu = qmu[u][j] - pmu[u][j];
-      const float vr = expf(qlv[u][j] - plv[u][j]);
-      float dpmu = G_lp * dpz * ivp - G_an * dmu * ivp;
-      float dplv = G_lp * 0.5f * (dpz * dpz * ivp - 1.f) + G_an * 0.5f * (1.f - vr - dmu * dmu * ivp);
-      float dqmu = G_lq * dqz * ivq + G_an * dmu * ivp;
-      float dqlv = G_lq * 0.5f * (dqz * dqz * ivq - 1.f) + G_an * 0.5f * (vr - 1.f);
-      if (a.mode <= 1) dqmu += Gz;
-      if (a.mode == 0) dqlv += Gz * 0.5f * expf(0.5f * qlv[u][j]) * ev[u][j];
-      dpm[j] = dpmu;
-      dpl[j] = dplv;
-      dqm[u][j] = dqmu;
-      dql[u][j] = dqlv;
+      const StochGrads g = abs_grads(pmu[u][j], plv[u][j], qmu[u][j], qlv[u][j], ev[u][j], zv[u][j], dzv[u][j], G_lp, G_lq, G_an, a.mode);
+      dpm[j] = g.pmu;
+      dpl[j] = g.plv;
+      dqm[u][j] = g.smu;
+      dql[u][j] = g.slv;
     }
     if (!eok[u]) dpm = dpl = dqm[u] = dql[u] = zero4;
     if (eok[u]) {

@@ -1118,17 +1118,23 @@ def colsum(x2d, out, accumulate):
 
 
 # ----------------------------------------------------------------------------------------------------------------
+def _stoch_outputs(N, H, W, Z, dev, rows, with_ks=True):
+    """What every form of the stochastic core writes: z (N,H,W,Z), small = the (N,) rows logprob_p, logprob_q, kl_samplewise (rows, where
+    given, takes the places of the first and the last) and kl_spatial (N,H,W), or None without it."""
+    z = torch.empty((N, H, W, Z), dtype=torch.float32, device=dev)
+    small = torch.empty((3, N), dtype=torch.float32, device=dev)
+    if rows is not None:
+        small = [rows[0], small[1], rows[1]]
+    ks = torch.empty((N, H, W), dtype=torch.float32, device=dev) if with_ks else None
+    return z, small, ks
+
+
 def normal_stochastic_fwd(p, q, eps_or_z, mode, analytical_kl, Z, N, rows=None):
     """p (N|1,H,W,2Z), q (N,H,W,2Z)|None. Returns z (N,H,W,Z), logprob_p, logprob_q, kl_samplewise (N,), kl_spatial (N,H,W).
     rows = (logprob_p row, kl row): (N,) views of the model's [L][N] matrices the kernel writes into directly (no stacking copies)."""
     p_bcast = int(p.shape[0] == 1 and N > 1)
     _, H, W, _ = p.shape
-    dev = p.device
-    z = torch.empty((N, H, W, Z), dtype=torch.float32, device=dev)
-    small = torch.empty((3, N), dtype=torch.float32, device=dev)
-    if rows is not None:
-        small = [rows[0], small[1], rows[1]]
-    ks = torch.empty((N, H, W), dtype=torch.float32, device=dev) if q is not None else None
+    z, small, ks = _stoch_outputs(N, H, W, Z, p.device, rows, with_ks=q is not None)
     call('lvae_normal_stochastic_fwd_f32', ptr(p), p_bcast, ptr(q), ptr(eps_or_z), N, H * W, Z, mode, int(bool(analytical_kl)),
          ptr(z), ptr(small[0]), ptr(small[1]) if q is not None else None, ptr(small[2]) if q is not None else None, ptr(ks),
          stream_ptr())
@@ -1143,13 +1149,8 @@ def normal_stochastic_res_fwd(p, d, eps_or_z, mode, analytical_kl, Z, N, rows=No
     p + d, or None with need_q=False: the kernel then writes nothing for it."""
     p_bcast = int(p.shape[0] == 1 and N > 1)
     _, H, W, _ = p.shape
-    dev = p.device
-    z = torch.empty((N, H, W, Z), dtype=torch.float32, device=dev)
-    small = torch.empty((3, N), dtype=torch.float32, device=dev)
-    if rows is not None:
-        small = [rows[0], small[1], rows[1]]
-    ks = torch.empty((N, H, W), dtype=torch.float32, device=dev)
-    q_out = torch.empty((N, H, W, 2 * Z), dtype=torch.float32, device=dev) if need_q else None
+    z, small, ks = _stoch_outputs(N, H, W, Z, p.device, rows)
+    q_out = torch.empty((N, H, W, 2 * Z), dtype=torch.float32, device=p.device) if need_q else None
     call('lvae_normal_stochastic_res_fwd_f32', ptr(p), p_bcast, ptr(d), ptr(eps_or_z), N, H * W, Z, mode, int(bool(analytical_kl)),
          ptr(z), ptr(q_out), ptr(small[0]), ptr(small[1]), ptr(small[2]), ptr(ks), stream_ptr())
     return z, small[0], small[1], small[2], ks, q_out
@@ -1226,12 +1227,8 @@ def stoch_block_fwd(x_p, cv_p, p_given, x_q, cv_q, cv_out, eps_or_z, mode, analy
     dev, Z = x_q.device, cv_out[1].Cin
     q_params = torch.empty((N, H, W, cv_q[1].Cout), dtype=torch.float32, device=dev)
     p_params = torch.empty_like(q_params) if cv_p is not None else p_given
-    z = torch.empty((N, H, W, Z), dtype=torch.float32, device=dev)
+    z, small, ks = _stoch_outputs(N, H, W, Z, dev, rows)
     out = torch.empty((N, H, W, cv_out[1].Cout), dtype=torch.float32, device=dev)
-    small = torch.empty((3, N), dtype=torch.float32, device=dev)
-    if rows is not None:
-        small = [rows[0], small[1], rows[1]]
-    ks = torch.empty((N, H, W), dtype=torch.float32, device=dev)
     if cv_p is not None:
         b.conv_p.y = ptr(p_params)
     b.conv_q.y, b.conv_out.x, b.conv_out.y = ptr(q_params), ptr(z), ptr(out)

@@ -484,6 +484,13 @@ class AddFn(Function):
 
 
 # ----------------------------------------------------------------------------------------------------------------
+def _batch_sum_like(t, d):
+    """The gradient of an operand t (1, ...) that was broadcast over the batch: the per-sample gradient d (N, ...) summed over N."""
+    red = torch.empty_like(t)
+    K.colsum(d.view(d.shape[0], -1), red.view(-1), False)
+    return red
+
+
 class NormalStochFn(Function):
     """lib/stochastic.py:45-99 elementwise core. Returns z, logprob_p, logprob_q, kl_samplewise, kl_spatial."""
 
@@ -507,11 +514,7 @@ class NormalStochFn(Function):
             return None, None, None, None, None, None, None, None
         dp, dq = K.normal_stochastic_bwd(p, q, eps, z, cc(dz), cc(g_lp), cc(g_lq), cc(g_kl), cc(g_ks), ctx.mode,
                                          ctx.analytical, ctx.Z)
-        if ctx.p_bcast:
-            red = torch.empty_like(p)
-            K.colsum(dp.view(dp.shape[0], -1), red.view(-1), False)
-            dp = red
-        return dp, dq, None, None, None, None, None, None
+        return (_batch_sum_like(p, dp) if ctx.p_bcast else dp), dq, None, None, None, None, None, None
 
 
 class NormalStochResFn(Function):
@@ -538,11 +541,7 @@ class NormalStochResFn(Function):
             return (None,) * 9
         dp, dd = K.normal_stochastic_res_bwd(p, d, eps, z, cc(dz), cc(g_lp), cc(g_lq), cc(g_kl), cc(g_ks), ctx.mode,
                                              ctx.analytical, ctx.Z)
-        if ctx.p_bcast:
-            red = torch.empty_like(p)
-            K.colsum(dp.view(dp.shape[0], -1), red.view(-1), False)
-            dp = red
-        return (dp, dd) + (None,) * 7
+        return (_batch_sum_like(p, dp) if ctx.p_bcast else dp, dd) + (None,) * 7
 
 
 class StochBlockFn(Function):
@@ -597,10 +596,7 @@ class StochBlockFn(Function):
                 wgrad(x, dy, m.weight, m.geom(), grad_buf(m.weight), grad_buf(m.bias))
         dpg = None
         if cp is None and ctx.needs_input_grad[1]:   # the given p_params: a broadcast parameter's gradient is summed over the batch
-            dpg = dp
-            if ctx.p_bcast:
-                dpg = torch.empty_like(p)
-                K.colsum(dp.view(dp.shape[0], -1), dpg.view(-1), False)
+            dpg = _batch_sum_like(p, dp) if ctx.p_bcast else dp
         return (dx_p, dpg, dx_q) + none[3:]
 
 
@@ -617,14 +613,8 @@ class KlElementwiseFn(Function):
     def backward(ctx, g):
         z, p, q = ctx.saved_tensors
         dp, dq, dz = K.kl_elementwise_bwd(p, q, z, _c(g), ctx.analytical, need_dz=ctx.needs_input_grad[0])
-        out = []
-        for t, d in ((p, dp), (q, dq)):
-            if t.shape[0] == 1 and d.shape[0] > 1:
-                red = torch.empty_like(t)
-                K.colsum(d.view(d.shape[0], -1), red.view(-1), False)
-                d = red
-            out.append(d)
-        return dz, out[0], out[1], None
+        dp, dq = (_batch_sum_like(t, d) if t.shape[0] == 1 and d.shape[0] > 1 else d for t, d in ((p, dp), (q, dq)))
+        return dz, dp, dq, None
 
 
 # ----------------------------------------------------------------------------------------------------------------

@@ -253,6 +253,21 @@ def test_normal_stochastic_bwd_generative_path(K, shape):
                                  zf if mode == 2 else eps, grads, mode, False, Z, N, True)
 
 
+def test_normal_stochastic_entry_points_refuse_a_sample_past_int32(K):
+    """The kernels index the elements of one sample with int: HW * Z * 2 > INT32_MAX is refused, by the entry point's name, as the residual
+    entry points refuse it. Nothing is launched: the two small tensors only stand for the operands."""
+    from lvae_amd import _C
+    a, b = torch.zeros(8, device='cuda'), torch.zeros(8, device='cuda')
+    pa, pb, s = _C.ptr(a), _C.ptr(b), _C.stream_ptr()
+    HW, Z = 1 << 25, 32   # HW * Z * 2 = 2^31, the first value past the bound
+    with pytest.raises(_C.LvaeHipError, match=r'lvae_normal_stochastic_fwd_f32: HW \* Z too large'):
+        _C.call('lvae_normal_stochastic_fwd_f32', pa, 0, pa, pa, 1, HW, Z, 0, 0, pb, pb, pb, pb, pb, s)
+    with pytest.raises(_C.LvaeHipError, match=r'lvae_normal_stochastic_bwd_f32: HW \* Z too large'):
+        _C.call('lvae_normal_stochastic_bwd_f32', pa, 0, pa, pa, pa, pa, None, None, None, None, 1, HW, Z, 0, 0, pb, pb, s)
+    torch.cuda.synchronize()
+    assert float(a.abs().max()) == 0.0 and float(b.abs().max()) == 0.0
+
+
 # ---------------------------------------------------------------------------------------------------------------------------------
 # 3. kl_elementwise
 # ---------------------------------------------------------------------------------------------------------------------------------

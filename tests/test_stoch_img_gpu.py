@@ -257,6 +257,26 @@ def test_fused_equals_composed(E, shape, top):
         assert a.log[0][0] is c.blk.conv_out.weight and b.log[0][0] is c.blk.conv_out.weight
 
 
+@pytest.mark.parametrize('top', [False, True])
+@pytest.mark.parametrize('shape', [(5, 4, 4), (3, 8, 8), (9, 2, 2)])   # both tile sizes, and a tile that ends inside the batch
+def test_core_equals_the_stand_alone_kernel(E, shape, top):
+    """The block's core and lvae_normal_stochastic_fwd_f32 call one element function (csrc/stoch_core.h). On the block's own p_params and
+    q_params, z and kl_spatial are the same bits: at Z = 32 both kernels sum a pixel's KL as four channels per lane, then shuffles of 4,
+    2, 1. The per-sample sums are added in another order and are held to check_forward's bounds."""
+    c = case(E, *shape, top)
+    for mode in (0, 1, 2):
+        for analytical in (False, True):
+            r = run(E, c, mode, analytical, True)
+            assert r.fused_calls == 1
+            noise = None if mode == 1 else nhwc(c.zf if mode == 2 else c.eps)
+            z, lp, lq, kl, ks = E.K.normal_stochastic_fwd(r.p.detach(), r.q.detach(), noise, mode, analytical, Z, c.N)
+            torch.cuda.synchronize()
+            assert torch.equal(z, r.z.detach()), (mode, analytical)
+            assert torch.equal(ks, r.ks.detach()), (mode, analytical)
+            for a, b in ((lp, r.lp), (lq, r.lq), (kl, r.kl)):
+                torch.testing.assert_close(a.cpu().double(), b.detach().cpu().double(), rtol=1e-5, atol=1e-3)
+
+
 def test_large_level_and_other_widths_decline(E):
     c = case(E, 2, 8, 8, False)
     cv = lambda m: (m.weight, m.geom(), m.bias)
