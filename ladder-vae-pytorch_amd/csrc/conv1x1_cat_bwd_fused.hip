@@ -15,7 +15,7 @@
 // usual slabs ([workgroup][128 ci][64 co] + [workgroup][64]) and are summed in a fixed order (wgrad_reduce_launch): deterministic. No
 // workgroup waits for another: the loop is tile = blockIdx.x, += gridDim.x and nothing else.
 #include "bf16_frag.h"
-#include "bn_stats.h"
+#include "bn_apply.h"
 #include "lvae_host.h"
 
 namespace lvae {
@@ -40,7 +40,7 @@ constexpr int CB_LDO = 128;   // dx staging row pitch in floats: no padding (the
 // three planes of each tile, the dx staging tile, the deferred apply's coefficient rows [6][64], the dgrad's pre-split W fragments
 // [4 k-steps][4 column blocks][3][64 lanes][8]
 constexpr size_t cbf_lds() {
-  return (size_t)3 * (64 * CB_LDD + 64 * CB_LDX) * 2 + (size_t)64 * CB_LDO * 4 + 6 * 64 * 4 + (size_t)4 * 4 * 3 * 64 * 16;
+  return (size_t)3 * (64 * CB_LDD + 64 * CB_LDX) * 2 + (size_t)64 * CB_LDO * 4 + AP_CF * 4 + (size_t)4 * 4 * 3 * 64 * 16;
 }
 static_assert(cbf_lds() <= 160 * 1024, "one workgroup's LDS");
 
@@ -54,56 +54,14 @@ __global__ __launch_bounds__(512) void conv1x1_cat_bwd_fused_kernel(CbfArgs a) {
   __bf16* Ds = reinterpret_cast<__bf16*>(smem_raw);                  // [3][64 px][72]: dy tile
   __bf16* Xs = Ds + 3 * D_PLANE;                                     // [3][64 px][136]: (x1 | x2) tile
   float* Os = reinterpret_cast<float*>(Xs + 3 * X_PLANE);            // [64 px][128]: dx staging (fp32)
-  float* Cf = Os + 64 * CB_LDO;                                      // [6][64]: scale, shift, mean, rstd, mean(g), mean(g xhat) of the deferred apply
-  bf16x8* Wf = reinterpret_cast<bf16x8*>(Cf + 6 * 64);               // [4][4][3][64]
+  float* Cf = Os + 64 * CB_LDO;                                      // the deferred apply's coefficient rows (bn_apply.h)
+  bf16x8* Wf = reinterpret_cast<bf16x8*>(Cf + AP_CF);               // [4][4][3][64]
   const int t = threadIdx.x, lane = t & 63, wave = t >> 6;
   const bool wg_role = wave >= 4;  // waves 4-7: weight gradient; waves 0-3: dgrad
   const int wm = (wave & 3) >> 1, wn = wave & 1, li = lane & 31, lh = lane >> 5, G = lane >> 4, i16 = lane & 15;
   const f32x4 zero4 = {0.f, 0.f, 0.f, 0.f};
 
-  if (AP) {
-    // the producer's partial rows [rows][2][64], summed by 16 row groups (8 independent 16-byte loads in flight per thread), then in double
-    const int q = t & 31, rg = t >> 5, rows = a.ap.rows;
-    f32x4 acc = zero4;
-    for (int r = rg; r < rows; r += 16 * 8) {
-      f32x4 v[8];
-#pragma unroll
-      for (int u = 0; u < 8; ++u) {
-        const int rr = r + 16 * u;
-        v[u] = *reinterpret_cast<const f32x4*>(a.ap.parts + (size_t)(rr < rows ? rr : 0) * 128 + q * 4);
-      }
-#pragma unroll
-      for (int u = 0; u < 8; ++u)
-        if (r + 16 * u < rows) acc += v[u];
-    }
-    *reinterpret_cast<f32x4*>(Os + rg * 128 + q * 4) = acc;   // [16][128] <= the staging tile
-    if (t < 256) Cf[t] = a.ap.coef[t];
-    __syncthreads();
-    if (t < 64) {
-      double sa = 0.0, sb = 0.0;
-#pragma unroll
-      for (int g = 0; g < 16; ++g) {
-        sa += (double)Os[g * 128 + t];
-        sb += (double)Os[g * 128 + 64 + t];
-      }
-      const BnBwdChannel r = bn_bwd_finish(sa, sb, a.ap.M);
-      Cf[256 + t] = r.c1;
-      Cf[320 + t] = r.c2;
-      if (blockIdx.x == 0) {
-        if (a.ap.dbeta) a.ap.dbeta[t] += r.dbeta;
-        if (a.ap.dgamma) a.ap.dgamma[t] += r.dgamma;
-      }
-    }
-    __syncthreads();
-  }
-  // dy[m][c .. c + 3] of the deferred apply from (dh, x, add) and the coefficient rows in LDS
-  auto ap_value = [&](const f32x4 dh, const f32x4 xv, const f32x4 ad, int c) {
-    const f32x4 sc = *reinterpret_cast<const f32x4*>(Cf + c), sh = *reinterpret_cast<const f32x4*>(Cf + 64 + c);
-    const f32x4 mu = *reinterpret_cast<const f32x4*>(Cf + 128 + c), rs = *reinterpret_cast<const f32x4*>(Cf + 192 + c);
-    const f32x4 c1 = *reinterpret_cast<const f32x4*>(Cf + 256 + c), c2 = *reinterpret_cast<const f32x4*>(Cf + 320 + c);
-    const f32x4 g = dh * act_grad4(xv * sc + sh, a.ap.act);
-    return bn_bwd_apply(g, xv, c1, c2, mu, rs, sc) + ad;
-  };
+  if (AP) ap_reduce(a.ap, Os, Cf, blockIdx.x == 0);   // the producer's partial rows -> Cf, through the (still unused) staging tile
 
   // dgrad waves: W[co = 16 s + 8 lh + 0..7][ci = 32 cb + li] as the B fragment of k-step s and column block cb, three pieces, in LDS in
   // fragment order (wave cb writes its block once; published by the first barrier of the tile loop)
@@ -166,7 +124,7 @@ __global__ __launch_bounds__(512) void conv1x1_cat_bwd_fused_kernel(CbfArgs a) {
     for (int u = 0; u < 2; ++u) {
       g[u] = v1[u] = v2[u] = zero4;
       if (m0 + r0 + 32 * u < a.M) {
-        g[u] = AP ? ap_value(pg[u], px[u], pd[u], c4) : pg[u];
+        g[u] = AP ? ap_value4(Cf, pg[u], px[u], c4, a.ap.act) + pd[u] : pg[u];
         v1[u] = p1[u];
         v2[u] = p2[u];
       }
@@ -336,9 +294,10 @@ extern "C" int lvae_conv1x1_cat_bwd_f32(const lvae_conv_desc* d, const float* x1
                "%s: not taken (needs the dgrad view of a 1x1 / stride-1 convolution over a 64 + 64 channel concat with 64 output channels: "
                "C1 = 64, Cout = 128, w_sk = 1, 16-byte aligned dy and w, fp32 tensors, precision LVAE_PREC_F32 and not LVAE_FORM_F32_MFMA); "
                "use lvae_conv2d_wgrad_f32 + lvae_conv1x1_dgrad_cat_f32", who);
-  if (with_ap)
-    LVAE_REQUIRE(ap->rows > 0 && ap->M == (int64_t)d->N * d->H * d->W && ap->coef && ap->dh && ap->x && ap->dh_bf16 == 0 && ap->drop == nullptr,
-                 LVAE_EINVAL, "%s: deferred apply needs parts / rows, M = N*H*W, the coefficient block, an fp32 dh and x, and no drop", who);
+  if (with_ap) {
+    const int rc = bn_apply_check(who, ap, (int64_t)d->N * d->H * d->W, BN_AP_ADD | BN_AP_OUT_OPTIONAL);
+    if (rc) return rc;
+  }
   LVAE_REQUIRE(workspace_bytes >= p.workspace, LVAE_EWORKSPACE, "%s: workspace %zu < %zu", who, workspace_bytes, p.workspace);
   CBF_REQUIRE_AL16(x1);
   CBF_REQUIRE_AL16(x2);
@@ -347,15 +306,7 @@ extern "C" int lvae_conv1x1_cat_bwd_f32(const lvae_conv_desc* d, const float* x1
   CBF_REQUIRE_AL16(workspace);
   CbfArgs a;
   a.ap = lvae_bn_apply{};
-  if (with_ap) {
-    CBF_REQUIRE_AL16(ap->parts);
-    CBF_REQUIRE_AL16(ap->coef);
-    CBF_REQUIRE_AL16(ap->dh);
-    CBF_REQUIRE_AL16(ap->x);
-    CBF_REQUIRE_AL16(ap->add);
-    CBF_REQUIRE_AL16(ap->out);
-    a.ap = *ap;
-  }
+  if (with_ap) a.ap = *ap;
   a.dy = d->x;
   a.x1 = x1;
   a.x2 = x2;

@@ -24,7 +24,7 @@
 //     v_mfma_f32_32x32x2_f32 and the vector ALU do not overlap on this chip (the fp32 matrix rate equals the packed-fp32 vector rate:
 //     the same lanes), so in an fp32 kernel VALU time adds to MFMA time whichever wave issues it. The bf16 MFMAs have their own unit.
 #include "bf16_frag.h"
-#include "bn_stats.h"
+#include "bn_apply.h"
 #include "lvae_host.h"
 
 namespace lvae {
@@ -200,7 +200,7 @@ constexpr int GBB_LDY = 72;   // y row pitch in bf16
 // + the deferred apply's coefficient rows [6][64] and, in the six-product form, the dgrad's pre-split W fragments [8 k-steps][2 column halves][3][64 lanes][8]
 // (48 KB: in registers they were 96 VGPRs of every wave of a kernel at the 256-register cap; with the deferred apply's extra operand rows it spilled)
 constexpr size_t gbb_lds(int split) {
-  return (size_t)split * (64 * GBB_LDA + 64 * GBB_LDY) * 2 + (size_t)64 * GB_LDY * 4 + 6 * 64 * 4 + (split == 3 ? (size_t)8 * 2 * 3 * 64 * 16 : 0);
+  return (size_t)split * (64 * GBB_LDA + 64 * GBB_LDY) * 2 + (size_t)64 * GB_LDY * 4 + AP_CF * 4 + (split == 3 ? (size_t)8 * 2 * 3 * 64 * 16 : 0);
 }
 
 // S16 (SPLIT == 1): ab, y and dx are bf16-stored (residual-block internals under compute_dtype bf16) and move as 16-byte pieces: a thread
@@ -235,63 +235,18 @@ __global__ __launch_bounds__(512) void conv1x1_gate_bwd_fused_bf16_kernel(GbfArg
   __bf16* As = reinterpret_cast<__bf16*>(smem_raw);                 // [SPLIT][64 px][136]: dab tile
   __bf16* Ys = As + SPLIT * A_PLANE;                                 // [SPLIT][64 px][72]: y tile
   float* Os = reinterpret_cast<float*>(Ys + SPLIT * Y_PLANE);        // [64 px][68]: dx staging (fp32)
-  float* Cf = Os + 64 * GB_LDY;                                      // [6][64]: scale, shift, mean, rstd, mean(g), mean(g xhat) of the deferred apply
+  float* Cf = Os + 64 * GB_LDY;                                      // the deferred apply's coefficient rows (bn_apply.h)
   const int t = threadIdx.x, lane = t & 63, wave = t >> 6;
   const bool wg_role = wave >= 4;  // waves 4-7: weight gradient; waves 0-3: dgrad
   const int wm = (wave & 3) >> 1, wn = wave & 1, li = lane & 31, lh = lane >> 5, G = lane >> 4, i16 = lane & 15;
   const f32x4 zero4 = {0.f, 0.f, 0.f, 0.f};
 
-  if (AP) {
-    // the producer's partial rows [rows][2][64], summed by 16 row groups (8 independent 16-byte loads in flight per thread), then in double
-    const int q = t & 31, rg = t >> 5, rows = a.ap.rows;
-    f32x4 acc = zero4;
-    for (int r = rg; r < rows; r += 16 * 8) {
-      f32x4 v[8];
-#pragma unroll
-      for (int u = 0; u < 8; ++u) {
-        const int rr = r + 16 * u;
-        v[u] = *reinterpret_cast<const f32x4*>(a.ap.parts + (size_t)(rr < rows ? rr : 0) * 128 + q * 4);
-      }
-#pragma unroll
-      for (int u = 0; u < 8; ++u)
-        if (r + 16 * u < rows) acc += v[u];
-    }
-    *reinterpret_cast<f32x4*>(Os + rg * 128 + q * 4) = acc;   // [16][128] <= the staging tile
-    if (t < 256) Cf[t] = a.ap.coef[t];
-    __syncthreads();
-    if (t < 64) {
-      double sa = 0.0, sb = 0.0;
-#pragma unroll
-      for (int g = 0; g < 16; ++g) {
-        sa += (double)Os[g * 128 + t];
-        sb += (double)Os[g * 128 + 64 + t];
-      }
-      const BnBwdChannel r = bn_bwd_finish(sa, sb, a.ap.M);
-      Cf[256 + t] = r.c1;
-      Cf[320 + t] = r.c2;
-      if (blockIdx.x == 0) {
-        if (a.ap.dbeta) a.ap.dbeta[t] += r.dbeta;
-        if (a.ap.dgamma) a.ap.dgamma[t] += r.dgamma;
-      }
-    }
-    __syncthreads();
-  }
-  // dout[m][c .. c + 3] of the deferred apply from (dh, x, add) and the coefficient rows in LDS
-  auto ap_value = [&](const f32x4 dh, const f32x4 xv, const f32x4 ad, int c) {
-    const f32x4 sc = *reinterpret_cast<const f32x4*>(Cf + c), sh = *reinterpret_cast<const f32x4*>(Cf + 64 + c);
-    const f32x4 mu = *reinterpret_cast<const f32x4*>(Cf + 128 + c), rs = *reinterpret_cast<const f32x4*>(Cf + 192 + c);
-    const f32x4 c1 = *reinterpret_cast<const f32x4*>(Cf + 256 + c), c2 = *reinterpret_cast<const f32x4*>(Cf + 320 + c);
-    const f32x4 u = xv * sc + sh;
-    f32x4 g;
-#pragma unroll
-    for (int j = 0; j < 4; ++j) g[j] = dh[j] * act_grad(u[j], apact);
-    return bn_bwd_apply(g, xv, c1, c2, mu, rs, sc) + ad;
-  };
+  if (AP) ap_reduce(a.ap, Os, Cf, blockIdx.x == 0);   // the producer's partial rows -> Cf, through the (still unused) staging tile
 
   // dgrad waves: W[co = 16 s + 8 lh + 0..7][ci = wn*32 + li] as the B fragment of k-step s, SPLIT pieces: in registers (bf16 operands) or,
   // in the six-product form, in LDS in fragment order (written once by waves 0 / 1, published by the first barrier below)
   constexpr bool WLDS = SPLIT == 3;
-  bf16x8* Wf = reinterpret_cast<bf16x8*>(Cf + 6 * 64);   // [8][2][SPLIT][64]
+  bf16x8* Wf = reinterpret_cast<bf16x8*>(Cf + AP_CF);   // [8][2][SPLIT][64]
   bf16x8 breg[WLDS ? 1 : 8][SPLIT];
   if (!wg_role && (!WLDS || wm == 0)) {
 #pragma unroll
@@ -410,7 +365,7 @@ __global__ __launch_bounds__(512) void conv1x1_gate_bwd_fused_bf16_kernel(GbfArg
         if (AP) {
 #pragma unroll
           for (int h = 0; h < 2; ++h) {
-            pg[h] = ap_value(pg[h], px[h], pd[h], c8 + 4 * h);
+            pg[h] = ap_value4(Cf, pg[h], px[h], c8 + 4 * h, apact) + pd[h];
             store_wt4(a.ap.out + (size_t)(m0 + r8) * 64 + c8 + 4 * h, pg[h]);
           }
         }
@@ -482,7 +437,7 @@ __global__ __launch_bounds__(512) void conv1x1_gate_bwd_fused_bf16_kernel(GbfArg
       f32x4 lo = zero4, hi = zero4, yv = zero4;
       if (m0 + r < a.M) {
         if (AP) {
-          pg[u] = ap_value(pg[u], px[u], pd[u], c4);
+          pg[u] = ap_value4(Cf, pg[u], px[u], c4, apact) + pd[u];
           if (!(dbg & 4)) store_wt4(a.ap.out + (size_t)(m0 + r) * 64 + c4, pg[u]);
         }
         if (dbg & 8) {
@@ -684,15 +639,7 @@ static int conv1x1_gate_bwd_fused_launch(const lvae_conv_desc* d, const float* d
   a.gws = static_cast<const __bf16*>(gws);
   a.gbias = gbias;
   a.ap = lvae_bn_apply{};
-  if (ap != nullptr && ap->parts != nullptr) {
-    GBF_REQUIRE_AL16(ap->parts);
-    GBF_REQUIRE_AL16(ap->coef);
-    GBF_REQUIRE_AL16(ap->dh);
-    GBF_REQUIRE_AL16(ap->x);
-    GBF_REQUIRE_AL16(ap->add);
-    GBF_REQUIRE_AL16(ap->out);
-    a.ap = *ap;
-  }
+  if (ap != nullptr && ap->parts != nullptr) a.ap = *ap;   // (checked by the entry point: bn_apply_check)
   a.dout = dout;
   a.ab = ab;
   a.y = y;
@@ -767,9 +714,10 @@ extern "C" int lvae_conv1x1_gate_bwd_wgrad_f32(const lvae_conv_desc* d, const fl
                                                size_t workspace_bytes, const lvae_bn_apply* ap, void* stream) {
   const bool with_ap = ap != nullptr && ap->parts != nullptr;
   LVAE_REQUIRE(d && (dout || with_ap) && ab && y && d->y && dw && workspace, LVAE_EINVAL, "lvae_conv1x1_gate_bwd_wgrad_f32: null pointer");
-  if (with_ap)
-    LVAE_REQUIRE(ap->rows > 0 && ap->M == (int64_t)d->N * d->H * d->W && ap->coef && ap->dh && ap->x && ap->out, LVAE_EINVAL,
-                 "lvae_conv1x1_gate_bwd_wgrad_f32: deferred apply needs parts / rows, M = N*H*W, the coefficient block, dh, x and out");
+  if (with_ap) {
+    const int rc = bn_apply_check("lvae_conv1x1_gate_bwd_wgrad_f32", ap, (int64_t)d->N * d->H * d->W, BN_AP_ADD | BN_AP_DH_BF16);
+    if (rc) return rc;
+  }
   ConvPlan p;
   LVAE_REQUIRE(conv1x1_gate_bwd_fused_plan(d, with_ap, p), LVAE_EINVAL,
                "lvae_conv1x1_gate_bwd_wgrad_f32: not supported (needs the gate of a 64-channel block: 1x1, 128 -> 64 dgrad view, at least 16384 "
@@ -792,9 +740,10 @@ extern "C" int lvae_conv1x1_gate_bwd_wgrad_recompute_f32(const lvae_conv_desc* d
   const char* who = "lvae_conv1x1_gate_bwd_wgrad_recompute_f32";
   const bool with_ap = ap != nullptr && ap->parts != nullptr;
   LVAE_REQUIRE(d && (dout || with_ap) && y && d->y && dw && workspace, LVAE_EINVAL, "%s: null pointer", who);
-  if (with_ap)
-    LVAE_REQUIRE(ap->rows > 0 && ap->M == (int64_t)d->N * d->H * d->W && ap->coef && ap->dh && ap->x && ap->out, LVAE_EINVAL,
-                 "%s: deferred apply needs parts / rows, M = N*H*W, the coefficient block, dh, x and out", who);
+  if (with_ap) {
+    const int rc = bn_apply_check(who, ap, (int64_t)d->N * d->H * d->W, BN_AP_ADD | BN_AP_DH_BF16);
+    if (rc) return rc;
+  }
   ConvPlan p;
   LVAE_REQUIRE(gbf_recompute_plan(d, with_ap, p), LVAE_EINVAL,
                "%s: not supported (needs what lvae_conv1x1_gate_bwd_wgrad_f32 needs, fp32 tensors, precision LVAE_PREC_F32 and not "

@@ -21,7 +21,7 @@
 #include <algorithm>
 #include <type_traits>
 
-#include "bn_stats.h"
+#include "bn_apply.h"
 #include "lvae_host.h"
 
 namespace lvae {

@@ -58,10 +58,11 @@
   }
   f32x4 xreg[XSLOTS], dreg[2];
   f32x4 yreg[AP ? 2 : 1], dmask = {1.f, 1.f, 1.f, 1.f};
-  float* Cf = smem + 2 * BUF;   // (AP) [6][64]: scale, shift, mean, rstd, mean(g), mean(g xhat) behind the two chunk buffers, inside the allocation
-                                // the epilogue's exchange sizes (131 KB); in registers they spilled a kernel that sits at 234-242 of 256
+  float* Cf = smem + 2 * BUF;   // (AP) the apply's coefficient rows (bn_apply.h), then in_scale and in_shift [2][64], behind the two chunk buffers,
+                                // inside the allocation the epilogue's exchange sizes (131 KB); in registers they spilled a kernel that sits at 234-242 of 256
   if (AP) {
-    // the producer's partial rows [rows][2][64], summed by 16 row groups (8 independent 16-byte loads in flight per thread), then in double
+    // This kernel's own copy of ap_reduce (bn_apply.h) with its in_scale / in_shift rows in front of the first barrier, kept word for word:
+    // through the shared helper the 32-pixel-wide instantiations, which sit at 256 registers, spill 5 values instead of 4 and take 5 % longer.
     const int q = t & 31, rg = t >> 5, rows = ap.rows;
     f32x4 accp = zero4;
     for (int r = rg; r < rows; r += 16 * 8) {
@@ -78,8 +79,8 @@
     *reinterpret_cast<f32x4*>(smem + rg * 128 + q * 4) = accp;   // [16][128], in front of the (still unused) chunk buffers
     if (t < 256) Cf[t] = ap.coef[t];
     if (t < 64) {
-      Cf[384 + t] = d.in_scale ? d.in_scale[t] : 1.f;
-      Cf[448 + t] = d.in_scale ? d.in_shift[t] : 0.f;
+      Cf[AP_CF + t] = d.in_scale ? d.in_scale[t] : 1.f;
+      Cf[AP_CF + 64 + t] = d.in_scale ? d.in_shift[t] : 0.f;
     }
     __syncthreads();
     if (t < 64) {
@@ -90,8 +91,8 @@
         sb += (double)smem[g2 * 128 + 64 + t];
       }
       const BnBwdChannel r = bn_bwd_finish(sa, sb, ap.M);
-      Cf[256 + t] = r.c1;
-      Cf[320 + t] = r.c2;
+      Cf[AP_C1 + t] = r.c1;
+      Cf[AP_C2 + t] = r.c2;
       if (bid_ == 0) {
         if (ap.dbeta) ap.dbeta[t] += r.dbeta;
         if (ap.dgamma) ap.dgamma[t] += r.dgamma;
@@ -139,22 +140,18 @@
     if (AP) {
       const int n = fastdiv(c, a.m_cpi), cr = c - n * a.cpi;
       const int64_t doff0 = (int64_t)(n * d.H + cr * (2 * TR)) * W * d.Cout + drel;
-      const f32x4 ap_sc = *reinterpret_cast<const f32x4*>(Cf + dc4), ap_sh = *reinterpret_cast<const f32x4*>(Cf + 64 + dc4);
-      const f32x4 ap_mu = *reinterpret_cast<const f32x4*>(Cf + 128 + dc4), ap_rs = *reinterpret_cast<const f32x4*>(Cf + 192 + dc4);
-      const f32x4 ap_c1 = *reinterpret_cast<const f32x4*>(Cf + 256 + dc4), ap_c2 = *reinterpret_cast<const f32x4*>(Cf + 320 + dc4);
+      const ApRows cf = ap_rows(Cf, dc4);
 #pragma unroll
       for (int k = 0; k < 2; ++k) {
-        const f32x4 xv = yreg[AP ? k : 0];
-        const f32x4 gq = dreg[k] * act_grad4(xv * ap_sc + ap_sh, ap.act);
-        f32x4 v = bn_bwd_apply(gq, xv, ap_c1, ap_c2, ap_mu, ap_rs, ap_sc) * dmask;
+        f32x4 v = ap_value4(cf, dreg[k], yreg[AP ? k : 0], ap.act) * dmask;
         if (!dy_ok) v = zero4;
         dreg[k] = v;
         if (cib == 0 && dy_ok) store_wt4(ap.out + doff0 + (k ? 32 * d.Cout : 0), v);
       }
     }
     if (AP) {
-      sc = *reinterpret_cast<const f32x4*>(Cf + 384 + cib * 32 + xc4);
-      sh = *reinterpret_cast<const f32x4*>(Cf + 448 + cib * 32 + xc4);
+      sc = *reinterpret_cast<const f32x4*>(Cf + AP_CF + cib * 32 + xc4);
+      sh = *reinterpret_cast<const f32x4*>(Cf + AP_CF + 64 + cib * 32 + xc4);
     }
 #pragma unroll
     for (int u = 0; u < XSLOTS; ++u) {

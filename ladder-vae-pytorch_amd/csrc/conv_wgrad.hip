@@ -637,13 +637,11 @@ extern "C" int lvae_conv2d_wgrad_apply_f32(const lvae_conv_desc* d, const lvae_b
   LVAE_REQUIRE(o.plan.apply_ok, LVAE_EINVAL,
                "%s: shape not supported (the Winograd-domain fp32 weight gradient of a 64 -> 64 layer, W = 16 or 32): "
                "use lvae_affine_act_bwd_parts_f32 + lvae_conv2d_wgrad_f32", who);
-  LVAE_REQUIRE(ap && ap->parts && ap->rows > 0 && ap->M == (int64_t)d->N * d->H * d->W && ap->coef && ap->dh && ap->x && ap->out && ap->add == nullptr &&
-                   ap->dh_bf16 == 0 && dw && workspace,
-               LVAE_EINVAL, "%s: needs parts / rows, M = N*H*W, the coefficient block, fp32 dh, x and out, no add", who);
+  LVAE_REQUIRE(dw && workspace, LVAE_EINVAL, "%s: null dw / workspace", who);
+  rc = bn_apply_check(who, ap, (int64_t)d->N * d->H * d->W, BN_AP_DROP);
+  if (rc) return rc;
   LVAE_REQUIRE(workspace_bytes >= o.plan.workspace, LVAE_EWORKSPACE, "%s: workspace %zu < %zu", who, workspace_bytes, o.plan.workspace);
-  const void* const operand[] = {workspace, ap->parts, ap->coef, ap->dh, ap->x, ap->out, ap->drop};
-  const char* const name[] = {"workspace", "ap->parts", "ap->coef", "ap->dh", "ap->x", "ap->out", "ap->drop"};
-  for (int i = 0; i < 7; ++i) LVAE_REQUIRE(al16_or_null(operand[i]), LVAE_EALIGN, "%s: %s must be 16-byte aligned", who, name[i]);
+  LVAE_REQUIRE(al16(workspace), LVAE_EALIGN, "%s: workspace must be 16-byte aligned", who);
   return conv_wgrad_wino_apply_launch(o, ap, (hipStream_t)stream);
 }
 
@@ -689,14 +687,12 @@ extern "C" int lvae_conv2d_wgrad_pair_f32(const lvae_conv_desc* a, const lvae_bn
   LVAE_REQUIRE(wgrad_pair_route(a, b, pa, pb, nullptr), LVAE_EINVAL,
                "%s: not a pair (two Winograd-domain fp32 weight gradients of 64 -> 64 layers of one geometry, W = 16 or 32, fp32 storage; "
                "lvae_conv2d_wgrad_pair_ok): use lvae_conv2d_wgrad_apply_f32 + lvae_conv2d_wgrad_f32", who);
-  LVAE_REQUIRE(ap && ap->parts && ap->rows > 0 && ap->M == (int64_t)a->N * a->H * a->W && ap->coef && ap->dh && ap->x && ap->out && ap->add == nullptr &&
-                   ap->dh_bf16 == 0 && dy_b && dw_a && dw_b && workspace,
-               LVAE_EINVAL, "%s: needs parts / rows, M = N*H*W, the coefficient block, fp32 dh, x and out, no add; dy of B, both dw, workspace", who);
+  LVAE_REQUIRE(dy_b && dw_a && dw_b && workspace, LVAE_EINVAL, "%s: null dy of B / dw / workspace", who);
+  rc = bn_apply_check(who, ap, (int64_t)a->N * a->H * a->W, BN_AP_DROP);
+  if (rc) return rc;
   const size_t piece_a = wgrad_piece(pa), need = piece_a + wgrad_piece(pb);
   LVAE_REQUIRE(workspace_bytes >= need, LVAE_EWORKSPACE, "%s: workspace %zu < %zu", who, workspace_bytes, need);
-  const void* const operand[] = {workspace, ap->parts, ap->coef, ap->dh, ap->x, ap->out, ap->drop, dy_b};
-  const char* const name[] = {"workspace", "ap->parts", "ap->coef", "ap->dh", "ap->x", "ap->out", "ap->drop", "dy_b"};
-  for (int i = 0; i < 8; ++i) LVAE_REQUIRE(al16_or_null(operand[i]), LVAE_EALIGN, "%s: %s must be 16-byte aligned", who, name[i]);
+  LVAE_REQUIRE(al16(workspace) && al16(dy_b), LVAE_EALIGN, "%s: %s must be 16-byte aligned", who, al16(workspace) ? "dy_b" : "workspace");
   const WgradOp oa{a, pa, nullptr, dw_a, db_a, workspace}, ob{b, pb, dy_b, dw_b, db_b, static_cast<char*>(workspace) + piece_a};
   return conv_wgrad_wino_pair_launch(oa, ap, ob, (hipStream_t)stream);
 }

@@ -150,6 +150,25 @@ int conv_wgrad_wino_shared_launch(const WgradOp* o, int n, hipStream_t s);
 bool conv1x1_wgrad_plan(const lvae_conv_desc* d, WgradPlan& p);
 int conv1x1_wgrad_launch(const WgradOp& o, hipStream_t s);
 
+// The one check of a lvae_bn_apply, for every entry point that takes one (`who`; resblock_img.hip passes views of its ap_* / bwd_* fields).
+// M = N*H*W of the launch; `allows`: what this launch can do beside the plain apply. LVAE_EINVAL for what is missing or not allowed,
+// then align_rc, naming the operand, for a pointer the kernels read or write 16 bytes at a time. Nothing is written. `name`: what the
+// entry point's caller knows parts, coef, dh, x, add, out, drop as (resblock_img.hip's fields have names of their own).
+enum { BN_AP_ADD = 1, BN_AP_DROP = 2, BN_AP_DH_BF16 = 4, BN_AP_OUT_OPTIONAL = 8 };
+constexpr const char* kBnApplyNames[7] = {"ap->parts", "ap->coef", "ap->dh", "ap->x", "ap->add", "ap->out", "ap->drop"};
+inline int bn_apply_check(const char* who, const lvae_bn_apply* ap, int64_t M, int allows, const char* const (&name)[7] = kBnApplyNames,
+                          int align_rc = LVAE_EALIGN) {
+  LVAE_REQUIRE(ap && ap->parts && ap->rows > 0 && ap->M == M && ap->coef && ap->dh && ap->x, LVAE_EINVAL,
+               "%s: the BatchNorm-backward apply needs %s / rows, M = N*H*W, %s (the coefficient block), %s and %s", who, name[0], name[1], name[2], name[3]);
+  LVAE_REQUIRE(ap->out || (allows & BN_AP_OUT_OPTIONAL), LVAE_EINVAL, "%s: the BatchNorm-backward apply needs %s", who, name[5]);
+  LVAE_REQUIRE(!ap->add || (allows & BN_AP_ADD), LVAE_EINVAL, "%s: this launch takes no %s with the BatchNorm-backward apply", who, name[4]);
+  LVAE_REQUIRE(!ap->drop || (allows & BN_AP_DROP), LVAE_EINVAL, "%s: this launch takes no %s with the BatchNorm-backward apply", who, name[6]);
+  LVAE_REQUIRE(!ap->dh_bf16 || (allows & BN_AP_DH_BF16), LVAE_EINVAL, "%s: this launch takes an fp32 %s only", who, name[2]);
+  const void* const operand[] = {ap->parts, ap->coef, ap->dh, ap->x, ap->add, ap->out, ap->drop};
+  for (int i = 0; i < 7; ++i) LVAE_REQUIRE(al16_or_null(operand[i]), align_rc, "%s: %s must be 16-byte aligned", who, name[i]);
+  return 0;
+}
+
 // Launch of a kernel whose dynamic LDS may exceed the 64 KB default: raises the kernel's limit to max_lds the first time THIS kernel is
 // launched (one flag per kernel: the template argument), launches, checks. name: as it appears in lvae_last_error().
 template <auto Kern, typename Args>

@@ -26,7 +26,7 @@
 #include <string.h>
 
 #include "bf16_frag.h"
-#include "bn_stats.h"
+#include "bn_apply.h"
 #include "lvae_host.h"
 
 namespace lvae {
@@ -117,6 +117,43 @@ __device__ __forceinline__ void rb_parts_finish(const float* __restrict__ parts,
     finish(t, sa, sb);
   }
   lds_barrier();
+}
+
+// The BatchNorm-backward apply of a prologue (PRO_BN_APPLY: e.bwd_*; the deferred apply in front of PRO_GATE_BWD: e.ap_*) in two calls
+// around the kernel's own operand loads, in the order of requests the comment above asks for: rb_apply_begin issues the partial rows,
+// calls `then` (the L2 touches), loads this thread's coefficient vectors at c4 and, in the workgroup that accumulates them
+// (writes_params), the old dgamma / dbeta; rb_apply_finish reduces the rows and completes k.r with c1 / c2. The value is ap_value4(k.r, dh, x, act).
+// The fields come by reference: they are kernel arguments, read where they are used. By value they would be live from the call on, and
+// the kernel has no scalar register to spare.
+struct RbApply {
+  ApRows r;
+  float db0, dg0;
+};
+template <typename F>
+__device__ __forceinline__ RbApply rb_apply_begin(const float* const& parts, const int& rows, const float* const& coef, float* const& dbeta,
+                                                  float* const& dgamma, bool writes_params, int c4, f32x4 (&pv)[RB_PF], F&& then) {
+  rb_parts_issue(parts, rows, pv);
+  then();
+  RbApply k;
+  k.r.sc = *reinterpret_cast<const f32x4*>(coef + AP_SCALE + c4), k.r.sh = *reinterpret_cast<const f32x4*>(coef + AP_SHIFT + c4);
+  k.r.mu = *reinterpret_cast<const f32x4*>(coef + AP_MEAN + c4), k.r.rs = *reinterpret_cast<const f32x4*>(coef + AP_RSTD + c4);
+  const int t = threadIdx.x;
+  const bool acc_here = writes_params && t < 64;
+  k.db0 = acc_here && dbeta ? dbeta[t] : 0.f, k.dg0 = acc_here && dgamma ? dgamma[t] : 0.f;
+  return k;
+}
+__device__ __forceinline__ void rb_apply_finish(const float* const& parts, const int& rows, const f32x4 (&pv)[RB_PF], float* scr, const int64_t& M,
+                                                float* const& dbeta, float* const& dgamma, bool writes_params, int c4, RbApply& k, unsigned long long* ts = nullptr) {
+  rb_parts_finish(parts, rows, pv, scr, [&](int c, double sa, double sb) {
+    const BnBwdChannel r = bn_bwd_finish(sa, sb, M);
+    scr[1024 + c] = r.c1;
+    scr[1024 + 64 + c] = r.c2;
+    if (writes_params) {
+      if (dbeta) dbeta[c] = k.db0 + r.dbeta;
+      if (dgamma) dgamma[c] = k.dg0 + r.dgamma;
+    }
+  }, ts);
+  k.r.c1 = *reinterpret_cast<const f32x4*>(scr + 1024 + c4), k.r.c2 = *reinterpret_cast<const f32x4*>(scr + 1024 + 64 + c4);
 }
 
 // The tile is 64 pixels (whole images) x 64 channels per workgroup, 4 waves. In the 3x3 reduction loop wave w owns the w-th 16-channel
@@ -319,12 +356,7 @@ __global__ __launch_bounds__(256) void rb_conv_kernel(RbArgs a) {
     // workgroup in the same order (bitwise identical coefficients); workgroup 0 accumulates dgamma / dbeta
     // small L2-resident things first (partial rows, coefficients, accumulators), the cold operand rows behind them (in-order memory counter)
     f32x4 pv[RB_PF];
-    rb_parts_issue(e.bwd_parts, e.bwd_rows, pv);
-    pf_issue();
-    const f32x4 sc = *reinterpret_cast<const f32x4*>(e.bwd_coef + c4), sh = *reinterpret_cast<const f32x4*>(e.bwd_coef + 64 + c4);
-    const f32x4 mu = *reinterpret_cast<const f32x4*>(e.bwd_coef + 128 + c4), rs = *reinterpret_cast<const f32x4*>(e.bwd_coef + 192 + c4);
-    const bool acc_here = bid == 0 && t < 64;
-    const float db0 = acc_here && e.dbeta ? e.dbeta[t] : 0.f, dg0 = acc_here && e.dgamma ? e.dgamma[t] : 0.f;
+    RbApply k = rb_apply_begin(e.bwd_parts, e.bwd_rows, e.bwd_coef, e.dbeta, e.dgamma, bid == 0, c4, pv, pf_issue);
     f32x4 gv[NQ], xv[NQ], dm[NQ];
 #pragma unroll
     for (int q = 0; q < NQ; ++q) {
@@ -333,25 +365,15 @@ __global__ __launch_bounds__(256) void rb_conv_kernel(RbArgs a) {
       dm[q] = e.pro_drop ? *reinterpret_cast<const f32x4*>(e.pro_drop + (size_t)img_n[q] * 64 + c4) : one4;
     }
     zero_ring();   // while the loads are in flight
-    rb_parts_finish(e.bwd_parts, e.bwd_rows, pv, scr, [&](int c, double sa, double sb) {
-      const BnBwdChannel r = bn_bwd_finish(sa, sb, e.bwd_M);
-      scr[1024 + c] = r.c1;
-      scr[1024 + 64 + c] = r.c2;
-      if (bid == 0) {
-        if (e.dbeta) e.dbeta[c] = db0 + r.dbeta;
-        if (e.dgamma) e.dgamma[c] = dg0 + r.dgamma;
-      }
-    }
+    rb_apply_finish(e.bwd_parts, e.bwd_rows, pv, scr, e.bwd_M, e.dbeta, e.dgamma, bid == 0, c4, k
 #ifdef LVAE_RB_DBG
     , rb_ts
 #endif
     );
-    const f32x4 c1 = *reinterpret_cast<const f32x4*>(scr + 1024 + c4), c2 = *reinterpret_cast<const f32x4*>(scr + 1024 + 64 + c4);
     RB_STAMP(1);
 #pragma unroll
     for (int q = 0; q < NQ; ++q) {
-      const f32x4 g = gv[q] * act_grad4(xv[q] * sc + sh, bwd_act);
-      f32x4 v = bn_bwd_apply(g, xv[q], c1, c2, mu, rs, sc) * dm[q];
+      f32x4 v = ap_value4(k.r, gv[q], xv[q], bwd_act) * dm[q];
       if (!ok[q]) v = zero4;
       if (ok[q] && once && e.xt_out) store_wt4(e.xt_out + grow[q] * 64 + c4, v);
       put_interior(q, v);
@@ -366,12 +388,7 @@ __global__ __launch_bounds__(256) void rb_conv_kernel(RbArgs a) {
     if (AP) {
       // small L2-resident things first (partial rows, coefficients, accumulators), the cold operand rows behind them (in-order memory counter)
       f32x4 pv[RB_PF];
-      rb_parts_issue(e.ap_parts, e.ap_rows, pv);
-      pf_issue();
-      const f32x4 sc = *reinterpret_cast<const f32x4*>(e.ap_coef + c4), sh = *reinterpret_cast<const f32x4*>(e.ap_coef + 64 + c4);
-      const f32x4 mu = *reinterpret_cast<const f32x4*>(e.ap_coef + 128 + c4), rs = *reinterpret_cast<const f32x4*>(e.ap_coef + 192 + c4);
-      const bool acc_here = bid == 0 && t < 64;
-      const float db0 = acc_here && e.ap_dbeta ? e.ap_dbeta[t] : 0.f, dg0 = acc_here && e.ap_dgamma ? e.ap_dgamma[t] : 0.f;
+      RbApply k = rb_apply_begin(e.ap_parts, e.ap_rows, e.ap_coef, e.ap_dbeta, e.ap_dgamma, bid == 0, c4, pv, pf_issue);
       f32x4 xa[NQ], ad[NQ];
 #pragma unroll
       for (int q = 0; q < NQ; ++q) {
@@ -384,20 +401,10 @@ __global__ __launch_bounds__(256) void rb_conv_kernel(RbArgs a) {
         aa[q] = *reinterpret_cast<const f32x4*>(e.ab_in + grow[q] * 128 + c4);
         bb[q] = *reinterpret_cast<const f32x4*>(e.ab_in + grow[q] * 128 + 64 + c4);
       }
-      rb_parts_finish(e.ap_parts, e.ap_rows, pv, scr, [&](int c, double sa, double sb) {
-        const BnBwdChannel r = bn_bwd_finish(sa, sb, e.ap_M);
-        scr[1024 + c] = r.c1;
-        scr[1024 + 64 + c] = r.c2;
-        if (bid == 0) {
-          if (e.ap_dbeta) e.ap_dbeta[c] = db0 + r.dbeta;
-          if (e.ap_dgamma) e.ap_dgamma[c] = dg0 + r.dgamma;
-        }
-      });
-      const f32x4 c1 = *reinterpret_cast<const f32x4*>(scr + 1024 + c4), c2 = *reinterpret_cast<const f32x4*>(scr + 1024 + 64 + c4);
+      rb_apply_finish(e.ap_parts, e.ap_rows, pv, scr, e.ap_M, e.ap_dbeta, e.ap_dgamma, bid == 0, c4, k);
 #pragma unroll
       for (int q = 0; q < NQ; ++q) {
-        const f32x4 g = go[q] * act_grad4(xa[q] * sc + sh, ap_act);
-        const f32x4 v = bn_bwd_apply(g, xa[q], c1, c2, mu, rs, sc) + ad[q];
+        const f32x4 v = ap_value4(k.r, go[q], xa[q], ap_act) + ad[q];
         go[q] = v;
         if (ok[q] && once) store_wt4(e.ap_out + grow[q] * 64 + c4, v);
       }
@@ -951,18 +958,24 @@ extern "C" int lvae_resblock_conv_f32(const lvae_conv_desc* d, const lvae_rb_ext
     LVAE_REQUIRE(d->in_fold == nullptr && d->in_scale == nullptr, LVAE_EINVAL, "lvae_resblock_conv_f32: input transform with a backward prologue");
     LVAE_REQUIRE(al16_or_null(e.pro_drop) && al16_or_null(e.xt_out), LVAE_EALIGN, "lvae_resblock_conv_f32: pro_drop / xt_out must be 16-byte aligned");
   }
+  // the two applies as lvae_bn_apply views of their fields, for the one check, under the names this entry point's caller knows them by
+  // (a misaligned operand is LVAE_EINVAL here)
+  const int64_t M = (int64_t)d->N * d->H * d->W;
   if (pro == LVAE_RB_PRO_BN_APPLY) {
-    LVAE_REQUIRE(d->x && e.bwd_x && e.bwd_parts && e.bwd_coef && e.bwd_rows > 0 && e.bwd_M > 0 && al16_or_null(d->x) && al16_or_null(e.bwd_x) &&
-                     al16_or_null(e.bwd_parts) && al16_or_null(e.bwd_coef),
-                 LVAE_EINVAL, "lvae_resblock_conv_f32: BatchNorm-apply prologue needs x (= dh), bwd_x, bwd_parts / rows / M and the coefficient block, 16-byte aligned");
+    static constexpr const char* name[7] = {"bwd_parts", "bwd_coef", "d->x (= dh)", "bwd_x", "add", "xt_out", "pro_drop"};
+    const lvae_bn_apply v{e.bwd_parts, e.bwd_rows, e.bwd_act, e.bwd_M, e.bwd_coef, d->x, e.bwd_x, nullptr, e.dgamma, e.dbeta, e.xt_out, 0, 0, e.pro_drop};
+    const int rc = bn_apply_check("lvae_resblock_conv_f32", &v, M, BN_AP_DROP | BN_AP_OUT_OPTIONAL, name, LVAE_EINVAL);
+    if (rc) return rc;
   }
   if (pro == LVAE_RB_PRO_GATE_BWD) {
     LVAE_REQUIRE((e.dout || e.ap_parts) && e.ab_in && al16_or_null(e.dout) && al16_or_null(e.ab_in) && al16_or_null(e.dab), LVAE_EINVAL,
                  "lvae_resblock_conv_f32: gate-backward prologue needs dout (or the deferred apply that produces it) and ab_in (16-byte aligned tensors)");
     if (e.ap_parts != nullptr) {
-      LVAE_REQUIRE(e.ap_rows > 0 && e.ap_M > 0 && e.ap_coef && e.ap_dh && e.ap_x && e.ap_add && e.ap_out && al16_or_null(e.ap_parts) && al16_or_null(e.ap_coef) &&
-                       al16_or_null(e.ap_dh) && al16_or_null(e.ap_x) && al16_or_null(e.ap_add) && al16_or_null(e.ap_out),
-                   LVAE_EINVAL, "lvae_resblock_conv_f32: deferred apply needs ap_parts / ap_rows / ap_M, the coefficient block, ap_dh, ap_x, ap_add and ap_out, 16-byte aligned");
+      LVAE_REQUIRE(e.ap_add, LVAE_EINVAL, "lvae_resblock_conv_f32: the deferred apply needs ap_add");
+      static constexpr const char* name[7] = {"ap_parts", "ap_coef", "ap_dh", "ap_x", "ap_add", "ap_out", "drop"};
+      const lvae_bn_apply v{e.ap_parts, e.ap_rows, e.ap_act, e.ap_M, e.ap_coef, e.ap_dh, e.ap_x, e.ap_add, e.ap_dgamma, e.ap_dbeta, e.ap_out, 0, 0, nullptr};
+      const int rc = bn_apply_check("lvae_resblock_conv_f32", &v, M, BN_AP_ADD, name, LVAE_EINVAL);
+      if (rc) return rc;
     }
   } else {
     LVAE_REQUIRE(e.ap_parts == nullptr, LVAE_EINVAL, "lvae_resblock_conv_f32: the deferred apply goes with the gate-backward prologue");

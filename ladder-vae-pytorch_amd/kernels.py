@@ -390,7 +390,7 @@ def gate_bwd_fused_ws(x_like, weight, g, dweight=None):
 
 def gate_bwd_apply_ok(x_like, weight, g, dweight=None):
     """True when conv1x1_gate_bwd_wgrad takes the gate convolution (weight, g) on tensors shaped like x_like (N,H,W,C) with a deferred
-    BatchNorm-backward apply (PendingApply) forming its dout."""
+    BatchNorm-backward apply (BnBwdApply) forming its dout."""
     d = _gate_bwd_fused_desc(x_like, weight, g, dweight)
     return d is not None and bool(_C.load().lvae_conv1x1_gate_bwd_wgrad_apply_ok(C.byref(d)))
 
@@ -401,7 +401,7 @@ gate_bwd_fused_ok = gate_bwd_apply_ok   # (the name the residual-block tests ask
 def conv1x1_gate_bwd_wgrad(dout, ab, y, weight, g, act, dweight, dbias, out_scale=None, out_bf16=False, apply=None):
     """conv1x1_gate_bwd and the weight / bias gradient of the gate convolution in one persistent kernel (dab never leaves LDS):
     returns dx, and accumulates into dweight / dbias. Returns None when the shape is not supported (caller composes the two).
-    apply (PendingApply): dout does not exist yet; the kernel forms it from the deferred BatchNorm-backward apply and stores it to apply.out."""
+    apply (BnBwdApply): dout does not exist yet; the kernel forms it from the deferred BatchNorm-backward apply and stores it to apply.out."""
     _chk_nhwc(dout, 'dout')
     N, H, W, Cn = dout.shape
     if g.Cout != 2 * Cn or tuple(dweight.stride()) != tuple(weight.stride()):
@@ -415,10 +415,7 @@ def conv1x1_gate_bwd_wgrad(dout, ab, y, weight, g, act, dweight, dbias, out_scal
     if not need or (apply is not None and not lib.lvae_conv1x1_gate_bwd_wgrad_apply_ok(C.byref(d))):
         return None
     ws = workspace(need, dout.device)
-    ap = None
-    if apply is not None:
-        ap = _C.BnApply(ptr(apply.parts), apply.parts.shape[0], ACT[apply.act], N * H * W, ptr(apply.coef0), ptr_dt(apply.dh), ptr(apply.x),
-                        ptr(apply.add), ptr(apply.dgamma), ptr(apply.dbeta), ptr(apply.out), int(apply.dh.dtype == torch.bfloat16), 0)
+    ap = apply.struct(N * H * W) if apply is not None else None
     call('lvae_conv1x1_gate_bwd_wgrad_f32', C.byref(d), ptr(dout), ptr_dt(ab), ptr_dt(y), ACT[act], ptr(dweight), g.s_ci, g.s_co, ptr(dbias),
          ws.data_ptr(), ws.numel(), C.byref(ap) if ap is not None else None, stream_ptr())
     return dx
@@ -449,10 +446,7 @@ def conv1x1_gate_bwd_wgrad_recompute(dout, y, weight, g, bias, act, dweight, dbi
     e = RbExt()
     _rb_gate_ws(e, weight, g, dout.device, False)   # the forward's planes: the buffer (and its ready flag) the forward launch used
     ws = workspace(need, dout.device)
-    ap = None
-    if apply is not None:
-        ap = _C.BnApply(ptr(apply.parts), apply.parts.shape[0], ACT[apply.act], N * H * W, ptr(apply.coef0), ptr_dt(apply.dh), ptr(apply.x),
-                        ptr(apply.add), ptr(apply.dgamma), ptr(apply.dbeta), ptr(apply.out), int(apply.dh.dtype == torch.bfloat16), 0)
+    ap = apply.struct(N * H * W) if apply is not None else None
     call('lvae_conv1x1_gate_bwd_wgrad_recompute_f32', C.byref(d), ptr(dout), ptr(y), ACT[act], e.gate_ws, e.gate_ws_bytes, e.gate_ws_ready,
          e.gate_w, e.gate_w_sk, e.gate_w_sn, ptr(bias), ptr(dweight), g.s_ci, g.s_co, ptr(dbias), ws.data_ptr(), ws.numel(),
          C.byref(ap) if ap is not None else None, stream_ptr())
@@ -630,19 +624,73 @@ def _rb_bn_bwd(d, bn_bwd, dx):
     return parts
 
 
-class PendingApply:
-    """A BatchNorm-backward apply that its block did NOT launch: dx = BN'(dh; x) + add from the partial rows `parts`, to be formed by the
-    first backward launch of the block that consumes dx (the previous block of the chain) and stored to `out` (ops.ResBlockFn)."""
-    __slots__ = ('parts', 'dh', 'x', 'coef0', 'act', 'dgamma', 'dbeta', 'add', 'out')
+class BnBwdApply:
+    """One BatchNorm-backward apply, dx = BN'(dh; x) [* drop] [+ add], from the partial rows `parts` the producer of dh left: what a fused
+    launch that forms dx itself is handed (struct / fill_ext), what a block that does not launch its last apply leaves for the consumer
+    of dx (ops.ResBlockFn), and the stand-alone launch (run). coef = (scale, shift, mean, rstd) as bn_stats / bn_finalize_parts return them;
+    dgamma / dbeta are accumulated; drop: the Dropout2d mask (N, C); out: the fp32 tensor dx goes to (None: allocated when a launch stores it)."""
+    __slots__ = ('parts', 'dh', 'x', 'coef', 'act', 'dgamma', 'dbeta', 'add', 'drop', 'out')
+
+    def __init__(self, parts, dh, x, coef, act, dgamma, dbeta, add=None, drop=None, out=None):
+        self.parts, self.dh, self.x, self.coef, self.act, self.dgamma, self.dbeta = parts, dh, x, tuple(coef), act, dgamma, dbeta
+        self.add, self.drop, self.out = add, drop, out
+
+    def _block(self):
+        if not bn_coef_block(*self.coef):
+            raise _C.LvaeHipError("BnBwdApply: a fused launch reads the four coefficient vectors as one (4, C) block")
+        return self.coef[0]
+
+    def _out(self):
+        if self.out is None:
+            self.out = torch.empty(self.x.shape, dtype=torch.float32, device=self.x.device)
+        return ptr(self.out)
+
+    def struct(self, M, store_out=True):
+        """The lvae_bn_apply of a launch over M = N*H*W pixels (store_out=False: the launch forms dx without storing it)."""
+        return _C.BnApply(ptr(self.parts), self.parts.shape[0], ACT[self.act], M, ptr(self._block()), ptr_dt(self.dh), ptr(self.x), ptr(self.add),
+                          ptr(self.dgamma), ptr(self.dbeta), self._out() if store_out else None, int(self.dh.dtype == torch.bfloat16), 0,
+                          ptr(self.drop))
+
+    def fill_ext(self, e, which):
+        """As a prologue of lvae_resblock_conv_f32: 'bwd' (RB_PRO_BN_APPLY: dh is the launch's x, out its xt_out) or 'ap' (deferred)."""
+        head = ptr(self.parts), self.parts.shape[0], ACT[self.act], self.x.numel() // self.x.shape[-1], ptr(self._block()), ptr(self.x)
+        if which == 'ap':
+            e.ap_parts, e.ap_rows, e.ap_act, e.ap_M, e.ap_coef, e.ap_x = head
+            e.ap_dh, e.ap_add, e.ap_dgamma, e.ap_dbeta, e.ap_out = ptr(self.dh), ptr(self.add), ptr(self.dgamma), ptr(self.dbeta), self._out()
+        else:
+            e.bwd_parts, e.bwd_rows, e.bwd_act, e.bwd_M, e.bwd_coef, e.bwd_x = head
+            e.dgamma, e.dbeta, e.pro_drop, e.xt_out = ptr(self.dgamma), ptr(self.dbeta), ptr(self.drop), self._out()
+
+    def run(self, out_bf16=False):
+        """The apply as a launch of its own (any four coefficient vectors). Returns dx."""
+        sc, sh, mean, rstd = self.coef
+        return affine_act_bwd_parts(self.parts, self.dh, self.x, sc, sh, self.act, mean, rstd, self.dgamma, self.dbeta, drop=self.drop,
+                                    add=self.add, out_bf16=out_bf16, out=self.out)
+
+
+class PendingApply(BnBwdApply):
+    """BnBwdApply as the existing tests construct it: coef0 = row 0 of the (4, C) coefficient block, add and out positional. The product
+    code builds BnBwdApply; this form and _flat_apply stay so that those tests run unedited against the single description."""
 
     def __init__(self, parts, dh, x, coef0, act, dgamma, dbeta, add, out):
-        self.parts, self.dh, self.x, self.coef0, self.act, self.dgamma, self.dbeta, self.add, self.out = parts, dh, x, coef0, act, dgamma, dbeta, add, out
+        Cn = coef0.numel()
+        super().__init__(parts, dh, x, torch.as_strided(coef0, (4, Cn), (Cn, 1)).unbind(0), act, dgamma, dbeta, add=add, out=out)
+
+
+def _flat_apply(args, drop=None, out=None):
+    """(apply, the arguments behind it) of a wrapper's positional tail: a BnBwdApply, or in its place the seven values parts, dh, x, coef0,
+    act, dgamma, dbeta (with drop / out as the wrapper got them) of the existing tests' calls."""
+    if isinstance(args[0], BnBwdApply):
+        return args[0], args[1:]
+    apply = PendingApply(*args[:7], None, out)
+    apply.drop = drop
+    return apply, args[7:]
 
 
 def rb_gate_dgrad(dout, ab, gate_w, gate_g, act, drop, weight, g, bn_bwd, prefetch=None, apply=None, nsplit=0):
     """Backward of rb_conv_gate up to the block's second BatchNorm in one launch: dab = gate'(dout, ab), dy2 = (dab . Wg^T) * drop,
     dh2 = dgrad3x3(dy2) with the BatchNorm-backward sums of bn_bwd = (y1, coef block row 0, act). Returns (dab, dy2, dh2, parts).
-    apply (PendingApply): dout does not exist yet; the launch forms it in its prologue and stores it to apply.out (= dout's memory)."""
+    apply (BnBwdApply): dout does not exist yet; the launch forms it in its prologue and stores it to apply.out (= dout's memory)."""
     N, H, W, Cn = dout.shape
     dev = dout.device
     dab = torch.empty_like(ab)
@@ -655,32 +703,31 @@ def rb_gate_dgrad(dout, ab, gate_w, gate_g, act, drop, weight, g, bn_bwd, prefet
     e.act = ACT[act]
     e.dout, e.ab_in, e.dab, e.pro_drop, e.xt_out = ptr(dout), ptr(ab), ptr(dab), ptr(drop), ptr(dy2)
     if apply is not None:
-        e.ap_parts, e.ap_rows, e.ap_act, e.ap_M = ptr(apply.parts), apply.parts.shape[0], ACT[apply.act], N * H * W
-        e.ap_coef, e.ap_dh, e.ap_x, e.ap_add = ptr(apply.coef0), ptr(apply.dh), ptr(apply.x), ptr(apply.add)
-        e.ap_dgamma, e.ap_dbeta, e.ap_out = ptr(apply.dgamma), ptr(apply.dbeta), ptr(apply.out)
+        apply.fill_ext(e, 'ap')
     parts = _rb_bn_bwd(d, bn_bwd, dh)
     _rb_prefetch(e, prefetch)
     call('lvae_resblock_conv_f32', C.byref(d), C.byref(e), stream_ptr())
     return dab, dy2, dh, parts
 
 
-def rb_apply_dgrad(parts_in, dh_in, x_bn, coef0, act, dgamma, dbeta, drop, weight, g, bn_bwd, prefetch=None, nsplit=0):
-    """BatchNorm backward (training mode; parts_in = the sums the producer of dh_in left) + Dropout2d mask + dgrad of the block's first
-    convolution in one launch: dy1 = BN'(dh_in; x_bn) * drop, dh1 = dgrad3x3(dy1) with the sums of bn_bwd = (x, coef block row 0, act).
-    coef0: row 0 of the (4, C) coefficient block of the BatchNorm being differentiated. Returns (dy1, dh1, parts)."""
-    N, H, W, Cn = dh_in.shape
-    dev = dh_in.device
-    dy1 = torch.empty((N, H, W, Cn), dtype=torch.float32, device=dev)
-    dh = torch.empty((N, H, W, g.Cin), dtype=torch.float32, device=dev)
-    d, _ = _rb_desc(dh_in, weight, g, True, dh)
+def rb_apply_dgrad(apply, *rest, bn_bwd, prefetch=None, nsplit=0):
+    """BatchNorm backward (training mode) + Dropout2d mask + dgrad of the block's first convolution in one launch: dy1 = the apply
+    (BnBwdApply, with the block's drop) stored to apply.out, dh1 = dgrad3x3(dy1) with the sums of bn_bwd = (x, coef block row 0, act).
+    Called as rb_apply_dgrad(apply, weight, g, bn_bwd=...). Returns (dy1, dh1, parts)."""
+    apply, rest = _flat_apply((apply,) + rest)
+    if len(rest) == 3:   # (the flat form carries drop behind its seven values)
+        apply.drop, rest = rest[0], rest[1:]
+    weight, g = rest
+    N, H, W, _ = apply.dh.shape
+    dh = torch.empty((N, H, W, g.Cin), dtype=torch.float32, device=apply.dh.device)
+    d, _ = _rb_desc(apply.dh, weight, g, True, dh)
     e = RbExt()
     e.prologue, e.epilogue, e.nsplit = _C.RB_PRO_BN_APPLY, _C.RB_EPI_PLAIN, nsplit
-    e.bwd_parts, e.bwd_rows, e.bwd_act, e.bwd_M = ptr(parts_in), parts_in.shape[0], ACT[act], N * H * W
-    e.bwd_coef, e.bwd_x, e.dgamma, e.dbeta, e.pro_drop, e.xt_out = ptr(coef0), ptr(x_bn), ptr(dgamma), ptr(dbeta), ptr(drop), ptr(dy1)
+    apply.fill_ext(e, 'bwd')
     parts = _rb_bn_bwd(d, bn_bwd, dh)
     _rb_prefetch(e, prefetch)
     call('lvae_resblock_conv_f32', C.byref(d), C.byref(e), stream_ptr())
-    return dy1, dh, parts
+    return apply.out, dh, parts
 
 
 def bn_coef_block(scale, shift, mean, rstd):
@@ -746,10 +793,11 @@ def conv2d_wgrad_apply_ok(x, weight, g):
     return bool(_C.load().lvae_conv2d_wgrad_apply_ok(C.byref(d)))
 
 
-def conv2d_wgrad_apply(x, weight, g, dweight, dbias, parts, dh, xbn, coef0, act, dgamma, dbeta, drop=None, in_scale=None, in_shift=None, in_act=None):
-    """conv2d_wgrad whose dy operand is the BatchNorm-backward apply that has not run: dy = affine_act_bwd_parts(parts, dh, xbn, ..., drop=drop)
-    is formed inside the weight-gradient kernel, stored and returned (the dgrad that follows reads it). coef0: row 0 of the (4, C) coefficient
-    block of the BatchNorm being differentiated; dgamma / dbeta are accumulated. Only where conv2d_wgrad_apply_ok()."""
+def conv2d_wgrad_apply(x, weight, g, dweight, dbias, *apply, drop=None, in_scale=None, in_shift=None, in_act=None):
+    """conv2d_wgrad whose dy operand is the BatchNorm-backward apply that has not run: dy = apply.run() (a BnBwdApply, with the block's drop)
+    is formed inside the weight-gradient kernel, stored to apply.out and returned (the dgrad that follows reads it). Only where
+    conv2d_wgrad_apply_ok(). Called as conv2d_wgrad_apply(x, weight, g, dweight, dbias, apply, ...)."""
+    apply, _ = _flat_apply(apply, drop)
     _chk_nhwc(x, 'x')
     N, H, W, _ = x.shape
     if tuple(dweight.stride()) != tuple(weight.stride()):
@@ -757,10 +805,9 @@ def conv2d_wgrad_apply(x, weight, g, dweight, dbias, parts, dh, xbn, coef0, act,
     d = _desc(g, weight, x, None, N, H, W, H, W, g.Cout, g.s_ci, g.s_co, GATHER_CONV, None, in_scale, in_shift, in_act)
     need = _C.load().lvae_conv2d_wgrad_workspace(C.byref(d))
     ws = workspace(need, x.device)
-    dy = torch.empty((N, H, W, g.Cout), dtype=torch.float32, device=x.device)
-    ap = _C.BnApply(ptr(parts), parts.shape[0], ACT[act], N * H * W, ptr(coef0), ptr(dh), ptr(xbn), None, ptr(dgamma), ptr(dbeta), ptr(dy), 0, 0, ptr(drop))
+    ap = apply.struct(N * H * W)
     call('lvae_conv2d_wgrad_apply_f32', C.byref(d), C.byref(ap), ptr(dweight), ptr(dbias), ws.data_ptr(), ws.numel(), stream_ptr())
-    return dy
+    return apply.out
 
 
 def _wgrad_pair_descs(x_a, w_a, g_a, x_b, w_b, g_b, in_a=(None, None, None), in_b=(None, None, None)):
@@ -791,11 +838,14 @@ def conv2d_wgrad_pair_schedule(x_a, w_a, g_a, x_b, w_b, g_b):
     return tuple(out[:3]), tuple(out[3:])
 
 
-def conv2d_wgrad_pair(x, weight, g, dweight, dbias, parts, dh, xbn, coef0, act, dgamma, dbeta, dy_b, weight_b, g_b, dweight_b, dbias_b,
-                      drop=None, in_scale=None, in_shift=None, in_act=None, in_scale_b=None, in_shift_b=None, in_act_b=None, out=None):
-    """conv2d_wgrad_apply(x, weight, g, dweight, dbias, parts, dh, xbn, ...) and conv2d_wgrad(xbn, dy_b, weight_b, g_b, dweight_b, dbias_b,
+def conv2d_wgrad_pair(x, weight, g, dweight, dbias, *rest, drop=None, out=None, in_scale=None, in_shift=None, in_act=None, in_scale_b=None,
+                      in_shift_b=None, in_act_b=None):
+    """conv2d_wgrad_apply(x, weight, g, dweight, dbias, apply, ...) and conv2d_wgrad(apply.x, dy_b, weight_b, g_b, dweight_b, dbias_b,
     in_scale_b ...) of one residual block as one launch and one slab reduce (conv2 reads the tensor whose BatchNorm conv1's apply
-    differentiates). Returns the stored dy of A (out: written into this tensor instead of a new one). Only where conv2d_wgrad_pair_ok()."""
+    differentiates). Returns the stored dy of A (apply.out). Only where conv2d_wgrad_pair_ok(). Called as conv2d_wgrad_pair(x, weight, g,
+    dweight, dbias, apply, dy_b, weight_b, g_b, dweight_b, dbias_b, ...)."""
+    apply, (dy_b, weight_b, g_b, dweight_b, dbias_b) = _flat_apply(rest, drop, out)
+    xbn = apply.x
     _chk_nhwc(x, 'x')
     _chk_nhwc(xbn, 'xbn')
     _chk_nhwc(dy_b, 'dy_b')
@@ -809,11 +859,10 @@ def conv2d_wgrad_pair(x, weight, g, dweight, dbias, parts, dh, xbn, coef0, act, 
     d_b.y_dtype = _dt(dy_b)
     need = _C.load().lvae_conv2d_wgrad_pair_workspace(C.byref(d_a), C.byref(d_b))
     ws = workspace(need, x.device)
-    dy = out if out is not None else torch.empty((N, H, W, g.Cout), dtype=torch.float32, device=x.device)
-    ap = _C.BnApply(ptr(parts), parts.shape[0], ACT[act], N * H * W, ptr(coef0), ptr(dh), ptr(xbn), None, ptr(dgamma), ptr(dbeta), ptr(dy), 0, 0, ptr(drop))
+    ap = apply.struct(N * H * W)
     call('lvae_conv2d_wgrad_pair_f32', C.byref(d_a), C.byref(ap), C.byref(d_b), ptr_dt(dy_b), ptr(dweight), ptr(dbias), ptr(dweight_b), ptr(dbias_b),
          ws.data_ptr(), ws.numel(), stream_ptr())
-    return dy
+    return apply.out
 
 
 def conv1x1_dgrad_cat(dy, weight, g, C1):
@@ -850,7 +899,7 @@ def cat_bwd_ws(dy_like, weight, g, C1, dweight=None):
 
 
 def cat_bwd_apply_ok(dy_like, weight, g, C1, dweight=None):
-    """True when conv1x1_cat_bwd takes the merge convolution (weight, g) with a deferred BatchNorm-backward apply (PendingApply) as its dy."""
+    """True when conv1x1_cat_bwd takes the merge convolution (weight, g) with a deferred BatchNorm-backward apply (BnBwdApply) as its dy."""
     d = _cat_bwd_desc(dy_like, weight, g, C1, dweight)
     return d is not None and bool(_C.load().lvae_conv1x1_cat_bwd_apply_ok(C.byref(d), C1))
 
@@ -858,7 +907,7 @@ def cat_bwd_apply_ok(dy_like, weight, g, C1, dweight=None):
 def conv1x1_cat_bwd(dy, x, x2, weight, g, dweight, dbias, apply=None, store_dy=False, max_workgroups=0, scratch=None):
     """The whole backward of a 1x1 convolution over the channel concat (x, x2) in one persistent kernel (+ its slab reduce): returns (dx, dx2)
     and accumulates into dweight / dbias; None, with nothing launched or written, when the library does not take it (the caller runs
-    conv2d_wgrad + conv1x1_dgrad_cat). apply (PendingApply): dy does not exist yet (dy is apply.out, unwritten); the kernel forms it from
+    conv2d_wgrad + conv1x1_dgrad_cat). apply (BnBwdApply): dy does not exist yet (dy is apply.out, unwritten); the kernel forms it from
     the deferred BatchNorm-backward apply and stores it to apply.out only with store_dy. max_workgroups caps the grid (0: default);
     scratch: a uint8 buffer to use instead of the shared workspace (too small: None)."""
     _chk_nhwc(dy, 'dy')
@@ -878,8 +927,7 @@ def conv1x1_cat_bwd(dy, x, x2, weight, g, dweight, dbias, apply=None, store_dy=F
     ap = None
     if apply is not None:
         d.x = None
-        ap = _C.BnApply(ptr(apply.parts), apply.parts.shape[0], ACT[apply.act], N * H * W, ptr(apply.coef0), ptr(apply.dh), ptr(apply.x),
-                        ptr(apply.add), ptr(apply.dgamma), ptr(apply.dbeta), ptr(apply.out) if store_dy else None, 0, 0)
+        ap = apply.struct(N * H * W, store_out=store_dy)
     dx = torch.empty((N, H, W, C1), dtype=torch.float32, device=dy.device)
     dx2 = torch.empty((N, H, W, g.Cin - C1), dtype=torch.float32, device=dy.device)
     call('lvae_conv1x1_cat_bwd_f32', C.byref(d), ptr(x), ptr(x2), ptr(dx), ptr(dx2), ptr(dweight), ptr(dbias),

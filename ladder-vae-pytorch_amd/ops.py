@@ -167,7 +167,7 @@ class ConvFn(Function):
         w = mod.weight
         if x2 is not None:
             # merge / skip 1x1: dgrad of both halves and the weight gradient in one persistent launch, which also forms a dy that the
-            # residual block behind the merge left as a PendingApply (merge_announces); anything it does not take goes the old way
+            # residual block behind the merge left as a BnBwdApply (merge_announces); anything it does not take goes the old way
             st = getattr(mod, 'sched', None)
             pend = st.take_pending(dy) if st is not None else None
             if (RB.switches.merge_bwd_fused and not ctx.out_act and w.requires_grad and ctx.needs_input_grad[0] and ctx.needs_input_grad[1] and
@@ -177,9 +177,7 @@ class ConvFn(Function):
                 if both is not None:
                     return both + (None,) * 5
             if pend is not None:   # never dropped: the apply the block did not launch runs here, into the tensor the block returned
-                C = pend.coef0.numel()
-                sc, sh, mean, rstd = torch.as_strided(pend.coef0, (4, C), (C, 1)).unbind(0)
-                K.affine_act_bwd_parts(pend.parts, pend.dh, pend.x, sc, sh, pend.act, mean, rstd, pend.dgamma, pend.dbeta, add=pend.add, out=pend.out)
+                pend.run()
         if ctx.out_act:
             dy = K.act_bwd_from_out(dy, y, ctx.out_act)
         if w.requires_grad:
@@ -294,7 +292,7 @@ def _fwd_per_op(call, x, blk, m1, m2, training):
 
 # The last launch of a residual block's backward is the BatchNorm-1 apply, dx = BN1'(dh1; x) + dout. When the tensor x is exactly the output
 # of the previous residual block of the chain (resblock.Handover) and that block's backward starts with a kernel that can form its `dout`
-# itself (BlockPlan.accepts), the apply is not launched: the block returns an unwritten dx and leaves a kernels.PendingApply with the producer,
+# itself (BlockPlan.accepts), the apply is not launched: the block returns an unwritten dx and leaves a kernels.BnBwdApply with the producer,
 # whose first backward launch computes dx in its prologue and stores it there. This assumes what loss.backward() does: the backward pass goes on
 # through the producing block (torch.autograd.grad w.r.t. a tensor BETWEEN two such blocks would get the unwritten dx). LVAE_DEFER_APPLY=0: never.
 class ResBlockFn(Function):
@@ -335,16 +333,16 @@ class ResBlockFn(Function):
                       K.bn_coef_block(*coef2))
             dh2, parts2 = _bwd_half(ctx, cv2, bn2, y1, dy2, coef2, wgrad_done=paired)
             absorbed = (plan.wgrad_absorbs_apply and parts2 is not None and _side['stream'] is None and dh2.dtype == torch.float32)
+            apply2 = K.BnBwdApply(parts2, dh2, y1, coef2, act, grad_buf(bn2.weight), grad_buf(bn2.bias), drop=m1) if absorbed else None
             if paired and absorbed:
-                dy1 = K.conv2d_wgrad_pair(x, cv1.weight, cv1.geom(), grad_buf(cv1.weight), grad_buf(cv1.bias), parts2, dh2, y1, sc2, act,
-                                          grad_buf(bn2.weight), grad_buf(bn2.bias), dy2, cv2.weight, cv2.geom(), grad_buf(cv2.weight),
-                                          grad_buf(cv2.bias), drop=m1, in_scale=sc1, in_shift=sh1, in_act=act, in_scale_b=sc2, in_shift_b=sh2,
-                                          in_act_b=act)
+                dy1 = K.conv2d_wgrad_pair(x, cv1.weight, cv1.geom(), grad_buf(cv1.weight), grad_buf(cv1.bias), apply2, dy2, cv2.weight, cv2.geom(),
+                                          grad_buf(cv2.weight), grad_buf(cv2.bias), in_scale=sc1, in_shift=sh1, in_act=act, in_scale_b=sc2,
+                                          in_shift_b=sh2, in_act_b=act)
             elif absorbed:
                 # >= 16x16 levels (fp32): the BatchNorm-2 apply runs inside conv1's weight-gradient kernel, which needs its result as an operand
                 # anyway (and stores it for the dgrad below): one launch, its finalize and one tensor pass less
-                dy1 = K.conv2d_wgrad_apply(x, cv1.weight, cv1.geom(), grad_buf(cv1.weight), grad_buf(cv1.bias), parts2, dh2, y1, sc2, act,
-                                           grad_buf(bn2.weight), grad_buf(bn2.bias), drop=m1, in_scale=sc1, in_shift=sh1, in_act=act)
+                dy1 = K.conv2d_wgrad_apply(x, cv1.weight, cv1.geom(), grad_buf(cv1.weight), grad_buf(cv1.bias), apply2, in_scale=sc1, in_shift=sh1,
+                                           in_act=act)
             else:
                 if paired:   # the dgrad left no partial sums after all: conv2's gradient as a launch of its own, late
                     wgrad(y1, dy2, cv2.weight, cv2.geom(), grad_buf(cv2.weight), grad_buf(cv2.bias), in_scale=sc2, in_shift=sh2, in_act=act)
@@ -352,7 +350,7 @@ class ResBlockFn(Function):
             dh1, parts1 = _bwd_half(ctx, cv1, blk.bn1, x, dy1, coef1, wgrad_done=absorbed)
         if parts1 is not None and ctx.defer is not None and (dh1.dtype == torch.float32 or ctx.defer[1] == 'any-dh') and K.bn_coef_block(*coef1):
             dx = torch.empty_like(x)   # left to the first backward launch of the block that produced x
-            ctx.defer[0].pending = K.PendingApply(parts1, dh1, x, sc1, act, grad_buf(blk.bn1.weight), grad_buf(blk.bn1.bias), dout, dx)
+            ctx.defer[0].pending = K.BnBwdApply(parts1, dh1, x, coef1, act, grad_buf(blk.bn1.weight), grad_buf(blk.bn1.bias), add=dout, out=dx)
         else:
             dx = _bwd_apply(ctx, blk.bn1, parts1, dh1, x, coef1, add=dout)
         return (dx, None, None, None, None, None) + (None,) * (len(ctx.needs_input_grad) - 6)
@@ -369,7 +367,7 @@ def _bwd_whole_image(blk, dout, x, y1, y2, ab, coef1, coef2, m1, m2):
     if gw.requires_grad:
         wgrad(y2, dab, gw, gate.geom(), grad_buf(gw), grad_buf(gate.bias))
     wgrad(y1, dy2, w2, cv2.geom(), grad_buf(w2), grad_buf(cv2.bias), in_scale=coef2[0], in_shift=coef2[1], in_act=act)
-    dy1, dh1, parts1 = K.rb_apply_dgrad(parts2, dh2, y1, coef2[0], act, grad_buf(bn2.weight), grad_buf(bn2.bias), m1, w1, cv1.geom(),
+    dy1, dh1, parts1 = K.rb_apply_dgrad(K.BnBwdApply(parts2, dh2, y1, coef2, act, grad_buf(bn2.weight), grad_buf(bn2.bias), drop=m1), w1, cv1.geom(),
                                         bn_bwd=(x, coef1[0], act), prefetch=st.next_ranges('bwd'), nsplit=RB.switches.rb_nsplit)
     wgrad(x, dy1, w1, cv1.geom(), grad_buf(w1), grad_buf(cv1.bias), in_scale=coef1[0], in_shift=coef1[1], in_act=act)
     return dh1, parts1
@@ -416,7 +414,7 @@ def _bwd_apply(ctx, bn, parts, dh, h, coef, drop=None, add=None, out_bf16=False)
     train = bn is not None and ctx.training
     dgamma, dbeta = (grad_buf(bn.weight), grad_buf(bn.bias)) if train else (None, None)
     if parts is not None:
-        return K.affine_act_bwd_parts(parts, dh, h, sc, sh, ctx.blk.act, mean, rstd, dgamma, dbeta, drop=drop, add=add, out_bf16=out_bf16)
+        return K.BnBwdApply(parts, dh, h, coef, ctx.blk.act, dgamma, dbeta, add=add, drop=drop).run(out_bf16=out_bf16)
     return K.affine_act_bwd(dh, h, sc, sh, ctx.blk.act, train, mean, rstd, dgamma, dbeta, drop=drop, add=add)
 
 

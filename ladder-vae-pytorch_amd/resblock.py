@@ -139,7 +139,7 @@ def tagged(out, blk, plan, parts, pivot):
 
 class BlockState:
     """What outlives a call on the block itself (lib.nn.ResidualBlock.sched; not a parameter, a buffer or a submodule).
-    pending: the kernels.PendingApply the consuming block's backward left for this block's first backward launch.
+    pending: the kernels.BnBwdApply the consuming block's backward left for this block's first backward launch.
     first / next, per direction 'fwd' | 'bwd': the whole-image blocks of the low-resolution levels run as one dependent chain, and every launch
     streams weights of its own that are cold in the L2s. Inside a block the first launch warms the L2s for the second (kernels.rb_weight_ranges);
     ACROSS blocks the order is only known from the previous step: each block remembers which whole-image block ran right after it and what

@@ -10,6 +10,8 @@ fed explicit coefficients computed in float64 from the full data. Sites:
   * resblock_img.hip  rb_parts_issue / rb_parts_finish: forward fold (PRO_AFFINE), BatchNorm-backward apply (PRO_BN_APPLY) and the deferred
                       apply in front of the gate backward (round 5)
   * conv1x1_gate_bwd_fused.hip  the deferred apply of the persistent gate-backward kernel (round 5)
+  * bn_apply.h        the reducer of the persistent gate backward and the merge backward, and its copy in the Winograd weight gradient, at
+                      the edges of their row loop
 """
 import math
 import types
@@ -93,7 +95,7 @@ def bwd_parts(dh, x, coef, rows):
     return parts.float().contiguous(), dx, g.reshape(-1, C).sum(0), (g * xh).reshape(-1, C).sum(0)
 
 
-@pytest.mark.parametrize('rows', [1, 3, 130])
+@pytest.mark.parametrize('rows', [1, 3, 130, 257])
 @pytest.mark.parametrize('shape', [(64, 4, 4), (7, 2, 2), (64, 16, 16), (256, 8, 8)])
 def test_batchnorm_backward_apply_from_few_partial_rows(K, shape, rows):
     """lvae_affine_act_bwd_parts_f32, and the same apply inside the fused launches (PRO_BN_APPLY; deferred in front of the gate backward)."""
@@ -178,5 +180,63 @@ def test_deferred_apply_of_the_persistent_gate_backward_from_few_rows(K, rows):
     assert dx is not None
     torch.cuda.synchronize()
     assert rel(out, dx_ref + add.double()) < 2e-6
+    torch.testing.assert_close(dbet.double(), sg, rtol=1e-4, atol=1e-3)
+    torch.testing.assert_close(dgam.double(), sgx, rtol=1e-4, atol=1e-3)
+
+
+def run_gate_bwd(K, g, rn, ap, shape):
+    N, H, W = shape
+    wg = packed_weight(torch.randn(2 * C, C, 1, 1, generator=g) / 8)
+    dx = K.conv1x1_gate_bwd_wgrad(ap.out, rn(N, H, W, 2 * C), rn(N, H, W, C), wg, K.ConvGeom(wg, 1, 0), 'elu', torch.zeros_like(wg),
+                                  torch.zeros(2 * C, device='cuda'), apply=ap)
+    assert dx is not None
+
+
+def run_cat_bwd(K, g, rn, ap, shape):
+    N, H, W = shape
+    w = packed_weight(torch.randn(C, 2 * C, 1, 1, generator=g) / (2 * C) ** 0.5)
+    both = K.conv1x1_cat_bwd(ap.out, rn(N, H, W, C), rn(N, H, W, C), w, K.ConvGeom(w, 1, 0), torch.zeros_like(w), torch.zeros(C, device='cuda'),
+                             apply=ap, store_dy=True, max_workgroups=3)
+    assert both is not None
+
+
+def run_wgrad_apply(K, g, rn, ap, shape, drop):
+    N, H, W = shape
+    w = packed_weight(torch.randn(C, C, 3, 3, generator=g) / 24)
+    xin = rn(N, H, W, C)
+    assert K.conv2d_wgrad_apply_ok(xin, w, K.ConvGeom(w, 1, 1))
+    dy = K.conv2d_wgrad_apply(xin, w, K.ConvGeom(w, 1, 1), torch.zeros_like(w), torch.zeros(C, device='cuda'), ap.parts, ap.dh, ap.x, ap.coef0,
+                              'elu', ap.dgamma, ap.dbeta, drop=drop)
+    ap.out.copy_(dy)
+
+
+# the 512-thread reducer of the three launches (csrc/bn_apply.h; the Winograd kernel's copy): 16 row groups, 128 rows per trip of its loop. One row; a partly
+# filled first batch; exactly one trip; one row into the second; two trips and one row. Each consumer at the smallest shape it takes.
+@pytest.mark.parametrize('rows', [1, 17, 128, 129, 257])
+@pytest.mark.parametrize('consumer,shape,extra', [(run_gate_bwd, (64, 16, 16), 'add'), (run_cat_bwd, (4, 8, 8), 'add'),
+                                                  (run_wgrad_apply, (64, 16, 16), 'drop')])
+def test_shared_reducer_of_the_fused_launches_at_its_row_edges(K, consumer, shape, extra, rows):
+    """dx = BN'(dh; x) + add (or * drop) as the launch forms and stores it, and dgamma / dbeta, against the float64 statement of bwd_parts."""
+    N, H, W = shape
+    g = torch.Generator().manual_seed(1000 + rows + N)
+    rn = lambda *s: torch.randn(*s, generator=g).cuda()
+    x, dh = rn(N, H, W, C), rn(N, H, W, C)
+    bn = make_bn(g)
+    coef = K.bn_stats(x, bn.weight, bn.bias, None, None)
+    parts, dx_ref, sg, sgx = bwd_parts(dh, x, coef, rows)
+    assert parts.shape[0] == rows
+    add = rn(N, H, W, C) if extra == 'add' else None
+    drop = ((torch.rand(N, C, generator=g) < 0.8).float() / 0.8).cuda() if extra == 'drop' else None
+    want = dx_ref + add.double() if extra == 'add' else dx_ref * drop.double().view(N, 1, 1, C)
+    dgam, dbet = torch.zeros(C, device='cuda'), torch.zeros(C, device='cuda')
+    ap = types.SimpleNamespace(parts=parts, dh=dh, x=x, coef0=coef[0], dgamma=dgam, dbeta=dbet, out=torch.full_like(x, float('nan')))
+    if extra == 'add':
+        ap = K.PendingApply(parts, dh, x, coef[0], 'elu', dgam, dbet, add, ap.out)
+        consumer(K, g, rn, ap, shape)
+    else:
+        consumer(K, g, rn, ap, shape, drop)
+    torch.cuda.synchronize()
+    print('%s rows %d: dx %.3g' % (consumer.__name__, rows, rel(ap.out, want)))
+    assert rel(ap.out, want) < 2e-6
     torch.testing.assert_close(dbet.double(), sg, rtol=1e-4, atol=1e-3)
     torch.testing.assert_close(dgam.double(), sgx, rtol=1e-4, atol=1e-3)

@@ -56,7 +56,7 @@ def timed(run, reps=20, replays=7):
 fwd = lambda want: K.rb_conv_gate(y1, w2, g2, b2, 'elu', drop, wg, gg, bg, x, 'elu', coef=coef, stats_pivot=pivot, want_ab=want)
 y2, ab = fwd(True)[:2]
 K.prepared.prepare_all()   # the planes of both directions: no launch rewrites them inside the timed graphs
-pend = lambda: K.PendingApply(parts, dh, xb, cb[0], 'elu', dga, dbe, add, out)
+pend = lambda: K.BnBwdApply(parts, dh, xb, cb, 'elu', dga, dbe, add=add, out=out)
 
 runs = (('forward, ab stored', lambda: fwd(True)),
         ('forward, no ab', lambda: fwd(False)),

@@ -30,7 +30,7 @@ dw, db = torch.zeros_like(wg), torch.zeros(2 * C, device='cuda')
 
 def run():
     if AP:
-        pend = K.PendingApply(parts, dh, x, coef[0], 'elu', dgam, dbet, add, out)
+        pend = K.BnBwdApply(parts, dh, x, coef, 'elu', dgam, dbet, add=add, out=out)
         return K.conv1x1_gate_bwd_wgrad(out, ab, y2, wg, geg, 'elu', dw, db, apply=pend)
     return K.conv1x1_gate_bwd_wgrad(dout, ab, y2, wg, geg, 'elu', dw, db)
 

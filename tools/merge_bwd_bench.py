@@ -51,7 +51,7 @@ coef = K.bn_stats(xbn, torch.ones(C, device='cuda'), torch.zeros(C, device='cuda
 parts = rn(128, 2, C)   # as many partial rows as the Winograd dgrad of this level leaves
 dgam, dbet = torch.zeros(C, device='cuda'), torch.zeros(C, device='cuda')
 out = torch.empty_like(dy)
-pend = K.PendingApply(parts, dh, xbn, coef[0], 'elu', dgam, dbet, add, out)
+pend = K.BnBwdApply(parts, dh, xbn, coef, 'elu', dgam, dbet, add=add, out=out)
 
 
 def old(with_apply):

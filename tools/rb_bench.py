@@ -84,7 +84,7 @@ def main():
         def new_bwd():
             y1, ab, c1, c2 = st['y1'], st['ab'], st['c1'], st['c2']
             dab, dy2, dh2, p2 = K.rb_gate_dgrad(dout, ab, wg, gg, 'elu', m2, w2, g2, bn_bwd=(y1, c2[0], 'elu'))
-            dy1, dh1, p1 = K.rb_apply_dgrad(p2, dh2, y1, c2[0], 'elu', dg, db, m1, w1, g1, bn_bwd=(x, c1[0], 'elu'))
+            dy1, dh1, p1 = K.rb_apply_dgrad(K.BnBwdApply(p2, dh2, y1, c2, 'elu', dg, db, drop=m1), w1, g1, bn_bwd=(x, c1[0], 'elu'))
             K.affine_act_bwd_parts(p1, dh1, x, c1[0], c1[1], 'elu', c1[2], c1[3], dg, db, add=dout)
 
         old_fwd(); new_fwd(); new_bwd(); old_bwd()

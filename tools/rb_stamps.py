@@ -46,7 +46,7 @@ def gate_dgrad():
 
 
 def apply_dgrad():
-    K.rb_apply_dgrad(st['bp2'], st['dh2'], st['y1'], st['c2'][0], 'elu', dg, db, m1, w1, g1, bn_bwd=(x, st['c1'][0], 'elu'), nsplit=NSPLIT)
+    K.rb_apply_dgrad(K.BnBwdApply(st['bp2'], st['dh2'], st['y1'], st['c2'], 'elu', dg, db, drop=m1), w1, g1, bn_bwd=(x, st['c1'][0], 'elu'), nsplit=NSPLIT)
 
 
 for fn in (conv1, conv2_gate, gate_dgrad, apply_dgrad):

@@ -30,7 +30,7 @@ out = torch.empty_like(x)
 
 
 def grad_a():
-    K.conv2d_wgrad_apply(x, w1, g1, dw1, db1, parts, dh, y1, c2[0], 'elu', dga, dbe, drop=drop, in_scale=c1[0], in_shift=c1[1], in_act='elu')
+    K.conv2d_wgrad_apply(x, w1, g1, dw1, db1, K.BnBwdApply(parts, dh, y1, c2, 'elu', dga, dbe, drop=drop, out=out), in_scale=c1[0], in_shift=c1[1], in_act='elu')
 
 
 def grad_b():
@@ -43,8 +43,8 @@ def both():
 
 
 def pair():
-    K.conv2d_wgrad_pair(x, w1, g1, dw1, db1, parts, dh, y1, c2[0], 'elu', dga, dbe, dy2, w2, g2, dw2, db2, drop=drop, in_scale=c1[0], in_shift=c1[1],
-                        in_act='elu', in_scale_b=c2[0], in_shift_b=c2[1], in_act_b='elu', out=out)
+    K.conv2d_wgrad_pair(x, w1, g1, dw1, db1, K.BnBwdApply(parts, dh, y1, c2, 'elu', dga, dbe, drop=drop, out=out), dy2, w2, g2, dw2, db2,
+                        in_scale=c1[0], in_shift=c1[1], in_act='elu', in_scale_b=c2[0], in_shift_b=c2[1], in_act_b='elu')
 
 
 def timed(run, reps=20, replays=7):
