@@ -1134,6 +1134,33 @@ typedef struct lvae_copy_entry {
   int64_t n;
 } lvae_copy_entry;
 int lvae_multi_copy_f32(const lvae_copy_entry* table, int32_t n_entries, const int32_t* flag, int32_t want, void* stream);
+/* Spectral regularisation of the convolution weights (csrc/spectral.hip; NVAE, §3.2): the penalty lambda * sum_i sigma_i over a table of
+ * matrices that lie in the parameter arena, sigma_i estimated by one power-iteration step per call from a persistent vector u_i, by the
+ * rule of torch.nn.utils.spectral_norm. Entry i is the row-major matrix A of K rows and Cout contiguous columns at params + param_off
+ * (a convolution weight as the arena stores it: K = KH*KW*Cin), its gradient slot of the same layout at grads + grad_off, its u (Cout
+ * floats) at u_in / u_out + u_off and its v (K floats) at v_out + v_off. All offsets in elements. */
+typedef struct lvae_spectral_entry {
+  int64_t param_off;
+  int64_t grad_off;
+  int64_t K;
+  int64_t Cout;
+  int64_t u_off;
+  int64_t v_off;
+} lvae_spectral_entry;
+/* For every entry, in one launch (table: device array, 8-byte aligned):
+ *   s = A u,  v' = s / max(|s|, 1e-12);   t = A^T v',  u' = t / max(|t|, 1e-12);   sigma = |t|
+ *   grads[k][c] += (lambda / gscale[0]) * v'[k] * u'[c]                        (grads NULL: iterate only, no gradient is touched)
+ * v' -> v_out, u' -> u_out (u_out may be u_in), sigma -> sigma_out[i]. u' and v' are constants of the gradient, as in torch. gscale: device
+ * float[1] or NULL (= 1), the factor the optimizer will multiply the arena by, so that the update sees lambda * v' u'^T. A zero matrix
+ * gives v' = u' = 0, sigma = 0 and a zero increment. Sums are fp32 in one fixed order per entry (a workgroup owns an entry; no atomics),
+ * the two norms are summed in double: the outputs do not depend on the grid (max_workgroups: 0 = one workgroup per entry). Nothing outside
+ * the K * Cout elements of an entry's gradient slot is written. n_params, n_grads, n_u, n_v: the lengths of the four buffers; an entry
+ * that does not lie inside them, or has K > 4096 or Cout > 1024, is not touched and gets sigma = NaN. */
+int lvae_spectral_step_f32(const lvae_spectral_entry* table, int32_t n_entries, const float* params, int64_t n_params, float* grads,
+                           int64_t n_grads, const float* u_in, float* u_out, int64_t n_u, float* v_out, int64_t n_v, float* sigma_out,
+                           float lambda, const float* gscale, int32_t max_workgroups, void* stream);
+/* out[0] = sum of sigma[0:n_entries] (added in double in a fixed order, rounded once), out[1] = their maximum; a NaN sigma makes both NaN. */
+int lvae_spectral_reduce_f32(const float* sigma, int32_t n_entries, float* out, void* stream);
 /* BatchNorm recalibration (csrc/bn_recal.hip): running statistics re-estimated for the weights a pass is about to evaluate, by the
  * momentum=None rule of torch.optim.swa_utils.update_bn. With momentum 1 a train-mode forward leaves each BatchNorm's batch mean and
  * unbiased batch variance in its running statistics; a fold after every forward and one finish give their equal-weight means.

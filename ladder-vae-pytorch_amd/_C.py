@@ -102,6 +102,12 @@ class CopyEntry(C.Structure):
     _fields_ = [('dst', C.c_void_p), ('src', C.c_void_p), ('n', C.c_int64)]
 
 
+class SpectralEntry(C.Structure):
+    """mirror of struct lvae_spectral_entry"""
+    _fields_ = [('param_off', C.c_int64), ('grad_off', C.c_int64), ('K', C.c_int64), ('Cout', C.c_int64), ('u_off', C.c_int64),
+                ('v_off', C.c_int64)]
+
+
 class BnRecalEntry(C.Structure):
     """mirror of struct lvae_bn_recal_entry"""
     _fields_ = [('stat', C.c_void_p), ('acc', C.c_void_p), ('n', C.c_int64)]
@@ -263,6 +269,8 @@ SIGNATURES = {
     'lvae_adam_step_f32': (C.c_int, [_P, _P, _P, _P, _P, _L, _F, C.POINTER(LrScheduleStruct), C.c_double, C.c_double, _F, _F, _I, _P, _P, _P,
                                      _F, _P, _P, _P]),
     'lvae_multi_copy_f32': (C.c_int, [_P, _I, _P, _I, _P]),
+    'lvae_spectral_step_f32': (C.c_int, [_P, _I, _P, _L, _P, _L, _P, _P, _L, _P, _L, _P, _F, _P, _I, _P]),
+    'lvae_spectral_reduce_f32': (C.c_int, [_P, _I, _P, _P]),
     'lvae_bn_recal_fold_f64': (C.c_int, [_P, _I, _P, _P]),
     'lvae_bn_recal_finish_f32': (C.c_int, [_P, _I, _P, _P, _P]),
     'lvae_swap_f32': (C.c_int, [_P, _P, _L, _P]),

@@ -104,6 +104,20 @@ def augment_record(ck):
     return ck.get('augment') if isinstance(ck, dict) and 'model' in ck else None
 
 
+def spectral_record(ck):
+    """The 'spectral' entry of a loaded file (SpectralReg.state_dict: lam, u, v, sigma); None for a file without one."""
+    return ck.get('spectral') if isinstance(ck, dict) and 'model' in ck else None
+
+
+def spectral_warning(path, ck, optimizer):
+    """The line a resumed run prints when the file's spectral penalty had another weight than the optimizer's own (the command line's is
+    the one that runs). None when there is nothing to say: no regulariser here, no entry in the file, or the same weight."""
+    sr, was = getattr(optimizer, 'spectral', None), spectral_record(ck)
+    if sr is None or was is None or float(was['lam']) == sr.lam:
+        return None
+    return 'warning: %s was written with --spectral-reg %g; continuing with %g' % (path, float(was['lam']), sr.lam)
+
+
 def recalibrated_bn_buffers(model, optimizer, bn_recal):
     """{key: CPU tensor} of every BatchNorm running_mean / running_var recalibrated for the AVERAGED weights on the batches bn_recal()
     returns (recalibrate.recalibrated inside optimizer.swap_ema(), as a test pass under --ema-bn-batches does it): the parameters and the
@@ -123,6 +137,8 @@ def save_checkpoint(path, model, optimizer=None, summary=None, bn_recal=None):
     the run trained on (model.iw_train_samples; 1 = the ELBO), by the same rule: load_checkpoint does not touch the resumed run's own.
     A guarded optimizer adds 'grad_guard' (GradGuard.state_dict: its limits and the cumulative clipped / skipped counts). 'accum_steps' notes
     the micro-batches per optimizer step (model.accum_steps; `accum_steps_record` reads it back, 1 from a file without the key).
+    A spectrally regularised optimizer adds 'spectral' (SpectralReg.state_dict: lam and the iterate u, v, sigma), so a resumed run continues
+    bit for bit; the resumed run's own lam is the one that runs (`spectral_warning`).
     bn_recal (--ema-bn-batches; a callable returning image batches, used only with an averaging optimizer): the BatchNorm running statistics
     of 'ema' are those recalibrated for the averaged weights (`recalibrated_bn_buffers`), so the dict a reference model loads is
     self-consistent, and 'ema_bn_batches' notes the flag (model.ema_bn_batches). 'model', the optimizer state and a resumed run are untouched.
@@ -141,6 +157,8 @@ def save_checkpoint(path, model, optimizer=None, summary=None, bn_recal=None):
             ck['lr_schedule'] = lr_schedule_record(optimizer)
         if getattr(optimizer, 'guard', None) is not None:
             ck['grad_guard'] = optimizer.guard.state_dict()
+        if getattr(optimizer, 'spectral', None) is not None:
+            ck['spectral'] = optimizer.spectral.attach(model).state_dict()
     ck['iw_train_samples'] = int(getattr(model, 'iw_train_samples', 1))   # what the file's run trained on; a resumed run uses its own flag
     ck['accum_steps'] = int(getattr(model, 'accum_steps', 1))             # micro-batches per optimizer step, by the same rule
     # whether conv_in_q predicts offsets from the prior (model.residual_posterior). The same weights mean a different model under the other
@@ -223,6 +241,8 @@ def load_checkpoint(path, model, optimizer=None, summary=None):
             optimizer.ema.copy_(arena.params[:arena.n_train])
     if optimizer is not None and getattr(optimizer, 'guard', None) is not None and isinstance(ck, dict) and 'grad_guard' in ck:
         optimizer.guard.load_state_dict(ck['grad_guard'])
+    if optimizer is not None and getattr(optimizer, 'spectral', None) is not None and spectral_record(ck) is not None:
+        optimizer.spectral.load_state_dict(ck['spectral'])   # (a file without the entry: the iterate warm-starts afresh on attach)
     if summary is not None:
         if isinstance(ck, dict) and 'model' in ck and 'summary' in ck:
             summary.load_state(ck['summary'])

@@ -10,6 +10,9 @@ With a `feed` (data.DeviceDataset) the step also forms its own batch: a gather f
 and the advance of the feed's cursor its last, so the replayed graph takes nothing from the host but an index table once per epoch.
 With a `summary` (summary.TrainSummary) the step also folds its own metrics and the norm of the final gradient into the log window's
 device accumulator, immediately before Adamax: two more launches, captured with the rest.
+With a spectral regulariser on the optimizer (spectral.SpectralReg) the step runs one power-iteration step over every convolution weight
+immediately before the guard's check / the summary's fold (after the exchange; under accum_steps once, in the epilogue): it adds the
+penalty's gradient into the arena, and the step's dict gains the device scalars `sr_sum` and `sr_max`. The printed loss stays what it is.
 With a guard on the optimizer (optim.GradGuard) the step saves the BatchNorm running statistics before the forward pass, and immediately
 before Adamax takes the gradient's norm, decides whether the step is clipped or skipped and, if skipped, puts the statistics back; the
 summary then reads the guard's norm instead of taking it again. A skipped step still counts as a step of the run: the global step, the beta
@@ -168,6 +171,9 @@ class TrainStep:
         if getattr(optimizer, 'guard', None) is not None:
             optimizer._state()
             optimizer.guard.attach(model)    # state, shadow and copy tables exist before anything is captured
+        if getattr(optimizer, 'spectral', None) is not None:
+            optimizer._state()
+            optimizer.spectral.prepare(model, guarded=getattr(optimizer, 'guard', None) is not None)   # table, iterate (warm start), twin
         if feed is not None:
             feed.attach(model, self.accum)   # cursor = model.global_step * M: a resumed run continues in the middle of its epoch
             self.static_x = feed.new_batch()
@@ -230,19 +236,30 @@ class TrainStep:
         """The step's metrics and the norm of the gradient Adamax is about to apply (summed over ranks by now, scaled like Adamax scales it)
         into the log window. Called immediately before every `self.opt.step()`; captured with it."""
         guard = getattr(self.opt, 'guard', None)
+        sr = getattr(self.opt, 'spectral', None)
+        if sr is not None:
+            # the spectral penalty's gradient joins the arena first: the guard's norm, the clip factor and `grad:` see the regularised gradient
+            sr.step(self.model, self.opt.gscale, guarded=guard is not None)
+            out['sr_sum'], out['sr_max'] = sr.sr_sum, sr.sr_max
         if guard is not None:
             # the same place is the guard's: norm, decision, and the BatchNorm statistics of a skipped step back where they were
             guard.check(self.model.arena.grads, self.opt.gscale)
+            if sr is not None:
+                sr.finish(guard.skip)    # a skipped step leaves u, v and sigma where they were
             guard.restore_bn()
             if self.summary is not None:
                 self.summary.fold(out, guard.norm, self.opt.gscale)
             return
         if self.summary is None:
+            if sr is not None:
+                sr.finish()
             return
         grads = self.model.arena.grads
         if self._grad_norm is None:
             self._grad_norm = torch.empty((1,), dtype=torch.float32, device=grads.device)
         self.summary.fold(out, K.l2norm(grads, out=self._grad_norm), self.opt.gscale)
+        if sr is not None:
+            sr.finish()
 
     def _eager(self, x):
         out = self._fwd_bwd(x)

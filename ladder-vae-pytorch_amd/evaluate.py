@@ -596,6 +596,9 @@ def build_eval_parser():
     p.add_argument('--nn-table-size', type=int, default=4096, dest='nn_table_size', metavar='N',
                    help='images of the synthetic table (drawn from seed + 1) when there is no --nn-table')
     # (--binarize is a flag of build_parser: here it gives the evaluation images their fixed binarization, data.binarize_fixed)
+    p.add_argument('--spectral-norms', action='store_true', dest='spectral_norms',
+                   help="the spectral norm of every convolution weight (50 power iterations on the device): sum, max and the five largest "
+                        'are printed, all of them written to spectral_norms.npz; with --ema, of the averaged weights')
     p.add_argument('--binarize-seed', type=int, default=None, dest='binarize_seed', metavar='S',
                    help="the seed of --binarize's fixed binarization (default: the one noted in --checkpoint's 'augment' record, else 0)")
     return p
@@ -782,6 +785,15 @@ def main(argv=None):
         if qual is not None:
             line += quality_line_suffix(res)
         print(line)
+    if args.spectral_norms:
+        from .spectral import spectral_norms
+        norms = spectral_norms(model, 50, seed=args.seed)
+        top = sorted(norms.items(), key=lambda kv: -kv[1])[:5]
+        print('spectral norms of %d convolution weights%s: sum %.5g   max %.5g' % (len(norms), ' (averaged weights)' if args.ema else '',
+                                                                                 sum(norms.values()), top[0][1]))
+        for name, s in top:
+            print('    %-60s %.5g' % (name, s))
+        np.savez('spectral_norms.npz', names=np.array(list(norms)), sigma=np.array(list(norms.values()), dtype=np.float32))
     if args.ps:
         np.save('prior_samples.npy', prior_samples(model, 64, temperature).cpu().numpy())
     if args.layer_repr:

@@ -153,6 +153,12 @@ def build_parser():
                    help='every test / log-likelihood pass also measures its reconstructions against the test images on the device (the first '
                         "sample of every batch: the likelihood's mean, or its sample where it has none): the mean PSNR and SSIM are printed "
                         "after the test line and --history records the quality/* values")
+    p.add_argument('--spectral-reg', type=float, default=0.0, dest='spectral_reg', metavar='LAMBDA',
+                   help="add LAMBDA times the sum of the convolution weights' spectral norms to the objective (NVAE's spectral regularisation): "
+                        'one power-iteration step per optimizer step over every convolution, inside the captured step; the train line adds '
+                        'the sum and the largest of the norms. The printed loss does not include the penalty. 0: off')
+    p.add_argument('--spectral-warm-iters', type=int, default=10, dest='spectral_warm_iters', metavar='N',
+                   help='with --spectral-reg: power iterations run before the first step, from the seeded start vectors')
     p.add_argument('--latent-kl-threshold', type=float, default=0.01, dest='latent_kl_threshold', metavar='T')
     p.add_argument('--latent-var-threshold', type=float, default=0.01, dest='latent_var_threshold', metavar='T')
     return p
@@ -227,6 +233,11 @@ class LVAEExperiment:
             raise SystemExit("--betas must be two numbers in [0, 1), got %s" % ' '.join('%g' % b for b in betas))
         if not getattr(args, 'opt_eps', 1e-8) >= 0.0:
             raise SystemExit("--opt-eps must not be negative, got %g" % args.opt_eps)
+        lam = getattr(args, 'spectral_reg', 0.0)
+        if not (lam >= 0.0 and lam != float('inf')):
+            raise SystemExit("--spectral-reg must be a finite number that is not negative, got %g" % lam)
+        if getattr(args, 'spectral_warm_iters', 10) < 0:
+            raise SystemExit("--spectral-warm-iters must not be negative, got %d" % args.spectral_warm_iters)
         assert args.weight_decay >= 0.0
         assert 0.0 <= args.dropout <= 1.0
         if args.dropout < 1e-5:
@@ -276,6 +287,8 @@ class LVAEExperiment:
             s += ',clip{:g}'.format(args.max_grad_norm)
         if getattr(args, 'grad_skip_threshold', None) is not None:
             s += ',skip{:g}'.format(args.grad_skip_threshold)
+        if getattr(args, 'spectral_reg', 0.0) > 0.0:
+            s += ',sr{:g}'.format(args.spectral_reg)
         s += ',seed{}'.format(args.seed)
         if len(args.additional_descr) > 0:
             s += ',' + args.additional_descr
@@ -328,12 +341,20 @@ class LVAEExperiment:
         g, t = getattr(args, 'max_grad_norm', None), getattr(args, 'grad_skip_threshold', None)
         return None if g is None and t is None else GradGuard(max_norm=g, skip_threshold=t)
 
+    @staticmethod
+    def _make_spectral(args):
+        """The SpectralReg of --spectral-reg / --spectral-warm-iters; None (the plain step) at 0."""
+        if not getattr(args, 'spectral_reg', 0.0) > 0.0:
+            return None
+        from ..spectral import SpectralReg
+        return SpectralReg(args.spectral_reg, warm_iters=getattr(args, 'spectral_warm_iters', 10), seed=args.seed)
+
     def _make_optimizer(self):
         a = self.args
         rule = {'adamax': Adamax, 'adam': Adam, 'adamw': AdamW}[getattr(a, 'optimizer', 'adamax')]
         return rule(self.model, lr=a.lr, betas=tuple(getattr(a, 'betas', (0.9, 0.999))), eps=getattr(a, 'opt_eps', 1e-8),
                     weight_decay=a.weight_decay, ema_decay=getattr(a, 'ema_decay', 0.0), schedule=self._make_schedule(a),
-                    guard=self._make_guard(a))
+                    guard=self._make_guard(a), spectral=self._make_spectral(a))
 
     def beta(self):
         if self.args.beta_anneal != 0:

@@ -2145,3 +2145,42 @@ def nn_l2(queries, table, k, exclude=None):
     call('lvae_nn_l2_f32', pq, Q, pt, _C.FEED_U8 if table.dtype == torch.uint8 else _C.FEED_F32, N, D, ptr(exclude, (torch.int32,)), int(k),
          ptr(index, (torch.int32,)), ptr(dist, (torch.float32,)), ws.data_ptr(), ws.numel(), stream_ptr())
     return index, dist
+
+
+SPECTRAL_MAX_K, SPECTRAL_MAX_COUT = 4096, 1024   # what lvae_spectral_step_f32 holds of one matrix in LDS
+
+
+def spectral_table(rows, device):
+    """[(param offset, grad offset, K, Cout, u offset, v offset)] -> the device table spectral_step takes (int64 [len][6]: struct
+    lvae_spectral_entry). ValueError for an empty list or a matrix the kernel does not take."""
+    if not rows:
+        raise ValueError("spectral_table: no entries")
+    for r in rows:
+        if len(r) != 6 or not (1 <= r[2] <= SPECTRAL_MAX_K and 1 <= r[3] <= SPECTRAL_MAX_COUT):
+            raise ValueError("spectral_table: an entry is (param offset, grad offset, K <= %d, Cout <= %d, u offset, v offset), got %r"
+                             % (SPECTRAL_MAX_K, SPECTRAL_MAX_COUT, tuple(r)))
+    return torch.tensor([list(map(int, r)) for r in rows], dtype=torch.int64).to(device)
+
+
+def spectral_step(table, params, grads, u_in, u_out, v_out, sigma_out, lam=0.0, gscale=None, max_workgroups=0):
+    """One power-iteration step for every entry of a spectral_table in one launch: u_in -> v_out, u_out (may be u_in), sigma_out; with
+    `grads` also grads[entry] += (lam / gscale) v' u'^T, with grads=None nothing but the iterate is written."""
+    if table.dtype != torch.int64 or table.dim() != 2 or table.shape[1] != 6 or not table.is_contiguous():
+        raise _C.LvaeHipError("spectral_step: the table is a contiguous device int64 [entries][6]")
+    if u_in.numel() != u_out.numel() or sigma_out.numel() != table.shape[0]:
+        raise _C.LvaeHipError("spectral_step: u_in and u_out have one length, sigma_out one float per entry")
+    for t in (params, grads, u_in, u_out, v_out, sigma_out):
+        if t is not None and not t.is_contiguous():
+            raise _C.LvaeHipError("spectral_step: every buffer is contiguous")
+    f = (torch.float32,)
+    call('lvae_spectral_step_f32', ptr(table, (torch.int64,)), table.shape[0], ptr(params, f), params.numel(), ptr(grads, f),
+         0 if grads is None else grads.numel(), ptr(u_in, f), ptr(u_out, f), u_in.numel(), ptr(v_out, f), v_out.numel(), ptr(sigma_out, f),
+         float(lam), ptr(gscale, f), int(max_workgroups), stream_ptr())
+
+
+def spectral_reduce(sigma, out):
+    """out[0] = sum of the sigmas, out[1] = their maximum (device float[2]); one launch."""
+    if out.numel() != 2 or not (sigma.is_contiguous() and out.is_contiguous()):
+        raise _C.LvaeHipError("spectral_reduce: out is a contiguous device float[2]")
+    call('lvae_spectral_reduce_f32', ptr(sigma, (torch.float32,)), sigma.numel(), ptr(out, (torch.float32,)), stream_ptr())
+    return out

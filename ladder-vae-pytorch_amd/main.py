@@ -129,6 +129,17 @@ def guard_metrics(guard, gscale, seen, m, with_norm):
     return now
 
 
+def spectral_suffix(m):
+    """What --spectral-reg appends to a train line: the sum and the largest of the convolutions' spectral norms, of the step the line falls
+    due at."""
+    return '   sr: {:.5g}   max: {:.4g}'.format(m['spectral/sum'], m['spectral/max']) if 'spectral/sum' in m else ''
+
+
+def spectral_metrics(out, m):
+    if 'sr_sum' in out:
+        m['spectral/sum'], m['spectral/max'] = out['sr_sum'].item(), out['sr_max'].item()
+
+
 def iw_suffix(m, k):
     """What --iw-train-samples K > 1 appends to a train line: the K-sample bound (at beta = 1) and the effective sample size of the weights,
     of the step the line falls due at."""
@@ -171,6 +182,10 @@ def main(argv=None):
         was_iw = ck.get('iw_train_samples', 1) if isinstance(ck, dict) and 'model' in ck else 1
         if rank == 0 and was_iw != args.iw_train_samples:
             print('warning: %s was written with --iw-train-samples %d; continuing with %d' % (args.resume, was_iw, args.iw_train_samples))
+        from .checkpoint import spectral_warning
+        line = spectral_warning(args.resume, ck, opt)
+        if rank == 0 and line:
+            print(line)
         from .checkpoint import accum_steps_record
         if rank == 0 and accum_steps_record(ck) != args.accum_steps:
             print('warning: %s was written with --accum-steps %d; continuing with %d' % (args.resume, accum_steps_record(ck), args.accum_steps))
@@ -286,8 +301,9 @@ def main(argv=None):
                     m['elbo/iw_train'], m['iw/ess'] = out['iw'].item(), out['ess'].item()
                 if opt.guard is not None:              # every rank decides alike: rank 0's counts are the run's
                     guard_seen = guard_metrics(opt.guard, opt.gscale, guard_seen, m, False)
+                spectral_metrics(out, m)               # of this step: the accumulator's layout stays as it is
                 print(exp.train_log_str(m, step) + train_line_suffix(m, summary.ranks) + lr_suffix(m) + '   [{:.0f} img/s]'.format(seen / dt)
-                      + iw_suffix(m, args.iw_train_samples) + guard_suffix(m))
+                      + iw_suffix(m, args.iw_train_samples) + guard_suffix(m) + spectral_suffix(m))
                 if history is not None:
                     history.write(step, 'train', m, steps=m['steps'], nonfinite_steps=m['nonfinite_steps'])
             t0, seen = time.time(), 0
@@ -298,8 +314,9 @@ def main(argv=None):
                 m['lr/lr'] = opt.current_lr()
             if opt.guard is not None:
                 guard_seen = guard_metrics(opt.guard, opt.gscale, guard_seen, m, True)
+            spectral_metrics(out, m)
             print(exp.train_log_str(m, step) + lr_suffix(m) + '   [{:.0f} img/s]'.format(seen / dt) + iw_suffix(m, args.iw_train_samples)
-                  + guard_suffix(m))
+                  + guard_suffix(m) + spectral_suffix(m))
             if history is not None:
                 history.write(step, 'train', m)
             t0, seen = time.time(), 0

@@ -11,6 +11,9 @@ With a `guard` (GradGuard) the step is preceded by a look at the gradient's norm
 step whose norm is not finite or exceeds `skip_threshold` is left out as if it had not happened (parameters, exp_avg, exp_inf, the step
 counter, the average and lr_now keep their bits), all of it inside the captured step.
 
+With `spectral` (spectral.SpectralReg) the step is preceded by one power-iteration step over every convolution weight, which adds the
+gradient of lam * sum sigma into the arena before the guard takes its norm; a skipped step leaves the iterate where it was.
+
 `Adam` / `AdamW` are a second update rule on the same arena (torch.optim.Adam with L2 decay, torch.optim.AdamW with decoupled decay) with the
 same average, schedule and guard: `ArenaOptimizer` holds what does not depend on the rule, each rule launches its own kernel.
 """
@@ -171,7 +174,7 @@ class ArenaOptimizer:
     (`rule`, a key of RULES) and launches its kernel in `_update(arena, guard_state)`."""
     rule = None
 
-    def __init__(self, model, lr, betas, eps, weight_decay, ema_decay, schedule, guard):
+    def __init__(self, model, lr, betas, eps, weight_decay, ema_decay, schedule, guard, spectral=None):
         self.model = model
         self.lr, self.betas, self.eps, self.weight_decay = float(lr), (float(betas[0]), float(betas[1])), float(eps), float(weight_decay)
         self.ema_decay = float(ema_decay)
@@ -185,6 +188,7 @@ class ArenaOptimizer:
         self._sched = None if schedule is None else schedule.struct(self.lr)
         self.lr_now = None  # device float[1] with a schedule: the lr the last step applied
         self.guard = guard  # GradGuard or None: clip / skip decided on the device before the update
+        self.spectral = spectral   # spectral.SpectralReg or None: its gradient joins the arena before the guard looks at it
         self._arena = None
         self._swapped = False
 
@@ -212,14 +216,24 @@ class ArenaOptimizer:
         arena = self._state()
         if self._swapped:
             raise RuntimeError("%s.step() inside swap_ema(): the parameters hold the average" % type(self).__name__)
-        guard = self.guard
+        guard, sr = self.guard, self.spectral
+        if sr is not None and not sr.open and not sr.done:
+            sr.step(self.model, self.gscale, guarded=guard is not None)   # (engine.TrainStep has run it by now; run here otherwise)
         if guard is None:
+            if sr is not None:
+                if sr.open:
+                    sr.finish()
+                sr.done = False   # this step's penalty is in the gradient, once: the next step() takes its own
             self._update(arena, None)
             K.counter_advance(self.step_count, 1)
             return
         if not guard.checked:
             guard.check(arena.grads, self.gscale)
         guard.checked = False
+        if sr is not None:
+            if sr.open:
+                sr.finish(guard.skip)
+            sr.done = False
         self._update(arena, guard.state)
         K.counter_advance_unless(self.step_count, 1, guard.skip)
 
@@ -295,8 +309,9 @@ class Adamax(ArenaOptimizer):
     """torch.optim.Adamax with L2 decay, the reference's rule."""
     rule = 'adamax'
 
-    def __init__(self, model, lr=3e-4, betas=(0.9, 0.999), eps=1e-8, weight_decay=0.0, ema_decay=0.0, schedule=None, guard=None):
-        super().__init__(model, lr, betas, eps, weight_decay, ema_decay, schedule, guard)
+    def __init__(self, model, lr=3e-4, betas=(0.9, 0.999), eps=1e-8, weight_decay=0.0, ema_decay=0.0, schedule=None, guard=None,
+                 spectral=None):
+        super().__init__(model, lr, betas, eps, weight_decay, ema_decay, schedule, guard, spectral)
 
     def _update(self, arena, guard_state):
         p, b1, b2 = arena.params[:arena.n_train], self.betas[0], self.betas[1]
@@ -320,7 +335,7 @@ class Adam(ArenaOptimizer):
     combination of average, schedule and guard (lvae_adam_step_f32); the bias corrections are formed in double on the device."""
 
     def __init__(self, model, lr=1e-3, betas=(0.9, 0.999), eps=1e-8, weight_decay=0.0, decoupled_weight_decay=False, ema_decay=0.0,
-                 schedule=None, guard=None):
+                 schedule=None, guard=None, spectral=None):
         self.decoupled = bool(decoupled_weight_decay)
         self.rule = 'adamw' if self.decoupled else 'adam'
         if not float(lr) >= 0.0:
@@ -331,7 +346,7 @@ class Adam(ArenaOptimizer):
             raise ValueError("eps must not be negative, got %r" % (eps,))
         if not float(weight_decay) >= 0.0:
             raise ValueError("weight_decay must not be negative, got %r" % (weight_decay,))
-        super().__init__(model, lr, betas, eps, weight_decay, ema_decay, schedule, guard)
+        super().__init__(model, lr, betas, eps, weight_decay, ema_decay, schedule, guard, spectral)
 
     def _update(self, arena, guard_state):
         K.adam_step(arena.params[:arena.n_train], arena.grads, self.exp_avg, self.exp_avg_sq, None, self.lr, self._sched, self.betas[0],
@@ -343,5 +358,5 @@ class AdamW(Adam):
     """Adam with decoupled decay and torch.optim.AdamW's default of 1e-2."""
 
     def __init__(self, model, lr=1e-3, betas=(0.9, 0.999), eps=1e-8, weight_decay=1e-2, decoupled_weight_decay=True, ema_decay=0.0,
-                 schedule=None, guard=None):
-        super().__init__(model, lr, betas, eps, weight_decay, decoupled_weight_decay, ema_decay, schedule, guard)
+                 schedule=None, guard=None, spectral=None):
+        super().__init__(model, lr, betas, eps, weight_decay, decoupled_weight_decay, ema_decay, schedule, guard, spectral)
