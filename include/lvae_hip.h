@@ -786,6 +786,21 @@ int lvae_kl_bookkeeping_fwd_f32(const float* kl, int32_t L, int32_t N, float fre
                                 float* kl_avg_layerwise, float* scalars, void* stream);
 int lvae_kl_bookkeeping_bwd_f32(const float* kl, int32_t L, int32_t N, float free_bits, const float* g_sep,
                                 const float* g_avg, const float* g_scalars, float* dkl, void* stream);
+/* The same bookkeeping with the KL terms balanced over the layers during the KL warm-up (csrc/kl_balance.hip; NVAE, §3.2):
+ *   m_l     = mean_n |kl[l][n]| + 0.01
+ *   gamma_l = (m_l / alpha_l) / mean_j (m_j / alpha_j)   while beta < 1, else exactly 1.0f      -> coeff[l], written on every call
+ *   scalars[0] = kl_loss = sum_l gamma_l * mean_n c(kl[l][n]),  c the free-bits clamp above; gamma is formed from the unclamped values
+ * alpha: device float[L], positive and finite (the caller validates). beta: the step's own, `beta` when step is NULL, else
+ * linear_anneal(step[0], 0, 1, anneal_steps) read on the device as lvae_elbo_loss_fwd_anneal_f32 reads it (`beta` is then ignored).
+ * kl_sep, kl_avg_layerwise and scalars[1] are the plain numbers with the bits lvae_kl_bookkeeping_fwd_f32 gives them; with beta >= 1
+ * scalars[0] has them too. The L-element part is formed in double and rounded once; one workgroup, no atomics: same inputs, same bits.
+ * bwd: gamma is a constant of the gradient, read from coeff (never formed again, no beta):
+ *   dkl[l][n] = g_sep[n] + g_avg[l]/N + g_scalars[1]/N + [clamp passes] * coeff[l] * g_scalars[0] / N      (each g may be NULL)
+ * with coeff all 1.0f, the bits of lvae_kl_bookkeeping_bwd_f32. */
+int lvae_kl_balance_fwd_f32(const float* kl, int32_t L, int32_t N, float free_bits, const float* alpha, float beta, const int64_t* step,
+                            int64_t anneal_steps, float* kl_sep, float* kl_avg_layerwise, float* scalars, float* coeff, void* stream);
+int lvae_kl_balance_bwd_f32(const float* kl, int32_t L, int32_t N, float free_bits, const float* coeff, const float* g_sep,
+                            const float* g_avg, const float* g_scalars, float* dkl, void* stream);
 /* ELBO / loss assembly — experiment/experiment_manager.py:329-344:
  *   elbo_sep[n] = ll[n] - kl_sep[n]; scalars[0] = loss = mean(-ll) + beta*kl_loss; [1] = elbo; [2] = recons
  * bwd (of `loss` only; elbo/recons are metrics): d_ll[n] = -g/N, d_kl_loss = g*beta, g = g_loss[0] on device. */

@@ -231,6 +231,8 @@ SIGNATURES = {
     'lvae_pad_crop_f32': (C.c_int, [_P, _I, _I, _I, _I, _I, _P, _I, _I, _I, _P]),
     'lvae_kl_bookkeeping_fwd_f32': (C.c_int, [_P, _I, _I, _F, _P, _P, _P, _P]),
     'lvae_kl_bookkeeping_bwd_f32': (C.c_int, [_P, _I, _I, _F, _P, _P, _P, _P, _P]),
+    'lvae_kl_balance_fwd_f32': (C.c_int, [_P, _I, _I, _F, _P, _F, _P, _L, _P, _P, _P, _P, _P]),
+    'lvae_kl_balance_bwd_f32': (C.c_int, [_P, _I, _I, _F, _P, _P, _P, _P, _P, _P]),
     'lvae_elbo_loss_fwd_f32': (C.c_int, [_P, _P, _P, _F, _I, _P, _P, _P]),
     'lvae_elbo_loss_bwd_f32': (C.c_int, [_P, _F, _I, _P, _P, _P]),
     'lvae_elbo_loss_fwd_anneal_f32': (C.c_int, [_P, _P, _P, _P, _L, _I, _P, _P, _P]),

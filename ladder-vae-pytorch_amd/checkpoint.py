@@ -118,6 +118,22 @@ def spectral_warning(path, ck, optimizer):
     return 'warning: %s was written with --spectral-reg %g; continuing with %g' % (path, float(was['lam']), sr.lam)
 
 
+def kl_balance_record(ck):
+    """The 'kl_balance' note of a loaded file: the rule's name or the list of weights its run balanced the KL terms with; None for a file
+    without the key (a run without KL balancing, an older file, a bare state_dict)."""
+    return ck.get('kl_balance') if isinstance(ck, dict) and 'model' in ck else None
+
+
+def kl_balance_warning(path, ck, now):
+    """The line a resumed run prints when the file's run balanced its KL terms another way than this one (`now`: this run's rule, list or
+    None; the command line's setting is the one that runs). None when they agree."""
+    was = kl_balance_record(ck)
+    if was == now:
+        return None
+    word = lambda r: 'no KL balancing' if r is None else '--kl-balance %s' % (r,)
+    return 'warning: %s was written with %s; continuing with %s' % (path, word(was), word(now))
+
+
 def recalibrated_bn_buffers(model, optimizer, bn_recal):
     """{key: CPU tensor} of every BatchNorm running_mean / running_var recalibrated for the AVERAGED weights on the batches bn_recal()
     returns (recalibrate.recalibrated inside optimizer.swap_ema(), as a test pass under --ema-bn-batches does it): the parameters and the
@@ -143,7 +159,10 @@ def save_checkpoint(path, model, optimizer=None, summary=None, bn_recal=None):
     of 'ema' are those recalibrated for the averaged weights (`recalibrated_bn_buffers`), so the dict a reference model loads is
     self-consistent, and 'ema_bn_batches' notes the flag (model.ema_bn_batches). 'model', the optimizer state and a resumed run are untouched.
     'augment' notes what the device-fed gather did to the training batches (model.augment: data.FeedAugment.record() and the seed; absent
-    without augmentation). The noise is stateless, so it is a note like 'accum_steps': a resumed run uses its own flags."""
+    without augmentation). The noise is stateless, so it is a note like 'accum_steps': a resumed run uses its own flags.
+    'kl_balance' notes how the run balanced its KL terms (model.kl_balance_record, else the record of model.kl_balance: the rule's name or
+    the list; absent without balancing). The coefficients have no state, so nothing else is saved and a resumed run continues bit for bit
+    under the same setting; its own setting is the one that runs (`kl_balance_warning`)."""
     ck = {'model': state_dict_reference_layout(model), 'global_step': int(model.global_step)}
     if optimizer is not None:
         ck['optimizer'] = optimizer_state_by_name(model, optimizer)
@@ -166,6 +185,11 @@ def save_checkpoint(path, model, optimizer=None, summary=None, bn_recal=None):
     ck['residual_posterior'] = bool(getattr(model, 'residual_posterior', False))
     if getattr(model, 'augment', None) is not None:
         ck['augment'] = dict(model.augment)   # the feed's augmentation and its seed; a file without the key means none
+    klb = getattr(model, 'kl_balance_record', None)
+    if klb is None and getattr(model, 'kl_balance', None) is not None:
+        klb = model.kl_balance.record()
+    if klb is not None:
+        ck['kl_balance'] = klb
     nz = noise_state(model)
     if nz is not None:
         ck['noise'] = nz

@@ -17,6 +17,9 @@ With a guard on the optimizer (optim.GradGuard) the step saves the BatchNorm run
 before Adamax takes the gradient's norm, decides whether the step is clipped or skipped and, if skipped, puts the statistics back; the
 summary then reads the guard's norm instead of taking it again. A skipped step still counts as a step of the run: the global step, the beta
 warm-up, the data cursor, the noise stream and num_batches_tracked advance; the model and the optimizer keep their bits.
+With kl_balance (balance.KlBalance) every forward pass of the step balances the per-layer KL terms of its loss while beta < 1, in the KL
+bookkeeping launch it issues anyway (one launch replaced each way); under accum_steps every micro-pass on its own rows, with several ranks
+every rank on its shard.
 With accum_steps = M > 1 one optimizer step consumes M micro-batches: zero_grad [+ the guard's save] once | gather, forward, backward, the
 fold of the pass's metrics into their means (kernels.micro_fold) and the cursor advance, M times | the exchange (split form) once | guard,
 summary, optimizer and beta counter once. Captured, these are three graphs in one pool, the middle one replayed M times.
@@ -77,13 +80,32 @@ def micro_slices(rows, accum_steps):
     return [(j * per, (j + 1) * per) for j in range(m)]
 
 
-def forward_pass(model, x, beta=1.0, compute_l2=True, beta_anneal=0, iw_samples=1):
+def bind_kl_balance(model, kl_balance, beta=1.0, beta_anneal=0, iw_samples=1):
+    """Hands a balance.KlBalance to the model, bound to the beta source the loss head uses: the device step counter under beta_anneal, else
+    the constant. ValueError with iw_samples > 1: the bound is formed from kl_sep, and a balanced bound has no reported meaning."""
+    if int(iw_samples) > 1:
+        raise ValueError("KL balancing reweights the per-layer terms of the ELBO's kl_loss; the importance-weighted bound (iw_samples=%d) "
+                         "is formed from kl_sep and has no balanced form" % int(iw_samples))
+    kl_balance.attach(model)
+    if beta_anneal:
+        kl_balance.bind(step=global_step_counter(model), anneal_steps=int(beta_anneal))
+    else:
+        kl_balance.bind(beta=float(beta))
+    model.kl_balance = kl_balance
+
+
+def forward_pass(model, x, beta=1.0, compute_l2=True, beta_anneal=0, iw_samples=1, kl_balance=None):
     """LVAEExperiment.forward_pass (experiment/experiment_manager.py:322-367) on the HIP engine. beta_anneal != 0: the KL warm-up,
     beta = linear_anneal(global step, 0, 1, beta_anneal) read on the device from `global_step_counter(model)` (`beta` is ignored).
     iw_samples = K > 1 (engine-only): the loss is the K-sample importance-weighted bound, -mean_b logmeanexp_k(ll - beta kl_sep), over K
     samples per image that share one bottom-up pass (LadderVAE.forward(n_samples=K)); `elbo`, `recons`, `kl` are means over the K * B rows
-    and `out` also carries `iw` (the bound at beta = 1), `ess` (the effective sample size of the weights) and `iw_weights`."""
+    and `out` also carries `iw` (the bound at beta = 1), `ess` (the effective sample size of the weights) and `iw_weights`.
+    kl_balance (engine-only; a balance.KlBalance): becomes the model's `kl_balance`, bound to this pass's beta source, so that a training
+    pass balances the per-layer KL terms of `loss` while beta < 1; `elbo`, `kl`, `recons` and `kl_avg_layerwise` stay the plain numbers.
+    None leaves the model as it is."""
     iw_samples = check_iw_objective(model, iw_samples)
+    if kl_balance is not None:
+        bind_kl_balance(model, kl_balance, beta, beta_anneal, iw_samples)
     mo = model(x, n_samples=iw_samples) if iw_samples > 1 else model(x)
     iw = None
     if iw_samples > 1 and beta_anneal:
@@ -112,12 +134,17 @@ class TrainStep:
     the device at the feed's cursor (eager steps and the captured step alike: gather | forward, backward, exchange, Adamax | cursor advance)."""
 
     def __init__(self, model, optimizer, beta=1.0, use_graph=True, allreduce=None, eager_warmup=2, async_wgrad=False,
-                 wgrad_streams=1, wgrad_group_rows=16384, beta_anneal=0, feed=None, summary=None, iw_samples=1, accum_steps=1):
+                 wgrad_streams=1, wgrad_group_rows=16384, beta_anneal=0, feed=None, summary=None, iw_samples=1, accum_steps=1,
+                 kl_balance=None):
         self.model, self.opt, self.beta = model, optimizer, beta
         self.accum = int(accum_steps)         # M > 1: one optimizer step over M micro-batches (prologue | M micro-passes | exchange | epilogue)
         if self.accum < 1:
             raise ValueError("accum_steps must be at least 1, got %d" % self.accum)
         self.iw_samples = check_iw_objective(model, iw_samples)   # K > 1: train on the K-sample importance-weighted bound
+        self.kl_balance = kl_balance          # balance.KlBalance: every (micro-)pass balances its KL terms on its own rows while beta < 1
+        if kl_balance is not None:
+            # weights on the device, beta source bound, the model's property set: all before anything is captured
+            bind_kl_balance(model, kl_balance, beta, beta_anneal, self.iw_samples)
         self.feed = feed
         self.summary = summary                # None: the step issues not one launch more
         self._grad_norm = None
@@ -190,6 +217,7 @@ class TrainStep:
             if not micro:
                 self.opt.zero_grad()
             K.prepared.prepare_all()  # one launch: transformed weights of every Winograd convolution seen so far
+            # (a kl_balance was bound and handed to the model by __init__, once: the pass finds it there)
             out = forward_pass(self.model, x, self.beta, beta_anneal=self.beta_anneal, iw_samples=self.iw_samples)
             if self.allreduce is not None:
                 self.allreduce.begin_step()

@@ -159,6 +159,13 @@ def build_parser():
                         'the sum and the largest of the norms. The printed loss does not include the penalty. 0: off')
     p.add_argument('--spectral-warm-iters', type=int, default=10, dest='spectral_warm_iters', metavar='N',
                    help='with --spectral-reg: power iterations run before the first step, from the seeded start vectors')
+    p.add_argument('--kl-balance', type=str, choices=['equal', 'sqrt', 'linear', 'square'], default=None, dest='kl_balance', metavar='RULE',
+                   help="with --beta-anneal: NVAE's KL balancing. While beta < 1 the per-layer KL terms of the objective are reweighted by "
+                        'coefficients that average 1 (a layer whose KL is small pays less, one whose KL is large pays more), decided on the '
+                        "device inside the captured step; exactly 1 once beta has reached 1. RULE sets the layers' fixed weights from their "
+                        'latent height r relative to the smallest: equal 1, sqrt sqrt(r), linear r, square r^2 / (layers of that size), '
+                        "NVAE's choice. The train line adds the range of the coefficients; the printed loss is the balanced objective, ELBO, "
+                        'KL and recons stay the plain numbers. Off by default')
     p.add_argument('--latent-kl-threshold', type=float, default=0.01, dest='latent_kl_threshold', metavar='T')
     p.add_argument('--latent-var-threshold', type=float, default=0.01, dest='latent_var_threshold', metavar='T')
     return p
@@ -238,6 +245,13 @@ class LVAEExperiment:
             raise SystemExit("--spectral-reg must be a finite number that is not negative, got %g" % lam)
         if getattr(args, 'spectral_warm_iters', 10) < 0:
             raise SystemExit("--spectral-warm-iters must not be negative, got %d" % args.spectral_warm_iters)
+        klb = getattr(args, 'kl_balance', None)
+        if klb is not None and args.beta_anneal == 0:
+            raise SystemExit("--kl-balance %s balances the KL terms while beta < 1: without --beta-anneal beta is 1 from the first step and "
+                             "the flag would do nothing (add --beta-anneal STEPS)" % klb)
+        if klb is not None and iw > 1:
+            raise SystemExit("--kl-balance %s cannot be combined with --iw-train-samples %d: the importance-weighted bound is formed from "
+                             "the per-row KL and has no balanced form" % (klb, iw))
         assert args.weight_decay >= 0.0
         assert 0.0 <= args.dropout <= 1.0
         if args.dropout < 1e-5:
@@ -289,6 +303,8 @@ class LVAEExperiment:
             s += ',skip{:g}'.format(args.grad_skip_threshold)
         if getattr(args, 'spectral_reg', 0.0) > 0.0:
             s += ',sr{:g}'.format(args.spectral_reg)
+        if getattr(args, 'kl_balance', None) is not None:
+            s += ',klb-{}'.format(args.kl_balance)
         s += ',seed{}'.format(args.seed)
         if len(args.additional_descr) > 0:
             s += ',' + args.additional_descr
@@ -310,6 +326,8 @@ class LVAEExperiment:
         model.accum_steps = getattr(a, 'accum_steps', 1)             # (likewise)
         model.ema_bn_batches = getattr(a, 'ema_bn_batches', 0)       # (likewise, when it is not 0)
         model.augment = self.augment_record(a)                        # (likewise, when there is one)
+        # (the KlBalance itself reaches the model through engine.TrainStep(kl_balance=), which binds its beta source)
+        model.kl_balance_record = getattr(a, 'kl_balance', None)      # (likewise: the rule of --kl-balance)
         return model
 
     @staticmethod
@@ -348,6 +366,14 @@ class LVAEExperiment:
             return None
         from ..spectral import SpectralReg
         return SpectralReg(args.spectral_reg, warm_iters=getattr(args, 'spectral_warm_iters', 10), seed=args.seed)
+
+    @staticmethod
+    def _make_kl_balance(args):
+        """The balance.KlBalance of --kl-balance; None (the plain KL bookkeeping) without the flag."""
+        if getattr(args, 'kl_balance', None) is None:
+            return None
+        from ..balance import KlBalance
+        return KlBalance(args.kl_balance)
 
     def _make_optimizer(self):
         a = self.args

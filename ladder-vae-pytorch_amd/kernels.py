@@ -1614,6 +1614,39 @@ def kl_bookkeeping_bwd(kl_ln, free_bits, g_sep, g_avg, g_scal):
     return dkl
 
 
+def kl_balance_fwd(kl_ln, free_bits, alpha, beta=1.0, step=None, anneal_steps=0, coeff=None):
+    """kl_bookkeeping_fwd with the KL terms balanced over the layers while beta < 1 (csrc/kl_balance.hip). alpha: device float[L], positive
+    and finite (balance.KlBalance validates it on the host). beta: a float, or with step (device int64[1]) linear_anneal(step[0], 0, 1,
+    anneal_steps) read on the device. coeff: device float[L] to write the coefficients to (allocated when None).
+    -> kl_sep, kl_avg_layerwise, scalars [kl_loss (balanced), kl], coeff."""
+    L, N = kl_ln.shape
+    dev = kl_ln.device
+    if alpha.numel() != L:
+        raise ValueError("kl_balance_fwd: %d weights for %d layers" % (alpha.numel(), L))
+    if coeff is None:
+        coeff = torch.empty((L,), dtype=torch.float32, device=dev)
+    elif coeff.numel() != L or not coeff.is_contiguous():
+        raise ValueError("kl_balance_fwd: coeff must be a contiguous float[%d]" % L)
+    kl_sep = torch.empty((N,), dtype=torch.float32, device=dev)
+    kl_avg = torch.empty((L,), dtype=torch.float32, device=dev)
+    scal = torch.empty((2,), dtype=torch.float32, device=dev)
+    call('lvae_kl_balance_fwd_f32', ptr(kl_ln), L, N, float(free_bits), ptr(alpha, (torch.float32,)), float(beta),
+         None if step is None else ptr(step, (torch.int64,)), int(anneal_steps), ptr(kl_sep), ptr(kl_avg), ptr(scal),
+         ptr(coeff, (torch.float32,)), stream_ptr())
+    return kl_sep, kl_avg, scal, coeff
+
+
+def kl_balance_bwd(kl_ln, free_bits, coeff, g_sep, g_avg, g_scal):
+    """kl_bookkeeping_bwd with the forward's coefficients on the kl_loss term (read from coeff, never formed again)."""
+    L, N = kl_ln.shape
+    if coeff.numel() != L:
+        raise ValueError("kl_balance_bwd: %d coefficients for %d layers" % (coeff.numel(), L))
+    dkl = torch.empty_like(kl_ln)
+    call('lvae_kl_balance_bwd_f32', ptr(kl_ln), L, N, float(free_bits), ptr(coeff, (torch.float32,)), ptr(g_sep), ptr(g_avg), ptr(g_scal),
+         ptr(dkl), stream_ptr())
+    return dkl
+
+
 def elbo_loss_fwd(ll, kl_sep, kl_loss, beta):
     N = ll.numel()
     elbo_sep = torch.empty((N,), dtype=torch.float32, device=ll.device)

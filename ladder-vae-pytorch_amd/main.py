@@ -12,7 +12,8 @@ import torch
 from . import dist as ldist
 from .checkpoint import lr_schedule_record, save_checkpoint
 from .data import DeviceDataset
-from .engine import TrainStep
+from .balance import klb_suffix
+from .engine import TrainStep, linear_anneal
 from .evaluate import image_pass, test_pass
 from .experiment.experiment_manager import LVAEExperiment
 from .images import write_png
@@ -140,6 +141,25 @@ def spectral_metrics(out, m):
         m['spectral/sum'], m['spectral/max'] = out['sr_sum'].item(), out['sr_max'].item()
 
 
+def balance_metrics(balance, m):
+    """Adds the KL-balancing coefficients of the step a train line falls due at as `kl_balance/coeff_<i>` (one device-to-host read; of an
+    accumulated step, its last micro-pass). Nothing else: these keys are what --history records."""
+    if balance is None:
+        return
+    for i, c in enumerate(balance.coeff.tolist()):
+        m['kl_balance/coeff_%d' % i] = c
+
+
+def balance_suffix(m, step, beta_anneal):
+    """What --kl-balance appends to a train line: `klb: <min>..<max>` of the coefficients, or `klb: off` once beta has reached 1. Step
+    `step` ran with the beta of `step - 1` completed steps: the schedule the device counter follows, restated on the host for the word
+    `off` alone (the coefficients themselves cannot say it: they can all be 1 while the rule is active, with one layer for instance)."""
+    coeff = [v for k, v in m.items() if k.startswith('kl_balance/coeff_')]
+    if not coeff:
+        return ''
+    return klb_suffix(coeff, linear_anneal(step - 1, 0.0, 1.0, beta_anneal) < 1.0)
+
+
 def iw_suffix(m, k):
     """What --iw-train-samples K > 1 appends to a train line: the K-sample bound (at beta = 1) and the effective sample size of the weights,
     of the step the line falls due at."""
@@ -193,6 +213,10 @@ def main(argv=None):
         if rank == 0 and augment_record(ck) != exp.augment_record(args):
             print('warning: %s was written with the feed augmentation %s; continuing with %s' % (args.resume, augment_record(ck),
                                                                                               exp.augment_record(args)))
+        from .checkpoint import kl_balance_warning
+        line = kl_balance_warning(args.resume, ck, args.kl_balance)
+        if rank == 0 and line:
+            print(line)
         del ck
     model.noise.seed ^= rank * 0x9E3779B9
     model.train()
@@ -227,9 +251,11 @@ def main(argv=None):
     # (an accumulated step exchanges once, after its last micro-pass: the split form, unless LVAE_DDP_MODE insists, which TrainStep refuses)
     ar_mode = 'split' if accum > 1 and os.environ.get('LVAE_DDP_MODE') is None else None
     allreduce = ldist.GradAllReduce(arena.grads, segments=arena.segments, mode=ar_mode) if world > 1 else None
+    # --kl-balance: the KL bookkeeping of every training pass balances the layers' terms while that beta is below 1
+    balance = exp._make_kl_balance(args)
     # --beta-anneal: beta is read on the device from a step counter the step advances itself, so the captured graph replays with it
     step_fn = TrainStep(model, opt, beta=1.0, use_graph=not args.no_graph, allreduce=allreduce, beta_anneal=args.beta_anneal,
-                        feed=feed, summary=summary, iw_samples=args.iw_train_samples, accum_steps=accum)
+                        feed=feed, summary=summary, iw_samples=args.iw_train_samples, accum_steps=accum, kl_balance=balance)
     history = History(args.history) if args.history and rank == 0 else None
     guard_seen = opt.guard.counts() if opt.guard is not None else None   # (after --resume: the file's counts)
     # --latent-stats: the first sample of every test batch also folds each layer's posterior into a device accumulator
@@ -302,8 +328,10 @@ def main(argv=None):
                 if opt.guard is not None:              # every rank decides alike: rank 0's counts are the run's
                     guard_seen = guard_metrics(opt.guard, opt.gscale, guard_seen, m, False)
                 spectral_metrics(out, m)               # of this step: the accumulator's layout stays as it is
+                balance_metrics(balance, m)            # likewise (of this step's last micro-pass, of rank 0)
                 print(exp.train_log_str(m, step) + train_line_suffix(m, summary.ranks) + lr_suffix(m) + '   [{:.0f} img/s]'.format(seen / dt)
-                      + iw_suffix(m, args.iw_train_samples) + guard_suffix(m) + spectral_suffix(m))
+                      + iw_suffix(m, args.iw_train_samples) + guard_suffix(m) + spectral_suffix(m)
+                      + balance_suffix(m, step, args.beta_anneal))
                 if history is not None:
                     history.write(step, 'train', m, steps=m['steps'], nonfinite_steps=m['nonfinite_steps'])
             t0, seen = time.time(), 0
@@ -315,8 +343,9 @@ def main(argv=None):
             if opt.guard is not None:
                 guard_seen = guard_metrics(opt.guard, opt.gscale, guard_seen, m, True)
             spectral_metrics(out, m)
+            balance_metrics(balance, m)
             print(exp.train_log_str(m, step) + lr_suffix(m) + '   [{:.0f} img/s]'.format(seen / dt) + iw_suffix(m, args.iw_train_samples)
-                  + guard_suffix(m) + spectral_suffix(m))
+                  + guard_suffix(m) + spectral_suffix(m) + balance_suffix(m, step, args.beta_anneal))
             if history is not None:
                 history.write(step, 'train', m)
             t0, seen = time.time(), 0

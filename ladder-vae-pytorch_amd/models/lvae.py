@@ -178,6 +178,11 @@ class LadderVAE(nn.Module):
         # accumulation, statistics, KL and likelihood (the arithmetic of the reference under torch.autocast(bfloat16)) for the
         # convolutions that have a bf16 kernel (lvae_conv2d_bf16); activations, parameters and gradients stay fp32 in HBM
         self.compute_dtype = 'f32'
+        # engine attribute, set after construction like compute_dtype: a balance.KlBalance (attached to this model and bound to a beta
+        # source) makes a TRAINING forward balance the per-layer terms of `kl_loss` while beta < 1 (NVAE's KL balancing); `kl_sep`,
+        # `kl_avg_layerwise` and `kl` stay the plain numbers. None, or eval mode: the plain bookkeeping, launch for launch. No parameter,
+        # no buffer: the state_dict does not know about it
+        self.kl_balance = None
         self.grad_tracker = None  # dist.GradAllReduce when gradients are exchanged while backward runs (engine.TrainStep sets it)
 
     @property
@@ -317,7 +322,12 @@ class LadderVAE(nn.Module):
             ll, likelihood_info = self.likelihood(out, x_nhwc, self.noise, mask=mask)
 
         kl_ln = ops.StackFn.apply(*td_data['kl'])  # (L, N)
-        kl_sep, kl_avg_layerwise, kl_loss, kl = ops.KLBookFn.apply(kl_ln, float(self.free_bits))
+        if self.kl_balance is not None and self.training:
+            # the same bookkeeping with the terms of kl_loss balanced over the layers while beta < 1; the other three keep their bits
+            kl_sep, kl_avg_layerwise, kl_loss, kl, coeff = ops.KlBalanceFn.apply(kl_ln, float(self.free_bits), self.kl_balance)
+            self.kl_balance.coeff = coeff.detach()
+        else:
+            kl_sep, kl_avg_layerwise, kl_loss, kl = ops.KLBookFn.apply(kl_ln, float(self.free_bits))
         self.noise.end()
 
         res = {

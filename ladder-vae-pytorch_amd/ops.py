@@ -862,6 +862,35 @@ class KLBookFn(Function):
         return K.kl_bookkeeping_bwd(kl_ln, ctx.fb, cc(g_sep), cc(g_avg), g_scal), None
 
 
+class KlBalanceFn(Function):
+    """KLBookFn with the terms of kl_loss balanced over the layers while beta < 1 (balance.KlBalance holds the fixed weights and the beta
+    source; csrc/kl_balance.hip): kl (L,N) -> kl_sep, kl_avg_layerwise, kl_loss (balanced), kl, coeff (L,). kl_sep, kl_avg_layerwise and kl
+    are KLBookFn's, bit for bit. coeff is a constant of the gradient: the backward reads what the forward wrote."""
+
+    @staticmethod
+    def forward(ctx, kl_ln, free_bits, balance):
+        ctx.fb = free_bits
+        ctx.set_materialize_grads(False)
+        kl_sep, kl_avg, scal, coeff = K.kl_balance_fwd(kl_ln, free_bits, balance.alpha, **balance.beta_source())
+        ctx.save_for_backward(kl_ln, coeff)
+        kl_loss, kl = scal[0], scal[1]
+        ctx.mark_non_differentiable(kl, coeff)
+        return kl_sep, kl_avg, kl_loss, kl, coeff
+
+    @staticmethod
+    def backward(ctx, g_sep, g_avg, g_kl_loss, g_kl, g_coeff):
+        kl_ln, coeff = ctx.saved_tensors
+        cc = lambda t: None if t is None else _c(t)
+        if g_sep is None and g_avg is None and g_kl_loss is None:
+            return None, None, None
+        g_scal = None
+        if g_kl_loss is not None:   # as in KLBookFn.backward
+            g_scal = torch.empty((2,), dtype=torch.float32, device=kl_ln.device)
+            K.scale_rows_add(cc(g_kl_loss).view(1, 1), None, None, out=g_scal[0:1])
+            K.fill_zero(g_scal[1:2])
+        return K.kl_balance_bwd(kl_ln, ctx.fb, coeff, cc(g_sep), cc(g_avg), g_scal), None, None
+
+
 class StackFn(Function):
     """stack L per-layer (N,) vectors into one (L,N) matrix; backward hands the rows back as views."""
 

@@ -126,6 +126,7 @@ class BnRecalibrator:
         bns = self.bns
         pending0, momentum0 = [bn._pending for bn in bns], [bn.momentum for bn in bns]
         was_training, old_noise = model.training, model.noise
+        balance, model.kl_balance = getattr(model, 'kl_balance', None), None   # (train-mode forwards, but no training: the plain bookkeeping)
         K.multi_copy(self._save)
         done = False
         keep = []
@@ -175,6 +176,7 @@ class BnRecalibrator:
                 bn._pending, bn.momentum = p0, m0
             model.noise = old_noise
             model.train(was_training)
+            model.kl_balance = balance
             if not done:
                 K.multi_copy(self._restore)
                 self.acc.zero_()
